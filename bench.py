@@ -8,7 +8,7 @@ One "step" = the whole set once.  Inputs are synthetic per-channel Laplace activ
 on the device (seed 12345), resident in HBM before the timed region; all inputs and outputs are
 distinct buffers, so nothing is re-read from a cache across layers.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Multi-GPU (inference_sim.py:196-200): ONE batch of 512 is sharded over the N ranks,
@@ -23,11 +23,18 @@ Per tensor the product entry point (ops.act_qdq_per_channel) picks a SINGLE laun
 and only for shapes neither supports (unaligned, odd H*W) the three-launch chain
 k_minmax (4 B read) -> k_minmax_params -> k_qdq (4 B read + 4 B write).
 
-Prints ONE JSON line (rank 0): `value` = elements/s of the whole job; `roofline` = the dominant
-kernel's algorithmic bytes / its measured launch time (HIP events on the launch stream) against
-the 8 TB/s HBM3E peak; `cpu_baseline` = the oracle (CPU restatement of the reference's op chain)
-timed on this host; `other_configs` = BASELINE configs 1, 3, 4, 5 timed the same way; `verified`
-= the outputs of the timed steps were checked after the timed region.
+Prints ONE JSON line (rank 0): `value` = elements/s of the whole job, `ms_per_step` = the time of one
+timed step.  A plain run does only what these need: set up, warm up, time K steps, write the outputs
+(--dump-outputs), print.  With --full the line also carries `roofline` = the dominant kernel's
+algorithmic bytes / its measured launch time (HIP events on the launch stream) against the 8 TB/s
+HBM3E peak; `cpu_baseline` = the oracle (CPU restatement of the reference's op chain) timed on this
+host; `other_configs` = BASELINE configs 1, 3, 4, 5 timed the same way; `sustained` = the step
+repeated for ~2 s more; `verified` = the outputs of the timed steps were checked after the timed region.
+
+--dump-outputs DIR: after the timed steps, the dequantized outputs of the last step as DIR/y_NN.npy
+(float32, one file per tensor in workload order; a tensor larger than DUMP_SAMPLE elements as a fixed,
+seeded sample of DUMP_SAMPLE of its elements, in increasing order of position).  The inputs are seeded,
+so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -54,6 +61,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 BYTES_QDQ = 8                  # fused Q/DQ pass, and the resident single launch: 4 B read + 4 B write per element
 BYTES_STATS = 4                # statistics pass: one read
 BYTES_PATH = 12                # dynamic min/max + Q/DQ as SURVEY.md 8(d3) accounts it
+DUMP_SAMPLE = 1 << 18          # --dump-outputs: elements kept per tensor (53 x 1 MiB of float32, inside a 64 MB budget)
+DUMP_SEED = 2019               # --dump-outputs: seed of the sampled positions (tensor i uses DUMP_SEED + i)
 
 
 def laplace_activation(shape, gen_seed, device):
@@ -86,6 +95,22 @@ def run_step(ops, layers, group):
     uses: IntQuantizer.gemmlowpQuantizeActivationPerChannel -> ops.act_qdq_per_channel)."""
     for L in layers:
         ops.act_qdq_per_channel(L['x'], 4, positive=L['half'], group=group, out=L['y'])
+
+
+def dump_outputs(layers, out_dir):
+    """--dump-outputs: what the last timed step returned to its caller, the dequantized y of every tensor, as
+    out_dir/y_NN.npy (float32, NN = the tensor's place in the workload).  A tensor of more than DUMP_SAMPLE elements is
+    written as DUMP_SAMPLE of its elements at positions drawn by a generator seeded with DUMP_SEED + NN and sorted, so
+    two runs with the same arguments write the same positions."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for i, L in enumerate(layers):
+        y = L['y'].reshape(-1)
+        if y.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(DUMP_SEED + i)
+            pos = torch.randint(y.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            y = y[pos.to(y.device)]
+        np.save(os.path.join(out_dir, 'y_%02d.npy' % i), y.cpu().numpy().astype(np.float32, copy=False))
 
 
 from bench_roofline import roofline_objects  # noqa: E402  (the `roofline` keys: live HIP-event timing per kernel class)
@@ -237,22 +262,31 @@ def main():
     ap.add_argument('--batch', type=int, default=512, help='GLOBAL batch of the forward (BASELINE config: 512)')
     ap.add_argument('--scaling', choices=('strong', 'weak'), default='strong',
                     help='strong: the one batch is sharded, batch/N per GPU (SURVEY 8 e1); weak: every GPU its own batch')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also verify their outputs, repeat the step for --sustained-secs, measure the '
+                         'per-kernel roofline, time the other BASELINE configs and the CPU baseline (off: the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/y_NN.npy (float32; a seeded sample of each large tensor)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-other-configs', action='store_true', help='--full: skip the other BASELINE configs')
     ap.add_argument('--graph', action='store_true',
                     help='replay the step from a HIP graph (also the sharded step, its exchange included: every rank captures '
                          'and replays the same launches)')
     ap.add_argument('--sustained-secs', type=float, default=2.0,
-                    help='after the timed K steps: keep stepping for about this long and report that rate too (0: skip)')
+                    help='--full: after the timed K steps keep stepping for about this long and report that rate too (0: skip)')
     ap.add_argument('--force-exchange', action='store_true',
                     help='single GPU: run the multi-GPU launch sequence with a 1-rank RCCL group (a self all_gather per '
                          'tensor) - measures what the collective costs on this box')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` started as a plain process: start the N ranks ourselves (one per GPU, the
-        # launcher the contract names); rank 0 of the children prints the one JSON line on the inherited stdout
+        # launcher the contract names) in a child process; rank 0 of the children prints the one JSON line on the
+        # inherited stdout, and this process exits with the launcher's status
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(('127.0.0.1', 0))
             port = sk.getsockname()[1]
@@ -260,7 +294,8 @@ def main():
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus),
                '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        rc = subprocess.call(cmd)
+        sys.exit(rc if rc >= 0 else 128 - rc)          # a launcher killed by a signal: the shell's 128 + signal
 
     # stdout carries exactly ONE line, the JSON: libraries that print to fd 1 (RCCL's version banner at communicator
     # creation, gloo's connection notes) are sent to stderr
@@ -406,9 +441,11 @@ def main():
         per_rank_ms = [float(v) for v in mine.tolist()]
         dt, total_elems = float(tmax[0].item()), int(t[1].item())
     ms_per_step = dt * 1e3 / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(layers, args.dump_outputs)
     # the same step for about two more seconds: the 20-step region of a fresh box flatters by 2-4 % (the part warms up)
     sustained = None
-    if args.sustained_secs > 0:
+    if args.full and args.sustained_secs > 0:
         ksus = max(args.steps, int(math.ceil(args.sustained_secs / (dt / args.steps))))
         dts, oks = region(0, ksus)
         if world > 1:
@@ -442,15 +479,16 @@ def main():
         from cnn_quantization_amd import rccl
         rccl_ranks = rccl.comm_ranks(group)          # what ncclCommCount says about the communicator actually used
 
-    verified = verify_outputs(ops, layers, group, world)
+    verified = None
+    if args.full:
+        verified = verify_outputs(ops, layers, group, world)
     group_status = ops.group_status(layers[0]['x'])      # 0: no bounded wait of the in-launch exchange expired
-    if world > 1:
+    if args.full and world > 1:
         v = torch.tensor([1 if verified else 0], device=device if backend == 'nccl' else 'cpu', dtype=torch.int32)
         dist.all_reduce(v, op=dist.ReduceOp.MIN)
         verified = bool(int(v.item()))
     single_route = (world == 1 and not args.force_exchange) or D.xrank_exchange(group) is not None
     bytes_moved = BYTES_QDQ if single_route else BYTES_PATH
-    dominant, objs = roofline_objects(layers, per_rank, world, single_launch=single_route)
     out = {
         'metric': 'activation elements/sec (and % HBM peak) for per-channel int4 Q/DQ, ResNet-50 b512',
         'value': value, 'unit': 'elements/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -463,7 +501,7 @@ def main():
                    'per_gpu_batch': per_rank, 'global_batch': args.batch * (world if args.scaling == 'weak' else 1),
                    'parallelism': 'batch-sharded dp%d, %s' % (world, 'per-channel extrema exchanged inside the launch' if (xrank_info or {}).get('used') else 'per-channel stats all_gather'),
                    'exchange': exchange_name, 'launch': launch_form},
-        'verified': verified, 'group_status': group_status, 'xrank': None, 'box': box_id(dev_index), 'sustained': sustained,
+        'full': args.full, 'group_status': group_status, 'xrank': None, 'box': box_id(dev_index),
         'path_gbs': value / world * bytes_moved / 1e9,
         'path_frac_hbm_peak': value / world * bytes_moved / 1e9 / HBM_PEAK_GBS,
         'path_bytes_moved_per_element': bytes_moved,
@@ -473,12 +511,15 @@ def main():
                      'read x twice): achieved bandwidth per GPU over the whole step, launch gaps included.  path_equiv_12B is SURVEY '
                      '8(d3)\'s accounting (statistics read + Q/DQ read + write), an equivalence kept for comparison with rounds 1-5, '
                      'where it was printed as path_frac_hbm_peak: it can exceed what a 12-byte path could reach',
-        'roofline': objs[dominant],
-        'roofline_other_kernels': {k: v for k, v in objs.items() if k != dominant},
     }
     out['xrank'] = xrank_info       # None: the collective from the start (1 GPU, ranks sharing a GPU, CNNQ_XRANK=0, not verified)
+    if args.full:
+        # what the headline does not need, each with runs of its own after the timed region
+        dominant, objs = roofline_objects(layers, per_rank, world, single_launch=single_route)
+        out.update(verified=verified, sustained=sustained, roofline=objs[dominant],
+                   roofline_other_kernels={k: v for k, v in objs.items() if k != dominant})
     shard = None
-    if (world > 1 or args.force_exchange) and not args.no_other_configs:
+    if args.full and (world > 1 or args.force_exchange) and not args.no_other_configs:
         # BASELINE configs 3 / 4 / 5 at the shard (round 6): collective - every rank takes part, rank 0 prints.  The legs run
         # through the exchange the headline ended on (in-launch: the ranks' sums meet inside the single launch; else the chain
         # around the collective) and recover like the product does (distributed.xrank_checkpoint per leg)
@@ -487,7 +528,7 @@ def main():
     if rank == 0:
         if shard is not None:
             out['other_configs'] = shard
-        if world == 1 and not args.force_exchange:
+        if args.full and world == 1 and not args.force_exchange:
             if not args.no_other_configs:
                 out['other_configs'] = other_configs(ops, device, args.batch)
             if not args.no_cpu_baseline:

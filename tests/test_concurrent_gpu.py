@@ -109,7 +109,7 @@ def test_two_processes_share_the_gpu(batch):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--batch', str(batch), '--steps', '6', '--warmup', '2', '--no-cpu-baseline',
-           '--no-other-configs']
+           '--no-other-configs', '--full']
     procs = [subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=root, env=env) for _ in range(2)]
     outs = [p.communicate(timeout=900) for p in procs]
     for i, (p, (so, se)) in enumerate(zip(procs, outs)):

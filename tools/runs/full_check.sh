@@ -3,7 +3,7 @@
 O=gpurun_out/full_check; mkdir -p $O
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -n 2 $O/smoke.log
 timeout 900 python -m pytest tests -m gpu -q -x > $O/pytest_all.log 2>&1; tail -n 4 $O/pytest_all.log
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err; tail -n 2 $O/bench_full.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err; tail -n 2 $O/bench_full.err
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/full_check/bench_full.json'))

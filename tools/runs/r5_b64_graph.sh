@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"; O=gpurun_out/r5; mkdir -p $O
 for v in "" "--graph" "--force-exchange" "--force-exchange --graph" "--force-exchange --xr" "--force-exchange --graph --xr"; do
   n=$(echo "b64$v" | tr -d ' ' | tr -s '-' '_')
   X=0; case "$v" in *--xr*) X=1; v=${v/ --xr/};; esac        # --xr: the in-launch exchange (CNNQ_XRANK=1) instead of the collective
-  CNNQ_XRANK=$X timeout 300 python bench.py --batch 64 --steps 40 --warmup 10 --no-cpu-baseline --no-other-configs $v > $O/r05_bench_line_$n.json 2> $O/$n.err
+  CNNQ_XRANK=$X timeout 300 python bench.py --full --batch 64 --steps 40 --warmup 10 --no-cpu-baseline --no-other-configs $v > $O/r05_bench_line_$n.json 2> $O/$n.err
   python -c "
 import json
 d=json.loads(open('$O/r05_bench_line_$n.json').read().strip().splitlines()[-1])

@@ -4,16 +4,16 @@
 # statistics + PMC traffic of the single-launch forms of configs 3 / 4 / 5.  Everything lands in gpurun_out/r5_profile/.
 O=$PWD/gpurun_out/r5_profile; rm -rf $O; mkdir -p $O
 R=$PWD
-timeout 900 python bench.py > $O/r05_bench_line_b512.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/r05_bench_line_b512.json 2> $O/bench.err
 B=$(python -c "import json; print(json.load(open('$O/r05_bench_line_b512.json'))['box'])")
 echo $B > $O/box.txt
 cd /tmp && export TMPDIR=/tmp
 for BT in 512 64; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_b$BT -o kt -- python $R/bench.py --batch $BT --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs > $O/r05_bench_line_b${BT}_under_rocprof.json 2> $O/kt_b$BT.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_b$BT -o kt -- python $R/bench.py --full --batch $BT --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs > $O/r05_bench_line_b${BT}_under_rocprof.json 2> $O/kt_b$BT.err
   f=$(find $O/kt_b$BT -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/r05_bench_b${BT}_kernel_stats.csv
 done
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -o pmc -- python $R/bench.py --batch 512 --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs > $O/pmc_$c.json 2> $O/pmc_$c.err
+  timeout 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -o pmc -- python $R/bench.py --full --batch 512 --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs > $O/pmc_$c.json 2> $O/pmc_$c.err
 done
 # configs 3 / 5 / 4 through their single launches
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c3 -o kt -- python $R/tools/bench_aciq.py --only single > $O/c3.log 2> $O/c3.err

@@ -4,16 +4,16 @@
 # statistics + PMC traffic of the single-launch forms of configs 3 / 4 / 5.  Everything lands in gpurun_out/r6_profile/.
 O=$PWD/gpurun_out/r6_profile; rm -rf $O; mkdir -p $O
 R=$PWD
-timeout 900 python bench.py > $O/r06_bench_line_b512.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/r06_bench_line_b512.json 2> $O/bench.err
 B=$(python -c "import json; print(json.load(open('$O/r06_bench_line_b512.json'))['box'])")
 echo $B > $O/box.txt
 cd /tmp && export TMPDIR=/tmp
 for BT in 512 64; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_b$BT -o kt -- python $R/bench.py --batch $BT --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs > $O/r06_bench_line_b${BT}_under_rocprof.json 2> $O/kt_b$BT.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_b$BT -o kt -- python $R/bench.py --full --batch $BT --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs > $O/r06_bench_line_b${BT}_under_rocprof.json 2> $O/kt_b$BT.err
   f=$(find $O/kt_b$BT -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/r06_bench_b${BT}_kernel_stats.csv
 done
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -o pmc -- python $R/bench.py --batch 512 --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --sustained-secs 0 > $O/pmc_$c.json 2> $O/pmc_$c.err
+  timeout 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -o pmc -- python $R/bench.py --full --batch 512 --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --sustained-secs 0 > $O/pmc_$c.json 2> $O/pmc_$c.err
 done
 # configs 3 / 5 / 4 through their single launches
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c3 -o kt -- python $R/tools/bench_aciq.py --only single > $O/c3.log 2> $O/c3.err
@@ -36,9 +36,9 @@ cp $O/c3/r06_pmc_traffic.json $O/r06_pmc_traffic_config3.json; cp $O/c3/r06_rocp
 cp $O/c4/r06_pmc_traffic.json $O/r06_pmc_traffic_config4.json; cp $O/c4/r06_rocprof_headline.json $O/r06_rocprof_config4.json
 # the 64-sample shard: configs 2 - 5 through the forced 1-rank exchange (in-launch, collective) and without exchange
 for x in 1 0; do
-  CNNQ_XRANK=$x timeout 300 python bench.py --batch 64 --force-exchange --no-cpu-baseline --steps 40 --warmup 5 > $O/r06_bench_line_b64_force_exchange_xr$x.json 2> $O/b64_xr$x.err
+  CNNQ_XRANK=$x timeout 300 python bench.py --full --batch 64 --force-exchange --no-cpu-baseline --steps 40 --warmup 5 > $O/r06_bench_line_b64_force_exchange_xr$x.json 2> $O/b64_xr$x.err
 done
-timeout 300 python bench.py --batch 64 --no-cpu-baseline --steps 40 --warmup 5 > $O/r06_bench_line_b64.json 2> $O/b64.err
+timeout 300 python bench.py --full --batch 64 --no-cpu-baseline --steps 40 --warmup 5 > $O/r06_bench_line_b64.json 2> $O/b64.err
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete; find $O -name "*agent_info.csv" -delete
 for c in 3 4 5; do echo "== config $c"; tail -n 2 $O/c$c.log; python tools/kstats.py $O/r06_config${c}_kernel_stats.csv | head -12; done
 python tools/kstats.py $O/r06_bench_b512_kernel_stats.csv | head; cat $O/r06_rocprof_headline.json; cat $O/r06_pmc_traffic.json; cat $O/r06_pmc_traffic_config3.json $O/r06_pmc_traffic_config4.json
