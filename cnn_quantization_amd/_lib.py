@@ -25,6 +25,7 @@ def mt_hist_words(C):
     return MT_HIST_BINS + 2 + 2 * C + MT_HIST_REPLICAS * MT_HIST_WINDOW + 1
 KLD_BINS, KLD_QBINS, KLD_NCAND = 2001, 15, 994
 DIAG_BITS, DIAG_ALPHA, DIAG_DELTA, DIAG_OFFSET, NDIAG = 0, 1, 2, 3, 4
+DTYPE_F32, DTYPE_BF16, DTYPE_F16, NDTYPE = 0, 1, 2, 3
 
 
 class ParamsCfg(ctypes.Structure):
@@ -131,6 +132,11 @@ SIGNATURES = {
     'cnnq_xrank_free': (_I, [_P]),
     'cnnq_kld_hist': (_I, [_P, _L, _L, _P, _P, _P]),
     'cnnq_kld_search': (_I, [_P, _L, _P, _P, _P, _P]),
+    'cnnq_pc_route_dt': (_I, [_L, _L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_pc_minmax_qdq_auto_dt': (_I, [_P, _P, _I, _L, _L, _L, _I, _I, _P, _P, ctypes.c_size_t, _I, _P]),
+    'cnnq_pc_qdq_dt': (_I, [_P, _P, _I, _L, _L, _L, _P, _P, _P, _I, _P]),
+    'cnnq_pc_minmax_local_dt': (_I, [_P, _I, _L, _L, _L, _P, _P, _P]),
+    'cnnq_pt_qdq_dt': (_I, [_P, _P, _I, _L, _P, _P, _P]),
 }
 
 _lib = None

@@ -44,6 +44,7 @@
 #include "cnnq_group.hip.h"
 #include "cnnq_plan.hip.h"
 #include "cnnq_kld.hip.h"
+#include "cnnq_half.hip.h"
 
 extern "C" {
 
@@ -1508,5 +1509,157 @@ int cnnq_xrank_open(const unsigned char handle[64], void** window) {
 }
 int cnnq_xrank_close(void* window) { return window ? (int)hipIpcCloseMemHandle(window) : CNNQ_EINVAL; }
 int cnnq_xrank_free(void* window) { return window ? (int)hipFree(window) : CNNQ_EINVAL; }
+
+// ---- activations of another element type (cnnq_half.hip.h): bf16 / fp16 x and y, fp32 tables ---------------------------------
+static bool dtype_ok(int dtype) { return dtype >= 0 && dtype < CNNQ_NDTYPE; }
+
+// the common alignment of x and y in bytes (16 at most): what h_piece needs to know of the pointers
+static int h_align(const void* x, const void* y) {
+    const uintptr_t a = (uintptr_t)x | (uintptr_t)y | 16u;
+    return (int)(a & (~a + 1));
+}
+
+// config 2's route for a bf16 / fp16 tensor: out = {1: the single launch k_h_whole / 2: the chain, piece width W, pieces per lane K
+// (0 for the chain), workgroups of the Q/DQ launch}
+static int h_route(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_single_launch, int32_t out[4]) {
+    const int rc = cnnq_pc_groups(N, C, HW, 0);       // the fp32 entry points' geometry limits
+    if (rc <= 0) return rc ? rc : CNNQ_EINVAL;
+    const int w = h_piece(HW, (uintptr_t)align_bytes, 0);
+    const bool whole = allow_single_launch && N * HW <= h_whole_cap(w);
+    out[0] = whole ? 1 : 2;
+    out[1] = w;
+    out[2] = whole ? h_whole_k_rt(w) : 0;
+    out[3] = whole ? (int32_t)C : (int32_t)(C * h_splits(N, C, HW, H_QDQ_ELEMS, N));
+    return 0;
+}
+
+// the statistics half of the chain: per-split extrema into pmm[S][2][C], S <= the fp32 plan's G (the callers' workspace rule)
+static int h_minmax(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, float* pmm, int* S, hipStream_t st) {
+    const int g1 = cnnq_pc_groups(N, C, HW, 1), g0 = cnnq_pc_groups(N, C, HW, 0);
+    const int G = g1 > g0 ? g1 : g0;
+    if (G <= 0) return G ? G : CNNQ_EINVAL;
+    HGeo g;
+    g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
+    const int w = h_piece(HW, (uintptr_t)x, 0);
+    g.ppr = (int)(HW / w);
+    // ~H_MM_ELEMS per workgroup: batch splits first, then (short batches: config 1's rows, N = 1) column splits of the rows
+    const int total = h_splits(N * HW, C, 1, H_MM_ELEMS, G);
+    g.S = total < N ? total : (int)N;
+    g.cs = total / g.S < g.ppr ? total / g.S : g.ppr;
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+#define LAUNCH_HMM(T, W) hipLaunchKernelGGL((k_h_minmax<T, W>), dim3((unsigned)(C * g.S * g.cs)), dim3(TPB), 0, st, xh, g, pmm)
+    CNNQ_H_DISPATCH(dtype, w, LAUNCH_HMM);
+#undef LAUNCH_HMM
+    *S = g.S * g.cs;
+    return launch_status();
+}
+
+// pmm == NULL: the parameters from the table qp; else from the statistics partials pmm (published to ha.qp / ha.mm, k_h_qdq)
+static int h_qdq(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, const float* pmm, const HArgs& ha,
+                 hipStream_t st) {
+    const int rc = cnnq_pc_groups(N, C, HW, 0);    // the fp32 entry points' geometry limits
+    if (rc <= 0) return rc ? rc : CNNQ_EINVAL;
+    HGeo g;
+    g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
+    g.S = h_splits(N, C, HW, H_QDQ_ELEMS, N);
+    g.cs = 1;
+    const int w = h_piece(HW, (uintptr_t)x, (uintptr_t)y);
+    g.ppr = (int)(HW / w);
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+    uint16_t* yh = static_cast<uint16_t*>(y);
+#define LAUNCH_HQ(T, W) hipLaunchKernelGGL((k_h_qdq<T, W>), dim3((unsigned)(C * g.S)), dim3(TPB), 0, st, xh, yh, g, qp, pmm, ha)
+    CNNQ_H_DISPATCH(dtype, w, LAUNCH_HQ);
+#undef LAUNCH_HQ
+    return launch_status();
+}
+
+int cnnq_pc_route_dt(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_single_launch, int32_t out[4]) {
+    if (!out || align_bytes <= 0 || (align_bytes & (align_bytes - 1))) return CNNQ_EINVAL;
+    return h_route(N, C, HW, align_bytes, allow_single_launch, out);
+}
+
+int cnnq_pc_minmax_qdq_auto_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, int num_bits,
+                               int positive, float* ws, void* gws, size_t gws_bytes, int allow_single_launch, void* stream) {
+    if (!dtype_ok(dtype)) return CNNQ_EINVAL;
+    if (dtype == CNNQ_DTYPE_F32)
+        return cnnq_pc_minmax_qdq_auto(static_cast<const float*>(x), static_cast<float*>(y), N, C, HW, num_bits, positive, ws,
+                                       gws, gws_bytes, allow_single_launch, stream);
+    if (!x || !y || !ws || num_bits < 1 || num_bits > 32 || N <= 0 || C <= 0 || HW <= 0) return CNNQ_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    float* qp = ws;                                    // the layout of cnnq_pc_minmax_qdq_auto's workspace
+    float* mm = ws + (size_t)CNNQ_NQP * C;
+    float* pmm = mm + 2 * (size_t)C;
+    int32_t route[4];
+    int rc = h_route(N, C, HW, h_align(x, y), allow_single_launch, route);
+    if (rc) return rc;
+    if (route[0] == 1) {
+        HGeo g;
+        g.N = (int)N; g.C = (int)C; g.HW = (int)HW; g.S = 1; g.cs = 1;
+        g.ppr = (int)(HW / route[1]);
+        const HArgs ha{0, num_bits, positive ? 1 : 0, qp, mm};
+        const uint16_t* xh = static_cast<const uint16_t*>(x);
+        uint16_t* yh = static_cast<uint16_t*>(y);
+#define LAUNCH_HW(T, W) \
+    hipLaunchKernelGGL((k_h_whole<T, W, h_whole_k<W>()>), dim3((unsigned)C), dim3(HTPB), 0, st, xh, yh, g, ha)
+        if (dtype == CNNQ_DTYPE_BF16) {
+            if (route[1] == 8) LAUNCH_HW(HBf16, 8); else if (route[1] == 4) LAUNCH_HW(HBf16, 4); else LAUNCH_HW(HBf16, 2);
+        } else {
+            if (route[1] == 8) LAUNCH_HW(HF16, 8); else if (route[1] == 4) LAUNCH_HW(HF16, 4); else LAUNCH_HW(HF16, 2);
+        }
+#undef LAUNCH_HW
+        return launch_status();
+    }
+    int S = 0;
+    rc = h_minmax(x, dtype, N, C, HW, pmm, &S, st);
+    if (rc) return rc;
+    return h_qdq(x, y, dtype, N, C, HW, qp, pmm, HArgs{S, num_bits, positive ? 1 : 0, qp, mm}, st);
+}
+
+int cnnq_pc_qdq_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, uint8_t* codes,
+                   uint64_t* hist, int reverse, void* stream) {
+    if (!dtype_ok(dtype)) return CNNQ_EINVAL;
+    if (dtype == CNNQ_DTYPE_F32)
+        return cnnq_pc_qdq(static_cast<const float*>(x), static_cast<float*>(y), N, C, HW, qp, codes, hist, reverse, stream);
+    if (!x || !y || !qp || N <= 0 || C <= 0 || HW <= 0) return CNNQ_EINVAL;
+    if (codes || hist) return CNNQ_ENOTSUP;
+    return h_qdq(x, y, dtype, N, C, HW, qp, nullptr, HArgs{}, (hipStream_t)stream);
+}
+
+int cnnq_pc_minmax_local_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, float* pmm, float* local,
+                            void* stream) {
+    if (!dtype_ok(dtype)) return CNNQ_EINVAL;
+    if (dtype == CNNQ_DTYPE_F32) return cnnq_pc_minmax_local(static_cast<const float*>(x), N, C, HW, pmm, local, stream);
+    if (!x || !pmm || !local || N <= 0 || C <= 0 || HW <= 0) return CNNQ_EINVAL;
+    int S = 0;
+    const int rc = h_minmax(x, dtype, N, C, HW, pmm, &S, (hipStream_t)stream);
+    if (rc) return rc;
+    return cnnq_pc_minmax_reduce(pmm, S, C, local, stream);
+}
+
+int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream) {
+    if (!dtype_ok(dtype)) return CNNQ_EINVAL;
+    if (dtype == CNNQ_DTYPE_F32) return cnnq_pt_qdq(static_cast<const float*>(x), static_cast<float*>(y), n, ptp, noise, stream);
+    if (!x || !y || !ptp || n <= 0) return CNNQ_EINVAL;
+    const bool vec = al16(x) && al16(y) && (!noise || al16(noise));
+    const int64_t work = vec ? (n + 7) / 8 : n;
+    const int64_t blocks = (work + TPB - 1) / TPB;
+    if (blocks >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    const dim3 grid((unsigned)blocks), block(TPB);
+    hipStream_t st = (hipStream_t)stream;
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+    uint16_t* yh = static_cast<uint16_t*>(y);
+#define LAUNCH_HPT(T, W)                                                                                              \
+    do {                                                                                                              \
+        if (noise) hipLaunchKernelGGL((k_h_pt_qdq<T, W, true>), grid, block, 0, st, xh, yh, n, ptp, noise);           \
+        else hipLaunchKernelGGL((k_h_pt_qdq<T, W, false>), grid, block, 0, st, xh, yh, n, ptp, noise);                \
+    } while (0)
+    if (dtype == CNNQ_DTYPE_BF16) {
+        if (vec) LAUNCH_HPT(HBf16, 8); else LAUNCH_HPT(HBf16, 1);
+    } else {
+        if (vec) LAUNCH_HPT(HF16, 8); else LAUNCH_HPT(HF16, 1);
+    }
+#undef LAUNCH_HPT
+    return launch_status();
+}
 
 }  // extern "C"

@@ -72,6 +72,9 @@ def build_parser():
     p.add_argument('--rho_act', '-ra', default=None, type=float)
     p.add_argument('--rho_weight', '-rw', default=None, type=float)
     p.add_argument('--no-bn-folding', action='store_true')
+    p.add_argument('--dtype', default='float32', choices=('float32', 'bfloat16', 'float16'),
+                   help='element type of the model and its activations; BN folding and the synthetic input are computed in '
+                        'float32 and then cast (configs 1 and 2 quantize bf16 / fp16 natively, every other path upcasts)')
     p.add_argument('--verbose', action='store_true')
     p.add_argument('--sharded', action='store_true',
                    help='one process per GPU (start under torchrun / torch.distributed.run): every rank takes its shard of each '
@@ -179,6 +182,9 @@ def run(args, quiet=False):
         if not args.no_bn_folding and args.qtype is not None:   # folded BN layers are skipped by the patched class only
             model_prep.absorb_bn(model)
             qm.bn_folding = True
+        dtype = getattr(torch, getattr(args, 'dtype', 'float32'))
+        if dtype != torch.float32:
+            model = model.to(dtype)
         qm.quantize_model(model)                     # weights (verbose=True inside, like the reference)
         timer = QuantTimer(qm)
         qm.verbose = args.verbose
@@ -187,6 +193,8 @@ def run(args, quiet=False):
         with torch.no_grad():
             for _ in range(args.batches + 1):        # first batch is warm-up (MIOpen find, allocator)
                 x = torch.randn(args.batch_size, 3, args.image_size, args.image_size, generator=g, device=dev)
+                if dtype != torch.float32:
+                    x = x.to(dtype)
                 if sharded:                          # the same batch on every rank (same seed); this rank's samples of it
                     n0, n1 = D.shard_batch(args.batch_size, D.rank(qm.group), D.world_size(qm.group))
                     x = x[n0:n1].contiguous()

@@ -32,6 +32,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..qtypes import DummyQuantizer, int_quantizer
+from ..qtypes.int_quantizer import upcast_fallback
 from ..utils.misc import Singleton
 from .statistic_manager import StatisticManager
 from .statistic_manager_perchannel import StatisticManagerPerChannel
@@ -58,7 +59,7 @@ class MeasureStatistics:
         self.stats_names = ['dist']
 
     def save_measure(self, tensor, id):
-        d = ops.row_sumsq(tensor.detach().contiguous(), tensor.shape[0]).cpu().numpy().astype(np.float64)
+        d = upcast_fallback(ops.row_sumsq, tensor.detach().contiguous(), tensor.shape[0], cast_back=False).cpu().numpy().astype(np.float64)
         self.stats[id] = np.concatenate([self.stats[id], d]) if id in self.stats else d
 
     def __enter__(self):
@@ -90,7 +91,7 @@ def _route(layer, out, out_id, tag, *, shifted=False, half_range=False, collect_
         return out
     if qm.stats_mode is StatsMode.collect_stats:
         kw = dict(force_global_min_max=True) if force_global else {}
-        qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, **kw)
+        upcast_fallback(qm.stats_manager.save_tensor_stats, out, tag if collect_tag is None else collect_tag, out_id, **kw)
         return out
     stat_id = out_id if qm.stats_mode is StatsMode.use_stats else None
     if shifted:
@@ -169,7 +170,7 @@ class Conv2dWithId(nn.Conv2d):
             if correct and not qm.op_manager.last_bcorr_fused:
                 # iqm.py:180-196: shift the positive outputs so the channel sums match the fp32 ones (the
                 # per-channel quantizers fold this into their own passes, see IntQuantizer.fuse_bcorr)
-                out = ops.act_bias_correction_(raw, out.contiguous(), relu_first, group=qm.group)
+                out = upcast_fallback(ops.act_bias_correction_, raw, out.contiguous(), relu_first, group=qm.group)
         if qm.measure_stats.enabled:
             qm.measure_stats.save_measure(out, act_id)
         return out
@@ -407,8 +408,8 @@ class QuantizationManagerInference(metaclass=Singleton):
             else:
                 continue
             if self.vcorr_weight or self.bcorr_weight:
-                weight_q = ops.weight_correction(m.weight.data, weight_q, vcorr=self.vcorr_weight,
-                                                 bcorr=self.bcorr_weight)
+                weight_q = upcast_fallback(ops.weight_correction, m.weight.data, weight_q, vcorr=self.vcorr_weight,
+                                             bcorr=self.bcorr_weight)
             m.weight.data = weight_q
 
 

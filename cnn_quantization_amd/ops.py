@@ -26,11 +26,11 @@ def _stream(t):
     return ctypes.c_void_p(_raw_stream(t.device.index))
 
 
-def _dev_f32(x, what='tensor'):
+def _dev_f32(x, what='tensor', dtypes=(torch.float32,)):
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise L.CnnqError('%s must be a CUDA/HIP tensor (there is no CPU path)' % what)
-    if x.dtype != torch.float32:
-        raise L.CnnqError('%s must be float32, got %s' % (what, x.dtype))
+    if x.dtype not in dtypes:
+        raise L.CnnqError('%s must be %s, got %s' % (what, ' or '.join(str(d).replace('torch.', '') for d in dtypes), x.dtype))
     if x.device.index != torch.cuda.current_device():
         # kernels are enqueued in the calling thread's current device context (one process per GPU is the
         # deployment model; in-process multi-GPU callers must enter torch.cuda.device(x.device) first)
@@ -38,6 +38,21 @@ def _dev_f32(x, what='tensor'):
     if x.requires_grad:
         x = x.detach()
     return x if x.is_contiguous() else x.contiguous()
+
+
+# activations of another element type (include/cnnq_hip.h, cnnq_dtype): the entry points of configs 1 and 2 that take them
+_HALF_DTYPES = {torch.bfloat16: L.DTYPE_BF16, torch.float16: L.DTYPE_F16}
+_ACT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _dev_act(x, what='tensor'):
+    """_dev_f32 for the activation paths that have bf16 / fp16 kernels."""
+    return _dev_f32(x, what, _ACT_DTYPES)
+
+
+def _half_only(what, reason):
+    """The error of a half-precision call that has no native kernel: the caller upcasts (qtypes/int_quantizer.py)."""
+    raise L.CnnqError('%s: no bfloat16 / float16 kernel for %s (compute on x.float())' % (what, reason))
 
 
 # switches, read ONCE at import (the hot call used to look three of them up per tensor: weak #10 of the round-2
@@ -102,10 +117,11 @@ def _out_like(x, out):
     """The result buffer: a new tensor like x, or the caller's - which must match x exactly."""
     if out is None:
         return torch.empty_like(x)
-    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == x.dtype and out.is_contiguous()
             and out.shape == x.shape and out.device == x.device):
-        raise L.CnnqError('out must be a contiguous float32 tensor on %s shaped like the input' % (x.device,))
-    nbytes = x.numel() * 4
+        raise L.CnnqError('out must be a contiguous %s tensor on %s shaped like the input'
+                          % (str(x.dtype).replace('torch.', ''), x.device))
+    nbytes = x.numel() * x.element_size()
     if out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + nbytes:
         # the kernels declare x and y __restrict__, and a single-launch workgroup whose bounded wait expires recomputes
         # its channels' extrema by re-reading x after other members may have stored y (include/cnnq_hip.h: x != y).
@@ -454,7 +470,14 @@ def pc_qdq(x, N, C, HW, qp, want_codes=False, out=None, hist=None, reverse=False
     """y = dequant(quant(x)) with per-channel parameters; optionally the uint8 codes; `hist`
     (optional zeroed int64[256] tensor) receives the code histogram; reverse: descending addresses."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev_act(x, 'x')
+    if x.dtype != torch.float32:
+        if want_codes or hist is not None:
+            _half_only('pc_qdq', 'codes / the code histogram')
+        y = _out_like(x, out)
+        L.check(lib.cnnq_pc_qdq_dt(_ptr(x), _ptr(y), _HALF_DTYPES[x.dtype], N, C, HW, _ptr(qp), None, None, 0, _stream(x)),
+                'cnnq_pc_qdq_dt')
+        return y
     y = _out_like(x, out)
     codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_codes else None
     L.check(lib.cnnq_pc_qdq(_ptr(x), _ptr(y), N, C, HW, _ptr(qp), _ptr(codes), _ptr(hist), int(bool(reverse)),
@@ -817,7 +840,9 @@ def minmax_qdq_fused(x, N, C, HW, num_bits, positive=False, want_codes=False, wa
     single-launch kernels are tested against.  _xrank: an XRankExchange to use (its verify()), False: never.  group=False:
     replicated data, the one-GPU route."""
     if not _checked:
-        x = _dev_f32(x, 'x')
+        x = _dev_act(x, 'x')
+    if x.dtype != torch.float32:
+        return _minmax_qdq_half(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group)
     # group=False: replicated data (weights) - never exchanged, whatever process group the job runs in.  (Until round 6 this
     # arrived here as None = the default group: every rank's identical weights went through the exchange - the same bits, one
     # needless collective per layer, and a wait that expired there left NaN WEIGHTS behind, outside any forward a checkpoint redoes.)
@@ -830,6 +855,26 @@ def minmax_qdq_fused(x, N, C, HW, num_bits, positive=False, want_codes=False, wa
         if res is not None:
             return res
     return _minmax_qdq_collective(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group, world, resident)
+
+
+def _minmax_qdq_half(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group):
+    """Config 2 on a bf16 / fp16 tensor on one GPU (cnnq_pc_minmax_qdq_auto_dt: one launch when a channel fits a workgroup,
+    else exact extrema of the 2-byte elements then the Q/DQ; the result rounded back into the input type).  Codes, entropy, the parts and the sharded
+    exchange have no half kernels: the quantizer computes those on x.float()."""
+    if want_codes or want_entropy or want_parts:
+        _half_only('minmax_qdq_fused', 'codes / entropy / parts')
+    if group is not False and (D.world_size(group) > 1 or D.forced_exchange()):
+        _half_only('minmax_qdq_fused', 'the sharded exchange')
+    lib = L.load()
+    nbytes = _cfg2_workspace_bytes(lib, N, C, HW)
+    y = _out_like(x, out)
+    st = _raw_stream(x.device.index)
+    rc = lib.cnnq_pc_minmax_qdq_auto_dt(x.data_ptr(), y.data_ptr(), _HALF_DTYPES[x.dtype], N, C, HW, int(num_bits),
+                                        1 if positive else 0, _scratch(x, 'cfg2', nbytes, st).data_ptr(), None, 0,
+                                        1 if _RESIDENT else 0, st)
+    if rc:
+        L.check(rc, 'cnnq_pc_minmax_qdq_auto_dt')
+    return y
 
 
 def _minmax_qdq_local(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, chain):
@@ -1185,11 +1230,15 @@ def pt_setup(device, num_bits, range_offset=None, stats=None, rows=0, rows_mode=
 
 def pt_qdq(x, ptp, noise=None, out=None):
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev_act(x, 'x')
     y = _out_like(x, out)
     if noise is not None:
         noise = _dev_f32(noise, 'noise')
     if x.numel() == 0:
+        return y
+    if x.dtype != torch.float32:
+        L.check(lib.cnnq_pt_qdq_dt(_ptr(x), _ptr(y), _HALF_DTYPES[x.dtype], x.numel(), _ptr(ptp), _ptr(noise), _stream(x)),
+                'cnnq_pt_qdq_dt')
         return y
     L.check(lib.cnnq_pt_qdq(_ptr(x), _ptr(y), x.numel(), _ptr(ptp), _ptr(noise), _stream(x)), 'cnnq_pt_qdq')
     return y
@@ -1208,9 +1257,18 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
     bcorr (None, or the relu-first flag): also apply the activation bias correction of iqm.py:180-196,
     fused into the passes where the parameter table is at hand (qdq_bias_corrected).
     Returns y [, codes] [, entropy (0-dim device tensor)] [, parts].  No host synchronisation."""
-    x = _dev_f32(x, 'x')
+    x = _dev_act(x, 'x')
     N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x, per_channel_dim)
     use_ba = bool(bit_alloc) and num_bits <= 4 and not whole_tensor
+    if x.dtype != torch.float32:
+        # bf16 / fp16: config 2, dynamic or from a statistics table - min/max parameters, no clipping, no bit allocation
+        if (clip != 'no' or use_ba or whole_tensor or per_channel_dim != 1 or bcorr is not None or want_codes or want_entropy
+                or want_parts):
+            _half_only('act_qdq_per_channel', 'clipping / bit allocation / whole-tensor / weights / bias correction / codes')
+        if stats is None:
+            return minmax_qdq_fused(x, N, C, HW, num_bits, positive, out=out, group=group, _checked=True)
+        qp, _ = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, direct_range=whole_tensor)
+        return pc_qdq(x, N, C, HW, qp, out=out)
     world = 1 if group is False else D.world_size(group)
     if bcorr is not None and (want_codes or want_entropy or want_parts or whole_tensor or per_channel_dim != 1):
         raise L.CnnqError('bcorr combines only with the plain per-channel activation Q/DQ')
@@ -1451,8 +1509,17 @@ def tensor_row_stats(x, rows):
     """Per-row MIN/MAX (and friends) of x viewed as [rows, numel/rows]: the per-sample statistics
     of iq.py:510-517 (rows = batch) - the per-channel kernels with N = 1, C = rows."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev_act(x, 'x')
     hw = x.numel() // rows
+    if x.dtype != torch.float32:
+        G = max(lib.cnnq_pc_groups(1, rows, hw, 1), lib.cnnq_pc_groups(1, rows, hw, 0))
+        if G <= 0:
+            L.check(G, 'cnnq_pc_groups(1,%d,%d)' % (rows, hw))
+        pmm = torch.empty((G, 2, rows), dtype=torch.float32, device=x.device)
+        table = torch.empty((2, rows), dtype=torch.float32, device=x.device)
+        L.check(lib.cnnq_pc_minmax_local_dt(_ptr(x), _HALF_DTYPES[x.dtype], 1, rows, hw, _ptr(pmm), _ptr(table), _stream(x)),
+                'cnnq_pc_minmax_local_dt')
+        return table
     G = lib.cnnq_pc_groups(1, rows, hw, int(x.data_ptr() % 16 == 0))
     if G <= 0:
         L.check(G, 'cnnq_pc_groups(1,%d,%d)' % (rows, hw))
@@ -1472,9 +1539,9 @@ def minmax_qdq_per_tensor(x, num_bits, avg_over_batch, zero_min=False, int_exp=F
     bits, but measured SLOWER than the chain - 70 against 54 us on the [32,64,112,112] tensor of BASELINE config 1: its
     second sweep is not served by the Infinity Cache once 103 MB of y are written next to it - so
     it is opt-in."""
-    x = _dev_f32(x, 'x')
+    x = _dev_act(x, 'x')
     rows = x.shape[0] if x.dim() > 1 else 1
-    if (_PT_FUSED if fused is None else fused) and D.world_size(group) == 1 and x.numel() > 0:
+    if (_PT_FUSED if fused is None else fused) and D.world_size(group) == 1 and x.numel() > 0 and x.dtype == torch.float32:
         # one launch (k_pt_fused): two sweeps with a tile count in between, the second served by the Infinity Cache
         st = _raw_stream(x.device.index)
         gws = _group_workspace(x, st)

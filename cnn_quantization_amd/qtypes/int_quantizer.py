@@ -13,7 +13,29 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from .. import distributed as D
 from .. import ops
+
+# bf16 / fp16 activations.  Configs 1 and 2 (per-tensor and per-channel min/max, dynamic or from a statistics file) run on
+# their half-precision kernels.  Every other path that meets a half tensor goes through upcast_fallback, the ONE place that
+# upcasts: it computes on x.float() and returns .to(x.dtype), and counts the call (HALF_FALLBACKS) so that tests can prove
+# configs 1 and 2 never arrive there.
+HALF_DTYPES = (torch.bfloat16, torch.float16)
+HALF_FALLBACKS = 0
+
+
+def upcast_fallback(fn, *args, cast_back=True, **kw):
+    """fn(*args, **kw) with every bf16 / fp16 tensor argument upcast to float32; a tensor result is cast back to the dtype
+    of the first half argument (cast_back=False: returned as computed).  Without a half argument: fn(*args, **kw), uncounted."""
+    global HALF_FALLBACKS
+    dt = next((a.dtype for a in args if isinstance(a, torch.Tensor) and a.dtype in HALF_DTYPES), None)
+    if dt is None:
+        return fn(*args, **kw)
+    HALF_FALLBACKS += 1
+    res = fn(*[a.float() if isinstance(a, torch.Tensor) and a.dtype in HALF_DTYPES else a for a in args], **kw)
+    if cast_back and isinstance(res, torch.Tensor) and res.is_floating_point():
+        return res.to(dt)
+    return res
 
 
 def _is_pc_act(t):
@@ -72,6 +94,8 @@ class IntQuantizer:
 
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
+        if isinstance(tensor, torch.Tensor) and tensor.dtype in HALF_DTYPES and not self._half_native(tensor, override_att):
+            return upcast_fallback(self.__call__, tensor, id, tag, stat_id, override_att)
         if override_att is not None:
             orig_att = getattr(self, override_att[0])
             setattr(self, override_att[0], override_att[1])
@@ -99,6 +123,19 @@ class IntQuantizer:
             if override_att is not None:
                 setattr(self, override_att[0], orig_att)
         return res
+
+    def _half_native(self, tensor, override_att=None):
+        """Whether a bf16 / fp16 tensor takes a path with half kernels: config 2 (gemmlowpQuantizeActivationPerChannel without
+        clipping, bit allocation, entropy, a bias correction to fold in or a sharded batch) or config 1 (gemmlowpMinMaxQuantize)."""
+        def att(k):
+            return override_att[1] if override_att is not None and override_att[0] == k else getattr(self, k)
+        if att('kld') or att('clipping') != 'no' or att('pcq_w'):
+            return False
+        if att('pcq_a') and _is_pc_act(tensor):
+            return (not att('mtd_quant') and not att('measure_entropy') and self.fuse_bcorr is None
+                    and not (att('bit_alloc_act') and att('num_bits') <= 4)
+                    and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+        return True
 
     def __repr__(self):
         # iq.py:124-126, printed by the manager in verbose mode
@@ -326,4 +363,4 @@ def int_quantizer(qtype, quant_params):
     return IntQuantizer(size, quant_params)
 
 
-__all__ = ['IntQuantizer', 'int_quantizer', 'math']
+__all__ = ['IntQuantizer', 'int_quantizer', 'math', 'upcast_fallback', 'HALF_DTYPES']

@@ -605,6 +605,38 @@ int cnnq_pt_minmax_qdq_fused(const float* x, float* y, int64_t n, int rows, int 
 int cnnq_kld_hist(const float* x, int64_t rows, int64_t len, const float* rowmm, uint32_t* hist, void* stream);
 int cnnq_kld_search(const uint32_t* hist, int64_t rows, const float* rowmm, double* div, double* out, void* stream);
 
+/* Activations of another element type: x and y are `const void*` / `void*` of the type `dtype` names, every table
+ * (qp, mm, pmm, ptp, the row extrema, noise) stays fp32 and codes stay uint8.  For BF16 / F16 the result is, bit for
+ * bit, the fp32 entry point's on the exactly upconverted input, rounded to nearest-even into the input type (a NaN
+ * stays a NaN; an fp16 value above 65504 becomes inf): y == fp32_path(x.float()).to(x.dtype).  CNNQ_DTYPE_F32 calls
+ * the fp32 entry point named with the same arguments.  A `dtype` outside the enum returns CNNQ_EINVAL before anything
+ * touches the device; CNNQ_ENOTSUP: nothing was enqueued. */
+enum { CNNQ_DTYPE_F32 = 0, CNNQ_DTYPE_BF16 = 1, CNNQ_DTYPE_F16 = 2, CNNQ_NDTYPE = 3 };
+
+/* Config 2 behind one call (iq.py:409-451,557-603; counterpart of cnnq_pc_minmax_qdq_auto, same `ws` of
+ * cnnq_pc_minmax_qdq_workspace(N, C, HW) bytes; qp[CNNQ_NQP][C] and mm[2][C] are written).  BF16 / F16, two routes:
+ *   - allow_single_launch != 0 and a channel's N*HW elements fit one workgroup's registers (131072) and the rows
+ *     load at least 4 bytes at a time (H*W even, pointers 4-byte aligned): ONE launch that reads x once, one workgroup per channel (k_h_whole);
+ *   - otherwise two launches - exact per-channel min / max partials into ws's pmm, then the Q/DQ, whose workgroups derive
+ *     their channel's parameters from the partials (cnnq_pc_minmax_params' arithmetic).
+ * gws / gws_bytes are not used: channels that span several workgroups take the two launches.
+ * cnnq_pc_route_dt (host only, nothing enqueued) names the route: out = {1 single launch / 2 two launches, elements per
+ * load W, loads per lane (0 for two launches), workgroups}; align_bytes: the power of two that divides both x and y (<= 16). */
+int cnnq_pc_route_dt(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_single_launch, int32_t out[4]);
+int cnnq_pc_minmax_qdq_auto_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, int num_bits,
+                               int positive, float* ws, void* gws, size_t gws_bytes, int allow_single_launch, void* stream);
+/* The table-driven Q/DQ (iq.py:573-592, counterpart of cnnq_pc_qdq).  BF16 / F16: codes and hist must be NULL
+ * (CNNQ_ENOTSUP otherwise); `reverse` is ignored. */
+int cnnq_pc_qdq_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, uint8_t* codes,
+                   uint64_t* hist, int reverse, void* stream);
+/* Per-channel extrema of x[N][C][HW] -> local[2][C] (counterpart of cnnq_pc_minmax_local; with N = 1, C = rows the
+ * per-sample statistics of config 1, iq.py:510-517).  pmm: workspace of
+ * max(cnnq_pc_groups(N, C, HW, 1), cnnq_pc_groups(N, C, HW, 0)) * 2 * C floats. */
+int cnnq_pc_minmax_local_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, float* pmm, float* local,
+                            void* stream);
+/* Config 1's GEMMLOWP Q/DQ (kernels/gemmlowp.cu:8-45, counterpart of cnnq_pt_qdq); ptp from cnnq_pt_setup; noise fp32. */
+int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
