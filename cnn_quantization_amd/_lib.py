@@ -133,6 +133,10 @@ SIGNATURES = {
     'cnnq_kld_hist': (_I, [_P, _L, _L, _P, _P, _P]),
     'cnnq_kld_search': (_I, [_P, _L, _P, _P, _P, _P]),
     'cnnq_pc_route_dt': (_I, [_L, _L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_pc_nhwc_workspace': (ctypes.c_size_t, [_L, _L, _I]),
+    'cnnq_pc_route_nhwc': (_I, [_L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_pc_minmax_qdq_nhwc': (_I, [_P, _P, _I, _L, _L, _I, _I, _P, _P, _P, _P]),
+    'cnnq_pc_qdq_nhwc': (_I, [_P, _P, _I, _L, _L, _P, _P]),
     'cnnq_pc_minmax_qdq_auto_dt': (_I, [_P, _P, _I, _L, _L, _L, _I, _I, _P, _P, ctypes.c_size_t, _I, _P]),
     'cnnq_pc_qdq_dt': (_I, [_P, _P, _I, _L, _L, _L, _P, _P, _P, _I, _P]),
     'cnnq_pc_minmax_local_dt': (_I, [_P, _I, _L, _L, _L, _P, _P, _P]),

@@ -45,6 +45,7 @@
 #include "cnnq_plan.hip.h"
 #include "cnnq_kld.hip.h"
 #include "cnnq_half.hip.h"
+#include "cnnq_nhwc.hip.h"
 
 extern "C" {
 
@@ -1660,6 +1661,74 @@ int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* pt
     }
 #undef LAUNCH_HPT
     return launch_status();
+}
+
+// ---- dense channels_last activations (cnnq_nhwc.hip.h): x and y [R = N*H*W][C], C innermost; fp32 tables ----------------------
+static int cl_check(int64_t R, int64_t C, int dtype) {
+    return (!dtype_ok(dtype) || R < 1 || C < 1 || C > CL_C_MAX) ? CNNQ_EINVAL : 0;
+}
+
+size_t cnnq_pc_nhwc_workspace(int64_t R, int64_t C, int dtype) {
+    if (cl_check(R, C, dtype)) return 0;
+    int64_t S = 1;
+    for (int w = 16 / cl_esize(dtype); w >= 1; w >>= 1) {
+        if (C % w) continue;
+        const int64_t s = cl_geo_mm(R, C, w).S;
+        S = s > S ? s : S;
+    }
+    return ((size_t)2 + 2 * (size_t)S) * (size_t)C * sizeof(float);
+}
+
+int cnnq_pc_route_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
+    if (cl_check(R, C, dtype) || !out || align_bytes <= 0 || (align_bytes & (align_bytes - 1))) return CNNQ_EINVAL;
+    const int w = cl_piece(C, cl_esize(dtype), align_bytes);
+    const ClGeo m = cl_geo_mm(R, C, w), q = cl_geo_qdq(R, C, w);
+    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    out[0] = w;
+    out[1] = m.S;
+    out[2] = q.S * q.nb;
+    out[3] = (int32_t)(m.rpw / m.RS);
+    return 0;
+}
+
+static int cl_qdq(const void* x, void* y, int dtype, int w, int64_t R, int64_t C, const float* qp, const float* mm, hipStream_t st) {
+    const ClGeo q = cl_geo_qdq(R, C, w);
+    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+#define LAUNCH_CLQ(T, W)                                                                                           \
+    hipLaunchKernelGGL((k_cl_qdq<T, W>), dim3((unsigned)(q.S * q.nb)), dim3(TPB), 0, st,                            \
+                       static_cast<const ClRaw<T>::type*>(x), static_cast<ClRaw<T>::type*>(y), q, qp, mm)
+    CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLQ);
+#undef LAUNCH_CLQ
+    return launch_status();
+}
+
+// int_quantizer.py:409-451, 557-603 on [R][C]: k_cl_minmax -> k_minmax_params (qp) -> k_minmax_reduce (the extrema) -> k_cl_qdq
+int cnnq_pc_minmax_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, int num_bits, int positive, float* ws,
+                            float* qp, float* mm, void* stream) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    if (!x || !y || !ws || !qp || num_bits < 1 || num_bits > 32) return CNNQ_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const int w = cl_piece(C, cl_esize(dtype), h_align(x, y));
+    const ClGeo m = cl_geo_mm(R, C, w);
+    if ((int64_t)cl_geo_qdq(R, C, w).S * m.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    float* ext = mm ? mm : ws;
+    float* pmm = ws + 2 * (size_t)C;
+#define LAUNCH_CLM(T, W) \
+    hipLaunchKernelGGL((k_cl_minmax<T, W>), dim3((unsigned)(m.S * m.nb)), dim3(TPB), 0, st, static_cast<const ClRaw<T>::type*>(x), m, pmm)
+    CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLM);
+#undef LAUNCH_CLM
+    int rc = launch_status();
+    if (!rc) rc = cnnq_pc_minmax_params(pmm, m.S, C, num_bits, positive, qp, stream);
+    if (!rc) rc = cnnq_pc_minmax_reduce(pmm, m.S, C, ext, stream);
+    if (!rc) rc = cl_qdq(x, y, dtype, w, R, C, qp, ext, st);
+    return rc;
+}
+
+// int_quantizer.py:573-592 on [R][C] with a given table (-sm use): the IEEE divide
+int cnnq_pc_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* qp, void* stream) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    if (!x || !y || !qp) return CNNQ_EINVAL;
+    return cl_qdq(x, y, dtype, cl_piece(C, cl_esize(dtype), h_align(x, y)), R, C, qp, nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,265 @@
+// cnnq_nhwc.hip.h - config 2 on dense channels_last (NHWC) activations: exact per-channel min / max partials over slabs of
+// rows and the per-channel Q/DQ, for fp32, bf16 and fp16 elements.
+// Part of the single translation unit cnnq_kernels.hip (see its header for the design).
+//
+// The contract: for a dense channels_last x, y has x's layout and y.contiguous() equals, bit for bit, the
+// NCHW path on x.contiguous().  Min / max do not depend on the order of the elements, and the Q/DQ works element by element, so
+// this holds when the arithmetic is the NCHW path's own: the parameters come from k_minmax_params on the partials written here,
+// the Q/DQ is qdq1 (IEEE divide) or, inside qdq_fast_domain, the divide-free quotient of the single-launch kernels (the same
+// bits, cnnq_qdq.hip.h); bf16 / fp16 go through h_up / h_down of cnnq_half.hip.h.
+//
+// Tiling: the tensor is the matrix [R = N*H*W][C], C innermost.  A row is cut into P = C / W pieces of W consecutive channels
+// (W the widest of 16 / 8 / 4 / 2 / 1 bytes that divides C and both pointers' alignment).  A workgroup owns a column block of
+// CP = min(P, TPB) pieces and a slab of rows; lane t keeps piece t % CP for its whole life and walks rows t / CP, t / CP + RS,
+// ... (RS = TPB / CP rows per step), so its channels never change: running extrema and Q/DQ parameters stay in registers.
+#pragma once
+#include "cnnq_common.hip.h"
+#include "cnnq_qdq.hip.h"
+#include "cnnq_half.hip.h"
+
+namespace {
+
+struct CF32 {};     // fp32 elements (HBf16 / HF16: cnnq_half.hip.h)
+
+template <class T>
+struct ClRaw { typedef uint16_t type; };
+template <>
+struct ClRaw<CF32> { typedef float type; };
+
+__device__ __forceinline__ float cl_up(CF32, float v) { return v; }
+__device__ __forceinline__ float cl_up(HBf16 t, uint16_t u) { return h_up(t, u); }
+__device__ __forceinline__ float cl_up(HF16 t, uint16_t u) { return h_up(t, u); }
+__device__ __forceinline__ float cl_down(CF32, float v) { return v; }
+__device__ __forceinline__ uint16_t cl_down(HBf16 t, float v) { return h_down(t, v); }
+__device__ __forceinline__ uint16_t cl_down(HF16 t, float v) { return h_down(t, v); }
+
+// W consecutive elements: one global load / store of W * sizeof(E) bytes (at most 16)
+template <class E, int W, bool NT>
+__device__ __forceinline__ void cl_ld(const E* __restrict__ p, E (&e)[W]) {
+    if constexpr (W == 1) {
+        e[0] = NT ? __builtin_nontemporal_load(p) : *p;
+    } else {
+        typedef E V __attribute__((ext_vector_type(W)));
+        V v;
+        if constexpr (NT) v = __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
+        else v = *reinterpret_cast<const V*>(p);
+#pragma unroll
+        for (int i = 0; i < W; ++i) e[i] = v[i];
+    }
+}
+template <class E, int W>
+__device__ __forceinline__ void cl_st_nt(E* __restrict__ p, const E (&e)[W]) {
+    if constexpr (W == 1) {
+        __builtin_nontemporal_store(e[0], p);
+    } else {
+        typedef E V __attribute__((ext_vector_type(W)));
+        V v;
+#pragma unroll
+        for (int i = 0; i < W; ++i) v[i] = e[i];
+        __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
+    }
+}
+
+// the launch geometry: grid = S * nb workgroups, workgroup b' = s * nb + b owns column block b and rows [s * rpw, (s + 1) * rpw)
+struct ClGeo {
+    int64_t R;      // rows (N * H * W)
+    int64_t rpw;    // rows per workgroup, a multiple of RS
+    int C;          // channels (the row length)
+    int P;          // pieces per row, C / W
+    int CP;         // pieces per column block, min(P, TPB)
+    int RS;         // rows per step, TPB / CP
+    int nb;         // column blocks, ceil(P / CP)
+    int S;          // row slabs
+};
+
+// this lane's piece (-1: idle) and first row of the workgroup's slab
+struct ClLane {
+    int piece;
+    int64_t r, r1;
+};
+__device__ __forceinline__ ClLane cl_lane(const ClGeo& g, int bid) {
+    const int s = bid / g.nb, b = bid - s * g.nb;
+    const int t = (int)threadIdx.x;
+    const int lr = t / g.CP, lp = t - lr * g.CP;
+    ClLane l;
+    l.piece = b * g.CP + lp;
+    if (lr >= g.RS || l.piece >= g.P) l.piece = -1;
+    l.r = (int64_t)s * g.rpw + lr;
+    l.r1 = (int64_t)(s + 1) * g.rpw;
+    if (l.r1 > g.R) l.r1 = g.R;
+    return l;
+}
+
+// exact per-channel {min, max} of slab s -> pmm[s][2][C] (the layout k_minmax_params / k_minmax_reduce merge): plain stores, every
+// entry written exactly once, no atomics.  v_min / v_max drop a NaN: a lane that saw one poisons that channel's result (torch.min /
+// max propagate it, as k_h_minmax does); pmin / pmax keep it through the reductions.
+template <class T, int W>
+__global__ void __launch_bounds__(TPB) k_cl_minmax(const typename ClRaw<T>::type* __restrict__ x, const ClGeo g,
+                                                   float* __restrict__ pmm) {
+    typedef typename ClRaw<T>::type E;
+    __shared__ float l_mn[TPB * W], l_mx[TPB * W];
+    const int bid = (int)blockIdx.x;
+    const ClLane l = cl_lane(g, bid);
+    float mn[W], mx[W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) { mn[i] = INFINITY; mx[i] = -INFINITY; }
+    unsigned nanm = 0;
+    if (l.piece >= 0) {
+        const E* p = x + l.r * g.C + (int64_t)l.piece * W;
+        const int64_t step = (int64_t)g.RS * g.C;
+#pragma unroll 4
+        for (int64_t r = l.r; r < l.r1; r += g.RS, p += step) {
+            E e[W];
+            cl_ld<E, W, false>(p, e);
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+                const float v = cl_up(T{}, e[i]);
+                mn[i] = fminf(mn[i], v);
+                mx[i] = fmaxf(mx[i], v);
+                nanm |= (unsigned)(v != v) << i;
+            }
+        }
+    }
+    const int t = (int)threadIdx.x;
+    if (t < g.RS * g.CP) {
+#pragma unroll
+        for (int i = 0; i < W; ++i) {
+            const bool n = (nanm >> i) & 1u;
+            l_mn[t * W + i] = n ? NAN : mn[i];
+            l_mx[t * W + i] = n ? NAN : mx[i];
+        }
+    }
+    __syncthreads();
+    // the lanes that share a piece: column j of the [RS][CP * W] table, one thread per column
+    const int s = bid / g.nb, b = bid - s * g.nb;
+    const int cols = g.CP * W;
+    for (int j = t; j < cols; j += TPB) {
+        const int c = b * cols + j;
+        if (c >= g.C) break;
+        float a = l_mn[j], z = l_mx[j];
+        for (int k = 1; k < g.RS; ++k) { a = pmin(a, l_mn[k * cols + j]); z = pmax(z, l_mx[k * cols + j]); }
+        pmm[(size_t)(2 * s) * g.C + c] = a;
+        pmm[(size_t)(2 * s + 1) * g.C + c] = z;
+    }
+}
+
+// y = dequant(quant(x)) per channel, x read and y written non-temporally, as k_qdq does.  Each lane loads its piece's parameters
+// once.  mm == NULL: the table qp alone (-sm use: a calibration table does not bound the channel's values), the IEEE divide of
+// k_qdq (qdq1).  mm = the channels' exact extrema [2][C] (config 2): inside qdq_fast_domain the divide-free quotient of the
+// single-launch kernels (qdq2_fast, two elements per packed instruction; the bits of the IEEE divide there), elsewhere qdq1.
+// Workgroups are dispatched in descending address order: what the statistics pass read last is re-read first.
+template <class T, int W>
+__global__ void __launch_bounds__(TPB) k_cl_qdq(const typename ClRaw<T>::type* __restrict__ x, typename ClRaw<T>::type* __restrict__ y,
+                                                const ClGeo g, const float* __restrict__ qp, const float* __restrict__ mm) {
+    typedef typename ClRaw<T>::type E;
+    const ClLane l = cl_lane(g, (int)gridDim.x - 1 - (int)blockIdx.x);
+    if (l.piece < 0) return;
+    const int c0 = l.piece * W;
+    float sc[W], zp[W], qm[W], rs[W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        sc[i] = qp[(size_t)CNNQ_QP_SCALE * g.C + c0 + i];
+        zp[i] = qp[(size_t)CNNQ_QP_ZP * g.C + c0 + i];
+        qm[i] = qp[(size_t)CNNQ_QP_QMAX * g.C + c0 + i];
+    }
+    bool fast = mm != nullptr;
+    if (fast) {
+#pragma unroll
+        for (int i = 0; i < W; ++i) fast = fast && qdq_fast_domain(mm[c0 + i], mm[g.C + c0 + i], sc[i]) && qm[i] == qm[0];
+    }
+#pragma unroll
+    for (int i = 0; i < W; ++i) rs[i] = fast ? 1.0f / sc[i] : 0.f;
+    const int64_t step = (int64_t)g.RS * g.C;
+    int64_t off = l.r * g.C + c0;
+    if (fast) {
+        for (int64_t r = l.r; r < l.r1; r += g.RS, off += step) {
+            E e[W];
+            cl_ld<E, W, true>(x + off, e);
+            if constexpr (W == 1) {
+                float cd;
+                e[0] = cl_down(T{}, qdq1_fast(cl_up(T{}, e[0]), sc[0], rs[0], zp[0], qm[0], cd));
+            } else {
+#pragma unroll
+                for (int i = 0; i < W; i += 2) {
+                    f2v cd;
+                    const f2v o = qdq2_fast(f2v{cl_up(T{}, e[i]), cl_up(T{}, e[i + 1])}, f2v{sc[i], sc[i + 1]},
+                                            f2v{rs[i], rs[i + 1]}, f2v{zp[i], zp[i + 1]}, qm[0], cd);
+                    e[i] = cl_down(T{}, o.x);
+                    e[i + 1] = cl_down(T{}, o.y);
+                }
+            }
+            cl_st_nt<E, W>(y + off, e);
+        }
+    } else {
+        for (int64_t r = l.r; r < l.r1; r += g.RS, off += step) {
+            E e[W];
+            cl_ld<E, W, true>(x + off, e);
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+                float cd;
+                e[i] = cl_down(T{}, qdq1(cl_up(T{}, e[i]), sc[i], zp[i], qm[i], cd));
+            }
+            cl_st_nt<E, W>(y + off, e);
+        }
+    }
+}
+
+// ---- host side: piece width, geometry, slabs
+constexpr int64_t CL_MM_ELEMS = 65536;       // elements per statistics workgroup at least (amortises the LDS reduction)
+constexpr int64_t CL_MM_MAX_WGS = 2048;      // statistics workgroups at most (8 per CU)
+constexpr int64_t CL_PMM_MAX = (int64_t)1 << 19;   // S * C at most: the partials stay <= 4 MB
+constexpr int64_t CL_QDQ_ELEMS = 8192;       // elements per Q/DQ workgroup (many short workgroups, as k_qdq)
+constexpr int64_t CL_C_MAX = (int64_t)1 << 26;
+
+inline int cl_esize(int dtype) { return dtype == CNNQ_DTYPE_F32 ? 4 : 2; }
+
+// the widest piece of at most 16 bytes that divides C and the alignment (bytes) both pointers share
+inline int cl_piece(int64_t C, int esize, int64_t align_bytes) {
+    for (int w = 16 / esize; w > 1; w >>= 1)
+        if (C % w == 0 && align_bytes % ((int64_t)w * esize) == 0) return w;
+    return 1;
+}
+
+// geometry for piece width w with ~per elements per workgroup (at least `per`, a multiple of RS rows), at most smax slabs
+inline ClGeo cl_geo(int64_t R, int64_t C, int w, int64_t per, int64_t max_wgs, int64_t smax) {
+    ClGeo g;
+    g.R = R;
+    g.C = (int)C;
+    g.P = (int)(C / w);
+    g.CP = g.P < TPB ? g.P : TPB;
+    g.RS = TPB / g.CP;
+    g.nb = (g.P + g.CP - 1) / g.CP;
+    const int64_t rstep = (R + g.RS - 1) / g.RS;                          // row steps of the whole tensor
+    const int64_t blk = (int64_t)g.CP * w * g.RS;                         // elements per row step of one workgroup
+    int64_t steps = (per + blk - 1) / blk;                                // row steps per workgroup
+    int64_t s = (rstep + steps - 1) / steps;
+    if (s * g.nb > max_wgs) s = (max_wgs + g.nb - 1) / g.nb;
+    if (s > smax) s = smax;
+    if (s < 1) s = 1;
+    steps = (rstep + s - 1) / s;
+    g.rpw = steps * g.RS;
+    g.S = (int)((R + g.rpw - 1) / g.rpw);
+    return g;
+}
+inline ClGeo cl_geo_mm(int64_t R, int64_t C, int w) {
+    int64_t smax = CL_PMM_MAX / C;
+    return cl_geo(R, C, w, CL_MM_ELEMS, CL_MM_MAX_WGS, smax < 1 ? 1 : smax);
+}
+inline ClGeo cl_geo_qdq(int64_t R, int64_t C, int w) {
+    return cl_geo(R, C, w, CL_QDQ_ELEMS, ((int64_t)1 << 31) - 1, ((int64_t)1 << 31) - 1);
+}
+
+#define CNNQ_CL_DISPATCH(dt, w, F)                                                  \
+    do {                                                                            \
+        if ((dt) == CNNQ_DTYPE_F32) {                                               \
+            if ((w) == 4) F(CF32, 4); else if ((w) == 2) F(CF32, 2); else F(CF32, 1); \
+        } else if ((dt) == CNNQ_DTYPE_BF16) {                                       \
+            if ((w) == 8) F(HBf16, 8); else if ((w) == 4) F(HBf16, 4);              \
+            else if ((w) == 2) F(HBf16, 2); else F(HBf16, 1);                       \
+        } else {                                                                    \
+            if ((w) == 8) F(HF16, 8); else if ((w) == 4) F(HF16, 4);                \
+            else if ((w) == 2) F(HF16, 2); else F(HF16, 1);                         \
+        }                                                                           \
+    } while (0)
+
+}  // namespace

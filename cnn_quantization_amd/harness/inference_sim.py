@@ -75,6 +75,9 @@ def build_parser():
     p.add_argument('--dtype', default='float32', choices=('float32', 'bfloat16', 'float16'),
                    help='element type of the model and its activations; BN folding and the synthetic input are computed in '
                         'float32 and then cast (configs 1 and 2 quantize bf16 / fp16 natively, every other path upcasts)')
+    p.add_argument('--channels-last', action='store_true',
+                   help='run the model and its input in the channels_last (NHWC) memory format, after BN folding, --dtype and '
+                        'the weight quantization (configs 1 and 2 quantize dense channels_last activations as they are)')
     p.add_argument('--verbose', action='store_true')
     p.add_argument('--sharded', action='store_true',
                    help='one process per GPU (start under torchrun / torch.distributed.run): every rank takes its shard of each '
@@ -186,6 +189,9 @@ def run(args, quiet=False):
         if dtype != torch.float32:
             model = model.to(dtype)
         qm.quantize_model(model)                     # weights (verbose=True inside, like the reference)
+        channels_last = getattr(args, 'channels_last', False)
+        if channels_last:
+            model = model.to(memory_format=torch.channels_last)
         timer = QuantTimer(qm)
         qm.verbose = args.verbose
         g = torch.Generator(device=dev).manual_seed(args.seed)
@@ -198,6 +204,8 @@ def run(args, quiet=False):
                 if sharded:                          # the same batch on every rank (same seed); this rank's samples of it
                     n0, n1 = D.shard_batch(args.batch_size, D.rank(qm.group), D.world_size(qm.group))
                     x = x[n0:n1].contiguous()
+                if channels_last:
+                    x = x.to(memory_format=torch.channels_last)
                 for attempt in range(2):
                     timer.rows.clear()
                     torch.cuda.synchronize()

@@ -23,7 +23,9 @@ def float2gemmlowp(input, range, offset, num_bits, int_exp, enforce_true_zero, n
         return input
     if not isinstance(input, torch.Tensor) or not input.is_cuda:
         raise RuntimeError('int_quantization.float2gemmlowp needs a CUDA/HIP float32 tensor')
-    x = input.contiguous()
+    # element by element: a dense channels_last input is quantized as it is and the result keeps its layout (ops.pt_qdq); with
+    # the noise of stochastic rounding, which is indexed in NCHW order, it is copied (and counted, ops.LAYOUT_COPIES)
+    x = input if noise is None else ops._dev_act(input, 'input')
     ptp = ops.pt_setup(x.device, int(num_bits), range_offset=(rng, off), int_exp=bool(int_exp),
                        enforce_true_zero=bool(enforce_true_zero))
     return ops.pt_qdq(x, ptp, noise=noise)

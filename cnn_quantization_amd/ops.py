@@ -26,7 +26,7 @@ def _stream(t):
     return ctypes.c_void_p(_raw_stream(t.device.index))
 
 
-def _dev_f32(x, what='tensor', dtypes=(torch.float32,)):
+def _dev_f32(x, what='tensor', dtypes=(torch.float32,), keep_nhwc=False):
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise L.CnnqError('%s must be a CUDA/HIP tensor (there is no CPU path)' % what)
     if x.dtype not in dtypes:
@@ -37,17 +37,54 @@ def _dev_f32(x, what='tensor', dtypes=(torch.float32,)):
         raise L.CnnqError('%s is on %s but the current device is cuda:%d' % (what, x.device, torch.cuda.current_device()))
     if x.requires_grad:
         x = x.detach()
-    return x if x.is_contiguous() else x.contiguous()
+    if x.is_contiguous():
+        return x
+    if _layout(x) == 'nhwc':
+        if keep_nhwc and _NHWC:
+            return x
+        global LAYOUT_COPIES
+        LAYOUT_COPIES += 1
+    return x.contiguous()
+
+
+# dense channels_last activations: configs 1 and 2 run on the storage as it is and return a result of the
+# input's layout.  Every copy _dev_f32 makes of such a tensor is counted here, so that tests can prove those paths never copy.
+LAYOUT_COPIES = 0
+
+
+def _layout(x):
+    """'nchw': dense in the default layout (also every tensor dense in both, C == 1 or H*W == 1); 'nhwc': a dense channels_last
+    4-D tensor that is not; 'copy': anything else.  Shape and strides only, so CPU tensors work too."""
+    if x.is_contiguous():
+        return 'nchw'
+    if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last):
+        return 'nhwc'
+    return 'copy'
+
+
+def _is_nhwc(x):
+    """A tensor _dev_act_layout let through is either contiguous or dense channels_last."""
+    return not x.is_contiguous()
+
+
+def _one_process(group):
+    return group is False or (D.world_size(group) == 1 and not D.forced_exchange())
 
 
 # activations of another element type (include/cnnq_hip.h, cnnq_dtype): the entry points of configs 1 and 2 that take them
 _HALF_DTYPES = {torch.bfloat16: L.DTYPE_BF16, torch.float16: L.DTYPE_F16}
+_DTYPE_CODES = {torch.float32: L.DTYPE_F32, **_HALF_DTYPES}
 _ACT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
 def _dev_act(x, what='tensor'):
     """_dev_f32 for the activation paths that have bf16 / fp16 kernels."""
     return _dev_f32(x, what, _ACT_DTYPES)
+
+
+def _dev_act_layout(x, what='tensor'):
+    """_dev_act for the paths that have channels_last kernels: a dense channels_last tensor passes as it is (CNNQ_NHWC=0: copied)."""
+    return _dev_f32(x, what, _ACT_DTYPES, keep_nhwc=True)
 
 
 def _half_only(what, reason):
@@ -58,7 +95,8 @@ def _half_only(what, reason):
 # switches, read ONCE at import (the hot call used to look three of them up per tensor: weak #10 of the round-2
 # review); reload_switches() re-reads them for callers that change the environment afterwards (tests, tools)
 def reload_switches():
-    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE
+    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC
+    _NHWC = os.environ.get('CNNQ_NHWC', '1') != '0'                    # 0: channels_last tensors take the NCHW copy route (A/B)
     _ACIQ_SINGLE = os.environ.get('CNNQ_ACIQ_SINGLE', '1') != '0'      # 0: the ACIQ path always takes the five-launch chain (A/B)
     _XRANK_ON = D.xrank_mode() != '0'                                  # opt-in (CNNQ_XRANK=1 / auto, D.set_xrank_mode): sharded config 2 exchanges INSIDE the single launch
     _PT_FUSED = os.environ.get('CNNQ_PT_FUSED', '0') == '1'           # 1: config 1 in one launch (slower: see ops.minmax_qdq_per_tensor)
@@ -116,11 +154,12 @@ def _scratch(x, tag, nbytes, st=None):
 def _out_like(x, out):
     """The result buffer: a new tensor like x, or the caller's - which must match x exactly."""
     if out is None:
-        return torch.empty_like(x)
-    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == x.dtype and out.is_contiguous()
-            and out.shape == x.shape and out.device == x.device):
-        raise L.CnnqError('out must be a contiguous %s tensor on %s shaped like the input'
-                          % (str(x.dtype).replace('torch.', ''), x.device))
+        return torch.empty_like(x)          # a dense channels_last x: a channels_last y (preserve_format)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == x.dtype and out.shape == x.shape
+            and out.device == x.device and (out.is_contiguous() if x.is_contiguous() else _layout(out) == 'nhwc')):
+        raise L.CnnqError('out must be a %s %s tensor on %s shaped like the input'
+                          % ('contiguous' if x.is_contiguous() else 'dense channels_last', str(x.dtype).replace('torch.', ''),
+                             x.device))
     nbytes = x.numel() * x.element_size()
     if out.data_ptr() < x.data_ptr() + nbytes and x.data_ptr() < out.data_ptr() + nbytes:
         # the kernels declare x and y __restrict__, and a single-launch workgroup whose bounded wait expires recomputes
@@ -470,7 +509,9 @@ def pc_qdq(x, N, C, HW, qp, want_codes=False, out=None, hist=None, reverse=False
     """y = dequant(quant(x)) with per-channel parameters; optionally the uint8 codes; `hist`
     (optional zeroed int64[256] tensor) receives the code histogram; reverse: descending addresses."""
     lib = L.load()
-    x = _dev_act(x, 'x')
+    x = _dev_act(x, 'x') if (want_codes or hist is not None) else _dev_act_layout(x, 'x')
+    if _is_nhwc(x):
+        return _pc_qdq_nhwc(x, qp, out)
     if x.dtype != torch.float32:
         if want_codes or hist is not None:
             _half_only('pc_qdq', 'codes / the code histogram')
@@ -483,6 +524,39 @@ def pc_qdq(x, N, C, HW, qp, want_codes=False, out=None, hist=None, reverse=False
     L.check(lib.cnnq_pc_qdq(_ptr(x), _ptr(y), N, C, HW, _ptr(qp), _ptr(codes), _ptr(hist), int(bool(reverse)),
                             _stream(x)), 'cnnq_pc_qdq')
     return (y, codes) if want_codes else y
+
+
+def _pc_qdq_nhwc(x, qp, out):
+    """pc_qdq on a dense channels_last x with the table qp (cnnq_pc_qdq_nhwc: the IEEE divide); y has x's layout."""
+    C = x.shape[1]
+    y = _out_like(x, out)
+    L.check(L.load().cnnq_pc_qdq_nhwc(_ptr(x), _ptr(y), _DTYPE_CODES[x.dtype], x.numel() // C, C, _ptr(qp), _stream(x)),
+            'cnnq_pc_qdq_nhwc')
+    return y
+
+
+def _minmax_qdq_nhwc(x, num_bits, positive, out):
+    """Config 2 on a dense channels_last x on one GPU (cnnq_pc_minmax_qdq_nhwc: statistics partials over slabs of rows, the
+    parameters, the channel extrema, the Q/DQ); one cached workspace, which also holds the parameter table.  y has x's layout."""
+    lib = L.load()
+    C = x.shape[1]
+    R = x.numel() // C
+    dt = _DTYPE_CODES[x.dtype]
+    key = ('nhwc', R, C, dt)
+    nbytes = _WS_BYTES.get(key)
+    if nbytes is None:
+        nbytes = lib.cnnq_pc_nhwc_workspace(R, C, dt)
+        if nbytes == 0:
+            raise L.CnnqError('cnnq_pc_nhwc_workspace(%d, %d, %d): bad arguments' % (R, C, dt))
+        nbytes = _WS_BYTES[key] = (nbytes + 15) // 16 * 16
+    y = _out_like(x, out)
+    st = _raw_stream(x.device.index)
+    ws = _scratch(x, 'nhwc', nbytes + L.NQP * C * 4, st).data_ptr()
+    rc = lib.cnnq_pc_minmax_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, int(num_bits), 1 if positive else 0, ws, ws + nbytes,
+                                     None, st)
+    if rc:
+        L.check(rc, 'cnnq_pc_minmax_qdq_nhwc')
+    return y
 
 
 _GROUP_WS = {}
@@ -840,7 +914,11 @@ def minmax_qdq_fused(x, N, C, HW, num_bits, positive=False, want_codes=False, wa
     single-launch kernels are tested against.  _xrank: an XRankExchange to use (its verify()), False: never.  group=False:
     replicated data, the one-GPU route."""
     if not _checked:
-        x = _dev_act(x, 'x')
+        nhwc = not (want_codes or want_entropy or want_parts or chain or _xrank) and _one_process(group)
+        x = _dev_act_layout(x, 'x') if nhwc else _dev_act(x, 'x')
+    if _is_nhwc(x):
+        # a dense channels_last x (DESIGN.md section 12): plain config 2 on one GPU, on the storage as it is
+        return _minmax_qdq_nhwc(x, num_bits, positive, out)
     if x.dtype != torch.float32:
         return _minmax_qdq_half(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group)
     # group=False: replicated data (weights) - never exchanged, whatever process group the job runs in.  (Until round 6 this
@@ -1230,7 +1308,9 @@ def pt_setup(device, num_bits, range_offset=None, stats=None, rows=0, rows_mode=
 
 def pt_qdq(x, ptp, noise=None, out=None):
     lib = L.load()
-    x = _dev_act(x, 'x')
+    # element by element: a dense channels_last x is quantized in its storage order, y has its layout (the noise of
+    # stochastic rounding is indexed in NCHW order: that route keeps the copy)
+    x = _dev_act(x, 'x') if noise is not None else _dev_act_layout(x, 'x')
     y = _out_like(x, out)
     if noise is not None:
         noise = _dev_f32(noise, 'noise')
@@ -1257,9 +1337,17 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
     bcorr (None, or the relu-first flag): also apply the activation bias correction of iqm.py:180-196,
     fused into the passes where the parameter table is at hand (qdq_bias_corrected).
     Returns y [, codes] [, entropy (0-dim device tensor)] [, parts].  No host synchronisation."""
-    x = _dev_act(x, 'x')
-    N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x, per_channel_dim)
     use_ba = bool(bit_alloc) and num_bits <= 4 and not whole_tensor
+    # config 2, dynamic on one GPU or from a statistics table, keeps a dense channels_last x as it is (DESIGN.md section 12)
+    nhwc = (per_channel_dim == 1 and not whole_tensor and clip == 'no' and not use_ba and bcorr is None
+            and not (want_codes or want_entropy or want_parts) and (stats is not None or _one_process(group)))
+    x = _dev_act_layout(x, 'x') if nhwc else _dev_act(x, 'x')
+    N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x, per_channel_dim)
+    if _is_nhwc(x):
+        if stats is None:
+            return _minmax_qdq_nhwc(x, num_bits, positive, out)
+        qp, _ = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
+        return _pc_qdq_nhwc(x, qp, out)
     if x.dtype != torch.float32:
         # bf16 / fp16: config 2, dynamic or from a statistics table - min/max parameters, no clipping, no bit allocation
         if (clip != 'no' or use_ba or whole_tensor or per_channel_dim != 1 or bcorr is not None or want_codes or want_entropy
@@ -1509,7 +1597,10 @@ def tensor_row_stats(x, rows):
     """Per-row MIN/MAX (and friends) of x viewed as [rows, numel/rows]: the per-sample statistics
     of iq.py:510-517 (rows = batch) - the per-channel kernels with N = 1, C = rows."""
     lib = L.load()
-    x = _dev_act(x, 'x')
+    # each sample of a dense channels_last tensor is one contiguous block of C*H*W elements: rows = samples (or 1) read the
+    # storage as it is
+    per_sample = isinstance(x, torch.Tensor) and x.dim() == 4 and rows in (1, x.shape[0])
+    x = _dev_act_layout(x, 'x') if per_sample else _dev_act(x, 'x')
     hw = x.numel() // rows
     if x.dtype != torch.float32:
         G = max(lib.cnnq_pc_groups(1, rows, hw, 1), lib.cnnq_pc_groups(1, rows, hw, 0))
@@ -1538,8 +1629,8 @@ def minmax_qdq_per_tensor(x, num_bits, avg_over_batch, zero_min=False, int_exp=F
     fused=True (default: CNNQ_PT_FUSED=1) takes the ONE-launch form on a single GPU (cnnq_pt_minmax_qdq_fused): the same
     bits, but measured SLOWER than the chain - 70 against 54 us on the [32,64,112,112] tensor of BASELINE config 1: its
     second sweep is not served by the Infinity Cache once 103 MB of y are written next to it - so
-    it is opt-in."""
-    x = _dev_act(x, 'x')
+    it is opt-in.  A dense channels_last x is read as it is (its samples are contiguous blocks too); y has its layout."""
+    x = _dev_act_layout(x, 'x')
     rows = x.shape[0] if x.dim() > 1 else 1
     if (_PT_FUSED if fused is None else fused) and D.world_size(group) == 1 and x.numel() > 0 and x.dtype == torch.float32:
         # one launch (k_pt_fused): two sweeps with a tile count in between, the second served by the Infinity Cache

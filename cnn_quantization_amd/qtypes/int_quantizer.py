@@ -327,8 +327,9 @@ class IntQuantizer:
         from .. import int_quantization
         delta, offset = float(delta), float(offset)
         preserve_zero = self.enforce_true_zero and (offset + delta) > 0 and offset < 0
-        return int_quantization.float2gemmlowp(tensor.contiguous(), delta, offset, self.num_bits, self.int_exp,
-                                               preserve_zero, None)
+        # the pass is element by element: a dense channels_last tensor goes as it is, and the result keeps its layout
+        x = tensor if ops._layout(tensor) == 'nhwc' else tensor.contiguous()
+        return int_quantization.float2gemmlowp(x, delta, offset, self.num_bits, self.int_exp, preserve_zero, None)
 
     # ------------------------------------------------------------------ mid-tread (config 5)
     def mid_tread_quantize_weights_per_channel(self, tensor, id):

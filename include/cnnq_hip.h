@@ -637,6 +637,27 @@ int cnnq_pc_minmax_local_dt(const void* x, int dtype, int64_t N, int64_t C, int6
 /* Config 1's GEMMLOWP Q/DQ (kernels/gemmlowp.cu:8-45, counterpart of cnnq_pt_qdq); ptp from cnnq_pt_setup; noise fp32. */
 int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream);
 
+/* Dense channels_last (NHWC) activations: x and y are the matrix [R = N*H*W][C] with C innermost, `const void*` / `void*`
+ * of cnnq_dtype; qp, mm and ws stay fp32.  y has x's layout and equals, bit for bit, the NCHW entry point's result on the
+ * same values in NCHW order (min / max do not depend on the order; the Q/DQ is element by element, with the NCHW path's
+ * arithmetic).  A bad dtype, R < 1 or C < 1 returns CNNQ_EINVAL before anything touches the device.  Rows load the widest
+ * of 16 / 8 / 4 / 2 / 1 bytes that divides C and the alignment of both pointers, so every C and every element offset has a
+ * route.  x != y (both are read / written in several launches).
+ * cnnq_pc_nhwc_workspace: bytes of `ws` for cnnq_pc_minmax_qdq_nhwc (0 on bad arguments).
+ * cnnq_pc_route_nhwc (host only, nothing enqueued): out = {elements per load W, row slabs S of the statistics launch,
+ * workgroups of the Q/DQ launch, row loads per lane of the statistics launch}; align_bytes: the power of two that
+ * divides both x and y (<= 16 is what matters). */
+size_t cnnq_pc_nhwc_workspace(int64_t R, int64_t C, int dtype);
+int cnnq_pc_route_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]);
+/* Config 2 (int_quantizer.py:409-451, 557-603; counterpart of cnnq_pc_minmax_qdq_auto): exact per-channel {min, max}
+ * partials over slabs of rows into ws, cnnq_pc_minmax_params -> qp[CNNQ_NQP][C], cnnq_pc_minmax_reduce -> mm[2][C] (the
+ * channel extrema; NULL: kept in ws), then the Q/DQ (divide-free inside the fast domain, the IEEE divide elsewhere: the
+ * same bits).  Four launches, no host synchronisation. */
+int cnnq_pc_minmax_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, int num_bits, int positive,
+                            float* ws, float* qp, float* mm, void* stream);
+/* The table-driven Q/DQ (int_quantizer.py:573-592, -sm use; counterpart of cnnq_pc_qdq): the IEEE divide, one launch. */
+int cnnq_pc_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* qp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
