@@ -257,11 +257,7 @@ class XRankExchange:
         from . import _lib as L
         for (n, c, h, w) in ((40, 6, 56, 56), (37, 24, 14, 14)):
             x = torch.randn((n, c, h, w), generator=g, device=self.device) * (1 + self.rank) - 0.3
-            plan = (self, self.group, ops._scratch(x, 'stats', L.load().cnnq_pc_stats_workspace(n, c, h * w, 1), ops._raw_stream(self.device.index)),
-                    ops._group_workspace(x))
-            ops._XPLAN[('stats', id(self.group), x.device.index, ops._raw_stream(self.device.index), n, c, h * w, x.data_ptr() % 16 == 0)] = plan
-            st, mom = ops._pc_stats_xrank(x, n, c, h * w, True, True, True, self.group)
-            ops.release_plans()
+            st, mom = ops._pc_stats_xrank(x, n, c, h * w, True, True, True, self.group, _xrank=self)
             part = ops.pc_moments(x, n, c, h * w, True)
             mom_local, _ = ops.pc_combine(part, True)
             mom_ref, st_ref = ops.pc_combine(all_gather_records(mom_local, self.group), True)

@@ -26,7 +26,7 @@ def _stream(t):
     return ctypes.c_void_p(_raw_stream(t.device.index))
 
 
-def _dev_f32(x, what='tensor', dtypes=(torch.float32,), keep_nhwc=False):
+def _dev(x, what='tensor', dtypes=(torch.float32,), keep_nhwc=False):
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise L.CnnqError('%s must be a CUDA/HIP tensor (there is no CPU path)' % what)
     if x.dtype not in dtypes:
@@ -48,7 +48,7 @@ def _dev_f32(x, what='tensor', dtypes=(torch.float32,), keep_nhwc=False):
 
 
 # dense channels_last activations: configs 1 and 2 run on the storage as it is and return a result of the
-# input's layout.  Every copy _dev_f32 makes of such a tensor is counted here, so that tests can prove those paths never copy.
+# input's layout.  Every copy _dev makes of such a tensor is counted here, so that tests can prove those paths never copy.
 LAYOUT_COPIES = 0
 
 
@@ -67,8 +67,9 @@ def _is_nhwc(x):
     return not x.is_contiguous()
 
 
-def _one_process(group):
-    return group is False or (D.world_size(group) == 1 and not D.forced_exchange())
+def _sharded(group):
+    """x is this rank's shard of the batch (a 1-rank group too under CNNQ_FORCE_EXCHANGE=1, which times the exchange on one GPU)."""
+    return group is not False and (D.world_size(group) > 1 or D.forced_exchange())
 
 
 # activations of another element type (include/cnnq_hip.h, cnnq_dtype): the entry points of configs 1 and 2 that take them
@@ -78,13 +79,13 @@ _ACT_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
 
 
 def _dev_act(x, what='tensor'):
-    """_dev_f32 for the activation paths that have bf16 / fp16 kernels."""
-    return _dev_f32(x, what, _ACT_DTYPES)
+    """_dev for the activation paths that have bf16 / fp16 kernels."""
+    return _dev(x, what, _ACT_DTYPES)
 
 
 def _dev_act_layout(x, what='tensor'):
     """_dev_act for the paths that have channels_last kernels: a dense channels_last tensor passes as it is (CNNQ_NHWC=0: copied)."""
-    return _dev_f32(x, what, _ACT_DTYPES, keep_nhwc=True)
+    return _dev(x, what, _ACT_DTYPES, keep_nhwc=True)
 
 
 def _half_only(what, reason):
@@ -92,8 +93,7 @@ def _half_only(what, reason):
     raise L.CnnqError('%s: no bfloat16 / float16 kernel for %s (compute on x.float())' % (what, reason))
 
 
-# switches, read ONCE at import (the hot call used to look three of them up per tensor: weak #10 of the round-2
-# review); reload_switches() re-reads them for callers that change the environment afterwards (tests, tools)
+# switches, read ONCE at import (not per hot call); reload_switches() re-reads them after the environment changed (tests, tools)
 def reload_switches():
     global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC
     _NHWC = os.environ.get('CNNQ_NHWC', '1') != '0'                    # 0: channels_last tensors take the NCHW copy route (A/B)
@@ -141,13 +141,12 @@ def _scratch(x, tag, nbytes, st=None):
     key = (x.device.index, _raw_stream(x.device.index) if st is None else st, tag)
     buf = _SCRATCH.get(key)
     if buf is None or buf.numel() < nbytes:
-        if torch.cuda.is_current_stream_capturing():
-            # inside a stream capture the buffer comes from the graph's private pool: hand it out WITHOUT caching it
-            # (a cached one would later serve eager calls from memory that belongs to the graph); the pool keeps the
-            # block for the graph's replays and reuses it in capture order
-            return torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=x.device)
         buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=x.device)
-        _SCRATCH[key] = buf
+        # inside a stream capture the buffer comes from the graph's private pool: hand it out WITHOUT caching it (a cached
+        # one would later serve eager calls from memory that belongs to the graph); the pool keeps the block for the
+        # graph's replays and reuses it in capture order
+        if not torch.cuda.is_current_stream_capturing():
+            _SCRATCH[key] = buf
     return buf
 
 
@@ -178,13 +177,75 @@ def geometry(x, per_channel_dim=1):
     return n, c, x.numel() // (n * c)
 
 
+# ------------------------------------------------------------------------------------- launch plumbing
+def _supported(rc, what):
+    """False on CNNQ_ENOTSUP (no single-launch kernel for this shape: the caller takes another route); other errors raise."""
+    if rc != L.ENOTSUP:
+        L.check(rc, what)
+    return rc != L.ENOTSUP
+
+
+def _gws_args(gws):
+    return gws, (GROUP_WS_BYTES if gws is not None else 0)
+
+
+def _groups(N, C, HW, aligned=None):
+    """The chain's partial-record count for x's alignment, or (None) the larger of both, so that G records serve either."""
+    lib = L.load()
+    if aligned is None:
+        G = max(lib.cnnq_pc_groups(N, C, HW, 1), lib.cnnq_pc_groups(N, C, HW, 0))
+    else:
+        G = lib.cnnq_pc_groups(N, C, HW, int(aligned))
+    if G <= 0:
+        L.check(G, 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
+    return G
+
+
+def _ws_bytes(kind, N, C, HW, arg=0):
+    """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
+    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', N = rows).  0 from the library: no plan for the geometry."""
+    key = (kind, N, C, HW, arg)
+    nbytes = _WS_BYTES.get(key)
+    if nbytes is None:
+        lib = L.load()
+        if kind == 'nhwc':
+            nbytes = lib.cnnq_pc_nhwc_workspace(N, C, arg)
+            if nbytes == 0:
+                raise L.CnnqError('cnnq_pc_nhwc_workspace(%d, %d, %d): bad arguments' % (N, C, arg))
+        elif kind == 'aciq':
+            nbytes = lib.cnnq_pc_aciq_workspace(N, C, HW, arg)
+        else:
+            nbytes = lib.cnnq_pc_minmax_qdq_workspace(N, C, HW) if kind == 'cfg2' else lib.cnnq_pc_stats_workspace(N, C, HW, arg)
+            if nbytes == 0:
+                L.check(min(lib.cnnq_pc_groups(N, C, HW, 1), -1), 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
+        nbytes = _WS_BYTES[key] = (nbytes + 15) // 16 * 16
+    return nbytes
+
+
+def _result(y, codes=None, entropy=None, parts=None):
+    res = tuple(v for v in (y, codes, entropy, parts) if v is not None)
+    return res if len(res) > 1 else y
+
+
+def _mt_result(y, entropy, codes=None, parts=None):
+    return (y, entropy) + tuple(v for v in (codes, parts) if v is not None)
+
+
+def _minmax_parts(mm, qp, g=None):
+    """Config 2's parts from the {min, max} rows mm, or (the chain) from the first g records of the partial extrema mm."""
+    if g is not None:
+        mm = (mm[:g, 0].min(dim=0)[0], mm[:g, 1].max(dim=0)[0])
+    stats = torch.zeros((L.NSTAT, qp.shape[1]), dtype=torch.float32, device=qp.device)
+    stats[L.STAT_MIN] = mm[0]
+    stats[L.STAT_MAX] = mm[1]
+    return dict(stats=stats, qp=qp, diag=None)
+
+
 # ------------------------------------------------------------------------------------- statistics
 def pc_moments(x, N, C, HW, want_relu=False):
     """Pass A partial records [G, NMOM, C] (float64)."""
     lib = L.load()
-    G = lib.cnnq_pc_groups(N, C, HW, int(x.data_ptr() % 16 == 0))
-    if G <= 0:
-        L.check(G, 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
+    G = _groups(N, C, HW, x.data_ptr() % 16 == 0)
     part = torch.empty((G, L.NMOM, C), dtype=torch.float64, device=x.device)
     L.check(lib.cnnq_pc_moments(_ptr(x), N, C, HW, int(want_relu), _ptr(part), _stream(x)), 'cnnq_pc_moments')
     return part
@@ -204,7 +265,7 @@ def pc_combine(part, has_relu=False, stats=None, want_mom=True):
 
 def pc_absdev(x, N, C, HW, stats, want_kurt=False):
     lib = L.load()
-    G = lib.cnnq_pc_groups(N, C, HW, int(x.data_ptr() % 16 == 0))
+    G = _groups(N, C, HW, x.data_ptr() % 16 == 0)
     part2 = torch.empty((G, L.NDEV, C), dtype=torch.float64, device=x.device)
     L.check(lib.cnnq_pc_absdev(_ptr(x), N, C, HW, _ptr(stats), int(want_kurt), _ptr(part2), _stream(x)),
             'cnnq_pc_absdev')
@@ -227,109 +288,76 @@ def pc_stats(x, N, C, HW, need_b=False, need_kurt=False, need_relu=False, group=
     With a process group of world size > 1 the tensor is this rank's batch shard: the fp64
     moment records are all-gathered (<= 7*C*8 bytes per rank, latency-bound on xGMI) and merged
     in rank order on every rank, so all ranks hold the statistics of the GLOBAL batch."""
-    x = _dev_f32(x, 'x')
-    world = 1 if local_only else D.world_size(group)
-    if not local_only and (world > 1 or D.forced_exchange()) and _ACIQ_SINGLE and _RESIDENT:
+    x = _dev(x, 'x')
+    sharded = not local_only and _sharded(group)
+    if sharded and _ACIQ_SINGLE and _RESIDENT:
         # the batch is sharded and the group has a (verified) in-launch exchange: the table of the GLOBAL batch from one read of
         # this rank's shard (cnnq_pc_stats_xrank; round 6) - every rank takes this route or none does
         res = _pc_stats_xrank(x, N, C, HW, need_b, need_kurt, need_relu, group)
         if res is not None:
             return res
-    if world == 1 and (local_only or not D.forced_exchange()):
+    if not sharded:
         # one C call, one cached workspace (cnnq_pc_stats_auto)
         lib = L.load()
-        nbytes = lib.cnnq_pc_stats_workspace(N, C, HW, int(x.data_ptr() % 16 == 0))
-        if nbytes == 0:
-            L.check(min(lib.cnnq_pc_groups(N, C, HW, 1), -1), 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
+        nbytes = _ws_bytes('stats', N, C, HW, int(x.data_ptr() % 16 == 0))
         stats = torch.empty((L.NSTAT, C), dtype=torch.float32, device=x.device)
         mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
         st = _raw_stream(x.device.index)
         gws = _group_workspace(x, st) if (_ACIQ_SINGLE and _RESIDENT) else None
         # one launch that reads x once where the shape has a flat plan (cnnq_pc_stats_single), else the three-launch chain
         L.check(lib.cnnq_pc_stats_auto(_ptr(x), N, C, HW, int(bool(need_b)), int(bool(need_kurt)), int(bool(need_relu)),
-                                       _ptr(_scratch(x, 'stats', nbytes, st)), gws, GROUP_WS_BYTES if gws is not None else 0,
-                                       _ptr(mom), _ptr(stats), st), 'cnnq_pc_stats')
+                                       _ptr(_scratch(x, 'stats', nbytes, st)), *_gws_args(gws), _ptr(mom), _ptr(stats), st),
+                'cnnq_pc_stats')
         return stats, mom
     # the collective route (ranks sharing a GPU, CNNQ_XRANK=0, after a recovery; also a 1-rank group under CNNQ_FORCE_EXCHANGE=1,
     # which times the real collectives on one GPU): the chain's passes with an all_gather of the fp64 records behind each
-    exchanging = world > 1 or D.forced_exchange()
-    part = pc_moments(x, N, C, HW, need_relu)
-    if exchanging:
-        mom_local, _ = pc_combine(part, need_relu)
-        part = D.all_gather_records(mom_local, group)
-    mom, stats = pc_combine(part, need_relu)
+    mom_local, _ = pc_combine(pc_moments(x, N, C, HW, need_relu), need_relu)
+    mom, stats = pc_combine(D.all_gather_records(mom_local, group), need_relu)
     if need_b or need_kurt:
-        part2 = pc_absdev(x, N, C, HW, stats, need_kurt)
-        if exchanging:
-            dev_local = pc_combine_dev(part2, mom, None, need_kurt, want_sums=True)
-            part2 = D.all_gather_records(dev_local, group)
-        pc_combine_dev(part2, mom, stats, need_kurt)
+        dev_local = pc_combine_dev(pc_absdev(x, N, C, HW, stats, need_kurt), mom, None, need_kurt, want_sums=True)
+        pc_combine_dev(D.all_gather_records(dev_local, group), mom, stats, need_kurt)
     return stats, mom
 
 
-def _xrank_for(group, C, words=1):
-    """The group's in-launch exchange (D.xrank_exchange: opt-in mode, verified against the collective on every rank) when a launch
-    over C channels with `words` slots per channel fits its windows, else None.  Depends on the group and the layer only - never
-    on this rank's shard - so all ranks decide alike."""
-    if not _XRANK_ON:
-        return None
-    xr = D.xrank_exchange(group)
-    return xr if (xr is not None and xr.fits(C, words)) else None
-
-
-def _xrank_plan(kind, x, N, C, HW, group, st, ws_bytes):
-    """What the sharded single-call routes need per (group, stream, geometry), looked up once: the exchange, the scratch
-    workspace and the group workspace.  None: the group has no in-launch exchange.  (Under a stream capture nothing is cached:
-    a capture-time scratch buffer belongs to the graph's pool.)"""
-    key = (kind, id(group), x.device.index, st, N, C, HW, x.data_ptr() % 16 == 0)
-    plan = _XPLAN.get(key)
+def _xrank_plan(kind, x, N, C, HW, group, xr=None):
+    """(exchange, group, scratch, group workspace arguments, stream) of the sharded one-call routes, looked up once; None: the group has no
+    (verified) in-launch exchange whose windows fit C channels - a test of the group and the layer, never of this rank's shard,
+    so all ranks decide alike.  The plan keeps `group` alive, so its id stays its own.  Not cached: under a stream capture (the
+    scratch would belong to the graph's pool) or with an exchange `xr` the caller forces (XRankExchange.verify)."""
+    st = _raw_stream(x.device.index)
+    key = (kind, id(group), x.device.index, st, N, C, HW, kind != 'cfg2' and x.data_ptr() % 16 == 0)
+    plan = _XPLAN.get(key) if xr is None else None
     if plan is None:
-        xr = _xrank_for(group, C, 8)
-        if xr is None:
-            plan = False
-        else:
-            plan = (xr, group, _scratch(x, kind, ws_bytes(), st), _group_workspace(x, st))
-        if not torch.cuda.is_current_stream_capturing():
+        cache = xr is None and not torch.cuda.is_current_stream_capturing()
+        if xr is None and _XRANK_ON:
+            xr = D.xrank_exchange(group)
+        plan = False
+        if xr is not None and xr.fits(C, 1 if kind == 'cfg2' else 8):
+            nbytes = _ws_bytes(kind, N, C, HW, int(key[-1]))
+            if kind == 'aciq':          # the tables that nobody outside the call reads live behind the workspace
+                nbytes += (L.NSTAT + L.NQP + L.NDIAG) * C * 4 + L.NMOM * C * 8
+            plan = (xr, group, _scratch(x, kind, nbytes, st), _gws_args(_group_workspace(x, st)), st)
+        if cache:
             _XPLAN[key] = plan
     return plan or None
 
 
-def _pc_stats_xrank(x, N, C, HW, need_b, need_kurt, need_relu, group, flags=0):
+def _pc_stats_xrank(x, N, C, HW, need_b, need_kurt, need_relu, group, flags=0, _xrank=None):
     """Config 4 of a batch shard in ONE host call and - where the shard has a flat-tile plan - one launch and one read of x
     (cnnq_pc_stats_xrank: k_stats_flat with the cross-rank stage; otherwise the chain's two passes with their records made global
     through the same window slots).  No collective.  Returns (stats, mom) of the GLOBAL batch, or None when the group has no
-    in-launch exchange."""
-    lib = L.load()
-    st = _raw_stream(x.device.index)
-
-    def nbytes():
-        n = lib.cnnq_pc_stats_workspace(N, C, HW, int(x.data_ptr() % 16 == 0))
-        if n == 0:
-            L.check(min(lib.cnnq_pc_groups(N, C, HW, 1), -1), 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
-        return n
-    plan = _xrank_plan('stats', x, N, C, HW, group, st, nbytes)
+    in-launch exchange.  _xrank: an XRankExchange to use instead of the group's (its verify())."""
+    plan = _xrank_plan('stats', x, N, C, HW, group, _xrank)
     if plan is None:
         return None
-    xr, _, ws, gws = plan
+    xr, _, ws, gws, st = plan
     stats = torch.empty((L.NSTAT, C), dtype=torch.float32, device=x.device)
     mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
-    ctx = xr.ctx(st)
-    rc = lib.cnnq_pc_stats_xrank(x.data_ptr(), N, C, HW, 1 if need_b else 0, 1 if need_kurt else 0, 1 if need_relu else 0, ws.data_ptr(),
-                                 gws, GROUP_WS_BYTES if gws is not None else 0, mom.data_ptr(), stats.data_ptr(), ctypes.byref(ctx),
-                                 int(flags), st)
+    rc = L.load().cnnq_pc_stats_xrank(x.data_ptr(), N, C, HW, 1 if need_b else 0, 1 if need_kurt else 0, 1 if need_relu else 0, ws.data_ptr(),
+                                 *gws, mom.data_ptr(), stats.data_ptr(), ctypes.byref(xr.ctx(st)), int(flags), st)
     if rc:
         L.check(rc, 'cnnq_pc_stats_xrank')
     return stats, mom
-
-
-def _aciq_ws_bytes(x, N, C, HW):
-    lib = L.load()
-    al = int(x.data_ptr() % 16 == 0)
-    key = ('aciq', N, C, HW, al)
-    nbytes = _WS_BYTES.get(key)
-    if nbytes is None:
-        nbytes = _WS_BYTES[key] = (lib.cnnq_pc_aciq_workspace(N, C, HW, al) + 15) // 16 * 16
-    return nbytes
 
 
 def _aciq_qdq_xrank(x, N, C, HW, cfg, group, want_parts, out, flags=0):
@@ -338,25 +366,21 @@ def _aciq_qdq_xrank(x, N, C, HW, cfg, group, want_parts, out, flags=0):
     for pass B + the ranks' sums of |x - mean| + parameters + Q/DQ - the four launches of one GPU, 12 bytes per element, no
     collective, where the chain moves 16 around two.  Returns y [, parts], or None when the group has no in-launch exchange (the
     caller takes the chain)."""
-    lib = L.load()
-    st = _raw_stream(x.device.index)
-    plan = _xrank_plan('aciq', x, N, C, HW, group, st,
-                       lambda: _aciq_ws_bytes(x, N, C, HW) + (L.NSTAT + L.NQP + L.NDIAG) * C * 4 + L.NMOM * C * 8)
+    plan = _xrank_plan('aciq', x, N, C, HW, group)
     if plan is None:
         return None
-    xr, _, ws, gws = plan
+    xr, _, ws, gws, st = plan
     y = _out_like(x, out)
     if want_parts:
         tabs = torch.empty((L.NSTAT + L.NQP + L.NDIAG, C), dtype=torch.float32, device=x.device)
         mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
         tp, mp = tabs.data_ptr(), mom.data_ptr()
     else:                       # nobody outside the call reads the tables: they live behind the workspace
-        mp = ws.data_ptr() + _aciq_ws_bytes(x, N, C, HW)
+        mp = ws.data_ptr() + _ws_bytes('aciq', N, C, HW, int(x.data_ptr() % 16 == 0))
         tp = mp + L.NMOM * C * 8
     sp, qp, dp = tp, tp + L.NSTAT * C * 4, tp + (L.NSTAT + L.NQP) * C * 4
-    ctx = xr.ctx(st)
-    rc = lib.cnnq_pc_aciq_fused_xrank(x.data_ptr(), y.data_ptr(), N, C, HW, ctypes.byref(cfg), ws.data_ptr(), gws,
-                                      GROUP_WS_BYTES if gws is not None else 0, sp, mp, qp, dp, ctypes.byref(ctx), int(flags), st)
+    rc = L.load().cnnq_pc_aciq_fused_xrank(x.data_ptr(), y.data_ptr(), N, C, HW, ctypes.byref(cfg), ws.data_ptr(), *gws, sp, mp, qp,
+                                      dp, ctypes.byref(xr.ctx(st)), int(flags), st)
     if rc:
         L.check(rc, 'cnnq_pc_aciq_fused_xrank')
     if want_parts:
@@ -368,35 +392,22 @@ def _mid_tread_qdq_xrank(x, N, C, HW, target, sym, tabs_mt, group, want_entropy,
     """Config 5 of a batch shard: as _aciq_qdq_xrank with the bin allocation and MODE 1 of the fused kernels
     (cnnq_pc_midtread_fused_xrank); the ranks' code counts are summed before the entropy (the one collective left: an integer
     all-reduce of the count table).  Returns what mid_tread_qdq returns, or None when the group has no in-launch exchange."""
-    lib = L.load()
-    st = _raw_stream(x.device.index)
-    plan = _xrank_plan('aciq', x, N, C, HW, group, st,
-                       lambda: _aciq_ws_bytes(x, N, C, HW) + (L.NSTAT + L.NQP + L.NDIAG) * C * 4 + L.NMOM * C * 8)
+    plan = _xrank_plan('aciq', x, N, C, HW, group)
     if plan is None:
         return None
-    xr, _, ws, gws = plan
+    xr, _, ws, gws, st = plan
     y = torch.empty_like(x)
     tabs = torch.empty((L.NSTAT + L.NMT, C), dtype=torch.float32, device=x.device)
     stats, mt = tabs[:L.NSTAT], tabs[L.NSTAT:]
     mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
     hist = torch.empty(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None     # zeroed by the call
-    ctx = xr.ctx(st)
-    rc = lib.cnnq_pc_midtread_fused_xrank(x.data_ptr(), y.data_ptr(), N, C, HW, float(target), int(bool(sym)), tabs_mt.data_ptr(),
-                                          tabs_mt.shape[1], ws.data_ptr(), gws, GROUP_WS_BYTES if gws is not None else 0, stats.data_ptr(),
-                                          mom.data_ptr(), mt.data_ptr(), _ptr(hist), ctypes.byref(ctx), int(flags), st)
+    rc = L.load().cnnq_pc_midtread_fused_xrank(x.data_ptr(), y.data_ptr(), N, C, HW, float(target), int(bool(sym)), tabs_mt.data_ptr(),
+                                          tabs_mt.shape[1], ws.data_ptr(), *gws, stats.data_ptr(), mom.data_ptr(), mt.data_ptr(),
+                                          _ptr(hist), ctypes.byref(xr.ctx(st)), int(flags), st)
     if rc:
         L.check(rc, 'cnnq_pc_midtread_fused_xrank')
-    entropy = None
-    if want_entropy:
-        D.all_reduce_sum_(hist, group)
-        ent = torch.empty(1, dtype=torch.float32, device=x.device)
-        # (the global batch's element count from the merged moment record: shards may differ by a sample)
-        L.check(lib.cnnq_midtread_entropy_count(_ptr(hist), _ptr(mt), C, mom[L.MOM_COUNT].data_ptr(), _ptr(ent), st), 'cnnq_midtread_entropy')
-        entropy = ent[0]
-    res = [y, entropy]
-    if want_parts:
-        res.append(dict(stats=stats, mt=mt, hist=hist, mom=mom))
-    return tuple(res)
+    entropy = _mt_entropy(x, hist, mt, C, st, group, mom) if want_entropy else None
+    return _mt_result(y, entropy, parts=dict(stats=stats, mt=mt, hist=hist, mom=mom) if want_parts else None)
 
 
 def pc_stats_single(x, N, C, HW, need_b=False, need_kurt=False, need_relu=False, flags=8):
@@ -404,7 +415,7 @@ def pc_stats_single(x, N, C, HW, need_b=False, need_kurt=False, need_relu=False,
     when the shape has no flat-tile plan.  flags: bit 3 (default here) also takes channels of more than 256 tiles, which
     ops.pc_stats leaves to the chain; bit 0 forces the recompute path (tests)."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     st = _raw_stream(x.device.index)
     gws = _group_workspace(x, st)
     if gws is None:
@@ -413,9 +424,8 @@ def pc_stats_single(x, N, C, HW, need_b=False, need_kurt=False, need_relu=False,
     mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
     rc = lib.cnnq_pc_stats_single(_ptr(x), N, C, HW, int(bool(need_b)), int(bool(need_kurt)), int(bool(need_relu)), gws,
                                   GROUP_WS_BYTES, _ptr(mom), _ptr(stats), int(flags), st)
-    if rc == L.ENOTSUP:
+    if not _supported(rc, 'cnnq_pc_stats_single'):
         return None
-    L.check(rc, 'cnnq_pc_stats_single')
     return stats, mom
 
 
@@ -470,7 +480,7 @@ def act_qdq_mix(x, num_bits, stats, mse, positive=False, bit_alloc=False, prior_
     laplace, gaus, lowp.  Everything downstream of the clipping value is per channel and elementwise, so the three
     candidates' parameter tables are merged per channel: two cnnq_pc_params launches, the min/max candidate in a few
     [C]-sized fp32 torch ops that repeat that kernel's arithmetic (iq.py:284-300, 351, 443, 559-572), one fused Q/DQ."""
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x)
     stats = stats.to(device=x.device, dtype=torch.float32)
     mse = torch.as_tensor(mse, dtype=torch.float32, device=x.device).view(3, C)
@@ -512,14 +522,13 @@ def pc_qdq(x, N, C, HW, qp, want_codes=False, out=None, hist=None, reverse=False
     x = _dev_act(x, 'x') if (want_codes or hist is not None) else _dev_act_layout(x, 'x')
     if _is_nhwc(x):
         return _pc_qdq_nhwc(x, qp, out)
+    if x.dtype != torch.float32 and (want_codes or hist is not None):
+        _half_only('pc_qdq', 'codes / the code histogram')
+    y = _out_like(x, out)
     if x.dtype != torch.float32:
-        if want_codes or hist is not None:
-            _half_only('pc_qdq', 'codes / the code histogram')
-        y = _out_like(x, out)
         L.check(lib.cnnq_pc_qdq_dt(_ptr(x), _ptr(y), _HALF_DTYPES[x.dtype], N, C, HW, _ptr(qp), None, None, 0, _stream(x)),
                 'cnnq_pc_qdq_dt')
         return y
-    y = _out_like(x, out)
     codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_codes else None
     L.check(lib.cnnq_pc_qdq(_ptr(x), _ptr(y), N, C, HW, _ptr(qp), _ptr(codes), _ptr(hist), int(bool(reverse)),
                             _stream(x)), 'cnnq_pc_qdq')
@@ -542,13 +551,7 @@ def _minmax_qdq_nhwc(x, num_bits, positive, out):
     C = x.shape[1]
     R = x.numel() // C
     dt = _DTYPE_CODES[x.dtype]
-    key = ('nhwc', R, C, dt)
-    nbytes = _WS_BYTES.get(key)
-    if nbytes is None:
-        nbytes = lib.cnnq_pc_nhwc_workspace(R, C, dt)
-        if nbytes == 0:
-            raise L.CnnqError('cnnq_pc_nhwc_workspace(%d, %d, %d): bad arguments' % (R, C, dt))
-        nbytes = _WS_BYTES[key] = (nbytes + 15) // 16 * 16
+    nbytes = _ws_bytes('nhwc', R, C, 1, dt)
     y = _out_like(x, out)
     st = _raw_stream(x.device.index)
     ws = _scratch(x, 'nhwc', nbytes + L.NQP * C * 4, st).data_ptr()
@@ -618,7 +621,7 @@ def minmax_qdq_group(x, N, C, HW, num_bits, positive=False, out=None, want_parts
     """Config 2 in ONE launch and ONE read of x for tensors whose channels span several workgroups
     (cnnq_pc_minmax_qdq_group).  Returns None when the shape is not supported (the caller takes the chain)."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     nbytes = lib.cnnq_pc_group_workspace(N, C, HW)
     if nbytes == 0 or nbytes > GROUP_WS_BYTES:
         return None
@@ -630,15 +633,9 @@ def minmax_qdq_group(x, N, C, HW, num_bits, positive=False, out=None, want_parts
     rc = lib.cnnq_pc_minmax_qdq_group(_ptr(x), _ptr(y), N, C, HW, int(num_bits), int(bool(positive)),
                                       gws, _ptr(qp), _ptr(qp[L.NQP:]) if want_parts else None,
                                       int(flags), _stream(x))
-    if rc == L.ENOTSUP:
+    if not _supported(rc, 'cnnq_pc_minmax_qdq_group'):
         return None
-    L.check(rc, 'cnnq_pc_minmax_qdq_group')
-    if want_parts:
-        stats = torch.zeros((L.NSTAT, C), dtype=torch.float32, device=x.device)
-        stats[L.STAT_MIN] = qp[L.NQP]
-        stats[L.STAT_MAX] = qp[L.NQP + 1]
-        return y, dict(stats=stats, qp=qp[:L.NQP], diag=None)
-    return y
+    return (y, _minmax_parts(qp[L.NQP:], qp[:L.NQP])) if want_parts else y
 
 
 def minmax_qdq_resident(x, N, C, HW, num_bits, positive=False, out=None, want_parts=False):
@@ -647,20 +644,14 @@ def minmax_qdq_resident(x, N, C, HW, num_bits, positive=False, out=None, want_pa
     population does not fit a workgroup's registers, unaligned pointers, H*W % 4 != 0 without a straddling
     layout) - the caller then takes the chain."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     y = _out_like(x, out)
     qp = torch.empty((L.NQP + 2, C), dtype=torch.float32, device=x.device)     # parameters + {min, max} rows
     rc = lib.cnnq_pc_minmax_qdq_resident(_ptr(x), _ptr(y), N, C, HW, int(num_bits), int(bool(positive)), _ptr(qp),
                                          _ptr(qp[L.NQP:]) if want_parts else None, _stream(x))
-    if rc == L.ENOTSUP:
+    if not _supported(rc, 'cnnq_pc_minmax_qdq_resident'):
         return None
-    L.check(rc, 'cnnq_pc_minmax_qdq_resident')
-    if want_parts:
-        stats = torch.zeros((L.NSTAT, C), dtype=torch.float32, device=x.device)
-        stats[L.STAT_MIN] = qp[L.NQP]
-        stats[L.STAT_MAX] = qp[L.NQP + 1]
-        return y, dict(stats=stats, qp=qp[:L.NQP], diag=None)
-    return y
+    return (y, _minmax_parts(qp[L.NQP:], qp[:L.NQP])) if want_parts else y
 
 
 _HIST_REP = {}
@@ -779,6 +770,15 @@ def _entropy_slot(x, st):
     return _hist_replicas(x, st), None
 
 
+def _replica_entropy(x, hist, ent_batched, st):
+    """The entropy of a single launch's replica tables: the entropy_batch result (filled at the block's end), else one launch."""
+    if ent_batched is not None:
+        return ent_batched
+    ent = torch.empty(1, dtype=torch.float32, device=x.device)
+    L.check(L.load().cnnq_entropy_replicas(_ptr(hist), _ptr(ent), st), 'cnnq_entropy_replicas')
+    return ent[0]
+
+
 def minmax_qdq_single(x, N, C, HW, num_bits, positive=False, want_codes=False, want_entropy=False, out=None,
                       want_parts=False):
     """Config 2 in ONE launch also when the codes and / or the entropy of the codes are wanted
@@ -787,7 +787,7 @@ def minmax_qdq_single(x, N, C, HW, num_bits, positive=False, want_codes=False, w
     if num_bits > 8 and (want_codes or want_entropy):
         return None
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     st = _raw_stream(x.device.index)
     gws = _group_workspace(x, st)
     y = _out_like(x, out)
@@ -796,28 +796,12 @@ def minmax_qdq_single(x, N, C, HW, num_bits, positive=False, want_codes=False, w
     hist, ent_batched = _entropy_slot(x, st) if want_entropy else (None, None)
     if want_entropy and hist is None:
         return None
-    rc = lib.cnnq_pc_minmax_qdq_single(_ptr(x), _ptr(y), N, C, HW, int(num_bits), int(bool(positive)), gws,
-                                       GROUP_WS_BYTES if gws is not None else 0, _ptr(qp), _ptr(qp[L.NQP:]), _ptr(codes),
-                                       _ptr(hist), None, st)
-    if rc == L.ENOTSUP:
+    rc = lib.cnnq_pc_minmax_qdq_single(_ptr(x), _ptr(y), N, C, HW, int(num_bits), int(bool(positive)), *_gws_args(gws),
+                                       _ptr(qp), _ptr(qp[L.NQP:]), _ptr(codes), _ptr(hist), None, st)
+    if not _supported(rc, 'cnnq_pc_minmax_qdq_single'):
         return None
-    L.check(rc, 'cnnq_pc_minmax_qdq_single')
-    res = [y]
-    if want_codes:
-        res.append(codes)
-    if want_entropy:
-        if ent_batched is not None:
-            res.append(ent_batched)              # filled by the one launch at the end of the entropy_batch block
-        else:
-            ent = torch.empty(1, dtype=torch.float32, device=x.device)
-            L.check(lib.cnnq_entropy_replicas(_ptr(hist), _ptr(ent), st), 'cnnq_entropy_replicas')
-            res.append(ent[0])
-    if want_parts:
-        stats = torch.zeros((L.NSTAT, C), dtype=torch.float32, device=x.device)
-        stats[L.STAT_MIN] = qp[L.NQP]
-        stats[L.STAT_MAX] = qp[L.NQP + 1]
-        res.append(dict(stats=stats, qp=qp[:L.NQP], diag=None))
-    return res[0] if len(res) == 1 else tuple(res)
+    return _result(y, codes, _replica_entropy(x, hist, ent_batched, st) if want_entropy else None,
+                   _minmax_parts(qp[L.NQP:], qp[:L.NQP]) if want_parts else None)
 
 
 def aciq_qdq_single(x, N, C, HW, num_bits, positive=False, bit_alloc=False, target=None, round_mode=True, want_codes=False,
@@ -827,7 +811,7 @@ def aciq_qdq_single(x, N, C, HW, num_bits, positive=False, bit_alloc=False, targ
     single launch).  Returns y [, codes] [, entropy] [, parts], or None when the shape has no single-launch plan (the
     caller takes the chain)."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     st = _raw_stream(x.device.index)
     gws = _group_workspace(x, st)
     if gws is None:
@@ -836,11 +820,7 @@ def aciq_qdq_single(x, N, C, HW, num_bits, positive=False, bit_alloc=False, targ
     if want_entropy and hist is None:
         return None
     cfg = _params_cfg(num_bits, positive, 'laplace', bit_alloc, False, target, round_mode, False)
-    al = int(x.data_ptr() % 16 == 0)
-    key = ('aciq', N, C, HW, al)
-    nbytes = _WS_BYTES.get(key)
-    if nbytes is None:
-        nbytes = _WS_BYTES[key] = (lib.cnnq_pc_aciq_workspace(N, C, HW, al) + 15) // 16 * 16
+    nbytes = _ws_bytes('aciq', N, C, HW, int(x.data_ptr() % 16 == 0))
     ws = _scratch(x, 'aciq', nbytes + (L.NQP + L.NDIAG) * C * 4, st)
     y = _out_like(x, out)
     tabs = torch.empty((L.NSTAT + L.NQP + L.NDIAG, C), dtype=torch.float32, device=x.device)
@@ -848,22 +828,10 @@ def aciq_qdq_single(x, N, C, HW, num_bits, positive=False, bit_alloc=False, targ
     codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_codes else None
     rc = lib.cnnq_pc_aciq_qdq_single(_ptr(x), _ptr(y), N, C, HW, ctypes.byref(cfg), ws.data_ptr(), gws, GROUP_WS_BYTES, _ptr(stats),
                                      _ptr(qp), _ptr(diag), _ptr(codes), _ptr(hist), int(flags), st)
-    if rc == L.ENOTSUP:
+    if not _supported(rc, 'cnnq_pc_aciq_qdq_single'):
         return None
-    L.check(rc, 'cnnq_pc_aciq_qdq_single')
-    res = [y]
-    if want_codes:
-        res.append(codes)
-    if want_entropy:
-        if ent_batched is not None:
-            res.append(ent_batched)
-        else:
-            ent = torch.empty(1, dtype=torch.float32, device=x.device)
-            L.check(lib.cnnq_entropy_replicas(_ptr(hist), _ptr(ent), st), 'cnnq_entropy_replicas')
-            res.append(ent[0])
-    if want_parts:
-        res.append(dict(stats=stats, qp=qp, diag=diag))
-    return res[0] if len(res) == 1 else tuple(res)
+    return _result(y, codes, _replica_entropy(x, hist, ent_batched, st) if want_entropy else None,
+                   dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
 
 
 def minmax_quantize_pack4(x, num_bits=4, positive=False, out=None):
@@ -872,7 +840,7 @@ def minmax_quantize_pack4(x, num_bits=4, positive=False, out=None):
     Returns (packed uint8 [numel / 2], qp [NQP, C]); dequantize_pack4(packed, x.shape, qp) gives back exactly what
     act_qdq_per_channel(x, num_bits) returns.  None when the shape has no single-launch kernel."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     if num_bits > 4 or x.numel() % 2:
         raise L.CnnqError('packed 4-bit storage needs num_bits <= 4 and an even number of elements')
     N, C, HW = geometry(x)
@@ -882,20 +850,11 @@ def minmax_quantize_pack4(x, num_bits=4, positive=False, out=None):
     if out is not None and not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= x.numel() // 2):
         raise L.CnnqError('out must be a contiguous uint8 device buffer of numel / 2 bytes')
     qp = torch.empty((L.NQP, C), dtype=torch.float32, device=x.device)
-    rc = lib.cnnq_pc_minmax_qdq_single(_ptr(x), None, N, C, HW, int(num_bits), int(bool(positive)), gws,
-                                       GROUP_WS_BYTES if gws is not None else 0, _ptr(qp), None, None, None, _ptr(packed), st)
-    if rc == L.ENOTSUP:
+    rc = lib.cnnq_pc_minmax_qdq_single(_ptr(x), None, N, C, HW, int(num_bits), int(bool(positive)), *_gws_args(gws), _ptr(qp),
+                                       None, None, None, _ptr(packed), st)
+    if not _supported(rc, 'cnnq_pc_minmax_qdq_single'):
         return None
-    L.check(rc, 'cnnq_pc_minmax_qdq_single')
     return packed, qp
-
-
-def _cfg2_workspace_bytes(lib, N, C, HW):
-    wplan = _WS_BYTES.get((N, C, HW))
-    nbytes = wplan[0] if wplan is not None else lib.cnnq_pc_minmax_qdq_workspace(N, C, HW)
-    if nbytes == 0:
-        L.check(min(lib.cnnq_pc_groups(N, C, HW, 1), -1), 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
-    return nbytes
 
 
 def minmax_qdq_fused(x, N, C, HW, num_bits, positive=False, want_codes=False, want_entropy=False, out=None,
@@ -914,25 +873,25 @@ def minmax_qdq_fused(x, N, C, HW, num_bits, positive=False, want_codes=False, wa
     single-launch kernels are tested against.  _xrank: an XRankExchange to use (its verify()), False: never.  group=False:
     replicated data, the one-GPU route."""
     if not _checked:
-        nhwc = not (want_codes or want_entropy or want_parts or chain or _xrank) and _one_process(group)
+        nhwc = not (want_codes or want_entropy or want_parts or chain or _xrank) and not _sharded(group)
         x = _dev_act_layout(x, 'x') if nhwc else _dev_act(x, 'x')
     if _is_nhwc(x):
         # a dense channels_last x (DESIGN.md section 12): plain config 2 on one GPU, on the storage as it is
         return _minmax_qdq_nhwc(x, num_bits, positive, out)
     if x.dtype != torch.float32:
         return _minmax_qdq_half(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group)
-    # group=False: replicated data (weights) - never exchanged, whatever process group the job runs in.  (Until round 6 this
-    # arrived here as None = the default group: every rank's identical weights went through the exchange - the same bits, one
-    # needless collective per layer, and a wait that expired there left NaN WEIGHTS behind, outside any forward a checkpoint redoes.)
-    world = 1 if group is False else D.world_size(group)
-    if group is False or not (world > 1 or D.forced_exchange()):
+    # group=False: replicated data (weights) - never exchanged, whatever process group the job runs in: an exchange would give
+    # the same bits for one needless collective per layer, and a wait that expired there would leave NaN WEIGHTS behind,
+    # outside any forward a checkpoint redoes
+    if not _sharded(group):
         return _minmax_qdq_local(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, chain)
     resident = _RESIDENT and not chain
     if _xrank is not False and (_xrank is not None or _XRANK_ON) and not ((want_codes or want_entropy) and num_bits > 8):
         res = _minmax_qdq_xrank(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group, resident, _xrank)
         if res is not None:
             return res
-    return _minmax_qdq_collective(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group, world, resident)
+    return _minmax_qdq_collective(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group,
+                                  D.world_size(group), resident)
 
 
 def _minmax_qdq_half(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group):
@@ -941,10 +900,10 @@ def _minmax_qdq_half(x, N, C, HW, num_bits, positive, want_codes, want_entropy, 
     exchange have no half kernels: the quantizer computes those on x.float()."""
     if want_codes or want_entropy or want_parts:
         _half_only('minmax_qdq_fused', 'codes / entropy / parts')
-    if group is not False and (D.world_size(group) > 1 or D.forced_exchange()):
+    if _sharded(group):
         _half_only('minmax_qdq_fused', 'the sharded exchange')
     lib = L.load()
-    nbytes = _cfg2_workspace_bytes(lib, N, C, HW)
+    nbytes = _ws_bytes('cfg2', N, C, HW)
     y = _out_like(x, out)
     st = _raw_stream(x.device.index)
     rc = lib.cnnq_pc_minmax_qdq_auto_dt(x.data_ptr(), y.data_ptr(), _HALF_DTYPES[x.dtype], N, C, HW, int(num_bits),
@@ -955,32 +914,31 @@ def _minmax_qdq_half(x, N, C, HW, num_bits, positive, want_codes, want_entropy, 
     return y
 
 
+_LOCAL_PLAN = {}    # per (N, C, HW): (workspace bytes, whether the one-GPU hot call hands the C side the group workspace)
+
+
 def _minmax_qdq_local(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, chain):
     """Config 2 on one GPU."""
     lib = L.load()
     resident = _RESIDENT and not chain
     if not (want_codes or want_entropy or want_parts):
         # the hot call: one C entry point, one cached workspace, no torch allocation besides the result
-        key = (N, C, HW)
-        plan = _WS_BYTES.get(key)
+        plan = _LOCAL_PLAN.get((N, C, HW))
         if plan is None:
-            nbytes = lib.cnnq_pc_minmax_qdq_workspace(N, C, HW)
-            if nbytes == 0:
-                L.check(min(lib.cnnq_pc_groups(N, C, HW, 1), -1), 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
+            nbytes = _ws_bytes('cfg2', N, C, HW)
             d = (ctypes.c_int32 * 8)()
             # the group workspace is needed when there is no whole-channel kernel, or one with too few workgroups
             # to fill the chip (RES_MIN_WGS in csrc/cnnq_plan.hip.h: the C side routes, this only decides whether
             # to hand it the workspace)
             wants_group = ((lib.cnnq_pc_resident_describe(N, C, HW, d) != 0 or d[6] < 192)
                            and 0 < lib.cnnq_pc_group_workspace(N, C, HW) <= GROUP_WS_BYTES)
-            plan = _WS_BYTES[key] = (nbytes, wants_group)
+            plan = _LOCAL_PLAN[(N, C, HW)] = (nbytes, wants_group)
         nbytes, wants_group = plan
         y = _out_like(x, out)
         st = _raw_stream(x.device.index)          # looked up once: workspace keys and the launch stream
         gws = _group_workspace(x, st) if (resident and wants_group) else None
         rc = lib.cnnq_pc_minmax_qdq_auto(x.data_ptr(), y.data_ptr(), N, C, HW, int(num_bits), 1 if positive else 0,
-                                         _scratch(x, 'cfg2', nbytes, st).data_ptr(), gws,
-                                         GROUP_WS_BYTES if gws is not None else 0, 1 if resident else 0, st)
+                                         _scratch(x, 'cfg2', nbytes, st).data_ptr(), *_gws_args(gws), 1 if resident else 0, st)
         if rc:
             L.check(rc, 'cnnq_pc_minmax_qdq_auto')
         return y
@@ -995,28 +953,22 @@ def _minmax_qdq_local(x, N, C, HW, num_bits, positive, want_codes, want_entropy,
         res = minmax_qdq_single(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out=out, want_parts=want_parts)
         if res is not None:
             return res
+    y, pmm, qp, codes, hist = _chain_buffers(x, N, C, HW, out, want_codes, want_entropy)
+    L.check(lib.cnnq_pc_minmax_qdq(_ptr(x), _ptr(y), N, C, HW, int(num_bits), int(bool(positive)), _ptr(pmm),
+                                   _ptr(qp), _ptr(codes), _ptr(hist), _stream(x)), 'cnnq_pc_minmax_qdq')
+    entropy = entropy_from_hist(hist) if want_entropy else None
+    parts = _minmax_parts(pmm, qp, lib.cnnq_pc_groups(N, C, HW, int(x.data_ptr() % 16 == 0))) if want_parts else None
+    return _result(y, codes, entropy, parts)
+
+
+def _chain_buffers(x, N, C, HW, out, want_codes, want_entropy):
     y = _out_like(x, out)
-    G = max(lib.cnnq_pc_groups(N, C, HW, 1), lib.cnnq_pc_groups(N, C, HW, 0))
-    if G <= 0:
-        L.check(G, 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
+    G = _groups(N, C, HW)
     pmm = torch.empty((G, 2, C), dtype=torch.float32, device=x.device)
     qp = torch.empty((L.NQP, C), dtype=torch.float32, device=x.device)
     codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_codes else None
     hist = torch.zeros(256, dtype=torch.int64, device=x.device) if want_entropy else None
-    L.check(lib.cnnq_pc_minmax_qdq(_ptr(x), _ptr(y), N, C, HW, int(num_bits), int(bool(positive)), _ptr(pmm),
-                                   _ptr(qp), _ptr(codes), _ptr(hist), _stream(x)), 'cnnq_pc_minmax_qdq')
-    res = [y]
-    if want_codes:
-        res.append(codes)
-    if want_entropy:
-        res.append(entropy_from_hist(hist))
-    if want_parts:
-        g_used = lib.cnnq_pc_groups(N, C, HW, int(x.data_ptr() % 16 == 0))
-        stats = torch.zeros((L.NSTAT, C), dtype=torch.float32, device=x.device)
-        stats[L.STAT_MIN] = pmm[:g_used, 0].min(dim=0)[0]
-        stats[L.STAT_MAX] = pmm[:g_used, 1].max(dim=0)[0]
-        res.append(dict(stats=stats, qp=qp, diag=None))
-    return res[0] if len(res) == 1 else tuple(res)
+    return y, pmm, qp, codes, hist
 
 
 def _minmax_qdq_xrank(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group, resident, _xrank):
@@ -1024,52 +976,27 @@ def _minmax_qdq_xrank(x, N, C, HW, num_bits, positive, want_codes, want_entropy,
     verified against the collective at first use): x is read once; every rank takes this route or none does.  Also with
     the codes / the entropy of the codes / the parameters wanted (the ranks' code counts are summed afterwards).  None: this
     group has no (verified) in-launch exchange - the caller takes the collective."""
-    lib = L.load()
-    st = _raw_stream(x.device.index)
-    if _xrank is None and resident and not (want_codes or want_entropy or want_parts):
-        # the sharded hot call: everything that does not change from call to call is looked up once (the exchange of the
-        # group, the workspaces); D.disable_xrank / release_plans() drop the plans
-        key = ('xr', id(group), x.device.index, st, N, C, HW)
-        plan = _XPLAN.get(key)
-        if plan is None and not torch.cuda.is_current_stream_capturing():    # (a capture-time scratch buffer is never cached)
-            xr = D.xrank_exchange(group)
-            plan = False
-            if xr is not None and xr.fits(C):
-                plan = (xr, group, _scratch(x, 'cfg2', _cfg2_workspace_bytes(lib, N, C, HW), st), _group_workspace(x, st))
-            _XPLAN[key] = plan
-        if plan:
-            y = _out_like(x, out)
-            plan[0].minmax_qdq(x, y, N, C, HW, num_bits, positive, plan[2].data_ptr(), plan[3], GROUP_WS_BYTES, st)
-            return y
-        xr = None if plan is False else D.xrank_exchange(group)
-    else:
-        xr = _xrank if _xrank is not None else D.xrank_exchange(group)
-    hist_rep = _hist_replicas(x, st) if (want_entropy and xr is not None) else None
-    if xr is None or not xr.fits(C) or (want_entropy and hist_rep is None):
+    plan = _xrank_plan('cfg2', x, N, C, HW, group, _xrank)      # D.disable_xrank / release_plans() drop the plans
+    hist_rep = _hist_replicas(x, plan[4]) if (want_entropy and plan is not None) else None
+    if plan is None or (want_entropy and hist_rep is None):
         return None
+    xr, _, ws, gws, st = plan
     y = _out_like(x, out)
-    gws = _group_workspace(x, st) if resident else None
-    ws = _scratch(x, 'cfg2', _cfg2_workspace_bytes(lib, N, C, HW), st)
     codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_codes else None
-    xr.minmax_qdq(x, y, N, C, HW, num_bits, positive, ws.data_ptr(), gws,
-                  GROUP_WS_BYTES if gws is not None else 0, st, codes=codes, hist_rep=hist_rep)
+    xr.minmax_qdq(x, y, N, C, HW, num_bits, positive, ws.data_ptr(), *(gws if resident else _gws_args(None)), st, codes=codes,
+                  hist_rep=hist_rep)
     if not (want_codes or want_entropy or want_parts):
         return y
-    res = [y]
-    if want_codes:
-        res.append(codes)
+    entropy = parts = None
     if want_entropy:
         hist = torch.zeros(256, dtype=torch.int64, device=x.device)
-        L.check(lib.cnnq_hist_replicas_fold(_ptr(hist_rep), _ptr(hist), st), 'cnnq_hist_replicas_fold')
+        L.check(L.load().cnnq_hist_replicas_fold(_ptr(hist_rep), _ptr(hist), st), 'cnnq_hist_replicas_fold')
         D.all_reduce_sum_(hist, group)                       # the global batch's code counts
-        res.append(entropy_from_hist(hist))
+        entropy = entropy_from_hist(hist)
     if want_parts:
         tab = ws[:4 * (L.NQP + 2) * C].view(torch.float32).view(L.NQP + 2, C).clone()    # qp rows, then the global {min, max}
-        stats = torch.zeros((L.NSTAT, C), dtype=torch.float32, device=x.device)
-        stats[L.STAT_MIN] = tab[L.NQP]
-        stats[L.STAT_MAX] = tab[L.NQP + 1]
-        res.append(dict(stats=stats, qp=tab[:L.NQP], diag=None))
-    return res[0] if len(res) == 1 else tuple(res)
+        parts = _minmax_parts(tab[L.NQP:], tab[:L.NQP])
+    return _result(y, codes, entropy, parts)
 
 
 def _minmax_qdq_collective(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group, world, resident):
@@ -1086,12 +1013,10 @@ def _minmax_qdq_collective(x, N, C, HW, num_bits, positive, want_codes, want_ent
             # everything that does not change from call to call: workspace slices, the gathered buffer, the direct
             # RCCL communicator (created collectively at first use).  The plan keeps `group` alive, so its id stays its
             # own, and its scratch buffers too (a later, larger tensor may make _scratch hand out new ones).
-            ws = _scratch(x, 'cfg2', _cfg2_workspace_bytes(lib, N, C, HW), st)
+            ws = _scratch(x, 'cfg2', _ws_bytes('cfg2', N, C, HW), st)
             gbuf = _scratch(x, 'gath', 8 * C * world, st)
-            dc = None
-            if x.is_cuda:
-                from . import rccl
-                dc = rccl.direct_comm(group)
+            from . import rccl
+            dc = rccl.direct_comm(group)
             plan = _XPLAN[key] = dict(
                 group=group, ws=ws, gbuf=gbuf, base=ws.data_ptr(), dc=dc,
                 local=ws[12 * C:20 * C].view(torch.float32).view(2, C),            # the mm[2][C] slot of the workspace
@@ -1099,8 +1024,7 @@ def _minmax_qdq_collective(x, N, C, HW, num_bits, positive, want_codes, want_ent
         base = plan['base']
         y = _out_like(x, out)
         gws = _group_workspace(x, st) if resident else None      # one launch for the local extrema when the plan allows
-        rc = lib.cnnq_pc_minmax_local_auto(x.data_ptr(), N, C, HW, base + 20 * C, gws,
-                                           GROUP_WS_BYTES if gws is not None else 0, base + 12 * C, st)
+        rc = lib.cnnq_pc_minmax_local_auto(x.data_ptr(), N, C, HW, base + 20 * C, *_gws_args(gws), base + 12 * C, st)
         if rc:
             L.check(rc, 'cnnq_pc_minmax_local_auto')
         dc = plan['dc']
@@ -1114,14 +1038,7 @@ def _minmax_qdq_collective(x, N, C, HW, num_bits, positive, want_codes, want_ent
         if rc:
             L.check(rc, 'cnnq_pc_gathered_qdq')
         return y
-    y = _out_like(x, out)
-    G = max(lib.cnnq_pc_groups(N, C, HW, 1), lib.cnnq_pc_groups(N, C, HW, 0))
-    if G <= 0:
-        L.check(G, 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
-    pmm = torch.empty((G, 2, C), dtype=torch.float32, device=x.device)
-    qp = torch.empty((L.NQP, C), dtype=torch.float32, device=x.device)
-    codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device) if want_codes else None
-    hist = torch.zeros(256, dtype=torch.int64, device=x.device) if want_entropy else None
+    y, pmm, qp, codes, hist = _chain_buffers(x, N, C, HW, out, want_codes, want_entropy)
     g_used = lib.cnnq_pc_groups(N, C, HW, int(x.data_ptr() % 16 == 0))
     L.check(lib.cnnq_pc_minmax(_ptr(x), N, C, HW, _ptr(pmm), _stream(x)), 'cnnq_pc_minmax')
     local = torch.empty((2, C), dtype=torch.float32, device=x.device)
@@ -1133,17 +1050,8 @@ def _minmax_qdq_collective(x, N, C, HW, num_bits, positive, want_codes, want_ent
             'cnnq_pc_qdq')
     if want_entropy:
         D.all_reduce_sum_(hist, group)
-    res = [y]
-    if want_codes:
-        res.append(codes)
-    if want_entropy:
-        res.append(entropy_from_hist(hist))
-    if want_parts:
-        stats = torch.zeros((L.NSTAT, C), dtype=torch.float32, device=x.device)
-        stats[L.STAT_MIN] = pmm[:world, 0].min(dim=0)[0]
-        stats[L.STAT_MAX] = pmm[:world, 1].max(dim=0)[0]
-        res.append(dict(stats=stats, qp=qp, diag=None))
-    return res[0] if len(res) == 1 else tuple(res)
+    return _result(y, codes, entropy_from_hist(hist) if want_entropy else None,
+                   _minmax_parts(pmm, qp, world) if want_parts else None)
 
 
 def _slice_ptr(t, c0, HW):
@@ -1159,15 +1067,13 @@ def minmax_qdq_channel_slice(x, c0, c1, num_bits, positive=False, out=None):
     the parent (no slice copy): e.g. the branches of a concatenated output, each with its own quantizer
     settings.  Returns `out` (default: a new tensor shaped like x; only the slice is written)."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     N, C, HW = geometry(x)
     if not 0 <= c0 < c1 <= C:
         raise L.CnnqError('bad channel slice [%d, %d) of %d' % (c0, c1, C))
     y = _out_like(x, out)
     Cs, stride = c1 - c0, C * HW
-    G = lib.cnnq_pc_groups(N, Cs, HW, _slice_aligned(x, c0, HW, stride))
-    if G <= 0:
-        L.check(G, 'cnnq_pc_groups(%d,%d,%d)' % (N, Cs, HW))
+    G = _groups(N, Cs, HW, _slice_aligned(x, c0, HW, stride))
     pmm = torch.empty((G, 2, Cs), dtype=torch.float32, device=x.device)
     qp = torch.empty((L.NQP, Cs), dtype=torch.float32, device=x.device)
     st = _stream(x)
@@ -1182,7 +1088,7 @@ def minmax_qdq_channel_slice(x, c0, c1, num_bits, positive=False, out=None):
 def quantize_pack4(x, qp):
     """x [N, C, H, W] + parameter table -> packed int4 codes (uint8, numel/2 bytes, two codes per byte)."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     N, C, HW = geometry(x)
     packed = torch.empty(x.numel() // 2, dtype=torch.uint8, device=x.device)
     L.check(lib.cnnq_pc_quantize_pack4(_ptr(x), _ptr(packed), N, C, HW, _ptr(qp), _stream(x)), 'cnnq_pc_quantize_pack4')
@@ -1203,7 +1109,7 @@ def quantize_u8(x, qp):
     """x [N, C, H, W] + parameter table -> uint8 codes (one byte each, numel bytes): the stored format for
     quantizations of up to 8 bits."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     N, C, HW = geometry(x)
     codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     L.check(lib.cnnq_pc_quantize_u8(_ptr(x), _ptr(codes), N, C, HW, _ptr(qp), _stream(x)), 'cnnq_pc_quantize_u8')
@@ -1249,7 +1155,7 @@ def quantize_packed(x, qp, bits, out=None, form=0, rowoff=None):
     general kernel, 2 = the lean kernel (cnnq_pc_quantize_packed_form); every form writes the same bytes.  rowoff: the
     layout of packed_layout(bits, H * W) when the caller already has it (one launch less)."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     N, C, HW = geometry(x)
     bits = bits.contiguous()
     if rowoff is None:
@@ -1313,7 +1219,7 @@ def pt_qdq(x, ptp, noise=None, out=None):
     x = _dev_act(x, 'x') if noise is not None else _dev_act_layout(x, 'x')
     y = _out_like(x, out)
     if noise is not None:
-        noise = _dev_f32(noise, 'noise')
+        noise = _dev(noise, 'noise')
     if x.numel() == 0:
         return y
     if x.dtype != torch.float32:
@@ -1340,7 +1246,7 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
     use_ba = bool(bit_alloc) and num_bits <= 4 and not whole_tensor
     # config 2, dynamic on one GPU or from a statistics table, keeps a dense channels_last x as it is
     nhwc = (per_channel_dim == 1 and not whole_tensor and clip == 'no' and not use_ba and bcorr is None
-            and not (want_codes or want_entropy or want_parts) and (stats is not None or _one_process(group)))
+            and not (want_codes or want_entropy or want_parts) and (stats is not None or not _sharded(group)))
     x = _dev_act_layout(x, 'x') if nhwc else _dev_act(x, 'x')
     N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x, per_channel_dim)
     if _is_nhwc(x):
@@ -1357,7 +1263,6 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
             return minmax_qdq_fused(x, N, C, HW, num_bits, positive, out=out, group=group, _checked=True)
         qp, _ = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, direct_range=whole_tensor)
         return pc_qdq(x, N, C, HW, qp, out=out)
-    world = 1 if group is False else D.world_size(group)
     if bcorr is not None and (want_codes or want_entropy or want_parts or whole_tensor or per_channel_dim != 1):
         raise L.CnnqError('bcorr combines only with the plain per-channel activation Q/DQ')
     if stats is None and clip == 'no' and not use_ba and not whole_tensor:
@@ -1368,11 +1273,11 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
         return res
     # Laplace clipping with dynamic statistics on one GPU: pass B, the parameters and the Q/DQ in ONE launch that reads
     # x once (cnnq_pc_aciq_qdq_single: 12 instead of 16 bytes per element) when the shape has a single-launch plan
-    exchanging = group is not False and (world > 1 or D.forced_exchange())     # x is this rank's shard of the batch
+    exchanging = _sharded(group)
     single = (_ACIQ_SINGLE and _RESIDENT and stats is None and bcorr is None and clip == 'laplace'
               and not whole_tensor and not (use_ba and prior_is_b) and num_bits <= 8)
     if single and exchanging and not (want_codes or want_entropy):
-        # sharded: the ranks' sums meet inside the single launch (round 6); None: no in-launch exchange for this group - the chain
+        # sharded: the ranks' sums meet inside the single launch; None: no in-launch exchange for this group - the chain
         cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, whole_tensor)
         res = _aciq_qdq_xrank(x, N, C, HW, cfg, group, want_parts, out)
         if res is not None:
@@ -1385,11 +1290,7 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
         lib = L.load()
         cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, whole_tensor)
         y = _out_like(x, out)
-        al = int(x.data_ptr() % 16 == 0)
-        key = ('aciq', N, C, HW, al)
-        nbytes = _WS_BYTES.get(key)
-        if nbytes is None:
-            nbytes = _WS_BYTES[key] = (lib.cnnq_pc_aciq_workspace(N, C, HW, al) + 15) // 16 * 16
+        nbytes = _ws_bytes('aciq', N, C, HW, int(x.data_ptr() % 16 == 0))
         st = _raw_stream(x.device.index)
         base = _scratch(x, 'aciq', nbytes + (L.NQP + L.NDIAG) * C * 4, st).data_ptr()
         qd = base + nbytes
@@ -1416,15 +1317,14 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
     if bcorr is not None:
         return qdq_bias_corrected(x, N, C, HW, qp, bool(bcorr), group=None if group is False else group, out=out)
     hist = torch.zeros(256, dtype=torch.int64, device=x.device) if want_entropy else None
-    res = pc_qdq(x, N, C, HW, qp, want_codes, out=out, hist=hist)
-    out = list(res) if want_codes else [res]
+    y = pc_qdq(x, N, C, HW, qp, want_codes, out=out, hist=hist)
+    y, codes = y if want_codes else (y, None)
+    entropy = None
     if want_entropy:
-        if D.world_size(None if group is False else group) > 1 and group is not False:
+        if group is not False and D.world_size(group) > 1:
             D.all_reduce_sum_(hist, group)
-        out.append(entropy_from_hist(hist))
-    if want_parts:
-        out.append(dict(stats=stats, qp=qp, diag=diag))
-    return out[0] if len(out) == 1 else tuple(out)
+        entropy = entropy_from_hist(hist)
+    return _result(y, codes, entropy, dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
 
 
 def weight_correction(w, w_q, vcorr=False, bcorr=False):
@@ -1433,8 +1333,8 @@ def weight_correction(w, w_q, vcorr=False, bcorr=False):
     if not (vcorr or bcorr):
         return w_q
     lib = L.load()
-    w = _dev_f32(w, 'w')
-    out = _dev_f32(w_q, 'w_q').clone()
+    w = _dev(w, 'w')
+    out = _dev(w_q, 'w_q').clone()
     C, HW = w.shape[0], w.numel() // w.shape[0]
     st_w, _ = pc_stats(w, 1, C, HW, local_only=True)
     st_q, _ = pc_stats(out, 1, C, HW, local_only=True)
@@ -1447,21 +1347,15 @@ def act_bias_correction_(out, out_q, relu_first, group=None):
     """Activation bias correction (iqm.py:180-196), IN PLACE on out_q; `out` is the unquantized
     activation.  With world size > 1 the per-channel sums are exchanged so the bias is global."""
     lib = L.load()
-    x = _dev_f32(out, 'out')
+    x = _dev(out, 'out')
     if not (isinstance(out_q, torch.Tensor) and out_q.is_cuda and out_q.is_contiguous() and out_q.dtype == torch.float32):
         raise L.CnnqError('out_q must be a contiguous float32 device tensor')
     N, C, HW = geometry(x)
-    G = lib.cnnq_pc_groups(N, C, HW, int(x.data_ptr() % 16 == 0 and out_q.data_ptr() % 16 == 0))
+    G = _groups(N, C, HW, x.data_ptr() % 16 == 0 and out_q.data_ptr() % 16 == 0)
     part3 = torch.empty((G, 3, C), dtype=torch.float64, device=x.device)
     L.check(lib.cnnq_pc_bcorr_sums(_ptr(x), _ptr(out_q), N, C, HW, int(bool(relu_first)), _ptr(part3), _stream(x)),
             'cnnq_pc_bcorr_sums')
-    bias = torch.empty(C, dtype=torch.float32, device=x.device)
-    if D.world_size(group) > 1:
-        sums = torch.empty((3, C), dtype=torch.float64, device=x.device)
-        L.check(lib.cnnq_pc_bcorr_bias(_ptr(part3), G, C, _ptr(sums), None, _stream(x)), 'cnnq_pc_bcorr_bias')
-        part3 = D.all_gather_records(sums, group)
-        G = part3.shape[0]
-    L.check(lib.cnnq_pc_bcorr_bias(_ptr(part3), G, C, None, _ptr(bias), _stream(x)), 'cnnq_pc_bcorr_bias')
+    bias = _bcorr_bias(x, part3, group)
     L.check(lib.cnnq_pc_bcorr_apply(_ptr(out_q), N, C, HW, _ptr(bias), _stream(x)), 'cnnq_pc_bcorr_apply')
     return out_q
 
@@ -1472,14 +1366,21 @@ def qdq_bias_corrected(x, N, C, HW, qp, relu_first, group=None, out=None):
     value is recomputed on the fly) and one fused quantize+correct pass - 12 B/elem instead of 24, the
     same floats as pc_qdq + act_bias_correction_."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     y = _out_like(x, out)
-    G = lib.cnnq_pc_groups(N, C, HW, int(x.data_ptr() % 16 == 0))
-    if G <= 0:
-        L.check(G, 'cnnq_pc_groups(%d,%d,%d)' % (N, C, HW))
+    G = _groups(N, C, HW, x.data_ptr() % 16 == 0)
     part3 = torch.empty((G, 3, C), dtype=torch.float64, device=x.device)
     L.check(lib.cnnq_pc_qdq_bcorr_sums(_ptr(x), N, C, HW, _ptr(qp), int(bool(relu_first)), _ptr(part3), _stream(x)),
             'cnnq_pc_qdq_bcorr_sums')
+    bias = _bcorr_bias(x, part3, group)
+    L.check(lib.cnnq_pc_qdq_bcorr(_ptr(x), _ptr(y), N, C, HW, _ptr(qp), _ptr(bias), 1, _stream(x)), 'cnnq_pc_qdq_bcorr')
+    return y
+
+
+def _bcorr_bias(x, part3, group):
+    """The correction's bias from the [G, 3, C] partial sums; with world size > 1 those of the global batch (an all_gather)."""
+    lib = L.load()
+    G, _, C = part3.shape
     bias = torch.empty(C, dtype=torch.float32, device=x.device)
     if D.world_size(group) > 1:
         sums = torch.empty((3, C), dtype=torch.float64, device=x.device)
@@ -1487,8 +1388,7 @@ def qdq_bias_corrected(x, N, C, HW, qp, relu_first, group=None, out=None):
         part3 = D.all_gather_records(sums, group)
         G = part3.shape[0]
     L.check(lib.cnnq_pc_bcorr_bias(_ptr(part3), G, C, None, _ptr(bias), _stream(x)), 'cnnq_pc_bcorr_bias')
-    L.check(lib.cnnq_pc_qdq_bcorr(_ptr(x), _ptr(y), N, C, HW, _ptr(qp), _ptr(bias), 1, _stream(x)), 'cnnq_pc_qdq_bcorr')
-    return y
+    return bias
 
 
 _MT_TABLES = {}
@@ -1509,25 +1409,24 @@ def mid_tread_qdq(x, target, clip, sym, per_channel_dim=1, whole_tensor=False, g
     cnnq_pc_midtread_params -> cnnq_pc_midtread_qdq (+ histogram -> entropy).  Returns
     (y, entropy or None [, codes] [, parts])."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x, per_channel_dim)
-    local = group is False
-    grp = None if local else group
+    grp = None if group is False else group
     tabs = _midtread_tables(x.device)
-    exchanging = not local and (D.world_size(grp) > 1 or D.forced_exchange())
-    if _ACIQ_SINGLE and _RESIDENT and clip and not whole_tensor and per_channel_dim == 1 and not want_codes and exchanging:
-        # sharded: pass A through the collective, the ranks' sums of |x - mean| inside the single launch (round 6)
+    single = _ACIQ_SINGLE and _RESIDENT and clip and not whole_tensor and per_channel_dim == 1 and not want_codes
+    exchanging = _sharded(group)
+    if single and exchanging:
+        # sharded: pass A through the collective, the ranks' sums of |x - mean| inside the single launch
         res = _mid_tread_qdq_xrank(x, N, C, HW, target, sym, tabs, grp, want_entropy, want_parts)
         if res is not None:
             return res
-    if (_ACIQ_SINGLE and _RESIDENT and clip and not whole_tensor and per_channel_dim == 1 and not want_codes
-            and not exchanging):
+    if single and not exchanging:
         # pass B, the step sizes / clamp bounds and the quantization in ONE launch that reads x once
         # (cnnq_pc_midtread_qdq_single: 12 instead of 16 bytes per element) when the shape has a single-launch plan
         res = mid_tread_qdq_single(x, N, C, HW, target, sym, tabs, want_entropy, want_parts)
         if res is not None:
             return res
-    stats, mom = pc_stats(x, N, C, HW, need_b=bool(clip), group=grp, local_only=local)
+    stats, mom = pc_stats(x, N, C, HW, need_b=bool(clip), group=grp, local_only=group is False)
     mt = torch.empty((L.NMT, C), dtype=torch.float32, device=x.device)
     L.check(lib.cnnq_pc_midtread_params(_ptr(stats), C, float(target), int(bool(clip)), int(bool(sym)), _ptr(tabs),
                                         tabs.shape[1], _ptr(mt), _stream(x)), 'cnnq_pc_midtread_params')
@@ -1536,24 +1435,9 @@ def mid_tread_qdq(x, target, clip, sym, per_channel_dim=1, whole_tensor=False, g
     hist = torch.zeros(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None
     L.check(lib.cnnq_pc_midtread_qdq(_ptr(x), _ptr(y), N, C, HW, _ptr(mt), int(bool(clip)), _ptr(codes), _ptr(hist),
                                      _stream(x)), 'cnnq_pc_midtread_qdq')
-    entropy = None
-    if want_entropy:
-        world = 1 if local else D.world_size(grp)
-        if world > 1:
-            D.all_reduce_sum_(hist, grp)
-        ent = torch.empty(1, dtype=torch.float32, device=x.device)
-        if world > 1:       # the global batch's element count from the merged moment record (shards may differ by a sample)
-            L.check(lib.cnnq_midtread_entropy_count(_ptr(hist), _ptr(mt), C, mom[L.MOM_COUNT].data_ptr(), _ptr(ent), _stream(x)),
-                    'cnnq_midtread_entropy')
-        else:
-            L.check(lib.cnnq_midtread_entropy(_ptr(hist), _ptr(mt), C, x.numel(), _ptr(ent), _stream(x)), 'cnnq_midtread_entropy')
-        entropy = ent[0]
-    res = [y, entropy]
-    if want_codes:
-        res.append(codes)
-    if want_parts:
-        res.append(dict(stats=stats, mt=mt, hist=hist))
-    return tuple(res)
+    multi = want_entropy and group is not False and D.world_size(grp) > 1      # (a 1-rank forced exchange issues no collective)
+    entropy = _mt_entropy(x, hist, mt, C, _raw_stream(x.device.index), grp, mom if multi else None) if want_entropy else None
+    return _mt_result(y, entropy, codes, dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
 
 
 def mid_tread_qdq_single(x, N, C, HW, target, sym, tabs, want_entropy=False, want_parts=False, flags=0):
@@ -1564,11 +1448,7 @@ def mid_tread_qdq_single(x, N, C, HW, target, sym, tabs, want_entropy=False, wan
     gws = _group_workspace(x, st)
     if gws is None:
         return None
-    al = int(x.data_ptr() % 16 == 0)
-    key = ('aciq', N, C, HW, al)
-    nbytes = _WS_BYTES.get(key)
-    if nbytes is None:
-        nbytes = _WS_BYTES[key] = (lib.cnnq_pc_aciq_workspace(N, C, HW, al) + 15) // 16 * 16
+    nbytes = _ws_bytes('aciq', N, C, HW, int(x.data_ptr() % 16 == 0))
     ws = _scratch(x, 'aciq', nbytes + (L.NQP + L.NDIAG) * C * 4, st)
     y = torch.empty_like(x)
     tabs_out = torch.empty((L.NSTAT + L.NMT, C), dtype=torch.float32, device=x.device)
@@ -1576,21 +1456,29 @@ def mid_tread_qdq_single(x, N, C, HW, target, sym, tabs, want_entropy=False, wan
     hist = torch.empty(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None     # zeroed by the call
     rc = lib.cnnq_pc_midtread_qdq_single(_ptr(x), _ptr(y), N, C, HW, float(target), int(bool(sym)), _ptr(tabs), tabs.shape[1],
                                          ws.data_ptr(), gws, GROUP_WS_BYTES, _ptr(stats), _ptr(mt), _ptr(hist), int(flags), st)
-    if rc == L.ENOTSUP:
+    if not _supported(rc, 'cnnq_pc_midtread_qdq_single'):
         return None
-    L.check(rc, 'cnnq_pc_midtread_qdq_single')
     entropy = None
     if want_entropy:
         if _ENT_BATCH is not None:
             entropy = _ENT_BATCH.add_midtread(hist, mt, C, x.numel(), x.device)      # one launch for the whole block, at its end
         else:
-            ent = torch.empty(1, dtype=torch.float32, device=x.device)
-            L.check(lib.cnnq_midtread_entropy(_ptr(hist), _ptr(mt), C, x.numel(), _ptr(ent), st), 'cnnq_midtread_entropy')
-            entropy = ent[0]
-    res = [y, entropy]
-    if want_parts:
-        res.append(dict(stats=stats, mt=mt, hist=hist))
-    return tuple(res)
+            entropy = _mt_entropy(x, hist, mt, C, st)
+    return _mt_result(y, entropy, parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
+
+
+def _mt_entropy(x, hist, mt, C, st, group=None, mom=None):
+    """The entropy of a mid-tread code histogram of x.  With the merged moment record `mom` x is a batch shard: the ranks'
+    counts are summed over `group` first, and the element count is the global batch's (shards may differ by a sample)."""
+    lib = L.load()
+    ent = torch.empty(1, dtype=torch.float32, device=x.device)
+    if mom is not None:
+        D.all_reduce_sum_(hist, group)
+        rc = lib.cnnq_midtread_entropy_count(_ptr(hist), _ptr(mt), C, mom[L.MOM_COUNT].data_ptr(), _ptr(ent), st)
+    else:
+        rc = lib.cnnq_midtread_entropy(_ptr(hist), _ptr(mt), C, x.numel(), _ptr(ent), st)
+    L.check(rc, 'cnnq_midtread_entropy')
+    return ent[0]
 
 
 def tensor_row_stats(x, rows):
@@ -1602,23 +1490,17 @@ def tensor_row_stats(x, rows):
     per_sample = isinstance(x, torch.Tensor) and x.dim() == 4 and rows in (1, x.shape[0])
     x = _dev_act_layout(x, 'x') if per_sample else _dev_act(x, 'x')
     hw = x.numel() // rows
-    if x.dtype != torch.float32:
-        G = max(lib.cnnq_pc_groups(1, rows, hw, 1), lib.cnnq_pc_groups(1, rows, hw, 0))
-        if G <= 0:
-            L.check(G, 'cnnq_pc_groups(1,%d,%d)' % (rows, hw))
-        pmm = torch.empty((G, 2, rows), dtype=torch.float32, device=x.device)
-        table = torch.empty((2, rows), dtype=torch.float32, device=x.device)
-        L.check(lib.cnnq_pc_minmax_local_dt(_ptr(x), _HALF_DTYPES[x.dtype], 1, rows, hw, _ptr(pmm), _ptr(table), _stream(x)),
-                'cnnq_pc_minmax_local_dt')
-        return table
-    G = lib.cnnq_pc_groups(1, rows, hw, int(x.data_ptr() % 16 == 0))
-    if G <= 0:
-        L.check(G, 'cnnq_pc_groups(1,%d,%d)' % (rows, hw))
+    half = x.dtype != torch.float32
+    G = _groups(1, rows, hw, None if half else x.data_ptr() % 16 == 0)
     pmm = torch.empty((G, 2, rows), dtype=torch.float32, device=x.device)
-    L.check(lib.cnnq_pc_minmax(_ptr(x), 1, rows, hw, _ptr(pmm), _stream(x)), 'cnnq_pc_minmax')
     # rows MIN (0) and MAX (1) of a stats table with stride `rows`: what cnnq_pt_setup reads
     table = torch.empty((2, rows), dtype=torch.float32, device=x.device)
-    L.check(lib.cnnq_pc_minmax_reduce(_ptr(pmm), G, rows, _ptr(table), _stream(x)), 'cnnq_pc_minmax_reduce')
+    if half:
+        L.check(lib.cnnq_pc_minmax_local_dt(_ptr(x), _HALF_DTYPES[x.dtype], 1, rows, hw, _ptr(pmm), _ptr(table), _stream(x)),
+                'cnnq_pc_minmax_local_dt')
+    else:
+        L.check(lib.cnnq_pc_minmax(_ptr(x), 1, rows, hw, _ptr(pmm), _stream(x)), 'cnnq_pc_minmax')
+        L.check(lib.cnnq_pc_minmax_reduce(_ptr(pmm), G, rows, _ptr(table), _stream(x)), 'cnnq_pc_minmax_reduce')
     return table
 
 
@@ -1641,10 +1523,8 @@ def minmax_qdq_per_tensor(x, num_bits, avg_over_batch, zero_min=False, int_exp=F
             rc = L.load().cnnq_pt_minmax_qdq_fused(x.data_ptr(), y.data_ptr(), x.numel(), rows, 0 if avg_over_batch else 1,
                                                    int(bool(zero_min)), int(num_bits), int(bool(int_exp)),
                                                    int(bool(enforce_true_zero)), gws, GROUP_WS_BYTES, None, st)
-            if rc == 0:
+            if _supported(rc, 'cnnq_pt_minmax_qdq_fused'):
                 return y
-            if rc != L.ENOTSUP:
-                L.check(rc, 'cnnq_pt_minmax_qdq_fused')
     stats = tensor_row_stats(x, rows)
     if D.world_size(group) > 1:
         stats = D.merge_row_minmax(stats, rows, avg_over_batch, group)
@@ -1660,7 +1540,7 @@ def kld_thresholds(x, rows=None, want_parts=False):
     {optimal clipping threshold, its KL divergence, candidate index}; the `kld_th` statistic of
     the batch is out[:, 0].max().  want_parts adds (hist [rows, 2001] int32, div [rows, 994])."""
     lib = L.load()
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     rows = int(rows if rows is not None else (x.shape[0] if x.dim() > 1 else 1))
     length = x.numel() // rows
     rowmm = tensor_row_stats(x, rows)
@@ -1677,7 +1557,7 @@ def kld_thresholds(x, rows=None, want_parts=False):
 def row_sumsq(x, rows=None):
     """Per-sample sum of squares, the runtime distance measure of distance_stats.py:22-33
     (`torch.sum(t**2, dim=-1)` on [N, -1]): the moments kernel with N = 1, C = rows (fp64 sums)."""
-    x = _dev_f32(x, 'x')
+    x = _dev(x, 'x')
     rows = int(rows if rows is not None else x.shape[0])
     _, mom = pc_stats(x, 1, rows, x.numel() // rows, local_only=True)
     return mom[L.MOM_SUMSQ].to(torch.float32)
