@@ -56,6 +56,8 @@ SIGNATURES = {
     'cnnq_pc_stats_auto': (_I, [_P, _L, _L, _L, _I, _I, _I, _P, _P, ctypes.c_size_t, _P, _P, _P]),
     'cnnq_pc_stats_route': (_I, [_L, _L, _L, _I, ctypes.c_size_t, ctypes.c_uint32]),
     'cnnq_pc_params': (_I, [_P, _L, ctypes.POINTER(ParamsCfg), _P, _P, _P]),
+    'cnnq_pc_qerr_workspace': (ctypes.c_size_t, [_L, _L, _L, _I]),
+    'cnnq_pc_qerr': (_I, [_P, _L, _L, _L, _P, _I, _P, _P, _P, _P]),
     'cnnq_pc_qdq': (_I, [_P, _P, _L, _L, _L, _P, _P, _P, _I, _P]),
     'cnnq_pc_quantize_pack4': (_I, [_P, _P, _L, _L, _L, _P, _P]),
     'cnnq_pc_dequantize_pack4': (_I, [_P, _P, _L, _L, _L, _P, _P]),

@@ -46,6 +46,7 @@
 #include "cnnq_kld.hip.h"
 #include "cnnq_half.hip.h"
 #include "cnnq_nhwc.hip.h"
+#include "cnnq_qerr.hip.h"
 
 extern "C" {
 
@@ -248,6 +249,67 @@ int cnnq_pc_params(const float* stats, int64_t C, const cnnq_params_cfg* cfg, fl
     const int threads = (int)(C >= PTPB ? PTPB : ((C + 63) / 64) * 64);
     hipLaunchKernelGGL(k_params, dim3(1), dim3(threads), 0, (hipStream_t)stream, stats, (int)C, *cfg, qp, diag,
                        bits_ws);
+    return launch_status();
+}
+
+// Per-channel error columns of K candidate parameter tables (cnnq_qerr.hip.h): k_qerr -> k_qerr_fold.  The load shape is the
+// plan's with at most two loads per lane and sample: the pass is bound by instruction issue, and its LDS tile (one fp32 entry
+// per load slot and sum) has to leave room for several workgroups per CU.
+static int qerr_plan(int64_t N, int64_t C, int64_t HW, bool aligned16, Variant* v, Geo* g) {
+    if (N < 1 || C < 1 || HW < 1) return CNNQ_EINVAL;
+    choose_variant(N, C, HW, aligned16, v);
+    if (v->J > 2) v->J = 2;
+    return make_geo(N, C, HW, *v, 0, C, /*max_groups=*/0, 0, 0, g);
+}
+static size_t qerr_records(int64_t N, int64_t C, int64_t HW, bool aligned16, int K) {
+    Variant v;
+    Geo g;
+    if (qerr_plan(N, C, HW, aligned16, &v, &g) != 0) return 0;
+    return (size_t)N * (size_t)(g.mode == 1 ? g.nb : 1) * (size_t)QE_NV(K) * (size_t)C;
+}
+
+size_t cnnq_pc_qerr_workspace(int64_t N, int64_t C, int64_t HW, int K) {
+    if (K < 1 || K > 3) return 0;
+    const size_t a = qerr_records(N, C, HW, true, K), u = qerr_records(N, C, HW, false, K);
+    if (a == 0 || u == 0) return 0;
+    return (a > u ? a : u) * sizeof(double);
+}
+
+int cnnq_pc_qerr(const float* x, int64_t N, int64_t C, int64_t HW, const float* qp, int K, const float* mm, void* ws, float* err,
+                 void* stream) {
+    if (!x || !qp || !ws || !err || K < 1 || K > 3 || N < 1 || C < 1 || HW < 1 || ((uintptr_t)ws & 7)) return CNNQ_EINVAL;
+    Variant v;
+    Geo g;
+    const int rc = qerr_plan(N, C, HW, al16(x), &v, &g);
+    if (rc) return rc;
+    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
+    hipStream_t st = (hipStream_t)stream;
+    double* rec = reinterpret_cast<double*>(ws);
+#define LAUNCH_QE_K(VEC, A, J, KK)                                                                                  \
+    do {                                                                                                            \
+        if (mm) hipLaunchKernelGGL((k_qerr<VEC, A, J, KK, true>), grid, block, 0, st, x, g, qp, mm, rec);     \
+        else hipLaunchKernelGGL((k_qerr<VEC, A, J, KK, false>), grid, block, 0, st, x, g, qp, mm, rec);       \
+    } while (0)
+#define LAUNCH_QE(VEC, A, J)                        \
+    do {                                            \
+        if (K == 1) LAUNCH_QE_K(VEC, A, J, 1);      \
+        else if (K == 2) LAUNCH_QE_K(VEC, A, J, 2); \
+        else LAUNCH_QE_K(VEC, A, J, 3);             \
+    } while (0)
+    if (v.vec == 4 && v.A == 1) {
+        if (v.J == 2) LAUNCH_QE(4, 1, 2);
+        else LAUNCH_QE(4, 1, 1);
+    } else if (v.vec == 4) LAUNCH_QE(4, 4, 1);
+    else LAUNCH_QE(1, 1, 2);
+#undef LAUNCH_QE
+#undef LAUNCH_QE_K
+    const int rc2 = launch_status();
+    if (rc2) return rc2;
+    const int nb = g.mode == 1 ? g.nb : 1;
+    const dim3 fgrid((unsigned)((C + QF_CH - 1) / QF_CH));
+    if (K == 1) hipLaunchKernelGGL((k_qerr_fold<1>), fgrid, block, 0, st, rec, (int)N, nb, (int)C, (int)HW, err);
+    else if (K == 2) hipLaunchKernelGGL((k_qerr_fold<2>), fgrid, block, 0, st, rec, (int)N, nb, (int)C, (int)HW, err);
+    else hipLaunchKernelGGL((k_qerr_fold<3>), fgrid, block, 0, st, rec, (int)N, nb, (int)C, (int)HW, err);
     return launch_status();
 }
 

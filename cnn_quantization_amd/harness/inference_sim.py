@@ -53,6 +53,9 @@ def build_parser():
     p.add_argument('--stats_kind', '-sk', default='mean')
     p.add_argument('--stats_folder', '-sf', default=None)
     p.add_argument('--stats_batch_avg', '-sba', action='store_true')
+    p.add_argument('--collect_err', '-ce', action='store_true',
+                   help='with -sm collect -pcq_a: also record the per-channel clipping-error columns (mse_* / cos_* of the '
+                        'laplace, gaus and min/max candidates) that -sm use -c mix compares')
     p.add_argument('--kld_threshold', '-kld', action='store_true')
     p.add_argument('--measure_stats', '-ms', action='store_true')
     p.add_argument('--per_channel_quant_weights', '-pcq_w', action='store_true')
@@ -275,7 +278,12 @@ def run(args, quiet=False):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.collect_err and not (args.stats_mode == 'collect' and args.per_channel_quant_act and args.qtype is not None
+                                 and not args.sharded):
+        parser.error('--collect_err / -ce needs -sm collect -pcq_a and a --qtype (the error columns belong to the per-channel '
+                     'statistics file and to the activation quantizer; not with --sharded)')
     if not torch.cuda.is_available():
         raise SystemExit('the harness needs an MI355X (there is no CPU path)')
     return run(args)

@@ -91,6 +91,9 @@ def _route(layer, out, out_id, tag, *, shifted=False, half_range=False, collect_
         return out
     if qm.stats_mode is StatsMode.collect_stats:
         kw = dict(force_global_min_max=True) if force_global else {}
+        if isinstance(qm.stats_manager, StatisticManagerPerChannel) and qm.stats_manager.collect_err:
+            # the error columns measure the candidates of the quantizer that `-sm use` will run on this output
+            kw.update(half_range=half_range, err_settings=qm.err_settings(out_id, '' if shifted else tag, half_range))
         upcast_fallback(qm.stats_manager.save_tensor_stats, out, tag if collect_tag is None else collect_tag, out_id, **kw)
         return out
     stat_id = out_id if qm.stats_mode is StatsMode.use_stats else None
@@ -329,6 +332,7 @@ class QuantizationManagerInference(metaclass=Singleton):
             self.stats_mode = StatsMode.collect_stats
             if args.per_channel_quant_act:
                 self.stats_manager = StatisticManagerPerChannel(sf, load_stats=False, batch_avg=args.stats_batch_avg,
+                                                                collect_err=bool(getattr(args, 'collect_err', False)),
                                                                 group=group)
             else:
                 self.stats_manager = StatisticManager(sf, load_stats=False, batch_avg=args.stats_batch_avg,
@@ -386,6 +390,17 @@ class QuantizationManagerInference(metaclass=Singleton):
 
     def set_8bit_list(self, ignore_ids):
         self.op_manager.set_8bit_list(ignore_ids)
+
+    def err_settings(self, stat_id, tag, half_range):
+        """The ops.mix_candidates arguments of the quantizer that quantize_instant picks for (stat_id, tag) under `-sm use`
+        (iq.py:310-359 reads them from the quantizer): what collect_err needs besides the statistics table."""
+        om = self.op_manager
+        q = om.get_quantizer('ignored' if any(l == stat_id for l in om.ignore_ids) else tag)
+        # bit_alloc as the consumer passes it (IntQuantizer._clipping_mix: bit_alloc_act and pc; the per-channel manager only
+        # records tensors for which pc is pcq_a)
+        return dict(num_bits=q.num_bits, positive=bool(q.force_positive or half_range),
+                    bit_alloc=bool(q.bit_alloc_act and q.pcq_a), prior_is_b=q.bit_alloc_prior != 'gaus',
+                    target=q.bit_alloc_target_act, round_mode=q.bit_alloc_round)
 
     def reset_counters(self):
         ReLUWithId._id = count(0)

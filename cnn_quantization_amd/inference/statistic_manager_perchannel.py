@@ -8,7 +8,17 @@ files written by either implementation are interchangeable.
 The seven statistics of one batch come from two coalesced passes over the activation on the
 device (cnnq_pc_moments + cnnq_pc_absdev) and ONE device->host copy of a [7, C] table, instead
 of a transposed copy, nine full-tensor reductions and seven synchronising copies
-(smpc.py:51-79,112)."""
+(smpc.py:51-79,112).
+
+`collect_err=True` adds the six clipping-error columns the reference declares (smpc.py:24-32: mse_lowp, mse_gaus,
+mse_laplace, cos_lowp, cos_gaus, cos_laplace; formulas smpc.py:80-100) - the columns `-sm use -c mix` (iq.py:310-323)
+compares per channel.  The reference never fills them (nothing passes it the quantized tensors, so its files hold NaN
+there); here every batch measures exactly the three quantizations `-c mix` chooses between: the candidates are built from
+the batch's own table (ops.mix_candidates) and their errors come from one more read of the activation
+(ops.pc_quant_errors: no quantized tensor is materialised), recorded through the same single device->host copy.  What
+the candidates need besides the table - bit width, half range, the bit-allocation settings - belongs to the layer's
+activation quantizer: `err_settings`, see save_tensor_stats.  A caller-supplied `tensors_q` stays ignored; a batch
+sharded over ranks is not supported with collect_err."""
 import os
 import pickle
 import shutil
@@ -28,19 +38,27 @@ _ROW = {'max': L.STAT_MAX, 'min': L.STAT_MIN, 'std': L.STAT_STD, 'mean': L.STAT_
         'kurtosis': L.STAT_KURT, 'b': L.STAT_B, 'std_pos': L.STAT_STD_POS}
 
 
+ERR_NAMES = ('mse_lowp', 'mse_gaus', 'mse_laplace', 'cos_lowp', 'cos_gaus', 'cos_laplace')
+
+
 def base_dir():
     return os.path.join(str(Path.home()), 'mxt-sim')
 
 
 class StatisticManagerPerChannel(metaclass=Singleton):
     def __init__(self, folder, load_stats, stats=('max', 'min', 'std', 'mean', 'kurtosis', 'b', 'std_pos'),
-                 batch_avg=False, collect_err=False, group=None):
+                 batch_avg=False, collect_err=False, group=None, err_settings=None):
         self.name = folder
         self.folder = os.path.join(base_dir(), 'statistics/per_channel', folder)
         self.stats_names = list(stats)
         if collect_err:
-            raise NotImplementedError('collect_err (mse/cos columns) is a diagnostic outside the hot path')
+            if D.world_size(group) > 1:
+                raise NotImplementedError('collect_err with a batch sharded over ranks (the row records are local to a sample)')
+            self.stats_names += [n for n in ERR_NAMES if n not in self.stats_names]   # smpc.py:24-32, in that order
         self.collect_err = collect_err
+        # what the three candidates need besides the table: a dict {num_bits, positive, bit_alloc, prior_is_b, target,
+        # round_mode} (the arguments of ops.mix_candidates) or a callable (tag, half_range) -> such a dict
+        self.err_settings = err_settings
         self.batch_avg = batch_avg
         self.group = group
         self.save_stats = not load_stats
@@ -52,21 +70,26 @@ class StatisticManagerPerChannel(metaclass=Singleton):
         else:
             self.stats = {}
 
-    def save_tensor_stats(self, tensor, tag, id, tensors_q={}, force_global_min_max=False):
+    def save_tensor_stats(self, tensor, tag, id, tensors_q={}, force_global_min_max=False, half_range=False,
+                          err_settings=None):
+        """smpc.py:45-125.  half_range / err_settings matter with collect_err only: err_settings (a dict, see __init__)
+        overrides the manager's own for this call; a callable provider is asked with (tag, half_range)."""
         # FC and 1x1-spatial outputs are not per-channel quantized (smpc.py:47-48)
         if len(tensor.shape) < 3 or (tensor.shape[2] == 1 and tensor.shape[3] == 1):
             return
         N, C = tensor.shape[0], tensor.shape[1]
         HW = tensor.numel() // (N * C)
         x = tensor.detach().contiguous()
-        table, _ = ops.pc_stats(x, N, C, HW, need_b='b' in self.stats_names,
+        settings = self._err_settings(tag, half_range, err_settings) if self.collect_err else None
+        table, _ = ops.pc_stats(x, N, C, HW, need_b='b' in self.stats_names or self.collect_err,
                                 need_kurt='kurtosis' in self.stats_names,
                                 need_relu='std_pos' in self.stats_names, group=self.group)
         if D.world_size(self.group) > 1 and not D.xrank_checkpoint(self.group):
             # sharded: a wait of the in-launch exchange expired on some rank (the table is NaN there); the group is on the
             # collective now - this layer's table again, before anything of it is recorded
-            table, _ = ops.pc_stats(x, N, C, HW, need_b='b' in self.stats_names, need_kurt='kurtosis' in self.stats_names,
-                                    need_relu='std_pos' in self.stats_names, group=self.group)
+            table, _ = ops.pc_stats(x, N, C, HW, need_b='b' in self.stats_names or self.collect_err,
+                                    need_kurt='kurtosis' in self.stats_names, need_relu='std_pos' in self.stats_names,
+                                    group=self.group)
         if self.batch_avg and not force_global_min_max:
             # mean over the batch of the per-sample extrema (smpc.py:72,78): rows = (n, c) pairs; with several ranks
             # the sums and the sample counts travel, so every rank holds the mean over the GLOBAL batch
@@ -80,11 +103,32 @@ class StatisticManagerPerChannel(metaclass=Singleton):
                 smax, smin, cnt = rec[0], rec[1], rec[2]
             table[L.STAT_MAX] = (smax / cnt).float()
             table[L.STAT_MIN] = (smin / cnt).float()
+        if self.collect_err:
+            # the three quantizations `-sm use -c mix` chooses between, from THIS batch's table; rows in ERR_NAMES' order.
+            # The table's min / max rows are x's exact extrema unless batch_avg replaced them.
+            exact = not (self.batch_avg and not force_global_min_max)
+            qp_l, qp_g, qp_p = ops.mix_candidates(table, **settings)
+            err = ops.pc_quant_errors(x, N, C, HW, (qp_p, qp_g, qp_l),
+                                      mm=table[[L.STAT_MIN, L.STAT_MAX]] if exact else None)
+            table = torch.cat([table, err])
         host = table.cpu().numpy()          # the only synchronisation of this call
         layer = self.stats.setdefault(id, {})
         for sn in self.stats_names:
-            st = host[_ROW[sn]].copy()
+            st = host[_ROW[sn] if sn in _ROW or not self.collect_err else L.NSTAT + ERR_NAMES.index(sn)].copy()
+            if sn.startswith('cos'):
+                st = np.nan_to_num(st)      # smpc.py:113-115
+                st[st == 0] = 1.
             layer[sn] = st if sn not in layer else np.vstack([layer[sn], st])
+
+    def _err_settings(self, tag, half_range, given):
+        s = given if given is not None else self.err_settings
+        if callable(s):
+            s = s(tag, half_range)
+        if s is None:
+            raise ValueError('collect_err needs the settings of the activation quantizer whose candidates it measures: pass '
+                             'err_settings (dict(num_bits=..., positive=..., bit_alloc=..., prior_is_b=..., target=..., '
+                             'round_mode=...) or a callable (tag, half_range) -> dict) to the manager or to save_tensor_stats')
+        return dict(s)
 
     def get_tensor_stat(self, id, stat, kind='mean'):
         if self.stats is not None:

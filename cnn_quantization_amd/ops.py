@@ -471,19 +471,13 @@ def pc_params(stats, num_bits, positive=False, clip='no', bit_alloc=False, prior
     return qp, diag
 
 
-def act_qdq_mix(x, num_bits, stats, mse, positive=False, bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
-                whole_tensor=False, want_codes=False, want_entropy=False, out=None):
-    """clip_type == 'mix' of the `-sm use` route (iq.py:310-323 + 327-359): per channel the Gaussian clipping value where
-    mse_gaus < mse_laplace, else the Laplace one, and the min/max half range (max - min) / 2 where mse_lowp < mse_gaus;
-    comparisons with NaN are False, so a file whose error columns are NaN - all the reference's own collection writes -
-    gives plain Laplace clipping.  stats [NSTAT, C]: the file's mean_{min, max, mean, b, std} rows; mse [3, C]: rows
-    laplace, gaus, lowp.  Everything downstream of the clipping value is per channel and elementwise, so the three
-    candidates' parameter tables are merged per channel: two cnnq_pc_params launches, the min/max candidate in a few
-    [C]-sized fp32 torch ops that repeat that kernel's arithmetic (iq.py:284-300, 351, 443, 559-572), one fused Q/DQ."""
-    x = _dev(x, 'x')
-    N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x)
-    stats = stats.to(device=x.device, dtype=torch.float32)
-    mse = torch.as_tensor(mse, dtype=torch.float32, device=x.device).view(3, C)
+def mix_candidates(stats, num_bits, positive=False, bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
+                   whole_tensor=False):
+    """The three parameter tables `-c mix` chooses between per channel (iq.py:310-323), from one statistics table
+    [NSTAT, C]: (qp_l, qp_g, qp_p) - Laplace clipping, Gaussian clipping, the min/max half range (max - min) / 2.  Two
+    cnnq_pc_params launches; the min/max candidate in a few [C]-sized fp32 torch ops that repeat that kernel's arithmetic
+    (iq.py:284-300, 351, 443, 559-572).  Shared by act_qdq_mix (the consumer) and the per-channel statistics manager's
+    collect_err (the producer of the error columns), so both speak about the same three quantizations."""
     kw = dict(positive=positive, bit_alloc=bit_alloc, prior_is_b=prior_is_b, target=target, round_mode=round_mode,
               direct_range=whole_tensor)
     qp_l, dg_l = pc_params(stats, num_bits, clip='laplace', **kw)
@@ -503,7 +497,59 @@ def act_qdq_mix(x, num_bits, stats, mse, positive=False, bit_alloc=False, prior_
         scale = delta / qmax
     scale = torch.where(scale < 1e-8, torch.full_like(scale, 1e-8), scale)
     zp = torch.round(0. - off / scale)
-    qp_p = torch.stack([scale, zp, qmax])
+    return qp_l, qp_g, torch.stack([scale, zp, qmax])
+
+
+def pc_quant_errors(x, N, C, HW, qps, mm=None):
+    """Error columns [2K, C] (float32, on the device) of K = 1..3 candidate parameter tables `qps` (each [NQP, C]) on
+    x[N][C][HW]: rows mse_0..K-1 (smpc.py:84), then cos_0..K-1 (smpc.py:96-98) - see cnnq_pc_qerr.  One read of x, no
+    quantized tensor is materialised.  mm [2, C] (optional): x's exact channel extrema (rows min, max), which let the kernel
+    take the divide-free quotient; the result does not depend on it.  float32 dense NCHW only."""
+    lib = L.load()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+        raise L.CnnqError('pc_quant_errors: x must be a contiguous float32 CUDA/HIP tensor (upcast / copy first)')
+    x = _dev(x, 'x')
+    qps = list(qps)
+    K = len(qps)
+    if not 1 <= K <= 3:
+        raise L.CnnqError('pc_quant_errors: 1..3 candidate tables, got %d' % K)
+    for q in qps:
+        if not (isinstance(q, torch.Tensor) and q.device == x.device and q.dtype == torch.float32 and tuple(q.shape) == (L.NQP, C)):
+            raise L.CnnqError('pc_quant_errors: every table must be a float32 [%d, %d] tensor on %s' % (L.NQP, C, x.device))
+    if x.numel() != N * C * HW:
+        raise L.CnnqError('pc_quant_errors: x has %d elements, N*C*HW = %d' % (x.numel(), N * C * HW))
+    qp = torch.stack(qps).contiguous()
+    if mm is not None:
+        mm = mm.to(device=x.device, dtype=torch.float32).contiguous()
+        if tuple(mm.shape) != (2, C):
+            raise L.CnnqError('pc_quant_errors: mm must be [2, %d]' % C)
+    key = ('qerr', N, C, HW, K)
+    nbytes = _WS_BYTES.get(key)
+    if nbytes is None:
+        nbytes = lib.cnnq_pc_qerr_workspace(N, C, HW, K)
+        if nbytes == 0:
+            raise L.CnnqError('cnnq_pc_qerr_workspace(%d, %d, %d, %d): no plan for these sizes' % (N, C, HW, K))
+        _WS_BYTES[key] = nbytes
+    st = _raw_stream(x.device.index)
+    err = torch.empty((2 * K, C), dtype=torch.float32, device=x.device)
+    L.check(lib.cnnq_pc_qerr(_ptr(x), N, C, HW, _ptr(qp), K, _ptr(mm), _ptr(_scratch(x, 'qerr', nbytes, st)), _ptr(err), st),
+            'cnnq_pc_qerr')
+    return err
+
+
+def act_qdq_mix(x, num_bits, stats, mse, positive=False, bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
+                whole_tensor=False, want_codes=False, want_entropy=False, out=None):
+    """clip_type == 'mix' of the `-sm use` route (iq.py:310-323 + 327-359): per channel the Gaussian clipping value where
+    mse_gaus < mse_laplace, else the Laplace one, and the min/max half range (max - min) / 2 where mse_lowp < mse_gaus;
+    comparisons with NaN are False, so a file whose error columns are NaN - all the reference's own collection writes -
+    gives plain Laplace clipping.  stats [NSTAT, C]: the file's mean_{min, max, mean, b, std} rows; mse [3, C]: rows
+    laplace, gaus, lowp.  Everything downstream of the clipping value is per channel and elementwise, so the three
+    candidates' parameter tables (mix_candidates) are merged per channel, then one fused Q/DQ."""
+    x = _dev(x, 'x')
+    N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x)
+    stats = stats.to(device=x.device, dtype=torch.float32)
+    mse = torch.as_tensor(mse, dtype=torch.float32, device=x.device).view(3, C)
+    qp_l, qp_g, qp_p = mix_candidates(stats, num_bits, positive, bit_alloc, prior_is_b, target, round_mode, whole_tensor=whole_tensor)
     pick_g = (mse[1] < mse[0]).view(1, C)
     pick_p = (mse[2] < mse[1]).view(1, C)
     qp = torch.where(pick_p, qp_p, torch.where(pick_g, qp_g, qp_l)).contiguous()

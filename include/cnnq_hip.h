@@ -191,6 +191,22 @@ typedef struct cnnq_params_cfg {
 int cnnq_pc_params(const float* stats, int64_t C, const cnnq_params_cfg* cfg /* host */, float* qp,
                    float* diag, void* stream);
 
+/* Per-channel clipping-error columns for `-c mix` (smpc.py:24-32 declares them, :80-100 are the formulas; iq.py:310-323 is the
+ * consumer) of K = 1..3 candidate quantizations, from ONE read of x and without writing a quantized tensor.
+ * qp: K parameter tables [K][CNNQ_NQP][C] as cnnq_pc_params writes them; q_k is exactly what cnnq_pc_qdq stores for table k.
+ * mm (optional): the channel extrema [2][C] of THIS tensor (rows min, max) - where they put a channel in the domain of the
+ * divide-free quotient - and no candidate of the channel has a NaN zero point or qmax - it is used (the same function there:
+ * the results do not depend on mm).
+ * err [2K][C] fp32: rows mse_0..K-1 - the mean over n of the mean over hw of (x - q_k)^2 (smpc.py:84) - then cos_0..K-1 -
+ * sum x q_k / (sqrt(sum_n sqrt(sum_hw x^2)) sqrt(sum_n sqrt(sum_hw q_k^2))), i.e. utils/misc.py:23-34 with dims = [-1, 0]
+ * as written (the root is taken inside the loop over the dimensions).  The nan_to_num / 0 -> 1 of smpc.py:113-115 is the
+ * caller's.  Sums in fp64, rounded once; no atomics: bit-identical run after run.
+ * ws: cnnq_pc_qerr_workspace bytes, 8-byte aligned (fp64 row records).  Two launches, no host synchronisation, no allocation.
+ * K outside 1..3, a size < 1 or a null x / qp / ws / err: CNNQ_EINVAL (0 bytes) before anything touches the device. */
+size_t cnnq_pc_qerr_workspace(int64_t N, int64_t C, int64_t HW, int K);
+int cnnq_pc_qerr(const float* x, int64_t N, int64_t C, int64_t HW, const float* qp, int K, const float* mm /* or NULL */,
+                 void* ws, float* err, void* stream);
+
 /* Weights (iq.py:453-476): identical parameter derivation with the range always min/max and
  * the bit allocation prior always STD; provided as cnnq_pc_params with clip = 0. */
 
