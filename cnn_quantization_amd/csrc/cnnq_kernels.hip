@@ -46,6 +46,7 @@
 #include "cnnq_kld.hip.h"
 #include "cnnq_half.hip.h"
 #include "cnnq_nhwc.hip.h"
+#include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_qerr.hip.h"
 
 extern "C" {
@@ -1730,15 +1731,20 @@ static int cl_check(int64_t R, int64_t C, int dtype) {
     return (!dtype_ok(dtype) || R < 1 || C < 1 || C > CL_C_MAX) ? CNNQ_EINVAL : 0;
 }
 
-size_t cnnq_pc_nhwc_workspace(int64_t R, int64_t C, int dtype) {
-    if (cl_check(R, C, dtype)) return 0;
+// the widest slab count of the statistics launches over the piece widths C allows (the alignment is not known yet)
+static int64_t cl_slabs_max(int64_t R, int64_t C, int dtype) {
     int64_t S = 1;
     for (int w = 16 / cl_esize(dtype); w >= 1; w >>= 1) {
         if (C % w) continue;
         const int64_t s = cl_geo_mm(R, C, w).S;
         S = s > S ? s : S;
     }
-    return ((size_t)2 + 2 * (size_t)S) * (size_t)C * sizeof(float);
+    return S;
+}
+
+size_t cnnq_pc_nhwc_workspace(int64_t R, int64_t C, int dtype) {
+    if (cl_check(R, C, dtype)) return 0;
+    return ((size_t)2 + 2 * (size_t)cl_slabs_max(R, C, dtype)) * (size_t)C * sizeof(float);
 }
 
 int cnnq_pc_route_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
@@ -1791,6 +1797,80 @@ int cnnq_pc_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, co
     if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
     if (!x || !y || !qp) return CNNQ_EINVAL;
     return cl_qdq(x, y, dtype, cl_piece(C, cl_esize(dtype), h_align(x, y)), R, C, qp, nullptr, (hipStream_t)stream);
+}
+
+// ---- config 3 on dense channels_last activations (cnnq_nhwc_aciq.hip.h) --------------------------------------------------------
+// ws of cnnq_pc_aciq_qdq_nhwc, doubles: part[S][CNNQ_NMOM][C], mom[CNNQ_NMOM][C], part2[S][CNNQ_NDEV][C]
+size_t cnnq_pc_aciq_nhwc_workspace(int64_t R, int64_t C, int dtype) {
+    if (cl_check(R, C, dtype)) return 0;
+    const size_t S = (size_t)cl_slabs_max(R, C, dtype);
+    return (S * (CNNQ_NMOM + CNNQ_NDEV) + CNNQ_NMOM) * (size_t)C * sizeof(double);
+}
+
+// Which launches cnnq_pc_aciq_qdq_nhwc makes for this geometry (host only).  out[5] is 1 throughout: no class of layer is sent
+// back to the copy route; one that measures slower native than through the copy (tools/bench_channels_last_aciq.py) goes back here.
+int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[6]) {
+    if (cl_check(R, C, dtype) || !out || align_bytes <= 0 || (align_bytes & (align_bytes - 1))) return CNNQ_EINVAL;
+    const int w = cl_piece(C, cl_esize(dtype), align_bytes);
+    const ClGeo m = cl_geo_mm(R, C, w), q = cl_geo_qdq(R, C, w);
+    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31) || m.rpw >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    out[0] = w;
+    out[1] = m.S;
+    out[2] = (int32_t)m.rpw;
+    out[3] = (int32_t)(m.rpw / m.RS);
+    out[4] = q.S * q.nb;
+    out[5] = 1;
+    return 0;
+}
+
+// int_quantizer.py:327-352 (statistics, ACIQ clipping, bit allocation) + 409-451, 557-603 (parameters, Q/DQ) on [R][C]:
+// k_cl_moments -> k_combine -> (k_cl_absdev -> k_combine_dev) -> k_params -> k_cl_qdq with the table
+int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
+                          float* stats, float* qp, float* diag, void* stream) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    if (!x || !y || !cfg || !ws || !stats || !qp || ((uintptr_t)ws & 7)) return CNNQ_EINVAL;
+    if (cfg->num_bits < 1 || cfg->num_bits > 32 || cfg->clip < 0 || cfg->clip > 3) return CNNQ_EINVAL;
+    if ((cfg->clip == 1 || cfg->clip == 2) && cfg->num_bits > 8) return CNNQ_EINVAL;   // as cnnq_pc_params, before any launch
+    if (cfg->direct_range) return CNNQ_EINVAL;                                           // the per-tensor branch has no channels
+    const bool use_ba = cfg->bit_alloc && cfg->num_bits <= 4;
+    if (use_ba && !diag) return CNNQ_EINVAL;                                             // the bit table lives in diag
+    const int w = cl_piece(C, cl_esize(dtype), h_align(x, y));
+    const ClGeo m = cl_geo_mm(R, C, w);
+    const ClGeo q = cl_geo_qdq(R, C, w);
+    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    const bool need_b = cfg->clip == 1 || (use_ba && cfg->prior_is_b);
+    double* part = reinterpret_cast<double*>(ws);
+    double* mom = part + (size_t)m.S * CNNQ_NMOM * C;
+    double* part2 = mom + (size_t)CNNQ_NMOM * C;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(m.S * m.nb)), block(TPB);
+    const bool ntl = R * C * cl_esize(dtype) > NT_BYTES;
+    // the Q/DQ walks the tensor descending: the statistics launch in front of it ascends, so with pass B pass A descends
+    const int rev = need_b ? 1 : 0;
+#define LAUNCH_CLA_NT(T, W) \
+    hipLaunchKernelGGL((k_cl_moments<T, W, true>), grid, block, 0, st, static_cast<const ClRaw<T>::type*>(x), m, rev, part)
+#define LAUNCH_CLA_LD(T, W) \
+    hipLaunchKernelGGL((k_cl_moments<T, W, false>), grid, block, 0, st, static_cast<const ClRaw<T>::type*>(x), m, rev, part)
+    if (ntl) CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLA_NT); else CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLA_LD);
+#undef LAUNCH_CLA_NT
+#undef LAUNCH_CLA_LD
+    int rc = launch_status();
+    // the merge writes every row of the table (zero for KURT, STD_POS; B without pass B)
+    if (!rc) rc = cnnq_pc_combine(part, m.S, C, 0, mom, stats, stream);
+    if (!rc && need_b) {
+#define LAUNCH_CLB_NT(T, W) \
+    hipLaunchKernelGGL((k_cl_absdev<T, W, true>), grid, block, 0, st, static_cast<const ClRaw<T>::type*>(x), m, stats, part2)
+#define LAUNCH_CLB_LD(T, W) \
+    hipLaunchKernelGGL((k_cl_absdev<T, W, false>), grid, block, 0, st, static_cast<const ClRaw<T>::type*>(x), m, stats, part2)
+        if (ntl) CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLB_NT); else CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLB_LD);
+#undef LAUNCH_CLB_NT
+#undef LAUNCH_CLB_LD
+        rc = launch_status();
+        if (!rc) rc = cnnq_pc_combine_dev(part2, m.S, C, mom, 0, nullptr, stats, stream);
+    }
+    if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
+    if (!rc) rc = cl_qdq(x, y, dtype, w, R, C, qp, nullptr, st);
+    return rc;
 }
 
 }  // extern "C"

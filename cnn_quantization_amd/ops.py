@@ -203,15 +203,17 @@ def _groups(N, C, HW, aligned=None):
 
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
-    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', N = rows).  0 from the library: no plan for the geometry."""
+    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc': N = rows).  0 from the library: no plan for
+    the geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
         lib = L.load()
-        if kind == 'nhwc':
-            nbytes = lib.cnnq_pc_nhwc_workspace(N, C, arg)
+        if kind in ('nhwc', 'aciq_nhwc'):
+            fn = 'cnnq_pc_nhwc_workspace' if kind == 'nhwc' else 'cnnq_pc_aciq_nhwc_workspace'
+            nbytes = getattr(lib, fn)(N, C, arg)
             if nbytes == 0:
-                raise L.CnnqError('cnnq_pc_nhwc_workspace(%d, %d, %d): bad arguments' % (N, C, arg))
+                raise L.CnnqError('%s(%d, %d, %d): bad arguments' % (fn, N, C, arg))
         elif kind == 'aciq':
             nbytes = lib.cnnq_pc_aciq_workspace(N, C, HW, arg)
         else:
@@ -1371,6 +1373,51 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
             D.all_reduce_sum_(hist, group)
         entropy = entropy_from_hist(hist)
     return _result(y, codes, entropy, dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
+
+
+def aciq_qdq_nhwc(x, num_bits, positive=False, clip='laplace', bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
+                  stats=None, out=None, want_parts=False):
+    """Config 3 (iq.py:327-352 -> 409-451: ACIQ clipping 'laplace' / 'gaus', optionally bit allocation) on a dense channels_last
+    activation of fp32 / bf16 / fp16, on the storage as it is: cnnq_pc_aciq_qdq_nhwc - statistics over
+    slabs of rows, parameters, Q/DQ, one host call, one cached workspace - or, with `stats` ([NSTAT, C], -sm use), pc_params and
+    the table-driven Q/DQ.  y has x's layout and dtype; want_parts: (y, dict(stats, qp, diag)).  One GPU: the statistics are this
+    tensor's.  A tensor that is not dense channels_last (or CNNQ_NHWC=0: copied, counted) takes act_qdq_per_channel."""
+    if clip not in ('laplace', 'gaus'):
+        raise L.CnnqError("aciq_qdq_nhwc: clip must be 'laplace' or 'gaus', got %r" % (clip,))
+    x = _dev_act_layout(x, 'x')
+    if x.dim() != 4:
+        raise L.CnnqError('aciq_qdq_nhwc: x must be a 4-D activation, got %d dimensions' % x.dim())
+    use_ba = bool(bit_alloc) and num_bits <= 4
+    if not _is_nhwc(x):
+        return act_qdq_per_channel(x, num_bits, positive, clip, bit_alloc, prior_is_b, target, round_mode, group=False,
+                                   want_parts=want_parts, stats=stats, out=out)
+    C = x.shape[1]
+    if stats is not None:
+        qp, diag = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
+        y = _pc_qdq_nhwc(x, qp, out)
+        return _result(y, parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
+    lib = L.load()
+    cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
+    R = x.numel() // C
+    dt = _DTYPE_CODES[x.dtype]
+    nbytes = _ws_bytes('aciq_nhwc', R, C, 1, dt)
+    y = _out_like(x, out)
+    st = _raw_stream(x.device.index)
+    ntab = (L.NSTAT + L.NQP + L.NDIAG) * C * 4
+    if want_parts:
+        tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, C, dtype=torch.float32, device=x.device)
+        ws, tp = _scratch(x, 'aciq_nhwc', nbytes, st).data_ptr(), tabs.data_ptr()
+    else:
+        # the tables nobody outside the call reads follow the records in the cached workspace
+        ws = _scratch(x, 'aciq_nhwc', nbytes + ntab, st).data_ptr()
+        tp = ws + nbytes
+    rc = lib.cnnq_pc_aciq_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                   tp + (L.NSTAT + L.NQP) * C * 4, st)
+    if rc:
+        L.check(rc, 'cnnq_pc_aciq_qdq_nhwc')
+    if not want_parts:
+        return y
+    return y, dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:])
 
 
 def weight_correction(w, w_q, vcorr=False, bcorr=False):

@@ -126,16 +126,33 @@ class IntQuantizer:
 
     def _half_native(self, tensor, override_att=None):
         """Whether a bf16 / fp16 tensor takes a path with half kernels: config 2 (gemmlowpQuantizeActivationPerChannel without
-        clipping, bit allocation, entropy, a bias correction to fold in or a sharded batch) or config 1 (gemmlowpMinMaxQuantize)."""
+        clipping, bit allocation, entropy, a bias correction to fold in or a sharded batch), config 1 (gemmlowpMinMaxQuantize), or
+        config 3 on a dense channels_last tensor (_nhwc_aciq: gemmlowpClippingQuantize's native route)."""
         def att(k):
             return override_att[1] if override_att is not None and override_att[0] == k else getattr(self, k)
-        if att('kld') or att('clipping') != 'no' or att('pcq_w'):
+        if att('kld'):
+            return False
+        if att('clipping') != 'no':
+            return not att('mtd_quant') and self._nhwc_aciq(tensor, att('clipping'), att)
+        if att('pcq_w'):
             return False
         if att('pcq_a') and _is_pc_act(tensor):
             return (not att('mtd_quant') and not att('measure_entropy') and self.fuse_bcorr is None
                     and not (att('bit_alloc_act') and att('num_bits') <= 4)
                     and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
         return True
+
+    def _nhwc_aciq(self, tensor, clip_type, att=None):
+        """Whether gemmlowpClippingQuantize runs this call on the channels_last storage as it is (ops.aciq_qdq_nhwc, DESIGN.md
+        section 14): a dense channels_last tensor on the per-channel branch with Laplace or Gaussian clipping, no entropy
+        measurement, no bias correction to fold in, and a batch that is not sharded.  Shape, strides and attributes only."""
+        att = att or (lambda k: getattr(self, k))
+        # dense channels_last and not contiguous: what ops._layout calls 'nhwc' (a contiguous tensor never asks ops)
+        return (bool(att('pcq_a')) and _is_pc_act(tensor) and clip_type in ('laplace', 'gaus')
+                and tensor.dim() == 4 and not tensor.is_contiguous()
+                and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
+                and not att('measure_entropy') and self.fuse_bcorr is None
+                and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
 
     def __repr__(self):
         # iq.py:124-126, printed by the manager in verbose mode
@@ -221,6 +238,11 @@ class IntQuantizer:
                 rows = {L.STAT_MIN: ('min', 'mean'), L.STAT_MAX: ('max', 'mean'), L.STAT_MEAN: ('mean', 'mean'),
                         L.STAT_B: ('b', 'mean'), L.STAT_STD: ('std', 'mean')}
                 table = self._stats_table(stat_id, C, tensor.device, rows)
+            if self._nhwc_aciq(tensor, clip_type):
+                # a dense channels_last activation: quantized where it lies, the result keeps layout and dtype
+                return ops.aciq_qdq_nhwc(tensor, self.num_bits, positive=self._positive, clip=clip_type,
+                                         bit_alloc=self.bit_alloc_act, prior_is_b=prior_b, target=self.bit_alloc_target_act,
+                                         round_mode=self.bit_alloc_round, stats=table)
             out = ops.act_qdq_per_channel(tensor, self.num_bits, positive=self._positive, clip=clip_type,
                                           bit_alloc=self.bit_alloc_act, prior_is_b=prior_b,
                                           target=self.bit_alloc_target_act, round_mode=self.bit_alloc_round,

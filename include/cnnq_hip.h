@@ -674,6 +674,30 @@ int cnnq_pc_minmax_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_
 /* The table-driven Q/DQ (int_quantizer.py:573-592, -sm use; counterpart of cnnq_pc_qdq): the IEEE divide, one launch. */
 int cnnq_pc_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* qp, void* stream);
 
+/* Config 3 - ACIQ clipping with bit allocation - on dense channels_last activations.  The per-channel sums are added in an
+ * order fixed by (R, C, dtype, alignment) alone: run after run the same bits, but not the NCHW chain's order, so the result
+ * is NOT promised to equal cnnq_pc_aciq_qdq's on the same values.  Promised: the table `stats` is within the statistics tier
+ * of fp64 (rows MIN / MAX exact, a NaN element makes them NaN), and given that table qp, diag and y are, bit for bit,
+ * cnnq_pc_params' and the table-driven Q/DQ's (cnnq_pc_qdq_nhwc: the IEEE divide) - for bf16 / fp16 on the exactly
+ * upconverted values with one round-to-nearest-even at the end.
+ * cnnq_pc_aciq_nhwc_workspace: bytes of `ws` for cnnq_pc_aciq_qdq_nhwc - the pass-A and pass-B records of the widest slab
+ * count over the piece widths and the merged moment record (0 on bad arguments).
+ * cnnq_pc_route_aciq_nhwc (host only, nothing enqueued; cnnq_pc_route_nhwc is unchanged): out = {elements per load W, row
+ * slabs S of the statistics launches, rows per slab, row loads per lane and slab, workgroups of the Q/DQ launch, 1 - the native
+ * launches (0 would say: this class of layer goes back to the copy route; none does)}. */
+size_t cnnq_pc_aciq_nhwc_workspace(int64_t R, int64_t C, int dtype);
+int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[6]);
+/* The dynamic ACIQ pipeline (int_quantizer.py:327-352: per-channel min / max / mean / std / b, alpha from the Laplace or
+ * Gaussian tables, bit allocation 227-253, delta / offset 284-300; then 409-451, 557-603: scale, zero point, Q/DQ) behind
+ * ONE call on [R][C]; counterpart of cnnq_pc_aciq_qdq: pass A -> merge -> (pass B -> merge, when b is needed: Laplace
+ * clipping, or bit allocation on the b prior) -> parameters -> Q/DQ, four or six launches.  stats[CNNQ_NSTAT][C] is an
+ * OUTPUT and is written completely (KURT, STD_POS zero; B zero without pass B); qp[CNNQ_NQP][C]; diag[CNNQ_NDIAG][C] may
+ * be NULL without bit allocation.  ws: cnnq_pc_aciq_nhwc_workspace bytes, 8-byte aligned.  cfg->direct_range (the
+ * per-tensor branch) is CNNQ_EINVAL, as are the cases cnnq_pc_aciq_qdq refuses - before anything touches the device.
+ * Re-entrant, allocates nothing, no host synchronisation; x != y. */
+int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
+                          float* stats, float* qp, float* diag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
