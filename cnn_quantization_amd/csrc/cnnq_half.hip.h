@@ -368,15 +368,4 @@ inline int h_splits(int64_t N, int64_t C, int64_t HW, int64_t per, int64_t smax)
     return (int)s;
 }
 
-#define CNNQ_H_DISPATCH(dt, w, F)                                        \
-    do {                                                                 \
-        if ((dt) == CNNQ_DTYPE_BF16) {                                   \
-            if ((w) == 8) F(HBf16, 8); else if ((w) == 4) F(HBf16, 4);   \
-            else if ((w) == 2) F(HBf16, 2); else F(HBf16, 1);            \
-        } else {                                                         \
-            if ((w) == 8) F(HF16, 8); else if ((w) == 4) F(HF16, 4);     \
-            else if ((w) == 2) F(HF16, 2); else F(HF16, 1);              \
-        }                                                                \
-    } while (0)
-
 }  // namespace

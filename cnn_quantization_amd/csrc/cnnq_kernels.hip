@@ -27,7 +27,11 @@
 // divide followed by a separately rounded add: bit-exactness with the reference's aten ops).
 //
 // Layout: the kernels live in the cnnq_*.hip.h files next to this one (one file per stage of the path),
-// all in one anonymous namespace of this single translation unit; below them is the C ABI.
+// all in one anonymous namespace of this single translation unit; below them is the C ABI.  The host glue the entry points
+// share is written once: the runtime -> template dispatchers (with_shape / with_int / with_bool), the exchange workspace view
+// (gws_view) and the fused-launch rule (fused_ok / plan_fused) in cnnq_plan.hip.h next to the launch_* functions, with_piece
+// (element type x piece width) in cnnq_nhwc.hip.h, and - right below the includes here - the argument checks and the small
+// argument builders; a caller workspace's layout (StatsWs, MmWs, AciqWs) stands next to the function that sizes it.
 
 #include <string.h>
 
@@ -48,6 +52,90 @@
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_qerr.hip.h"
+
+namespace {
+
+// ---- shared host helpers of the C ABI below ---------------------------------------------------------------------------------
+inline bool nt_loads(int64_t bytes) { return bytes > NT_BYTES; }      // beyond the Infinity Cache: non-temporal loads
+inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }   // a: a power of two (NULL is aligned)
+inline bool pow2(int v) { return v > 0 && !(v & (v - 1)); }
+inline int g_error(int G) { return G ? G : CNNQ_EINVAL; }             // what a group count G <= 0 says: the plan's error
+inline hipStream_t hs(void* stream) { return (hipStream_t)stream; }
+inline unsigned long long* u64p(uint64_t* p) { return reinterpret_cast<unsigned long long*>(p); }
+
+// one wave (at least) per 64 channels, PTPB at most: the single-workgroup parameter kernels
+inline int param_threads(int64_t C) { return (int)(C >= PTPB ? PTPB : ((C + 63) / 64) * 64); }
+// the merge kernels: merge_cpw channels per workgroup
+inline dim3 merge_grid(int G, int64_t C) { return dim3((unsigned)((C + merge_cpw(G, (int)C) - 1) / merge_cpw(G, (int)C))); }
+
+// cnnq_params_cfg as every entry point that takes one checks it before its first launch
+inline int check_cfg(const cnnq_params_cfg* cfg) {
+    if (cfg->num_bits < 1 || cfg->num_bits > 32 || cfg->clip < 0 || cfg->clip > 3) return CNNQ_EINVAL;
+    // the ACIQ factor tables have entries for 0..8 bits only (iq.py:14-41: the reference's alpha_laplace / alpha_gaus
+    // dictionaries raise KeyError beyond 8); wider codes are accepted for min/max and the '<p>std' clip alone
+    return ((cfg->clip == 1 || cfg->clip == 2) && cfg->num_bits > 8) ? CNNQ_EINVAL : 0;
+}
+inline bool cfg_bit_alloc(const cnnq_params_cfg* cfg) { return cfg->bit_alloc && cfg->num_bits <= 4; }   // (its table lives in diag)
+
+inline XOut xout(uint8_t* codes, uint64_t* hist_rep, uint8_t* packed = nullptr) {
+    XOut xo;
+    xo.codes = codes;
+    xo.hist = u64p(hist_rep);
+    xo.packed = packed;
+    return xo;
+}
+// the cross-rank stage's arguments.  seq != 0: host numbering (seq_dev, if `mirror`, follows it); seq == 0: device numbering in
+// seq_dev; either way the launches keep the slot counts themselves behind seq_dev (round 6)
+inline XRank xrank_args(void* const* windows, int rank, int world, int cmax, uint32_t seq, uint32_t* seq_dev, bool mirror, int zero_c, int nslots,
+                        int slot0, uint32_t* status, int64_t timeout) {
+    XRank xr;
+    xr.windows = windows;
+    xr.rank = rank;
+    xr.world = world;
+    xr.seq = seq;
+    xr.seq_dev = seq ? nullptr : seq_dev;
+    xr.seq_mirror = (seq && mirror) ? seq_dev : nullptr;
+    xr.zero_c = zero_c;
+    xr.cdev = seq_dev ? seq_dev + 4 : nullptr;
+    xr.nslots = nslots;
+    xr.slot0 = slot0;
+    xr.no_prologue = 0;
+    xr.cmax = cmax;
+    xr.status = status;
+    xr.timeout = timeout;
+    return xr;
+}
+inline St1Args st1_args(float* stats, double* mom, int64_t N, int64_t HW, int need_b, int need_kurt, int need_relu) {
+    St1Args sa;
+    sa.stats = stats;
+    sa.mom = mom;
+    sa.count = (double)N * (double)HW;
+    sa.need_relu = need_relu ? 1 : 0;
+    sa.need_dev = (need_b || need_kurt) ? 1 : 0;
+    sa.need_kurt = need_kurt ? 1 : 0;
+    return sa;
+}
+
+// pass B (k_absdev, descending: it follows the ascending pass A) from the merged table `stats`, or - raw != NULL - straight
+// from the UNMERGED pass-A records (each workgroup merges its own channels' records in its prologue)
+int launch_absdev(const float* x, int64_t N, int64_t C, int64_t HW, const float* stats, const double* raw, int want_kurt, double* part2,
+                  void* stream) {
+    Variant v;
+    Geo g;
+    const int rc = plan(N, C, HW, al16(x), /*rev=*/1, &v, &g);
+    if (rc) return rc;
+    const int G = raw ? g.S * g.nb : 0;
+    with_shape(v, [&](auto s) {
+        with_bool(want_kurt != 0, nt_loads(N * C * HW * 4), raw != nullptr, [&](auto k, auto nt, auto r) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((k_absdev<S::VEC, S::A, S::J, decltype(k)::value, decltype(nt)::value, decltype(r)::value>), geo_grid(g), dim3(TPB), 0,
+                               hs(stream), x, g, stats, part2, raw, G);
+        });
+    });
+    return launch_status();
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -78,100 +166,61 @@ int cnnq_pc_moments(const float* x, int64_t N, int64_t C, int64_t HW, int want_r
     Geo g;
     const int rc = plan(N, C, HW, al16(x), 0, &v, &g);
     if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-    const bool ntl = N * C * HW * 4 > NT_BYTES;
-#define LAUNCH_MOM(VEC, A, J)                                                                                        \
-    do {                                                                                                             \
-        if (want_relu && ntl) hipLaunchKernelGGL((k_moments<VEC, A, J, true, true>), grid, block, 0, st, x, g, part);   \
-        else if (want_relu) hipLaunchKernelGGL((k_moments<VEC, A, J, true, false>), grid, block, 0, st, x, g, part);    \
-        else if (ntl) hipLaunchKernelGGL((k_moments<VEC, A, J, false, true>), grid, block, 0, st, x, g, part);          \
-        else hipLaunchKernelGGL((k_moments<VEC, A, J, false, false>), grid, block, 0, st, x, g, part);                  \
-    } while (0)
-    CNNQ_DISPATCH(v, LAUNCH_MOM);
-#undef LAUNCH_MOM
+    with_shape(v, [&](auto s) {
+        with_bool(want_relu != 0, nt_loads(N * C * HW * 4), [&](auto r, auto nt) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((k_moments<S::VEC, S::A, S::J, decltype(r)::value, decltype(nt)::value>), geo_grid(g), dim3(TPB), 0, hs(stream), x, g, part);
+        });
+    });
     return launch_status();
 }
 
 int cnnq_pc_combine(const double* part, int G, int64_t C, int has_relu, double* mom, float* stats, void* stream) {
     if (!part || G <= 0 || C <= 0 || C >= ((int64_t)1 << 31) || (!mom && !stats)) return CNNQ_EINVAL;
-    const dim3 grid((unsigned)((C + merge_cpw(G, (int)C) - 1) / merge_cpw(G, (int)C))), block(TPB);
-    hipLaunchKernelGGL(k_combine, grid, block, 0, (hipStream_t)stream, part, G, (int)C, has_relu, mom, stats);
+    hipLaunchKernelGGL(k_combine, merge_grid(G, C), dim3(TPB), 0, (hipStream_t)stream, part, G, (int)C, has_relu, mom, stats);
     return launch_status();
 }
 
 int cnnq_pc_absdev(const float* x, int64_t N, int64_t C, int64_t HW, const float* stats, int want_kurt,
                    double* part2, void* stream) {
     if (!x || !stats || !part2) return CNNQ_EINVAL;
-    Variant v;
-    Geo g;
-    const int rc = plan(N, C, HW, al16(x), /*rev=*/1, &v, &g);   // descending: follows the ascending pass A
-    if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-    const bool ntl = N * C * HW * 4 > NT_BYTES;
-#define LAUNCH_DEV(VEC, A, J)                                                                                             \
-    do {                                                                                                                  \
-        if (want_kurt && ntl) hipLaunchKernelGGL((k_absdev<VEC, A, J, true, true>), grid, block, 0, st, x, g, stats, part2);  \
-        else if (want_kurt) hipLaunchKernelGGL((k_absdev<VEC, A, J, true, false>), grid, block, 0, st, x, g, stats, part2);   \
-        else if (ntl) hipLaunchKernelGGL((k_absdev<VEC, A, J, false, true>), grid, block, 0, st, x, g, stats, part2);         \
-        else hipLaunchKernelGGL((k_absdev<VEC, A, J, false, false>), grid, block, 0, st, x, g, stats, part2);                 \
-    } while (0)
-    CNNQ_DISPATCH(v, LAUNCH_DEV);
-#undef LAUNCH_DEV
-    return launch_status();
-}
-
-// pass B straight from the UNMERGED pass-A records (each workgroup merges its own channels' records in its prologue)
-static int absdev_raw(const float* x, int64_t N, int64_t C, int64_t HW, const double* part, int want_kurt, double* part2,
-                      void* stream) {
-    Variant v;
-    Geo g;
-    const int rc = plan(N, C, HW, al16(x), /*rev=*/1, &v, &g);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-    const bool ntl = N * C * HW * 4 > NT_BYTES;
-    const int G = g.S * g.nb;
-    const float* nostats = nullptr;
-#define LAUNCH_DEVR(VEC, A, J)                                                                                              \
-    do {                                                                                                                    \
-        if (want_kurt && ntl) hipLaunchKernelGGL((k_absdev<VEC, A, J, true, true, true>), grid, block, 0, st, x, g, nostats, part2, part, G);   \
-        else if (want_kurt) hipLaunchKernelGGL((k_absdev<VEC, A, J, true, false, true>), grid, block, 0, st, x, g, nostats, part2, part, G);    \
-        else if (ntl) hipLaunchKernelGGL((k_absdev<VEC, A, J, false, true, true>), grid, block, 0, st, x, g, nostats, part2, part, G);          \
-        else hipLaunchKernelGGL((k_absdev<VEC, A, J, false, false, true>), grid, block, 0, st, x, g, nostats, part2, part, G);                  \
-    } while (0)
-    CNNQ_DISPATCH(v, LAUNCH_DEVR);
-#undef LAUNCH_DEVR
-    return launch_status();
+    return launch_absdev(x, N, C, HW, stats, nullptr, want_kurt, part2, stream);
 }
 
 // All per-channel statistics of one tensor behind ONE call and one caller workspace: pass A -> (pass B with the
 // pass-A merge fused into its prologue -> one final merge of both passes) - three launches for the full set of
 // smpc.py:45-79 instead of four, two for {min, max, mean, std}.  ws: doubles part[G][NMOM][C], part2[G][NDEV][C].
+struct StatsWs {
+    double *part, *part2;
+    StatsWs(void* ws, int G, int64_t C) : part(reinterpret_cast<double*>(ws)), part2(part + (size_t)G * CNNQ_NMOM * C) {}
+    static size_t bytes(int G, int64_t C) { return ((size_t)G * (CNNQ_NMOM + CNNQ_NDEV)) * (size_t)C * sizeof(double); }
+};
+
 size_t cnnq_pc_stats_workspace(int64_t N, int64_t C, int64_t HW, int aligned16) {
     const int G = cnnq_pc_groups(N, C, HW, aligned16);
-    if (G <= 0) return 0;
-    return ((size_t)G * (CNNQ_NMOM + CNNQ_NDEV)) * (size_t)C * sizeof(double);
+    return G <= 0 ? 0 : StatsWs::bytes(G, C);
+}
+
+// the final merge of both passes: every row of the table, and the merged moment record
+static int combine_all(const double* part, const double* part2, int G, int64_t C, int need_relu, int need_kurt, double* mom, float* stats,
+                       void* stream) {
+    hipLaunchKernelGGL(k_combine_all, merge_grid(G, C), dim3(TPB), 0, hs(stream), part, part2, G, (int)C, need_relu, need_kurt, mom, stats);
+    return launch_status();
 }
 
 int cnnq_pc_stats(const float* x, int64_t N, int64_t C, int64_t HW, int need_b, int need_kurt, int need_relu, void* ws,
                   double* mom, float* stats, void* stream) {
-    if (!x || !ws || !stats || ((uintptr_t)ws & 7)) return CNNQ_EINVAL;
+    if (!x || !ws || !stats || misaligned(ws, 8)) return CNNQ_EINVAL;
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
-    double* part = reinterpret_cast<double*>(ws);
-    double* part2 = part + (size_t)G * CNNQ_NMOM * C;
-    hipStream_t st = (hipStream_t)stream;
+    if (G <= 0) return g_error(G);
+    const StatsWs w(ws, G, C);
     // the merge kernels write every row of the table (zero where nothing was requested): no memset
-    int rc = cnnq_pc_moments(x, N, C, HW, need_relu, part, stream);
+    int rc = cnnq_pc_moments(x, N, C, HW, need_relu, w.part, stream);
     if (rc) return rc;
-    if (!(need_b || need_kurt)) return cnnq_pc_combine(part, G, C, need_relu, mom, stats, stream);
-    rc = absdev_raw(x, N, C, HW, part, need_kurt, part2, stream);
+    if (!(need_b || need_kurt)) return cnnq_pc_combine(w.part, G, C, need_relu, mom, stats, stream);
+    rc = launch_absdev(x, N, C, HW, nullptr, w.part, need_kurt, w.part2, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_combine_all, dim3((unsigned)((C + merge_cpw(G, (int)C) - 1) / merge_cpw(G, (int)C))), dim3(TPB), 0, st, part, part2, G,
-                       (int)C, need_relu, need_kurt, mom, stats);
-    return launch_status();
+    return combine_all(w.part, w.part2, G, C, need_relu, need_kurt, mom, stats, stream);
 }
 
 // The same table from ONE launch that reads x once (cnnq_stats1.hip.h: the tile stays in registers across pass A and pass B,
@@ -187,13 +236,7 @@ static int stats_single_impl(const float* x, int64_t N, int64_t C, int64_t HW, i
     // up to 196 members ([512,64,112,112]: 431 us against the chain's 495-560 since the arithmetic of the tile went two elements
     // per instruction, round 6; 529 before, when the rule was 128); nothing measured beyond 256 - tests force those with flag 8
     if (gp.Gs > ST_MAX_MEMBERS && !(flags & 8u)) return CNNQ_ENOTSUP;
-    St1Args sa;
-    sa.stats = stats;
-    sa.mom = mom;
-    sa.count = (double)N * (double)HW;
-    sa.need_relu = need_relu ? 1 : 0;
-    sa.need_dev = (need_b || need_kurt) ? 1 : 0;
-    sa.need_kurt = need_kurt ? 1 : 0;
+    const St1Args sa = st1_args(stats, mom, N, HW, need_b, need_kurt, need_relu);
     if (!gp.flat) {
         // short rows: row-piece tiles (k_stats_group), where they beat the chain (stats_group_pays: every one-channel-per-lane
         // shape, straddling rows only while the tensor is small)
@@ -201,13 +244,13 @@ static int stats_single_impl(const float* x, int64_t N, int64_t C, int64_t HW, i
         const int rc = launch_stats_group(x, gp, sa, gws, gws_bytes, flags & 1u, (hipStream_t)stream, nullptr, dry);
         return (dry && rc == 0) ? 2 : rc;
     }
-    const int rc = launch_stats_flat(x, gp, sa, gws, flags & 1u, N * C * HW * 4 > NT_BYTES, (hipStream_t)stream, nullptr, dry);
+    const int rc = launch_stats_flat(x, gp, sa, gws, flags & 1u, nt_loads(N * C * HW * 4), hs(stream), nullptr, dry);
     return (dry && rc == 0) ? 1 : rc;
 }
 
 int cnnq_pc_stats_single(const float* x, int64_t N, int64_t C, int64_t HW, int need_b, int need_kurt, int need_relu, void* gws,
                          size_t gws_bytes, double* mom, float* stats, unsigned flags, void* stream) {
-    if (!x || !stats || (gws && ((uintptr_t)gws & 127)) || ((uintptr_t)mom & 7)) return CNNQ_EINVAL;
+    if (!x || !stats || misaligned(gws, 128) || misaligned(mom, 8)) return CNNQ_EINVAL;
     if (!gws) return CNNQ_ENOTSUP;
     return stats_single_impl(x, N, C, HW, need_b, need_kurt, need_relu, gws, gws_bytes, mom, stats, flags, stream, al16(x), false);
 }
@@ -232,8 +275,7 @@ int cnnq_pc_combine_dev(const double* part2, int G, int64_t C, const double* mom
                         float* stats, void* stream) {
     if (!part2 || G <= 0 || C <= 0 || C >= ((int64_t)1 << 31) || (!dev_out && !stats) || (stats && !mom))
         return CNNQ_EINVAL;
-    const dim3 grid((unsigned)((C + merge_cpw(G, (int)C) - 1) / merge_cpw(G, (int)C))), block(TPB);
-    hipLaunchKernelGGL(k_combine_dev, grid, block, 0, (hipStream_t)stream, part2, G, (int)C, mom, want_kurt, dev_out,
+    hipLaunchKernelGGL(k_combine_dev, merge_grid(G, C), dim3(TPB), 0, (hipStream_t)stream, part2, G, (int)C, mom, want_kurt, dev_out,
                        stats);
     return launch_status();
 }
@@ -241,14 +283,10 @@ int cnnq_pc_combine_dev(const double* part2, int G, int64_t C, const double* mom
 int cnnq_pc_params(const float* stats, int64_t C, const cnnq_params_cfg* cfg, float* qp, float* diag,
                    void* stream) {
     if (!stats || !cfg || !qp || C <= 0 || C >= ((int64_t)1 << 31)) return CNNQ_EINVAL;
-    if (cfg->num_bits < 1 || cfg->num_bits > 32 || cfg->clip < 0 || cfg->clip > 3) return CNNQ_EINVAL;
-    // the ACIQ factor tables have entries for 0..8 bits only (iq.py:14-41: the reference's alpha_laplace / alpha_gaus
-    // dictionaries raise KeyError beyond 8); wider codes are accepted for min/max and the '<p>std' clip alone
-    if ((cfg->clip == 1 || cfg->clip == 2) && cfg->num_bits > 8) return CNNQ_EINVAL;
-    if (cfg->bit_alloc && cfg->num_bits <= 4 && !diag) return CNNQ_EINVAL;  // bit table lives in diag
+    if (check_cfg(cfg)) return CNNQ_EINVAL;
+    if (cfg_bit_alloc(cfg) && !diag) return CNNQ_EINVAL;  // bit table lives in diag
     float* bits_ws = diag ? diag + (size_t)CNNQ_DIAG_BITS * C : nullptr;
-    const int threads = (int)(C >= PTPB ? PTPB : ((C + 63) / 64) * 64);
-    hipLaunchKernelGGL(k_params, dim3(1), dim3(threads), 0, (hipStream_t)stream, stats, (int)C, *cfg, qp, diag,
+    hipLaunchKernelGGL(k_params, dim3(1), dim3(param_threads(C)), 0, (hipStream_t)stream, stats, (int)C, *cfg, qp, diag,
                        bits_ws);
     return launch_status();
 }
@@ -278,39 +316,29 @@ size_t cnnq_pc_qerr_workspace(int64_t N, int64_t C, int64_t HW, int K) {
 
 int cnnq_pc_qerr(const float* x, int64_t N, int64_t C, int64_t HW, const float* qp, int K, const float* mm, void* ws, float* err,
                  void* stream) {
-    if (!x || !qp || !ws || !err || K < 1 || K > 3 || N < 1 || C < 1 || HW < 1 || ((uintptr_t)ws & 7)) return CNNQ_EINVAL;
+    if (!x || !qp || !ws || !err || K < 1 || K > 3 || N < 1 || C < 1 || HW < 1 || misaligned(ws, 8)) return CNNQ_EINVAL;
     Variant v;
     Geo g;
     const int rc = qerr_plan(N, C, HW, al16(x), &v, &g);
     if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = hs(stream);
     double* rec = reinterpret_cast<double*>(ws);
-#define LAUNCH_QE_K(VEC, A, J, KK)                                                                                  \
-    do {                                                                                                            \
-        if (mm) hipLaunchKernelGGL((k_qerr<VEC, A, J, KK, true>), grid, block, 0, st, x, g, qp, mm, rec);     \
-        else hipLaunchKernelGGL((k_qerr<VEC, A, J, KK, false>), grid, block, 0, st, x, g, qp, mm, rec);       \
-    } while (0)
-#define LAUNCH_QE(VEC, A, J)                        \
-    do {                                            \
-        if (K == 1) LAUNCH_QE_K(VEC, A, J, 1);      \
-        else if (K == 2) LAUNCH_QE_K(VEC, A, J, 2); \
-        else LAUNCH_QE_K(VEC, A, J, 3);             \
-    } while (0)
-    if (v.vec == 4 && v.A == 1) {
-        if (v.J == 2) LAUNCH_QE(4, 1, 2);
-        else LAUNCH_QE(4, 1, 1);
-    } else if (v.vec == 4) LAUNCH_QE(4, 4, 1);
-    else LAUNCH_QE(1, 1, 2);
-#undef LAUNCH_QE
-#undef LAUNCH_QE_K
+    with_shape(v, [&](auto s) {
+        with_int<1, 2, 3>(K, [&](auto k) {
+            with_bool(mm != nullptr, [&](auto m) {
+                using S = decltype(s);
+                constexpr int J = S::J > 2 ? 2 : S::J;          // qerr_plan's bound
+                hipLaunchKernelGGL((k_qerr<S::VEC, S::A, J, decltype(k)::value, decltype(m)::value>), geo_grid(g), dim3(TPB), 0, st, x, g, qp, mm, rec);
+            });
+        });
+    });
     const int rc2 = launch_status();
     if (rc2) return rc2;
     const int nb = g.mode == 1 ? g.nb : 1;
-    const dim3 fgrid((unsigned)((C + QF_CH - 1) / QF_CH));
-    if (K == 1) hipLaunchKernelGGL((k_qerr_fold<1>), fgrid, block, 0, st, rec, (int)N, nb, (int)C, (int)HW, err);
-    else if (K == 2) hipLaunchKernelGGL((k_qerr_fold<2>), fgrid, block, 0, st, rec, (int)N, nb, (int)C, (int)HW, err);
-    else hipLaunchKernelGGL((k_qerr_fold<3>), fgrid, block, 0, st, rec, (int)N, nb, (int)C, (int)HW, err);
+    with_int<1, 2, 3>(K, [&](auto k) {
+        hipLaunchKernelGGL((k_qerr_fold<decltype(k)::value>), dim3((unsigned)((C + QF_CH - 1) / QF_CH)), dim3(TPB), 0, st, rec, (int)N, nb, (int)C,
+                           (int)HW, err);
+    });
     return launch_status();
 }
 
@@ -326,7 +354,7 @@ int cnnq_pc_qdq_strided(const float* x, float* y, int64_t N, int64_t C, int64_t 
     if (!x || !y || !qp || !strided_ok(C, HW, sample_stride)) return CNNQ_EINVAL;
     Variant v;
     Geo g;
-    const bool al = al16(x) && al16(y) && (!codes || ((uintptr_t)codes & 3) == 0) && sample_stride % 4 == 0;
+    const bool al = al16(x) && al16(y) && !misaligned(codes, 4) && sample_stride % 4 == 0;
     // the histogram variant zeroes and flushes an LDS table per workgroup: keep its workgroups long
     const int rc = plan(N, C, HW, al, reverse ? 1 : 0, &v, &g, /*fine=*/hist ? 0 : 1);
     if (rc) return rc;
@@ -339,66 +367,40 @@ int cnnq_pc_qdq(const float* x, float* y, int64_t N, int64_t C, int64_t HW, cons
     return cnnq_pc_qdq_strided(x, y, N, C, HW, 0, qp, codes, hist, reverse, stream);
 }
 
-// stored-format codes: bits = 4 (two per byte) or 8 (one per byte)
-static int quantize_codes(const float* x, uint8_t* packed, int64_t N, int64_t C, int64_t HW, const float* qp, int bits,
-                          void* stream) {
-    if (!x || !packed || !qp) return CNNQ_EINVAL;
-    if (HW % 4 != 0 || !al16(x) || ((uintptr_t)packed & (bits == 4 ? 1 : 3))) return CNNQ_EINVAL;   // whole float4s
+// stored-format codes: bits = 4 (two per byte) or 8 (one per byte); x != NULL: x -> packed, else packed -> y
+static int codes_launch(const float* x, float* y, uint8_t* packed, int64_t N, int64_t C, int64_t HW, const float* qp, int bits, void* stream) {
+    const float* t = x ? x : y;
+    if (!t || !packed || !qp) return CNNQ_EINVAL;
+    if (HW % 4 != 0 || !al16(t) || misaligned(packed, bits == 4 ? 2 : 4)) return CNNQ_EINVAL;   // whole float4s
     Variant v;
     Geo g;
     const int rc = plan(N, C, HW, true, 0, &v, &g, /*fine=*/1);
     if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_QP(J)                                                                              \
-    do {                                                                                          \
-        if (bits == 4) hipLaunchKernelGGL((k_q_pack4<J, 4>), grid, block, 0, st, x, packed, g, qp); \
-        else hipLaunchKernelGGL((k_q_pack4<J, 8>), grid, block, 0, st, x, packed, g, qp);           \
-    } while (0)
-    if (v.J == 4) LAUNCH_QP(4);
-    else if (v.J == 2) LAUNCH_QP(2);
-    else LAUNCH_QP(1);
-#undef LAUNCH_QP
-    return launch_status();
-}
-
-static int dequantize_codes(const uint8_t* packed, float* y, int64_t N, int64_t C, int64_t HW, const float* qp, int bits,
-                            void* stream) {
-    if (!packed || !y || !qp) return CNNQ_EINVAL;
-    if (HW % 4 != 0 || !al16(y) || ((uintptr_t)packed & (bits == 4 ? 1 : 3))) return CNNQ_EINVAL;
-    Variant v;
-    Geo g;
-    const int rc = plan(N, C, HW, true, 0, &v, &g, /*fine=*/1);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_UP(J)                                                                                 \
-    do {                                                                                             \
-        if (bits == 4) hipLaunchKernelGGL((k_unpack4_dq<J, 4>), grid, block, 0, st, packed, y, g, qp); \
-        else hipLaunchKernelGGL((k_unpack4_dq<J, 8>), grid, block, 0, st, packed, y, g, qp);           \
-    } while (0)
-    if (v.J == 4) LAUNCH_UP(4);
-    else if (v.J == 2) LAUNCH_UP(2);
-    else LAUNCH_UP(1);
-#undef LAUNCH_UP
+    with_int<4, 2, 1>(v.J, [&](auto j) {
+        with_bool(bits == 4, [&](auto b4) {
+            constexpr int J = decltype(j)::value, BITS = decltype(b4)::value ? 4 : 8;
+            if (x) hipLaunchKernelGGL((k_q_pack4<J, BITS>), geo_grid(g), dim3(TPB), 0, hs(stream), x, packed, g, qp);
+            else hipLaunchKernelGGL((k_unpack4_dq<J, BITS>), geo_grid(g), dim3(TPB), 0, hs(stream), packed, y, g, qp);
+        });
+    });
     return launch_status();
 }
 
 int cnnq_pc_quantize_pack4(const float* x, uint8_t* packed, int64_t N, int64_t C, int64_t HW, const float* qp,
                            void* stream) {
-    return quantize_codes(x, packed, N, C, HW, qp, 4, stream);
+    return codes_launch(x, nullptr, packed, N, C, HW, qp, 4, stream);
 }
 int cnnq_pc_dequantize_pack4(const uint8_t* packed, float* y, int64_t N, int64_t C, int64_t HW, const float* qp,
                              void* stream) {
-    return dequantize_codes(packed, y, N, C, HW, qp, 4, stream);
+    return codes_launch(nullptr, y, const_cast<uint8_t*>(packed), N, C, HW, qp, 4, stream);
 }
 int cnnq_pc_quantize_u8(const float* x, uint8_t* codes, int64_t N, int64_t C, int64_t HW, const float* qp,
                         void* stream) {
-    return quantize_codes(x, codes, N, C, HW, qp, 8, stream);
+    return codes_launch(x, nullptr, codes, N, C, HW, qp, 8, stream);
 }
 int cnnq_pc_dequantize_u8(const uint8_t* codes, float* y, int64_t N, int64_t C, int64_t HW, const float* qp,
                           void* stream) {
-    return dequantize_codes(codes, y, N, C, HW, qp, 8, stream);
+    return codes_launch(nullptr, y, const_cast<uint8_t*>(codes), N, C, HW, qp, 8, stream);
 }
 
 // variable-width packed codes (bit allocation as the stored format)
@@ -436,28 +438,34 @@ static int packed_launch(bool quant, const float* x, float* y, uint8_t* packed, 
         }
         if (form == 3) return CNNQ_ENOTSUP;
     }
-    if (quant && form != 1) {
+    // the lean form of either direction (k_pack_lean / k_unpack_lean: one channel per wave) on the tensor t: whole-float4 rows of
+    // an aligned t, or (RAG) any row of at least 8 elements: its slots are 4-byte aligned; the load direction reads the packed
+    // stream as dwords.  1: launched; 0: the geometry does not allow it; CNNQ_ERANGE
+    auto lean = [&](const float* t) -> int {
         const int64_t nsl = 2 * ngroups;
         const int64_t rpc = nsl <= 128 ? 128 / nsl : 1;
-        // whole-float4 rows of an aligned x, or (RAG) any row of at least 8 elements: its slots are 4-byte aligned
         const bool rag = HW % 4 != 0;
-        const bool lean_ok = (rag ? HW >= 8 && ((uintptr_t)x & 3) == 0 : al16(x)) && rpc * C * HW * 4 < ((int64_t)1 << 32);
-        if (lean_ok) {
-            // ~8 KB of x per wave (32 KB per workgroup of four adjacent channels), whole chunks of rows
-            static const int64_t wave_bytes = env_int("CNNQ_PACK_WAVE_BYTES", 8192);   // development knob
-            int64_t rpw = (wave_bytes + HW * 2) / (HW * 4);
-            if (rpw < 1) rpw = 1;
-            rpw = ((rpw + rpc - 1) / rpc) * rpc;
-            const int64_t Sl = (N + rpw - 1) / rpw, ncb4 = (C + 3) / 4;
-            if (Sl * ncb4 >= (int64_t)1 << 31) return CNNQ_ERANGE;
-            const dim3 lgrid((unsigned)(Sl * ncb4)), lblock(TPB);
-            hipStream_t lst = (hipStream_t)stream;
-#define LAUNCH_LEAN(S, R) hipLaunchKernelGGL((k_pack_lean<S, R>), lgrid, lblock, 0, lst, x, packed, (int)N, (int)C, (int)HW, (int)rpw, qp, bits, rowoff)
-            if (nsl <= 128) { if (rag) LAUNCH_LEAN(true, true); else LAUNCH_LEAN(true, false); }
-            else { if (rag) LAUNCH_LEAN(false, true); else LAUNCH_LEAN(false, false); }
-#undef LAUNCH_LEAN
-            return launch_status();
-        }
+        if (!((rag ? HW >= 8 && !misaligned(t, 4) : al16(t)) && (quant || !misaligned(packed, 4)) && rpc * C * HW * 4 < ((int64_t)1 << 32))) return 0;
+        // ~8 KB of x per wave (32 KB per workgroup of four adjacent channels), whole chunks of rows
+        int64_t wave_bytes;                                                          // development knobs
+        if (quant) { static const int64_t v = env_int("CNNQ_PACK_WAVE_BYTES", 8192); wave_bytes = v; }
+        else { static const int64_t v = env_int("CNNQ_UNPACK_WAVE_BYTES", 8192); wave_bytes = v; }
+        int64_t rpw = (wave_bytes + HW * 2) / (HW * 4);
+        if (rpw < 1) rpw = 1;
+        rpw = ((rpw + rpc - 1) / rpc) * rpc;
+        const int64_t Sl = (N + rpw - 1) / rpw, ncb4 = (C + 3) / 4;
+        if (Sl * ncb4 >= (int64_t)1 << 31) return CNNQ_ERANGE;
+        const dim3 lgrid((unsigned)(Sl * ncb4)), lblock(TPB);
+        with_bool(nsl <= 128, rag, [&](auto sh, auto r) {
+            constexpr bool S = decltype(sh)::value, R = decltype(r)::value;
+            if (quant) hipLaunchKernelGGL((k_pack_lean<S, R>), lgrid, lblock, 0, hs(stream), x, packed, (int)N, (int)C, (int)HW, (int)rpw, qp, bits, rowoff);
+            else hipLaunchKernelGGL((k_unpack_lean<S, R>), lgrid, lblock, 0, hs(stream), packed, y, (int)N, (int)C, (int)HW, (int)rpw, qp, bits, rowoff);
+        });
+        return 1;
+    };
+    if (quant && form != 1) {
+        const int rc = lean(x);
+        if (rc) return rc < 0 ? rc : launch_status();
         if (form == 2) return CNNQ_ENOTSUP;
     }
     if (!quant && (form == 0 || form == 3)) {
@@ -470,49 +478,31 @@ static int packed_launch(bool quant, const float* x, float* y, uint8_t* packed, 
             const unsigned total4 = (unsigned)((total + 3) / 4), tail = (unsigned)(total - (int64_t)(total4 - 1) * 4);
             hipStream_t fst = (hipStream_t)stream;
             static const int U = env_int("CNNQ_UNPACK_U", 4);                     // development knob: float4 per lane
-            const dim3 fblock(TPB);
-#define LAUNCH_UF(R, UU) hipLaunchKernelGGL((k_unpack_flat<R, UU>), dim3((total4 + TPB * UU - 1) / (TPB * UU)), fblock, 0, fst, packed, y, (int)N, (int)C, (int)HW, qp, bits, rowoff, total4, tail)
-            if (HW % 4 == 0) { if (U == 1) LAUNCH_UF(1, 1); else if (U == 2) LAUNCH_UF(1, 2); else if (U == 8) LAUNCH_UF(1, 8); else LAUNCH_UF(1, 4); }
-            else if (HW >= 4) { if (U == 1) LAUNCH_UF(2, 1); else if (U == 2) LAUNCH_UF(2, 2); else LAUNCH_UF(2, 4); }
-            else LAUNCH_UF(4, 1);
-#undef LAUNCH_UF
+            // R = 1: whole-float4 rows, 2: rows of at least 4 elements, 4: shorter ones; U = 8 exists for R = 1 alone, R = 4 takes U = 1
+            with_int<1, 2, 4>(HW % 4 == 0 ? 1 : HW >= 4 ? 2 : 4, [&](auto r) {
+                with_int<1, 2, 8, 4>(U, [&](auto u) {
+                    constexpr int R = decltype(r)::value, UU = R == 4 ? 1 : (R == 2 && decltype(u)::value == 8) ? 4 : decltype(u)::value;
+                    hipLaunchKernelGGL((k_unpack_flat<R, UU>), dim3((total4 + TPB * UU - 1) / (TPB * UU)), dim3(TPB), 0, fst, packed, y, (int)N, (int)C,
+                                       (int)HW, qp, bits, rowoff, total4, tail);
+                });
+            });
             return launch_status();
         }
         if (form == 3) return CNNQ_ENOTSUP;
     }
     if (!quant && form != 1 && form != 3) {
-        // the load direction's lean form (k_unpack_lean): the same geometry; the packed stream is read as dwords
-        const int64_t nsl = 2 * ngroups;
-        const int64_t rpc = nsl <= 128 ? 128 / nsl : 1;
-        const bool rag = HW % 4 != 0;
-        const bool lean_ok = (rag ? HW >= 8 && ((uintptr_t)y & 3) == 0 : al16(y)) && ((uintptr_t)packed & 3) == 0 &&
-                             rpc * C * HW * 4 < ((int64_t)1 << 32);
-        if (lean_ok) {
-            static const int64_t wave_bytes = env_int("CNNQ_UNPACK_WAVE_BYTES", 8192);   // development knob
-            int64_t rpw = (wave_bytes + HW * 2) / (HW * 4);
-            if (rpw < 1) rpw = 1;
-            rpw = ((rpw + rpc - 1) / rpc) * rpc;
-            const int64_t Sl = (N + rpw - 1) / rpw, ncb4 = (C + 3) / 4;
-            if (Sl * ncb4 >= (int64_t)1 << 31) return CNNQ_ERANGE;
-            const dim3 lgrid((unsigned)(Sl * ncb4)), lblock(TPB);
-            hipStream_t lst = (hipStream_t)stream;
-#define LAUNCH_ULEAN(S, R) hipLaunchKernelGGL((k_unpack_lean<S, R>), lgrid, lblock, 0, lst, packed, y, (int)N, (int)C, (int)HW, (int)rpw, qp, bits, rowoff)
-            if (nsl <= 128) { if (rag) LAUNCH_ULEAN(true, true); else LAUNCH_ULEAN(true, false); }
-            else { if (rag) LAUNCH_ULEAN(false, true); else LAUNCH_ULEAN(false, false); }
-#undef LAUNCH_ULEAN
-            return launch_status();
-        }
+        const int rc = lean(y);
+        if (rc) return rc < 0 ? rc : launch_status();
         if (form == 2) return CNNQ_ENOTSUP;
     }
     const dim3 grid((unsigned)(ncb * S)), block(TPB);
     static const int64_t rows_min = env_int("CNNQ_PACK_ROWS_MIN", 256);   // development knob (slots per row)
     const bool rows_form = 2 * ngroups >= rows_min;
     hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_PK(Q, R) \
-    hipLaunchKernelGGL((k_packed<Q, R>), grid, block, 0, st, x, y, packed, (int)N, (int)C, (int)HW, (int)S, (int)k, qp, bits, rowoff)
-    if (quant) { if (rows_form) LAUNCH_PK(true, true); else LAUNCH_PK(true, false); }
-    else { if (rows_form) LAUNCH_PK(false, true); else LAUNCH_PK(false, false); }
-#undef LAUNCH_PK
+    with_bool(quant, rows_form, [&](auto q, auto r) {
+        hipLaunchKernelGGL((k_packed<decltype(q)::value, decltype(r)::value>), grid, block, 0, st, x, y, packed, (int)N, (int)C, (int)HW, (int)S, (int)k,
+                           qp, bits, rowoff);
+    });
     return launch_status();
 }
 
@@ -558,16 +548,12 @@ int cnnq_pc_minmax_strided(const float* x, int64_t N, int64_t C, int64_t HW, int
     const int rc = plan(N, C, HW, al16(x) && sample_stride % 4 == 0, 0, &v, &g);
     if (rc) return rc;
     if (sample_stride) g.P = (int)sample_stride;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-    const bool ntl = N * C * HW * 4 > NT_BYTES;
-#define LAUNCH_MM(VEC, A, J)                                                                         \
-    do {                                                                                             \
-        if (ntl) hipLaunchKernelGGL((k_minmax<VEC, A, J, true>), grid, block, 0, st, x, g, pmm);       \
-        else hipLaunchKernelGGL((k_minmax<VEC, A, J, false>), grid, block, 0, st, x, g, pmm);          \
-    } while (0)
-    CNNQ_DISPATCH(v, LAUNCH_MM);
-#undef LAUNCH_MM
+    with_shape(v, [&](auto s) {
+        with_bool(nt_loads(N * C * HW * 4), [&](auto nt) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((k_minmax<S::VEC, S::A, S::J, decltype(nt)::value>), geo_grid(g), dim3(TPB), 0, hs(stream), x, g, pmm);
+        });
+    });
     return launch_status();
 }
 
@@ -595,7 +581,7 @@ int cnnq_pc_minmax_qdq(const float* x, float* y, int64_t N, int64_t C, int64_t H
     if (!x || !y || !pmm || !qp || num_bits < 1 || num_bits > 32) return CNNQ_EINVAL;
     if ((codes || hist) && num_bits > 8) return CNNQ_EINVAL;   // one byte per code, 256 histogram bins
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
+    if (G <= 0) return g_error(G);
     int rc = cnnq_pc_minmax(x, N, C, HW, pmm, stream);
     if (rc) return rc;
     rc = cnnq_pc_minmax_params(pmm, G, C, num_bits, positive, qp, stream);
@@ -697,7 +683,7 @@ int cnnq_pc_group_describe(int64_t N, int64_t C, int64_t HW, int32_t out[8]) {
 
 int cnnq_pc_minmax_qdq_group(const float* x, float* y, int64_t N, int64_t C, int64_t HW, int num_bits, int positive,
                              void* ws, float* qp, float* mm, unsigned flags, void* stream) {
-    if (!x || !y || !ws || !qp || num_bits < 1 || num_bits > 32 || ((uintptr_t)ws & 127)) return CNNQ_EINVAL;
+    if (!x || !y || !ws || !qp || num_bits < 1 || num_bits > 32 || misaligned(ws, 128)) return CNNQ_EINVAL;
     GPlan p;
     const int rc = plan_group(N, C, HW, al16(x) && al16(y), &p, true, flat_lds_rows(0, false));
     if (rc) return rc;
@@ -710,7 +696,7 @@ int cnnq_pc_minmax_qdq_group(const float* x, float* y, int64_t N, int64_t C, int
 int cnnq_pc_minmax_local(const float* x, int64_t N, int64_t C, int64_t HW, float* pmm, float* local, void* stream) {
     if (!x || !pmm || !local) return CNNQ_EINVAL;
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
+    if (G <= 0) return g_error(G);
     const int rc = cnnq_pc_minmax(x, N, C, HW, pmm, stream);
     if (rc) return rc;
     return cnnq_pc_minmax_reduce(pmm, G, C, local, stream);
@@ -724,7 +710,7 @@ int cnnq_pc_minmax_local_auto(const float* x, int64_t N, int64_t C, int64_t HW, 
     // tensors beyond the Infinity Cache keep the streaming k_minmax (6.5-6.9 TB/s against ~5.5 for 128 KB register
     // tiles; one launch boundary is nothing next to their 60+ us)
     static const int64_t max_bytes = env_int("CNNQ_LOCAL_GROUP_MAX_MB", 384) * ((int64_t)1 << 20);   // development knob
-    if (gws && !((uintptr_t)gws & 127) && N * C * HW * 4 <= max_bytes) {
+    if (gws && !misaligned(gws, 128) && N * C * HW * 4 <= max_bytes) {
         GPlan p;
         if (plan_group(N, C, HW, al16(x), &p, /*allow_flat=*/false) == 0 && p.ws_bytes <= gws_bytes)
             return launch_minmax_group(x, p, gws, local, (hipStream_t)stream);
@@ -747,37 +733,45 @@ int cnnq_pc_gathered_qdq(const float* x, float* y, int64_t N, int64_t C, int64_t
 
 // Config 2 behind ONE call: the resident single launch when the shape has one, else the group-exchange single
 // launch (needs gws), else the three-launch chain.  ws layout (floats): qp[CNNQ_NQP][C], mm[2][C], pmm[G][2][C].
+struct MmWs {
+    float *qp, *mm, *pmm;
+    MmWs(float* ws, int64_t C) : qp(ws), mm(ws + (size_t)CNNQ_NQP * C), pmm(mm + 2 * (size_t)C) {}
+    static size_t bytes(int G, int64_t C) { return ((size_t)CNNQ_NQP + 2 + 2 * (size_t)G) * (size_t)C * sizeof(float); }
+};
+
 size_t cnnq_pc_minmax_qdq_workspace(int64_t N, int64_t C, int64_t HW) {
     const int g1 = cnnq_pc_groups(N, C, HW, 1), g0 = cnnq_pc_groups(N, C, HW, 0);
     const int G = g1 > g0 ? g1 : g0;
-    if (G <= 0) return 0;
-    return ((size_t)CNNQ_NQP + 2 + 2 * (size_t)G) * (size_t)C * sizeof(float);
+    return G <= 0 ? 0 : MmWs::bytes(G, C);
+}
+
+// Config 2's single-launch route: the whole-channel form when the shape has one and it is not starved, else the group form,
+// else whole.  group_ok: the caller's own group plan fits (each caller plans the group form with its own arguments, on purpose).
+enum { ROUTE_NONE = 0, ROUTE_WHOLE, ROUTE_GROUP };
+static int mm_route(int64_t N, int64_t C, int64_t HW, bool aligned16, bool group_ok, WPlan* wp) {
+    // whole channels per workgroup needs no exchange, but with fewer channel blocks than ~3/4 of the CUs it leaves
+    // the chip idle: [64,128,28,28] = 128 workgroups takes 17.8 us, the group form (1024 tiles) 13.4
+    const bool whole_ok = plan_whole(N, C, HW, aligned16, wp) == 0;
+    if (whole_ok && !(group_ok && wp->wgs < RES_MIN_WGS)) return ROUTE_WHOLE;
+    return group_ok ? ROUTE_GROUP : whole_ok ? ROUTE_WHOLE : ROUTE_NONE;
 }
 
 int cnnq_pc_minmax_qdq_auto(const float* x, float* y, int64_t N, int64_t C, int64_t HW, int num_bits, int positive,
                             float* ws, void* gws, size_t gws_bytes, int allow_single_launch, void* stream) {
     if (!x || !y || !ws || num_bits < 1 || num_bits > 32 || C <= 0) return CNNQ_EINVAL;
-    float* qp = ws;
-    float* mm = ws + (size_t)CNNQ_NQP * C;
-    float* pmm = mm + 2 * (size_t)C;
+    const MmWs w(ws, C);
     if (allow_single_launch) {
         const size_t gneed = gws ? cnnq_pc_group_workspace(N, C, HW) : 0;
-        const bool group_ok = gneed > 0 && gneed <= gws_bytes;
-        // whole channels per workgroup needs no exchange, but with fewer channel blocks than ~3/4 of the CUs it leaves
-        // the chip idle: [64,128,28,28] = 128 workgroups takes 17.8 us, the group form (1024 tiles) 13.4
         WPlan wp;
-        const bool whole_ok = plan_whole(N, C, HW, al16(x) && al16(y), &wp) == 0;
-        int rc = CNNQ_ENOTSUP;
-        if (whole_ok && !(group_ok && wp.wgs < RES_MIN_WGS))
-            rc = cnnq_pc_minmax_qdq_resident(x, y, N, C, HW, num_bits, positive, qp, mm, stream);
-        if (rc != CNNQ_ENOTSUP) return rc;
-        if (group_ok) {
-            rc = cnnq_pc_minmax_qdq_group(x, y, N, C, HW, num_bits, positive, gws, qp, mm, 0u, stream);
+        int route = mm_route(N, C, HW, al16(x) && al16(y), gneed > 0 && gneed <= gws_bytes, &wp);
+        if (route == ROUTE_GROUP) {
+            const int rc = cnnq_pc_minmax_qdq_group(x, y, N, C, HW, num_bits, positive, gws, w.qp, w.mm, 0u, stream);
             if (rc != CNNQ_ENOTSUP) return rc;
+            route = mm_route(N, C, HW, al16(x) && al16(y), false, &wp);      // no group plan for these pointers after all
         }
-        if (whole_ok) return cnnq_pc_minmax_qdq_resident(x, y, N, C, HW, num_bits, positive, qp, mm, stream);
+        if (route == ROUTE_WHOLE) return launch_whole(x, y, wp, num_bits, positive ? 1 : 0, w.qp, w.mm, hs(stream));
     }
-    return cnnq_pc_minmax_qdq(x, y, N, C, HW, num_bits, positive, pmm, qp, nullptr, nullptr, stream);
+    return cnnq_pc_minmax_qdq(x, y, N, C, HW, num_bits, positive, w.pmm, w.qp, nullptr, nullptr, stream);
 }
 
 // Config 2 in ONE launch with the outputs the chain form used to be needed for: the uint8 codes, the code histogram
@@ -789,24 +783,19 @@ int cnnq_pc_minmax_qdq_single(const float* x, float* y, int64_t N, int64_t C, in
                               void* gws, size_t gws_bytes, float* qp, float* mm, uint8_t* codes, uint64_t* hist_rep,
                               uint8_t* packed, void* stream) {
     if (!x || !qp || num_bits < 1 || num_bits > 32 || C <= 0) return CNNQ_EINVAL;
-    if (packed ? (y || codes || hist_rep || num_bits > 4 || ((uintptr_t)packed & 1)) : !y) return CNNQ_EINVAL;
+    if (packed ? (y || codes || hist_rep || num_bits > 4 || misaligned(packed, 2)) : !y) return CNNQ_EINVAL;
     if ((codes || hist_rep) && num_bits > 8) return CNNQ_EINVAL;
-    if (((uintptr_t)codes & 3) || ((uintptr_t)hist_rep & 7) || (gws && ((uintptr_t)gws & 127))) return CNNQ_EINVAL;
+    if (misaligned(codes, 4) || misaligned(hist_rep, 8) || misaligned(gws, 128)) return CNNQ_EINVAL;
     const int out = packed ? 2 : (codes || hist_rep) ? 1 : 0;
-    XOut xo;
-    xo.codes = codes;
-    xo.hist = reinterpret_cast<unsigned long long*>(hist_rep);
-    xo.packed = packed;
+    const XOut xo = xout(codes, hist_rep, packed);
     const bool al = al16(x) && (packed ? true : al16(y));
     GPlan gp;
     const bool group_ok = gws && plan_group(N, C, HW, al, &gp, true, flat_lds_rows(out, false)) == 0 && gp.ws_bytes <= gws_bytes;
     WPlan wp;
-    const bool whole_ok = plan_whole(N, C, HW, al, &wp) == 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (whole_ok && !(group_ok && wp.wgs < RES_MIN_WGS))
-        return launch_whole(x, y, wp, num_bits, positive ? 1 : 0, qp, mm, st, out, xo);
-    if (group_ok) return launch_group(x, y, gp, num_bits, positive ? 1 : 0, gws, qp, mm, 0u, st, out, xo);
-    if (whole_ok) return launch_whole(x, y, wp, num_bits, positive ? 1 : 0, qp, mm, st, out, xo);
+    switch (mm_route(N, C, HW, al, group_ok, &wp)) {
+    case ROUTE_WHOLE: return launch_whole(x, y, wp, num_bits, positive ? 1 : 0, qp, mm, hs(stream), out, xo);
+    case ROUTE_GROUP: return launch_group(x, y, gp, num_bits, positive ? 1 : 0, gws, qp, mm, 0u, hs(stream), out, xo);
+    }
     return CNNQ_ENOTSUP;
 }
 
@@ -845,43 +834,24 @@ static int xrank_launch(const float* x, float* y, int64_t N, int64_t C, int64_t 
                         bool lean = false) {
     if (!x || !y || !ws || num_bits < 1 || num_bits > 32 || C <= 0) return CNNQ_EINVAL;
     if (!windows || !status || world <= 0 || rank < 0 || rank >= world || (!seq && !seq_dev) || C > cmax || timeout_ticks <= 0) return CNNQ_EINVAL;
-    if (gws && ((uintptr_t)gws & 127)) return CNNQ_EINVAL;
+    if (misaligned(gws, 128)) return CNNQ_EINVAL;
     if ((codes || hist_rep) && num_bits > 8) return CNNQ_EINVAL;
-    if (((uintptr_t)codes & 3) || ((uintptr_t)hist_rep & 7) || ((uintptr_t)seq_dev & 3)) return CNNQ_EINVAL;
-    float* qp = ws;                                       // the layout of cnnq_pc_minmax_qdq_auto's workspace
-    float* mm = ws + (size_t)CNNQ_NQP * C;
-    float* pmm = mm + 2 * (size_t)C;
-    XRank xr;
-    xr.windows = windows;
-    xr.rank = rank;
-    xr.world = world;
+    if (misaligned(codes, 4) || misaligned(hist_rep, 8) || misaligned(seq_dev, 4)) return CNNQ_EINVAL;
+    const MmWs w(ws, C);                                  // the layout of cnnq_pc_minmax_qdq_auto's workspace
+    float *const qp = w.qp, *const mm = w.mm, *const pmm = w.pmm;
     if (zero_c < 0 || zero_c > cmax || (lean && !seq)) return CNNQ_EINVAL;
-    xr.seq = seq;
-    xr.seq_dev = seq ? nullptr : seq_dev;
-    xr.seq_mirror = (seq && lean) ? seq_dev : nullptr;
-    xr.zero_c = zero_c;
-    xr.cdev = seq_dev ? seq_dev + 4 : nullptr;            // round 6: the launches keep the slot counts themselves
-    xr.nslots = (int)C;
-    xr.slot0 = 0;
-    xr.no_prologue = 0;
-    xr.cmax = cmax;
-    xr.status = status;
-    xr.timeout = timeout_ticks;
+    const XRank xr = xrank_args(windows, rank, world, cmax, seq, seq_dev, lean, zero_c, (int)C, 0, status, timeout_ticks);
     const int out = (codes || hist_rep) ? 1 : 0;
-    XOut xo;
-    xo.codes = codes;
-    xo.hist = reinterpret_cast<unsigned long long*>(hist_rep);
-    xo.packed = nullptr;
+    const XOut xo = xout(codes, hist_rep);
     const bool al = al16(x) && al16(y);
     GPlan gp;
     const bool group_ok = gws && plan_group(N, C, HW, al, &gp) == 0 && gp.ws_bytes <= gws_bytes;
     WPlan wp;
-    const bool whole_ok = plan_whole(N, C, HW, al, &wp) == 0;
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = hs(stream);
+    const int route = mm_route(N, C, HW, al, group_ok, &wp);
     int rc;
-    if (whole_ok && !(group_ok && wp.wgs < RES_MIN_WGS)) rc = launch_whole(x, y, wp, num_bits, positive ? 1 : 0, qp, mm, st, out, xo, 0u, &xr);
-    else if (group_ok) rc = launch_group(x, y, gp, num_bits, positive ? 1 : 0, gws, qp, mm, 0u, st, out, xo, &xr);
-    else if (whole_ok) rc = launch_whole(x, y, wp, num_bits, positive ? 1 : 0, qp, mm, st, out, xo, 0u, &xr);
+    if (route == ROUTE_WHOLE) rc = launch_whole(x, y, wp, num_bits, positive ? 1 : 0, qp, mm, st, out, xo, 0u, &xr);
+    else if (route == ROUTE_GROUP) rc = launch_group(x, y, gp, num_bits, positive ? 1 : 0, gws, qp, mm, 0u, st, out, xo, &xr);
     else {
         // no single-launch kernel for this rank's shard (the ranks' shards may differ by a sample, and so may their plans):
         // the same window protocol around two passes - local extrema, one thread per channel pushes / waits / folds, Q/DQ
@@ -967,45 +937,81 @@ int cnnq_entropy_replicas(uint64_t* hist_rep, float* out, void* stream) {
 // when b is needed, merge, parameters (ACIQ clipping, bit allocation, scale / zero point), fused Q/DQ - six
 // launches (five since round 2: the first merge runs inside pass B), one host call, one caller workspace.  ws layout (doubles first): part[G][NMOM][C], mom[NMOM][C],
 // part2[G][NDEV][C], then floats stats[NSTAT][C].
+// (the channels_last form, cnnq_pc_aciq_qdq_nhwc, carves the same doubles with its slab count for G and keeps stats outside)
+struct AciqWs {
+    double *part, *mom, *part2;
+    float* stats;
+    AciqWs(void* ws, int G, int64_t C)
+        : part(reinterpret_cast<double*>(ws)), mom(part + (size_t)G * CNNQ_NMOM * C), part2(mom + (size_t)CNNQ_NMOM * C),
+          stats(reinterpret_cast<float*>(part2 + (size_t)G * CNNQ_NDEV * C)) {}
+    static size_t bytes(size_t G, int64_t C, bool with_stats) {
+        return (G * CNNQ_NMOM + CNNQ_NMOM + G * CNNQ_NDEV) * (size_t)C * sizeof(double) + (with_stats ? (size_t)CNNQ_NSTAT * (size_t)C * sizeof(float) : 0);
+    }
+};
+
 size_t cnnq_pc_aciq_workspace(int64_t N, int64_t C, int64_t HW, int aligned16) {
     const int G = cnnq_pc_groups(N, C, HW, aligned16);
-    if (G <= 0) return 0;
-    return ((size_t)G * CNNQ_NMOM + CNNQ_NMOM + (size_t)G * CNNQ_NDEV) * (size_t)C * sizeof(double) +
-           (size_t)CNNQ_NSTAT * (size_t)C * sizeof(float);
+    return G <= 0 ? 0 : AciqWs::bytes((size_t)G, C, true);
 }
 
 int cnnq_pc_aciq_qdq(const float* x, float* y, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws,
                      float* qp, float* diag, void* stream) {
-    if (!x || !y || !cfg || !ws || !qp || ((uintptr_t)ws & 7)) return CNNQ_EINVAL;
-    if (cfg->num_bits < 1 || cfg->num_bits > 32 || cfg->clip < 0 || cfg->clip > 3) return CNNQ_EINVAL;
-    if ((cfg->clip == 1 || cfg->clip == 2) && cfg->num_bits > 8) return CNNQ_EINVAL;   // as cnnq_pc_params, before any launch
+    if (!x || !y || !cfg || !ws || !qp || misaligned(ws, 8)) return CNNQ_EINVAL;
+    if (check_cfg(cfg)) return CNNQ_EINVAL;                                      // as cnnq_pc_params, before any launch
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
-    double* part = reinterpret_cast<double*>(ws);
-    double* mom = part + (size_t)G * CNNQ_NMOM * C;
-    double* part2 = mom + (size_t)CNNQ_NMOM * C;
-    float* stats = reinterpret_cast<float*>(part2 + (size_t)G * CNNQ_NDEV * C);
-    const bool use_ba = cfg->bit_alloc && cfg->num_bits <= 4;
-    const bool need_b = cfg->clip == 1 || (use_ba && cfg->prior_is_b);
-    hipStream_t st = (hipStream_t)stream;
+    if (G <= 0) return g_error(G);
+    const AciqWs w(ws, G, C);
+    const bool need_b = cfg->clip == 1 || (cfg_bit_alloc(cfg) && cfg->prior_is_b);
     // the merge kernels write every row of the table (zero for KURT, STD_POS; B without pass B)
-    int rc = cnnq_pc_moments(x, N, C, HW, 0, part, stream);
+    int rc = cnnq_pc_moments(x, N, C, HW, 0, w.part, stream);
     if (rc) return rc;
     if (need_b) {
         // pass B merges the pass-A records of its own channels in its prologue; one final merge writes all rows
-        rc = absdev_raw(x, N, C, HW, part, 0, part2, stream);
+        rc = launch_absdev(x, N, C, HW, nullptr, w.part, 0, w.part2, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_combine_all, dim3((unsigned)((C + merge_cpw(G, (int)C) - 1) / merge_cpw(G, (int)C))), dim3(TPB), 0, st, part, part2, G,
-                           (int)C, 0, 0, mom, stats);
-        rc = launch_status();
+        rc = combine_all(w.part, w.part2, G, C, 0, 0, w.mom, w.stats, stream);
     } else {
-        rc = cnnq_pc_combine(part, G, C, 0, mom, stats, stream);
+        rc = cnnq_pc_combine(w.part, G, C, 0, w.mom, w.stats, stream);
     }
     if (rc) return rc;
-    rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
+    rc = cnnq_pc_params(w.stats, C, cfg, qp, diag, stream);
     if (rc) return rc;
     // pass B walks the tensor descending, so the Q/DQ after it ascends; straight after pass A it descends
     return cnnq_pc_qdq(x, y, N, C, HW, qp, nullptr, nullptr, /*reverse=*/need_b ? 0 : 1, stream);
+}
+
+// the bit allocation in front of a fused launch (k_bitalloc on the std row): *bits = the table inside diag
+static int launch_bitalloc(const float* stats, int64_t C, const cnnq_params_cfg* cfg, float* diag, float** bits, hipStream_t st) {
+    *bits = diag + (size_t)CNNQ_DIAG_BITS * C;
+    hipLaunchKernelGGL(k_bitalloc, dim3(1), dim3(param_threads(C)), 0, st, stats + (size_t)CNNQ_STAT_STD * C, (int)C, *cfg, *bits);
+    return launch_status();
+}
+// launch_fused's arguments, mode 0 / mode 1; count_dev (the sharded forms): the global batch's count row, else count
+static FusedArgs fused_aciq(float* stats, const float* bits, float* qp, float* diag, const cnnq_params_cfg* cfg, double count, const double* count_dev) {
+    FusedArgs fa = {};
+    fa.stats = stats;
+    fa.bits = bits;
+    fa.qp = qp;
+    fa.diag = diag;
+    fa.cfg = *cfg;
+    fa.count = count;
+    fa.count_dev = count_dev;
+    return fa;
+}
+static FusedArgs fused_mt(float* stats, float* mt, const MtCfg& mcfg, uint64_t* hist, double count, const double* count_dev) {
+    FusedArgs fa = {};
+    fa.stats = stats;
+    fa.count = count;
+    fa.count_dev = count_dev;
+    fa.mt = mt;
+    fa.mcfg = mcfg;
+    fa.hist = u64p(hist);
+    return fa;
+}
+// omega and the clipping multiplier from the std alone (k_mt_params<GUESS>), in front of a fused mode-1 launch
+static int launch_mt_guess(const float* stats, int64_t C, const MtCfg& mcfg, const double* tables, int ntab, float* mt, hipStream_t st) {
+    hipLaunchKernelGGL(k_mt_params<true>, dim3(1), dim3(PTPB), 0, st, stats, (int)C, mcfg, tables, ntab, mt);
+    return launch_status();
 }
 
 // Config 3 with pass B, the parameters and the Q/DQ in ONE launch (cnnq_aciq.hip.h): pass A -> merge -> (bit allocation)
@@ -1017,57 +1023,37 @@ int cnnq_pc_aciq_qdq(const float* x, float* y, int64_t N, int64_t C, int64_t HW,
 int cnnq_pc_aciq_qdq_single(const float* x, float* y, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws,
                             void* gws, size_t gws_bytes, float* stats, float* qp, float* diag, uint8_t* codes,
                             uint64_t* hist_rep, unsigned flags, void* stream) {
-    if (!x || !y || !cfg || !ws || !stats || !qp || ((uintptr_t)ws & 7)) return CNNQ_EINVAL;
-    if (cfg->num_bits < 1 || cfg->num_bits > 32 || cfg->clip < 0 || cfg->clip > 3) return CNNQ_EINVAL;
-    if ((cfg->clip == 1 || cfg->clip == 2) && cfg->num_bits > 8) return CNNQ_EINVAL;
-    if (((uintptr_t)codes & 3) || ((uintptr_t)hist_rep & 7) || (gws && ((uintptr_t)gws & 127))) return CNNQ_EINVAL;
-    const bool use_ba = cfg->bit_alloc && cfg->num_bits <= 4;
+    if (!x || !y || !cfg || !ws || !stats || !qp || misaligned(ws, 8)) return CNNQ_EINVAL;
+    if (check_cfg(cfg)) return CNNQ_EINVAL;
+    if (misaligned(codes, 4) || misaligned(hist_rep, 8) || misaligned(gws, 128)) return CNNQ_EINVAL;
+    const bool use_ba = cfg_bit_alloc(cfg);
     if (use_ba && !diag) return CNNQ_EINVAL;                     // the bit table lives in diag
     if (cfg->clip != 1 || cfg->direct_range || (use_ba && cfg->prior_is_b) || !gws) return CNNQ_ENOTSUP;
+    const int out = (codes || hist_rep) ? 1 : 0;
     GPlan gp;
-    // (with the codes / the histogram wanted the 160 KB tiles of a big channel have no instance - 32 KB of LDS rows next to the 32 KB
-    //  code table: planned without them, so that CNNQ_ENOTSUP comes BEFORE anything is enqueued: ADVICE r5)
-    if (plan_sums(N, C, HW, al16(x) && al16(y), &gp, (codes || hist_rep) ? 0 : 1) != 0 || gp.ws_bytes > gws_bytes) return CNNQ_ENOTSUP;
-    if ((size_t)gp.ngroups * gp.gstride * 8 > GRP_WS_SLOT_BYTES) return CNNQ_ENOTSUP;
-    if (gp.KL && !(gp.flat && gp.K == 32 && gp.KL == 8)) return CNNQ_ENOTSUP;
+    if (!plan_fused(0, N, C, HW, al16(x) && al16(y), gws_bytes, out, &gp)) return CNNQ_ENOTSUP;
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
+    if (G <= 0) return g_error(G);
     double* part = reinterpret_cast<double*>(ws);
-    hipStream_t st = (hipStream_t)stream;
     int rc = cnnq_pc_moments(x, N, C, HW, 0, part, stream);
     if (rc) return rc;
     rc = cnnq_pc_combine(part, G, C, 0, nullptr, stats, stream);
     if (rc) return rc;
     float* bits = nullptr;
-    if (use_ba) {
-        bits = diag + (size_t)CNNQ_DIAG_BITS * C;
-        const int threads = (int)(C >= PTPB ? PTPB : ((C + 63) / 64) * 64);
-        hipLaunchKernelGGL(k_bitalloc, dim3(1), dim3(threads), 0, st, stats + (size_t)CNNQ_STAT_STD * C, (int)C, *cfg, bits);
-        rc = launch_status();
-    }
+    if (use_ba) rc = launch_bitalloc(stats, C, cfg, diag, &bits, hs(stream));
     if (rc) return rc;
-    FusedArgs aa = {};
-    aa.stats = stats;
-    aa.bits = bits;
-    aa.qp = qp;
-    aa.diag = diag;
-    aa.cfg = *cfg;
-    aa.count = (double)N * (double)HW;
-    XOut xo;
-    xo.codes = codes;
-    xo.hist = reinterpret_cast<unsigned long long*>(hist_rep);
-    xo.packed = nullptr;
-    return launch_fused(0, x, y, gp, aa, gws, flags & 3u, st, (codes || hist_rep) ? 1 : 0, xo);
+    return launch_fused(0, x, y, gp, fused_aciq(stats, bits, qp, diag, cfg, (double)N * (double)HW, nullptr), gws, flags & 3u, hs(stream), out,
+                        xout(codes, hist_rep));
 }
 
 // ... behind ONE call with the chain as the fallback: ws as cnnq_pc_aciq_qdq (cnnq_pc_aciq_workspace bytes); the
 // statistics table is the one inside ws either way
 int cnnq_pc_aciq_qdq_auto(const float* x, float* y, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws,
                           void* gws, size_t gws_bytes, float* qp, float* diag, void* stream) {
-    if (!x || !y || !cfg || !ws || !qp || ((uintptr_t)ws & 7)) return CNNQ_EINVAL;
+    if (!x || !y || !cfg || !ws || !qp || misaligned(ws, 8)) return CNNQ_EINVAL;
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
-    float* stats = reinterpret_cast<float*>(reinterpret_cast<double*>(ws) + ((size_t)G * CNNQ_NMOM + CNNQ_NMOM + (size_t)G * CNNQ_NDEV) * C);
+    if (G <= 0) return g_error(G);
+    float* stats = AciqWs(ws, G, C).stats;
     const int rc = cnnq_pc_aciq_qdq_single(x, y, N, C, HW, cfg, ws, gws, gws_bytes, stats, qp, diag, nullptr, nullptr, 0u, stream);
     if (rc != CNNQ_ENOTSUP) return rc;
     return cnnq_pc_aciq_qdq(x, y, N, C, HW, cfg, ws, qp, diag, stream);
@@ -1077,22 +1063,11 @@ int cnnq_pc_aciq_qdq_auto(const float* x, float* y, int64_t N, int64_t C, int64_
 // (cnnq_xrank.hip.h; the same windows, numbering and status word as config 2's cnnq_pc_minmax_qdq_xrank_seq / _dev).  One host
 // call per tensor, ONE launch number, no collective: every statistic of the global batch travels through the windows.
 static int xr_from_ctx(const cnnq_xrank_ctx* xc, int64_t C, XRank* xr) {
-    if (!xc || !xc->windows || !xc->status || !xc->seq_dev || ((uintptr_t)xc->seq_dev & 3)) return CNNQ_EINVAL;
+    if (!xc || !xc->windows || !xc->status || !xc->seq_dev || misaligned(xc->seq_dev, 4)) return CNNQ_EINVAL;
     if (xc->world <= 0 || xc->rank < 0 || xc->rank >= xc->world || xc->timeout_ticks <= 0 || C <= 0 || C * ST_XW > xc->cmax) return CNNQ_EINVAL;
-    xr->windows = xc->windows;
-    xr->rank = xc->rank;
-    xr->world = xc->world;
-    xr->seq = xc->seq;
-    xr->seq_dev = xc->seq ? nullptr : xc->seq_dev;
-    xr->seq_mirror = xc->seq ? xc->seq_dev : nullptr;
-    xr->zero_c = 0;
-    xr->cdev = xc->seq_dev + 4;
-    xr->nslots = (int)(C * ST_XW);                       // the sums layout: eight words per channel
-    xr->slot0 = (int)(C * (ST_XW_COUNT + 1));            // word 6: sum |x - mean|
-    xr->no_prologue = 0;
-    xr->cmax = xc->cmax;
-    xr->status = xc->status;
-    xr->timeout = xc->timeout_ticks;
+    // the sums layout: eight words per channel; the fused kernels' sum |x - mean| is word 6
+    *xr = xrank_args(xc->windows, xc->rank, xc->world, xc->cmax, xc->seq, xc->seq_dev, true, 0, (int)(C * ST_XW), (int)(C * (ST_XW_COUNT + 1)),
+                     xc->status, xc->timeout_ticks);
     return 0;
 }
 // device numbering: the slots of the launch zeroed and the number advanced behind it (host numbering: the launch after next cleans up)
@@ -1132,42 +1107,28 @@ static int xr_pass_b(const float* x, int64_t N, int64_t C, int64_t HW, int nw, i
 int cnnq_pc_aciq_fused_xrank(const float* x, float* y, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws, void* gws,
                              size_t gws_bytes, float* stats, double* mom, float* qp, float* diag, const cnnq_xrank_ctx* xc, unsigned flags,
                              void* stream) {
-    if (!x || !y || !cfg || !ws || !stats || !mom || !qp || ((uintptr_t)ws & 7) || ((uintptr_t)mom & 7)) return CNNQ_EINVAL;
-    if (cfg->num_bits < 1 || cfg->num_bits > 8 || (gws && ((uintptr_t)gws & 127))) return CNNQ_EINVAL;
-    const bool use_ba = cfg->bit_alloc && cfg->num_bits <= 4;
+    if (!x || !y || !cfg || !ws || !stats || !mom || !qp || misaligned(ws, 8) || misaligned(mom, 8)) return CNNQ_EINVAL;
+    if (cfg->num_bits < 1 || cfg->num_bits > 8 || misaligned(gws, 128)) return CNNQ_EINVAL;
+    const bool use_ba = cfg_bit_alloc(cfg);
     if (use_ba && !diag) return CNNQ_EINVAL;
     if (cfg->clip != 1 || cfg->direct_range || (use_ba && cfg->prior_is_b)) return CNNQ_ENOTSUP;
     XRank xr;
     int rc = xr_from_ctx(xc, C, &xr);
     if (rc) return rc;
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
+    if (G <= 0) return g_error(G);
     hipStream_t st = (hipStream_t)stream;
     double* part = reinterpret_cast<double*>(ws);
     rc = xr_pass_a(x, N, C, HW, 0, part, G, xr, mom, stats, stream);
     if (rc) return rc;
     GPlan gp;
-    const bool single = gws && plan_sums(N, C, HW, al16(x) && al16(y), &gp, 1) == 0 && gp.ws_bytes <= gws_bytes &&
-                        (size_t)gp.ngroups * gp.gstride * 8 <= GRP_WS_SLOT_BYTES && !(gp.KL && !(gp.flat && gp.K == 32 && gp.KL == 8));
-    if (single) {
+    if (gws && plan_fused(0, N, C, HW, al16(x) && al16(y), gws_bytes, 0, &gp)) {
         float* bits = nullptr;
-        if (use_ba) {
-            bits = diag + (size_t)CNNQ_DIAG_BITS * C;
-            const int threads = (int)(C >= PTPB ? PTPB : ((C + 63) / 64) * 64);
-            hipLaunchKernelGGL(k_bitalloc, dim3(1), dim3(threads), 0, st, stats + (size_t)CNNQ_STAT_STD * C, (int)C, *cfg, bits);
-            rc = launch_status();
-            if (rc) return rc;
-        }
-        FusedArgs aa = {};
-        aa.stats = stats;
-        aa.bits = bits;
-        aa.qp = qp;
-        aa.diag = diag;
-        aa.cfg = *cfg;
-        aa.count_dev = mom + (size_t)CNNQ_MOM_COUNT * C;
+        if (use_ba) rc = launch_bitalloc(stats, C, cfg, diag, &bits, st);
+        if (rc) return rc;
         XRank xb = xr;
         xb.no_prologue = 1;
-        rc = launch_fused(0, x, y, gp, aa, gws, flags & 3u, st, 0, XOut{}, &xb);
+        rc = launch_fused(0, x, y, gp, fused_aciq(stats, bits, qp, diag, cfg, 0., mom + (size_t)CNNQ_MOM_COUNT * C), gws, flags & 3u, st, 0, XOut{}, &xb);
     } else {
         rc = xr_pass_b(x, N, C, HW, 1, 0, part, G, mom, xr, stats, stream);
         if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
@@ -1183,36 +1144,26 @@ int cnnq_pc_aciq_fused_xrank(const float* x, float* y, int64_t N, int64_t C, int
 int cnnq_pc_midtread_fused_xrank(const float* x, float* y, int64_t N, int64_t C, int64_t HW, double target, int sym, const double* tables,
                                  int ntab, void* ws, void* gws, size_t gws_bytes, float* stats, double* mom, float* mt, uint64_t* hist,
                                  const cnnq_xrank_ctx* xc, unsigned flags, void* stream) {
-    if (!x || !y || !tables || ntab < 2 || !ws || !stats || !mom || !mt || ((uintptr_t)ws & 7) || ((uintptr_t)hist & 7) || ((uintptr_t)mom & 7)) return CNNQ_EINVAL;
-    if (gws && ((uintptr_t)gws & 127)) return CNNQ_EINVAL;
+    if (!x || !y || !tables || ntab < 2 || !ws || !stats || !mom || !mt || misaligned(ws, 8) || misaligned(hist, 8) || misaligned(mom, 8)) return CNNQ_EINVAL;
+    if (misaligned(gws, 128)) return CNNQ_EINVAL;
     XRank xr;
     int rc = xr_from_ctx(xc, C, &xr);
     if (rc) return rc;
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
+    if (G <= 0) return g_error(G);
     hipStream_t st = (hipStream_t)stream;
     if (hist && hipMemsetAsync(hist, 0, (size_t)CNNQ_MT_HIST_WORDS(C) * sizeof(uint64_t), st) != hipSuccess) return launch_status();
     double* part = reinterpret_cast<double*>(ws);
     rc = xr_pass_a(x, N, C, HW, 0, part, G, xr, mom, stats, stream);
     if (rc) return rc;
     GPlan gp;
-    const bool single = gws && plan_sums(N, C, HW, al16(x) && al16(y), &gp, 1) == 0 && gp.ws_bytes <= gws_bytes &&
-                        (size_t)gp.ngroups * gp.gstride * 8 <= GRP_WS_SLOT_BYTES && (gp.flat || gp.v.A == 1) &&
-                        !(gp.KL && !(gp.flat && gp.K == 32 && gp.KL == 8));
     const MtCfg mcfg{target, 1, sym ? 1 : 0};
-    if (single) {
-        hipLaunchKernelGGL(k_mt_params<true>, dim3(1), dim3(PTPB), 0, st, stats, (int)C, mcfg, tables, ntab, mt);
-        rc = launch_status();
+    if (gws && plan_fused(1, N, C, HW, al16(x) && al16(y), gws_bytes, hist ? 1 : 0, &gp)) {
+        rc = launch_mt_guess(stats, C, mcfg, tables, ntab, mt, st);
         if (rc) return rc;
-        FusedArgs fa = {};
-        fa.stats = stats;
-        fa.count_dev = mom + (size_t)CNNQ_MOM_COUNT * C;
-        fa.mt = mt;
-        fa.mcfg = mcfg;
-        fa.hist = reinterpret_cast<unsigned long long*>(hist);
         XRank xb = xr;
         xb.no_prologue = 1;
-        rc = launch_fused(1, x, y, gp, fa, gws, flags & 3u, st, hist ? 1 : 0, XOut{}, &xb);
+        rc = launch_fused(1, x, y, gp, fused_mt(stats, mt, mcfg, hist, 0., mom + (size_t)CNNQ_MOM_COUNT * C), gws, flags & 3u, st, hist ? 1 : 0, XOut{}, &xb);
     } else {
         rc = xr_pass_b(x, N, C, HW, 1, 0, part, G, mom, xr, stats, stream);
         if (!rc) rc = cnnq_pc_midtread_params(stats, C, target, 1, sym, tables, ntab, mt, stream);
@@ -1229,25 +1180,18 @@ int cnnq_pc_midtread_fused_xrank(const float* x, float* y, int64_t N, int64_t C,
 // four launches, no collective (ws: cnnq_pc_stats_workspace bytes).  ONE launch number per call.
 int cnnq_pc_stats_xrank(const float* x, int64_t N, int64_t C, int64_t HW, int need_b, int need_kurt, int need_relu, void* ws, void* gws,
                         size_t gws_bytes, double* mom, float* stats, const cnnq_xrank_ctx* xc, unsigned flags, void* stream) {
-    if (!x || !stats || !mom || !ws || ((uintptr_t)ws & 7) || (gws && ((uintptr_t)gws & 127)) || ((uintptr_t)mom & 7)) return CNNQ_EINVAL;
+    if (!x || !stats || !mom || !ws || misaligned(ws, 8) || misaligned(gws, 128) || misaligned(mom, 8)) return CNNQ_EINVAL;
     XRank xr;
     int rc = xr_from_ctx(xc, C, &xr);
     if (rc) return rc;
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
+    if (G <= 0) return g_error(G);
     hipStream_t st = (hipStream_t)stream;
     const int need_dev = (need_b || need_kurt) ? 1 : 0;
     GPlan gp;
     const bool planned = gws && plan_sums(N, C, HW, al16(x), &gp, 0) == 0 && gp.ws_bytes <= gws_bytes;
-    const bool single = planned && gp.flat && !gp.KL && (gp.Gs <= ST_MAX_MEMBERS || (flags & 8u)) &&
-                        (size_t)gp.ngroups * gp.gstride * ST_LINE * 8 <= GRP_WS_SLOT_BYTES;
-    St1Args sa;
-    sa.stats = stats;
-    sa.mom = mom;
-    sa.count = (double)N * (double)HW;                     // this rank's; the launch exchanges it with the sums
-    sa.need_relu = need_relu ? 1 : 0;
-    sa.need_dev = need_dev;
-    sa.need_kurt = need_kurt ? 1 : 0;
+    const bool single = planned && gp.flat && !gp.KL && (gp.Gs <= ST_MAX_MEMBERS || (flags & 8u)) && slots_fit(gp, ST_LINE);
+    const St1Args sa = st1_args(stats, mom, N, HW, need_b, need_kurt, need_relu);      // count: this rank's; the launch exchanges it with the sums
     rc = CNNQ_ENOTSUP;
     if (single) {
         rc = launch_stats_flat(x, gp, sa, gws, flags & 1u, false, st, &xr);
@@ -1255,10 +1199,9 @@ int cnnq_pc_stats_xrank(const float* x, int64_t N, int64_t C, int64_t HW, int ne
         rc = launch_stats_group(x, gp, sa, gws, gws_bytes, flags & 1u, st, &xr);       // CNNQ_ENOTSUP (nothing enqueued): the slots do not fit
     }
     if (rc == CNNQ_ENOTSUP) {
-        double* part = reinterpret_cast<double*>(ws);
-        double* part2 = part + (size_t)G * CNNQ_NMOM * C;
-        rc = xr_pass_a(x, N, C, HW, need_relu ? 1 : 0, part, G, xr, mom, stats, stream);
-        if (!rc && need_dev) rc = xr_pass_b(x, N, C, HW, 2, need_kurt ? 1 : 0, part2, G, mom, xr, stats, stream);
+        const StatsWs w(ws, G, C);
+        rc = xr_pass_a(x, N, C, HW, need_relu ? 1 : 0, w.part, G, xr, mom, stats, stream);
+        if (!rc && need_dev) rc = xr_pass_b(x, N, C, HW, 2, need_kurt ? 1 : 0, w.part2, G, mom, xr, stats, stream);
     }
     if (rc) return rc;
     return xr_finish_ctx(xc, C, st);
@@ -1276,44 +1219,34 @@ int cnnq_pc_weight_correct(float* wq, int64_t C, int64_t HW, const float* stats_
     return launch_status();
 }
 
+// the bias-correction sums of x against y, or - qp != NULL - against the Q/DQ of x computed in flight
+static int bcorr_sums_launch(const float* x, const float* y, bool aligned16, int64_t N, int64_t C, int64_t HW, const float* qp, int relu_first,
+                             double* part3, void* stream) {
+    Variant v;
+    Geo g;
+    const int rc = plan(N, C, HW, aligned16, 0, &v, &g);
+    if (rc) return rc;
+    with_shape(v, [&](auto s) {
+        with_bool(qp != nullptr, qp && nt_loads(N * C * HW * 4), [&](auto q, auto nt) {
+            using S = decltype(s);
+            constexpr bool Q = decltype(q)::value, NT = decltype(nt)::value;
+            if constexpr (Q || !NT)                                 // two tensors to read: plain loads
+                hipLaunchKernelGGL((k_bcorr_sums<S::VEC, S::A, S::J, Q, NT>), geo_grid(g), dim3(TPB), 0, hs(stream), x, y, g, relu_first, qp, part3);
+        });
+    });
+    return launch_status();
+}
+
 int cnnq_pc_bcorr_sums(const float* x, const float* y, int64_t N, int64_t C, int64_t HW, int relu_first,
                        double* part3, void* stream) {
     if (!x || !y || !part3) return CNNQ_EINVAL;
-    Variant v;
-    Geo g;
-    const int rc = plan(N, C, HW, al16(x) && al16(y), 0, &v, &g);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_BS(VEC, A, J) \
-    hipLaunchKernelGGL((k_bcorr_sums<VEC, A, J, false, false>), grid, block, 0, st, x, y, g, relu_first, nullptr, part3)
-    CNNQ_DISPATCH(v, LAUNCH_BS);
-#undef LAUNCH_BS
-    return launch_status();
+    return bcorr_sums_launch(x, y, al16(x) && al16(y), N, C, HW, nullptr, relu_first, part3, stream);
 }
 
 int cnnq_pc_qdq_bcorr_sums(const float* x, int64_t N, int64_t C, int64_t HW, const float* qp, int relu_first,
                            double* part3, void* stream) {
     if (!x || !qp || !part3) return CNNQ_EINVAL;
-    Variant v;
-    Geo g;
-    const int rc = plan(N, C, HW, al16(x), 0, &v, &g);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-    const bool ntl = N * C * HW * 4 > NT_BYTES;
-#define LAUNCH_BS(VEC, A, J)                                                                                          \
-    do {                                                                                                              \
-        if (ntl)                                                                                                      \
-            hipLaunchKernelGGL((k_bcorr_sums<VEC, A, J, true, true>), grid, block, 0, st, x, nullptr, g, relu_first,  \
-                               qp, part3);                                                                            \
-        else                                                                                                          \
-            hipLaunchKernelGGL((k_bcorr_sums<VEC, A, J, true, false>), grid, block, 0, st, x, nullptr, g, relu_first, \
-                               qp, part3);                                                                            \
-    } while (0)
-    CNNQ_DISPATCH(v, LAUNCH_BS);
-#undef LAUNCH_BS
-    return launch_status();
+    return bcorr_sums_launch(x, nullptr, al16(x), N, C, HW, qp, relu_first, part3, stream);
 }
 
 int cnnq_pc_qdq_bcorr(const float* x, float* y, int64_t N, int64_t C, int64_t HW, const float* qp, const float* bias,
@@ -1323,11 +1256,10 @@ int cnnq_pc_qdq_bcorr(const float* x, float* y, int64_t N, int64_t C, int64_t HW
     Geo g;
     const int rc = plan(N, C, HW, al16(x) && al16(y), reverse != 0, &v, &g, /*fine=*/1);
     if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_QB(VEC, A, J) hipLaunchKernelGGL((k_qdq_bias<VEC, A, J>), grid, block, 0, st, x, y, g, qp, bias)
-    CNNQ_DISPATCH(v, LAUNCH_QB);
-#undef LAUNCH_QB
+    with_shape(v, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((k_qdq_bias<S::VEC, S::A, S::J>), geo_grid(g), dim3(TPB), 0, hs(stream), x, y, g, qp, bias);
+    });
     return launch_status();
 }
 
@@ -1344,11 +1276,10 @@ int cnnq_pc_bcorr_apply(float* y, int64_t N, int64_t C, int64_t HW, const float*
     Geo g;
     const int rc = plan(N, C, HW, al16(y), 0, &v, &g, /*fine=*/1);
     if (rc) return rc;
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_BA(VEC, A, J) hipLaunchKernelGGL((k_bcorr_apply<VEC, A, J>), grid, block, 0, st, y, g, bias)
-    CNNQ_DISPATCH(v, LAUNCH_BA);
-#undef LAUNCH_BA
+    with_shape(v, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((k_bcorr_apply<S::VEC, S::A, S::J>), geo_grid(g), dim3(TPB), 0, hs(stream), y, g, bias);
+    });
     return launch_status();
 }
 
@@ -1370,25 +1301,14 @@ int cnnq_pc_midtread_qdq(const float* x, float* y, int64_t N, int64_t C, int64_t
     const int rc = plan(N, C, HW, al16(x) && al16(y) && (!codes || al16(codes)), 0, &v, &g, /*fine=*/hist ? 57344 : 1);
     if (rc) return rc;
     const int total = g.S * g.ncb;
-    const int wgs = total;
-    const dim3 grid((unsigned)wgs), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-    unsigned long long* h = reinterpret_cast<unsigned long long*>(hist);
-#define LAUNCH_MT3(VEC, A, J, CL, HI)                                                                                   \
-    do {                                                                                                               \
-        if (codes) hipLaunchKernelGGL((k_mt_qdq<VEC, A, J, CL, HI, true>), grid, block, 0, st, x, y, g, mt, codes, h, total); \
-        else hipLaunchKernelGGL((k_mt_qdq<VEC, A, J, CL, HI, false>), grid, block, 0, st, x, y, g, mt, codes, h, total);      \
-    } while (0)
-#define LAUNCH_MT(VEC, A, J)                                      \
-    do {                                                          \
-        if (clip && h) LAUNCH_MT3(VEC, A, J, true, true);         \
-        else if (clip) LAUNCH_MT3(VEC, A, J, true, false);        \
-        else if (h) LAUNCH_MT3(VEC, A, J, false, true);           \
-        else LAUNCH_MT3(VEC, A, J, false, false);                 \
-    } while (0)
-    CNNQ_DISPATCH(v, LAUNCH_MT);
-#undef LAUNCH_MT
-#undef LAUNCH_MT3
+    unsigned long long* h = u64p(hist);
+    with_shape(v, [&](auto s) {
+        with_bool(clip != 0, h != nullptr, codes != nullptr, [&](auto cl, auto hi, auto co) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((k_mt_qdq<S::VEC, S::A, S::J, decltype(cl)::value, decltype(hi)::value, decltype(co)::value>), dim3((unsigned)total),
+                               dim3(TPB), 0, hs(stream), x, y, g, mt, codes, h, total);
+        });
+    });
     return launch_status();
 }
 
@@ -1400,32 +1320,24 @@ int cnnq_pc_midtread_qdq(const float* x, float* y, int64_t N, int64_t C, int64_t
 int cnnq_pc_midtread_qdq_single(const float* x, float* y, int64_t N, int64_t C, int64_t HW, double target, int sym,
                                 const double* tables, int ntab, void* ws, void* gws, size_t gws_bytes, float* stats, float* mt,
                                 uint64_t* hist, unsigned flags, void* stream) {
-    if (!x || !y || !tables || ntab < 2 || !ws || !stats || !mt || ((uintptr_t)ws & 7) || ((uintptr_t)hist & 7)) return CNNQ_EINVAL;
-    if (gws && ((uintptr_t)gws & 127)) return CNNQ_EINVAL;
+    if (!x || !y || !tables || ntab < 2 || !ws || !stats || !mt || misaligned(ws, 8) || misaligned(hist, 8)) return CNNQ_EINVAL;
+    if (misaligned(gws, 128)) return CNNQ_EINVAL;
     if (!gws) return CNNQ_ENOTSUP;
     GPlan gp;
-    if (plan_sums(N, C, HW, al16(x) && al16(y), &gp, 1) != 0 || gp.ws_bytes > gws_bytes) return CNNQ_ENOTSUP;
-    if ((size_t)gp.ngroups * gp.gstride * 8 > GRP_WS_SLOT_BYTES || (!gp.flat && gp.v.A != 1)) return CNNQ_ENOTSUP;
+    if (!plan_fused(1, N, C, HW, al16(x) && al16(y), gws_bytes, hist ? 1 : 0, &gp)) return CNNQ_ENOTSUP;
     const int G = cnnq_pc_groups(N, C, HW, al16(x) ? 1 : 0);
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
+    if (G <= 0) return g_error(G);
     double* part = reinterpret_cast<double*>(ws);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = hs(stream);
     if (hist && hipMemsetAsync(hist, 0, (size_t)CNNQ_MT_HIST_WORDS(C) * sizeof(uint64_t), st) != hipSuccess) return launch_status();
     int rc = cnnq_pc_moments(x, N, C, HW, 0, part, stream);
     if (rc) return rc;
     rc = cnnq_pc_combine(part, G, C, 0, nullptr, stats, stream);
     if (rc) return rc;
     const MtCfg mcfg{target, 1, sym ? 1 : 0};
-    hipLaunchKernelGGL(k_mt_params<true>, dim3(1), dim3(PTPB), 0, st, stats, (int)C, mcfg, tables, ntab, mt);
-    rc = launch_status();
+    rc = launch_mt_guess(stats, C, mcfg, tables, ntab, mt, st);
     if (rc) return rc;
-    FusedArgs fa = {};
-    fa.stats = stats;
-    fa.count = (double)N * (double)HW;
-    fa.mt = mt;
-    fa.mcfg = mcfg;
-    fa.hist = reinterpret_cast<unsigned long long*>(hist);
-    return launch_fused(1, x, y, gp, fa, gws, flags & 3u, st, hist ? 1 : 0, XOut{});
+    return launch_fused(1, x, y, gp, fused_mt(stats, mt, mcfg, hist, (double)N * (double)HW, nullptr), gws, flags & 3u, st, hist ? 1 : 0, XOut{});
 }
 
 int cnnq_midtread_entropy(const uint64_t* hist, const float* mt, int64_t C, int64_t total, float* out, void* stream) {
@@ -1438,7 +1350,7 @@ int cnnq_midtread_entropy(const uint64_t* hist, const float* mt, int64_t C, int6
 // the same with the element count taken from device memory: count[0] elements per channel (row CNNQ_MOM_COUNT of the merged
 // moment record of a batch-sharded run, whose global batch size only the device knows exactly - shards may differ by a sample)
 int cnnq_midtread_entropy_count(const uint64_t* hist, const float* mt, int64_t C, const double* count, float* out, void* stream) {
-    if (!hist || !mt || !out || !count || ((uintptr_t)count & 7) || C <= 0) return CNNQ_EINVAL;
+    if (!hist || !mt || !out || !count || misaligned(count, 8) || C <= 0) return CNNQ_EINVAL;
     hipLaunchKernelGGL(k_mt_entropy, dim3(1), dim3(PTPB), 0, (hipStream_t)stream,
                        reinterpret_cast<const unsigned long long*>(hist), mt, (int)C, 0., out, count);
     return launch_status();
@@ -1486,7 +1398,7 @@ int cnnq_pt_setup(const float* range_offset_host, const float* stats, int64_t st
 // 1024 rows, unaligned pointers, more 16 KB tiles than the workspace has records for) - use cnnq_pc_minmax + cnnq_pc_minmax_reduce + cnnq_pt_setup + cnnq_pt_qdq.
 int cnnq_pt_minmax_qdq_fused(const float* x, float* y, int64_t n, int rows, int rows_mode, int zero_min, int num_bits,
                              int int_exp, int enforce_true_zero, void* gws, size_t gws_bytes, float* ptp_out, void* stream) {
-    if (!x || !y || !gws || gws_bytes < GRP_WS_PAIRS || n <= 0 || rows <= 0 || num_bits < 1 || num_bits > 31 || ((uintptr_t)gws & 127)) return CNNQ_EINVAL;
+    if (!x || !y || !gws || gws_bytes < GRP_WS_PAIRS || n <= 0 || rows <= 0 || num_bits < 1 || num_bits > 31 || misaligned(gws, 128)) return CNNQ_EINVAL;
     if (n % rows) return CNNQ_EINVAL;
     const int64_t L = n / rows;
     if (L % 4 || rows > PTF_MAX_ROWS || !al16(x) || !al16(y) || L / 4 >= ((int64_t)1 << 31)) return CNNQ_ENOTSUP;
@@ -1514,31 +1426,18 @@ int cnnq_pt_minmax_qdq_fused(const float* x, float* y, int64_t n, int rows, int 
     const dim3 grid((unsigned)G), block(TPB);
     hipStream_t st = (hipStream_t)stream;
     // beyond the Infinity Cache the first sweep leaves nothing behind for the second: stream it
-    if (n * 4 > ((int64_t)192 << 20))
-        hipLaunchKernelGGL(k_pt_fused<true>, grid, block, 0, st, x, y, rows, (unsigned)L4, (unsigned)tpr, (unsigned)per, w,
-                           rows_mode, zero_min, num_bits, int_exp, enforce_true_zero, ptp_out);
-    else
-        hipLaunchKernelGGL(k_pt_fused<false>, grid, block, 0, st, x, y, rows, (unsigned)L4, (unsigned)tpr, (unsigned)per, w,
-                           rows_mode, zero_min, num_bits, int_exp, enforce_true_zero, ptp_out);
+    with_bool(n * 4 > ((int64_t)192 << 20), [&](auto nt) {
+        hipLaunchKernelGGL(k_pt_fused<decltype(nt)::value>, grid, block, 0, st, x, y, rows, (unsigned)L4, (unsigned)tpr, (unsigned)per, w, rows_mode,
+                           zero_min, num_bits, int_exp, enforce_true_zero, ptp_out);
+    });
     return launch_status();
 }
 
+// fp32: float4 or single elements; bf16 / fp16 (cnnq_half.hip.h): eight elements or one
+static int pt_qdq_launch(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream);
+
 int cnnq_pt_qdq(const float* x, float* y, int64_t n, const float* ptp, const float* noise, void* stream) {
-    if (!x || !y || !ptp || n <= 0) return CNNQ_EINVAL;
-    const bool vec = al16(x) && al16(y) && (!noise || al16(noise));
-    const int64_t work = vec ? (n + 3) / 4 : n;
-    const int64_t blocks = (work + TPB - 1) / TPB;
-    if (blocks >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
-    const dim3 grid((unsigned)blocks), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-    if (vec) {
-        if (noise) hipLaunchKernelGGL((k_pt_qdq<4, true>), grid, block, 0, st, x, y, n, ptp, noise);
-        else hipLaunchKernelGGL((k_pt_qdq<4, false>), grid, block, 0, st, x, y, n, ptp, noise);
-    } else {
-        if (noise) hipLaunchKernelGGL((k_pt_qdq<1, true>), grid, block, 0, st, x, y, n, ptp, noise);
-        else hipLaunchKernelGGL((k_pt_qdq<1, false>), grid, block, 0, st, x, y, n, ptp, noise);
-    }
-    return launch_status();
+    return pt_qdq_launch(x, y, CNNQ_DTYPE_F32, n, ptp, noise, stream);
 }
 
 int cnnq_kld_hist(const float* x, int64_t rows, int64_t len, const float* rowmm, uint32_t* hist, void* stream) {
@@ -1587,7 +1486,7 @@ static int h_align(const void* x, const void* y) {
 // (0 for the chain), workgroups of the Q/DQ launch}
 static int h_route(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_single_launch, int32_t out[4]) {
     const int rc = cnnq_pc_groups(N, C, HW, 0);       // the fp32 entry points' geometry limits
-    if (rc <= 0) return rc ? rc : CNNQ_EINVAL;
+    if (rc <= 0) return g_error(rc);
     const int w = h_piece(HW, (uintptr_t)align_bytes, 0);
     const bool whole = allow_single_launch && N * HW <= h_whole_cap(w);
     out[0] = whole ? 1 : 2;
@@ -1601,7 +1500,7 @@ static int h_route(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_
 static int h_minmax(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, float* pmm, int* S, hipStream_t st) {
     const int g1 = cnnq_pc_groups(N, C, HW, 1), g0 = cnnq_pc_groups(N, C, HW, 0);
     const int G = g1 > g0 ? g1 : g0;
-    if (G <= 0) return G ? G : CNNQ_EINVAL;
+    if (G <= 0) return g_error(G);
     HGeo g;
     g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
     const int w = h_piece(HW, (uintptr_t)x, 0);
@@ -1611,9 +1510,10 @@ static int h_minmax(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, 
     g.S = total < N ? total : (int)N;
     g.cs = total / g.S < g.ppr ? total / g.S : g.ppr;
     const uint16_t* xh = static_cast<const uint16_t*>(x);
-#define LAUNCH_HMM(T, W) hipLaunchKernelGGL((k_h_minmax<T, W>), dim3((unsigned)(C * g.S * g.cs)), dim3(TPB), 0, st, xh, g, pmm)
-    CNNQ_H_DISPATCH(dtype, w, LAUNCH_HMM);
-#undef LAUNCH_HMM
+    with_piece<false>(dtype, w, [&](auto pc) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_h_minmax<typename P::T, P::W>), dim3((unsigned)(C * g.S * g.cs)), dim3(TPB), 0, st, xh, g, pmm);
+    });
     *S = g.S * g.cs;
     return launch_status();
 }
@@ -1622,7 +1522,7 @@ static int h_minmax(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, 
 static int h_qdq(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, const float* pmm, const HArgs& ha,
                  hipStream_t st) {
     const int rc = cnnq_pc_groups(N, C, HW, 0);    // the fp32 entry points' geometry limits
-    if (rc <= 0) return rc ? rc : CNNQ_EINVAL;
+    if (rc <= 0) return g_error(rc);
     HGeo g;
     g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
     g.S = h_splits(N, C, HW, H_QDQ_ELEMS, N);
@@ -1631,14 +1531,15 @@ static int h_qdq(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_
     g.ppr = (int)(HW / w);
     const uint16_t* xh = static_cast<const uint16_t*>(x);
     uint16_t* yh = static_cast<uint16_t*>(y);
-#define LAUNCH_HQ(T, W) hipLaunchKernelGGL((k_h_qdq<T, W>), dim3((unsigned)(C * g.S)), dim3(TPB), 0, st, xh, yh, g, qp, pmm, ha)
-    CNNQ_H_DISPATCH(dtype, w, LAUNCH_HQ);
-#undef LAUNCH_HQ
+    with_piece<false>(dtype, w, [&](auto pc) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_h_qdq<typename P::T, P::W>), dim3((unsigned)(C * g.S)), dim3(TPB), 0, st, xh, yh, g, qp, pmm, ha);
+    });
     return launch_status();
 }
 
 int cnnq_pc_route_dt(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_single_launch, int32_t out[4]) {
-    if (!out || align_bytes <= 0 || (align_bytes & (align_bytes - 1))) return CNNQ_EINVAL;
+    if (!out || !pow2(align_bytes)) return CNNQ_EINVAL;
     return h_route(N, C, HW, align_bytes, allow_single_launch, out);
 }
 
@@ -1650,9 +1551,8 @@ int cnnq_pc_minmax_qdq_auto_dt(const void* x, void* y, int dtype, int64_t N, int
                                        gws, gws_bytes, allow_single_launch, stream);
     if (!x || !y || !ws || num_bits < 1 || num_bits > 32 || N <= 0 || C <= 0 || HW <= 0) return CNNQ_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    float* qp = ws;                                    // the layout of cnnq_pc_minmax_qdq_auto's workspace
-    float* mm = ws + (size_t)CNNQ_NQP * C;
-    float* pmm = mm + 2 * (size_t)C;
+    const MmWs w(ws, C);                               // the layout of cnnq_pc_minmax_qdq_auto's workspace
+    float *const qp = w.qp, *const mm = w.mm, *const pmm = w.pmm;
     int32_t route[4];
     int rc = h_route(N, C, HW, h_align(x, y), allow_single_launch, route);
     if (rc) return rc;
@@ -1663,14 +1563,11 @@ int cnnq_pc_minmax_qdq_auto_dt(const void* x, void* y, int dtype, int64_t N, int
         const HArgs ha{0, num_bits, positive ? 1 : 0, qp, mm};
         const uint16_t* xh = static_cast<const uint16_t*>(x);
         uint16_t* yh = static_cast<uint16_t*>(y);
-#define LAUNCH_HW(T, W) \
-    hipLaunchKernelGGL((k_h_whole<T, W, h_whole_k<W>()>), dim3((unsigned)C), dim3(HTPB), 0, st, xh, yh, g, ha)
-        if (dtype == CNNQ_DTYPE_BF16) {
-            if (route[1] == 8) LAUNCH_HW(HBf16, 8); else if (route[1] == 4) LAUNCH_HW(HBf16, 4); else LAUNCH_HW(HBf16, 2);
-        } else {
-            if (route[1] == 8) LAUNCH_HW(HF16, 8); else if (route[1] == 4) LAUNCH_HW(HF16, 4); else LAUNCH_HW(HF16, 2);
-        }
-#undef LAUNCH_HW
+        with_piece<false>(dtype, route[1] >= 4 ? route[1] : 2, [&](auto pc) {      // (no whole-tensor instance of single elements)
+            using P = decltype(pc);
+            if constexpr (P::W > 1)
+                hipLaunchKernelGGL((k_h_whole<typename P::T, P::W, h_whole_k<P::W>()>), dim3((unsigned)C), dim3(HTPB), 0, st, xh, yh, g, ha);
+        });
         return launch_status();
     }
     int S = 0;
@@ -1702,27 +1599,32 @@ int cnnq_pc_minmax_local_dt(const void* x, int dtype, int64_t N, int64_t C, int6
 
 int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream) {
     if (!dtype_ok(dtype)) return CNNQ_EINVAL;
-    if (dtype == CNNQ_DTYPE_F32) return cnnq_pt_qdq(static_cast<const float*>(x), static_cast<float*>(y), n, ptp, noise, stream);
+    return pt_qdq_launch(x, y, dtype, n, ptp, noise, stream);
+}
+
+static int pt_qdq_launch(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream) {
     if (!x || !y || !ptp || n <= 0) return CNNQ_EINVAL;
     const bool vec = al16(x) && al16(y) && (!noise || al16(noise));
-    const int64_t work = vec ? (n + 7) / 8 : n;
+    const int wide = dtype == CNNQ_DTYPE_F32 ? 4 : 8;
+    const int64_t work = vec ? (n + wide - 1) / wide : n;
     const int64_t blocks = (work + TPB - 1) / TPB;
     if (blocks >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
     const dim3 grid((unsigned)blocks), block(TPB);
-    hipStream_t st = (hipStream_t)stream;
-    const uint16_t* xh = static_cast<const uint16_t*>(x);
-    uint16_t* yh = static_cast<uint16_t*>(y);
-#define LAUNCH_HPT(T, W)                                                                                              \
-    do {                                                                                                              \
-        if (noise) hipLaunchKernelGGL((k_h_pt_qdq<T, W, true>), grid, block, 0, st, xh, yh, n, ptp, noise);           \
-        else hipLaunchKernelGGL((k_h_pt_qdq<T, W, false>), grid, block, 0, st, xh, yh, n, ptp, noise);                \
-    } while (0)
-    if (dtype == CNNQ_DTYPE_BF16) {
-        if (vec) LAUNCH_HPT(HBf16, 8); else LAUNCH_HPT(HBf16, 1);
-    } else {
-        if (vec) LAUNCH_HPT(HF16, 8); else LAUNCH_HPT(HF16, 1);
+    if (dtype == CNNQ_DTYPE_F32) {
+        with_bool(vec, noise != nullptr, [&](auto vc, auto nz) {
+            hipLaunchKernelGGL((k_pt_qdq<decltype(vc)::value ? 4 : 1, decltype(nz)::value>), grid, block, 0, hs(stream), static_cast<const float*>(x),
+                               static_cast<float*>(y), n, ptp, noise);
+        });
+        return launch_status();
     }
-#undef LAUNCH_HPT
+    with_piece<false>(dtype, vec ? 8 : 1, [&](auto pc) {
+        with_bool(noise != nullptr, [&](auto nz) {
+            using P = decltype(pc);
+            if constexpr (P::W == 8 || P::W == 1)
+                hipLaunchKernelGGL((k_h_pt_qdq<typename P::T, P::W, decltype(nz)::value>), grid, block, 0, hs(stream), static_cast<const uint16_t*>(x),
+                                   static_cast<uint16_t*>(y), n, ptp, noise);
+        });
+    });
     return launch_status();
 }
 
@@ -1747,11 +1649,20 @@ size_t cnnq_pc_nhwc_workspace(int64_t R, int64_t C, int dtype) {
     return ((size_t)2 + 2 * (size_t)cl_slabs_max(R, C, dtype)) * (size_t)C * sizeof(float);
 }
 
+// the head of both route functions: the piece width and the two geometries of this tensor
+static int cl_route(int64_t R, int64_t C, int dtype, int align_bytes, const void* out, int* w, ClGeo* m, ClGeo* q) {
+    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
+    *w = cl_piece(C, cl_esize(dtype), align_bytes);
+    *m = cl_geo_mm(R, C, *w);
+    *q = cl_geo_qdq(R, C, *w);
+    return (int64_t)q->S * q->nb >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
+}
+
 int cnnq_pc_route_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
-    if (cl_check(R, C, dtype) || !out || align_bytes <= 0 || (align_bytes & (align_bytes - 1))) return CNNQ_EINVAL;
-    const int w = cl_piece(C, cl_esize(dtype), align_bytes);
-    const ClGeo m = cl_geo_mm(R, C, w), q = cl_geo_qdq(R, C, w);
-    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    int w;
+    ClGeo m, q;
+    const int rc = cl_route(R, C, dtype, align_bytes, out, &w, &m, &q);
+    if (rc) return rc;
     out[0] = w;
     out[1] = m.S;
     out[2] = q.S * q.nb;
@@ -1762,11 +1673,12 @@ int cnnq_pc_route_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t
 static int cl_qdq(const void* x, void* y, int dtype, int w, int64_t R, int64_t C, const float* qp, const float* mm, hipStream_t st) {
     const ClGeo q = cl_geo_qdq(R, C, w);
     if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
-#define LAUNCH_CLQ(T, W)                                                                                           \
-    hipLaunchKernelGGL((k_cl_qdq<T, W>), dim3((unsigned)(q.S * q.nb)), dim3(TPB), 0, st,                            \
-                       static_cast<const ClRaw<T>::type*>(x), static_cast<ClRaw<T>::type*>(y), q, qp, mm)
-    CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLQ);
-#undef LAUNCH_CLQ
+    with_piece(dtype, w, [&](auto pc) {
+        using T = typename decltype(pc)::T;
+        using Raw = typename ClRaw<T>::type;
+        hipLaunchKernelGGL((k_cl_qdq<T, decltype(pc)::W>), dim3((unsigned)(q.S * q.nb)), dim3(TPB), 0, st, static_cast<const Raw*>(x),
+                           static_cast<Raw*>(y), q, qp, mm);
+    });
     return launch_status();
 }
 
@@ -1781,10 +1693,11 @@ int cnnq_pc_minmax_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_
     if ((int64_t)cl_geo_qdq(R, C, w).S * m.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
     float* ext = mm ? mm : ws;
     float* pmm = ws + 2 * (size_t)C;
-#define LAUNCH_CLM(T, W) \
-    hipLaunchKernelGGL((k_cl_minmax<T, W>), dim3((unsigned)(m.S * m.nb)), dim3(TPB), 0, st, static_cast<const ClRaw<T>::type*>(x), m, pmm)
-    CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLM);
-#undef LAUNCH_CLM
+    with_piece(dtype, w, [&](auto pc) {
+        using T = typename decltype(pc)::T;
+        hipLaunchKernelGGL((k_cl_minmax<T, decltype(pc)::W>), dim3((unsigned)(m.S * m.nb)), dim3(TPB), 0, st,
+                           static_cast<const typename ClRaw<T>::type*>(x), m, pmm);
+    });
     int rc = launch_status();
     if (!rc) rc = cnnq_pc_minmax_params(pmm, m.S, C, num_bits, positive, qp, stream);
     if (!rc) rc = cnnq_pc_minmax_reduce(pmm, m.S, C, ext, stream);
@@ -1803,17 +1716,17 @@ int cnnq_pc_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, co
 // ws of cnnq_pc_aciq_qdq_nhwc, doubles: part[S][CNNQ_NMOM][C], mom[CNNQ_NMOM][C], part2[S][CNNQ_NDEV][C]
 size_t cnnq_pc_aciq_nhwc_workspace(int64_t R, int64_t C, int dtype) {
     if (cl_check(R, C, dtype)) return 0;
-    const size_t S = (size_t)cl_slabs_max(R, C, dtype);
-    return (S * (CNNQ_NMOM + CNNQ_NDEV) + CNNQ_NMOM) * (size_t)C * sizeof(double);
+    return AciqWs::bytes((size_t)cl_slabs_max(R, C, dtype), C, false);
 }
 
 // Which launches cnnq_pc_aciq_qdq_nhwc makes for this geometry (host only).  out[5] is 1 throughout: no class of layer is sent
 // back to the copy route; one that measures slower native than through the copy (tools/bench_channels_last_aciq.py) goes back here.
 int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[6]) {
-    if (cl_check(R, C, dtype) || !out || align_bytes <= 0 || (align_bytes & (align_bytes - 1))) return CNNQ_EINVAL;
-    const int w = cl_piece(C, cl_esize(dtype), align_bytes);
-    const ClGeo m = cl_geo_mm(R, C, w), q = cl_geo_qdq(R, C, w);
-    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31) || m.rpw >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    int w;
+    ClGeo m, q;
+    const int rc = cl_route(R, C, dtype, align_bytes, out, &w, &m, &q);
+    if (rc) return rc;
+    if (m.rpw >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
     out[0] = w;
     out[1] = m.S;
     out[2] = (int32_t)m.rpw;
@@ -1828,44 +1741,41 @@ int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, in
 int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
                           float* stats, float* qp, float* diag, void* stream) {
     if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
-    if (!x || !y || !cfg || !ws || !stats || !qp || ((uintptr_t)ws & 7)) return CNNQ_EINVAL;
-    if (cfg->num_bits < 1 || cfg->num_bits > 32 || cfg->clip < 0 || cfg->clip > 3) return CNNQ_EINVAL;
-    if ((cfg->clip == 1 || cfg->clip == 2) && cfg->num_bits > 8) return CNNQ_EINVAL;   // as cnnq_pc_params, before any launch
+    if (!x || !y || !cfg || !ws || !stats || !qp || misaligned(ws, 8)) return CNNQ_EINVAL;
+    if (check_cfg(cfg)) return CNNQ_EINVAL;                                              // as cnnq_pc_params, before any launch
     if (cfg->direct_range) return CNNQ_EINVAL;                                           // the per-tensor branch has no channels
-    const bool use_ba = cfg->bit_alloc && cfg->num_bits <= 4;
+    const bool use_ba = cfg_bit_alloc(cfg);
     if (use_ba && !diag) return CNNQ_EINVAL;                                             // the bit table lives in diag
     const int w = cl_piece(C, cl_esize(dtype), h_align(x, y));
     const ClGeo m = cl_geo_mm(R, C, w);
     const ClGeo q = cl_geo_qdq(R, C, w);
     if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
     const bool need_b = cfg->clip == 1 || (use_ba && cfg->prior_is_b);
-    double* part = reinterpret_cast<double*>(ws);
-    double* mom = part + (size_t)m.S * CNNQ_NMOM * C;
-    double* part2 = mom + (size_t)CNNQ_NMOM * C;
-    hipStream_t st = (hipStream_t)stream;
+    const AciqWs a(ws, m.S, C);
+    double *const part = a.part, *const mom = a.mom, *const part2 = a.part2;
+    hipStream_t st = hs(stream);
     const dim3 grid((unsigned)(m.S * m.nb)), block(TPB);
-    const bool ntl = R * C * cl_esize(dtype) > NT_BYTES;
+    const bool ntl = nt_loads(R * C * cl_esize(dtype));
     // the Q/DQ walks the tensor descending: the statistics launch in front of it ascends, so with pass B pass A descends
     const int rev = need_b ? 1 : 0;
-#define LAUNCH_CLA_NT(T, W) \
-    hipLaunchKernelGGL((k_cl_moments<T, W, true>), grid, block, 0, st, static_cast<const ClRaw<T>::type*>(x), m, rev, part)
-#define LAUNCH_CLA_LD(T, W) \
-    hipLaunchKernelGGL((k_cl_moments<T, W, false>), grid, block, 0, st, static_cast<const ClRaw<T>::type*>(x), m, rev, part)
-    if (ntl) CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLA_NT); else CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLA_LD);
-#undef LAUNCH_CLA_NT
-#undef LAUNCH_CLA_LD
-    int rc = launch_status();
+    // pass A (k_cl_moments), then pass B (k_cl_absdev) on the merged table
+    auto pass = [&](bool b) {
+        with_piece(dtype, w, [&](auto pc) {
+            with_bool(ntl, [&](auto nt) {
+                using T = typename decltype(pc)::T;
+                constexpr int W = decltype(pc)::W;
+                const auto* xr = static_cast<const typename ClRaw<T>::type*>(x);
+                if (b) hipLaunchKernelGGL((k_cl_absdev<T, W, decltype(nt)::value>), grid, block, 0, st, xr, m, stats, part2);
+                else hipLaunchKernelGGL((k_cl_moments<T, W, decltype(nt)::value>), grid, block, 0, st, xr, m, rev, part);
+            });
+        });
+        return launch_status();
+    };
+    int rc = pass(false);
     // the merge writes every row of the table (zero for KURT, STD_POS; B without pass B)
     if (!rc) rc = cnnq_pc_combine(part, m.S, C, 0, mom, stats, stream);
     if (!rc && need_b) {
-#define LAUNCH_CLB_NT(T, W) \
-    hipLaunchKernelGGL((k_cl_absdev<T, W, true>), grid, block, 0, st, static_cast<const ClRaw<T>::type*>(x), m, stats, part2)
-#define LAUNCH_CLB_LD(T, W) \
-    hipLaunchKernelGGL((k_cl_absdev<T, W, false>), grid, block, 0, st, static_cast<const ClRaw<T>::type*>(x), m, stats, part2)
-        if (ntl) CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLB_NT); else CNNQ_CL_DISPATCH(dtype, w, LAUNCH_CLB_LD);
-#undef LAUNCH_CLB_NT
-#undef LAUNCH_CLB_LD
-        rc = launch_status();
+        rc = pass(true);
         if (!rc) rc = cnnq_pc_combine_dev(part2, m.S, C, mom, 0, nullptr, stats, stream);
     }
     if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);

@@ -249,17 +249,27 @@ inline ClGeo cl_geo_qdq(int64_t R, int64_t C, int w) {
     return cl_geo(R, C, w, CL_QDQ_ELEMS, ((int64_t)1 << 31) - 1, ((int64_t)1 << 31) - 1);
 }
 
-#define CNNQ_CL_DISPATCH(dt, w, F)                                                  \
-    do {                                                                            \
-        if ((dt) == CNNQ_DTYPE_F32) {                                               \
-            if ((w) == 4) F(CF32, 4); else if ((w) == 2) F(CF32, 2); else F(CF32, 1); \
-        } else if ((dt) == CNNQ_DTYPE_BF16) {                                       \
-            if ((w) == 8) F(HBf16, 8); else if ((w) == 4) F(HBf16, 4);              \
-            else if ((w) == 2) F(HBf16, 2); else F(HBf16, 1);                       \
-        } else {                                                                    \
-            if ((w) == 8) F(HF16, 8); else if ((w) == 4) F(HF16, 4);                \
-            else if ((w) == 2) F(HF16, 2); else F(HF16, 1);                         \
-        }                                                                           \
-    } while (0)
+// runtime (element type, piece width) -> template arguments: f(Piece<T, W>) with T = CF32 (W = 4 / 2 / 1), HBf16 or HF16
+// (W = 8 / 4 / 2 / 1).  F32 = false: the bf16 / fp16 kernels of cnnq_half.hip.h, which have no fp32 instance.  A width a kernel
+// lacks stays an `if constexpr` at its launch site.
+template <class T_, int W_>
+struct Piece { using T = T_; static constexpr int W = W_; };
+template <class T, int WMAX, class F>
+inline void with_width(int w, F&& f) {
+    if constexpr (WMAX > 1) {
+        if (w == WMAX) f(Piece<T, WMAX>{});
+        else with_width<T, WMAX / 2>(w, f);
+    } else {
+        f(Piece<T, 1>{});
+    }
+}
+template <bool F32 = true, class F>
+inline void with_piece(int dt, int w, F&& f) {
+    if constexpr (F32) {
+        if (dt == CNNQ_DTYPE_F32) return with_width<CF32, 4>(w, f);
+    }
+    if (dt == CNNQ_DTYPE_BF16) with_width<HBf16, 8>(w, f);
+    else with_width<HF16, 8>(w, f);
+}
 
 }  // namespace

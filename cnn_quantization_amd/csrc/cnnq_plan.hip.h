@@ -118,29 +118,59 @@ int plan(int64_t N, int64_t C, int64_t HW, bool aligned16, int rev, Variant* v, 
     return make_geo(N, C, HW, *v, 0, C, MAXG, rev, fine, g);
 }
 
-// dispatch on the runtime load shape: invokes F<VEC, A, J>()
-#define CNNQ_DISPATCH(v, F)                                          \
-    do {                                                             \
-        if ((v).vec == 4 && (v).A == 1) {                            \
-            if ((v).J == 4) { F(4, 1, 4); }                          \
-            else if ((v).J == 2) { F(4, 1, 2); }                     \
-            else { F(4, 1, 1); }                                     \
-        } else if ((v).vec == 4) { F(4, 4, 1); }                     \
-        else { F(1, 1, 4); }                                         \
-    } while (0)
+// ---- runtime value -> template argument -------------------------------------------------------------------------------------
+// Each dispatcher hands a generic lambda a tag whose members are constants inside it (the idiom of CNNQ_SEG_DISPATCH); the
+// launch site reads them with decltype(tag).  Only what a site names is instantiated: an instance that does not exist
+// (registers, scratch, LDS budget) stays an explicit `if constexpr` at that site, never a silent cross product.
+template <bool V>
+struct BoolC { static constexpr bool value = V; };
+template <int VEC_, int A_, int J_>
+struct Shape { static constexpr int VEC = VEC_, A = A_, J = J_; };
+
+// the load shape of a plan: f(Shape<VEC, A, J>)
+template <class F>
+inline void with_shape(const Variant& v, F&& f) {
+    if (v.vec == 4 && v.A == 1) {
+        if (v.J == 4) f(Shape<4, 1, 4>{});
+        else if (v.J == 2) f(Shape<4, 1, 2>{});
+        else f(Shape<4, 1, 1>{});
+    } else if (v.vec == 4) f(Shape<4, 4, 1>{});
+    else f(Shape<1, 1, 4>{});
+}
+// one of a fixed list, the last one when nothing matches: f(IntC<V>)
+template <int V0, int... Vs, class F>
+inline void with_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(IntC<V0>{});
+    else if (v == V0) f(IntC<V0>{});
+    else with_int<Vs...>(v, f);
+}
+// one, two or three flags: f(BoolC<a>[, BoolC<b>[, BoolC<c>]])
+template <class F>
+inline void with_bool(bool a, F&& f) {
+    if (a) f(BoolC<true>{});
+    else f(BoolC<false>{});
+}
+template <class F>
+inline void with_bool(bool a, bool b, F&& f) {
+    with_bool(a, [&](auto ta) { with_bool(b, [&](auto tb) { f(ta, tb); }); });
+}
+template <class F>
+inline void with_bool(bool a, bool b, bool c, F&& f) {
+    with_bool(a, b, [&](auto ta, auto tb) { with_bool(c, [&](auto tc) { f(ta, tb, tc); }); });
+}
+
+// the grid of a pass over the plan's column blocks
+inline dim3 geo_grid(const Geo& g) { return dim3((unsigned)(g.S * g.ncb)); }
 
 int launch_qdq(const float* x, float* y, const Geo& g, const Variant& v, const float* qp, uint8_t* codes,
                unsigned long long* h, hipStream_t st) {
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
-#define LAUNCH_QDQ(VEC, A, J)                                                                                       \
-    do {                                                                                                            \
-        if (codes && h) hipLaunchKernelGGL((k_qdq<VEC, A, J, true, true>), grid, block, 0, st, x, y, g, qp, codes, h);   \
-        else if (codes) hipLaunchKernelGGL((k_qdq<VEC, A, J, true, false>), grid, block, 0, st, x, y, g, qp, codes, h);  \
-        else if (h) hipLaunchKernelGGL((k_qdq<VEC, A, J, false, true>), grid, block, 0, st, x, y, g, qp, codes, h);      \
-        else hipLaunchKernelGGL((k_qdq<VEC, A, J, false, false>), grid, block, 0, st, x, y, g, qp, codes, h);            \
-    } while (0)
-    CNNQ_DISPATCH(v, LAUNCH_QDQ);
-#undef LAUNCH_QDQ
+    with_shape(v, [&](auto s) {
+        with_bool(codes != nullptr, h != nullptr, [&](auto c, auto hi) {
+            using S = decltype(s);
+            hipLaunchKernelGGL((k_qdq<S::VEC, S::A, S::J, decltype(c)::value, decltype(hi)::value>), geo_grid(g), dim3(TPB), 0, st, x, y, g, qp,
+                               codes, h);
+        });
+    });
     return launch_status();
 }
 
@@ -245,24 +275,24 @@ int launch_whole(const float* x, float* y, const WPlan& p, int num_bits, int pos
     const bool xrank = xrp && xrp->world > 0;          // the batch is sharded: the cross-rank stage of cnnq_xrank.hip.h (y, or y + codes / histogram)
     if (xrank && out == 2) return CNNQ_ENOTSUP;
     const XRank xr = xrank ? *xrp : XRank{};
-    const size_t hb = xhist_lds_bytes(out, xo.hist, 1 << (num_bits < 8 ? num_bits : 8));
-#define LAUNCH_W(A, T, K)                                                                                                     \
-    do {                                                                                                                      \
-        if (xrank && out == 1) hipLaunchKernelGGL((k_mmq_whole<A, T, K, 1, true>), grid, dim3(T), hb, st, x, y, p.g, num_bits, positive, qp, mm, flags, xo, xr); \
-        else if (xrank) hipLaunchKernelGGL((k_mmq_whole<A, T, K, 0, true>), grid, dim3(T), 0, st, x, y, p.g, num_bits, positive, qp, mm, flags, xo, xr); \
-        else if (out == 0) hipLaunchKernelGGL((k_mmq_whole<A, T, K, 0>), grid, dim3(T), 0, st, x, y, p.g, num_bits, positive, qp, mm, flags, xo);      \
-        else if (out == 1) hipLaunchKernelGGL((k_mmq_whole<A, T, K, 1>), grid, dim3(T), hb, st, x, y, p.g, num_bits, positive, qp, mm, flags, xo); \
-        else hipLaunchKernelGGL((k_mmq_whole<A, T, K, 2>), grid, dim3(T), 0, st, x, y, p.g, num_bits, positive, qp, mm, flags, xo);               \
-    } while (0)
-    if (p.A == 1) {
-        if (p.T == 256) { if (p.K == 8) LAUNCH_W(1, 256, 8); else if (p.K == 16) LAUNCH_W(1, 256, 16); else LAUNCH_W(1, 256, 32); }
-        else if (p.T == 512) { if (p.K == 16) LAUNCH_W(1, 512, 16); else LAUNCH_W(1, 512, 32); }
-        else { if (p.K == 8) LAUNCH_W(1, 1024, 8); else LAUNCH_W(1, 1024, 16); }
-    } else {
-        if (p.T == 256) { if (p.K == 8) LAUNCH_W(4, 256, 8); else if (p.K == 16) LAUNCH_W(4, 256, 16); else LAUNCH_W(4, 256, 32); }
-        else { if (p.K == 8) LAUNCH_W(4, 1024, 8); else LAUNCH_W(4, 1024, 16); }
-    }
-#undef LAUNCH_W
+    const size_t hb = xhist_lds_bytes(out, xo.hist, 1 << (num_bits < 8 ? num_bits : 8));   // 0 unless out == 1 with a histogram
+    // the instances: A = 1: T = 256 x K = 8 / 16 / 32, 512 x 16 / 32, 1024 x 8 / 16; A = 4: the same without T = 512 (plan_whole)
+    auto launch = [&](auto a, auto t, auto k) {
+        with_int<0, 1, 2>(out, [&](auto o) {
+            with_bool(xrank, [&](auto xc) {
+                constexpr int A = decltype(a)::value, T = decltype(t)::value, K = decltype(k)::value, OUT = decltype(o)::value;
+                constexpr bool XR = decltype(xc)::value;
+                if constexpr (!(XR && OUT == 2))
+                    hipLaunchKernelGGL((k_mmq_whole<A, T, K, OUT, XR>), grid, dim3(T), hb, st, x, y, p.g, num_bits, positive, qp, mm, flags, xo, xr);
+            });
+        });
+    };
+    with_int<1, 4>(p.A, [&](auto a) {
+        if (p.T == 256) return with_int<8, 16, 32>(p.K, [&](auto k) { launch(a, IntC<256>{}, k); });
+        if constexpr (decltype(a)::value == 1)
+            if (p.T == 512) return with_int<16, 32>(p.K, [&](auto k) { launch(a, IntC<512>{}, k); });
+        with_int<8, 16>(p.K, [&](auto k) { launch(a, IntC<1024>{}, k); });
+    });
     return launch_status();
 }
 
@@ -292,6 +322,17 @@ constexpr int GRP_MAX_LINES = 16384;   // counter lines (4 MB)
 constexpr size_t GRP_WS_SLOTS = GRP_WS_HDR + (size_t)GRP_MAX_LINES * GRP_CNT_STRIDE * 4;   // the slot meeting's slots: ZERO AT REST
 constexpr size_t GRP_WS_SLOT_BYTES = (size_t)16 * GRP_MAX_LINES * 8;   // 2 MB: groups * ceil16(members) <= 16 * GRP_MAX_LINES by the line bound
 constexpr size_t GRP_WS_PAIRS = GRP_WS_SLOTS + GRP_WS_SLOT_BYTES;      // pair blocks / records: written before read, may hold anything
+// ... as the kernels take it; gstride: 8-byte words per group block of this launch
+inline GWs gws_view(void* ws, int gstride) {
+    char* const b = reinterpret_cast<char*>(ws);
+    GWs w;
+    w.status = reinterpret_cast<unsigned*>(b);
+    w.cnt = reinterpret_cast<unsigned*>(b + GRP_WS_HDR);
+    w.part = reinterpret_cast<unsigned long long*>(b + GRP_WS_PAIRS);
+    w.slots = reinterpret_cast<unsigned long long*>(b + GRP_WS_SLOTS);
+    w.gstride = gstride;
+    return w;
+}
 
 // flat tiles (k_mmq_flat) when a channel row is long enough that the row-piece tiling of k_mmq_group would idle lanes
 // lds_rows: 0 - never; 1 - eight more tile rows in LDS (KL = 8) only for channels too populous for GRP_GS_MAX plain K = 32
@@ -461,23 +502,21 @@ int plan_rows(int64_t N, int64_t C, int64_t HW, GPlan* p, int a4_kmax) {
     return 0;
 }
 
+// do the group's blocks fit the slot region (the slot meeting; zero at rest)?  words: 8-byte words per member pair
+inline bool slots_fit(const GPlan& p, int words = 1) { return (size_t)p.ngroups * p.gstride * words * 8 <= GRP_WS_SLOT_BYTES; }
+
 int launch_group(const float* x, float* y, const GPlan& p, int num_bits, int positive, void* ws, float* qp, float* mm,
                  unsigned flags, hipStream_t st, int out = 0, const XOut& xo = XOut{}, const XRank* xrp = nullptr) {
     flags |= mmq_env_flags();
     const bool xrank = xrp && xrp->world > 0;
     if (xrank && out == 2) return CNNQ_ENOTSUP;
     const XRank xr = xrank ? *xrp : XRank{};
-    const size_t hb = xhist_lds_bytes(out, xo.hist, 1 << (num_bits < 8 ? num_bits : 8));
-    GWs w;
-    w.status = reinterpret_cast<unsigned*>(ws);
-    w.cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + GRP_WS_HDR);
-    w.part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_PAIRS);
-    w.slots = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_SLOTS);
-    w.gstride = p.gstride;
+    const size_t hb = xhist_lds_bytes(out, xo.hist, 1 << (num_bits < 8 ? num_bits : 8));   // 0 unless out == 1 with a histogram
+    const GWs w = gws_view(ws, p.gstride);
     const dim3 grid((unsigned)((int64_t)p.g.S * p.g.ncb)), block(TPB);
     // the slot meeting (cnnq_group.hip.h): +11 % on the packed output at b512 (nothing hides its waits there), +-0.5 % on the
     // b512 / b64 steps with y to write; MMQ_FLAG_COUNTERS (tests, A/B): the counter meeting of round 2
-    if (!(flags & MMQ_FLAG_COUNTERS) && (size_t)p.ngroups * p.gstride * 8 <= GRP_WS_SLOT_BYTES) flags |= MMQ_FLAG_SLOTS;
+    if (!(flags & MMQ_FLAG_COUNTERS) && slots_fit(p)) flags |= MMQ_FLAG_SLOTS;
     if (p.flat) {
         const dim3 fgrid((unsigned)((int64_t)p.fg.C * p.fg.Gs));
         static const int pk_narrow = env_int("CNNQ_PK_NARROW", 0);          // development knob: the 2-byte stores of round 3
@@ -490,37 +529,52 @@ int launch_group(const float* x, float* y, const GPlan& p, int num_bits, int pos
         FGeo fg = p.fg;
         static const int cb_forced = env_int("CNNQ_GRP_CB", 0);
         if (out == 2 && !cb_forced) fg.cb = 1;
-#define LAUNCH_F(K)                                                                                                                  \
-    do {                                                                                                                             \
-        if (xrank && out == 1) hipLaunchKernelGGL((k_mmq_flat<K, 1, true>), fgrid, block, hb, st, x, y, fg, num_bits, positive, w, qp, mm, flags, xo, xr); \
-        else if (xrank) hipLaunchKernelGGL((k_mmq_flat<K, 0, true>), fgrid, block, 0, st, x, y, fg, num_bits, positive, w, qp, mm, flags, xo, xr); \
-        else if (out == 0) hipLaunchKernelGGL((k_mmq_flat<K, 0>), fgrid, block, 0, st, x, y, fg, num_bits, positive, w, qp, mm, flags, xo);      \
-        else if (out == 1) hipLaunchKernelGGL((k_mmq_flat<K, 1>), fgrid, block, hb, st, x, y, fg, num_bits, positive, w, qp, mm, flags, xo); \
-        else hipLaunchKernelGGL((k_mmq_flat<K, 2>), fgrid, block, 0, st, x, y, fg, num_bits, positive, w, qp, mm, flags, xo);               \
-    } while (0)
-        if (p.K == 32 && p.KL == 8) {
-            if (xrank || out == 1) return CNNQ_EINVAL;      // flat_lds_rows() never plans these
-            if (out == 0) hipLaunchKernelGGL((k_mmq_flat<32, 0, false, 8>), fgrid, block, 0, st, x, y, fg, num_bits, positive, w, qp, mm, flags, xo);
-            else hipLaunchKernelGGL((k_mmq_flat<32, 2, false, 8>), fgrid, block, 0, st, x, y, fg, num_bits, positive, w, qp, mm, flags, xo);
-        } else if (p.K == 32) LAUNCH_F(32); else if (p.K == 16) LAUNCH_F(16); else LAUNCH_F(8);
-#undef LAUNCH_F
+        const bool lds = p.K == 32 && p.KL == 8;
+        if (lds && (xrank || out == 1)) return CNNQ_EINVAL;      // flat_lds_rows() never plans these
+        with_int<32, 16, 8>(p.K, [&](auto k) {
+            with_int<0, 1, 2>(out, [&](auto o) {
+                with_bool(xrank, lds, [&](auto xc, auto l) {
+                    constexpr int K = decltype(k)::value, OUT = decltype(o)::value, KL = decltype(l)::value ? 8 : 0;
+                    constexpr bool XR = decltype(xc)::value;
+                    // KL = 8: <32, 0 / 2, false, 8> alone (the codes table and the cross-rank stage leave no room for the LDS rows)
+                    if constexpr (!(XR && OUT == 2) && !(KL && (K != 32 || XR || OUT == 1)))
+                        hipLaunchKernelGGL((k_mmq_flat<K, OUT, XR, KL>), fgrid, block, hb, st, x, y, fg, num_bits, positive, w, qp, mm, flags, xo, xr);
+                });
+            });
+        });
         return launch_status();
     }
-#define LAUNCH_G(A, K)                                                                                                                     \
-    do {                                                                                                                                   \
-        if (xrank && out == 1) hipLaunchKernelGGL((k_mmq_group<A, K, 1, true>), grid, block, hb, st, x, y, p.g, p.Gs, num_bits, positive, w, qp, mm, flags, xo, xr); \
-        else if (xrank) hipLaunchKernelGGL((k_mmq_group<A, K, 0, true>), grid, block, 0, st, x, y, p.g, p.Gs, num_bits, positive, w, qp, mm, flags, xo, xr); \
-        else if (out == 0) hipLaunchKernelGGL((k_mmq_group<A, K, 0>), grid, block, 0, st, x, y, p.g, p.Gs, num_bits, positive, w, qp, mm, flags, xo);      \
-        else if (out == 1) hipLaunchKernelGGL((k_mmq_group<A, K, 1>), grid, block, hb, st, x, y, p.g, p.Gs, num_bits, positive, w, qp, mm, flags, xo); \
-        else hipLaunchKernelGGL((k_mmq_group<A, K, 2>), grid, block, 0, st, x, y, p.g, p.Gs, num_bits, positive, w, qp, mm, flags, xo);               \
-    } while (0)
-    if (p.v.A == 4) {
-        if (p.K == 32) LAUNCH_G(4, 32); else if (p.K == 16) LAUNCH_G(4, 16); else if (p.K == 8) LAUNCH_G(4, 8); else LAUNCH_G(4, 4);
-    } else {
-        if (p.K == 32) LAUNCH_G(1, 32); else if (p.K == 16) LAUNCH_G(1, 16); else if (p.K == 8) LAUNCH_G(1, 8); else LAUNCH_G(1, 4);
-    }
-#undef LAUNCH_G
+    with_int<4, 1>(p.v.A, [&](auto a) {
+        with_int<32, 16, 8, 4>(p.K, [&](auto k) {
+            with_int<0, 1, 2>(out, [&](auto o) {
+                with_bool(xrank, [&](auto xc) {
+                    constexpr int A = decltype(a)::value, K = decltype(k)::value, OUT = decltype(o)::value;
+                    constexpr bool XR = decltype(xc)::value;
+                    if constexpr (!(XR && OUT == 2))
+                        hipLaunchKernelGGL((k_mmq_group<A, K, OUT, XR>), grid, block, hb, st, x, y, p.g, p.Gs, num_bits, positive, w, qp, mm, flags, xo, xr);
+                });
+            });
+        });
+    });
     return launch_status();
+}
+
+// May launch_fused take this plan (mode 0: ACIQ, 1: mid-tread; out as there)?  THE rule: every caller asks it before its first
+// launch - CNNQ_ENOTSUP means nothing was enqueued - and launch_fused asks it again.
+inline bool fused_ok(int mode, const GPlan& p, int out) {
+    if (!slots_fit(p)) return false;                                      // slot meeting only
+    // (plan_flat is the only source of KL and sets 8 with K = 32 alone: this clause guards the instance set, no plan trips it)
+    if (p.KL && !(p.flat && p.K == 32 && p.KL == 8)) return false;
+    if (mode == 1 && !p.flat && p.v.A != 1) return false;                 // no straddling mid-tread instance
+    if (mode == 0 && !p.flat && p.v.A == 4 && p.K == 32) return false;    // plan_sums never plans it (no such instance: it spilled)
+    if (p.KL && mode == 0 && out == 1) return false;   // 32 KB of LDS rows + the 32 KB code table: two workgroups per CU, a big channel needs three
+    return true;
+}
+// the plan of launch_fused for this tensor, or false: no single launch (nothing has been enqueued)
+// (with the codes / the histogram wanted in mode 0 the 160 KB tiles of a big channel have no instance: planned without them, so
+//  that CNNQ_ENOTSUP comes BEFORE anything is enqueued: ADVICE r5)
+inline bool plan_fused(int mode, int64_t N, int64_t C, int64_t HW, bool aligned16, size_t gws_bytes, int out, GPlan* p) {
+    return plan_sums(N, C, HW, aligned16, p, (mode == 0 && out == 1) ? 0 : 1) == 0 && p->ws_bytes <= gws_bytes && fused_ok(mode, *p, out);
 }
 
 // the single-launch ACIQ / mid-tread kernels (cnnq_aciq.hip.h; mode 0 / 1) on the plan and the workspace of launch_group;
@@ -531,57 +585,40 @@ int launch_fused(int mode, const float* x, float* y, const GPlan& p, const Fused
     const bool xrank = xrp && xrp->world > 0;
     if (xrank && mode == 0 && out == 1) return CNNQ_ENOTSUP;
     const XRank xr = xrank ? *xrp : XRank{};
-    if ((size_t)p.ngroups * p.gstride * 8 > GRP_WS_SLOT_BYTES) return CNNQ_ENOTSUP;
-    if (p.KL && !(p.flat && p.K == 32 && p.KL == 8)) return CNNQ_ENOTSUP;
-    if (mode == 1 && !p.flat && p.v.A != 1) return CNNQ_ENOTSUP;      // no straddling mid-tread instance
-    if (p.KL && mode == 0 && out == 1) return CNNQ_ENOTSUP;          // 32 KB of LDS rows + the 32 KB code table: two workgroups per CU, a big channel needs three
+    if (!fused_ok(mode, p, out)) return CNNQ_ENOTSUP;
     flags |= mmq_env_flags();
     // mode 0 counts codes in the table of the config-2 kernels: 256 bins with bit allocation (a channel's width is its own), else 2^bits
     const bool ba = fa.cfg.bit_alloc && fa.cfg.num_bits <= 4;
     const size_t hb = mode == 0 ? xhist_lds_bytes(out, xo.hist, ba ? 256 : 1 << (fa.cfg.num_bits < 8 ? fa.cfg.num_bits : 8)) : 0;
-    GWs w;
-    w.status = reinterpret_cast<unsigned*>(ws);
-    w.cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + GRP_WS_HDR);
-    w.part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_PAIRS);
-    w.slots = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_SLOTS);
-    w.gstride = p.gstride;
+    const GWs w = gws_view(ws, p.gstride);
     const dim3 block(TPB);
     if (p.flat) {
         const dim3 fgrid((unsigned)((int64_t)p.fg.C * p.fg.Gs));
-#define LAUNCH_FF(K, KL)                                                                                                   \
-    do {                                                                                                                   \
-        if (xrank && mode == 0) hipLaunchKernelGGL((k_fused_flat<K, 0, KL, 0, true>), fgrid, block, 0, st, x, y, p.fg, w, fa, flags, xo, xr);       \
-        else if (xrank && out == 1) hipLaunchKernelGGL((k_fused_flat<K, 1, KL, 1, true>), fgrid, block, 0, st, x, y, p.fg, w, fa, flags, xo, xr);   \
-        else if (xrank) hipLaunchKernelGGL((k_fused_flat<K, 0, KL, 1, true>), fgrid, block, 0, st, x, y, p.fg, w, fa, flags, xo, xr);               \
-        else if (mode == 0 && out == 1) hipLaunchKernelGGL((k_fused_flat<K, 1, 0, 0>), fgrid, block, hb, st, x, y, p.fg, w, fa, flags, xo);   \
-        else if (mode == 0) hipLaunchKernelGGL((k_fused_flat<K, 0, KL, 0>), fgrid, block, 0, st, x, y, p.fg, w, fa, flags, xo);         \
-        else if (out == 1) hipLaunchKernelGGL((k_fused_flat<K, 1, KL, 1>), fgrid, block, 0, st, x, y, p.fg, w, fa, flags, xo);          \
-        else hipLaunchKernelGGL((k_fused_flat<K, 0, KL, 1>), fgrid, block, 0, st, x, y, p.fg, w, fa, flags, xo);                        \
-    } while (0)
-        if (p.K == 32 && p.KL == 8) LAUNCH_FF(32, 8);
-        else if (p.K == 32) LAUNCH_FF(32, 0);
-        else if (p.K == 16) LAUNCH_FF(16, 0);
-        else LAUNCH_FF(8, 0);
-#undef LAUNCH_FF
+        with_int<32, 16, 8>(p.K, [&](auto k) {
+            with_bool(p.K == 32 && p.KL == 8, mode == 1, out == 1, [&](auto l, auto m, auto o) {
+                with_bool(xrank, [&](auto xc) {
+                    constexpr int K = decltype(k)::value, KL = decltype(l)::value ? 8 : 0, MODE = decltype(m)::value, OUT = decltype(o)::value;
+                    constexpr bool XR = decltype(xc)::value;
+                    // mode 0 with the codes: no cross-rank instance, none with LDS rows (both refused above)
+                    if constexpr (!(KL && K != 32) && !(MODE == 0 && OUT == 1 && (XR || KL)))
+                        hipLaunchKernelGGL((k_fused_flat<K, OUT, KL, MODE, XR>), fgrid, block, hb, st, x, y, p.fg, w, fa, flags, xo, xr);
+                });
+            });
+        });
         return launch_status();
     }
     const dim3 grid((unsigned)((int64_t)p.g.S * p.g.ncb));
-#define LAUNCH_FG(A, K, MODE)                                                                                                   \
-    do {                                                                                                                        \
-        if (xrank && out == 1) { if constexpr (MODE == 1) hipLaunchKernelGGL((k_fused_group<A, K, 1, MODE, true>), grid, block, 0, st, x, y, p.g, p.Gs, w, fa, flags, xo, xr); } \
-        else if (xrank) hipLaunchKernelGGL((k_fused_group<A, K, 0, MODE, true>), grid, block, 0, st, x, y, p.g, p.Gs, w, fa, flags, xo, xr);   \
-        else if (out == 1) hipLaunchKernelGGL((k_fused_group<A, K, 1, MODE>), grid, block, (MODE == 0 ? hb : 0), st, x, y, p.g, p.Gs, w, fa, flags, xo);   \
-        else hipLaunchKernelGGL((k_fused_group<A, K, 0, MODE>), grid, block, 0, st, x, y, p.g, p.Gs, w, fa, flags, xo);            \
-    } while (0)
-    if (mode == 1) {
-        if (p.K == 32) LAUNCH_FG(1, 32, 1); else if (p.K == 16) LAUNCH_FG(1, 16, 1); else if (p.K == 8) LAUNCH_FG(1, 8, 1); else LAUNCH_FG(1, 4, 1);
-    } else if (p.v.A == 4) {
-        if (p.K == 32) return CNNQ_ENOTSUP;      // plan_sums never plans it (no such instance: it spilled)
-        if (p.K == 16) LAUNCH_FG(4, 16, 0); else if (p.K == 8) LAUNCH_FG(4, 8, 0); else LAUNCH_FG(4, 4, 0);
-    } else {
-        if (p.K == 32) LAUNCH_FG(1, 32, 0); else if (p.K == 16) LAUNCH_FG(1, 16, 0); else if (p.K == 8) LAUNCH_FG(1, 8, 0); else LAUNCH_FG(1, 4, 0);
-    }
-#undef LAUNCH_FG
+    with_int<4, 1>(mode == 1 ? 1 : p.v.A, [&](auto a) {
+        with_int<32, 16, 8, 4>(p.K, [&](auto k) {
+            with_bool(mode == 1, out == 1, xrank, [&](auto m, auto o, auto xc) {
+                constexpr int A = decltype(a)::value, K = decltype(k)::value, MODE = decltype(m)::value, OUT = decltype(o)::value;
+                constexpr bool XR = decltype(xc)::value;
+                // straddling rows: mode 0 alone and K <= 16 (K = 32 spilled); mode 0 with the codes: no cross-rank instance
+                if constexpr (!(A == 4 && (MODE == 1 || K == 32)) && !(MODE == 0 && OUT == 1 && XR))
+                    hipLaunchKernelGGL((k_fused_group<A, K, OUT, MODE, XR>), grid, block, hb, st, x, y, p.g, p.Gs, w, fa, flags, xo, xr);
+            });
+        });
+    });
     return launch_status();
 }
 
@@ -591,30 +628,20 @@ int launch_stats_flat(const float* x, const GPlan& p, const St1Args& sa, void* w
     const bool xrank = xrp && xrp->world > 0;          // the batch is sharded: both phases' folds exchanged inside the launch
     const XRank xr = xrank ? *xrp : XRank{};
     if (!p.flat || p.KL) return CNNQ_ENOTSUP;
-    if ((size_t)p.ngroups * p.gstride * ST_LINE * 8 > GRP_WS_SLOT_BYTES) return CNNQ_ENOTSUP;
+    if (!slots_fit(p, ST_LINE)) return CNNQ_ENOTSUP;
     if (dry) return 0;                                 // cnnq_pc_stats_route: the checks alone
-    GWs w;
-    w.status = reinterpret_cast<unsigned*>(ws);
-    w.cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + GRP_WS_HDR);
-    w.part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_PAIRS);
-    w.slots = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_SLOTS);
-    w.gstride = p.gstride;
+    const GWs w = gws_view(ws, p.gstride);
     const dim3 grid((unsigned)((int64_t)p.fg.C * p.fg.Gs)), block(TPB);
     FGeo fg = p.fg;
     fg.cb = 1;          // member fastest: with nothing to write the launch is bound by how long a group's members wait for each other
-#define LAUNCH_SF(KR, KL)                                                                                              \
-    do {                                                                                                               \
-        if (xrank) {                                                                                                   \
-            if (sa.need_relu) hipLaunchKernelGGL((k_stats_flat<KR, KL, true, false, true>), grid, block, 0, st, x, fg, w, sa, flags, xr);   \
-            else hipLaunchKernelGGL((k_stats_flat<KR, KL, false, false, true>), grid, block, 0, st, x, fg, w, sa, flags, xr);                \
-        }                                                                                                              \
-        else if (sa.need_relu && ntl) hipLaunchKernelGGL((k_stats_flat<KR, KL, true, true>), grid, block, 0, st, x, fg, w, sa, flags);   \
-        else if (sa.need_relu) hipLaunchKernelGGL((k_stats_flat<KR, KL, true, false>), grid, block, 0, st, x, fg, w, sa, flags);    \
-        else if (ntl) hipLaunchKernelGGL((k_stats_flat<KR, KL, false, true>), grid, block, 0, st, x, fg, w, sa, flags);             \
-        else hipLaunchKernelGGL((k_stats_flat<KR, KL, false, false>), grid, block, 0, st, x, fg, w, sa, flags);                     \
-    } while (0)
-    if (p.K == 32) LAUNCH_SF(24, 8); else if (p.K == 16) LAUNCH_SF(16, 0); else LAUNCH_SF(8, 0);
-#undef LAUNCH_SF
+    with_int<32, 16, 8>(p.K, [&](auto k) {
+        with_bool(sa.need_relu != 0, ntl && !xrank, xrank, [&](auto r, auto nt, auto xc) {
+            constexpr int K = decltype(k)::value, KL = K == 32 ? 8 : 0;        // the K = 32 tile: 24 rows in registers, 8 in LDS
+            constexpr bool NTL = decltype(nt)::value, XR = decltype(xc)::value;
+            if constexpr (!(XR && NTL))                                        // the cross-rank instances load plainly
+                hipLaunchKernelGGL((k_stats_flat<K - KL, KL, decltype(r)::value, NTL, XR>), grid, block, 0, st, x, fg, w, sa, flags, xr);
+        });
+    });
     return launch_status();
 }
 
@@ -641,59 +668,42 @@ int launch_stats_group(const float* x, const GPlan& p, const St1Args& sa, void* 
     if (p.v.A == 4 && p.K == 32) return CNNQ_ENOTSUP;      // plan_sums never plans it (no such instance: it spilled)
     if (p.K == 32 && (int64_t)p.g.P * 4 * 32 >= ((int64_t)1 << 32)) return CNNQ_ENOTSUP;     // the LDS rows' 32-bit offsets from the tile's base
     if (dry) return 0;
-    GWs w;
-    w.status = reinterpret_cast<unsigned*>(ws);
-    w.cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + GRP_WS_HDR);
-    w.part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_PAIRS);
-    w.slots = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_SLOTS);
-    w.gstride = (int)words;
+    const GWs w = gws_view(ws, (int)words);
     const dim3 grid((unsigned)((int64_t)p.g.S * p.g.ncb)), block(TPB);
-#define LAUNCH_SG(A, KR, KL)                                                                                             \
-    do {                                                                                                                 \
-        if (xrank && sa.need_relu) hipLaunchKernelGGL((k_stats_group<A, KR, KL, true, true>), grid, block, 0, st, x, p.g, p.Gs, w, sa, flags, xr);  \
-        else if (xrank) hipLaunchKernelGGL((k_stats_group<A, KR, KL, false, true>), grid, block, 0, st, x, p.g, p.Gs, w, sa, flags, xr);            \
-        else if (sa.need_relu) hipLaunchKernelGGL((k_stats_group<A, KR, KL, true>), grid, block, 0, st, x, p.g, p.Gs, w, sa, flags);  \
-        else hipLaunchKernelGGL((k_stats_group<A, KR, KL, false>), grid, block, 0, st, x, p.g, p.Gs, w, sa, flags);              \
-    } while (0)
-    if (p.v.A == 4) {
-        if (p.K == 32) return CNNQ_ENOTSUP;      // plan_sums never plans it (no such instance: it spilled)
-        if (p.K == 16) LAUNCH_SG(4, 16, 0); else if (p.K == 8) LAUNCH_SG(4, 8, 0); else LAUNCH_SG(4, 4, 0);
-    } else {
-        if (p.K == 32) LAUNCH_SG(1, 24, 8); else if (p.K == 16) LAUNCH_SG(1, 16, 0); else if (p.K == 8) LAUNCH_SG(1, 8, 0); else LAUNCH_SG(1, 4, 0);
-    }
-#undef LAUNCH_SG
+    with_int<4, 1>(p.v.A, [&](auto a) {
+        with_int<32, 16, 8, 4>(p.K, [&](auto k) {
+            with_bool(sa.need_relu != 0, xrank, [&](auto r, auto xc) {
+                constexpr int A = decltype(a)::value, K = decltype(k)::value, KL = K == 32 ? 8 : 0;   // as k_stats_flat's tile
+                if constexpr (!(A == 4 && K == 32))
+                    hipLaunchKernelGGL((k_stats_group<A, K - KL, KL, decltype(r)::value, decltype(xc)::value>), grid, block, 0, st, x, p.g, p.Gs, w,
+                                       sa, flags, xr);
+            });
+        });
+    });
     return launch_status();
 }
 
 // rank-local extrema in one launch (k_minmax_group): the plan and workspace of launch_group
 int launch_minmax_group(const float* x, const GPlan& p, void* ws, float* out, hipStream_t st) {
-    GWs w;
-    w.status = reinterpret_cast<unsigned*>(ws);
-    w.cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + GRP_WS_HDR);
-    w.part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_PAIRS);
-    w.slots = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + GRP_WS_SLOTS);
-    w.gstride = p.gstride;
+    const GWs w = gws_view(ws, p.gstride);
     const dim3 grid((unsigned)((int64_t)p.g.S * p.g.ncb)), block(TPB);
-#define LAUNCH_MG(A, K) hipLaunchKernelGGL((k_minmax_group<A, K>), grid, block, 0, st, x, p.g, p.Gs, w, out)
-    if (p.v.A == 4) {
-        if (p.K == 32) LAUNCH_MG(4, 32); else if (p.K == 16) LAUNCH_MG(4, 16); else if (p.K == 8) LAUNCH_MG(4, 8); else LAUNCH_MG(4, 4);
-    } else {
-        if (p.K == 32) LAUNCH_MG(1, 32); else if (p.K == 16) LAUNCH_MG(1, 16); else if (p.K == 8) LAUNCH_MG(1, 8); else LAUNCH_MG(1, 4);
-    }
-#undef LAUNCH_MG
+    with_int<4, 1>(p.v.A, [&](auto a) {
+        with_int<32, 16, 8, 4>(p.K, [&](auto k) {
+            hipLaunchKernelGGL((k_minmax_group<decltype(a)::value, decltype(k)::value>), grid, block, 0, st, x, p.g, p.Gs, w, out);
+        });
+    });
     return launch_status();
 }
 
 // fused Q/DQ whose workgroups derive their parameters from the W gathered {min, max} records (k_qdq<GATH>)
 int launch_qdq_gathered(const float* x, float* y, const Geo& g, const Variant& v, const float* gathered, const GathArgs& ga,
                         hipStream_t st) {
-    const dim3 grid((unsigned)(g.S * g.ncb)), block(TPB);
     uint8_t* nocodes = nullptr;
     unsigned long long* nohist = nullptr;
-#define LAUNCH_QG(VEC, A, J) \
-    hipLaunchKernelGGL((k_qdq<VEC, A, J, false, false, true>), grid, block, 0, st, x, y, g, gathered, nocodes, nohist, ga)
-    CNNQ_DISPATCH(v, LAUNCH_QG);
-#undef LAUNCH_QG
+    with_shape(v, [&](auto s) {
+        using S = decltype(s);
+        hipLaunchKernelGGL((k_qdq<S::VEC, S::A, S::J, false, false, true>), geo_grid(g), dim3(TPB), 0, st, x, y, g, gathered, nocodes, nohist, ga);
+    });
     return launch_status();
 }
 
