@@ -51,6 +51,7 @@
 #include "cnnq_half.hip.h"
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
+#include "cnnq_nhwc_bcorr.hip.h"
 #include "cnnq_qerr.hip.h"
 
 namespace {
@@ -1781,6 +1782,43 @@ int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t 
     if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
     if (!rc) rc = cl_qdq(x, y, dtype, w, R, C, qp, nullptr, st);
     return rc;
+}
+
+// ---- activation bias correction on dense channels_last activations (cnnq_nhwc_bcorr.hip.h) --------------------------------------
+// ws of cnnq_pc_qdq_bcorr_nhwc, doubles: part3[S][3][C]
+size_t cnnq_pc_qdq_bcorr_nhwc_workspace(int64_t R, int64_t C, int dtype) {
+    if (cl_check(R, C, dtype)) return 0;
+    return (size_t)cl_slabs_max(R, C, dtype) * 3 * (size_t)C * sizeof(double);
+}
+
+// iqm.py:180-196 folded into int_quantizer.py:573-592 on [R][C] with a given table (-sm use):
+// k_cl_bcorr_sums (ascending) -> k_bcorr_bias on its S records -> k_cl_qdq_bias (descending)
+int cnnq_pc_qdq_bcorr_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* qp, int relu_first, void* ws,
+                           double* sums, float* bias, void* stream) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    if (!x || !y || x == y || !qp || !ws || !bias || misaligned(ws, 8) || misaligned(sums, 8)) return CNNQ_EINVAL;
+    const int w = cl_piece(C, cl_esize(dtype), h_align(x, y));
+    const ClGeo m = cl_geo_mm(R, C, w);
+    const ClGeo q = cl_geo_qdq(R, C, w);
+    // a lane counts its rows in 32 bits
+    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31) || m.rpw >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    double* part3 = static_cast<double*>(ws);
+    hipStream_t st = hs(stream);
+    with_piece(dtype, w, [&](auto pc) {
+        using T = typename decltype(pc)::T;
+        hipLaunchKernelGGL((k_cl_bcorr_sums<T, decltype(pc)::W>), dim3((unsigned)(m.S * m.nb)), dim3(TPB), 0, st,
+                           static_cast<const typename ClRaw<T>::type*>(x), m, relu_first ? 1 : 0, qp, part3);
+    });
+    int rc = launch_status();
+    if (!rc) rc = cnnq_pc_bcorr_bias(part3, m.S, C, sums, bias, stream);
+    if (rc) return rc;
+    with_piece(dtype, w, [&](auto pc) {
+        using T = typename decltype(pc)::T;
+        using Raw = typename ClRaw<T>::type;
+        hipLaunchKernelGGL((k_cl_qdq_bias<T, decltype(pc)::W>), dim3((unsigned)(q.S * q.nb)), dim3(TPB), 0, st,
+                           static_cast<const Raw*>(x), static_cast<Raw*>(y), q, qp, bias);
+    });
+    return launch_status();
 }
 
 }  // extern "C"

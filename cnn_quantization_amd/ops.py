@@ -201,16 +201,20 @@ def _groups(N, C, HW, aligned=None):
     return G
 
 
+_NHWC_WS = {'nhwc': 'cnnq_pc_nhwc_workspace', 'aciq_nhwc': 'cnnq_pc_aciq_nhwc_workspace',
+            'bcorr_nhwc': 'cnnq_pc_qdq_bcorr_nhwc_workspace'}
+
+
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
-    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc': N = rows).  0 from the library: no plan for
-    the geometry."""
+    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc': N = rows).  0 from the
+    library: no plan for the geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
         lib = L.load()
-        if kind in ('nhwc', 'aciq_nhwc'):
-            fn = 'cnnq_pc_nhwc_workspace' if kind == 'nhwc' else 'cnnq_pc_aciq_nhwc_workspace'
+        if kind in _NHWC_WS:
+            fn = _NHWC_WS[kind]
             nbytes = getattr(lib, fn)(N, C, arg)
             if nbytes == 0:
                 raise L.CnnqError('%s(%d, %d, %d): bad arguments' % (fn, N, C, arg))
@@ -1453,11 +1457,11 @@ def act_bias_correction_(out, out_q, relu_first, group=None):
     return out_q
 
 
-def qdq_bias_corrected(x, N, C, HW, qp, relu_first, group=None, out=None):
+def qdq_bias_corrected(x, N, C, HW, qp, relu_first, group=None, out=None, want_parts=False):
     """Q/DQ with the parameter table qp followed by the activation bias correction, without ever
     storing the uncorrected tensor: one read-only pass over x for the per-channel sums (the quantized
     value is recomputed on the fly) and one fused quantize+correct pass - 12 B/elem instead of 24, the
-    same floats as pc_qdq + act_bias_correction_."""
+    same floats as pc_qdq + act_bias_correction_.  want_parts: (y, dict(sums [3, C] float64, bias [C]))."""
     lib = L.load()
     x = _dev(x, 'x')
     y = _out_like(x, out)
@@ -1465,13 +1469,51 @@ def qdq_bias_corrected(x, N, C, HW, qp, relu_first, group=None, out=None):
     part3 = torch.empty((G, 3, C), dtype=torch.float64, device=x.device)
     L.check(lib.cnnq_pc_qdq_bcorr_sums(_ptr(x), N, C, HW, _ptr(qp), int(bool(relu_first)), _ptr(part3), _stream(x)),
             'cnnq_pc_qdq_bcorr_sums')
-    bias = _bcorr_bias(x, part3, group)
+    sums = torch.empty((3, C), dtype=torch.float64, device=x.device) if want_parts else None
+    bias = _bcorr_bias(x, part3, group, sums)
     L.check(lib.cnnq_pc_qdq_bcorr(_ptr(x), _ptr(y), N, C, HW, _ptr(qp), _ptr(bias), 1, _stream(x)), 'cnnq_pc_qdq_bcorr')
-    return y
+    return _result(y, parts=dict(sums=sums, bias=bias) if want_parts else None)
 
 
-def _bcorr_bias(x, part3, group):
-    """The correction's bias from the [G, 3, C] partial sums; with world size > 1 those of the global batch (an all_gather)."""
+def qdq_bias_corrected_nhwc(x, qp, relu_first, out=None, want_parts=False):
+    """qdq_bias_corrected on a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is (DESIGN.md section
+    15): cnnq_pc_qdq_bcorr_nhwc - the per-channel sums over slabs of rows, the bias, the fused quantize + correct pass; one host
+    call, one cached workspace - 12 B/elem in fp32, 6 in bf16 / fp16.  y has x's layout and dtype; want_parts: (y, dict(sums
+    [3, C] float64 = {sum x', sum q, count(x' > 0)}, bias [C])).  One GPU: the sums are this tensor's.  A tensor that is not
+    dense channels_last (or CNNQ_NHWC=0: copied, counted) takes qdq_bias_corrected, which is float32 only."""
+    x = _dev_act_layout(x, 'x')
+    if x.dim() != 4:
+        raise L.CnnqError('qdq_bias_corrected_nhwc: x must be a 4-D activation, got %d dimensions' % x.dim())
+    if not _is_nhwc(x):
+        if x.dtype != torch.float32:
+            _half_only('qdq_bias_corrected_nhwc', 'the bias correction of a tensor that is not dense channels_last')
+        N, C, HW = geometry(x)
+        return qdq_bias_corrected(x, N, C, HW, qp, relu_first, out=out, want_parts=want_parts)
+    C = x.shape[1]
+    if not (qp.is_cuda and qp.dtype == torch.float32 and qp.is_contiguous() and tuple(qp.shape) == (L.NQP, C)):
+        raise L.CnnqError('qdq_bias_corrected_nhwc: qp must be a contiguous float32 [%d, %d] device table' % (L.NQP, C))
+    R = x.numel() // C
+    dt = _DTYPE_CODES[x.dtype]
+    nbytes = _ws_bytes('bcorr_nhwc', R, C, 1, dt)
+    y = _out_like(x, out)
+    st = _raw_stream(x.device.index)
+    if want_parts:
+        sums = torch.empty((3, C), dtype=torch.float64, device=x.device)
+        bias = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws, sp, bp = _scratch(x, 'bcorr_nhwc', nbytes, st).data_ptr(), sums.data_ptr(), bias.data_ptr()
+    else:
+        # the bias nobody outside the call reads follows the records in the cached workspace
+        ws = _scratch(x, 'bcorr_nhwc', nbytes + C * 4, st).data_ptr()
+        sp, bp = None, ws + nbytes
+    rc = L.load().cnnq_pc_qdq_bcorr_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, _ptr(qp), int(bool(relu_first)), ws, sp, bp, st)
+    if rc:
+        L.check(rc, 'cnnq_pc_qdq_bcorr_nhwc')
+    return _result(y, parts=dict(sums=sums, bias=bias) if want_parts else None)
+
+
+def _bcorr_bias(x, part3, group, sums_out=None):
+    """The correction's bias from the [G, 3, C] partial sums; with world size > 1 those of the global batch (an all_gather).
+    sums_out (optional [3, C] float64) receives the merged sums the bias was made from."""
     lib = L.load()
     G, _, C = part3.shape
     bias = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -1480,7 +1522,7 @@ def _bcorr_bias(x, part3, group):
         L.check(lib.cnnq_pc_bcorr_bias(_ptr(part3), G, C, _ptr(sums), None, _stream(x)), 'cnnq_pc_bcorr_bias')
         part3 = D.all_gather_records(sums, group)
         G = part3.shape[0]
-    L.check(lib.cnnq_pc_bcorr_bias(_ptr(part3), G, C, None, _ptr(bias), _stream(x)), 'cnnq_pc_bcorr_bias')
+    L.check(lib.cnnq_pc_bcorr_bias(_ptr(part3), G, C, _ptr(sums_out), _ptr(bias), _stream(x)), 'cnnq_pc_bcorr_bias')
     return bias
 
 

@@ -94,7 +94,8 @@ class IntQuantizer:
 
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
-        if isinstance(tensor, torch.Tensor) and tensor.dtype in HALF_DTYPES and not self._half_native(tensor, override_att):
+        if (isinstance(tensor, torch.Tensor) and tensor.dtype in HALF_DTYPES
+                and not self._half_native(tensor, override_att, stat_id)):
             return upcast_fallback(self.__call__, tensor, id, tag, stat_id, override_att)
         if override_att is not None:
             orig_att = getattr(self, override_att[0])
@@ -124,14 +125,17 @@ class IntQuantizer:
                 setattr(self, override_att[0], orig_att)
         return res
 
-    def _half_native(self, tensor, override_att=None):
+    def _half_native(self, tensor, override_att=None, stat_id=None):
         """Whether a bf16 / fp16 tensor takes a path with half kernels: config 2 (gemmlowpQuantizeActivationPerChannel without
-        clipping, bit allocation, entropy, a bias correction to fold in or a sharded batch), config 1 (gemmlowpMinMaxQuantize), or
-        config 3 on a dense channels_last tensor (_nhwc_aciq: gemmlowpClippingQuantize's native route)."""
+        clipping, bit allocation, entropy, a bias correction to fold in or a sharded batch), config 1 (gemmlowpMinMaxQuantize),
+        config 3 on a dense channels_last tensor (_nhwc_aciq: gemmlowpClippingQuantize's native route), or - stat_id given - a
+        pending bias correction on a dense channels_last tensor (_nhwc_bcorr)."""
         def att(k):
             return override_att[1] if override_att is not None and override_att[0] == k else getattr(self, k)
         if att('kld'):
             return False
+        if self._nhwc_bcorr(tensor, att('clipping'), stat_id, att):
+            return True
         if att('clipping') != 'no':
             return not att('mtd_quant') and self._nhwc_aciq(tensor, att('clipping'), att)
         if att('pcq_w'):
@@ -153,6 +157,27 @@ class IntQuantizer:
                 and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
                 and not att('measure_entropy') and self.fuse_bcorr is None
                 and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+
+    def _nhwc_bcorr(self, tensor, clip_type, stat_id, att=None):
+        """Whether the per-channel activation branches fold a pending bias correction in on the channels_last storage as it is
+        (ops.qdq_bias_corrected_nhwc): a dense channels_last tensor on the per-channel activation branch
+        (min/max, Laplace or Gaussian clipping) with calibrated statistics (stat_id: the product requests the correction only
+        under -sm use, so only the table-driven form exists), a pending fuse_bcorr, no entropy measurement, and a batch that is
+        not sharded.  Without stat_id: False, and every other answer is what it was.  Shape, strides and attributes only."""
+        att = att or (lambda k: getattr(self, k))
+        return (stat_id is not None and self.fuse_bcorr is not None and bool(att('pcq_a')) and _is_pc_act(tensor)
+                and clip_type in ('no', 'laplace', 'gaus') and not (clip_type == 'no' and att('pcq_w'))
+                and tensor.dim() == 4 and not tensor.is_contiguous()
+                and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
+                and not att('mtd_quant') and not att('kld') and not att('measure_entropy')
+                and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+
+    def _bcorr_nhwc(self, tensor, table, clip_type, prior_b):
+        """The _nhwc_bcorr route: the parameters of the calibration table, then Q/DQ and correction where the tensor lies."""
+        use_ba = bool(self.bit_alloc_act) and self.num_bits <= 4
+        qp, _ = ops.pc_params(table, self.num_bits, self._positive, clip_type, use_ba, prior_b, self.bit_alloc_target_act,
+                              self.bit_alloc_round)
+        return ops.qdq_bias_corrected_nhwc(tensor, qp, bool(self._take_bcorr()))
 
     def __repr__(self):
         # iq.py:124-126, printed by the manager in verbose mode
@@ -215,6 +240,8 @@ class IntQuantizer:
             if use_ba:
                 rows[L.STAT_B if prior_b else L.STAT_STD] = ('b' if prior_b else 'std', 'mean')
             table = self._stats_table(stat_id, C, tensor.device, rows)
+            if self._nhwc_bcorr(tensor, 'no', stat_id):
+                return self._bcorr_nhwc(tensor, table, 'no', prior_b)
         out = ops.act_qdq_per_channel(tensor, self.num_bits, positive=self._positive, clip='no',
                                       bit_alloc=self.bit_alloc_act, prior_is_b=prior_b,
                                       target=self.bit_alloc_target_act, round_mode=self.bit_alloc_round,
@@ -238,6 +265,8 @@ class IntQuantizer:
                 rows = {L.STAT_MIN: ('min', 'mean'), L.STAT_MAX: ('max', 'mean'), L.STAT_MEAN: ('mean', 'mean'),
                         L.STAT_B: ('b', 'mean'), L.STAT_STD: ('std', 'mean')}
                 table = self._stats_table(stat_id, C, tensor.device, rows)
+                if self._nhwc_bcorr(tensor, clip_type, stat_id):
+                    return self._bcorr_nhwc(tensor, table, clip_type, prior_b)
             if self._nhwc_aciq(tensor, clip_type):
                 # a dense channels_last activation: quantized where it lies, the result keeps layout and dtype
                 return ops.aciq_qdq_nhwc(tensor, self.num_bits, positive=self._positive, clip=clip_type,

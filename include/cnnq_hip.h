@@ -698,6 +698,23 @@ int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, in
 int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
                           float* stats, float* qp, float* diag, void* stream);
 
+/* Activation bias correction (iqm.py:180-196) fused into the table-driven Q/DQ on dense channels_last activations; counterpart
+ * of cnnq_pc_qdq_bcorr_sums + cnnq_pc_bcorr_bias + cnnq_pc_qdq_bcorr behind ONE call on [R][C], three launches:
+ *   1. per channel sum x', sum q, count(x' > 0) over slabs of rows, with q = the fp32 Q/DQ of x from qp[CNNQ_NQP][C] (the IEEE
+ *      divide) and x' = relu(x) when relu_first != 0, into ws (read-only pass over x);
+ *   2. cnnq_pc_bcorr_bias on those records: bias[c] = ((float)sum x' - (float)sum q) / ((float)count + 1e-8f), and - sums !=
+ *      NULL - the merged sums[3][C] (doubles);
+ *   3. y = q + (q > 0) * bias[c], rounded once into the element type.
+ * The sums are added in an order fixed by (R, C, dtype, alignment) alone: run after run the same bits, not the NCHW chain's
+ * order.  Promised: the sums within the statistics tier of fp64 (the count exact), and given them bias and y bit for bit.
+ * bias[C] is an OUTPUT.  ws: cnnq_pc_qdq_bcorr_nhwc_workspace bytes (the records of the widest slab count over the piece
+ * widths; 0 on bad arguments), 8-byte aligned, as sums.  A bad dtype, R < 1, C < 1, a NULL x / y / qp / ws / bias, a
+ * misaligned ws / sums or x == y returns CNNQ_EINVAL before anything touches the device.  Re-entrant, allocates nothing, no host
+ * synchronisation. */
+size_t cnnq_pc_qdq_bcorr_nhwc_workspace(int64_t R, int64_t C, int dtype);
+int cnnq_pc_qdq_bcorr_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* qp, int relu_first, void* ws,
+                           double* sums, float* bias, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
