@@ -30,8 +30,9 @@
 // all in one anonymous namespace of this single translation unit; below them is the C ABI.  The host glue the entry points
 // share is written once: the runtime -> template dispatchers (with_shape / with_int / with_bool), the exchange workspace view
 // (gws_view) and the fused-launch rule (fused_ok / plan_fused) in cnnq_plan.hip.h next to the launch_* functions, with_piece
-// (element type x piece width) in cnnq_nhwc.hip.h, and - right below the includes here - the argument checks and the small
-// argument builders; a caller workspace's layout (StatsWs, MmWs, AciqWs) stands next to the function that sizes it.
+// (element type x piece width) in cnnq_nhwc.hip.h, and - right below the includes here - the argument checks, the small
+// argument builders and the channels_last plan and dispatcher (ClPlan, cl_launch); a caller workspace's layout (StatsWs, MmWs,
+// AciqWs) stands next to the function that sizes it.
 
 #include <string.h>
 
@@ -134,6 +135,43 @@ int launch_absdev(const float* x, int64_t N, int64_t C, int64_t HW, const float*
         });
     });
     return launch_status();
+}
+
+// ---- dense channels_last activations: the plan and the dispatcher of the *_nhwc entry points at the end of this file ----------
+// What every channels_last entry point and route function derives - after its argument checks (R, C >= 1, C <= CL_C_MAX), before
+// its first launch - from the shape, the element type and the alignment x and y share: the piece width w, the geometry m of the
+// statistics launches (cl_geo_mm), the geometry q of the element-wise pass (cl_geo_qdq), and whether 32 bits index them.
+struct ClPlan {
+    int w;
+    ClGeo m, q;
+    ClPlan(int64_t R, int64_t C, int dtype, int align_bytes)
+        : w(cl_piece(C, cl_esize(dtype), align_bytes)), m(cl_geo_mm(R, C, w)), q(cl_geo_qdq(R, C, w)) {}
+    dim3 mgrid() const { return dim3((unsigned)(m.S * m.nb)); }
+    dim3 qgrid() const { return dim3((unsigned)(q.S * q.nb)); }
+    // CNNQ_ERANGE unless the largest grid, the element-wise pass' q.S * q.nb workgroups, stays below 2^31 (m has q's nb - both
+    // come from P and CP - and fewer than CL_MM_MAX_WGS + nb workgroups).  rows32: and a slab has fewer than 2^31 rows.  Asked
+    // only by who keeps that count in 32 bits: k_cl_bcorr_sums' per-lane counter and out[2] of cnnq_pc_route_aciq_nhwc.
+    // k_cl_minmax counts nothing and k_cl_moments takes its count in fp64 from the 64-bit row bounds, so configs 2 and 3 and
+    // cnnq_pc_route_nhwc accept such a slab.
+    int range(bool rows32) const {
+        if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+        return (rows32 && m.rpw >= ((int64_t)1 << 31)) ? CNNQ_ERANGE : 0;
+    }
+};
+
+// with_piece plus the tensors as the kernels' element pointers: f(Piece<T, W>, const Raw* x, Raw* y), or f(Piece<T, W>, const Raw* x)
+// for a launch that only reads; the launch's status
+template <class F>
+inline int cl_launch(int dtype, int w, const void* x, void* y, F&& f) {
+    with_piece(dtype, w, [&](auto pc) {
+        using Raw = typename ClRaw<typename decltype(pc)::T>::type;
+        f(pc, static_cast<const Raw*>(x), static_cast<Raw*>(y));
+    });
+    return launch_status();
+}
+template <class F>
+inline int cl_launch(int dtype, int w, const void* x, F&& f) {
+    return cl_launch(dtype, w, x, nullptr, [&](auto pc, auto* xr, auto*) { f(pc, xr); });
 }
 
 }  // namespace
@@ -1650,37 +1688,22 @@ size_t cnnq_pc_nhwc_workspace(int64_t R, int64_t C, int dtype) {
     return ((size_t)2 + 2 * (size_t)cl_slabs_max(R, C, dtype)) * (size_t)C * sizeof(float);
 }
 
-// the head of both route functions: the piece width and the two geometries of this tensor
-static int cl_route(int64_t R, int64_t C, int dtype, int align_bytes, const void* out, int* w, ClGeo* m, ClGeo* q) {
-    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
-    *w = cl_piece(C, cl_esize(dtype), align_bytes);
-    *m = cl_geo_mm(R, C, *w);
-    *q = cl_geo_qdq(R, C, *w);
-    return (int64_t)q->S * q->nb >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
-}
-
 int cnnq_pc_route_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
-    int w;
-    ClGeo m, q;
-    const int rc = cl_route(R, C, dtype, align_bytes, out, &w, &m, &q);
-    if (rc) return rc;
-    out[0] = w;
-    out[1] = m.S;
-    out[2] = q.S * q.nb;
-    out[3] = (int32_t)(m.rpw / m.RS);
+    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, align_bytes);
+    if (const int rc = p.range(false)) return rc;
+    out[0] = p.w;
+    out[1] = p.m.S;
+    out[2] = p.q.S * p.q.nb;
+    out[3] = (int32_t)(p.m.rpw / p.m.RS);
     return 0;
 }
 
-static int cl_qdq(const void* x, void* y, int dtype, int w, int64_t R, int64_t C, const float* qp, const float* mm, hipStream_t st) {
-    const ClGeo q = cl_geo_qdq(R, C, w);
-    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
-    with_piece(dtype, w, [&](auto pc) {
-        using T = typename decltype(pc)::T;
-        using Raw = typename ClRaw<T>::type;
-        hipLaunchKernelGGL((k_cl_qdq<T, decltype(pc)::W>), dim3((unsigned)(q.S * q.nb)), dim3(TPB), 0, st, static_cast<const Raw*>(x),
-                           static_cast<Raw*>(y), q, qp, mm);
+static int cl_qdq(const void* x, void* y, int dtype, const ClPlan& p, const float* qp, const float* mm, hipStream_t st) {
+    return cl_launch(dtype, p.w, x, y, [&](auto pc, auto* xr, auto* yr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_cl_qdq<typename P::T, P::W>), p.qgrid(), dim3(TPB), 0, st, xr, yr, p.q, qp, mm);
     });
-    return launch_status();
 }
 
 // int_quantizer.py:409-451, 557-603 on [R][C]: k_cl_minmax -> k_minmax_params (qp) -> k_minmax_reduce (the extrema) -> k_cl_qdq
@@ -1688,21 +1711,18 @@ int cnnq_pc_minmax_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_
                             float* qp, float* mm, void* stream) {
     if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
     if (!x || !y || !ws || !qp || num_bits < 1 || num_bits > 32) return CNNQ_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int w = cl_piece(C, cl_esize(dtype), h_align(x, y));
-    const ClGeo m = cl_geo_mm(R, C, w);
-    if ((int64_t)cl_geo_qdq(R, C, w).S * m.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(false)) return rc;
+    hipStream_t st = hs(stream);
     float* ext = mm ? mm : ws;
     float* pmm = ws + 2 * (size_t)C;
-    with_piece(dtype, w, [&](auto pc) {
-        using T = typename decltype(pc)::T;
-        hipLaunchKernelGGL((k_cl_minmax<T, decltype(pc)::W>), dim3((unsigned)(m.S * m.nb)), dim3(TPB), 0, st,
-                           static_cast<const typename ClRaw<T>::type*>(x), m, pmm);
+    int rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_cl_minmax<typename P::T, P::W>), p.mgrid(), dim3(TPB), 0, st, xr, p.m, pmm);
     });
-    int rc = launch_status();
-    if (!rc) rc = cnnq_pc_minmax_params(pmm, m.S, C, num_bits, positive, qp, stream);
-    if (!rc) rc = cnnq_pc_minmax_reduce(pmm, m.S, C, ext, stream);
-    if (!rc) rc = cl_qdq(x, y, dtype, w, R, C, qp, ext, st);
+    if (!rc) rc = cnnq_pc_minmax_params(pmm, p.m.S, C, num_bits, positive, qp, stream);
+    if (!rc) rc = cnnq_pc_minmax_reduce(pmm, p.m.S, C, ext, stream);
+    if (!rc) rc = cl_qdq(x, y, dtype, p, qp, ext, st);
     return rc;
 }
 
@@ -1710,7 +1730,9 @@ int cnnq_pc_minmax_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_
 int cnnq_pc_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* qp, void* stream) {
     if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
     if (!x || !y || !qp) return CNNQ_EINVAL;
-    return cl_qdq(x, y, dtype, cl_piece(C, cl_esize(dtype), h_align(x, y)), R, C, qp, nullptr, (hipStream_t)stream);
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(false)) return rc;
+    return cl_qdq(x, y, dtype, p, qp, nullptr, hs(stream));
 }
 
 // ---- config 3 on dense channels_last activations (cnnq_nhwc_aciq.hip.h) --------------------------------------------------------
@@ -1723,16 +1745,14 @@ size_t cnnq_pc_aciq_nhwc_workspace(int64_t R, int64_t C, int dtype) {
 // Which launches cnnq_pc_aciq_qdq_nhwc makes for this geometry (host only).  out[5] is 1 throughout: no class of layer is sent
 // back to the copy route; one that measures slower native than through the copy (tools/bench_channels_last_aciq.py) goes back here.
 int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[6]) {
-    int w;
-    ClGeo m, q;
-    const int rc = cl_route(R, C, dtype, align_bytes, out, &w, &m, &q);
-    if (rc) return rc;
-    if (m.rpw >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
-    out[0] = w;
-    out[1] = m.S;
-    out[2] = (int32_t)m.rpw;
-    out[3] = (int32_t)(m.rpw / m.RS);
-    out[4] = q.S * q.nb;
+    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, align_bytes);
+    if (const int rc = p.range(true)) return rc;
+    out[0] = p.w;
+    out[1] = p.m.S;
+    out[2] = (int32_t)p.m.rpw;
+    out[3] = (int32_t)(p.m.rpw / p.m.RS);
+    out[4] = p.q.S * p.q.nb;
     out[5] = 1;
     return 0;
 }
@@ -1747,30 +1767,26 @@ int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t 
     if (cfg->direct_range) return CNNQ_EINVAL;                                           // the per-tensor branch has no channels
     const bool use_ba = cfg_bit_alloc(cfg);
     if (use_ba && !diag) return CNNQ_EINVAL;                                             // the bit table lives in diag
-    const int w = cl_piece(C, cl_esize(dtype), h_align(x, y));
-    const ClGeo m = cl_geo_mm(R, C, w);
-    const ClGeo q = cl_geo_qdq(R, C, w);
-    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(false)) return rc;
+    const ClGeo& m = p.m;
     const bool need_b = cfg->clip == 1 || (use_ba && cfg->prior_is_b);
     const AciqWs a(ws, m.S, C);
     double *const part = a.part, *const mom = a.mom, *const part2 = a.part2;
     hipStream_t st = hs(stream);
-    const dim3 grid((unsigned)(m.S * m.nb)), block(TPB);
     const bool ntl = nt_loads(R * C * cl_esize(dtype));
     // the Q/DQ walks the tensor descending: the statistics launch in front of it ascends, so with pass B pass A descends
     const int rev = need_b ? 1 : 0;
     // pass A (k_cl_moments), then pass B (k_cl_absdev) on the merged table
     auto pass = [&](bool b) {
-        with_piece(dtype, w, [&](auto pc) {
+        return cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
             with_bool(ntl, [&](auto nt) {
-                using T = typename decltype(pc)::T;
-                constexpr int W = decltype(pc)::W;
-                const auto* xr = static_cast<const typename ClRaw<T>::type*>(x);
-                if (b) hipLaunchKernelGGL((k_cl_absdev<T, W, decltype(nt)::value>), grid, block, 0, st, xr, m, stats, part2);
-                else hipLaunchKernelGGL((k_cl_moments<T, W, decltype(nt)::value>), grid, block, 0, st, xr, m, rev, part);
+                using P = decltype(pc);
+                constexpr bool NT = decltype(nt)::value;
+                if (b) hipLaunchKernelGGL((k_cl_absdev<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, part2);
+                else hipLaunchKernelGGL((k_cl_moments<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, part);
             });
         });
-        return launch_status();
     };
     int rc = pass(false);
     // the merge writes every row of the table (zero for KURT, STD_POS; B without pass B)
@@ -1780,7 +1796,7 @@ int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t 
         if (!rc) rc = cnnq_pc_combine_dev(part2, m.S, C, mom, 0, nullptr, stats, stream);
     }
     if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
-    if (!rc) rc = cl_qdq(x, y, dtype, w, R, C, qp, nullptr, st);
+    if (!rc) rc = cl_qdq(x, y, dtype, p, qp, nullptr, st);
     return rc;
 }
 
@@ -1797,28 +1813,20 @@ int cnnq_pc_qdq_bcorr_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t
                            double* sums, float* bias, void* stream) {
     if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
     if (!x || !y || x == y || !qp || !ws || !bias || misaligned(ws, 8) || misaligned(sums, 8)) return CNNQ_EINVAL;
-    const int w = cl_piece(C, cl_esize(dtype), h_align(x, y));
-    const ClGeo m = cl_geo_mm(R, C, w);
-    const ClGeo q = cl_geo_qdq(R, C, w);
-    // a lane counts its rows in 32 bits
-    if ((int64_t)q.S * q.nb >= ((int64_t)1 << 31) || m.rpw >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(true)) return rc;                                         // a lane counts its rows in 32 bits
     double* part3 = static_cast<double*>(ws);
     hipStream_t st = hs(stream);
-    with_piece(dtype, w, [&](auto pc) {
-        using T = typename decltype(pc)::T;
-        hipLaunchKernelGGL((k_cl_bcorr_sums<T, decltype(pc)::W>), dim3((unsigned)(m.S * m.nb)), dim3(TPB), 0, st,
-                           static_cast<const typename ClRaw<T>::type*>(x), m, relu_first ? 1 : 0, qp, part3);
+    int rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_cl_bcorr_sums<typename P::T, P::W>), p.mgrid(), dim3(TPB), 0, st, xr, p.m, relu_first ? 1 : 0, qp, part3);
     });
-    int rc = launch_status();
-    if (!rc) rc = cnnq_pc_bcorr_bias(part3, m.S, C, sums, bias, stream);
+    if (!rc) rc = cnnq_pc_bcorr_bias(part3, p.m.S, C, sums, bias, stream);
     if (rc) return rc;
-    with_piece(dtype, w, [&](auto pc) {
-        using T = typename decltype(pc)::T;
-        using Raw = typename ClRaw<T>::type;
-        hipLaunchKernelGGL((k_cl_qdq_bias<T, decltype(pc)::W>), dim3((unsigned)(q.S * q.nb)), dim3(TPB), 0, st,
-                           static_cast<const Raw*>(x), static_cast<Raw*>(y), q, qp, bias);
+    return cl_launch(dtype, p.w, x, y, [&](auto pc, auto* xr, auto* yr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_cl_qdq_bias<typename P::T, P::W>), p.qgrid(), dim3(TPB), 0, st, xr, yr, p.q, qp, bias);
     });
-    return launch_status();
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
-// cnnq_nhwc.hip.h - config 2 on dense channels_last (NHWC) activations: exact per-channel min / max partials over slabs of
-// rows and the per-channel Q/DQ, for fp32, bf16 and fp16 elements.
+// cnnq_nhwc.hip.h - dense channels_last (NHWC) activations: the tiling, the two summation regimes and the LDS meeting that
+// every channels_last kernel shares (cnnq_nhwc_aciq.hip.h and cnnq_nhwc_bcorr.hip.h hold the sum reductions built on them),
+// and config 2 itself: exact per-channel min / max partials over slabs of rows and the
+// per-channel Q/DQ, for fp32, bf16 and fp16 elements.
 // Part of the single translation unit cnnq_kernels.hip (see its header for the design).
 //
 // The contract: for a dense channels_last x, y has x's layout and y.contiguous() equals, bit for bit, the
@@ -11,7 +13,13 @@
 // Tiling: the tensor is the matrix [R = N*H*W][C], C innermost.  A row is cut into P = C / W pieces of W consecutive channels
 // (W the widest of 16 / 8 / 4 / 2 / 1 bytes that divides C and both pointers' alignment).  A workgroup owns a column block of
 // CP = min(P, TPB) pieces and a slab of rows; lane t keeps piece t % CP for its whole life and walks rows t / CP, t / CP + RS,
-// ... (RS = TPB / CP rows per step), so its channels never change: running extrema and Q/DQ parameters stay in registers.
+// ... (RS = TPB / CP rows per step), so its channels never change: running extrema, running sums and Q/DQ parameters stay in
+// registers.
+//
+// Sums: above CL_EXACT_ROWS rows, CL_FOLD rows are added in fp32 and folded into an fp64 accumulator; smaller tensors and a
+// lane's leftover rows are added in fp64 element by element (why, and why there: at CL_EXACT_ROWS below).  The lanes that share
+// a piece meet through LDS and are combined in ascending row order by one thread per channel (cl_fold_sums for the sums):
+// an order fixed by ClGeo alone.
 #pragma once
 #include "cnnq_common.hip.h"
 #include "cnnq_qdq.hip.h"
@@ -88,6 +96,45 @@ __device__ __forceinline__ ClLane cl_lane(const ClGeo& g, int bid) {
     l.r1 = (int64_t)(s + 1) * g.rpw;
     if (l.r1 > g.R) l.r1 = g.R;
     return l;
+}
+
+// The two summation regimes of the sum reductions (k_cl_moments, k_cl_absdev, k_cl_bcorr_sums).  CL_FOLD rows are added in fp32 - (v0 + v1) + (v2 + v3), three roundings, each
+// relative to a four-term sum, as Mom::add4 - and folded into an fp64 accumulator.  Those roundings are unbiased and average out
+// over the R / 4 partial sums of a channel, but a channel's variance is the small difference sum x^2 - (sum x)^2 / R, which
+// magnifies them by k = 1 + mean^2 / var.  So a tensor of at most CL_EXACT_ROWS rows (the elements per channel), and the rows a lane
+// has left over, are added in fp64 element by element - exact sums of the fp32 values.  Derivation of the border: a four-term fp32
+// partial sum of squares carries a relative rounding error of about e4 = 6e-8 (rms); over the R / 4 partials of a channel the
+// relative error of sum x^2 is e4 / sqrt(R / 4), the variance magnifies it by k, and the std takes half of that.  Assumed
+// conditioning: k <= 300 (|mean| <= 3.5 at std >= 0.2, the worst channel of the test generator over 2048 channels; real
+// post-BN activations are far below).  R = 4096 then gives 300 * 6e-8 / 32 / 2 = 2.8e-7 (1 sigma) against the 2e-6 tier - seven
+// sigma; R = 49 gives 2.6e-6, which is what was seen there (3e-6 on the two worst of 2048 channels).  Channels worse conditioned
+// than k = 300 are the open item DESIGN.md section 14 names.  The fp64 path costs one v_add_f64 and one v_fma_f64 per element
+// instead of half an fp64 operation; only tensors of at most 4096 * C elements take it, and its speed has not been measured.
+constexpr int CL_FOLD = 4;           // rows per fp32 partial sum
+static_assert(CL_FOLD == 4, "the fold bodies name their four rows");
+constexpr int CL_EXACT_ROWS = 4096;
+
+// The meeting of the lanes that share a piece, for fp64 sums: each stores its W values into the [RS][CP * W] LDS table, and one
+// thread per column j (channel c of the tensor) adds the column's RS entries in ascending row order -> rec_row[c], a row of this
+// slab's record; two barriers (the table is free again on return).  (The extrema meet the same way in k_cl_minmax, k_cl_moments.)
+template <int W>
+__device__ __forceinline__ void cl_fold_sums(double* __restrict__ l_d, const ClGeo& g, int b, const double (&v)[W],
+                                             double* __restrict__ rec_row) {
+    const int t = (int)threadIdx.x;
+    if (t < g.RS * g.CP) {
+#pragma unroll
+        for (int i = 0; i < W; ++i) l_d[t * W + i] = v[i];
+    }
+    __syncthreads();
+    const int cols = g.CP * W;
+    for (int j = t; j < cols; j += TPB) {
+        const int c = b * cols + j;
+        if (c >= g.C) break;
+        double a = l_d[j];
+        for (int k = 1; k < g.RS; ++k) a += l_d[k * cols + j];
+        rec_row[c] = a;
+    }
+    __syncthreads();
 }
 
 // exact per-channel {min, max} of slab s -> pmm[s][2][C] (the layout k_minmax_params / k_minmax_reduce merge): plain stores, every

@@ -9,53 +9,13 @@
 // are added in an order fixed by the geometry (ClGeo) alone - it is not the NCHW chain's order, so equality with that chain is
 // not promised - and run after run the same: no atomics, every record entry stored once by one lane.
 //
-// Tiling: k_cl_minmax's (cnnq_nhwc.hip.h).  A lane keeps one piece of W consecutive channels and walks the rows of its slab, so
-// it owns W running sums per quantity.  Sums: CL_FOLD rows are added in fp32 - (v0 + v1) + (v2 + v3), three roundings, each
-// relative to a four-term sum, as Mom::add4 - and folded into an fp64 accumulator.  Those roundings are unbiased and average out
-// over the R / 4 partial sums of a channel, but a channel's variance is the small difference sum x^2 - (sum x)^2 / R, which
-// magnifies them by 1 + mean^2 / var: with R = 49 two of 2048 channels had a std 3e-6 off (measured), beyond the 2e-6 of the
-// statistics tier.  So a tensor of at most CL_EXACT_ROWS rows (the elements per channel), and the rows a lane has left over, are
-// added in fp64 element by element - exact sums of the fp32 values; above it the error falls as 1 / sqrt(R) (a channel of few
-// elements has no thousands of terms for the fp32 roundings to average out over).  The lanes that share a piece meet through LDS
-// and are added in ascending row order by one thread per channel.
+// Tiling, the two summation regimes (CL_FOLD, CL_EXACT_ROWS and why) and the LDS meeting of the sums: cnnq_nhwc.hip.h.  A lane
+// keeps one piece of W consecutive channels and walks the rows of its slab, so it owns W running sums per quantity.
 #pragma once
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_stats.hip.h"
 
 namespace {
-
-constexpr int CL_FOLD = 4;           // rows per fp32 partial sum
-static_assert(CL_FOLD == 4, "the fold loops name their four rows");
-// Tensors of at most this many rows (elements per channel) are summed in fp64 throughout.  Derivation: a four-term fp32 partial sum
-// of squares carries a relative rounding error of about e4 = 6e-8 (rms); over the R / 4 partials of a channel the relative error of
-// sum x^2 is e4 / sqrt(R / 4), the variance magnifies it by k = 1 + mean^2 / var, and the std takes half of that.  Assumed
-// conditioning: k <= 300 (|mean| <= 3.5 at std >= 0.2, the worst channel of the test generator over 2048 channels; real
-// post-BN activations are far below).  R = 4096 then gives 300 * 6e-8 / 32 / 2 = 2.8e-7 (1 sigma) against the 2e-6 tier - seven
-// sigma; R = 49 gives 2.6e-6, which is what was seen there (3e-6 on the two worst of 2048 channels).  Channels worse conditioned
-// than k = 300 are the open item DESIGN.md section 14 names.  The fp64 path costs one v_add_f64 and one v_fma_f64 per element
-// instead of half an fp64 operation; only tensors of at most 4096 * C elements take it, and its speed has not been measured.
-constexpr int CL_EXACT_ROWS = 4096;
-
-// column sums of the [RS][CP * W] table of the lanes' fp64 sums -> row `row` of this slab's record; two barriers
-template <int W>
-__device__ __forceinline__ void cl_fold_sums(double* __restrict__ l_d, const ClGeo& g, int b, const double (&v)[W],
-                                             double* __restrict__ rec_row) {
-    const int t = (int)threadIdx.x;
-    if (t < g.RS * g.CP) {
-#pragma unroll
-        for (int i = 0; i < W; ++i) l_d[t * W + i] = v[i];
-    }
-    __syncthreads();
-    const int cols = g.CP * W;
-    for (int j = t; j < cols; j += TPB) {
-        const int c = b * cols + j;
-        if (c >= g.C) break;
-        double a = l_d[j];
-        for (int k = 1; k < g.RS; ++k) a += l_d[k * cols + j];
-        rec_row[c] = a;
-    }
-    __syncthreads();
-}
 
 // pass A: slab s -> part[s][CNNQ_NMOM][C] (rows SUM_RELU / SUMSQ_RELU zero).  v_min / v_max drop a NaN; the sum of squares is
 // NaN iff an element was (inf * inf = inf, nothing cancels), and then the channel's extrema become NaN - k_cl_minmax's rule with

@@ -10,15 +10,11 @@
 // added in an order fixed by the geometry (ClGeo) alone - not the NCHW chain's - and run after run the same: no atomics, every
 // record entry stored once by one lane.
 //
-// Tiling: k_cl_moments' for the sums (a lane keeps one piece of W consecutive channels, their scale / zero point / qmax in
-// registers, and walks the rows of its slab), k_cl_qdq's for the second pass.  Sums: as k_cl_moments - above CL_EXACT_ROWS rows
-// four rows are added in fp32, (a + b) + (c + d), three roundings each relative to a four-term sum, and folded into an fp64
-// accumulator; a tensor of at most CL_EXACT_ROWS rows and the rows a lane has left over are added in fp64 element by element.
-// The bias is the small difference (sum x' - sum q) / count, which magnifies the roundings of either sum as the variance does in
-// pass A of config 3: the same border keeps a channel of few elements exact.
+// Tiling, the two summation regimes and the LDS meeting of the sums: cnnq_nhwc.hip.h (k_cl_moments' geometry for the sums,
+// k_cl_qdq's for the second pass).  The bias is the small difference (sum x' - sum q) / count, which magnifies the roundings of
+// either sum as the variance does in pass A of config 3: the same border, CL_EXACT_ROWS, keeps a channel of few elements exact.
 #pragma once
 #include "cnnq_nhwc.hip.h"
-#include "cnnq_nhwc_aciq.hip.h"
 
 namespace {
 
