@@ -53,6 +53,7 @@
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_nhwc_bcorr.hip.h"
+#include "cnnq_nhwc_midtread.hip.h"
 #include "cnnq_qerr.hip.h"
 
 namespace {
@@ -1757,8 +1758,37 @@ int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, in
     return 0;
 }
 
+// The statistics table of a channels_last tensor, the front of configs 3 and 5: pass A (k_cl_moments) -> k_combine (-> pass B
+// (k_cl_absdev) on the merged table -> k_combine_dev, need_b).  The merge writes every row of stats (zero for KURT, STD_POS; B
+// without pass B); ws: the AciqWs records for the plan's slab count.  The element-wise pass behind it walks the tensor
+// descending, so the statistics launch in front of it ascends: with pass B, pass A descends.
+static int cl_table(const void* x, int dtype, int64_t R, int64_t C, const ClPlan& p, bool need_b, void* ws, float* stats, void* stream) {
+    const ClGeo& m = p.m;
+    const AciqWs a(ws, m.S, C);
+    hipStream_t st = hs(stream);
+    const bool ntl = nt_loads(R * C * cl_esize(dtype));
+    const int rev = need_b ? 1 : 0;
+    auto pass = [&](bool b) {
+        return cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
+            with_bool(ntl, [&](auto nt) {
+                using P = decltype(pc);
+                constexpr bool NT = decltype(nt)::value;
+                if (b) hipLaunchKernelGGL((k_cl_absdev<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, a.part2);
+                else hipLaunchKernelGGL((k_cl_moments<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, a.part);
+            });
+        });
+    };
+    int rc = pass(false);
+    if (!rc) rc = cnnq_pc_combine(a.part, m.S, C, 0, a.mom, stats, stream);
+    if (!rc && need_b) {
+        rc = pass(true);
+        if (!rc) rc = cnnq_pc_combine_dev(a.part2, m.S, C, a.mom, 0, nullptr, stats, stream);
+    }
+    return rc;
+}
+
 // int_quantizer.py:327-352 (statistics, ACIQ clipping, bit allocation) + 409-451, 557-603 (parameters, Q/DQ) on [R][C]:
-// k_cl_moments -> k_combine -> (k_cl_absdev -> k_combine_dev) -> k_params -> k_cl_qdq with the table
+// cl_table -> k_params -> k_cl_qdq with the table
 int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
                           float* stats, float* qp, float* diag, void* stream) {
     if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
@@ -1769,34 +1799,61 @@ int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t 
     if (use_ba && !diag) return CNNQ_EINVAL;                                             // the bit table lives in diag
     const ClPlan p(R, C, dtype, h_align(x, y));
     if (const int rc = p.range(false)) return rc;
-    const ClGeo& m = p.m;
     const bool need_b = cfg->clip == 1 || (use_ba && cfg->prior_is_b);
-    const AciqWs a(ws, m.S, C);
-    double *const part = a.part, *const mom = a.mom, *const part2 = a.part2;
-    hipStream_t st = hs(stream);
-    const bool ntl = nt_loads(R * C * cl_esize(dtype));
-    // the Q/DQ walks the tensor descending: the statistics launch in front of it ascends, so with pass B pass A descends
-    const int rev = need_b ? 1 : 0;
-    // pass A (k_cl_moments), then pass B (k_cl_absdev) on the merged table
-    auto pass = [&](bool b) {
-        return cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
-            with_bool(ntl, [&](auto nt) {
-                using P = decltype(pc);
-                constexpr bool NT = decltype(nt)::value;
-                if (b) hipLaunchKernelGGL((k_cl_absdev<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, part2);
-                else hipLaunchKernelGGL((k_cl_moments<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, part);
-            });
-        });
-    };
-    int rc = pass(false);
-    // the merge writes every row of the table (zero for KURT, STD_POS; B without pass B)
-    if (!rc) rc = cnnq_pc_combine(part, m.S, C, 0, mom, stats, stream);
-    if (!rc && need_b) {
-        rc = pass(true);
-        if (!rc) rc = cnnq_pc_combine_dev(part2, m.S, C, mom, 0, nullptr, stats, stream);
-    }
+    int rc = cl_table(x, dtype, R, C, p, need_b, ws, stats, stream);
     if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
-    if (!rc) rc = cl_qdq(x, y, dtype, p, qp, nullptr, st);
+    if (!rc) rc = cl_qdq(x, y, dtype, p, qp, nullptr, hs(stream));
+    return rc;
+}
+
+// ---- config 5 on dense channels_last activations (cnnq_nhwc_midtread.hip.h) ----------------------------------------------------
+// Which launches cnnq_pc_midtread_nhwc makes for this geometry (host only): cnnq_pc_route_aciq_nhwc's report with out[4] the
+// workgroups of the Q/DQ launch without (hist = 0) or with the code histogram.  out[5] is 1 throughout: no class of layer is sent
+// back to the copy route; one that measures slower native than through the copy (tools/bench_channels_last_midtread.py) goes back here.
+int cnnq_pc_route_midtread_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int hist, int32_t out[6]) {
+    const int rc = cnnq_pc_route_aciq_nhwc(R, C, dtype, align_bytes, out);
+    if (rc) return rc;
+    if (hist) {
+        const ClGeo g = cl_geo_mt_hist(R, C, out[0]);
+        out[4] = g.S * g.nb;
+    }
+    return 0;
+}
+
+static int cl_mt_qdq(const void* x, void* y, int dtype, const ClPlan& p, int64_t R, int64_t C, const float* mt, uint64_t* hist, hipStream_t st) {
+    const ClGeo g = hist ? cl_geo_mt_hist(R, C, p.w) : p.q;
+    const dim3 grid((unsigned)(g.S * g.nb));
+    return cl_launch(dtype, p.w, x, y, [&](auto pc, auto* xr, auto* yr) {
+        with_bool(hist != nullptr, [&](auto h) {
+            using P = decltype(pc);
+            hipLaunchKernelGGL((k_cl_mt_qdq<typename P::T, P::W, decltype(h)::value>), grid, dim3(TPB), 0, st, xr, yr, g, mt, u64p(hist));
+        });
+    });
+}
+
+// iq.py:202-224 on [R][C] with a given table mt (cnnq_pc_midtread_params, clip = 1): one launch
+int cnnq_pc_midtread_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* mt, uint64_t* hist, void* stream) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    if (!x || !y || x == y || !mt || misaligned(hist, 8)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(false)) return rc;
+    return cl_mt_qdq(x, y, dtype, p, R, C, mt, hist, hs(stream));
+}
+
+// iq.py:170-225 (per-channel statistics, bin allocation eq. 10, Laplace clipping, mid-tread Q/DQ) on [R][C]:
+// cl_table with pass B -> k_mt_params -> k_cl_mt_qdq
+int cnnq_pc_midtread_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, double target, int sym, const double* tables, int ntab,
+                          void* ws, float* stats, float* mt, uint64_t* hist, void* stream) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    if (!x || !y || x == y || !tables || ntab < 2 || !ws || !stats || !mt || misaligned(ws, 8) || misaligned(hist, 8)) return CNNQ_EINVAL;
+    if (!(target - target == 0.)) return CNNQ_EINVAL;                                    // NaN or infinite
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(false)) return rc;
+    hipStream_t st = hs(stream);
+    if (hist && hipMemsetAsync(hist, 0, (size_t)CNNQ_MT_HIST_WORDS(C) * sizeof(uint64_t), st) != hipSuccess) return launch_status();
+    int rc = cl_table(x, dtype, R, C, p, /*need_b=*/true, ws, stats, stream);
+    if (!rc) rc = cnnq_pc_midtread_params(stats, C, target, 1, sym, tables, ntab, mt, stream);
+    if (!rc) rc = cl_mt_qdq(x, y, dtype, p, R, C, mt, hist, st);
     return rc;
 }
 

@@ -80,7 +80,8 @@ def build_parser():
                         'float32 and then cast (configs 1 and 2 quantize bf16 / fp16 natively, every other path upcasts)')
     p.add_argument('--channels-last', action='store_true',
                    help='run the model and its input in the channels_last (NHWC) memory format, after BN folding, --dtype and '
-                        'the weight quantization (configs 1 and 2 quantize dense channels_last activations as they are)')
+                        'the weight quantization (configs 1, 2, 3 and - with -mtq, with or without -me - 5 quantize dense '
+                        'channels_last activations as they are)')
     p.add_argument('--verbose', action='store_true')
     p.add_argument('--sharded', action='store_true',
                    help='one process per GPU (start under torchrun / torch.distributed.run): every rank takes its shard of each '

@@ -1602,6 +1602,86 @@ def mid_tread_qdq_single(x, N, C, HW, target, sym, tabs, want_entropy=False, wan
     return _mt_result(y, entropy, parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
 
 
+_MT_NHWC_NATIVE = {}
+
+
+def _mt_nhwc_native(R, C, dtype):
+    """Whether this class of layer runs on the channels_last kernels: word 5 of cnnq_pc_route_midtread_nhwc's report (0: a class
+    that measured slower native than copied is sent back to the copy route there; a function of R, C and the dtype alone)."""
+    key = (R, C, dtype)
+    v = _MT_NHWC_NATIVE.get(key)
+    if v is None:
+        out = (ctypes.c_int32 * 6)()
+        L.check(L.load().cnnq_pc_route_midtread_nhwc(R, C, _DTYPE_CODES.get(dtype, -1), 16, 0, out), 'cnnq_pc_route_midtread_nhwc')
+        v = _MT_NHWC_NATIVE[key] = bool(out[5])
+    return v
+
+
+def mid_tread_qdq_nhwc(x, target, sym, want_entropy=False, stats=None, out=None, want_parts=False):
+    """Config 5 with clipping (iq.py:170-225: mid-tread quantization with per-channel bin allocation; want_entropy: the entropy of
+    the codes, -me) on a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is:
+    cnnq_pc_midtread_nhwc - statistics over slabs of rows, step sizes and clamp bounds, Q/DQ with the code histogram, one host
+    call, one cached workspace - or, with `stats` ([NSTAT, C]), cnnq_pc_midtread_params on that table and the table-driven pass.
+    16 B/elem in fp32, 8 in bf16 / fp16.  y has x's layout and dtype.  Returns what mid_tread_qdq returns: (y, entropy or None
+    [, dict(stats, mt, hist)]); inside an entropy_batch block the entropy is filled by the block's one launch.  One GPU: the
+    statistics are this tensor's.  A tensor that is not dense channels_last (or CNNQ_NHWC=0, or a class of layer the route function
+    sends back: copied, counted) takes mid_tread_qdq, which is float32 only - a half tensor raises before anything is copied -
+    and knows neither `stats` nor `out`."""
+    if isinstance(x, torch.Tensor) and x.dim() != 4:
+        raise L.CnnqError('mid_tread_qdq_nhwc: x must be a 4-D activation, got %d dimensions' % x.dim())
+    native = (isinstance(x, torch.Tensor) and x.is_cuda and _NHWC and _layout(x) == 'nhwc'
+              and _mt_nhwc_native(x.numel() // x.shape[1], x.shape[1], x.dtype))
+    if not native and isinstance(x, torch.Tensor) and x.dtype in _HALF_DTYPES:
+        # before anything is copied or counted
+        _half_only('mid_tread_qdq_nhwc', 'the mid-tread quantization of a tensor that does not take the channels_last kernels')
+    x = _dev(x, 'x', _ACT_DTYPES, keep_nhwc=native)
+    if not native:
+        if stats is not None or out is not None:
+            raise L.CnnqError('mid_tread_qdq_nhwc: stats= and out= need a dense channels_last tensor')
+        return mid_tread_qdq(x, target, clip=True, sym=sym, group=False, want_entropy=want_entropy, want_parts=want_parts)
+    lib = L.load()
+    C = x.shape[1]
+    R = x.numel() // C
+    dt = _DTYPE_CODES[x.dtype]
+    tabs = _midtread_tables(x.device)
+    y = _out_like(x, out)
+    st = _raw_stream(x.device.index)
+    if stats is not None:
+        if not (stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous() and tuple(stats.shape) == (L.NSTAT, C)):
+            raise L.CnnqError('mid_tread_qdq_nhwc: stats must be a contiguous float32 [%d, %d] device table' % (L.NSTAT, C))
+        mt = torch.empty((L.NMT, C), dtype=torch.float32, device=x.device)
+        L.check(lib.cnnq_pc_midtread_params(_ptr(stats), C, float(target), 1, int(bool(sym)), _ptr(tabs), tabs.shape[1], _ptr(mt), st),
+                'cnnq_pc_midtread_params')
+        hist = torch.zeros(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None
+        rc = lib.cnnq_pc_midtread_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, _ptr(mt), _ptr(hist), st)
+        if rc:
+            L.check(rc, 'cnnq_pc_midtread_qdq_nhwc')
+    else:
+        nbytes = _ws_bytes('aciq_nhwc', R, C, 1, dt)
+        hist = torch.empty(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None     # zeroed by the call
+        if want_parts or want_entropy:
+            # (the entropy launch reads mt behind the call - at the end of the block inside an entropy_batch)
+            out_tabs = torch.empty((L.NSTAT + L.NMT, C), dtype=torch.float32, device=x.device)
+            stats, mt = out_tabs[:L.NSTAT], out_tabs[L.NSTAT:]
+            ws, tp = _scratch(x, 'aciq_nhwc', nbytes, st).data_ptr(), out_tabs.data_ptr()
+        else:
+            # the tables nobody outside the call reads follow the records in the cached workspace
+            ws = _scratch(x, 'aciq_nhwc', nbytes + (L.NSTAT + L.NMT) * C * 4, st).data_ptr()
+            tp = ws + nbytes
+            mt = None
+        rc = lib.cnnq_pc_midtread_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, float(target), int(bool(sym)), _ptr(tabs), tabs.shape[1],
+                                       ws, tp, tp + L.NSTAT * C * 4, _ptr(hist), st)
+        if rc:
+            L.check(rc, 'cnnq_pc_midtread_nhwc')
+    entropy = None
+    if want_entropy:
+        if _ENT_BATCH is not None:
+            entropy = _ENT_BATCH.add_midtread(hist, mt, C, x.numel(), x.device)      # one launch for the whole block, at its end
+        else:
+            entropy = _mt_entropy(x, hist, mt, C, st)
+    return _mt_result(y, entropy, parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
+
+
 def _mt_entropy(x, hist, mt, C, st, group=None, mom=None):
     """The entropy of a mid-tread code histogram of x.  With the merged moment record `mom` x is a batch shard: the ranks'
     counts are summed over `group` first, and the element count is the global batch's (shards may differ by a sample)."""

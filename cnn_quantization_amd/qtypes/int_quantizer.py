@@ -95,7 +95,7 @@ class IntQuantizer:
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
         if (isinstance(tensor, torch.Tensor) and tensor.dtype in HALF_DTYPES
-                and not self._half_native(tensor, override_att, stat_id)):
+                and not self._half_native(tensor, override_att, stat_id) and not self._nhwc_midtread(tensor, self._att(override_att))):
             return upcast_fallback(self.__call__, tensor, id, tag, stat_id, override_att)
         if override_att is not None:
             orig_att = getattr(self, override_att[0])
@@ -125,13 +125,17 @@ class IntQuantizer:
                 setattr(self, override_att[0], orig_att)
         return res
 
+    def _att(self, override_att=None):
+        """The attribute lookup the dispatch predicates share: __call__'s override_att pair wins over the attribute."""
+        return lambda k: override_att[1] if override_att is not None and override_att[0] == k else getattr(self, k)
+
     def _half_native(self, tensor, override_att=None, stat_id=None):
         """Whether a bf16 / fp16 tensor takes a path with half kernels: config 2 (gemmlowpQuantizeActivationPerChannel without
         clipping, bit allocation, entropy, a bias correction to fold in or a sharded batch), config 1 (gemmlowpMinMaxQuantize),
         config 3 on a dense channels_last tensor (_nhwc_aciq: gemmlowpClippingQuantize's native route), or - stat_id given - a
-        pending bias correction on a dense channels_last tensor (_nhwc_bcorr)."""
-        def att(k):
-            return override_att[1] if override_att is not None and override_att[0] == k else getattr(self, k)
+        pending bias correction on a dense channels_last tensor (_nhwc_bcorr).  Config 5 on a dense channels_last tensor has half
+        kernels too, but is asked separately (_nhwc_midtread): the answers given here for mtd_quant are pinned by tests."""
+        att = self._att(override_att)
         if att('kld'):
             return False
         if self._nhwc_bcorr(tensor, att('clipping'), stat_id, att):
@@ -170,6 +174,21 @@ class IntQuantizer:
                 and tensor.dim() == 4 and not tensor.is_contiguous()
                 and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
                 and not att('mtd_quant') and not att('kld') and not att('measure_entropy')
+                and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+
+    def _nhwc_midtread(self, tensor, att=None):
+        """Whether mid_tread_quantize_activation_per_channel runs this call on the channels_last storage as it is
+        (ops.mid_tread_qdq_nhwc): mid-tread quantization with clipping on the per-channel activation branch,
+        a dense channels_last tensor, no KLD, no bias correction to fold in, replicated data excluded (group is not False) and a
+        batch that is not sharded; the entropy measurement may be on or off.  att: the lookup of _att, as _nhwc_aciq takes it.  Shape,
+        strides and attributes only.  Kept apart from _half_native, which goes on answering False for mtd_quant: the tests of
+        the earlier channels_last routes pin that answer, so __call__ asks both before it upcasts."""
+        get = att or self._att()
+        return (bool(get('mtd_quant')) and get('clipping') != 'no' and not get('kld')
+                and bool(get('pcq_a')) and _is_pc_act(tensor)
+                and tensor.dim() == 4 and not tensor.is_contiguous()
+                and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
+                and self.fuse_bcorr is None
                 and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
 
     def _bcorr_nhwc(self, tensor, table, clip_type, prior_b):
@@ -400,10 +419,16 @@ class IntQuantizer:
 
     def mid_tread_quantize_activation_per_channel(self, tensor, id):
         """iq.py:170-183."""
-        out, entropy = ops.mid_tread_qdq(tensor, self.bit_alloc_target_act, clip=True, sym=not self._positive,
-                                         group=self.group, want_entropy=self.measure_entropy)
+        if self._nhwc_midtread(tensor):
+            # a dense channels_last activation: quantized where it lies, the result keeps layout and dtype
+            out, entropy = ops.mid_tread_qdq_nhwc(tensor, self.bit_alloc_target_act, sym=not self._positive,
+                                                  want_entropy=self.measure_entropy)
+        else:
+            out, entropy = ops.mid_tread_qdq(tensor, self.bit_alloc_target_act, clip=True, sym=not self._positive,
+                                             group=self.group, want_entropy=self.measure_entropy)
+            out = out.view(tensor.shape)
         self._log_entropy(id, entropy, 'avg.entropy.act', tensor.numel())
-        return out.view(tensor.shape)
+        return out
 
 
 def int_quantizer(qtype, quant_params):

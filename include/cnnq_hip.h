@@ -698,6 +698,35 @@ int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, in
 int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
                           float* stats, float* qp, float* diag, void* stream);
 
+/* Config 5 - mid-tread quantization with per-channel bin allocation, and the histogram of its codes for the entropy - on dense
+ * channels_last activations.  As for config 3 the per-channel sums are added in an order fixed by (R, C, dtype, alignment)
+ * alone, so `stats` is promised within the statistics tier of fp64 (MIN / MAX exact), not equal to the NCHW chain's.  Given
+ * the table mt[CNNQ_NMT][C] (cnnq_pc_midtread_params with clip = 1 on stats), y is, bit for bit, cnnq_pc_midtread_qdq's with
+ * clip = 1 on the same values in NCHW order - for bf16 / fp16 on the exactly upconverted values with one round-to-nearest-even
+ * at the end - and so is the histogram: its first CNNQ_MT_HIST_BINS + 2 + 2 * C words and its flag word (zero or not), and the
+ * window bins summed over the replica tables; cnnq_midtread_entropy / _batch consume it unchanged.  Activations always clip:
+ * there is no clip = 0 form, and no codes output.
+ * cnnq_pc_route_midtread_nhwc (host only, nothing enqueued): out as cnnq_pc_route_aciq_nhwc - {elements per load W, row slabs S
+ * of the statistics launches, rows per slab, row loads per lane and slab, workgroups of the Q/DQ launch without (hist = 0) or
+ * with (hist != 0) the histogram, 1 - the native launches (0 would say: this class of layer goes back to the copy route; none
+ * does)}. */
+int cnnq_pc_route_midtread_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int hist, int32_t out[6]);
+/* The table-driven pass (int_quantizer.py:202-224: t = round(x / delta[c]), the two clamps, t * delta[c]; counterpart of
+ * cnnq_pc_midtread_qdq with clip = 1): one launch.  hist: NULL, or CNNQ_MT_HIST_WORDS(C) words zeroed by the caller, 8-byte
+ * aligned.  A bad dtype, R < 1, C < 1, a NULL x / y / mt, a misaligned hist or x == y returns CNNQ_EINVAL before anything
+ * touches the device.  Re-entrant, allocates nothing, no host synchronisation. */
+int cnnq_pc_midtread_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* mt, uint64_t* hist, void* stream);
+/* The dynamic pipeline (int_quantizer.py:170-225: per-channel min / max / mean / std / b, omega by eq. 10 128-135, the clipping
+ * multiplier 137-145, delta and the clamp bounds 193-214, the Q/DQ 202-224, the codes' histogram for 179, 217) behind ONE call
+ * on [R][C]; counterpart of cnnq_pc_stats + cnnq_pc_midtread_params + cnnq_pc_midtread_qdq: pass A -> merge -> pass B -> merge
+ * -> cnnq_pc_midtread_params (clip = 1) -> Q/DQ, six launches.  stats[CNNQ_NSTAT][C] and mt[CNNQ_NMT][C] are OUTPUTS.  hist:
+ * NULL, or CNNQ_MT_HIST_WORDS(C) words, 8-byte aligned, zeroed HERE on the stream.  tables: the (omega, alpha) tables
+ * [2][ntab] in device memory.  ws: cnnq_pc_aciq_nhwc_workspace bytes (the same records), 8-byte aligned.  On top of the
+ * refusals above: a NULL tables / ws / stats / mt, ntab < 2, a misaligned ws or a target that is not finite - CNNQ_EINVAL
+ * before anything touches the device.  Re-entrant, allocates nothing, no host synchronisation. */
+int cnnq_pc_midtread_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, double target, int sym, const double* tables,
+                          int ntab, void* ws, float* stats, float* mt, uint64_t* hist, void* stream);
+
 /* Activation bias correction (iqm.py:180-196) fused into the table-driven Q/DQ on dense channels_last activations; counterpart
  * of cnnq_pc_qdq_bcorr_sums + cnnq_pc_bcorr_bias + cnnq_pc_qdq_bcorr behind ONE call on [R][C], three launches:
  *   1. per channel sum x', sum q, count(x' > 0) over slabs of rows, with q = the fp32 Q/DQ of x from qp[CNNQ_NQP][C] (the IEEE
