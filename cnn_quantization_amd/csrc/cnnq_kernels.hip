@@ -54,6 +54,7 @@
 #include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_nhwc_bcorr.hip.h"
 #include "cnnq_nhwc_midtread.hip.h"
+#include "cnnq_nhwc_entropy.hip.h"
 #include "cnnq_qerr.hip.h"
 
 namespace {
@@ -1707,23 +1708,31 @@ static int cl_qdq(const void* x, void* y, int dtype, const ClPlan& p, const floa
     });
 }
 
-// int_quantizer.py:409-451, 557-603 on [R][C]: k_cl_minmax -> k_minmax_params (qp) -> k_minmax_reduce (the extrema) -> k_cl_qdq
+// The front of config 2 on [R][C], three launches: k_cl_minmax -> k_minmax_params (qp) -> k_minmax_reduce (the extrema, into mm or -
+// mm == NULL - the head of ws); returns them through *ext
+static int cl_minmax_front(const void* x, int dtype, int64_t C, const ClPlan& p, int num_bits, int positive, float* ws, float* qp, float* mm,
+                           float** ext, void* stream) {
+    *ext = mm ? mm : ws;
+    float* pmm = ws + 2 * (size_t)C;
+    int rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_cl_minmax<typename P::T, P::W>), p.mgrid(), dim3(TPB), 0, hs(stream), xr, p.m, pmm);
+    });
+    if (!rc) rc = cnnq_pc_minmax_params(pmm, p.m.S, C, num_bits, positive, qp, stream);
+    if (!rc) rc = cnnq_pc_minmax_reduce(pmm, p.m.S, C, *ext, stream);
+    return rc;
+}
+
+// int_quantizer.py:409-451, 557-603 on [R][C]: cl_minmax_front -> k_cl_qdq
 int cnnq_pc_minmax_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, int num_bits, int positive, float* ws,
                             float* qp, float* mm, void* stream) {
     if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
     if (!x || !y || !ws || !qp || num_bits < 1 || num_bits > 32) return CNNQ_EINVAL;
     const ClPlan p(R, C, dtype, h_align(x, y));
     if (const int rc = p.range(false)) return rc;
-    hipStream_t st = hs(stream);
-    float* ext = mm ? mm : ws;
-    float* pmm = ws + 2 * (size_t)C;
-    int rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
-        using P = decltype(pc);
-        hipLaunchKernelGGL((k_cl_minmax<typename P::T, P::W>), p.mgrid(), dim3(TPB), 0, st, xr, p.m, pmm);
-    });
-    if (!rc) rc = cnnq_pc_minmax_params(pmm, p.m.S, C, num_bits, positive, qp, stream);
-    if (!rc) rc = cnnq_pc_minmax_reduce(pmm, p.m.S, C, ext, stream);
-    if (!rc) rc = cl_qdq(x, y, dtype, p, qp, ext, st);
+    float* ext;
+    int rc = cl_minmax_front(x, dtype, C, p, num_bits, positive, ws, qp, mm, &ext, stream);
+    if (!rc) rc = cl_qdq(x, y, dtype, p, qp, ext, hs(stream));
     return rc;
 }
 
@@ -1787,21 +1796,33 @@ static int cl_table(const void* x, int dtype, int64_t R, int64_t C, const ClPlan
     return rc;
 }
 
-// int_quantizer.py:327-352 (statistics, ACIQ clipping, bit allocation) + 409-451, 557-603 (parameters, Q/DQ) on [R][C]:
-// cl_table -> k_params -> k_cl_qdq with the table
-int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
-                          float* stats, float* qp, float* diag, void* stream) {
+// The argument checks of config 3's entry points, before any launch
+static int cl_aciq_check(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws, float* stats, float* qp,
+                         float* diag) {
     if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
     if (!x || !y || !cfg || !ws || !stats || !qp || misaligned(ws, 8)) return CNNQ_EINVAL;
     if (check_cfg(cfg)) return CNNQ_EINVAL;                                              // as cnnq_pc_params, before any launch
     if (cfg->direct_range) return CNNQ_EINVAL;                                           // the per-tensor branch has no channels
-    const bool use_ba = cfg_bit_alloc(cfg);
-    if (use_ba && !diag) return CNNQ_EINVAL;                                             // the bit table lives in diag
-    const ClPlan p(R, C, dtype, h_align(x, y));
-    if (const int rc = p.range(false)) return rc;
-    const bool need_b = cfg->clip == 1 || (use_ba && cfg->prior_is_b);
+    return (cfg_bit_alloc(cfg) && !diag) ? CNNQ_EINVAL : 0;                              // the bit table lives in diag
+}
+
+// The front of config 3 on [R][C]: cl_table -> k_params (qp, diag)
+static int cl_aciq_front(const void* x, int dtype, int64_t R, int64_t C, const ClPlan& p, const cnnq_params_cfg* cfg, void* ws, float* stats,
+                         float* qp, float* diag, void* stream) {
+    const bool need_b = cfg->clip == 1 || (cfg_bit_alloc(cfg) && cfg->prior_is_b);
     int rc = cl_table(x, dtype, R, C, p, need_b, ws, stats, stream);
     if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
+    return rc;
+}
+
+// int_quantizer.py:327-352 (statistics, ACIQ clipping, bit allocation) + 409-451, 557-603 (parameters, Q/DQ) on [R][C]:
+// cl_aciq_front -> k_cl_qdq with the table
+int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
+                          float* stats, float* qp, float* diag, void* stream) {
+    if (cl_aciq_check(x, y, dtype, R, C, cfg, ws, stats, qp, diag)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(false)) return rc;
+    int rc = cl_aciq_front(x, dtype, R, C, p, cfg, ws, stats, qp, diag, stream);
     if (!rc) rc = cl_qdq(x, y, dtype, p, qp, nullptr, hs(stream));
     return rc;
 }
@@ -1814,14 +1835,14 @@ int cnnq_pc_route_midtread_nhwc(int64_t R, int64_t C, int dtype, int align_bytes
     const int rc = cnnq_pc_route_aciq_nhwc(R, C, dtype, align_bytes, out);
     if (rc) return rc;
     if (hist) {
-        const ClGeo g = cl_geo_mt_hist(R, C, out[0]);
+        const ClGeo g = cl_geo_hist(R, C, out[0]);
         out[4] = g.S * g.nb;
     }
     return 0;
 }
 
 static int cl_mt_qdq(const void* x, void* y, int dtype, const ClPlan& p, int64_t R, int64_t C, const float* mt, uint64_t* hist, hipStream_t st) {
-    const ClGeo g = hist ? cl_geo_mt_hist(R, C, p.w) : p.q;
+    const ClGeo g = hist ? cl_geo_hist(R, C, p.w) : p.q;
     const dim3 grid((unsigned)(g.S * g.nb));
     return cl_launch(dtype, p.w, x, y, [&](auto pc, auto* xr, auto* yr) {
         with_bool(hist != nullptr, [&](auto h) {
@@ -1854,6 +1875,72 @@ int cnnq_pc_midtread_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t 
     int rc = cl_table(x, dtype, R, C, p, /*need_b=*/true, ws, stats, stream);
     if (!rc) rc = cnnq_pc_midtread_params(stats, C, target, 1, sym, tables, ntab, mt, stream);
     if (!rc) rc = cl_mt_qdq(x, y, dtype, p, R, C, mt, hist, st);
+    return rc;
+}
+
+// ---- the uniform Q/DQ that counts its codes (-me) on dense channels_last activations (cnnq_nhwc_entropy.hip.h) ------------------
+static bool hist_bins_ok(int nbins) { return nbins >= 2 && nbins <= 256 && pow2(nbins); }
+static size_t cl_hist_lds(int nbins) { return (size_t)nbins * HREP * sizeof(unsigned); }
+
+// Which launch the counting pass makes for this geometry (host only): out = {elements per load W, workgroups of the counting
+// launch, its dynamic LDS bytes, 1 - the native launch}.  out[3] is 1 throughout: no class of layer is sent back to the copy
+// route; one that measures slower native than through the copy (tools/bench_channels_last_entropy.py) goes back here, with the
+// figure next to the rule.
+int cnnq_pc_route_qdq_hist_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int nbins, int32_t out[4]) {
+    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes) || !hist_bins_ok(nbins)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, align_bytes);
+    if (const int rc = p.range(false)) return rc;
+    const ClGeo g = cl_geo_hist(R, C, p.w);
+    out[0] = p.w;
+    out[1] = g.S * g.nb;
+    out[2] = (int32_t)cl_hist_lds(nbins);
+    out[3] = 1;
+    return 0;
+}
+
+static int cl_qdq_hist(const void* x, void* y, int dtype, const ClPlan& p, int64_t R, int64_t C, const float* qp, int nbins, uint64_t* hist_rep,
+                       hipStream_t st) {
+    const ClGeo g = cl_geo_hist(R, C, p.w);          // at most p.q's workgroups: inside ClPlan::range
+    const dim3 grid((unsigned)(g.S * g.nb));
+    return cl_launch(dtype, p.w, x, y, [&](auto pc, auto* xr, auto* yr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_cl_qdq_hist<typename P::T, P::W>), grid, dim3(TPB), cl_hist_lds(nbins), st, xr, yr, g, qp, nbins, u64p(hist_rep));
+    });
+}
+
+// int_quantizer.py:573-592 on [R][C] with a given table, and the codes of 586-587 counted into hist_rep: one launch
+int cnnq_pc_qdq_hist_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* qp, int nbins, uint64_t* hist_rep, void* stream) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    if (!x || !y || x == y || !qp || !hist_rep || misaligned(hist_rep, 8) || !hist_bins_ok(nbins)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(false)) return rc;
+    return cl_qdq_hist(x, y, dtype, p, R, C, qp, nbins, hist_rep, hs(stream));
+}
+
+// int_quantizer.py:409-451, 557-603 with 586-587 on [R][C]: cl_minmax_front -> k_cl_qdq_hist with 2^num_bits bins
+int cnnq_pc_minmax_qdq_hist_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, int num_bits, int positive, float* ws, float* qp,
+                                 float* mm, uint64_t* hist_rep, void* stream) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    if (!x || !y || x == y || !ws || !qp || !hist_rep || misaligned(ws, 4) || misaligned(hist_rep, 8)) return CNNQ_EINVAL;
+    if (num_bits < 1 || num_bits > 8) return CNNQ_EINVAL;                                // the codes fit a byte, the bins 256
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(false)) return rc;
+    float* ext;
+    int rc = cl_minmax_front(x, dtype, C, p, num_bits, positive, ws, qp, mm, &ext, stream);
+    if (!rc) rc = cl_qdq_hist(x, y, dtype, p, R, C, qp, 1 << num_bits, hist_rep, hs(stream));
+    return rc;
+}
+
+// int_quantizer.py:327-352 + 409-451, 557-603 with 586-587 on [R][C]: cl_aciq_front -> k_cl_qdq_hist; 256 bins under bit
+// allocation (the channels' qmax is decided on the device), else 2^num_bits
+int cnnq_pc_aciq_qdq_hist_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws, float* stats,
+                               float* qp, float* diag, uint64_t* hist_rep, void* stream) {
+    if (cl_aciq_check(x, y, dtype, R, C, cfg, ws, stats, qp, diag)) return CNNQ_EINVAL;
+    if (x == y || !hist_rep || misaligned(hist_rep, 8) || cfg->num_bits > 8) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, h_align(x, y));
+    if (const int rc = p.range(false)) return rc;
+    int rc = cl_aciq_front(x, dtype, R, C, p, cfg, ws, stats, qp, diag, stream);
+    if (!rc) rc = cl_qdq_hist(x, y, dtype, p, R, C, qp, cfg_bit_alloc(cfg) ? 256 : 1 << cfg->num_bits, hist_rep, hs(stream));
     return rc;
 }
 

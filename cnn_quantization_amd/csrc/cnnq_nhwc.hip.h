@@ -295,6 +295,17 @@ inline ClGeo cl_geo_mm(int64_t R, int64_t C, int w) {
 inline ClGeo cl_geo_qdq(int64_t R, int64_t C, int w) {
     return cl_geo(R, C, w, CL_QDQ_ELEMS, ((int64_t)1 << 31) - 1, ((int64_t)1 << 31) - 1);
 }
+// The element-wise passes that count their codes (k_cl_mt_qdq<HIST>, k_cl_qdq_hist): every workgroup zeroes and folds an LDS table
+// and flushes one global atomic per live bin - and k_cl_mt_qdq, for a tensor of up to TPB * W channels, hits the same 2 * C clamp
+// counters - so they take 8 times CL_QDQ_ELEMS per workgroup, to keep the flush a small part of the workgroup's life.  The factor
+// is a design guess (CL_MM_ELEMS of the statistics launches); tools/bench_channels_last_entropy.py sweeps it through the
+// development knob CNNQ_CL_HIST_ELEMS (builds with -DCNNQ_DEV_KNOBS only, read per call; a workgroup's counts stay in 32 bits).
+constexpr int CL_HIST_ELEMS = 65536;
+inline ClGeo cl_geo_hist(int64_t R, int64_t C, int w) {
+    int64_t per = env_int("CNNQ_CL_HIST_ELEMS", CL_HIST_ELEMS);
+    per = per < 1 ? 1 : per > ((int64_t)1 << 30) ? ((int64_t)1 << 30) : per;
+    return cl_geo(R, C, w, per, ((int64_t)1 << 31) - 1, ((int64_t)1 << 31) - 1);
+}
 
 // runtime (element type, piece width) -> template arguments: f(Piece<T, W>) with T = CF32 (W = 4 / 2 / 1), HBf16 or HF16
 // (W = 8 / 4 / 2 / 1).  F32 = false: the bf16 / fp16 kernels of cnnq_half.hip.h, which have no fp32 instance.  A width a kernel

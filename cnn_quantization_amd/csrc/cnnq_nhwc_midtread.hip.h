@@ -25,7 +25,7 @@ namespace {
 // registers, everything else (rare) goes to global memory at once.  What a workgroup hands over at its end: one atomic per live
 // window bin into replica table (workgroup id % MT_GR), and - the RS lanes that share a piece folded through LDS first - one
 // atomic per channel and bound that was hit.  Every workgroup of a tensor of up to TPB * W channels hits the same 2 * C clamp
-// counters, so the histogram variant runs on a geometry of its own (cl_geo_mt_hist) with longer slabs.
+// counters, so the histogram variant runs on the long slabs of cl_geo_hist (cnnq_nhwc.hip.h).
 // The update and the flush are k_mt_qdq's, copied: the contract needs both to stay the same for good, and shared __device__
 // helpers would make that structural.  They are not shared yet because k_mt_qdq's speed is measured (the note above it: the
 // branch-free update was worth 2.2x the VALU instructions) and moving its body behind a call was not re-measured; who changes
@@ -152,15 +152,6 @@ __global__ void __launch_bounds__(TPB) k_cl_mt_qdq(const typename ClRaw<T>::type
             }
         }
     }
-}
-
-// ---- host side: the histogram variant's geometry
-// Every workgroup flushes its window bins and - for a tensor of up to TPB * W channels - hits the same 2 * C clamp counters, so
-// the histogram variant takes 8 times CL_QDQ_ELEMS per workgroup, to keep the flush a small part of the workgroup's life.  The
-// factor is a design guess (CL_MM_ELEMS of the statistics launches), not a swept value.
-constexpr int64_t CL_MT_HIST_ELEMS = 65536;
-inline ClGeo cl_geo_mt_hist(int64_t R, int64_t C, int w) {
-    return cl_geo(R, C, w, CL_MT_HIST_ELEMS, ((int64_t)1 << 31) - 1, ((int64_t)1 << 31) - 1);
 }
 
 }  // namespace

@@ -614,6 +614,72 @@ def _minmax_qdq_nhwc(x, num_bits, positive, out):
     return y
 
 
+def _hist_bins(num_bits, use_ba):
+    """The bins a counting channels_last pass keeps (nbins of cnnq_pc_qdq_hist_nhwc): 2^num_bits where the parameters come from
+    num_bits alone - every channel's qmax is 2^num_bits - 1 - and 256 under bit allocation, whose per-channel qmax is decided on
+    the device."""
+    return 256 if use_ba else 1 << int(num_bits)
+
+
+def _pc_qdq_hist_nhwc(x, qp, nbins, out, slot, st):
+    """_pc_qdq_nhwc that also counts its codes into the replica tables of `slot` (cnnq_pc_qdq_hist_nhwc): (y, entropy)."""
+    hist, ent_batched = slot
+    C = x.shape[1]
+    y = _out_like(x, out)
+    rc = L.load().cnnq_pc_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), _DTYPE_CODES[x.dtype], x.numel() // C, C, _ptr(qp), nbins, _ptr(hist), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_qdq_hist_nhwc')
+    return y, _replica_entropy(x, hist, ent_batched, st)
+
+
+def _minmax_qdq_hist_nhwc(x, num_bits, positive, out, slot, st):
+    """_minmax_qdq_nhwc that also counts its codes into the replica tables of `slot` (cnnq_pc_minmax_qdq_hist_nhwc): (y, entropy)."""
+    hist, ent_batched = slot
+    lib = L.load()
+    C = x.shape[1]
+    R = x.numel() // C
+    dt = _DTYPE_CODES[x.dtype]
+    nbytes = _ws_bytes('nhwc', R, C, 1, dt)
+    y = _out_like(x, out)
+    ws = _scratch(x, 'nhwc', nbytes + L.NQP * C * 4, st).data_ptr()
+    rc = lib.cnnq_pc_minmax_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, int(num_bits), 1 if positive else 0, ws, ws + nbytes,
+                                          None, _ptr(hist), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_minmax_qdq_hist_nhwc')
+    return y, _replica_entropy(x, hist, ent_batched, st)
+
+
+_HIST_NHWC_NATIVE = {}
+
+
+def _hist_nhwc_native(R, C, dtype):
+    """Whether this class of layer runs the counting channels_last pass: word 3 of cnnq_pc_route_qdq_hist_nhwc's report (0: a class
+    that measured slower native than copied is sent back to the copy route there; a function of R, C and the dtype alone)."""
+    key = (R, C, dtype)
+    v = _HIST_NHWC_NATIVE.get(key)
+    if v is None:
+        out = (ctypes.c_int32 * 4)()
+        L.check(L.load().cnnq_pc_route_qdq_hist_nhwc(R, C, _DTYPE_CODES.get(dtype, -1), 16, 256, out), 'cnnq_pc_route_qdq_hist_nhwc')
+        v = _HIST_NHWC_NATIVE[key] = bool(out[3])
+    return v
+
+
+def _nhwc_hist_slot(x, what, st):
+    """Where the counting pass of a dense channels_last x counts, as _entropy_slot gives it: (x, (tables, result or None)).  A class
+    of layer the route function sends back, and a call that can have no replica table (first use under a stream capture), take the
+    copy route instead: (x.contiguous() - counted, as _dev counts it - , None); that route is float32 only, so a half tensor raises
+    before anything is copied."""
+    C = x.shape[1]
+    slot = _entropy_slot(x, st) if _hist_nhwc_native(x.numel() // C, C, x.dtype) else (None, None)
+    if slot[0] is not None:
+        return x, slot
+    if x.dtype != torch.float32:
+        _half_only(what, 'the entropy of a tensor that does not take the channels_last kernels')
+    global LAYOUT_COPIES
+    LAYOUT_COPIES += 1
+    return x.contiguous(), None
+
+
 _GROUP_WS = {}
 GROUP_WS_BYTES = 18 << 20
 
@@ -1296,11 +1362,21 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
     fused into the passes where the parameter table is at hand (qdq_bias_corrected).
     Returns y [, codes] [, entropy (0-dim device tensor)] [, parts].  No host synchronisation."""
     use_ba = bool(bit_alloc) and num_bits <= 4 and not whole_tensor
-    # config 2, dynamic on one GPU or from a statistics table, keeps a dense channels_last x as it is (DESIGN.md section 12)
+    # config 2, dynamic on one GPU or from a statistics table, keeps a dense channels_last x as it is (DESIGN.md section 12) - also
+    # with the entropy of its codes when they fit a byte (section 17; a sharded batch sums the ranks' counts: the NCHW route)
     nhwc = (per_channel_dim == 1 and not whole_tensor and clip == 'no' and not use_ba and bcorr is None
-            and not (want_codes or want_entropy or want_parts) and (stats is not None or not _sharded(group)))
+            and not (want_codes or want_parts) and (stats is not None or not _sharded(group))
+            and not (want_entropy and (num_bits > 8 or _sharded(group))))
     x = _dev_act_layout(x, 'x') if nhwc else _dev_act(x, 'x')
     N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x, per_channel_dim)
+    if _is_nhwc(x) and want_entropy:
+        st = _raw_stream(x.device.index)
+        x, slot = _nhwc_hist_slot(x, 'act_qdq_per_channel', st)
+        if slot is not None:
+            if stats is None:
+                return _minmax_qdq_hist_nhwc(x, num_bits, positive, out, slot, st)
+            qp, _ = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
+            return _pc_qdq_hist_nhwc(x, qp, _hist_bins(num_bits, use_ba), out, slot, st)
     if _is_nhwc(x):
         if stats is None:
             return _minmax_qdq_nhwc(x, num_bits, positive, out)
@@ -1380,33 +1456,50 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
 
 
 def aciq_qdq_nhwc(x, num_bits, positive=False, clip='laplace', bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
-                  stats=None, out=None, want_parts=False):
+                  stats=None, out=None, want_parts=False, want_entropy=False):
     """Config 3 (iq.py:327-352 -> 409-451: ACIQ clipping 'laplace' / 'gaus', optionally bit allocation) on a dense channels_last
     activation of fp32 / bf16 / fp16, on the storage as it is: cnnq_pc_aciq_qdq_nhwc - statistics over
     slabs of rows, parameters, Q/DQ, one host call, one cached workspace - or, with `stats` ([NSTAT, C], -sm use), pc_params and
     the table-driven Q/DQ.  y has x's layout and dtype; want_parts: (y, dict(stats, qp, diag)).  One GPU: the statistics are this
-    tensor's.  A tensor that is not dense channels_last (or CNNQ_NHWC=0: copied, counted) takes act_qdq_per_channel."""
+    tensor's.  A tensor that is not dense channels_last (or CNNQ_NHWC=0: copied, counted) takes act_qdq_per_channel.
+    want_entropy: the Q/DQ pass counts its codes (cnnq_pc_aciq_qdq_hist_nhwc, or cnnq_pc_qdq_hist_nhwc
+    with `stats`) and the entropy follows y as act_qdq_per_channel returns it - y, entropy [, parts]; inside an entropy_batch
+    block it is filled by the block's one launch.  Who takes the counted copy instead: _nhwc_hist_slot."""
     if clip not in ('laplace', 'gaus'):
         raise L.CnnqError("aciq_qdq_nhwc: clip must be 'laplace' or 'gaus', got %r" % (clip,))
+    if want_entropy and num_bits > 8:
+        raise L.CnnqError('aciq_qdq_nhwc: the ACIQ factor tables end at 8 bits')
     x = _dev_act_layout(x, 'x')
     if x.dim() != 4:
         raise L.CnnqError('aciq_qdq_nhwc: x must be a 4-D activation, got %d dimensions' % x.dim())
     use_ba = bool(bit_alloc) and num_bits <= 4
+    st = _raw_stream(x.device.index)
+    hist = ent_batched = None
+    if want_entropy and _is_nhwc(x):
+        x, slot = _nhwc_hist_slot(x, 'aciq_qdq_nhwc', st)
+        if slot is not None:
+            hist, ent_batched = slot
     if not _is_nhwc(x):
         return act_qdq_per_channel(x, num_bits, positive, clip, bit_alloc, prior_is_b, target, round_mode, group=False,
-                                   want_parts=want_parts, stats=stats, out=out)
-    C = x.shape[1]
-    if stats is not None:
-        qp, diag = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
-        y = _pc_qdq_nhwc(x, qp, out)
-        return _result(y, parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
+                                   want_parts=want_parts, stats=stats, out=out, want_entropy=want_entropy)
     lib = L.load()
-    cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
+    C = x.shape[1]
     R = x.numel() // C
     dt = _DTYPE_CODES[x.dtype]
+    if stats is not None:
+        qp, diag = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
+        if want_entropy:
+            y = _out_like(x, out)
+            rc = lib.cnnq_pc_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, _ptr(qp), _hist_bins(num_bits, use_ba), _ptr(hist), st)
+            if rc:
+                L.check(rc, 'cnnq_pc_qdq_hist_nhwc')
+        else:
+            y = _pc_qdq_nhwc(x, qp, out)
+        return _result(y, entropy=_replica_entropy(x, hist, ent_batched, st) if want_entropy else None,
+                       parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
+    cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
     nbytes = _ws_bytes('aciq_nhwc', R, C, 1, dt)
     y = _out_like(x, out)
-    st = _raw_stream(x.device.index)
     ntab = (L.NSTAT + L.NQP + L.NDIAG) * C * 4
     if want_parts:
         tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, C, dtype=torch.float32, device=x.device)
@@ -1415,13 +1508,16 @@ def aciq_qdq_nhwc(x, num_bits, positive=False, clip='laplace', bit_alloc=False, 
         # the tables nobody outside the call reads follow the records in the cached workspace
         ws = _scratch(x, 'aciq_nhwc', nbytes + ntab, st).data_ptr()
         tp = ws + nbytes
-    rc = lib.cnnq_pc_aciq_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
-                                   tp + (L.NSTAT + L.NQP) * C * 4, st)
+    if want_entropy:
+        rc = lib.cnnq_pc_aciq_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                            tp + (L.NSTAT + L.NQP) * C * 4, _ptr(hist), st)
+    else:
+        rc = lib.cnnq_pc_aciq_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                       tp + (L.NSTAT + L.NQP) * C * 4, st)
     if rc:
         L.check(rc, 'cnnq_pc_aciq_qdq_nhwc')
-    if not want_parts:
-        return y
-    return y, dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:])
+    return _result(y, entropy=_replica_entropy(x, hist, ent_batched, st) if want_entropy else None,
+                   parts=dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:]) if want_parts else None)
 
 
 def weight_correction(w, w_q, vcorr=False, bcorr=False):

@@ -95,7 +95,8 @@ class IntQuantizer:
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
         if (isinstance(tensor, torch.Tensor) and tensor.dtype in HALF_DTYPES
-                and not self._half_native(tensor, override_att, stat_id) and not self._nhwc_midtread(tensor, self._att(override_att))):
+                and not self._half_native(tensor, override_att, stat_id) and not self._nhwc_midtread(tensor, self._att(override_att))
+                and not self._nhwc_entropy(tensor, self._att(override_att))):
             return upcast_fallback(self.__call__, tensor, id, tag, stat_id, override_att)
         if override_att is not None:
             orig_att = getattr(self, override_att[0])
@@ -186,6 +187,24 @@ class IntQuantizer:
         get = att or self._att()
         return (bool(get('mtd_quant')) and get('clipping') != 'no' and not get('kld')
                 and bool(get('pcq_a')) and _is_pc_act(tensor)
+                and tensor.dim() == 4 and not tensor.is_contiguous()
+                and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
+                and self.fuse_bcorr is None
+                and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+
+    def _nhwc_entropy(self, tensor, att=None):
+        """Whether gemmlowpQuantizeActivationPerChannel measures the entropy of its codes on the channels_last storage as it is
+        (ops.act_qdq_per_channel's counting route): measure_entropy on the per-channel activation branch
+        without clipping - no KLD, no weight branch in front of it, no mid-tread, no bit allocation in effect, codes that fit a
+        byte - a dense channels_last tensor, no bias correction pending (with -me the layer corrects afterwards), replicated data
+        excluded (group is not False) and a batch that is not sharded; dynamic or with stat_id.  att: the lookup of _att.  Shape,
+        strides and attributes only.  Kept apart from _half_native, which goes on answering False for measure_entropy: the
+        tests of the earlier channels_last routes pin that answer, so __call__ asks both before it upcasts.  Config 3 with
+        -me is one predicate away (ops.aciq_qdq_nhwc takes want_entropy) and stays on the copy route, as its tests pin it."""
+        get = att or self._att()
+        return (bool(get('measure_entropy')) and bool(get('pcq_a')) and _is_pc_act(tensor)
+                and get('clipping') == 'no' and not get('pcq_w') and not get('mtd_quant') and not get('kld')
+                and not (get('bit_alloc_act') and get('num_bits') <= 4) and get('num_bits') <= 8
                 and tensor.dim() == 4 and not tensor.is_contiguous()
                 and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
                 and self.fuse_bcorr is None

@@ -727,6 +727,38 @@ int cnnq_pc_midtread_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int6
 int cnnq_pc_midtread_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, double target, int sym, const double* tables,
                           int ntab, void* ws, float* stats, float* mt, uint64_t* hist, void* stream);
 
+/* The uniform per-channel Q/DQ with the histogram of its codes (-me: int_quantizer.py:586-587, the codes exist in the
+ * reference only as the argument of shannon_entropy, 445) on dense channels_last activations.  Given the table
+ * qp[CNNQ_NQP][C], y is cnnq_pc_qdq_nhwc's bit for bit, and the counts are, word for word once the replica tables are summed,
+ * the histogram cnnq_pc_qdq fills on the same values in NCHW order (for bf16 / fp16 on the exactly upconverted values).
+ * hist_rep: cnnq_hist_replica_bytes() bytes, 8-byte aligned, zero at rest - the contract of the single-launch kernels: the
+ * calls ADD to it, cnnq_entropy_replicas[_batch] and cnnq_hist_replicas_fold consume it and leave it zero.
+ * nbins: the bins the counting workgroups keep, a power of two in [2, 256] above every channel's qmax (a code is counted in
+ * bin code & (nbins - 1)); the dynamic forms choose it: 2^num_bits, 256 under bit allocation.
+ * All three refuse - CNNQ_EINVAL before anything touches the device - a bad dtype, R < 1, C < 1, a NULL required pointer
+ * (hist_rep included), a misaligned ws or hist_rep, and x == y; CNNQ_ERANGE as their counterparts without the histogram.
+ * Re-entrant, no allocation, no host synchronisation, graph-capturable.
+ * cnnq_pc_route_qdq_hist_nhwc (host only, nothing enqueued): out = {elements per load W (cnnq_pc_route_nhwc's out[0]),
+ * workgroups of the counting launch, its dynamic LDS bytes (nbins * 32 replicas * 4), 1 - the native launch (0 would say:
+ * this class of layer goes back to the copy route; none does)}. */
+int cnnq_pc_route_qdq_hist_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int nbins, int32_t out[4]);
+/* The table-driven pass (int_quantizer.py:573-592 with 586-587; counterpart of cnnq_pc_qdq with hist): one launch.  On top
+ * of the refusals above: an nbins that is not a power of two in [2, 256]. */
+int cnnq_pc_qdq_hist_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* qp, int nbins, uint64_t* hist_rep,
+                          void* stream);
+/* Config 2, dynamic (int_quantizer.py:409-451, 557-603 with 586-587; counterpart of cnnq_pc_minmax_qdq_single with hist_rep):
+ * the three launches in front of cnnq_pc_minmax_qdq_nhwc's Q/DQ unchanged, then the counting pass with 2^num_bits bins.  ws:
+ * cnnq_pc_nhwc_workspace bytes, 4-byte aligned; qp and mm (may be NULL) as cnnq_pc_minmax_qdq_nhwc.  On top of the refusals
+ * above: num_bits outside [1, 8]. */
+int cnnq_pc_minmax_qdq_hist_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, int num_bits, int positive, float* ws,
+                                 float* qp, float* mm, uint64_t* hist_rep, void* stream);
+/* Config 3, dynamic (int_quantizer.py:327-352 + 409-451, 557-603 with 586-587; counterpart of cnnq_pc_aciq_qdq_single with
+ * hist_rep): cnnq_pc_aciq_qdq_nhwc's statistics and parameter launches unchanged, then the counting pass - 256 bins under bit
+ * allocation, else 2^num_bits.  ws: cnnq_pc_aciq_nhwc_workspace bytes, 8-byte aligned; cfg, stats, qp, diag as
+ * cnnq_pc_aciq_qdq_nhwc, whose refusals apply; on top of them: num_bits > 8. */
+int cnnq_pc_aciq_qdq_hist_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
+                               float* stats, float* qp, float* diag, uint64_t* hist_rep, void* stream);
+
 /* Activation bias correction (iqm.py:180-196) fused into the table-driven Q/DQ on dense channels_last activations; counterpart
  * of cnnq_pc_qdq_bcorr_sums + cnnq_pc_bcorr_bias + cnnq_pc_qdq_bcorr behind ONE call on [R][C], three launches:
  *   1. per channel sum x', sum q, count(x' > 0) over slabs of rows, with q = the fp32 Q/DQ of x from qp[CNNQ_NQP][C] (the IEEE
