@@ -52,6 +52,7 @@
 #include "cnnq_half.hip.h"
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
+#include "cnnq_nhwc_collect.hip.h"
 #include "cnnq_nhwc_bcorr.hip.h"
 #include "cnnq_nhwc_midtread.hip.h"
 #include "cnnq_nhwc_entropy.hip.h"
@@ -1824,6 +1825,67 @@ int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t 
     if (const int rc = p.range(false)) return rc;
     int rc = cl_aciq_front(x, dtype, R, C, p, cfg, ws, stats, qp, diag, stream);
     if (!rc) rc = cl_qdq(x, y, dtype, p, qp, nullptr, hs(stream));
+    return rc;
+}
+
+// ---- `-sm collect` on dense channels_last activations (cnnq_nhwc_collect.hip.h) ---------------------------------------------------
+// ws of cnnq_pc_stats_nhwc: config 3's records (AciqWs without the table) for the widest slab count over the piece widths
+size_t cnnq_pc_stats_nhwc_workspace(int64_t R, int64_t C, int dtype) { return cnnq_pc_aciq_nhwc_workspace(R, C, dtype); }
+
+// Which launches cnnq_pc_stats_nhwc makes for this geometry (host only): out = {elements per load W, row slabs S, rows per slab, 1 -
+// the native launches}.  out[3] is 1 throughout: no class of layer is sent back to the copy route; one that measures slower native
+// than through the copy (tools/bench_channels_last_collect.py) goes back here, with the figures next to the rule.
+int cnnq_pc_route_stats_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
+    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, align_bytes);
+    if (const int rc = p.range(true)) return rc;
+    out[0] = p.w;
+    out[1] = p.m.S;
+    out[2] = (int32_t)p.m.rpw;
+    out[3] = 1;
+    return 0;
+}
+
+// smpc.py:45-79 on [R][C]: pass A (k_cl_moments, with the rectified sums k_cl_moments_relu) -> k_combine(has_relu) (-> pass B
+// (k_cl_absdev, with the fourth moment k_cl_absdev_kurt) on the merged table -> k_combine_dev(want_kurt)), two or four launches.
+// Without need_kurt and need_relu these are cl_table's launches with cl_table's arguments.  As there, pass A descends when an
+// ascending pass B follows it.
+int cnnq_pc_stats_nhwc(const void* x, int dtype, int64_t R, int64_t C, int need_b, int need_kurt, int need_relu, void* ws, double* mom,
+                       float* stats, void* stream) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    if (!x || !ws || !stats || misaligned(ws, 8) || misaligned(mom, 8)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, h_align(x, x));
+    if (const int rc = p.range(true)) return rc;
+    const ClGeo& m = p.m;
+    const AciqWs a(ws, m.S, C);
+    double* rec = mom ? mom : a.mom;
+    hipStream_t st = hs(stream);
+    const bool ntl = nt_loads(R * C * cl_esize(dtype));
+    const bool pass_b = need_b || need_kurt;
+    const int rev = pass_b ? 1 : 0;
+    int rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
+        with_bool(ntl, need_relu != 0, [&](auto nt, auto relu) {
+            using P = decltype(pc);
+            constexpr bool NT = decltype(nt)::value;
+            if constexpr (decltype(relu)::value)
+                hipLaunchKernelGGL((k_cl_moments_relu<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, a.part);
+            else
+                hipLaunchKernelGGL((k_cl_moments<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, a.part);
+        });
+    });
+    if (!rc) rc = cnnq_pc_combine(a.part, m.S, C, need_relu ? 1 : 0, rec, stats, stream);
+    if (rc || !pass_b) return rc;
+    rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
+        with_bool(ntl, need_kurt != 0, [&](auto nt, auto kurt) {
+            using P = decltype(pc);
+            constexpr bool NT = decltype(nt)::value;
+            if constexpr (decltype(kurt)::value)
+                hipLaunchKernelGGL((k_cl_absdev_kurt<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, a.part2);
+            else
+                hipLaunchKernelGGL((k_cl_absdev<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, a.part2);
+        });
+    });
+    if (!rc) rc = cnnq_pc_combine_dev(a.part2, m.S, C, rec, need_kurt ? 1 : 0, nullptr, stats, stream);
     return rc;
 }
 

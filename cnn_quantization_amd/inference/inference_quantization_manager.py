@@ -35,7 +35,7 @@ from ..qtypes import DummyQuantizer, int_quantizer
 from ..qtypes.int_quantizer import upcast_fallback
 from ..utils.misc import Singleton
 from .statistic_manager import StatisticManager
-from .statistic_manager_perchannel import StatisticManagerPerChannel
+from .statistic_manager_perchannel import StatisticManagerPerChannel, collects_native_nhwc
 
 FUSED_RELU_ARCHS = ('alexnet', 'vgg16', 'vgg16_bn', 'inception_v3')
 
@@ -94,6 +94,10 @@ def _route(layer, out, out_id, tag, *, shifted=False, half_range=False, collect_
         if isinstance(qm.stats_manager, StatisticManagerPerChannel) and qm.stats_manager.collect_err:
             # the error columns measure the candidates of the quantizer that `-sm use` will run on this output
             kw.update(half_range=half_range, err_settings=qm.err_settings(out_id, '' if shifted else tag, half_range))
+        if isinstance(qm.stats_manager, StatisticManagerPerChannel) and collects_native_nhwc(qm.stats_manager, out, force_global):
+            # a dense channels_last output the manager reads where it lies, in its own dtype: nothing to upcast
+            qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, **kw)
+            return out
         upcast_fallback(qm.stats_manager.save_tensor_stats, out, tag if collect_tag is None else collect_tag, out_id, **kw)
         return out
     stat_id = out_id if qm.stats_mode is StatsMode.use_stats else None

@@ -9,6 +9,8 @@ The seven statistics of one batch come from two coalesced passes over the activa
 device (cnnq_pc_moments + cnnq_pc_absdev) and ONE device->host copy of a [7, C] table, instead
 of a transposed copy, nine full-tensor reductions and seven synchronising copies
 (smpc.py:51-79,112).
+A dense channels_last activation of fp32 / bf16 / fp16 is read where it lies (ops.pc_stats_nhwc, DESIGN.md section 18: no
+layout copy, no upcast) whenever collects_native_nhwc says so; every other tensor takes the NCHW kernels on a contiguous copy.
 
 `collect_err=True` adds the six clipping-error columns the reference declares (smpc.py:24-32: mse_lowp, mse_gaus,
 mse_laplace, cos_lowp, cos_gaus, cos_laplace; formulas smpc.py:80-100) - the columns `-sm use -c mix` (iq.py:310-323)
@@ -45,6 +47,20 @@ def base_dir():
     return os.path.join(str(Path.home()), 'mxt-sim')
 
 
+def collects_native_nhwc(manager, tensor, force_global_min_max=False):
+    """Whether save_tensor_stats takes this tensor on its channels_last storage (ops.pc_stats_nhwc: no layout copy, no upcast):
+    a dense channels_last activation that is not contiguous, of a dtype the kernels have, with the channels_last switch on, one
+    process and no forced exchange, no error columns, the extrema of the whole batch (batch_avg off, or the caller forces them),
+    and a class of layer the route function keeps native.  Shape, strides and attributes only: nothing touches the device."""
+    if manager.collect_err or (manager.batch_avg and not force_global_min_max):
+        return False
+    if not (isinstance(tensor, torch.Tensor) and tensor.dtype in ops._ACT_DTYPES and ops._NHWC and ops._layout(tensor) == 'nhwc'):
+        return False
+    if D.world_size(manager.group) > 1 or D.forced_exchange():
+        return False
+    return ops._stats_nhwc_native(tensor.numel() // tensor.shape[1], tensor.shape[1], tensor.dtype)
+
+
 class StatisticManagerPerChannel(metaclass=Singleton):
     def __init__(self, folder, load_stats, stats=('max', 'min', 'std', 'mean', 'kurtosis', 'b', 'std_pos'),
                  batch_avg=False, collect_err=False, group=None, err_settings=None):
@@ -77,6 +93,11 @@ class StatisticManagerPerChannel(metaclass=Singleton):
         # FC and 1x1-spatial outputs are not per-channel quantized (smpc.py:47-48)
         if len(tensor.shape) < 3 or (tensor.shape[2] == 1 and tensor.shape[3] == 1):
             return
+        if collects_native_nhwc(self, tensor, force_global_min_max):
+            # dense channels_last, fp32 / bf16 / fp16: the table from the storage as it lies
+            table, _ = ops.pc_stats_nhwc(tensor.detach(), need_b='b' in self.stats_names, need_kurt='kurtosis' in self.stats_names,
+                                         need_relu='std_pos' in self.stats_names)
+            return self._record(id, table)
         N, C = tensor.shape[0], tensor.shape[1]
         HW = tensor.numel() // (N * C)
         x = tensor.detach().contiguous()
@@ -111,6 +132,9 @@ class StatisticManagerPerChannel(metaclass=Singleton):
             err = ops.pc_quant_errors(x, N, C, HW, (qp_p, qp_g, qp_l),
                                       mm=table[[L.STAT_MIN, L.STAT_MAX]] if exact else None)
             table = torch.cat([table, err])
+        self._record(id, table)
+
+    def _record(self, id, table):
         host = table.cpu().numpy()          # the only synchronisation of this call
         layer = self.stats.setdefault(id, {})
         for sn in self.stats_names:

@@ -202,12 +202,12 @@ def _groups(N, C, HW, aligned=None):
 
 
 _NHWC_WS = {'nhwc': 'cnnq_pc_nhwc_workspace', 'aciq_nhwc': 'cnnq_pc_aciq_nhwc_workspace',
-            'bcorr_nhwc': 'cnnq_pc_qdq_bcorr_nhwc_workspace'}
+            'bcorr_nhwc': 'cnnq_pc_qdq_bcorr_nhwc_workspace', 'stats_nhwc': 'cnnq_pc_stats_nhwc_workspace'}
 
 
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
-    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc': N = rows).  0 from the
+    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc', 'stats_nhwc': N = rows).  0 from the
     library: no plan for the geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
@@ -322,6 +322,55 @@ def pc_stats(x, N, C, HW, need_b=False, need_kurt=False, need_relu=False, group=
     if need_b or need_kurt:
         dev_local = pc_combine_dev(pc_absdev(x, N, C, HW, stats, need_kurt), mom, None, need_kurt, want_sums=True)
         pc_combine_dev(D.all_gather_records(dev_local, group), mom, stats, need_kurt)
+    return stats, mom
+
+
+_STATS_NHWC_NATIVE = {}
+
+
+def _stats_nhwc_native(R, C, dtype):
+    """Whether this class of layer collects its statistics on the channels_last kernels: word 3 of cnnq_pc_route_stats_nhwc's
+    report (0: a class that measured slower native than copied is sent back to the copy route there; a function of R, C and the
+    dtype alone), asked once per (R, C, dtype)."""
+    key = (R, C, dtype)
+    v = _STATS_NHWC_NATIVE.get(key)
+    if v is None:
+        out = (ctypes.c_int32 * 4)()
+        L.check(L.load().cnnq_pc_route_stats_nhwc(R, C, _DTYPE_CODES.get(dtype, -1), 16, out), 'cnnq_pc_route_stats_nhwc')
+        v = _STATS_NHWC_NATIVE[key] = bool(out[3])
+    return v
+
+
+def pc_stats_nhwc(x, need_b=False, need_kurt=False, need_relu=False):
+    """pc_stats of a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is (-sm
+    collect, smpc.py:45-79): cnnq_pc_stats_nhwc - pass A over slabs of rows, the merge, pass B when b or the kurtosis is asked
+    for, its merge - one host call, one cached workspace, 8 B/elem in fp32 and 4 in bf16 / fp16 for the full table.  Returns
+    (stats [NSTAT, C] f32, mom [NMOM, C] f64) as pc_stats; rows nobody asked for are zero (B comes with pass B: need_b or
+    need_kurt, as in pc_stats).  One GPU: the statistics are this tensor's.  A tensor that is not dense channels_last (or
+    CNNQ_NHWC=0, or a class of layer the route function sends back: copied, counted) takes pc_stats, which is float32 only - a
+    half tensor raises before anything is copied."""
+    if isinstance(x, torch.Tensor) and x.dim() != 4:
+        raise L.CnnqError('pc_stats_nhwc: x must be a 4-D activation, got %d dimensions' % x.dim())
+    native = (isinstance(x, torch.Tensor) and x.is_cuda and _NHWC and _layout(x) == 'nhwc' and x.dtype in _ACT_DTYPES
+              and _stats_nhwc_native(x.numel() // x.shape[1], x.shape[1], x.dtype))
+    if not native and isinstance(x, torch.Tensor) and x.dtype in _HALF_DTYPES:
+        # before anything is copied or counted
+        _half_only('pc_stats_nhwc', 'the statistics of a tensor that does not take the channels_last kernels')
+    x = _dev(x, 'x', _ACT_DTYPES, keep_nhwc=native)
+    if not native:
+        N, C, HW = geometry(x)
+        return pc_stats(x, N, C, HW, need_b, need_kurt, need_relu, group=False)
+    C = x.shape[1]
+    R = x.numel() // C
+    dt = _DTYPE_CODES[x.dtype]
+    st = _raw_stream(x.device.index)
+    stats = torch.empty((L.NSTAT, C), dtype=torch.float32, device=x.device)
+    mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
+    ws = _scratch(x, 'stats_nhwc', _ws_bytes('stats_nhwc', R, C, 1, dt), st)
+    rc = L.load().cnnq_pc_stats_nhwc(x.data_ptr(), dt, R, C, int(bool(need_b)), int(bool(need_kurt)), int(bool(need_relu)),
+                                     ws.data_ptr(), mom.data_ptr(), stats.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_stats_nhwc')
     return stats, mom
 
 

@@ -698,6 +698,30 @@ int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, in
 int cnnq_pc_aciq_qdq_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
                           float* stats, float* qp, float* diag, void* stream);
 
+/* `-sm collect` - the per-channel calibration table of statistic_manager_perchannel.py:45-125 (the permuted copy of 49-50 and
+ * the nine full-tensor reductions of 51-79) - on dense channels_last activations, on the storage as it lies: no layout copy and
+ * no upcast, x is read once per pass (8 B/elem in fp32, 4 in bf16 / fp16 for the full table).  As for config 3 the per-channel
+ * sums are added in an order fixed by (R, C, dtype, alignment) alone: run after run the same bits, no atomics, but not the NCHW
+ * chain's order.  Promised: rows MIN / MAX exact (a NaN element makes them NaN), every other row within the statistics tier of
+ * fp64 that cnnq_pc_stats_single keeps; rows MIN, MAX, MEAN, STD (and B) do not depend on which of the other rows were asked for
+ * and equal, bit for bit, the table cnnq_pc_aciq_qdq_nhwc writes for the same tensor.
+ * cnnq_pc_stats_nhwc_workspace: bytes of `ws` - cnnq_pc_aciq_nhwc_workspace's: the pass-A and pass-B records of the widest slab
+ * count over the piece widths and the merged moment record (0 on bad arguments).
+ * cnnq_pc_route_stats_nhwc (host only, nothing enqueued): out = {elements per load W, row slabs S of the statistics launches,
+ * rows per slab, 1 - the native launches (0 would say: this class of layer goes back to the copy route; none does)};
+ * align_bytes: the power of two that divides x (<= 16 is what matters). */
+size_t cnnq_pc_stats_nhwc_workspace(int64_t R, int64_t C, int dtype);
+int cnnq_pc_route_stats_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]);
+/* The table behind ONE call on [R][C]; counterpart of cnnq_pc_stats: pass A -> cnnq_pc_combine(has_relu = need_relu) (-> pass B
+ * -> cnnq_pc_combine_dev(want_kurt = need_kurt), when need_b or need_kurt), two or four launches.  stats[CNNQ_NSTAT][C] is
+ * written completely: STD_POS is zero without need_relu, KURT without need_kurt, B unless pass B ran (need_b or need_kurt, as
+ * cnnq_pc_stats).  mom[CNNQ_NMOM][C]: the merged moment record, may be NULL (kept in ws).  ws: cnnq_pc_stats_nhwc_workspace
+ * bytes, 8-byte aligned.  A bad dtype, R < 1, C < 1, a NULL x / ws / stats or a misaligned ws / mom returns CNNQ_EINVAL, a
+ * slab of 2^31 rows or a grid of 2^31 workgroups CNNQ_ERANGE, before anything touches the device.  Re-entrant, allocates
+ * nothing, no host synchronisation, graph-capturable. */
+int cnnq_pc_stats_nhwc(const void* x, int dtype, int64_t R, int64_t C, int need_b, int need_kurt, int need_relu, void* ws,
+                       double* mom, float* stats, void* stream);
+
 /* Config 5 - mid-tread quantization with per-channel bin allocation, and the histogram of its codes for the entropy - on dense
  * channels_last activations.  As for config 3 the per-channel sums are added in an order fixed by (R, C, dtype, alignment)
  * alone, so `stats` is promised within the statistics tier of fp64 (MIN / MAX exact), not equal to the NCHW chain's.  Given
