@@ -100,7 +100,10 @@ __device__ __forceinline__ ChanParams channel_params(const cnnq_params_cfg& cfg,
         r.delta = vmax - r.offset;
     } else {
         if (cfg.clip == 1) {
-            const int ib = (int)bits;  // NaN bits cannot occur: clamped comparisons leave 0..8
+            // bits is 0..8 or NaN: an all-zero or non-finite prior makes `bins` NaN and both clamps of bit_alloc_block
+            // compare false.  The reference raises there (int(nan)); here NaN bits take the 0-bit factor, by a range check
+            // and not by what a conversion of NaN happens to give
+            const int ib = (bits >= 0.f && bits <= 8.f) ? (int)bits : 0;
             r.alpha = vb * (cfg.positive ? c_laplace_pos[ib] : c_laplace[ib]);
         } else if (cfg.clip == 2) {
             r.alpha = vstd * (cfg.positive ? c_gaus_pos[cfg.num_bits] : c_gaus[cfg.num_bits]);
@@ -108,19 +111,20 @@ __device__ __forceinline__ ChanParams channel_params(const cnnq_params_cfg& cfg,
             r.alpha = cfg.pstd * vstd;
         }
         float range;
+        // np.maximum (iq.py:290, :298) propagates NaN, fmaxf would drop it: a NaN statistic stays visible
         if (cfg.positive) {
-            range = fmaxf(vmean, 0.f) + r.alpha;
+            range = pmax(vmean, 0.f) + r.alpha;
             r.offset = 0.f;
         } else {
             range = 2.f * r.alpha;
-            r.offset = fmaxf(vmin, vmean - r.alpha);
+            r.offset = pmax(vmin, vmean - r.alpha);
         }
         const float mx = r.offset + range;                     // iq.py:351
         r.delta = cfg.direct_range ? range : mx - r.offset;    // iq.py:443 (per channel) / :357 (per tensor)
     }
     if (ba) {
         r.qmax = exp2f(bits) - 1.f;
-        r.scale = (r.qmax > 0.f) ? r.delta / r.qmax : 0.f;
+        r.scale = (r.qmax > 0.f) ? r.delta / r.qmax : 0.f;     // NaN bits: NaN qmax compares false, as in torch.where
     } else {
         r.qmax = qmax_of(cfg.num_bits);
         r.scale = r.delta / r.qmax;

@@ -9,6 +9,10 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // per-tensor GEMMLOWP path (replaces kernels/gemmlowp.cu)
 // ------------------------------------------------------------------------------------------
+// int_exp, gemmlowp.cu:36-37: powf(2, int(ceilf(log2f(scale)))).  The power by ldexpf, which is exact: the device's powf is an
+// ulp off for some integer exponents (powf(2.f, 16.f) = 65535.996), and a scale of 2^k has to stay 2^k
+__device__ __forceinline__ float pow2_scale(float scale) { return ldexpf(1.f, (int)ceilf(log2f(scale))); }
+
 // ptp: [0] scale [1] shift [2] qmax [3] true-zero flag [4] passthrough flag [5] range [6] offset
 __global__ void __launch_bounds__(64) k_pt_setup(int have_host, float h_range, float h_offset,
                                                  const float* __restrict__ stats, int64_t stride, int rows,
@@ -46,7 +50,7 @@ __global__ void __launch_bounds__(64) k_pt_setup(int have_host, float h_range, f
     if (lane != 0) return;
     const float qmax = (float)((1ll << num_bits) - 1);
     float scale = range / qmax;
-    if (int_exp) scale = powf(2.f, (float)(int)ceilf(log2f(scale)));
+    if (int_exp) scale = pow2_scale(scale);
     const float zero_point = roundf(-offset / scale);
     ptp[0] = scale;
     ptp[1] = ptz ? zero_point : -offset;
@@ -173,7 +177,7 @@ __device__ __forceinline__ void ptf_params(const PtfWs& w, int rows, int rows_mo
     if (lane != 0) return;
     const float qmax = (float)((1ll << num_bits) - 1);
     float scale = range / qmax;
-    if (int_exp) scale = powf(2.f, (float)(int)ceilf(log2f(scale)));
+    if (int_exp) scale = pow2_scale(scale);
     const float zero_point = roundf(-offset / scale);
     sh_p[0] = scale;
     sh_p[1] = ptz ? zero_point : -offset;
