@@ -154,6 +154,13 @@ SIGNATURES = {
     'cnnq_pc_aciq_qdq_hist_nhwc': (_I, [_P, _P, _I, _L, _L, ctypes.POINTER(ParamsCfg), _P, _P, _P, _P, _P, _P]),
     'cnnq_pc_qdq_bcorr_nhwc_workspace': (ctypes.c_size_t, [_L, _L, _I]),
     'cnnq_pc_qdq_bcorr_nhwc': (_I, [_P, _P, _I, _L, _L, _P, _I, _P, _P, _P, _P]),
+    'cnnq_pc_packed_nhwc_capacity': (ctypes.c_size_t, [_L, _L]),
+    'cnnq_pc_packed_layout_nhwc': (_I, [_P, _I, _L, _P, _P]),
+    'cnnq_pc_route_packed_nhwc': (_I, [_L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_pc_quantize_packed_nhwc': (_I, [_P, _I, _L, _L, _P, _P, _P, _P, _P]),
+    'cnnq_pc_dequantize_packed_nhwc': (_I, [_P, _P, _I, _L, _L, _P, _P, _P]),
+    'cnnq_pc_minmax_quantize_packed_nhwc': (_I, [_P, _I, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'cnnq_pc_aciq_quantize_packed_nhwc': (_I, [_P, _I, _L, _L, ctypes.POINTER(ParamsCfg), _P, _P, _P, _P, _P, _P, _P]),
     'cnnq_pc_minmax_qdq_auto_dt': (_I, [_P, _P, _I, _L, _L, _L, _I, _I, _P, _P, ctypes.c_size_t, _I, _P]),
     'cnnq_pc_qdq_dt': (_I, [_P, _P, _I, _L, _L, _L, _P, _P, _P, _I, _P]),
     'cnnq_pc_minmax_local_dt': (_I, [_P, _I, _L, _L, _L, _P, _P, _P]),

@@ -56,6 +56,7 @@
 #include "cnnq_nhwc_bcorr.hip.h"
 #include "cnnq_nhwc_midtread.hip.h"
 #include "cnnq_nhwc_entropy.hip.h"
+#include "cnnq_nhwc_packed.hip.h"
 #include "cnnq_qerr.hip.h"
 
 namespace {
@@ -2033,6 +2034,115 @@ int cnnq_pc_qdq_bcorr_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t
         using P = decltype(pc);
         hipLaunchKernelGGL((k_cl_qdq_bias<typename P::T, P::W>), p.qgrid(), dim3(TPB), 0, st, xr, yr, p.q, qp, bias);
     });
+}
+
+// ---- integer codes as the stored format of dense channels_last activations (cnnq_nhwc_packed.hip.h) ------------------------------
+size_t cnnq_pc_packed_nhwc_capacity(int64_t R, int64_t C) {
+    if (R < 1 || C < 1) return 0;
+    return (size_t)R * 4 * (size_t)cl_pk_capdw(C);
+}
+
+int cnnq_pc_packed_layout_nhwc(const float* bits, int uniform_bits, int64_t C, uint32_t* coloff, void* stream) {
+    if (!coloff || C < 1 || C > CL_C_MAX) return CNNQ_EINVAL;
+    if (!bits && (uniform_bits < 0 || uniform_bits > 8)) return CNNQ_EINVAL;
+    hipLaunchKernelGGL(k_cl_packed_layout, dim3(1), dim3(PTPB), 0, hs(stream), bits, uniform_bits, (int)C, coloff);
+    return launch_status();
+}
+
+// Which launch cnnq_pc_quantize_packed_nhwc makes for this geometry (host only).  out[3] is 0 only for a row image beyond
+// CL_PK_IMG (C > 8192): a class of layer the pack kernel cannot stage.  No class is sent back to the copy route for speed; one
+// that measures slower native than through the copy beyond the run's spread (tools/bench_channels_last_packed.py,
+// profiles/channels_last_packed.md) goes back here.
+int cnnq_pc_route_packed_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
+    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, align_bytes);
+    if (const int rc = p.range(false)) return rc;
+    out[0] = p.w;
+    out[1] = out[2] = out[3] = 0;
+    if (!cl_pk_native(C)) return 0;
+    const PkGeo g = cl_pk_geo(R, C, p.w);
+    if (cl_pk_wgs(g) >= ((int64_t)1 << 31) || g.rpw >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    out[1] = (int32_t)cl_pk_wgs(g);
+    out[2] = (int32_t)g.rpw;
+    out[3] = 1;
+    return 0;
+}
+
+// the pack launch.  uniform: the width every channel has when the host knows it (the one-call fronts), else -1; it selects the
+// register-to-memory form where every piece's run is whole dwords
+static int cl_pack(const void* x, int dtype, int64_t R, int64_t C, const ClPlan& p, const float* qp, const float* mm, const uint32_t* coloff,
+                   uint8_t* packed, int uniform, hipStream_t st) {
+    if (!cl_pk_native(C)) return CNNQ_ENOTSUP;
+    const PkGeo g = cl_pk_geo(R, C, p.w);
+    if (cl_pk_wgs(g) >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    const bool direct = uniform > 0 && (p.w * uniform) % 32 == 0;
+    uint32_t* out = reinterpret_cast<uint32_t*>(packed);
+    return cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
+        using P = decltype(pc);
+        if constexpr (P::W >= 4) {
+            if (direct) {
+                hipLaunchKernelGGL((k_cl_pack<typename P::T, P::W, true>), dim3((unsigned)cl_pk_wgs(g)), dim3(TPB), 0, st, xr, out, g, qp, mm, coloff);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((k_cl_pack<typename P::T, P::W, false>), dim3((unsigned)cl_pk_wgs(g)), dim3(TPB), 0, st, xr, out, g, qp, mm, coloff);
+    });
+}
+
+static int cl_pack_check(const void* x, int dtype, int64_t R, int64_t C, const float* qp, const uint32_t* coloff, const uint8_t* packed) {
+    if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
+    return (!x || !qp || !coloff || !packed || misaligned(packed, 4)) ? CNNQ_EINVAL : 0;
+}
+
+int cnnq_pc_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int64_t C, const float* qp, const float* mm, const uint32_t* coloff,
+                                 uint8_t* packed, void* stream) {
+    if (cl_pack_check(x, dtype, R, C, qp, coloff, packed)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, h_align(x, x));
+    if (const int rc = p.range(false)) return rc;
+    return cl_pack(x, dtype, R, C, p, qp, mm, coloff, packed, -1, hs(stream));
+}
+
+int cnnq_pc_dequantize_packed_nhwc(const uint8_t* packed, void* y, int dtype, int64_t R, int64_t C, const float* qp, const uint32_t* coloff,
+                                   void* stream) {
+    if (cl_pack_check(y, dtype, R, C, qp, coloff, packed)) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, h_align(y, y));
+    if (const int rc = p.range(false)) return rc;
+    const uint32_t* in = reinterpret_cast<const uint32_t*>(packed);
+    return cl_launch(dtype, p.w, nullptr, y, [&](auto pc, auto*, auto* yr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_cl_unpack<typename P::T, P::W>), p.qgrid(), dim3(TPB), 0, hs(stream), in, yr, p.q, qp, coloff, cl_pk_capdw(C));
+    });
+}
+
+// int_quantizer.py:409-451, 557-587 on [R][C], the codes kept: cl_minmax_front -> k_cl_packed_layout (uniform) -> k_cl_pack with the extrema
+int cnnq_pc_minmax_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int64_t C, int num_bits, int positive, float* ws, float* qp,
+                                        float* mm, uint32_t* coloff, uint8_t* packed, void* stream) {
+    if (cl_pack_check(x, dtype, R, C, qp, coloff, packed)) return CNNQ_EINVAL;
+    if (!ws || misaligned(ws, 4) || num_bits < 1 || num_bits > 8) return CNNQ_EINVAL;
+    if (!cl_pk_native(C)) return CNNQ_ENOTSUP;
+    const ClPlan p(R, C, dtype, h_align(x, x));
+    if (const int rc = p.range(false)) return rc;
+    float* ext;
+    int rc = cl_minmax_front(x, dtype, C, p, num_bits, positive, ws, qp, mm, &ext, stream);
+    if (!rc) rc = cnnq_pc_packed_layout_nhwc(nullptr, num_bits, C, coloff, stream);
+    if (!rc) rc = cl_pack(x, dtype, R, C, p, qp, ext, coloff, packed, num_bits, hs(stream));
+    return rc;
+}
+
+// int_quantizer.py:327-352 + 409-451, 557-587 on [R][C], the codes kept: cl_aciq_front -> k_cl_packed_layout (the allocated widths, or
+// cfg->num_bits) -> k_cl_pack with the table
+int cnnq_pc_aciq_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws, float* stats,
+                                      float* qp, float* diag, uint32_t* coloff, uint8_t* packed, void* stream) {
+    if (cl_aciq_check(x, packed, dtype, R, C, cfg, ws, stats, qp, diag)) return CNNQ_EINVAL;
+    if (!coloff || misaligned(packed, 4) || cfg->num_bits > 8) return CNNQ_EINVAL;
+    if (!cl_pk_native(C)) return CNNQ_ENOTSUP;
+    const ClPlan p(R, C, dtype, h_align(x, x));
+    if (const int rc = p.range(false)) return rc;
+    const bool ba = cfg_bit_alloc(cfg);
+    int rc = cl_aciq_front(x, dtype, R, C, p, cfg, ws, stats, qp, diag, stream);
+    if (!rc) rc = cnnq_pc_packed_layout_nhwc(ba ? diag + (size_t)CNNQ_DIAG_BITS * C : nullptr, ba ? 0 : cfg->num_bits, C, coloff, stream);
+    if (!rc) rc = cl_pack(x, dtype, R, C, p, qp, nullptr, coloff, packed, ba ? -1 : cfg->num_bits, hs(stream));
+    return rc;
 }
 
 }  // extern "C"

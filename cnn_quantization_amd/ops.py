@@ -1356,6 +1356,198 @@ def dequantize_packed(packed, shape, qp, bits, rowoff, out=None, form=0):
     return y
 
 
+# ------------------------------------------------------------------------------------- stored codes on channels_last storage
+# the packed format of a dense channels_last activation of fp32 / bf16 / fp16 - row r of [R = N*H*W][C] is
+# one little-endian bit stream, channel c at bits [coloff[c], coloff[c] + bits[c]), padded to whole dwords.  These functions take
+# the storage as it is or raise: no copy, no upcast (LAYOUT_COPIES never moves here).
+def _packed_x(x, what):
+    """x as the packed channels_last entry points take it: a dense channels_last 4-D fp32 / bf16 / fp16 tensor on the current device."""
+    if not isinstance(x, torch.Tensor):
+        raise L.CnnqError('%s: x must be a tensor' % what)
+    if x.dtype not in _ACT_DTYPES:
+        raise L.CnnqError('%s: x must be float32, bfloat16 or float16, got %s' % (what, x.dtype))
+    if x.dim() != 4 or _layout(x) != 'nhwc':             # shape and strides only
+        raise L.CnnqError('%s: x must be a dense channels_last 4-D activation (no copy is made here)' % what)
+    if not x.is_cuda:
+        raise L.CnnqError('%s: x must be a CUDA/HIP tensor (there is no CPU path)' % what)
+    if x.device.index != torch.cuda.current_device():
+        raise L.CnnqError('%s: x is on %s but the current device is cuda:%d' % (what, x.device, torch.cuda.current_device()))
+    return x.detach() if x.requires_grad else x
+
+
+def _packed_table(t, what, dtype, shape, device):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == dtype and t.is_contiguous()
+            and tuple(t.shape) == tuple(shape)):
+        raise L.CnnqError('%s must be a contiguous %s device tensor of shape %s' % (what, str(dtype).replace('torch.', ''), list(shape)))
+    return t
+
+
+def _packed_rowbytes(bits, C):
+    return (int(bits) * C + 31) // 32 * 4
+
+
+def _packed_buffer(out, nbytes, device, what):
+    """The code buffer and what the caller gets back: a new one, cut to exactly nbytes, or the caller's (returned whole) - uint8,
+    contiguous, 4-byte aligned, at least nbytes long."""
+    if out is None:
+        buf = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=device)      # never empty: the C side refuses a null pointer
+        return buf, buf[:nbytes]
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == device and out.dtype == torch.uint8 and out.is_contiguous()
+            and out.numel() >= max(nbytes, 1) and out.data_ptr() % 4 == 0):
+        raise L.CnnqError('%s: out must be a contiguous, 4-byte aligned uint8 device buffer of at least %d bytes' % (what, nbytes))
+    return out, out
+
+
+def _uniform_width(bits, what):
+    if isinstance(bits, bool) or not isinstance(bits, int):
+        return None
+    if not 0 <= bits <= 8:
+        raise L.CnnqError('%s: a uniform width must be in 0..8, got %d' % (what, bits))
+    return bits
+
+
+def packed_capacity_nhwc(shape):
+    """Worst-case bytes of the channels_last packed format for an activation of this shape (every channel at 8 bits):
+    cnnq_pc_packed_nhwc_capacity, R * 4 * ceil(8 * C / 32)."""
+    C = int(shape[1])
+    R = 1
+    for d in tuple(shape[:1]) + tuple(shape[2:]):
+        R *= int(d)
+    return R * ((8 * C + 31) // 32 * 4)
+
+
+def packed_layout_nhwc(bits, C, device=None):
+    """coloff int32 [C + 1] of the channels_last packed format (cnnq_pc_packed_layout_nhwc): the exclusive prefix sum of the
+    per-channel widths `bits` (a float32 device table of C entries, e.g. diag[DIAG_BITS]) or of one integer width 0..8 for every
+    channel.  A function of the widths only: computed once, it serves every quantize / dequantize call with them."""
+    lib = L.load()
+    C = int(C)
+    uni = _uniform_width(bits, 'packed_layout_nhwc')
+    if uni is None:
+        device = bits.device if isinstance(bits, torch.Tensor) else None
+        bits = _packed_table(bits, 'bits', torch.float32, (C,), device)
+    elif device is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    coloff = torch.empty(C + 1, dtype=torch.int32, device=device)
+    L.check(lib.cnnq_pc_packed_layout_nhwc(None if uni is not None else _ptr(bits), uni or 0, C, _ptr(coloff), _stream(coloff)),
+            'cnnq_pc_packed_layout_nhwc')
+    return coloff
+
+
+def quantize_packed_nhwc(x, qp, bits, mm=None, out=None, coloff=None):
+    """A dense channels_last x + parameter table qp [NQP, C] + widths -> (packed uint8, coloff int32 [C + 1])
+    (cnnq_pc_quantize_packed_nhwc, one launch on the storage as it is).  bits: an integer 0..8 for every channel - the buffer is
+    sized exactly on the host, R * 4 * ceil(bits * C / 32) bytes - or a float32 device table [C] (diag[DIAG_BITS]): a buffer of
+    packed_capacity_nhwc(x.shape) bytes comes back, of which R * 4 * ceil(coloff[C] / 32) are used, and nothing synchronises.
+    mm: the channels' exact extrema [2, C] (config 2's), or None; the bytes do not depend on it.  out: the caller's buffer, returned
+    whole.  coloff: packed_layout_nhwc(bits, C) when the caller already has it (one launch less)."""
+    lib = L.load()
+    x = _packed_x(x, 'quantize_packed_nhwc')
+    C = x.shape[1]
+    R = x.numel() // C
+    qp = _packed_table(qp, 'qp', torch.float32, (L.NQP, C), x.device)
+    if mm is not None:
+        mm = _packed_table(mm, 'mm', torch.float32, (2, C), x.device)
+    uni = _uniform_width(bits, 'quantize_packed_nhwc')
+    if coloff is None:
+        coloff = packed_layout_nhwc(bits, C, x.device)
+    else:
+        coloff = _packed_table(coloff, 'coloff', torch.int32, (C + 1,), x.device)
+    nbytes = R * _packed_rowbytes(uni, C) if uni is not None else packed_capacity_nhwc(x.shape)
+    buf, packed = _packed_buffer(out, nbytes, x.device, 'quantize_packed_nhwc')
+    L.check(lib.cnnq_pc_quantize_packed_nhwc(_ptr(x), _DTYPE_CODES[x.dtype], R, C, _ptr(qp), _ptr(mm), _ptr(coloff),
+                                             _ptr(buf), _stream(x)), 'cnnq_pc_quantize_packed_nhwc')
+    return packed, coloff
+
+
+def dequantize_packed_nhwc(packed, shape, dtype, qp, coloff, out=None):
+    """Inverse of quantize_packed_nhwc (cnnq_pc_dequantize_packed_nhwc): a dense channels_last tensor of `shape` and `dtype`
+    (float32 / bfloat16 / float16) holding (code - zp) * scale - pc_qdq's result on the channels_last x with the same qp, bit for bit
+    (a NaN element of a channel with finite parameters, stored as code 0, excepted)."""
+    lib = L.load()
+    if not isinstance(packed, torch.Tensor) or not packed.is_cuda:
+        raise L.CnnqError('dequantize_packed_nhwc: packed must be a CUDA/HIP tensor (there is no CPU path)')
+    if dtype not in _ACT_DTYPES:
+        raise L.CnnqError('dequantize_packed_nhwc: dtype must be float32, bfloat16 or float16, got %s' % (dtype,))
+    shape = tuple(int(d) for d in shape)
+    if len(shape) != 4:
+        raise L.CnnqError('dequantize_packed_nhwc: shape must be that of a 4-D activation')
+    if not (packed.dtype == torch.uint8 and packed.is_contiguous() and packed.data_ptr() % 4 == 0):
+        raise L.CnnqError('dequantize_packed_nhwc: packed must be a contiguous, 4-byte aligned uint8 buffer')
+    if packed.device.index != torch.cuda.current_device():
+        raise L.CnnqError('dequantize_packed_nhwc: packed is on %s but the current device is cuda:%d' % (packed.device, torch.cuda.current_device()))
+    C = shape[1]
+    qp = _packed_table(qp, 'qp', torch.float32, (L.NQP, C), packed.device)
+    coloff = _packed_table(coloff, 'coloff', torch.int32, (C + 1,), packed.device)
+    if out is None:
+        y = torch.empty(shape, dtype=dtype, device=packed.device, memory_format=torch.channels_last)
+    else:
+        y = out
+        if not (isinstance(y, torch.Tensor) and y.is_cuda and y.device == packed.device and y.dtype == dtype and tuple(y.shape) == shape
+                and y.is_contiguous(memory_format=torch.channels_last)):
+            raise L.CnnqError('dequantize_packed_nhwc: out must be a dense channels_last %s tensor of the given shape' % str(dtype).replace('torch.', ''))
+    R = y.numel() // C
+    # an empty buffer (every width 0) has no address; nothing is read through the pointer then
+    L.check(lib.cnnq_pc_dequantize_packed_nhwc(ctypes.c_void_p(packed.data_ptr() or y.data_ptr()), _ptr(y), _DTYPE_CODES[dtype], R, C,
+                                               _ptr(qp), _ptr(coloff), _stream(y)), 'cnnq_pc_dequantize_packed_nhwc')
+    return y
+
+
+def minmax_quantize_packed_nhwc(x, num_bits=4, positive=False, out=None):
+    """Config 2 straight into the stored format (cnnq_pc_minmax_quantize_packed_nhwc): per-channel min / max of a dense
+    channels_last x, the parameter table, the uniform num_bits (1..8) layout and the packed codes, one host call ->
+    (packed uint8 [R * 4 * ceil(num_bits * C / 32)], dict(qp, mm, coloff))."""
+    lib = L.load()
+    x = _packed_x(x, 'minmax_quantize_packed_nhwc')
+    if not 1 <= int(num_bits) <= 8:
+        raise L.CnnqError('minmax_quantize_packed_nhwc: num_bits must be in 1..8, got %r' % (num_bits,))
+    C = x.shape[1]
+    R = x.numel() // C
+    dt = _DTYPE_CODES[x.dtype]
+    st = _raw_stream(x.device.index)
+    ws = _scratch(x, 'nhwc', _ws_bytes('nhwc', R, C, 1, dt), st).data_ptr()
+    qp = torch.empty(L.NQP, C, dtype=torch.float32, device=x.device)
+    mm = torch.empty(2, C, dtype=torch.float32, device=x.device)
+    coloff = torch.empty(C + 1, dtype=torch.int32, device=x.device)
+    buf, packed = _packed_buffer(out, R * _packed_rowbytes(num_bits, C), x.device, 'minmax_quantize_packed_nhwc')
+    rc = lib.cnnq_pc_minmax_quantize_packed_nhwc(x.data_ptr(), dt, R, C, int(num_bits), 1 if positive else 0, ws, qp.data_ptr(),
+                                                 mm.data_ptr(), coloff.data_ptr(), buf.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_minmax_quantize_packed_nhwc')
+    return packed, dict(qp=qp, mm=mm, coloff=coloff)
+
+
+def aciq_quantize_packed_nhwc(x, num_bits, positive=False, clip='laplace', bit_alloc=False, prior_is_b=False, target=None,
+                              round_mode=True, out=None):
+    """Config 3 straight into the stored format (cnnq_pc_aciq_quantize_packed_nhwc): aciq_qdq_nhwc's statistics and parameters of a
+    dense channels_last x, then the packed codes instead of y, one host call -> (packed uint8, dict(stats, qp, diag, coloff)).  With
+    bit allocation the widths are diag[DIAG_BITS] - a buffer of packed_capacity_nhwc(x.shape) bytes comes back, of which
+    R * 4 * ceil(coloff[C] / 32) are used, and nothing synchronises; without it the width is num_bits (<= 8) and the buffer exact."""
+    if clip not in ('laplace', 'gaus'):
+        raise L.CnnqError("aciq_quantize_packed_nhwc: clip must be 'laplace' or 'gaus', got %r" % (clip,))
+    lib = L.load()
+    x = _packed_x(x, 'aciq_quantize_packed_nhwc')
+    if not 1 <= int(num_bits) <= 8:
+        raise L.CnnqError('aciq_quantize_packed_nhwc: num_bits must be in 1..8, got %r' % (num_bits,))
+    use_ba = bool(bit_alloc) and num_bits <= 4
+    C = x.shape[1]
+    R = x.numel() // C
+    dt = _DTYPE_CODES[x.dtype]
+    st = _raw_stream(x.device.index)
+    cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
+    ws = _scratch(x, 'aciq_nhwc', _ws_bytes('aciq_nhwc', R, C, 1, dt), st).data_ptr()
+    tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, C, dtype=torch.float32, device=x.device)
+    coloff = torch.empty(C + 1, dtype=torch.int32, device=x.device)
+    nbytes = packed_capacity_nhwc(x.shape) if use_ba else R * _packed_rowbytes(num_bits, C)
+    buf, packed = _packed_buffer(out, nbytes, x.device, 'aciq_quantize_packed_nhwc')
+    tp = tabs.data_ptr()
+    rc = lib.cnnq_pc_aciq_quantize_packed_nhwc(x.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                               tp + (L.NSTAT + L.NQP) * C * 4, coloff.data_ptr(), buf.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_aciq_quantize_packed_nhwc')
+    return packed, dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:], coloff=coloff)
+
+
 def entropy_from_hist(hist):
     """Shannon entropy (bits) of an int64 histogram tensor -> 0-dim float32 tensor on the device."""
     lib = L.load()

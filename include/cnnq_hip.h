@@ -800,6 +800,58 @@ size_t cnnq_pc_qdq_bcorr_nhwc_workspace(int64_t R, int64_t C, int dtype);
 int cnnq_pc_qdq_bcorr_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t C, const float* qp, int relu_first, void* ws,
                            double* sums, float* bias, void* stream);
 
+/* Integer codes as the STORED format of a dense channels_last activation: per-channel widths of 0..8
+ * bits on [R = N*H*W][C], C innermost, fp32 / bf16 / fp16 elements, on the storage as it is (no upcast, no transpose).
+ *
+ * Format.  Row r stores the codes of channels 0..C-1 as one little-endian bit stream: channel c occupies bits
+ * [coloff[c], coloff[c] + bits[c]) of the row.  coloff holds C + 1 uint32 entries (device memory), the exclusive prefix sum of
+ * the widths; coloff[C] is the number of bits per row.  A row is padded with zero bits to whole dwords, rowbytes =
+ * 4 * ceil(coloff[C] / 32), and row r starts at byte r * rowbytes; the buffer holds R * rowbytes bytes and no byte beyond them
+ * is ever written.  Every width is an integer in 0..8; a 0-bit channel stores nothing and decodes to (0 - zp) * scale.  Uniform
+ * 4 bits (coloff[c] = 4 c) and uniform 8 bits are this format with a constant width table: there is no second format.
+ * Examples: bits = {3, 0, 5} with the codes {5, 0, 17} is the row 8D 00 00 00; bits = {8, 8, 8, 7, 3} gives coloff =
+ * {0, 8, 16, 24, 31, 34} - the last channel straddles dwords 0 and 1 - and rowbytes = 8.
+ *
+ * The stored code is the code of cnnq_pc_qdq_nhwc for that element with the same qp[CNNQ_NQP][C] (with the channels' exact
+ * extrema mm[2][C] the divide-free quotient's inside its domain: the same bits; mm may be NULL), masked to the channel's width:
+ * a qp whose qmax[c] exceeds 2^bits[c] - 1 is the caller's error and may truncate that channel's codes, never touch a
+ * neighbour's bits.  Decode is (code - zp) * scale rounded once into the element type, so the round trip reproduces
+ * cnnq_pc_qdq_nhwc bit for bit - with one exception: a NaN code cannot be stored and is stored as 0, so a NaN element of a
+ * channel with finite parameters comes back as (0 - zp) * scale; a channel whose zp is NaN still decodes to NaN.
+ *
+ * cnnq_pc_packed_nhwc_capacity (host only): R * 4 * ceil(8 * C / 32), the bytes of the buffer at 8 bits per code - enough for
+ *   every width table; 0 on R < 1 or C < 1.
+ * cnnq_pc_packed_layout_nhwc: coloff from the device table bits[C] (floats, e.g. row CNNQ_DIAG_BITS of diag), or - bits == NULL -
+ *   from the width uniform_bits for every channel.  Every width is clamped into 0..8, NaN to 0.
+ * cnnq_pc_route_packed_nhwc (host only, nothing enqueued): out = {elements per load W (cnnq_pc_route_nhwc's out[0]), workgroups
+ *   of the pack launch, rows per pack workgroup, 1 - native}.  out[3] == 0: the library has no pack kernel for this class of
+ *   layer (a row image beyond 8 KB, C > 8192: cnnq_pc_quantize_packed_nhwc returns CNNQ_ENOTSUP) and out[1], out[2] are 0.
+ * cnnq_pc_quantize_packed_nhwc: x -> packed, one launch.  Every dword of the R * rowbytes bytes is written exactly once by a
+ *   plain store, padding bits included: no atomics on global memory, the same bytes run after run.
+ * cnnq_pc_dequantize_packed_nhwc: packed -> y, one launch (any C).
+ * cnnq_pc_minmax_quantize_packed_nhwc: config 2 in one call - the three statistics launches of cnnq_pc_minmax_qdq_nhwc, the
+ *   layout for the uniform width num_bits (1..8), the pack launch with the extrema.  ws: cnnq_pc_nhwc_workspace bytes; qp and
+ *   mm (may be NULL) as cnnq_pc_minmax_qdq_nhwc; coloff[C + 1] is an OUTPUT.
+ * cnnq_pc_aciq_quantize_packed_nhwc: config 3 in one call - cnnq_pc_aciq_qdq_nhwc's statistics and parameter launches, the
+ *   layout from diag[CNNQ_DIAG_BITS] under bit allocation, else from cfg->num_bits (which must then be <= 8), the pack launch.
+ *   ws: cnnq_pc_aciq_nhwc_workspace bytes, 8-byte aligned; cfg, stats, qp, diag as cnnq_pc_aciq_qdq_nhwc; coloff is an OUTPUT.
+ * The piece width comes from x's (the decoder: y's) alignment alone, so a Q/DQ entry point whose plan has the same W writes the
+ * same tables bit for bit.  All of them return CNNQ_EINVAL before anything touches the device for a NULL required pointer,
+ * R < 1, C < 1, a bad dtype, a `packed` that is not 4-byte aligned, a misaligned ws, num_bits outside 1..8; CNNQ_ERANGE as
+ * cnnq_pc_qdq_nhwc; CNNQ_ENOTSUP (the encoders, C > 8192) before any launch.  Re-entrant, allocate nothing, no host
+ * synchronisation. */
+size_t cnnq_pc_packed_nhwc_capacity(int64_t R, int64_t C);
+int cnnq_pc_packed_layout_nhwc(const float* bits, int uniform_bits, int64_t C, uint32_t* coloff, void* stream);
+int cnnq_pc_route_packed_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]);
+int cnnq_pc_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int64_t C, const float* qp, const float* mm,
+                                 const uint32_t* coloff, uint8_t* packed, void* stream);
+int cnnq_pc_dequantize_packed_nhwc(const uint8_t* packed, void* y, int dtype, int64_t R, int64_t C, const float* qp,
+                                   const uint32_t* coloff, void* stream);
+int cnnq_pc_minmax_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int64_t C, int num_bits, int positive, float* ws,
+                                        float* qp, float* mm, uint32_t* coloff, uint8_t* packed, void* stream);
+int cnnq_pc_aciq_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
+                                      float* stats, float* qp, float* diag, uint32_t* coloff, uint8_t* packed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
