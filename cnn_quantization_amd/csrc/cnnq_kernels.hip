@@ -178,6 +178,22 @@ inline int cl_launch(int dtype, int w, const void* x, F&& f) {
     return cl_launch(dtype, w, x, nullptr, [&](auto pc, auto* xr, auto*) { f(pc, xr); });
 }
 
+inline bool dtype_ok(int dtype) { return dtype >= 0 && dtype < CNNQ_NDTYPE; }
+
+inline int cl_check(int64_t R, int64_t C, int dtype) {
+    return (!dtype_ok(dtype) || R < 1 || C < 1 || C > CL_C_MAX) ? CNNQ_EINVAL : 0;
+}
+
+// What every channels_last route function opens with: its argument checks (ok: the function's own, refused with them), the plan,
+// the plan's range; then report(plan) fills out
+template <class F>
+inline int cl_route(int64_t R, int64_t C, int dtype, int align_bytes, const int32_t* out, bool rows32, bool ok, F&& report) {
+    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes) || !ok) return CNNQ_EINVAL;
+    const ClPlan p(R, C, dtype, align_bytes);
+    if (const int rc = p.range(rows32)) return rc;
+    return report(p);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1517,7 +1533,6 @@ int cnnq_xrank_close(void* window) { return window ? (int)hipIpcCloseMemHandle(w
 int cnnq_xrank_free(void* window) { return window ? (int)hipFree(window) : CNNQ_EINVAL; }
 
 // ---- activations of another element type (cnnq_half.hip.h): bf16 / fp16 x and y, fp32 tables ---------------------------------
-static bool dtype_ok(int dtype) { return dtype >= 0 && dtype < CNNQ_NDTYPE; }
 
 // the common alignment of x and y in bytes (16 at most): what h_piece needs to know of the pointers
 static int h_align(const void* x, const void* y) {
@@ -1672,10 +1687,6 @@ static int pt_qdq_launch(const void* x, void* y, int dtype, int64_t n, const flo
 }
 
 // ---- dense channels_last activations (cnnq_nhwc.hip.h): x and y [R = N*H*W][C], C innermost; fp32 tables ----------------------
-static int cl_check(int64_t R, int64_t C, int dtype) {
-    return (!dtype_ok(dtype) || R < 1 || C < 1 || C > CL_C_MAX) ? CNNQ_EINVAL : 0;
-}
-
 // the widest slab count of the statistics launches over the piece widths C allows (the alignment is not known yet)
 static int64_t cl_slabs_max(int64_t R, int64_t C, int dtype) {
     int64_t S = 1;
@@ -1693,14 +1704,13 @@ size_t cnnq_pc_nhwc_workspace(int64_t R, int64_t C, int dtype) {
 }
 
 int cnnq_pc_route_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
-    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
-    const ClPlan p(R, C, dtype, align_bytes);
-    if (const int rc = p.range(false)) return rc;
-    out[0] = p.w;
-    out[1] = p.m.S;
-    out[2] = p.q.S * p.q.nb;
-    out[3] = (int32_t)(p.m.rpw / p.m.RS);
-    return 0;
+    return cl_route(R, C, dtype, align_bytes, out, /*rows32=*/false, /*ok=*/true, [&](const ClPlan& p) {
+        out[0] = p.w;
+        out[1] = p.m.S;
+        out[2] = p.q.S * p.q.nb;
+        out[3] = (int32_t)(p.m.rpw / p.m.RS);
+        return 0;
+    });
 }
 
 static int cl_qdq(const void* x, void* y, int dtype, const ClPlan& p, const float* qp, const float* mm, hipStream_t st) {
@@ -1757,44 +1767,55 @@ size_t cnnq_pc_aciq_nhwc_workspace(int64_t R, int64_t C, int dtype) {
 // Which launches cnnq_pc_aciq_qdq_nhwc makes for this geometry (host only).  out[5] is 1 throughout: no class of layer is sent
 // back to the copy route; one that measures slower native than through the copy (tools/bench_channels_last_aciq.py) goes back here.
 int cnnq_pc_route_aciq_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[6]) {
-    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
-    const ClPlan p(R, C, dtype, align_bytes);
-    if (const int rc = p.range(true)) return rc;
-    out[0] = p.w;
-    out[1] = p.m.S;
-    out[2] = (int32_t)p.m.rpw;
-    out[3] = (int32_t)(p.m.rpw / p.m.RS);
-    out[4] = p.q.S * p.q.nb;
-    out[5] = 1;
-    return 0;
+    return cl_route(R, C, dtype, align_bytes, out, /*rows32=*/true, /*ok=*/true, [&](const ClPlan& p) {
+        out[0] = p.w;
+        out[1] = p.m.S;
+        out[2] = (int32_t)p.m.rpw;
+        out[3] = (int32_t)(p.m.rpw / p.m.RS);
+        out[4] = p.q.S * p.q.nb;
+        out[5] = 1;
+        return 0;
+    });
 }
 
-// The statistics table of a channels_last tensor, the front of configs 3 and 5: pass A (k_cl_moments) -> k_combine (-> pass B
-// (k_cl_absdev) on the merged table -> k_combine_dev, need_b).  The merge writes every row of stats (zero for KURT, STD_POS; B
-// without pass B); ws: the AciqWs records for the plan's slab count.  The element-wise pass behind it walks the tensor
-// descending, so the statistics launch in front of it ascends: with pass B, pass A descends.
-static int cl_table(const void* x, int dtype, int64_t R, int64_t C, const ClPlan& p, bool need_b, void* ws, float* stats, void* stream) {
+// The statistics table of a channels_last tensor - the front of configs 3 and 5 and all of `-sm collect` (smpc.py:45-79): pass A
+// (k_cl_moments, with the rectified sums k_cl_moments_relu) -> k_combine(has_relu) (-> pass B (k_cl_absdev, with the fourth moment
+// k_cl_absdev_kurt) on the merged table -> k_combine_dev(want_kurt); need_b or need_kurt), two or four launches.  The merge writes
+// every row of stats (zero for the rows nobody asked for; B comes with pass B); ws: the AciqWs records for the plan's slab count;
+// mom: where the caller wants the merged moment record, or NULL (it stays in ws).  The element-wise pass behind it walks the
+// tensor descending, so the statistics launch in front of it ascends: with pass B, pass A descends.
+static int cl_table(const void* x, int dtype, int64_t R, int64_t C, const ClPlan& p, bool need_b, bool need_kurt, bool need_relu, void* ws,
+                    double* mom, float* stats, void* stream) {
     const ClGeo& m = p.m;
     const AciqWs a(ws, m.S, C);
+    double* rec = mom ? mom : a.mom;
     hipStream_t st = hs(stream);
     const bool ntl = nt_loads(R * C * cl_esize(dtype));
-    const int rev = need_b ? 1 : 0;
-    auto pass = [&](bool b) {
-        return cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
-            with_bool(ntl, [&](auto nt) {
-                using P = decltype(pc);
-                constexpr bool NT = decltype(nt)::value;
-                if (b) hipLaunchKernelGGL((k_cl_absdev<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, a.part2);
-                else hipLaunchKernelGGL((k_cl_moments<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, a.part);
-            });
+    const bool pass_b = need_b || need_kurt;
+    const int rev = pass_b ? 1 : 0;
+    int rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
+        with_bool(ntl, need_relu, [&](auto nt, auto relu) {
+            using P = decltype(pc);
+            constexpr bool NT = decltype(nt)::value;
+            if constexpr (decltype(relu)::value)
+                hipLaunchKernelGGL((k_cl_moments_relu<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, a.part);
+            else
+                hipLaunchKernelGGL((k_cl_moments<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, a.part);
         });
-    };
-    int rc = pass(false);
-    if (!rc) rc = cnnq_pc_combine(a.part, m.S, C, 0, a.mom, stats, stream);
-    if (!rc && need_b) {
-        rc = pass(true);
-        if (!rc) rc = cnnq_pc_combine_dev(a.part2, m.S, C, a.mom, 0, nullptr, stats, stream);
-    }
+    });
+    if (!rc) rc = cnnq_pc_combine(a.part, m.S, C, need_relu ? 1 : 0, rec, stats, stream);
+    if (rc || !pass_b) return rc;
+    rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
+        with_bool(ntl, need_kurt, [&](auto nt, auto kurt) {
+            using P = decltype(pc);
+            constexpr bool NT = decltype(nt)::value;
+            if constexpr (decltype(kurt)::value)
+                hipLaunchKernelGGL((k_cl_absdev_kurt<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, a.part2);
+            else
+                hipLaunchKernelGGL((k_cl_absdev<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, a.part2);
+        });
+    });
+    if (!rc) rc = cnnq_pc_combine_dev(a.part2, m.S, C, rec, need_kurt ? 1 : 0, nullptr, stats, stream);
     return rc;
 }
 
@@ -1812,7 +1833,7 @@ static int cl_aciq_check(const void* x, void* y, int dtype, int64_t R, int64_t C
 static int cl_aciq_front(const void* x, int dtype, int64_t R, int64_t C, const ClPlan& p, const cnnq_params_cfg* cfg, void* ws, float* stats,
                          float* qp, float* diag, void* stream) {
     const bool need_b = cfg->clip == 1 || (cfg_bit_alloc(cfg) && cfg->prior_is_b);
-    int rc = cl_table(x, dtype, R, C, p, need_b, ws, stats, stream);
+    int rc = cl_table(x, dtype, R, C, p, need_b, false, false, ws, nullptr, stats, stream);
     if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
     return rc;
 }
@@ -1837,57 +1858,23 @@ size_t cnnq_pc_stats_nhwc_workspace(int64_t R, int64_t C, int dtype) { return cn
 // the native launches}.  out[3] is 1 throughout: no class of layer is sent back to the copy route; one that measures slower native
 // than through the copy (tools/bench_channels_last_collect.py) goes back here, with the figures next to the rule.
 int cnnq_pc_route_stats_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
-    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
-    const ClPlan p(R, C, dtype, align_bytes);
-    if (const int rc = p.range(true)) return rc;
-    out[0] = p.w;
-    out[1] = p.m.S;
-    out[2] = (int32_t)p.m.rpw;
-    out[3] = 1;
-    return 0;
+    return cl_route(R, C, dtype, align_bytes, out, /*rows32=*/true, /*ok=*/true, [&](const ClPlan& p) {
+        out[0] = p.w;
+        out[1] = p.m.S;
+        out[2] = (int32_t)p.m.rpw;
+        out[3] = 1;
+        return 0;
+    });
 }
 
-// smpc.py:45-79 on [R][C]: pass A (k_cl_moments, with the rectified sums k_cl_moments_relu) -> k_combine(has_relu) (-> pass B
-// (k_cl_absdev, with the fourth moment k_cl_absdev_kurt) on the merged table -> k_combine_dev(want_kurt)), two or four launches.
-// Without need_kurt and need_relu these are cl_table's launches with cl_table's arguments.  As there, pass A descends when an
-// ascending pass B follows it.
+// smpc.py:45-79 on [R][C]: cl_table with every flag the caller raises
 int cnnq_pc_stats_nhwc(const void* x, int dtype, int64_t R, int64_t C, int need_b, int need_kurt, int need_relu, void* ws, double* mom,
                        float* stats, void* stream) {
     if (cl_check(R, C, dtype)) return CNNQ_EINVAL;
     if (!x || !ws || !stats || misaligned(ws, 8) || misaligned(mom, 8)) return CNNQ_EINVAL;
     const ClPlan p(R, C, dtype, h_align(x, x));
     if (const int rc = p.range(true)) return rc;
-    const ClGeo& m = p.m;
-    const AciqWs a(ws, m.S, C);
-    double* rec = mom ? mom : a.mom;
-    hipStream_t st = hs(stream);
-    const bool ntl = nt_loads(R * C * cl_esize(dtype));
-    const bool pass_b = need_b || need_kurt;
-    const int rev = pass_b ? 1 : 0;
-    int rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
-        with_bool(ntl, need_relu != 0, [&](auto nt, auto relu) {
-            using P = decltype(pc);
-            constexpr bool NT = decltype(nt)::value;
-            if constexpr (decltype(relu)::value)
-                hipLaunchKernelGGL((k_cl_moments_relu<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, a.part);
-            else
-                hipLaunchKernelGGL((k_cl_moments<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, rev, a.part);
-        });
-    });
-    if (!rc) rc = cnnq_pc_combine(a.part, m.S, C, need_relu ? 1 : 0, rec, stats, stream);
-    if (rc || !pass_b) return rc;
-    rc = cl_launch(dtype, p.w, x, [&](auto pc, auto* xr) {
-        with_bool(ntl, need_kurt != 0, [&](auto nt, auto kurt) {
-            using P = decltype(pc);
-            constexpr bool NT = decltype(nt)::value;
-            if constexpr (decltype(kurt)::value)
-                hipLaunchKernelGGL((k_cl_absdev_kurt<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, a.part2);
-            else
-                hipLaunchKernelGGL((k_cl_absdev<typename P::T, P::W, NT>), p.mgrid(), dim3(TPB), 0, st, xr, m, stats, a.part2);
-        });
-    });
-    if (!rc) rc = cnnq_pc_combine_dev(a.part2, m.S, C, rec, need_kurt ? 1 : 0, nullptr, stats, stream);
-    return rc;
+    return cl_table(x, dtype, R, C, p, need_b != 0, need_kurt != 0, need_relu != 0, ws, mom, stats, stream);
 }
 
 // ---- config 5 on dense channels_last activations (cnnq_nhwc_midtread.hip.h) ----------------------------------------------------
@@ -1935,7 +1922,7 @@ int cnnq_pc_midtread_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t 
     if (const int rc = p.range(false)) return rc;
     hipStream_t st = hs(stream);
     if (hist && hipMemsetAsync(hist, 0, (size_t)CNNQ_MT_HIST_WORDS(C) * sizeof(uint64_t), st) != hipSuccess) return launch_status();
-    int rc = cl_table(x, dtype, R, C, p, /*need_b=*/true, ws, stats, stream);
+    int rc = cl_table(x, dtype, R, C, p, /*need_b=*/true, false, false, ws, nullptr, stats, stream);
     if (!rc) rc = cnnq_pc_midtread_params(stats, C, target, 1, sym, tables, ntab, mt, stream);
     if (!rc) rc = cl_mt_qdq(x, y, dtype, p, R, C, mt, hist, st);
     return rc;
@@ -1950,15 +1937,14 @@ static size_t cl_hist_lds(int nbins) { return (size_t)nbins * HREP * sizeof(unsi
 // route; one that measures slower native than through the copy (tools/bench_channels_last_entropy.py) goes back here, with the
 // figure next to the rule.
 int cnnq_pc_route_qdq_hist_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int nbins, int32_t out[4]) {
-    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes) || !hist_bins_ok(nbins)) return CNNQ_EINVAL;
-    const ClPlan p(R, C, dtype, align_bytes);
-    if (const int rc = p.range(false)) return rc;
-    const ClGeo g = cl_geo_hist(R, C, p.w);
-    out[0] = p.w;
-    out[1] = g.S * g.nb;
-    out[2] = (int32_t)cl_hist_lds(nbins);
-    out[3] = 1;
-    return 0;
+    return cl_route(R, C, dtype, align_bytes, out, /*rows32=*/false, hist_bins_ok(nbins), [&](const ClPlan& p) {
+        const ClGeo g = cl_geo_hist(R, C, p.w);
+        out[0] = p.w;
+        out[1] = g.S * g.nb;
+        out[2] = (int32_t)cl_hist_lds(nbins);
+        out[3] = 1;
+        return 0;
+    });
 }
 
 static int cl_qdq_hist(const void* x, void* y, int dtype, const ClPlan& p, int64_t R, int64_t C, const float* qp, int nbins, uint64_t* hist_rep,
@@ -2054,18 +2040,17 @@ int cnnq_pc_packed_layout_nhwc(const float* bits, int uniform_bits, int64_t C, u
 // that measures slower native than through the copy beyond the run's spread (tools/bench_channels_last_packed.py,
 // profiles/channels_last_packed.md) goes back here.
 int cnnq_pc_route_packed_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
-    if (cl_check(R, C, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
-    const ClPlan p(R, C, dtype, align_bytes);
-    if (const int rc = p.range(false)) return rc;
-    out[0] = p.w;
-    out[1] = out[2] = out[3] = 0;
-    if (!cl_pk_native(C)) return 0;
-    const PkGeo g = cl_pk_geo(R, C, p.w);
-    if (cl_pk_wgs(g) >= ((int64_t)1 << 31) || g.rpw >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
-    out[1] = (int32_t)cl_pk_wgs(g);
-    out[2] = (int32_t)g.rpw;
-    out[3] = 1;
-    return 0;
+    return cl_route(R, C, dtype, align_bytes, out, /*rows32=*/false, /*ok=*/true, [&](const ClPlan& p) {
+        out[0] = p.w;
+        out[1] = out[2] = out[3] = 0;
+        if (!cl_pk_native(C)) return 0;
+        const PkGeo g = cl_pk_geo(R, C, p.w);
+        if (cl_pk_wgs(g) >= ((int64_t)1 << 31) || g.rpw >= ((int64_t)1 << 31)) return (int)CNNQ_ERANGE;
+        out[1] = (int32_t)cl_pk_wgs(g);
+        out[2] = (int32_t)g.rpw;
+        out[3] = 1;
+        return 0;
+    });
 }
 
 // the pack launch.  uniform: the width every channel has when the host knows it (the one-call fronts), else -1; it selects the

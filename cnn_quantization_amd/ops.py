@@ -325,20 +325,86 @@ def pc_stats(x, N, C, HW, need_b=False, need_kurt=False, need_relu=False, group=
     return stats, mom
 
 
+# ------------------------------------------------------------------------------------- the channels_last front
+# what the *_nhwc entry points share on the host - who runs native (_nhwc_native) and how a tensor is
+# admitted, with the geometry its C calls take (_admit_nhwc).  The hot calls keep their pointer arithmetic inline: a helper
+# per call costs more host time than it saves lines (profiles/host_overhead_nhwc.md).
+_NHWC_ROUTES = {    # kind: (route function, its arguments behind align_bytes, words of out, the word that says "native")
+    'stats': ('cnnq_pc_route_stats_nhwc', (), 4, 3),
+    'hist': ('cnnq_pc_route_qdq_hist_nhwc', (256,), 4, 3),
+    'midtread': ('cnnq_pc_route_midtread_nhwc', (0,), 6, 5)}
+_NHWC_NATIVE = {}
+
+
+def _nhwc_native(kind, R, C, dtype):
+    """Whether this class of layer runs on the channels_last kernels of `kind`: the "native" word of its route function's report
+    (0: a class that measured slower native than copied is sent back to the copy route there; a function of R, C and the dtype
+    alone), asked once per (kind, R, C, dtype) with alignment 16.  'stats' is kept under its own name: _stats_nhwc_native."""
+    if kind == 'stats':
+        return _stats_nhwc_native(R, C, dtype)
+    key = (kind, R, C, dtype)
+    v = _NHWC_NATIVE.get(key)
+    if v is None:
+        v = _NHWC_NATIVE[key] = _ask_route(kind, R, C, dtype)
+    return v
+
+
+def _ask_route(kind, R, C, dtype):
+    fn, extra, words, word = _NHWC_ROUTES[kind]
+    out = (ctypes.c_int32 * words)()
+    L.check(getattr(L.load(), fn)(R, C, _DTYPE_CODES.get(dtype, -1), 16, *extra, out), fn)
+    return bool(out[word])
+
+
 _STATS_NHWC_NATIVE = {}
 
 
 def _stats_nhwc_native(R, C, dtype):
-    """Whether this class of layer collects its statistics on the channels_last kernels: word 3 of cnnq_pc_route_stats_nhwc's
-    report (0: a class that measured slower native than copied is sent back to the copy route there; a function of R, C and the
-    dtype alone), asked once per (R, C, dtype)."""
+    """The 'stats' answer under the name, and with the cache, that the statistics manager (collects_native_nhwc) and the tests
+    of the collect family use: they patch the function and empty the cache by name."""
     key = (R, C, dtype)
     v = _STATS_NHWC_NATIVE.get(key)
     if v is None:
-        out = (ctypes.c_int32 * 4)()
-        L.check(L.load().cnnq_pc_route_stats_nhwc(R, C, _DTYPE_CODES.get(dtype, -1), 16, out), 'cnnq_pc_route_stats_nhwc')
-        v = _STATS_NHWC_NATIVE[key] = bool(out[3])
+        v = _STATS_NHWC_NATIVE[key] = _ask_route('stats', R, C, dtype)
     return v
+
+
+def _admit_nhwc(x, what, route=None, half_reason=None, dev_first=False):
+    """(x, geo) - x as a channels_last entry point takes it, and geo = (C, R = N*H*W, dtype code, raw stream), what its C call
+    takes, when x runs native: a dense channels_last 4-D CUDA tensor of fp32 / bf16 / fp16 with CNNQ_NHWC on and - route - a class
+    of layer the route function keeps.  Otherwise geo is None and x the contiguous copy _dev makes and counts, for the caller's
+    fallback.  Two orders, chosen by the caller:
+      dev_first=False: the 4-D check, the decision, then - half_reason: the fallback is float32 only - the error of a half tensor
+        before anything is copied or counted, then _dev;
+      dev_first=True: _dev's checks and its copy, then the 4-D check; no route, no half error (the caller raises its own)."""
+    if dev_first:
+        x = _dev(x, 'x', _ACT_DTYPES, keep_nhwc=True)
+        if x.dim() != 4:
+            _not_4d(x, what)
+        native = not x.is_contiguous()
+    else:
+        tensor = isinstance(x, torch.Tensor)
+        if tensor and x.dim() != 4:
+            _not_4d(x, what)
+        native = (tensor and x.is_cuda and _NHWC and _layout(x) == 'nhwc' and x.dtype in _ACT_DTYPES
+                  and (route is None or _nhwc_native(route, x.numel() // x.shape[1], x.shape[1], x.dtype)))
+        if not native and half_reason is not None and tensor and x.dtype in _HALF_DTYPES:
+            _half_only(what, half_reason)
+        x = _dev(x, 'x', _ACT_DTYPES, keep_nhwc=native)
+    if not native:
+        return x, None
+    C = x.shape[1]
+    return x, (C, x.numel() // C, _DTYPE_CODES[x.dtype], _raw_stream(x.device.index))
+
+
+def _not_4d(x, what):
+    raise L.CnnqError('%s: x must be a 4-D activation, got %d dimensions' % (what, x.dim()))
+
+
+def _is_table(t, dtype, shape, device):
+    """A contiguous `dtype` table of `shape` on `device`: what the C side reads through a bare pointer."""
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == dtype and t.is_contiguous()
+            and tuple(t.shape) == tuple(shape))
 
 
 def pc_stats_nhwc(x, need_b=False, need_kurt=False, need_relu=False):
@@ -349,21 +415,11 @@ def pc_stats_nhwc(x, need_b=False, need_kurt=False, need_relu=False):
     need_kurt, as in pc_stats).  One GPU: the statistics are this tensor's.  A tensor that is not dense channels_last (or
     CNNQ_NHWC=0, or a class of layer the route function sends back: copied, counted) takes pc_stats, which is float32 only - a
     half tensor raises before anything is copied."""
-    if isinstance(x, torch.Tensor) and x.dim() != 4:
-        raise L.CnnqError('pc_stats_nhwc: x must be a 4-D activation, got %d dimensions' % x.dim())
-    native = (isinstance(x, torch.Tensor) and x.is_cuda and _NHWC and _layout(x) == 'nhwc' and x.dtype in _ACT_DTYPES
-              and _stats_nhwc_native(x.numel() // x.shape[1], x.shape[1], x.dtype))
-    if not native and isinstance(x, torch.Tensor) and x.dtype in _HALF_DTYPES:
-        # before anything is copied or counted
-        _half_only('pc_stats_nhwc', 'the statistics of a tensor that does not take the channels_last kernels')
-    x = _dev(x, 'x', _ACT_DTYPES, keep_nhwc=native)
-    if not native:
+    x, geo = _admit_nhwc(x, 'pc_stats_nhwc', 'stats', 'the statistics of a tensor that does not take the channels_last kernels')
+    if geo is None:
         N, C, HW = geometry(x)
         return pc_stats(x, N, C, HW, need_b, need_kurt, need_relu, group=False)
-    C = x.shape[1]
-    R = x.numel() // C
-    dt = _DTYPE_CODES[x.dtype]
-    st = _raw_stream(x.device.index)
+    C, R, dt, st = geo
     stats = torch.empty((L.NSTAT, C), dtype=torch.float32, device=x.device)
     mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
     ws = _scratch(x, 'stats_nhwc', _ws_bytes('stats_nhwc', R, C, 1, dt), st)
@@ -636,31 +692,49 @@ def pc_qdq(x, N, C, HW, qp, want_codes=False, out=None, hist=None, reverse=False
     return (y, codes) if want_codes else y
 
 
-def _pc_qdq_nhwc(x, qp, out):
-    """pc_qdq on a dense channels_last x with the table qp (cnnq_pc_qdq_nhwc: the IEEE divide); y has x's layout."""
+def _pc_qdq_nhwc(x, qp, out, nbins=0, slot=None, st=None):
+    """pc_qdq on a dense channels_last x with the table qp (cnnq_pc_qdq_nhwc: the IEEE divide); y has x's layout.  slot (the
+    replica tables of _nhwc_hist_slot, st the stream they belong to): the pass also counts its codes into them, nbins bins
+    (cnnq_pc_qdq_hist_nhwc): (y, entropy)."""
     C = x.shape[1]
     y = _out_like(x, out)
-    L.check(L.load().cnnq_pc_qdq_nhwc(_ptr(x), _ptr(y), _DTYPE_CODES[x.dtype], x.numel() // C, C, _ptr(qp), _stream(x)),
-            'cnnq_pc_qdq_nhwc')
-    return y
+    if slot is None:
+        rc = L.load().cnnq_pc_qdq_nhwc(x.data_ptr(), y.data_ptr(), _DTYPE_CODES[x.dtype], x.numel() // C, C, qp.data_ptr(),
+                                       _raw_stream(x.device.index))
+        if rc:
+            L.check(rc, 'cnnq_pc_qdq_nhwc')
+        return y
+    rc = L.load().cnnq_pc_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), _DTYPE_CODES[x.dtype], x.numel() // C, C, qp.data_ptr(), nbins,
+                                        slot[0].data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_qdq_hist_nhwc')
+    return y, _replica_entropy(x, slot[0], slot[1], st)
 
 
-def _minmax_qdq_nhwc(x, num_bits, positive, out):
+def _minmax_qdq_nhwc(x, num_bits, positive, out, slot=None, st=None):
     """Config 2 on a dense channels_last x on one GPU (cnnq_pc_minmax_qdq_nhwc: statistics partials over slabs of rows, the
-    parameters, the channel extrema, the Q/DQ); one cached workspace, which also holds the parameter table.  y has x's layout."""
+    parameters, the channel extrema, the Q/DQ); one cached workspace, which also holds the parameter table.  y has x's layout.
+    slot, st: as _pc_qdq_nhwc, 2^num_bits bins (cnnq_pc_minmax_qdq_hist_nhwc): (y, entropy)."""
     lib = L.load()
     C = x.shape[1]
     R = x.numel() // C
     dt = _DTYPE_CODES[x.dtype]
     nbytes = _ws_bytes('nhwc', R, C, 1, dt)
     y = _out_like(x, out)
-    st = _raw_stream(x.device.index)
+    if slot is None:
+        st = _raw_stream(x.device.index)
     ws = _scratch(x, 'nhwc', nbytes + L.NQP * C * 4, st).data_ptr()
-    rc = lib.cnnq_pc_minmax_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, int(num_bits), 1 if positive else 0, ws, ws + nbytes,
-                                     None, st)
+    if slot is None:
+        rc = lib.cnnq_pc_minmax_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, int(num_bits), 1 if positive else 0, ws, ws + nbytes,
+                                         None, st)
+        if rc:
+            L.check(rc, 'cnnq_pc_minmax_qdq_nhwc')
+        return y
+    rc = lib.cnnq_pc_minmax_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, int(num_bits), 1 if positive else 0, ws, ws + nbytes,
+                                          None, slot[0].data_ptr(), st)
     if rc:
-        L.check(rc, 'cnnq_pc_minmax_qdq_nhwc')
-    return y
+        L.check(rc, 'cnnq_pc_minmax_qdq_hist_nhwc')
+    return y, _replica_entropy(x, slot[0], slot[1], st)
 
 
 def _hist_bins(num_bits, use_ba):
@@ -670,56 +744,13 @@ def _hist_bins(num_bits, use_ba):
     return 256 if use_ba else 1 << int(num_bits)
 
 
-def _pc_qdq_hist_nhwc(x, qp, nbins, out, slot, st):
-    """_pc_qdq_nhwc that also counts its codes into the replica tables of `slot` (cnnq_pc_qdq_hist_nhwc): (y, entropy)."""
-    hist, ent_batched = slot
-    C = x.shape[1]
-    y = _out_like(x, out)
-    rc = L.load().cnnq_pc_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), _DTYPE_CODES[x.dtype], x.numel() // C, C, _ptr(qp), nbins, _ptr(hist), st)
-    if rc:
-        L.check(rc, 'cnnq_pc_qdq_hist_nhwc')
-    return y, _replica_entropy(x, hist, ent_batched, st)
-
-
-def _minmax_qdq_hist_nhwc(x, num_bits, positive, out, slot, st):
-    """_minmax_qdq_nhwc that also counts its codes into the replica tables of `slot` (cnnq_pc_minmax_qdq_hist_nhwc): (y, entropy)."""
-    hist, ent_batched = slot
-    lib = L.load()
-    C = x.shape[1]
-    R = x.numel() // C
-    dt = _DTYPE_CODES[x.dtype]
-    nbytes = _ws_bytes('nhwc', R, C, 1, dt)
-    y = _out_like(x, out)
-    ws = _scratch(x, 'nhwc', nbytes + L.NQP * C * 4, st).data_ptr()
-    rc = lib.cnnq_pc_minmax_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, int(num_bits), 1 if positive else 0, ws, ws + nbytes,
-                                          None, _ptr(hist), st)
-    if rc:
-        L.check(rc, 'cnnq_pc_minmax_qdq_hist_nhwc')
-    return y, _replica_entropy(x, hist, ent_batched, st)
-
-
-_HIST_NHWC_NATIVE = {}
-
-
-def _hist_nhwc_native(R, C, dtype):
-    """Whether this class of layer runs the counting channels_last pass: word 3 of cnnq_pc_route_qdq_hist_nhwc's report (0: a class
-    that measured slower native than copied is sent back to the copy route there; a function of R, C and the dtype alone)."""
-    key = (R, C, dtype)
-    v = _HIST_NHWC_NATIVE.get(key)
-    if v is None:
-        out = (ctypes.c_int32 * 4)()
-        L.check(L.load().cnnq_pc_route_qdq_hist_nhwc(R, C, _DTYPE_CODES.get(dtype, -1), 16, 256, out), 'cnnq_pc_route_qdq_hist_nhwc')
-        v = _HIST_NHWC_NATIVE[key] = bool(out[3])
-    return v
-
-
 def _nhwc_hist_slot(x, what, st):
     """Where the counting pass of a dense channels_last x counts, as _entropy_slot gives it: (x, (tables, result or None)).  A class
-    of layer the route function sends back, and a call that can have no replica table (first use under a stream capture), take the
-    copy route instead: (x.contiguous() - counted, as _dev counts it - , None); that route is float32 only, so a half tensor raises
-    before anything is copied."""
+    of layer the route function sends back ('hist', asked with 256 bins), and a call that can have no replica table (first use
+    under a stream capture), take the copy route instead: (x.contiguous() - counted, as _dev counts it - , None); that route is
+    float32 only, so a half tensor raises before anything is copied."""
     C = x.shape[1]
-    slot = _entropy_slot(x, st) if _hist_nhwc_native(x.numel() // C, C, x.dtype) else (None, None)
+    slot = _entropy_slot(x, st) if _nhwc_native('hist', x.numel() // C, C, x.dtype) else (None, None)
     if slot[0] is not None:
         return x, slot
     if x.dtype != torch.float32:
@@ -1376,8 +1407,7 @@ def _packed_x(x, what):
 
 
 def _packed_table(t, what, dtype, shape, device):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == dtype and t.is_contiguous()
-            and tuple(t.shape) == tuple(shape)):
+    if not _is_table(t, dtype, shape, device):
         raise L.CnnqError('%s must be a contiguous %s device tensor of shape %s' % (what, str(dtype).replace('torch.', ''), list(shape)))
     return t
 
@@ -1615,9 +1645,9 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
         x, slot = _nhwc_hist_slot(x, 'act_qdq_per_channel', st)
         if slot is not None:
             if stats is None:
-                return _minmax_qdq_hist_nhwc(x, num_bits, positive, out, slot, st)
+                return _minmax_qdq_nhwc(x, num_bits, positive, out, slot, st)
             qp, _ = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
-            return _pc_qdq_hist_nhwc(x, qp, _hist_bins(num_bits, use_ba), out, slot, st)
+            return _pc_qdq_nhwc(x, qp, out, _hist_bins(num_bits, use_ba), slot, st)
     if _is_nhwc(x):
         if stats is None:
             return _minmax_qdq_nhwc(x, num_bits, positive, out)
@@ -1710,51 +1740,41 @@ def aciq_qdq_nhwc(x, num_bits, positive=False, clip='laplace', bit_alloc=False, 
         raise L.CnnqError("aciq_qdq_nhwc: clip must be 'laplace' or 'gaus', got %r" % (clip,))
     if want_entropy and num_bits > 8:
         raise L.CnnqError('aciq_qdq_nhwc: the ACIQ factor tables end at 8 bits')
-    x = _dev_act_layout(x, 'x')
-    if x.dim() != 4:
-        raise L.CnnqError('aciq_qdq_nhwc: x must be a 4-D activation, got %d dimensions' % x.dim())
+    x, geo = _admit_nhwc(x, 'aciq_qdq_nhwc', dev_first=True)
     use_ba = bool(bit_alloc) and num_bits <= 4
-    st = _raw_stream(x.device.index)
     hist = ent_batched = None
-    if want_entropy and _is_nhwc(x):
-        x, slot = _nhwc_hist_slot(x, 'aciq_qdq_nhwc', st)
-        if slot is not None:
+    if want_entropy and geo is not None:
+        x, slot = _nhwc_hist_slot(x, 'aciq_qdq_nhwc', geo[3])
+        if slot is None:
+            geo = None
+        else:
             hist, ent_batched = slot
-    if not _is_nhwc(x):
+    if geo is None:
         return act_qdq_per_channel(x, num_bits, positive, clip, bit_alloc, prior_is_b, target, round_mode, group=False,
                                    want_parts=want_parts, stats=stats, out=out, want_entropy=want_entropy)
-    lib = L.load()
-    C = x.shape[1]
-    R = x.numel() // C
-    dt = _DTYPE_CODES[x.dtype]
+    C, R, dt, st = geo
     if stats is not None:
         qp, diag = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
         if want_entropy:
-            y = _out_like(x, out)
-            rc = lib.cnnq_pc_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, _ptr(qp), _hist_bins(num_bits, use_ba), _ptr(hist), st)
-            if rc:
-                L.check(rc, 'cnnq_pc_qdq_hist_nhwc')
-        else:
-            y = _pc_qdq_nhwc(x, qp, out)
-        return _result(y, entropy=_replica_entropy(x, hist, ent_batched, st) if want_entropy else None,
-                       parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
+            y, entropy = _pc_qdq_nhwc(x, qp, out, _hist_bins(num_bits, use_ba), slot, st)
+            return _result(y, entropy=entropy, parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
+        return _result(_pc_qdq_nhwc(x, qp, out), parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
     cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
     nbytes = _ws_bytes('aciq_nhwc', R, C, 1, dt)
     y = _out_like(x, out)
-    ntab = (L.NSTAT + L.NQP + L.NDIAG) * C * 4
     if want_parts:
         tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, C, dtype=torch.float32, device=x.device)
         ws, tp = _scratch(x, 'aciq_nhwc', nbytes, st).data_ptr(), tabs.data_ptr()
     else:
         # the tables nobody outside the call reads follow the records in the cached workspace
-        ws = _scratch(x, 'aciq_nhwc', nbytes + ntab, st).data_ptr()
+        ws = _scratch(x, 'aciq_nhwc', nbytes + (L.NSTAT + L.NQP + L.NDIAG) * C * 4, st).data_ptr()
         tp = ws + nbytes
     if want_entropy:
-        rc = lib.cnnq_pc_aciq_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
-                                            tp + (L.NSTAT + L.NQP) * C * 4, _ptr(hist), st)
+        rc = L.load().cnnq_pc_aciq_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                                 tp + (L.NSTAT + L.NQP) * C * 4, hist.data_ptr(), st)
     else:
-        rc = lib.cnnq_pc_aciq_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
-                                       tp + (L.NSTAT + L.NQP) * C * 4, st)
+        rc = L.load().cnnq_pc_aciq_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                            tp + (L.NSTAT + L.NQP) * C * 4, st)
     if rc:
         L.check(rc, 'cnnq_pc_aciq_qdq_nhwc')
     return _result(y, entropy=_replica_entropy(x, hist, ent_batched, st) if want_entropy else None,
@@ -1818,22 +1838,17 @@ def qdq_bias_corrected_nhwc(x, qp, relu_first, out=None, want_parts=False):
     call, one cached workspace - 12 B/elem in fp32, 6 in bf16 / fp16.  y has x's layout and dtype; want_parts: (y, dict(sums
     [3, C] float64 = {sum x', sum q, count(x' > 0)}, bias [C])).  One GPU: the sums are this tensor's.  A tensor that is not
     dense channels_last (or CNNQ_NHWC=0: copied, counted) takes qdq_bias_corrected, which is float32 only."""
-    x = _dev_act_layout(x, 'x')
-    if x.dim() != 4:
-        raise L.CnnqError('qdq_bias_corrected_nhwc: x must be a 4-D activation, got %d dimensions' % x.dim())
-    if not _is_nhwc(x):
+    x, geo = _admit_nhwc(x, 'qdq_bias_corrected_nhwc', dev_first=True)
+    if geo is None:
         if x.dtype != torch.float32:
             _half_only('qdq_bias_corrected_nhwc', 'the bias correction of a tensor that is not dense channels_last')
         N, C, HW = geometry(x)
         return qdq_bias_corrected(x, N, C, HW, qp, relu_first, out=out, want_parts=want_parts)
-    C = x.shape[1]
-    if not (qp.is_cuda and qp.dtype == torch.float32 and qp.is_contiguous() and tuple(qp.shape) == (L.NQP, C)):
+    C, R, dt, st = geo
+    if not _is_table(qp, torch.float32, (L.NQP, C), x.device):
         raise L.CnnqError('qdq_bias_corrected_nhwc: qp must be a contiguous float32 [%d, %d] device table' % (L.NQP, C))
-    R = x.numel() // C
-    dt = _DTYPE_CODES[x.dtype]
     nbytes = _ws_bytes('bcorr_nhwc', R, C, 1, dt)
     y = _out_like(x, out)
-    st = _raw_stream(x.device.index)
     if want_parts:
         sums = torch.empty((3, C), dtype=torch.float64, device=x.device)
         bias = torch.empty(C, dtype=torch.float32, device=x.device)
@@ -1842,7 +1857,7 @@ def qdq_bias_corrected_nhwc(x, qp, relu_first, out=None, want_parts=False):
         # the bias nobody outside the call reads follows the records in the cached workspace
         ws = _scratch(x, 'bcorr_nhwc', nbytes + C * 4, st).data_ptr()
         sp, bp = None, ws + nbytes
-    rc = L.load().cnnq_pc_qdq_bcorr_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, _ptr(qp), int(bool(relu_first)), ws, sp, bp, st)
+    rc = L.load().cnnq_pc_qdq_bcorr_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, qp.data_ptr(), int(bool(relu_first)), ws, sp, bp, st)
     if rc:
         L.check(rc, 'cnnq_pc_qdq_bcorr_nhwc')
     return _result(y, parts=dict(sums=sums, bias=bias) if want_parts else None)
@@ -1930,28 +1945,8 @@ def mid_tread_qdq_single(x, N, C, HW, target, sym, tabs, want_entropy=False, wan
                                          ws.data_ptr(), gws, GROUP_WS_BYTES, _ptr(stats), _ptr(mt), _ptr(hist), int(flags), st)
     if not _supported(rc, 'cnnq_pc_midtread_qdq_single'):
         return None
-    entropy = None
-    if want_entropy:
-        if _ENT_BATCH is not None:
-            entropy = _ENT_BATCH.add_midtread(hist, mt, C, x.numel(), x.device)      # one launch for the whole block, at its end
-        else:
-            entropy = _mt_entropy(x, hist, mt, C, st)
-    return _mt_result(y, entropy, parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
-
-
-_MT_NHWC_NATIVE = {}
-
-
-def _mt_nhwc_native(R, C, dtype):
-    """Whether this class of layer runs on the channels_last kernels: word 5 of cnnq_pc_route_midtread_nhwc's report (0: a class
-    that measured slower native than copied is sent back to the copy route there; a function of R, C and the dtype alone)."""
-    key = (R, C, dtype)
-    v = _MT_NHWC_NATIVE.get(key)
-    if v is None:
-        out = (ctypes.c_int32 * 6)()
-        L.check(L.load().cnnq_pc_route_midtread_nhwc(R, C, _DTYPE_CODES.get(dtype, -1), 16, 0, out), 'cnnq_pc_route_midtread_nhwc')
-        v = _MT_NHWC_NATIVE[key] = bool(out[5])
-    return v
+    return _mt_result(y, _mt_entropy_here(x, hist, mt, C, st) if want_entropy else None,
+                      parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
 
 
 def mid_tread_qdq_nhwc(x, target, sym, want_entropy=False, stats=None, out=None, want_parts=False):
@@ -1964,27 +1959,18 @@ def mid_tread_qdq_nhwc(x, target, sym, want_entropy=False, stats=None, out=None,
     statistics are this tensor's.  A tensor that is not dense channels_last (or CNNQ_NHWC=0, or a class of layer the route function
     sends back: copied, counted) takes mid_tread_qdq, which is float32 only - a half tensor raises before anything is copied -
     and knows neither `stats` nor `out`."""
-    if isinstance(x, torch.Tensor) and x.dim() != 4:
-        raise L.CnnqError('mid_tread_qdq_nhwc: x must be a 4-D activation, got %d dimensions' % x.dim())
-    native = (isinstance(x, torch.Tensor) and x.is_cuda and _NHWC and _layout(x) == 'nhwc'
-              and _mt_nhwc_native(x.numel() // x.shape[1], x.shape[1], x.dtype))
-    if not native and isinstance(x, torch.Tensor) and x.dtype in _HALF_DTYPES:
-        # before anything is copied or counted
-        _half_only('mid_tread_qdq_nhwc', 'the mid-tread quantization of a tensor that does not take the channels_last kernels')
-    x = _dev(x, 'x', _ACT_DTYPES, keep_nhwc=native)
-    if not native:
+    x, geo = _admit_nhwc(x, 'mid_tread_qdq_nhwc', 'midtread',
+                         'the mid-tread quantization of a tensor that does not take the channels_last kernels')
+    if geo is None:
         if stats is not None or out is not None:
             raise L.CnnqError('mid_tread_qdq_nhwc: stats= and out= need a dense channels_last tensor')
         return mid_tread_qdq(x, target, clip=True, sym=sym, group=False, want_entropy=want_entropy, want_parts=want_parts)
     lib = L.load()
-    C = x.shape[1]
-    R = x.numel() // C
-    dt = _DTYPE_CODES[x.dtype]
+    C, R, dt, st = geo
     tabs = _midtread_tables(x.device)
     y = _out_like(x, out)
-    st = _raw_stream(x.device.index)
     if stats is not None:
-        if not (stats.is_cuda and stats.dtype == torch.float32 and stats.is_contiguous() and tuple(stats.shape) == (L.NSTAT, C)):
+        if not _is_table(stats, torch.float32, (L.NSTAT, C), x.device):
             raise L.CnnqError('mid_tread_qdq_nhwc: stats must be a contiguous float32 [%d, %d] device table' % (L.NSTAT, C))
         mt = torch.empty((L.NMT, C), dtype=torch.float32, device=x.device)
         L.check(lib.cnnq_pc_midtread_params(_ptr(stats), C, float(target), 1, int(bool(sym)), _ptr(tabs), tabs.shape[1], _ptr(mt), st),
@@ -2010,13 +1996,16 @@ def mid_tread_qdq_nhwc(x, target, sym, want_entropy=False, stats=None, out=None,
                                        ws, tp, tp + L.NSTAT * C * 4, _ptr(hist), st)
         if rc:
             L.check(rc, 'cnnq_pc_midtread_nhwc')
-    entropy = None
-    if want_entropy:
-        if _ENT_BATCH is not None:
-            entropy = _ENT_BATCH.add_midtread(hist, mt, C, x.numel(), x.device)      # one launch for the whole block, at its end
-        else:
-            entropy = _mt_entropy(x, hist, mt, C, st)
-    return _mt_result(y, entropy, parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
+    return _mt_result(y, _mt_entropy_here(x, hist, mt, C, st) if want_entropy else None,
+                      parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
+
+
+def _mt_entropy_here(x, hist, mt, C, st):
+    """The entropy of this GPU's mid-tread code histogram of x: inside an entropy_batch block one launch for the whole block, at its
+    end; else one launch behind the tensor."""
+    if _ENT_BATCH is not None:
+        return _ENT_BATCH.add_midtread(hist, mt, C, x.numel(), x.device)
+    return _mt_entropy(x, hist, mt, C, st)
 
 
 def _mt_entropy(x, hist, mt, C, st, group=None, mom=None):

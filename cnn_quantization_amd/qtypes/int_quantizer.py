@@ -43,6 +43,12 @@ def _is_pc_act(t):
     return len(t.shape) > 3 and (t.shape[2] > 1 or t.shape[3] > 1)
 
 
+def _dense_nhwc(t):
+    """A dense channels_last 4-D tensor that is not contiguous - what ops._layout calls 'nhwc'; a contiguous tensor never asks ops -
+    with the channels_last switch on.  Shape and strides only."""
+    return t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
+
+
 def _to_f32_vec(v, C):
     a = np.asarray(v, dtype=np.float32).reshape(-1)
     if a.size == 1 and C > 1:
@@ -130,6 +136,10 @@ class IntQuantizer:
         """The attribute lookup the dispatch predicates share: __call__'s override_att pair wins over the attribute."""
         return lambda k: override_att[1] if override_att is not None and override_att[0] == k else getattr(self, k)
 
+    def _one_gpu(self):
+        """Replicated data excluded (group is not False), a batch that is not sharded, no forced exchange."""
+        return self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange()
+
     def _half_native(self, tensor, override_att=None, stat_id=None):
         """Whether a bf16 / fp16 tensor takes a path with half kernels: config 2 (gemmlowpQuantizeActivationPerChannel without
         clipping, bit allocation, entropy, a bias correction to fold in or a sharded batch), config 1 (gemmlowpMinMaxQuantize),
@@ -147,68 +157,49 @@ class IntQuantizer:
             return False
         if att('pcq_a') and _is_pc_act(tensor):
             return (not att('mtd_quant') and not att('measure_entropy') and self.fuse_bcorr is None
-                    and not (att('bit_alloc_act') and att('num_bits') <= 4)
-                    and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+                    and not (att('bit_alloc_act') and att('num_bits') <= 4) and self._one_gpu())
         return True
 
+    # The four channels_last routes.  Each wants a dense channels_last tensor (_dense_nhwc) on the per-channel activation branch and
+    # one GPU's own data (_one_gpu), and reads shape, strides and attributes only; att: the lookup of _att.  _nhwc_midtread and
+    # _nhwc_entropy are kept apart from _half_native, which goes on answering False for mtd_quant and measure_entropy: the tests
+    # of the earlier channels_last routes pin those answers, so __call__ asks all three before it upcasts.
     def _nhwc_aciq(self, tensor, clip_type, att=None):
-        """Whether gemmlowpClippingQuantize runs this call on the channels_last storage as it is (ops.aciq_qdq_nhwc, DESIGN.md
-        section 14): a dense channels_last tensor on the per-channel branch with Laplace or Gaussian clipping, no entropy
-        measurement, no bias correction to fold in, and a batch that is not sharded.  Shape, strides and attributes only."""
+        """gemmlowpClippingQuantize runs on the storage as it is (ops.aciq_qdq_nhwc): Laplace or Gaussian
+        clipping, no entropy measurement, no bias correction to fold in."""
         att = att or (lambda k: getattr(self, k))
-        # dense channels_last and not contiguous: what ops._layout calls 'nhwc' (a contiguous tensor never asks ops)
-        return (bool(att('pcq_a')) and _is_pc_act(tensor) and clip_type in ('laplace', 'gaus')
-                and tensor.dim() == 4 and not tensor.is_contiguous()
-                and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
-                and not att('measure_entropy') and self.fuse_bcorr is None
-                and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+        return (bool(att('pcq_a')) and _is_pc_act(tensor) and clip_type in ('laplace', 'gaus') and _dense_nhwc(tensor)
+                and not att('measure_entropy') and self.fuse_bcorr is None and self._one_gpu())
 
     def _nhwc_bcorr(self, tensor, clip_type, stat_id, att=None):
-        """Whether the per-channel activation branches fold a pending bias correction in on the channels_last storage as it is
-        (ops.qdq_bias_corrected_nhwc): a dense channels_last tensor on the per-channel activation branch
-        (min/max, Laplace or Gaussian clipping) with calibrated statistics (stat_id: the product requests the correction only
-        under -sm use, so only the table-driven form exists), a pending fuse_bcorr, no entropy measurement, and a batch that is
-        not sharded.  Without stat_id: False, and every other answer is what it was.  Shape, strides and attributes only."""
+        """The per-channel activation branches (min/max, Laplace or Gaussian clipping) fold a pending bias correction in on the
+        storage as it is (ops.qdq_bias_corrected_nhwc): calibrated statistics (stat_id: the product requests
+        the correction only under -sm use, so only the table-driven form exists; without it False), a pending fuse_bcorr, no
+        entropy measurement."""
         att = att or (lambda k: getattr(self, k))
         return (stat_id is not None and self.fuse_bcorr is not None and bool(att('pcq_a')) and _is_pc_act(tensor)
-                and clip_type in ('no', 'laplace', 'gaus') and not (clip_type == 'no' and att('pcq_w'))
-                and tensor.dim() == 4 and not tensor.is_contiguous()
-                and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
-                and not att('mtd_quant') and not att('kld') and not att('measure_entropy')
-                and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+                and clip_type in ('no', 'laplace', 'gaus') and not (clip_type == 'no' and att('pcq_w')) and _dense_nhwc(tensor)
+                and not att('mtd_quant') and not att('kld') and not att('measure_entropy') and self._one_gpu())
 
     def _nhwc_midtread(self, tensor, att=None):
-        """Whether mid_tread_quantize_activation_per_channel runs this call on the channels_last storage as it is
-        (ops.mid_tread_qdq_nhwc): mid-tread quantization with clipping on the per-channel activation branch,
-        a dense channels_last tensor, no KLD, no bias correction to fold in, replicated data excluded (group is not False) and a
-        batch that is not sharded; the entropy measurement may be on or off.  att: the lookup of _att, as _nhwc_aciq takes it.  Shape,
-        strides and attributes only.  Kept apart from _half_native, which goes on answering False for mtd_quant: the tests of
-        the earlier channels_last routes pin that answer, so __call__ asks both before it upcasts."""
+        """mid_tread_quantize_activation_per_channel runs on the storage as it is (ops.mid_tread_qdq_nhwc):
+        mid-tread quantization with clipping, no KLD, no bias correction to fold in; the entropy measurement may be on or off."""
         get = att or self._att()
         return (bool(get('mtd_quant')) and get('clipping') != 'no' and not get('kld')
-                and bool(get('pcq_a')) and _is_pc_act(tensor)
-                and tensor.dim() == 4 and not tensor.is_contiguous()
-                and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
-                and self.fuse_bcorr is None
-                and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+                and bool(get('pcq_a')) and _is_pc_act(tensor) and _dense_nhwc(tensor)
+                and self.fuse_bcorr is None and self._one_gpu())
 
     def _nhwc_entropy(self, tensor, att=None):
-        """Whether gemmlowpQuantizeActivationPerChannel measures the entropy of its codes on the channels_last storage as it is
-        (ops.act_qdq_per_channel's counting route): measure_entropy on the per-channel activation branch
-        without clipping - no KLD, no weight branch in front of it, no mid-tread, no bit allocation in effect, codes that fit a
-        byte - a dense channels_last tensor, no bias correction pending (with -me the layer corrects afterwards), replicated data
-        excluded (group is not False) and a batch that is not sharded; dynamic or with stat_id.  att: the lookup of _att.  Shape,
-        strides and attributes only.  Kept apart from _half_native, which goes on answering False for measure_entropy: the
-        tests of the earlier channels_last routes pin that answer, so __call__ asks both before it upcasts.  Config 3 with
-        -me is one predicate away (ops.aciq_qdq_nhwc takes want_entropy) and stays on the copy route, as its tests pin it."""
+        """gemmlowpQuantizeActivationPerChannel measures the entropy of its codes on the storage as it is (ops.act_qdq_per_channel's
+        counting route): measure_entropy without clipping - no KLD, no weight branch in front of it, no
+        mid-tread, no bit allocation in effect, codes that fit a byte - and no bias correction pending (with -me the layer
+        corrects afterwards); dynamic or with stat_id.  Config 3 with -me is one predicate away (ops.aciq_qdq_nhwc takes
+        want_entropy) and stays on the copy route, as its tests pin it."""
         get = att or self._att()
         return (bool(get('measure_entropy')) and bool(get('pcq_a')) and _is_pc_act(tensor)
                 and get('clipping') == 'no' and not get('pcq_w') and not get('mtd_quant') and not get('kld')
-                and not (get('bit_alloc_act') and get('num_bits') <= 4) and get('num_bits') <= 8
-                and tensor.dim() == 4 and not tensor.is_contiguous()
-                and tensor.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
-                and self.fuse_bcorr is None
-                and self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange())
+                and not (get('bit_alloc_act') and get('num_bits') <= 4) and get('num_bits') <= 8 and _dense_nhwc(tensor)
+                and self.fuse_bcorr is None and self._one_gpu())
 
     def _bcorr_nhwc(self, tensor, table, clip_type, prior_b):
         """The _nhwc_bcorr route: the parameters of the calibration table, then Q/DQ and correction where the tensor lies."""
