@@ -17,6 +17,7 @@ namespace {
 //                 expansion stops one bin short, kld_threshold.py:62-65), both smoothed in float32
 //                 exactly as the reference, KL(P || Q) accumulated in fp64 (the reference: float32)
 //   k_kld_pick    numpy.argmin over the 994 divergences (first NaN wins, else first minimum)
+//   A row whose min or max is not finite (kld_range: ok == false) gets an all-zero histogram and the pick (NaN, NaN, 0).
 // ------------------------------------------------------------------------------------------
 constexpr int KB = CNNQ_KLD_BINS;
 constexpr int KQ = CNNQ_KLD_QBINS;
@@ -27,9 +28,17 @@ static_assert(KC == KB / 2 + 1 - KQ / 2, "candidate count");
 
 struct KldRange {
     double first, last, step, scale;
+    bool ok;
 };
 __device__ __forceinline__ KldRange kld_range(float mn, float mx) {
     KldRange r;
+    // a row whose min or max is NaN or +-inf has no histogram range (numpy.histogram raises there): by this range check - no
+    // arithmetic on infinities, no NaN converted to int - its histogram stays empty and its pick is (NaN, NaN, 0)
+    r.ok = fabsf(mn) <= 3.402823466e+38f && fabsf(mx) <= 3.402823466e+38f;
+    if (!r.ok) {
+        r.first = r.last = r.step = r.scale = __longlong_as_double(0x7ff8000000000000LL);
+        return r;
+    }
     const double th = fmax(fabs((double)mn), fabs((double)mx));
     r.first = -th;
     r.last = th;
@@ -54,6 +63,7 @@ __global__ void __launch_bounds__(TPB) k_kld_hist(const float* __restrict__ x, i
     const int row = blockIdx.y, tid = threadIdx.x;
     for (int i = tid; i < KB * KREP; i += TPB) sh[i] = 0;
     const KldRange r = kld_range(rowmm[row], rowmm[rows + row]);
+    if (!r.ok) return;   // the whole workgroup: the row stays as the host zeroed it
     __syncthreads();
     const int64_t beg = (int64_t)blockIdx.x * KCHUNK;
     const int64_t end = min(beg + (int64_t)KCHUNK, len);
@@ -256,9 +266,9 @@ __global__ void __launch_bounds__(64) k_kld_pick(const double* __restrict__ div,
     if (lane == 0) {
         const int k = nan_idx < KC ? nan_idx : min(best_idx, KC - 1);
         const KldRange r = kld_range(rowmm[row], rowmm[rows + row]);
-        out[(size_t)row * 3 + 0] = kld_edge(r, KB / 2 + (k + KQ / 2) + 1);
-        out[(size_t)row * 3 + 1] = d[k];
-        out[(size_t)row * 3 + 2] = (double)k;
+        out[(size_t)row * 3 + 0] = r.ok ? kld_edge(r, KB / 2 + (k + KQ / 2) + 1) : r.last;
+        out[(size_t)row * 3 + 1] = r.ok ? d[k] : r.last;
+        out[(size_t)row * 3 + 2] = r.ok ? (double)k : 0.;
     }
 }
 

@@ -614,7 +614,9 @@ int cnnq_pt_minmax_qdq_fused(const float* x, float* y, int64_t n, int rows, int 
  *                    (kld_threshold.py:31-77, 15 quantized bins), then per row
  *                    out[rows][3] = {optimal threshold (the upper histogram edge of the kept range),
  *                    its divergence, candidate index}: numpy.argmin semantics (kld_threshold.py:79-81).
- *                    The `kld_th` statistic is the maximum of out[:,0] over the batch. */
+ *                    The `kld_th` statistic is the maximum of out[:,0] over the batch.
+ * A row whose min or max is NaN or +-inf has no range (numpy.histogram raises): its hist row stays all zero and its
+ * out is {NaN, NaN, 0}, whatever hist holds; the other rows are not affected. */
 #define CNNQ_KLD_BINS 2001
 #define CNNQ_KLD_QBINS 15
 #define CNNQ_KLD_NCAND 994
