@@ -58,6 +58,7 @@
 #include "cnnq_nhwc_entropy.hip.h"
 #include "cnnq_nhwc_packed.hip.h"
 #include "cnnq_qerr.hip.h"
+#include "cnnq_rows.hip.h"
 
 namespace {
 
@@ -2127,6 +2128,72 @@ int cnnq_pc_aciq_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int64
     int rc = cl_aciq_front(x, dtype, R, C, p, cfg, ws, stats, qp, diag, stream);
     if (!rc) rc = cnnq_pc_packed_layout_nhwc(ba ? diag + (size_t)CNNQ_DIAG_BITS * C : nullptr, ba ? 0 : cfg->num_bits, C, coloff, stream);
     if (!rc) rc = cl_pack(x, dtype, R, C, p, qp, nullptr, coloff, packed, ba ? -1 : cfg->num_bits, hs(stream));
+    return rc;
+}
+
+
+// ---- statistics of few, very long rows over flat storage (cnnq_rows.hip.h): x [rows][len], fp32 / bf16 / fp16 -------------------
+// What the three entry points derive from (rows, len, dtype, alignment) after their argument checks: the piece width and the
+// geometry.  CNNQ_ERANGE: 2^31 rows (the merge kernels index the records' columns in 32 bits), a chunk of 2^31 pieces (out[2] of
+// the route function), or a tensor whose byte offsets leave 63 bits.
+static int rows_check(int64_t rows, int64_t len, int dtype) { return (!dtype_ok(dtype) || rows < 1 || len < 1) ? CNNQ_EINVAL : 0; }
+static int rows_plan(int64_t rows, int64_t len, int dtype, int align_bytes, int* w, RowsGeo* g) {
+    if (rows >= ((int64_t)1 << 31) || len > (INT64_MAX >> 3) / rows) return CNNQ_ERANGE;
+    *w = cl_piece(len, cl_esize(dtype), align_bytes);
+    *g = rows_geo(rows, len, *w);
+    return g->ppc >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
+}
+
+// ws, doubles: part[S][CNNQ_NMOM][rows], mom[CNNQ_NMOM][rows], part2[S][CNNQ_NDEV][rows] (AciqWs without the table) for the largest
+// S over the piece widths len allows (the alignment is not known yet)
+size_t cnnq_rows_stats_workspace(int64_t rows, int64_t len, int dtype) {
+    if (rows_check(rows, len, dtype) || rows >= ((int64_t)1 << 31)) return 0;
+    int64_t S = 1;
+    for (int w = 16 / cl_esize(dtype); w >= 1; w >>= 1) {
+        if (len % w) continue;
+        const int64_t s = rows_geo(rows, len, w).S;
+        S = s > S ? s : S;
+    }
+    return AciqWs::bytes((size_t)S, rows, false);
+}
+
+// Which launches cnnq_rows_stats makes for this geometry (host only): out = {elements per load W, chunks per row S, pieces per
+// chunk, 1 - the row is summed in fp64 throughout}.  No class of tensor is sent back to the copy route: none measured slower
+// native than through the copy (tools/bench_tensor_collect.py); one that does gets its rule here, with the figures next to it.
+int cnnq_rows_stats_route(int64_t rows, int64_t len, int dtype, int align_bytes, int32_t out[4]) {
+    if (rows_check(rows, len, dtype) || !out || !pow2(align_bytes) || align_bytes < cl_esize(dtype)) return CNNQ_EINVAL;
+    int w;
+    RowsGeo g;
+    if (const int rc = rows_plan(rows, len, dtype, align_bytes, &w, &g)) return rc;
+    out[0] = w;
+    out[1] = g.S;
+    out[2] = (int32_t)g.ppc;
+    out[3] = g.exact;
+    return 0;
+}
+
+// statistic_manager.py:55-96 (rows = 1) and distance_stats.py:22-33 (rows = N) on the storage as it lies: k_rows_moments ->
+// k_combine(has_relu) (-> k_rows_absdev on the merged table -> k_combine_dev(want_kurt); need_dev), two or four launches
+int cnnq_rows_stats(const void* x, int dtype, int64_t rows, int64_t len, int need_dev, void* ws, double* mom, float* stats, void* stream) {
+    if (rows_check(rows, len, dtype)) return CNNQ_EINVAL;
+    if (!x || !ws || !stats || misaligned(ws, 8) || misaligned(mom, 8) || misaligned(x, (uintptr_t)cl_esize(dtype))) return CNNQ_EINVAL;
+    int w;
+    RowsGeo g;
+    if (const int rc = rows_plan(rows, len, dtype, h_align(x, x), &w, &g)) return rc;
+    const AciqWs a(ws, g.S, rows);
+    double* rec = mom ? mom : a.mom;
+    hipStream_t st = hs(stream);
+    int rc = cl_launch(dtype, w, x, [&](auto pc, auto* xr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_rows_moments<typename P::T, P::W>), rows_grid(g), dim3(TPB), 0, st, xr, g, a.part);
+    });
+    if (!rc) rc = cnnq_pc_combine(a.part, g.S, rows, 1, rec, stats, stream);
+    if (rc || !need_dev) return rc;
+    rc = cl_launch(dtype, w, x, [&](auto pc, auto* xr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_rows_absdev<typename P::T, P::W>), rows_grid(g), dim3(TPB), 0, st, xr, g, stats, a.part2);
+    });
+    if (!rc) rc = cnnq_pc_combine_dev(a.part2, g.S, rows, rec, 1, nullptr, stats, stream);
     return rc;
 }
 

@@ -34,7 +34,7 @@ from .. import ops
 from ..qtypes import DummyQuantizer, int_quantizer
 from ..qtypes.int_quantizer import upcast_fallback
 from ..utils.misc import Singleton
-from .statistic_manager import StatisticManager
+from .statistic_manager import StatisticManager, collects_native_flat
 from .statistic_manager_perchannel import StatisticManagerPerChannel, collects_native_nhwc
 
 FUSED_RELU_ARCHS = ('alexnet', 'vgg16', 'vgg16_bn', 'inception_v3')
@@ -59,7 +59,12 @@ class MeasureStatistics:
         self.stats_names = ['dist']
 
     def save_measure(self, tensor, id):
-        d = upcast_fallback(ops.row_sumsq, tensor.detach().contiguous(), tensor.shape[0], cast_back=False).cpu().numpy().astype(np.float64)
+        t = tensor.detach()
+        if t.is_cuda and t.dim() > 0 and t.numel() > 0 and (t.dtype in ops._HALF_DTYPES or (t.dtype == torch.float32 and ops._NHWC and ops._layout(t) == 'nhwc')):
+            # bf16 / fp16 and dense channels_last outputs: ops.row_sumsq reads them where they lie
+            d = ops.row_sumsq(t, t.shape[0]).cpu().numpy().astype(np.float64)
+        else:
+            d = upcast_fallback(ops.row_sumsq, t.contiguous(), tensor.shape[0], cast_back=False).cpu().numpy().astype(np.float64)
         self.stats[id] = np.concatenate([self.stats[id], d]) if id in self.stats else d
 
     def __enter__(self):
@@ -96,6 +101,10 @@ def _route(layer, out, out_id, tag, *, shifted=False, half_range=False, collect_
             kw.update(half_range=half_range, err_settings=qm.err_settings(out_id, '' if shifted else tag, half_range))
         if isinstance(qm.stats_manager, StatisticManagerPerChannel) and collects_native_nhwc(qm.stats_manager, out, force_global):
             # a dense channels_last output the manager reads where it lies, in its own dtype: nothing to upcast
+            qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, **kw)
+            return out
+        if isinstance(qm.stats_manager, StatisticManager) and collects_native_flat(qm.stats_manager, out):
+            # a bf16 / fp16 or dense channels_last output the per-tensor manager reads where it lies: nothing to upcast
             qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, **kw)
             return out
         upcast_fallback(qm.stats_manager.save_tensor_stats, out, tag if collect_tag is None else collect_tag, out_id, **kw)

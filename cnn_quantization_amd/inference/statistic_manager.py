@@ -4,7 +4,8 @@ pytorch_quantizer/quantization/inference/statistic_manager.py: same API and file
 id).  Serves the per-tensor quantizers (pooling, classifier, linear) in `-sm use` mode.
 
 The scalar statistics of a batch are one pass of the device kernels over the tensor viewed as a
-single channel.  `kld_threshold=True` adds the `kld_th` column (statistic_manager.py:80-82: the
+single channel; a bf16 / fp16 tensor and a dense channels_last one are read where they lie, in their
+own dtype (collects_native_flat, ops.tensor_stats).  `kld_threshold=True` adds the `kld_th` column (statistic_manager.py:80-82: the
 maximum over the batch's samples of the KLD-optimal clipping threshold) from the device
 histogram + search kernels (ops.kld_thresholds).  The error columns (mse_*/cos_*,
 statistic_manager.py:22-30) exist in the reference's files but no caller ever passes the quantized
@@ -26,6 +27,24 @@ from ..utils.misc import Singleton, sorted_nicely
 
 def base_dir():
     return os.path.join(str(Path.home()), 'mxt-sim')
+
+
+def collects_native_flat(manager, tensor):
+    """Whether save_tensor_stats takes this tensor on its storage as it lies (ops.tensor_stats: no layout copy, no upcast): a
+    CUDA tensor of fp32 / bf16 / fp16 that is contiguous and not float32, or dense channels_last with the channels_last switch
+    on; one process and no forced exchange; and not a half tensor when the KLD threshold is collected (its histogram has no half
+    kernel).  A contiguous float32 tensor and every sharded run answer False and take the code they took.  Shape, strides, dtype
+    and attributes only: nothing touches the device.  No class of tensor measured slower native than through the copy
+    (profiles/tensor_collect.md), so the route function is not asked."""
+    if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype in ops._ACT_DTYPES and tensor.numel() > 0):
+        return False
+    half = tensor.dtype != torch.float32
+    layout = ops._layout(tensor)
+    if not ((layout == 'nchw' and half) or (layout == 'nhwc' and ops._NHWC)):
+        return False
+    if D.world_size(manager.group) != 1 or D.forced_exchange():
+        return False
+    return not (manager.kld_threshold and half)
 
 
 class StatisticManager(metaclass=Singleton):
@@ -55,12 +74,17 @@ class StatisticManager(metaclass=Singleton):
     def save_tensor_stats(self, tensor, tag, id, tensors_q={}, force_global_min_max=False):
         if len(tensors_q) > 0:
             raise NotImplementedError('error columns from quantized tensors: no caller in the reference')
-        x = tensor.detach().contiguous()
+        native = collects_native_flat(self, tensor)
+        x = tensor.detach() if native else tensor.detach().contiguous()
         n = x.numel()
         # with several ranks x is this rank's batch shard: the moment records travel (ops.pc_stats), every rank
         # holds the statistics of the GLOBAL batch
         world = D.world_size(self.group)
-        table, mom = ops.pc_stats(x, 1, 1, n, need_b=True, need_kurt=True, need_relu=True, group=self.group)
+        if native:
+            # bf16 / fp16 and dense channels_last tensors, one process: the flat-row kernels on the storage as it lies
+            table, mom = ops.tensor_stats(x, 1)
+        else:
+            table, mom = ops.pc_stats(x, 1, 1, n, need_b=True, need_kurt=True, need_relu=True, group=self.group)
         if world > 1 and not D.xrank_checkpoint(self.group):
             # a wait of the in-launch exchange expired on some rank: the group is on the collective now - the table again
             table, mom = ops.pc_stats(x, 1, 1, n, need_b=True, need_kurt=True, need_relu=True, group=self.group)
@@ -71,7 +95,10 @@ class StatisticManager(metaclass=Singleton):
                 'mean': host[L.STAT_MEAN], 'kurtosis': host[L.STAT_KURT], 'b': host[L.STAT_B],
                 'mean_abs': np.float32((2. * m[L.MOM_SUM_RELU] - m[L.MOM_SUM]) / total), 'dim': int(total)}
         if self.batch_avg and not force_global_min_max and x.dim() > 1:
-            rows, _ = ops.pc_stats(x, 1, x.shape[0], n // x.shape[0], local_only=True)
+            if native:      # the exact per-sample extrema, rows MIN / MAX: native in the three dtypes and both layouts
+                rows = ops.tensor_row_stats(x, x.shape[0])
+            else:
+                rows, _ = ops.pc_stats(x, 1, x.shape[0], n // x.shape[0], local_only=True)
             rec = torch.stack([rows[L.STAT_MAX].double().sum(), rows[L.STAT_MIN].double().sum(),
                                torch.tensor(float(x.shape[0]), dtype=torch.float64, device=x.device)]).view(3, 1)
             if world > 1:           # sums and sample counts travel: the mean over the global batch

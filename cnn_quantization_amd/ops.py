@@ -202,13 +202,14 @@ def _groups(N, C, HW, aligned=None):
 
 
 _NHWC_WS = {'nhwc': 'cnnq_pc_nhwc_workspace', 'aciq_nhwc': 'cnnq_pc_aciq_nhwc_workspace',
-            'bcorr_nhwc': 'cnnq_pc_qdq_bcorr_nhwc_workspace', 'stats_nhwc': 'cnnq_pc_stats_nhwc_workspace'}
+            'bcorr_nhwc': 'cnnq_pc_qdq_bcorr_nhwc_workspace', 'stats_nhwc': 'cnnq_pc_stats_nhwc_workspace',
+            'rows': 'cnnq_rows_stats_workspace'}
 
 
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
-    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc', 'stats_nhwc': N = rows).  0 from the
-    library: no plan for the geometry."""
+    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc', 'stats_nhwc': N = rows; 'rows':
+    N = rows, C = their length).  0 from the library: no plan for the geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
@@ -2022,6 +2023,32 @@ def _mt_entropy(x, hist, mt, C, st, group=None, mom=None):
     return ent[0]
 
 
+def tensor_stats(x, rows=1, need_dev=True):
+    """The statistics of x viewed as [rows, numel / rows], rows contiguous and back to back - rows = 1: the whole tensor, the
+    per-tensor calibration table of statistic_manager.py:55-96; rows = N: the samples - for fp32 / bf16 / fp16 on the storage as
+    it lies: cnnq_rows_stats - pass A, the merge, and with need_dev pass B and its merge - one host call,
+    one cached workspace, 8 B/elem in fp32 and 4 in bf16 / fp16 for the full table.  Returns (stats [NSTAT, rows] f32, mom
+    [NMOM, rows] f64); rows B and KURT are zero without need_dev, the rectified sums are always there.  Taken as it is: a
+    contiguous tensor, and - the sums and extrema of a sample do not depend on its elements' order - a dense channels_last 4-D
+    tensor with rows in (1, N).  Anything else is copied by _dev_act, counted.  One GPU: the statistics are this tensor's."""
+    rows = int(rows)
+    keep = isinstance(x, torch.Tensor) and x.dim() == 4 and rows in (1, x.shape[0])
+    x = _dev_act_layout(x, 'x') if keep else _dev_act(x, 'x')
+    n = x.numel()
+    if rows < 1 or n == 0 or n % rows:
+        raise L.CnnqError('tensor_stats: %d elements do not make %d rows' % (n, rows))
+    length = n // rows
+    dt = _DTYPE_CODES[x.dtype]
+    st = _raw_stream(x.device.index)
+    stats = torch.empty((L.NSTAT, rows), dtype=torch.float32, device=x.device)
+    mom = torch.empty((L.NMOM, rows), dtype=torch.float64, device=x.device)
+    ws = _scratch(x, 'rows', _ws_bytes('rows', rows, length, 1, dt), st)
+    rc = L.load().cnnq_rows_stats(x.data_ptr(), dt, rows, length, int(bool(need_dev)), ws.data_ptr(), mom.data_ptr(), stats.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_rows_stats')
+    return stats, mom
+
+
 def tensor_row_stats(x, rows):
     """Per-row MIN/MAX (and friends) of x viewed as [rows, numel/rows]: the per-sample statistics
     of iq.py:510-517 (rows = batch) - the per-channel kernels with N = 1, C = rows."""
@@ -2079,10 +2106,14 @@ def kld_thresholds(x, rows=None, want_parts=False):
     """`-kld` calibration (inference/kld_threshold.py:6-84 per sample, statistic_manager.py:80-82):
     x viewed as [rows, numel/rows] (rows = batch samples) -> float64 tensor [rows, 3] =
     {optimal clipping threshold, its KL divergence, candidate index}; the `kld_th` statistic of
-    the batch is out[:, 0].max().  want_parts adds (hist [rows, 2001] int32, div [rows, 994])."""
+    the batch is out[:, 0].max().  want_parts adds (hist [rows, 2001] int32, div [rows, 994]).  float32 only."""
     lib = L.load()
-    x = _dev(x, 'x')
-    rows = int(rows if rows is not None else (x.shape[0] if x.dim() > 1 else 1))
+    if rows is None and isinstance(x, torch.Tensor):
+        rows = x.shape[0] if x.dim() > 1 else 1
+    # the histogram of a sample (or of the whole tensor) does not depend on the order of its elements, and a sample of a dense
+    # channels_last tensor is one contiguous block: rows = samples (or 1) read the storage as it is, the copy route's bits
+    x = _dev(x, 'x', keep_nhwc=isinstance(x, torch.Tensor) and x.dim() == 4 and rows is not None and int(rows) in (1, x.shape[0]))
+    rows = int(rows)
     length = x.numel() // rows
     rowmm = tensor_row_stats(x, rows)
     hist = torch.empty((rows, L.KLD_BINS), dtype=torch.int32, device=x.device)
@@ -2097,7 +2128,13 @@ def kld_thresholds(x, rows=None, want_parts=False):
 
 def row_sumsq(x, rows=None):
     """Per-sample sum of squares, the runtime distance measure of distance_stats.py:22-33
-    (`torch.sum(t**2, dim=-1)` on [N, -1]): the moments kernel with N = 1, C = rows (fp64 sums)."""
+    (`torch.sum(t**2, dim=-1)` on [N, -1]): the moments kernel with N = 1, C = rows (fp64 sums) for a contiguous float32
+    tensor; a bf16 / fp16 tensor, and a dense channels_last one with rows = its samples, take tensor_stats where they lie."""
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.dim() > 0:
+        n = int(rows if rows is not None else x.shape[0])
+        if x.dtype in _HALF_DTYPES or (x.dtype == torch.float32 and _NHWC and _layout(x) == 'nhwc' and n == x.shape[0]):
+            # bf16 / fp16, and the samples of a dense channels_last tensor: the flat-row kernels on the storage as it lies
+            return tensor_stats(x, n, need_dev=False)[1][L.MOM_SUMSQ].to(torch.float32)
     x = _dev(x, 'x')
     rows = int(rows if rows is not None else x.shape[0])
     _, mom = pc_stats(x, 1, rows, x.numel() // rows, local_only=True)

@@ -724,6 +724,33 @@ int cnnq_pc_route_stats_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, i
 int cnnq_pc_stats_nhwc(const void* x, int dtype, int64_t R, int64_t C, int need_b, int need_kurt, int need_relu, void* ws,
                        double* mom, float* stats, void* stream);
 
+/* The statistics of FEW, VERY LONG rows over flat storage - the per-tensor calibration table of statistic_manager.py:55-96
+ * (rows = 1: the whole tensor) and the per-sample sums of squares of distance_stats.py:22-33 (rows = N: the samples) - for fp32 /
+ * bf16 / fp16 elements, on the storage as it lies: x is viewed as [rows][len], every row contiguous and the rows back to back.
+ * Whole-tensor and per-sample sums and extrema do not depend on the order of the elements and a sample of a dense channels_last
+ * tensor is one contiguous block, so one reduction serves both layouts: no layout copy, no upcast, x read once per pass (8 B/elem
+ * in fp32, 4 in bf16 / fp16 for the full table).  A row is cut into pieces of W elements (the widest of 16 / 8 / 4 / 2 bytes, or
+ * one element, that divides len * sizeof(element) and x's alignment: every (rows, len, alignment) has a route) and into S chunks
+ * of consecutive pieces, one 256-lane workgroup per (row, chunk); the sums are added in an order fixed by (rows, len, dtype,
+ * alignment) alone: run after run the same bits, no atomics.  Promised: rows MIN / MAX exact (a NaN element makes them NaN),
+ * every other row within the statistics tier of fp64 that cnnq_pc_stats_single keeps.  All offsets are 64 bits.
+ * cnnq_rows_stats_workspace: bytes of `ws` - doubles part[S][CNNQ_NMOM][rows], mom[CNNQ_NMOM][rows], part2[S][CNNQ_NDEV][rows] for
+ * the largest S over the piece widths (0 on bad arguments).
+ * cnnq_rows_stats_route (host only, nothing enqueued): out = {elements per load W, chunks per row S, pieces per chunk, 1 - the row
+ * has at most 4096 elements and is summed in fp64 element by element}; align_bytes: the power of two that divides x (at least the
+ * element size; <= 16 is what matters). */
+size_t cnnq_rows_stats_workspace(int64_t rows, int64_t len, int dtype);
+int cnnq_rows_stats_route(int64_t rows, int64_t len, int dtype, int align_bytes, int32_t out[4]);
+/* The table behind ONE call: pass A (all seven moment rows, the rectified sums included) -> cnnq_pc_combine(G = S, C = rows,
+ * has_relu = 1) (-> pass B -> cnnq_pc_combine_dev(want_kurt = 1), when need_dev), two or four launches.  stats[CNNQ_NSTAT][rows]
+ * is written completely: rows B and KURT are zero without need_dev.  mom[CNNQ_NMOM][rows]: the merged moment record, may be NULL
+ * (kept in ws).  ws: cnnq_rows_stats_workspace bytes, 8-byte aligned.  A dtype outside cnnq_dtype, rows < 1, len < 1, a NULL x / ws /
+ * stats, a misaligned ws / mom or an x not aligned to its element size returns CNNQ_EINVAL; 2^31 rows, a chunk of 2^31 pieces or
+ * byte offsets beyond 63 bits CNNQ_ERANGE - before anything touches the device.  Re-entrant, allocates nothing, no host
+ * synchronisation, graph-capturable. */
+int cnnq_rows_stats(const void* x, int dtype, int64_t rows, int64_t len, int need_dev, void* ws, double* mom, float* stats,
+                    void* stream);
+
 /* Config 5 - mid-tread quantization with per-channel bin allocation, and the histogram of its codes for the entropy - on dense
  * channels_last activations.  As for config 3 the per-channel sums are added in an order fixed by (R, C, dtype, alignment)
  * alone, so `stats` is promised within the statistics tier of fp64 (MIN / MAX exact), not equal to the NCHW chain's.  Given
