@@ -148,6 +148,11 @@ SIGNATURES = {
     'cnnq_rows_stats_workspace': (ctypes.c_size_t, [_L, _L, _I]),
     'cnnq_rows_stats_route': (_I, [_L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
     'cnnq_rows_stats': (_I, [_P, _I, _L, _L, _I, _P, _P, _P, _P]),
+    'cnnq_flat_qdq': (_I, [_P, _P, _I, _L, _P, _P]),
+    'cnnq_flat_midtread_qdq': (_I, [_P, _P, _I, _L, _P, _P]),
+    'cnnq_pt_clip_workspace': (ctypes.c_size_t, [_L, _I]),
+    'cnnq_pt_clip_qdq': (_I, [_P, _P, _I, _L, ctypes.POINTER(ParamsCfg), _P, _P, _P, _P, _P]),
+    'cnnq_pt_midtread': (_I, [_P, _P, _I, _L, ctypes.c_double, _I, _P, _I, _P, _P, _P, _P]),
     'cnnq_pc_route_midtread_nhwc': (_I, [_L, _L, _I, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
     'cnnq_pc_midtread_qdq_nhwc': (_I, [_P, _P, _I, _L, _L, _P, _P, _P]),
     'cnnq_pc_midtread_nhwc': (_I, [_P, _P, _I, _L, _L, ctypes.c_double, _I, _P, _I, _P, _P, _P, _P, _P]),

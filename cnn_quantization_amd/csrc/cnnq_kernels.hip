@@ -59,6 +59,7 @@
 #include "cnnq_nhwc_packed.hip.h"
 #include "cnnq_qerr.hip.h"
 #include "cnnq_rows.hip.h"
+#include "cnnq_flat.hip.h"
 
 namespace {
 
@@ -2194,6 +2195,67 @@ int cnnq_rows_stats(const void* x, int dtype, int64_t rows, int64_t len, int nee
         hipLaunchKernelGGL((k_rows_absdev<typename P::T, P::W>), rows_grid(g), dim3(TPB), 0, st, xr, g, stats, a.part2);
     });
     if (!rc) rc = cnnq_pc_combine_dev(a.part2, g.S, rows, rec, 1, nullptr, stats, stream);
+    return rc;
+}
+
+
+// ---- per-tensor clipping and mid-tread over flat storage (cnnq_flat.hip.h): x and y [n], fp32 / bf16 / fp16 ---------------------
+// What every entry point of the family refuses before anything touches the device
+static int flat_check(const void* x, const void* y, int dtype, int64_t n) {
+    if (!dtype_ok(dtype) || n < 1 || !x || !y || x == y) return CNNQ_EINVAL;
+    if (misaligned(x, (uintptr_t)cl_esize(dtype)) || misaligned(y, (uintptr_t)cl_esize(dtype))) return CNNQ_EINVAL;
+    if (n > (INT64_MAX >> 3)) return CNNQ_ERANGE;
+    return flat_blocks(n, flat_piece(cl_esize(dtype), h_align(x, y))) >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
+}
+// the launch of k_flat_qdq (midtread = false) or k_flat_midtread on a checked tensor
+static int flat_launch(bool midtread, const void* x, void* y, int dtype, int64_t n, const float* tab, void* stream) {
+    const int w = flat_piece(cl_esize(dtype), h_align(x, y));
+    const dim3 grid((unsigned)flat_blocks(n, w));
+    return cl_launch(dtype, w, x, y, [&](auto pc, auto* xr, auto* yr) {
+        using P = decltype(pc);
+        if (midtread) hipLaunchKernelGGL((k_flat_midtread<typename P::T, P::W>), grid, dim3(TPB), 0, hs(stream), xr, yr, n, tab);
+        else hipLaunchKernelGGL((k_flat_qdq<typename P::T, P::W>), grid, dim3(TPB), 0, hs(stream), xr, yr, n, tab);
+    });
+}
+
+int cnnq_flat_qdq(const void* x, void* y, int dtype, int64_t n, const float* qp, void* stream) {
+    if (const int rc = flat_check(x, y, dtype, n)) return rc;
+    if (!qp) return CNNQ_EINVAL;
+    return flat_launch(false, x, y, dtype, n, qp, stream);
+}
+
+int cnnq_flat_midtread_qdq(const void* x, void* y, int dtype, int64_t n, const float* mt, void* stream) {
+    if (const int rc = flat_check(x, y, dtype, n)) return rc;
+    if (!mt) return CNNQ_EINVAL;
+    return flat_launch(true, x, y, dtype, n, mt, stream);
+}
+
+// ws of cnnq_pt_clip_qdq / cnnq_pt_midtread: the records of cnnq_rows_stats on one row of n elements
+size_t cnnq_pt_clip_workspace(int64_t n, int dtype) { return cnnq_rows_stats_workspace(1, n, dtype); }
+
+// iq.py:353-357 in one host call: the whole-tensor table (pass B only where the clipping reads b: Laplace), the parameters of
+// one channel with delta = the range itself, the flat Q/DQ
+int cnnq_pt_clip_qdq(const void* x, void* y, int dtype, int64_t n, const cnnq_params_cfg* cfg, void* ws, float* stats, float* qp, float* diag,
+                     void* stream) {
+    if (const int rc = flat_check(x, y, dtype, n)) return rc;
+    if (!cfg || !ws || !stats || !qp || misaligned(ws, 8)) return CNNQ_EINVAL;
+    if (check_cfg(cfg) || cfg->clip == 0 || cfg->bit_alloc) return CNNQ_EINVAL;
+    cnnq_params_cfg c = *cfg;
+    c.direct_range = 1;
+    int rc = cnnq_rows_stats(x, dtype, 1, n, c.clip == 1, ws, nullptr, stats, stream);
+    if (!rc) rc = cnnq_pc_params(stats, 1, &c, qp, diag, stream);
+    if (!rc) rc = flat_launch(false, x, y, dtype, n, qp, stream);
+    return rc;
+}
+
+// iq.py:158-168 without -pcq_a in one host call: the whole-tensor table with b, step size and clamp bounds of one channel, the flat pass
+int cnnq_pt_midtread(const void* x, void* y, int dtype, int64_t n, double target, int sym, const double* tables, int ntab, void* ws,
+                     float* stats, float* mt, void* stream) {
+    if (const int rc = flat_check(x, y, dtype, n)) return rc;
+    if (!tables || ntab < 2 || !ws || !stats || !mt || misaligned(ws, 8) || !(target - target == 0.)) return CNNQ_EINVAL;
+    int rc = cnnq_rows_stats(x, dtype, 1, n, 1, ws, nullptr, stats, stream);
+    if (!rc) rc = cnnq_pc_midtread_params(stats, 1, target, 1, sym, tables, ntab, mt, stream);
+    if (!rc) rc = flat_launch(true, x, y, dtype, n, mt, stream);
     return rc;
 }
 

@@ -209,7 +209,7 @@ _NHWC_WS = {'nhwc': 'cnnq_pc_nhwc_workspace', 'aciq_nhwc': 'cnnq_pc_aciq_nhwc_wo
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
     arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc', 'stats_nhwc': N = rows; 'rows':
-    N = rows, C = their length).  0 from the library: no plan for the geometry."""
+    N = rows, C = their length; 'pt_clip': N = elements).  0 from the library: no plan for the geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
@@ -219,6 +219,10 @@ def _ws_bytes(kind, N, C, HW, arg=0):
             nbytes = getattr(lib, fn)(N, C, arg)
             if nbytes == 0:
                 raise L.CnnqError('%s(%d, %d, %d): bad arguments' % (fn, N, C, arg))
+        elif kind == 'pt_clip':
+            nbytes = lib.cnnq_pt_clip_workspace(N, arg)
+            if nbytes == 0:
+                raise L.CnnqError('cnnq_pt_clip_workspace(%d, %d): bad arguments' % (N, arg))
         elif kind == 'aciq':
             nbytes = lib.cnnq_pc_aciq_workspace(N, C, HW, arg)
         else:
@@ -2047,6 +2051,82 @@ def tensor_stats(x, rows=1, need_dev=True):
     if rc:
         L.check(rc, 'cnnq_rows_stats')
     return stats, mom
+
+
+def _flat_x(x, what):
+    """x as the per-tensor entry points take it: an fp32 / bf16 / fp16 tensor on the current device whose storage is its elements
+    back to back - contiguous, or 4-D and dense channels_last.  Anything else raises: no copy is made here."""
+    if not isinstance(x, torch.Tensor):
+        raise L.CnnqError('%s: x must be a tensor' % what)
+    if x.dtype not in _ACT_DTYPES:
+        raise L.CnnqError('%s: x must be float32, bfloat16 or float16, got %s' % (what, x.dtype))
+    if _layout(x) == 'copy' or x.numel() == 0:             # shape and strides only
+        raise L.CnnqError('%s: x must be a non-empty contiguous or dense channels_last tensor (no copy is made here)' % what)
+    if not x.is_cuda:
+        raise L.CnnqError('%s: x must be a CUDA/HIP tensor (there is no CPU path)' % what)
+    if x.device.index != torch.cuda.current_device():
+        raise L.CnnqError('%s: x is on %s but the current device is cuda:%d' % (what, x.device, torch.cuda.current_device()))
+    return x.detach() if x.requires_grad else x
+
+
+def clip_qdq_tensor(x, num_bits, positive=False, clip='laplace', stats=None, out=None, want_parts=False):
+    """Per-tensor clipping (iq.py:353-357: ACIQ layer-wise - 'laplace', 'gaus' or '<p>std' with scalar statistics, delta the range
+    itself, no bit allocation) of an fp32 / bf16 / fp16 tensor on the storage as it lies: the result does
+    not depend on the elements' order, so a contiguous tensor and a dense channels_last 4-D one are read as they are - no upcast,
+    no layout copy; anything else raises.  Dynamic: cnnq_pt_clip_qdq - the whole-tensor statistics of tensor_stats, the
+    parameters, the flat Q/DQ - one host call, one cached workspace.  With `stats` ([NSTAT, 1], -sm use): pc_params on that
+    table and cnnq_flat_qdq.  y has x's dtype, shape and strides; want_parts: (y, dict(stats, qp, diag)).  One GPU: the
+    statistics are this tensor's."""
+    x = _flat_x(x, 'clip_qdq_tensor')
+    cfg = _params_cfg(num_bits, positive, clip, False, False, None, True, True)
+    if cfg.clip == 0:
+        raise L.CnnqError("clip_qdq_tensor: clip must be 'laplace', 'gaus' or '<p>std', got %r" % (clip,))
+    if stats is not None and not _is_table(stats, torch.float32, (L.NSTAT, 1), x.device):
+        raise L.CnnqError('clip_qdq_tensor: stats must be a contiguous float32 [%d, 1] device table' % L.NSTAT)
+    y = _out_like(x, out)
+    lib = L.load()
+    n, dt, st = x.numel(), _DTYPE_CODES[x.dtype], _raw_stream(x.device.index)
+    if stats is not None:
+        qp, diag = pc_params(stats, num_bits, positive, clip, direct_range=True)
+        rc = lib.cnnq_flat_qdq(x.data_ptr(), y.data_ptr(), dt, n, qp.data_ptr(), st)
+        if rc:
+            L.check(rc, 'cnnq_flat_qdq')
+        return _result(y, parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
+    nbytes = _ws_bytes('pt_clip', n, 1, 1, dt)
+    if want_parts:
+        tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, 1, dtype=torch.float32, device=x.device)
+        ws, tp = _scratch(x, 'pt_clip', nbytes, st).data_ptr(), tabs.data_ptr()
+    else:
+        # the tables nobody outside the call reads follow the records in the cached workspace
+        ws = _scratch(x, 'pt_clip', nbytes + (L.NSTAT + L.NQP + L.NDIAG) * 4, st).data_ptr()
+        tp = ws + nbytes
+    rc = lib.cnnq_pt_clip_qdq(x.data_ptr(), y.data_ptr(), dt, n, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * 4, tp + (L.NSTAT + L.NQP) * 4, st)
+    if rc:
+        L.check(rc, 'cnnq_pt_clip_qdq')
+    return _result(y, parts=dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:]) if want_parts else None)
+
+
+def mid_tread_qdq_tensor(x, target, sym, out=None, want_parts=False):
+    """Per-tensor mid-tread quantization with clipping (iq.py:158-168 without -pcq_a: the whole tensor is one channel) of an fp32 /
+    bf16 / fp16 tensor on the storage as it lies, taken and refused as clip_qdq_tensor takes and refuses:
+    cnnq_pt_midtread - the whole-tensor statistics, step size and clamp bounds, the flat pass - one host call, one cached
+    workspace.  No entropy: the per-tensor branch discards it.  y has x's dtype, shape and strides; want_parts: (y, dict(stats, mt))."""
+    x = _flat_x(x, 'mid_tread_qdq_tensor')
+    y = _out_like(x, out)
+    n, dt, st = x.numel(), _DTYPE_CODES[x.dtype], _raw_stream(x.device.index)
+    tabs = _midtread_tables(x.device)
+    nbytes = _ws_bytes('pt_clip', n, 1, 1, dt)
+    if want_parts:
+        out_tabs = torch.empty(L.NSTAT + L.NMT, 1, dtype=torch.float32, device=x.device)
+        ws, tp = _scratch(x, 'pt_clip', nbytes, st).data_ptr(), out_tabs.data_ptr()
+    else:
+        ws = _scratch(x, 'pt_clip', nbytes + (L.NSTAT + L.NMT) * 4, st).data_ptr()
+        tp = ws + nbytes
+    rc = L.load().cnnq_pt_midtread(x.data_ptr(), y.data_ptr(), dt, n, float(target), int(bool(sym)), _ptr(tabs), tabs.shape[1], ws, tp,
+                                   tp + L.NSTAT * 4, st)
+    if rc:
+        L.check(rc, 'cnnq_pt_midtread')
+    return _result(y, parts=dict(stats=out_tabs[:L.NSTAT], mt=out_tabs[L.NSTAT:]) if want_parts else None)
 
 
 def tensor_row_stats(x, rows):

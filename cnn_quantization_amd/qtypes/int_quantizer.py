@@ -102,7 +102,8 @@ class IntQuantizer:
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
         if (isinstance(tensor, torch.Tensor) and tensor.dtype in HALF_DTYPES
                 and not self._half_native(tensor, override_att, stat_id) and not self._nhwc_midtread(tensor, self._att(override_att))
-                and not self._nhwc_entropy(tensor, self._att(override_att))):
+                and not self._nhwc_entropy(tensor, self._att(override_att)) and not self._flat_clip(tensor, self._att(override_att))
+                and not self._flat_midtread(tensor, self._att(override_att)) and not self._flat_kld(tensor, self._att(override_att))):
             return upcast_fallback(self.__call__, tensor, id, tag, stat_id, override_att)
         if override_att is not None:
             orig_att = getattr(self, override_att[0])
@@ -200,6 +201,40 @@ class IntQuantizer:
                 and get('clipping') == 'no' and not get('pcq_w') and not get('mtd_quant') and not get('kld')
                 and not (get('bit_alloc_act') and get('num_bits') <= 4) and get('num_bits') <= 8 and _dense_nhwc(tensor)
                 and self.fuse_bcorr is None and self._one_gpu())
+
+    # The three per-tensor routes over flat storage.  One parameter set serves the whole tensor, so the element
+    # order does not matter: a contiguous bf16 / fp16 tensor and a dense channels_last tensor of any of the three dtypes are
+    # quantized where they lie.  A contiguous fp32 tensor keeps ops.act_qdq_per_channel(whole_tensor=True) / ops.mid_tread_qdq: its
+    # dynamic statistics differ from the flat rows' in the last bits.  Kept apart from _half_native for the reason above: tests pin it.
+    def _flat_tensor(self, tensor):
+        """On the device and either bf16 / fp16, contiguous or dense channels_last, or fp32 dense channels_last; not empty."""
+        if not getattr(tensor, 'is_cuda', False) or tensor.numel() == 0:
+            return False
+        if tensor.dtype in HALF_DTYPES:
+            return tensor.is_contiguous() or _dense_nhwc(tensor)
+        return tensor.dtype == torch.float32 and _dense_nhwc(tensor)
+
+    def _flat_clip(self, tensor, att=None):
+        """The per-tensor tail of gemmlowpClippingQuantize runs on ops.clip_qdq_tensor: the clipping branch where -pcq_a does not
+        apply, 'laplace', 'gaus' or '<p>std' (not 'mix': its candidates come from error columns), no mid-tread, no KLD, one GPU."""
+        get = att or self._att()
+        clip = get('clipping')
+        return (not get('kld') and not get('mtd_quant') and not (get('pcq_a') and _is_pc_act(tensor))
+                and (clip in ('laplace', 'gaus') or (isinstance(clip, str) and clip.endswith('std')))
+                and self._one_gpu() and self._flat_tensor(tensor))
+
+    def _flat_midtread(self, tensor, att=None):
+        """mid_tread_quantize_activation without -pcq_a runs on ops.mid_tread_qdq_tensor."""
+        get = att or self._att()
+        return (not get('kld') and bool(get('mtd_quant')) and get('clipping') != 'no' and not (get('pcq_a') and _is_pc_act(tensor))
+                and self._one_gpu() and self._flat_tensor(tensor))
+
+    def _flat_kld(self, tensor, att=None):
+        """gemmlowpKldQuantize needs no upcast: __gemmlowpQuantize__ hands a half tensor, contiguous or dense channels_last, to
+        ops.pt_qdq's half kernel as it is.  Nothing is routed by this: it only keeps __call__ from upcasting."""
+        get = att or self._att()
+        return (bool(get('kld')) and getattr(tensor, 'is_cuda', False) and tensor.dtype in HALF_DTYPES
+                and (tensor.is_contiguous() or _dense_nhwc(tensor)))
 
     def _bcorr_nhwc(self, tensor, table, clip_type, prior_b):
         """The _nhwc_bcorr route: the parameters of the calibration table, then Q/DQ and correction where the tensor lies."""
@@ -317,6 +352,9 @@ class IntQuantizer:
             rows = {L.STAT_MIN: ('min', 'mean'), L.STAT_MAX: ('max', 'mean'), L.STAT_MEAN: ('mean', 'mean'),
                     L.STAT_B: ('b', 'mean'), L.STAT_STD: ('std', 'mean')}
             table = self._stats_table(stat_id, 1, tensor.device, rows)
+        if self._flat_clip(tensor, self._att(('clipping', clip_type))):
+            # half or dense channels_last: quantized where it lies, the result keeps dtype and layout
+            return ops.clip_qdq_tensor(tensor, self.num_bits, positive=self._positive, clip=clip_type, stats=table)
         out = ops.act_qdq_per_channel(tensor, self.num_bits, positive=self._positive, clip=clip_type,
                                       bit_alloc=False, group=self.group, stats=table, whole_tensor=True)
         return out.view(tensor.shape)
@@ -423,6 +461,8 @@ class IntQuantizer:
         """iq.py:158-168."""
         if self.pcq_a and _is_pc_act(tensor):
             return self.mid_tread_quantize_activation_per_channel(tensor, id)
+        if self._flat_midtread(tensor):
+            return ops.mid_tread_qdq_tensor(tensor, self.bit_alloc_target_act, sym=not self._positive)
         out, _ = ops.mid_tread_qdq(tensor, self.bit_alloc_target_act, clip=True, sym=not self._positive,
                                    whole_tensor=True, group=self.group, want_entropy=self.measure_entropy)
         return out.view(tensor.shape)

@@ -751,6 +751,39 @@ int cnnq_rows_stats_route(int64_t rows, int64_t len, int dtype, int align_bytes,
 int cnnq_rows_stats(const void* x, int dtype, int64_t rows, int64_t len, int need_dev, void* ws, double* mom, float* stats,
                     void* stream);
 
+/* Per-tensor clipping (iq.py:353-357: gemmlowpClippingQuantize where -pcq_a does not apply - "ACIQ layer-wise") and per-tensor
+ * mid-tread quantization (iq.py:158-168) of fp32 / bf16 / fp16 elements over flat storage: x and y are n elements back to back.
+ * One parameter set serves the whole tensor and y[i] depends on x[i] alone, so a contiguous tensor and a dense channels_last one
+ * are the same call: no layout copy, no upcast, x read and y written once (8 B/elem in fp32, 4 in bf16 / fp16).  The arithmetic is
+ * the per-channel kernels': given the table, y is, bit for bit, what cnnq_pc_qdq (cnnq_pc_midtread_qdq with clip = 1) gives for
+ * N = 1, C = 1, HW = n on the same values - the IEEE divide, separate roundings, clamp before round, half to even; bf16 / fp16
+ * elements are upconverted exactly and the fp32 result is rounded to nearest-even once (a NaN stays a NaN, an fp16 overflow
+ * becomes inf): y == fp32_path(x.float()).to(x.dtype).  Elements go in pieces of 16 / 8 / 4 / 2 bytes (or one element), the widest
+ * the alignment x and y share allows; the length does not matter (the first lanes take the n % W tail).
+ * All of them return - before anything touches the device - CNNQ_EINVAL for a dtype outside cnnq_dtype, n < 1, a NULL required
+ * pointer, an x or y not aligned to its element size, x == y; CNNQ_ERANGE for byte offsets beyond 63 bits or a grid of 2^31
+ * workgroups.  Re-entrant, allocate nothing, no host synchronisation, graph-capturable.
+ * cnnq_flat_qdq: the table-driven pass, one launch; qp[CNNQ_NQP][1] as cnnq_pc_params writes it for C = 1 (direct_range = 1 for
+ *   the per-tensor branch: the kernel reads the three scalars and does not care).
+ * cnnq_flat_midtread_qdq: the same for mt[CNNQ_NMT][1] of cnnq_pc_midtread_params (C = 1, clip = 1): t = round(x / delta), the two
+ *   clamps, t * delta.  No histogram: the per-tensor branch discards the entropy. */
+int cnnq_flat_qdq(const void* x, void* y, int dtype, int64_t n, const float* qp, void* stream);
+int cnnq_flat_midtread_qdq(const void* x, void* y, int dtype, int64_t n, const float* mt, void* stream);
+/* The dynamic forms behind ONE call.  ws: cnnq_pt_clip_workspace(n, dtype) bytes (= cnnq_rows_stats_workspace(1, n, dtype); 0 on
+ * bad arguments), 8-byte aligned; stats[CNNQ_NSTAT][1] is an OUTPUT and is cnnq_rows_stats' table of the tensor, bit for bit.
+ * cnnq_pt_clip_qdq: cnnq_rows_stats(rows = 1, need_dev = the clipping reads b: cfg->clip == 1) -> cnnq_pc_params(C = 1, with
+ *   direct_range forced to 1: delta is the range itself, iq.py:357) -> the flat pass; three or five launches.  cfg->clip is 1, 2 or
+ *   3 (laplace / gaus / pstd * std); bit allocation does not apply per tensor (iq.py:236): clip == 0 or bit_alloc != 0 is
+ *   CNNQ_EINVAL, as is a cfg cnnq_pc_params refuses.  qp[CNNQ_NQP][1] out; diag[CNNQ_NDIAG][1] out, may be NULL.
+ * cnnq_pt_midtread: cnnq_rows_stats(rows = 1, need_dev = 1) -> cnnq_pc_midtread_params(C = 1, clip = 1) -> the flat pass, five
+ *   launches.  mt[CNNQ_NMT][1] out; tables: the (omega, alpha) tables [2][ntab] in device memory.  On top of the refusals above: a
+ *   NULL cfg / ws / stats / qp / mt / tables, ntab < 2, a misaligned ws or a target that is not finite - CNNQ_EINVAL. */
+size_t cnnq_pt_clip_workspace(int64_t n, int dtype);
+int cnnq_pt_clip_qdq(const void* x, void* y, int dtype, int64_t n, const cnnq_params_cfg* cfg, void* ws, float* stats, float* qp,
+                     float* diag, void* stream);
+int cnnq_pt_midtread(const void* x, void* y, int dtype, int64_t n, double target, int sym, const double* tables, int ntab, void* ws,
+                     float* stats, float* mt, void* stream);
+
 /* Config 5 - mid-tread quantization with per-channel bin allocation, and the histogram of its codes for the entropy - on dense
  * channels_last activations.  As for config 3 the per-channel sums are added in an order fixed by (R, C, dtype, alignment)
  * alone, so `stats` is promised within the statistics tier of fp64 (MIN / MAX exact), not equal to the NCHW chain's.  Given
