@@ -890,7 +890,7 @@ class entropy_batch:
     once) - the calls then take the per-tensor launch."""
 
     def __init__(self):
-        self.n, self.out, self.tables, self.st, self.mt, self.pending = 0, None, None, None, [], []
+        self.n, self.out, self.tables, self.st, self.key, self.mt, self.pending = 0, None, None, None, None, [], []
 
     def after(self, fn):
         """run fn() once the entropies of the block are there (IntQuantizer's logger calls: float(entropy) is a host read)"""
@@ -906,22 +906,31 @@ class entropy_batch:
         _ENT_BATCH = self._outer
         if exc[0] is None:
             self.flush()
+        else:
+            self._abandon()
         return False
+
+    def _abandon(self):
+        """The block raised: nothing is launched and no callback runs.  The table sets the block counted into are not zero, so
+        the stream's cache entry goes - the next block allocates zeroed ones (the allocator hands the old block out again on the
+        same stream only, behind the launches that still count into it)."""
+        if self.n:
+            _ENT_TABLES.pop(self.key, None)
+        self.n, self.out, self.tables, self.mt, self.pending = 0, None, None, [], []
 
     def slot(self, x, st):
         """(replica tables of this tensor, the 0-dim result) or None when no table set can be had (first use under a capture)"""
-        if self.st is None:
-            self.st = st
+        if self.st is not None and st != self.st:
+            raise L.CnnqError('entropy_batch: one stream per block')
+        if self.tables is None:             # (not `self.st is None`: add_midtread sets the stream too)
             key = (x.device.index, st)
-            self.tables = _ENT_TABLES.get(key)
-            if self.tables is None:
+            tables = _ENT_TABLES.get(key)
+            if tables is None:
                 if torch.cuda.is_current_stream_capturing():
-                    self.st = None
                     return None
                 words = L.load().cnnq_hist_replica_bytes() // 8
-                self.tables = _ENT_TABLES[key] = torch.zeros((ENT_BATCH_CAP, words), dtype=torch.int64, device=x.device)
-        elif st != self.st:
-            raise L.CnnqError('entropy_batch: one stream per block')
+                tables = _ENT_TABLES[key] = torch.zeros((ENT_BATCH_CAP, words), dtype=torch.int64, device=x.device)
+            self.st, self.tables, self.key = st, tables, key
         if self.n == ENT_BATCH_CAP:
             self.flush()
         if self.out is None:
@@ -932,8 +941,11 @@ class entropy_batch:
 
     def add_midtread(self, hist, mt, C, total, device):
         """the mid-tread path's histogram of one tensor (cnnq_midtread_entropy's arguments); returns the 0-dim result"""
+        st = _raw_stream(device.index)
         if self.st is None:
-            self.st = _raw_stream(device.index)
+            self.st = st
+        elif st != self.st:
+            raise L.CnnqError('entropy_batch: one stream per block')
         if len(self.mt) == 16:
             self._flush_midtread()
         if not self.mt:

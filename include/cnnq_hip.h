@@ -549,7 +549,9 @@ int cnnq_pc_bcorr_apply(float* y, int64_t N, int64_t C, int64_t HW, const float*
  *       quantized mean; clip == 0 (weights): range = max-min (sym) or max.  One workgroup.
  *   cnnq_pc_midtread_qdq     y = clamp(round(x/Delta[c]), c_min[c], c_max[c]) * Delta[c] in one pass;
  *       `codes` (optional) fp32 codes; `hist` (optional, zeroed by the caller,
- *       CNNQ_MT_HIST_WORDS(C) uint64 words) the code histogram.
+ *       CNNQ_MT_HIST_WORDS(C) uint64 words) the code histogram.  A NaN code (a NaN in x) is counted in
+ *       its channel's c_min counter, where torch.unique would keep every NaN apart: nothing in the
+ *       reference depends on either, and no test feeds one.
  *   cnnq_midtread_entropy    Shannon entropy of that histogram (equal clamp values merged). */
 int cnnq_pc_midtread_params(const float* stats, int64_t C, double target, int clip, int sym, const double* tables,
                             int ntab, float* mt, void* stream);

@@ -96,3 +96,80 @@ def test_the_quantizer_logs_after_the_block_in_layer_order(ops):
     assert [r[0] for r in a.rows] == [r[0] for r in b.rows] and len(b.rows) == len(xs)
     assert a.rows == b.rows
     assert all(torch.equal(u, v) for u, v in zip(ya, yb))
+
+
+# a shape whose mid-tread call takes the single launch: only that form defers its entropy to the block (the tests assert it did)
+MT_SINGLE = (8, 32, 14, 14)
+
+
+def _same(ref, got):
+    for (y0, e0), (y1, e1) in zip(ref, got):
+        assert torch.equal(y0, y1) and float(e0) == float(e1)
+
+
+def test_a_block_whose_first_tensor_is_mid_tread(ops):
+    """add_midtread() sets the block's stream as slot() does: the config 2 / 3 calls behind it still have to find their table sets"""
+    xs = [_x(20 + i, s) for i, s in enumerate([MT_SINGLE] + SHAPES[1:5])]
+    ref5 = [ops.mid_tread_qdq(x, 4, clip=True, sym=True, want_entropy=True) for x in xs]
+    ref2 = [ops.act_qdq_per_channel(x, 4, positive=bool(i & 1), want_entropy=True) for i, x in enumerate(xs)]
+    ref3 = [ops.act_qdq_per_channel(x, 4, clip='laplace', bit_alloc=True, want_entropy=True) for x in xs]
+    torch.cuda.synchronize()
+    with ops.entropy_batch() as eb:
+        got5 = [ops.mid_tread_qdq(xs[0], 4, clip=True, sym=True, want_entropy=True)]
+        assert len(eb.mt) == 1 and eb.n == 0
+        got2 = [ops.act_qdq_per_channel(x, 4, positive=bool(i & 1), want_entropy=True) for i, x in enumerate(xs)]
+        got3 = [ops.act_qdq_per_channel(x, 4, clip='laplace', bit_alloc=True, want_entropy=True) for x in xs]
+        got5 += [ops.mid_tread_qdq(x, 4, clip=True, sym=True, want_entropy=True) for x in xs[1:]]
+        assert eb.n > 0 and len(eb.mt) >= 1
+    torch.cuda.synchronize()
+    _same(ref5 + ref2 + ref3, got5 + got2 + got3)
+    st = ops._raw_stream(xs[0].device.index)
+    assert int(ops._ENT_TABLES[(xs[0].device.index, st)].abs().sum()) == 0
+
+
+def test_more_mid_tread_tensors_than_one_launch_takes(ops):
+    """19 tensors: cnnq_midtread_entropy_batch takes 16, so the block launches once in the middle and once at its end"""
+    xs = [_x(40 + i, MT_SINGLE) for i in range(19)]
+    ref = [ops.mid_tread_qdq(x, 4, clip=True, sym=bool(i & 1), want_entropy=True) for i, x in enumerate(xs)]
+    torch.cuda.synchronize()
+    with ops.entropy_batch() as eb:
+        got = [ops.mid_tread_qdq(x, 4, clip=True, sym=bool(i & 1), want_entropy=True) for i, x in enumerate(xs)]
+        assert len(eb.mt) == 3                                   # sixteen went out when the seventeenth came
+    torch.cuda.synchronize()
+    _same(ref, got)
+    assert len({float(e) for _, e in ref}) > 4                   # (different tensors: a result in the wrong slot would show)
+
+
+def test_a_block_that_raises_leaves_the_table_cache_as_documented(ops):
+    """The block's exception reaches the caller unchanged, nothing is launched for the block and no after() callback runs; the table
+    sets it counted into are not handed, non-zero, to the next block on the stream."""
+    xs = [_x(60 + i, s) for i, s in enumerate(SHAPES[1:4])]
+    assert tuple(xs[2].shape) == MT_SINGLE
+    ref = [ops.act_qdq_per_channel(x, 4, want_entropy=True) for x in xs]
+    ref5 = ops.mid_tread_qdq(xs[2], 4, clip=True, sym=True, want_entropy=True)
+    torch.cuda.synchronize()
+    dev = xs[0].device.index
+    key = (dev, ops._raw_stream(dev))
+    ran, boom = [], RuntimeError('the block failed')
+    with pytest.raises(RuntimeError) as caught:
+        with ops.entropy_batch() as eb:
+            for x in xs:
+                ops.act_qdq_per_channel(x, 4, want_entropy=True)
+            ops.mid_tread_qdq(xs[2], 4, clip=True, sym=True, want_entropy=True)
+            eb.after(lambda: ran.append('callback'))
+            assert eb.n == len(xs) and len(eb.mt) == 1           # (the launches counted into the block's table sets)
+            raise boom
+    assert caught.value is boom
+    assert ran == [] and (eb.n, eb.mt, eb.pending) == (0, [], [])
+    assert ops._ENT_BATCH is None
+    torch.cuda.synchronize()
+    tables = ops._ENT_TABLES.get(key)
+    assert tables is None or int(tables.abs().sum()) == 0
+    with ops.entropy_batch():
+        got = [ops.act_qdq_per_channel(x, 4, want_entropy=True) for x in xs]
+        got5 = ops.mid_tread_qdq(xs[2], 4, clip=True, sym=True, want_entropy=True)
+    torch.cuda.synchronize()
+    _same(ref + [ref5], got + [got5])
+    assert ran == []
+    assert int(ops._ENT_TABLES[key].abs().sum()) == 0
+    assert int(ops._hist_replicas(xs[0], key[1]).abs().sum()) == 0
