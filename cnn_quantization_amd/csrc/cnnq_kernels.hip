@@ -50,6 +50,7 @@
 #include "cnnq_plan.hip.h"
 #include "cnnq_kld.hip.h"
 #include "cnnq_half.hip.h"
+#include "cnnq_half_stats.hip.h"
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_nhwc_collect.hip.h"
@@ -1655,6 +1656,90 @@ int cnnq_pc_minmax_local_dt(const void* x, int dtype, int64_t N, int64_t C, int6
     const int rc = h_minmax(x, dtype, N, C, HW, pmm, &S, (hipStream_t)stream);
     if (rc) return rc;
     return cnnq_pc_minmax_reduce(pmm, S, C, local, stream);
+}
+
+// ---- `-sm collect` on contiguous bf16 / fp16 activations (cnnq_half_stats.hip.h) ------------------------------------------------
+// What the three entry points derive from (N, C, HW) after their argument checks: the fp32 entry points' geometry limits, then
+// the batch splits S and the column splits cs of the two statistics launches (S * cs records per channel)
+static int h_stats_plan(int64_t N, int64_t C, int64_t HW, int* S, int* cs) {
+    const int rc = cnnq_pc_groups(N, C, HW, 0);
+    if (rc <= 0) return g_error(rc);
+    h_stats_splits(N, C, HW, S, cs);
+    return 0;
+}
+static int h_stats_check(int64_t N, int64_t C, int64_t HW, int dtype) { return (!dtype_ok(dtype) || N < 1 || C < 1 || HW < 1) ? CNNQ_EINVAL : 0; }
+
+// ws, doubles: part[G][CNNQ_NMOM][C], mom[CNNQ_NMOM][C], part2[G][CNNQ_NDEV][C] (AciqWs without the table) with G = S * cs; fp32:
+// what cnnq_pc_stats takes at either alignment
+size_t cnnq_pc_stats_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype) {
+    if (h_stats_check(N, C, HW, dtype)) return 0;
+    if (dtype == CNNQ_DTYPE_F32) {
+        const size_t a = cnnq_pc_stats_workspace(N, C, HW, 1), b = cnnq_pc_stats_workspace(N, C, HW, 0);
+        return a > b ? a : b;
+    }
+    int S, cs;
+    if (h_stats_plan(N, C, HW, &S, &cs)) return 0;
+    return AciqWs::bytes((size_t)S * cs, C, false);
+}
+
+// Which launches cnnq_pc_stats_dt makes for this geometry (host only): out = {piece width W, batch splits S, column splits,
+// 1 - the native launches / 0 - a class of layer that did not win against the upcast route and stays there: h_stats_native, with
+// the figures next to the rule}.  fp32: {0, the records of cnnq_pc_stats' own plan, 1, 1}.  cnnq_pc_stats_dt itself runs every class.
+int cnnq_pc_route_stats_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int32_t out[4]) {
+    if (h_stats_check(N, C, HW, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
+    int S, cs;
+    if (const int rc = h_stats_plan(N, C, HW, &S, &cs)) return rc;
+    if (dtype == CNNQ_DTYPE_F32) {
+        out[0] = 0;
+        out[1] = cnnq_pc_groups(N, C, HW, align_bytes >= 16);
+        out[2] = 1;
+    } else {
+        out[0] = h_piece(HW, (uintptr_t)align_bytes, 0);
+        out[1] = S;
+        out[2] = cs;
+    }
+    out[3] = h_stats_native(N, C, HW, dtype);
+    return 0;
+}
+
+// smpc.py:45-79 on x[N][C][HW] of bf16 / fp16: k_h_moments -> k_combine(has_relu) (-> k_h_absdev on the merged table ->
+// k_combine_dev(want_kurt); need_b or need_kurt), two or four launches
+int cnnq_pc_stats_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, int need_b, int need_kurt, int need_relu, void* ws,
+                     double* mom, float* stats, void* stream) {
+    if (h_stats_check(N, C, HW, dtype)) return CNNQ_EINVAL;
+    if (!x || !ws || !stats || misaligned(ws, 8) || misaligned(mom, 8)) return CNNQ_EINVAL;
+    if (dtype == CNNQ_DTYPE_F32)
+        return cnnq_pc_stats(static_cast<const float*>(x), N, C, HW, need_b, need_kurt, need_relu, ws, mom, stats, stream);
+    if (misaligned(x, 2)) return CNNQ_EINVAL;
+    HGeo g;
+    if (const int rc = h_stats_plan(N, C, HW, &g.S, &g.cs)) return rc;
+    g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
+    const int w = h_piece(HW, (uintptr_t)x, 0);
+    g.ppr = (int)(HW / w);
+    const int G = g.S * g.cs;
+    const AciqWs a(ws, G, C);
+    double* rec = mom ? mom : a.mom;
+    const dim3 grid((unsigned)(C * G));
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+    hipStream_t st = hs(stream);
+    with_piece<false>(dtype, w, [&](auto pc) {
+        with_bool(need_relu != 0, [&](auto relu) {
+            using P = decltype(pc);
+            hipLaunchKernelGGL((k_h_moments<typename P::T, P::W, decltype(relu)::value>), grid, dim3(TPB), 0, st, xh, g, a.part);
+        });
+    });
+    int rc = launch_status();
+    if (!rc) rc = cnnq_pc_combine(a.part, G, C, need_relu ? 1 : 0, rec, stats, stream);
+    if (rc || !(need_b || need_kurt)) return rc;
+    with_piece<false>(dtype, w, [&](auto pc) {
+        with_bool(need_kurt != 0, [&](auto kurt) {
+            using P = decltype(pc);
+            hipLaunchKernelGGL((k_h_absdev<typename P::T, P::W, decltype(kurt)::value>), grid, dim3(TPB), 0, st, xh, g, stats, a.part2);
+        });
+    });
+    rc = launch_status();
+    if (!rc) rc = cnnq_pc_combine_dev(a.part2, G, C, rec, need_kurt ? 1 : 0, nullptr, stats, stream);
+    return rc;
 }
 
 int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream) {

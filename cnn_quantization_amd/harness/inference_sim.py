@@ -77,7 +77,8 @@ def build_parser():
     p.add_argument('--no-bn-folding', action='store_true')
     p.add_argument('--dtype', default='float32', choices=('float32', 'bfloat16', 'float16'),
                    help='element type of the model and its activations; BN folding and the synthetic input are computed in '
-                        'float32 and then cast (configs 1 and 2 quantize bf16 / fp16 natively, every other path upcasts)')
+                        'float32 and then cast (configs 1 and 2 quantize bf16 / fp16 natively and -sm collect reads them as '
+                        'they are, every other path upcasts)')
     p.add_argument('--channels-last', action='store_true',
                    help='run the model and its input in the channels_last (NHWC) memory format, after BN folding, --dtype and '
                         'the weight quantization (configs 1, 2, 3 and - with -mtq, with or without -me - 5 quantize dense '

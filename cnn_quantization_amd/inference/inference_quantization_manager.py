@@ -35,7 +35,7 @@ from ..qtypes import DummyQuantizer, int_quantizer
 from ..qtypes.int_quantizer import upcast_fallback
 from ..utils.misc import Singleton
 from .statistic_manager import StatisticManager, collects_native_flat
-from .statistic_manager_perchannel import StatisticManagerPerChannel, collects_native_nhwc
+from .statistic_manager_perchannel import StatisticManagerPerChannel, collects_native_half, collects_native_nhwc
 
 FUSED_RELU_ARCHS = ('alexnet', 'vgg16', 'vgg16_bn', 'inception_v3')
 
@@ -101,6 +101,10 @@ def _route(layer, out, out_id, tag, *, shifted=False, half_range=False, collect_
             kw.update(half_range=half_range, err_settings=qm.err_settings(out_id, '' if shifted else tag, half_range))
         if isinstance(qm.stats_manager, StatisticManagerPerChannel) and collects_native_nhwc(qm.stats_manager, out, force_global):
             # a dense channels_last output the manager reads where it lies, in its own dtype: nothing to upcast
+            qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, **kw)
+            return out
+        if isinstance(qm.stats_manager, StatisticManagerPerChannel) and collects_native_half(qm.stats_manager, out, force_global):
+            # a contiguous bf16 / fp16 output the manager reads in its own dtype: nothing to upcast
             qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, **kw)
             return out
         if isinstance(qm.stats_manager, StatisticManager) and collects_native_flat(qm.stats_manager, out):

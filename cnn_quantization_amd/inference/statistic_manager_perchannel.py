@@ -10,7 +10,9 @@ device (cnnq_pc_moments + cnnq_pc_absdev) and ONE device->host copy of a [7, C] 
 of a transposed copy, nine full-tensor reductions and seven synchronising copies
 (smpc.py:51-79,112).
 A dense channels_last activation of fp32 / bf16 / fp16 is read where it lies (ops.pc_stats_nhwc, DESIGN.md section 18: no
-layout copy, no upcast) whenever collects_native_nhwc says so; every other tensor takes the NCHW kernels on a contiguous copy.
+layout copy, no upcast) whenever collects_native_nhwc says so, a contiguous bf16 / fp16 activation in its own dtype
+(ops.pc_stats_half) whenever collects_native_half does; every other tensor takes the NCHW kernels on a
+contiguous float32 copy.
 
 `collect_err=True` adds the six clipping-error columns the reference declares (smpc.py:24-32: mse_lowp, mse_gaus,
 mse_laplace, cos_lowp, cos_gaus, cos_laplace; formulas smpc.py:80-100) - the columns `-sm use -c mix` (iq.py:310-323)
@@ -61,6 +63,22 @@ def collects_native_nhwc(manager, tensor, force_global_min_max=False):
     return ops._stats_nhwc_native(tensor.numel() // tensor.shape[1], tensor.shape[1], tensor.dtype)
 
 
+def collects_native_half(manager, tensor, force_global_min_max=False):
+    """Whether save_tensor_stats takes this tensor in its own dtype (ops.pc_stats_half: no upcast, no fp32 temporary): a contiguous
+    bf16 / fp16 CUDA activation with a spatial extent, one process and no forced exchange, no error columns, the extrema of the
+    whole batch (batch_avg off, or the caller forces them), and a class of layer the route function keeps native.  Shape, strides
+    and attributes only: nothing touches the device."""
+    if manager.collect_err or (manager.batch_avg and not force_global_min_max):
+        return False
+    if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype in ops._HALF_DTYPES and tensor.dim() == 4
+            and tensor.numel() > 0 and tensor.is_contiguous() and (tensor.shape[2] > 1 or tensor.shape[3] > 1)):
+        return False
+    if D.world_size(manager.group) > 1 or D.forced_exchange():
+        return False
+    N, C, HW = ops.geometry(tensor)
+    return ops._stats_half_native(N, C, HW, tensor.dtype)
+
+
 class StatisticManagerPerChannel(metaclass=Singleton):
     def __init__(self, folder, load_stats, stats=('max', 'min', 'std', 'mean', 'kurtosis', 'b', 'std_pos'),
                  batch_avg=False, collect_err=False, group=None, err_settings=None):
@@ -96,6 +114,11 @@ class StatisticManagerPerChannel(metaclass=Singleton):
         if collects_native_nhwc(self, tensor, force_global_min_max):
             # dense channels_last, fp32 / bf16 / fp16: the table from the storage as it lies
             table, _ = ops.pc_stats_nhwc(tensor.detach(), need_b='b' in self.stats_names, need_kurt='kurtosis' in self.stats_names,
+                                         need_relu='std_pos' in self.stats_names)
+            return self._record(id, table)
+        if collects_native_half(self, tensor, force_global_min_max):
+            # contiguous bf16 / fp16: the table from the tensor in its own dtype
+            table, _ = ops.pc_stats_half(tensor.detach(), need_b='b' in self.stats_names, need_kurt='kurtosis' in self.stats_names,
                                          need_relu='std_pos' in self.stats_names)
             return self._record(id, table)
         N, C = tensor.shape[0], tensor.shape[1]

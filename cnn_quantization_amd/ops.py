@@ -209,7 +209,7 @@ _NHWC_WS = {'nhwc': 'cnnq_pc_nhwc_workspace', 'aciq_nhwc': 'cnnq_pc_aciq_nhwc_wo
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
     arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc', 'stats_nhwc': N = rows; 'rows':
-    N = rows, C = their length; 'pt_clip': N = elements).  0 from the library: no plan for the geometry."""
+    N = rows, C = their length; 'pt_clip': N = elements; 'stats_half': the dtype code).  0 from the library: no plan for the geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
@@ -225,6 +225,10 @@ def _ws_bytes(kind, N, C, HW, arg=0):
                 raise L.CnnqError('cnnq_pt_clip_workspace(%d, %d): bad arguments' % (N, arg))
         elif kind == 'aciq':
             nbytes = lib.cnnq_pc_aciq_workspace(N, C, HW, arg)
+        elif kind == 'stats_half':
+            nbytes = lib.cnnq_pc_stats_dt_workspace(N, C, HW, arg)
+            if nbytes == 0:
+                L.check(min(lib.cnnq_pc_groups(N, C, HW, 0), -1), 'cnnq_pc_stats_dt_workspace(%d,%d,%d,%d)' % (N, C, HW, arg))
         else:
             nbytes = lib.cnnq_pc_minmax_qdq_workspace(N, C, HW) if kind == 'cfg2' else lib.cnnq_pc_stats_workspace(N, C, HW, arg)
             if nbytes == 0:
@@ -432,6 +436,55 @@ def pc_stats_nhwc(x, need_b=False, need_kurt=False, need_relu=False):
                                      ws.data_ptr(), mom.data_ptr(), stats.data_ptr(), st)
     if rc:
         L.check(rc, 'cnnq_pc_stats_nhwc')
+    return stats, mom
+
+
+_STATS_HALF_NATIVE = {}
+
+
+def _stats_half_native(N, C, HW, dtype):
+    """Whether this class of layer collects its statistics on the contiguous bf16 / fp16 kernels: the "native" word of
+    cnnq_pc_route_stats_dt's report (0: a class that measured slower native than through the upcast is sent back there; a function
+    of N, C, HW and the dtype alone), asked once per class with alignment 16.  The statistics manager (collects_native_half) and
+    the tests patch the function and empty the cache by name."""
+    key = (N, C, HW, dtype)
+    v = _STATS_HALF_NATIVE.get(key)
+    if v is None:
+        out = (ctypes.c_int32 * 4)()
+        L.check(L.load().cnnq_pc_route_stats_dt(N, C, HW, _DTYPE_CODES.get(dtype, -1), 16, out), 'cnnq_pc_route_stats_dt')
+        v = _STATS_HALF_NATIVE[key] = bool(out[3])
+    return v
+
+
+def pc_stats_half(x, need_b=False, need_kurt=False, need_relu=False):
+    """pc_stats of a contiguous 4-D bf16 / fp16 activation, on the storage as it is (-sm collect,
+    smpc.py:45-79): cnnq_pc_stats_dt - pass A over (channel, batch split) workgroups, the merge, pass B when b or the kurtosis is
+    asked for, its merge - one host call, one cached workspace, 4 B/elem for the full table.  Returns (stats [NSTAT, C] f32, mom
+    [NMOM, C] f64) as pc_stats; rows nobody asked for are zero (B comes with pass B: need_b or need_kurt, as in pc_stats).  One
+    GPU: the statistics are this tensor's.  Anything else - a CPU tensor, float32, not 4-D, not contiguous - raises: nothing is
+    copied or upcast here."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise L.CnnqError('pc_stats_half: x must be a CUDA/HIP tensor (there is no CPU path)')
+    if x.dtype not in _HALF_DTYPES:
+        raise L.CnnqError('pc_stats_half: x must be bfloat16 or float16, got %s (float32 takes pc_stats)' % x.dtype)
+    if x.dim() != 4:
+        _not_4d(x, 'pc_stats_half')
+    if not x.is_contiguous() or x.numel() == 0:
+        raise L.CnnqError('pc_stats_half: x must be a non-empty contiguous tensor (no copy is made here)')
+    if x.device.index != torch.cuda.current_device():
+        raise L.CnnqError('pc_stats_half: x is on %s but the current device is cuda:%d' % (x.device, torch.cuda.current_device()))
+    if x.requires_grad:
+        x = x.detach()
+    N, C, HW = geometry(x)
+    dt = _HALF_DTYPES[x.dtype]
+    st = _raw_stream(x.device.index)
+    stats = torch.empty((L.NSTAT, C), dtype=torch.float32, device=x.device)
+    mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
+    ws = _scratch(x, 'stats_half', _ws_bytes('stats_half', N, C, HW, dt), st)
+    rc = L.load().cnnq_pc_stats_dt(x.data_ptr(), dt, N, C, HW, int(bool(need_b)), int(bool(need_kurt)), int(bool(need_relu)),
+                                   ws.data_ptr(), mom.data_ptr(), stats.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_stats_dt')
     return stats, mom
 
 

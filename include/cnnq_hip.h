@@ -726,6 +726,33 @@ int cnnq_pc_route_stats_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, i
 int cnnq_pc_stats_nhwc(const void* x, int dtype, int64_t R, int64_t C, int need_b, int need_kurt, int need_relu, void* ws,
                        double* mom, float* stats, void* stream);
 
+/* `-sm collect` - the same table - on CONTIGUOUS bf16 / fp16 activations x[N][C][HW], on the storage as it lies: no fp32 copy, x is
+ * read once per pass (4 B/elem for the full table).  A row x[n][c][0 .. HW) is cut into pieces of W elements (the widest of 8 / 4 /
+ * 2 / 1 that divides HW and x's alignment: every (HW, alignment) has a route); a 256-lane workgroup owns one channel and one of S
+ * ranges of samples, or - short batches - one of `column splits` ranges of the pieces of its rows.  Every element is upconverted
+ * exactly; the values of a piece are added in fp32 (pairs, then halves), the pieces in fp64, in an order fixed by (N, C, HW,
+ * alignment) alone: run after run the same bits, no atomics, but not the fp32 chain's order.  Promised: rows MIN / MAX exact - the
+ * extrema of cnnq_pc_stats on x.float(), a NaN element makes them NaN - every other row within the statistics tier of fp64 that
+ * cnnq_pc_stats_single keeps; rows MIN, MAX, MEAN, STD (and B) do not depend on which of the other rows were asked for.
+ * CNNQ_DTYPE_F32 forwards to cnnq_pc_stats (its workspace: what that call takes at either alignment).
+ * cnnq_pc_stats_dt_workspace: bytes of `ws` - doubles part[G][CNNQ_NMOM][C], mom[CNNQ_NMOM][C], part2[G][CNNQ_NDEV][C] with
+ * G = S * column splits, which do not depend on the alignment (0 on bad arguments or a geometry beyond cnnq_pc_groups' limits).
+ * cnnq_pc_route_stats_dt (host only, nothing enqueued): out = {piece width W, batch splits S, column splits, 1 - the native
+ * launches / 0 - a class of layer that did not measure faster than the upcast route and is left there by callers that have the
+ * choice: an odd HW with N * HW >= 16384 (cnnq_pc_stats_dt itself runs every class)}; a function of N, C, HW and the dtype alone;
+ * fp32: {0, cnnq_pc_groups' records, 1, 1}; align_bytes: the power of two that divides x (<= 16 is what matters). */
+size_t cnnq_pc_stats_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype);
+int cnnq_pc_route_stats_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int32_t out[4]);
+/* The table behind ONE call; counterpart of cnnq_pc_stats: pass A -> cnnq_pc_combine(has_relu = need_relu) (-> pass B on the merged
+ * table -> cnnq_pc_combine_dev(want_kurt = need_kurt), when need_b or need_kurt), two or four launches.  stats[CNNQ_NSTAT][C] is
+ * written completely: STD_POS is zero without need_relu, KURT without need_kurt, B unless pass B ran (need_b or need_kurt, as
+ * cnnq_pc_stats).  mom[CNNQ_NMOM][C]: the merged moment record - row COUNT is exactly N * HW - may be NULL (kept in ws).  ws:
+ * cnnq_pc_stats_dt_workspace bytes, 8-byte aligned.  A bad dtype, N, C or HW < 1, a NULL x / ws / stats, a misaligned ws / mom or
+ * an x not aligned to its element size returns CNNQ_EINVAL, a geometry beyond cnnq_pc_groups' limits that function's code - before
+ * anything touches the device.  Re-entrant, allocates nothing, no host synchronisation, graph-capturable. */
+int cnnq_pc_stats_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, int need_b, int need_kurt, int need_relu, void* ws,
+                     double* mom, float* stats, void* stream);
+
 /* The statistics of FEW, VERY LONG rows over flat storage - the per-tensor calibration table of statistic_manager.py:55-96
  * (rows = 1: the whole tensor) and the per-sample sums of squares of distance_stats.py:22-33 (rows = N: the samples) - for fp32 /
  * bf16 / fp16 elements, on the storage as it lies: x is viewed as [rows][len], every row contiguous and the rows back to back.
