@@ -150,6 +150,12 @@ __global__ void __launch_bounds__(TPB) k_bcorr_sums(const float* __restrict__ x,
     }
 }
 
+// q_bias of a channel from its merged sums (iqm.py:192-194): the fp32 difference over the fp32 count
+__device__ __forceinline__ float bcorr_bias_of(double sum_x, double sum_q, double count) {
+    const float qb = (float)sum_x - (float)sum_q;
+    return qb / ((float)count + 1e-8f);
+}
+
 // merge G records -> q_bias[c] = (sum x' - sum y) / (count + 1e-8)   (iqm.py:192-194); sums[3][C] optional
 __global__ void __launch_bounds__(TPB) k_bcorr_bias(const double* __restrict__ part3, int G, int C,
                                                     double* __restrict__ sums, float* __restrict__ bias) {
@@ -167,10 +173,7 @@ __global__ void __launch_bounds__(TPB) k_bcorr_bias(const double* __restrict__ p
     for (int m = 32; m >= 1; m >>= 1) { a += shfl_xor_d(a, m); bq += shfl_xor_d(bq, m); cn += shfl_xor_d(cn, m); }
     if (lane) return;
     if (sums) { sums[c] = a; sums[(size_t)C + c] = bq; sums[(size_t)2 * C + c] = cn; }
-    if (bias) {
-        const float qb = (float)a - (float)bq;
-        bias[c] = qb / ((float)cn + 1e-8f);
-    }
+    if (bias) bias[c] = bcorr_bias_of(a, bq, cn);
 }
 
 // pass 2: y += (y > 0) * q_bias[c]   (iqm.py:196), in place

@@ -51,6 +51,7 @@
 #include "cnnq_kld.hip.h"
 #include "cnnq_half.hip.h"
 #include "cnnq_half_stats.hip.h"
+#include "cnnq_half_bcorr.hip.h"
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_nhwc_collect.hip.h"
@@ -1740,6 +1741,109 @@ int cnnq_pc_stats_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW,
     rc = launch_status();
     if (!rc) rc = cnnq_pc_combine_dev(a.part2, G, C, rec, need_kurt ? 1 : 0, nullptr, stats, stream);
     return rc;
+}
+
+// ---- `-sm use ... -bca` on contiguous bf16 / fp16 activations (cnnq_half_bcorr.hip.h) -------------------------------------------
+// the fp32 chain's record count at either alignment (what cnnq_pc_qdq_bcorr_sums writes); <= 0: cnnq_pc_groups' code
+static int bcorr_groups_f32(int64_t N, int64_t C, int64_t HW) {
+    const int g1 = cnnq_pc_groups(N, C, HW, 1), g0 = cnnq_pc_groups(N, C, HW, 0);
+    return g1 > g0 ? g1 : g0;
+}
+
+// ws, doubles: part3[G][3][C] with G = S * column splits (h_stats_splits: not the alignment's); fp32: the chain's records
+size_t cnnq_pc_qdq_bcorr_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype) {
+    if (h_stats_check(N, C, HW, dtype)) return 0;
+    int64_t G;
+    if (dtype == CNNQ_DTYPE_F32) {
+        G = bcorr_groups_f32(N, C, HW);
+        if (G <= 0) return 0;
+    } else {
+        int S, cs;
+        if (h_stats_plan(N, C, HW, &S, &cs)) return 0;
+        G = (int64_t)S * cs;
+    }
+    return (size_t)G * 3 * (size_t)C * sizeof(double);
+}
+
+// Which launches cnnq_pc_qdq_bcorr_dt makes for this geometry with allow_single_launch 0 / 1 (host only): out = {piece width W,
+// batch splits S, column splits of the sums pass, route}; route 1 - k_h_bcorr_whole / 2 - the two passes and the bias between them
+// / 0 - a class of layer that did not win against the upcast route and stays there (h_bcorr_native; the call itself runs every
+// class).  fp32: {0, the chain's records, 1, 2}.
+int cnnq_pc_route_qdq_bcorr_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int allow_single_launch, int32_t out[4]) {
+    if (h_stats_check(N, C, HW, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
+    int S, cs;
+    if (const int rc = h_stats_plan(N, C, HW, &S, &cs)) return rc;
+    if (dtype == CNNQ_DTYPE_F32) {
+        out[0] = 0;
+        out[1] = bcorr_groups_f32(N, C, HW);
+        out[2] = 1;
+        out[3] = 2;
+        return 0;
+    }
+    const int w = h_piece(HW, (uintptr_t)align_bytes, 0);
+    out[0] = w;
+    out[1] = S;
+    out[2] = cs;
+    if (allow_single_launch && h_bcorr_whole_fits(N, HW, w) && (allow_single_launch > 1 || h_bcorr_whole_wins(N, C, HW, dtype))) out[3] = 1;
+    else out[3] = h_bcorr_native(N, C, HW, dtype) ? 2 : 0;
+    return 0;
+}
+
+// iqm.py:180-196 folded into int_quantizer.py:573-592 on x[N][C][HW] of bf16 / fp16 with a given table (-sm use): k_h_bcorr_whole,
+// or k_h_bcorr_sums (ascending) -> k_bcorr_bias on its S * cs records -> k_h_qdq_bias (descending)
+int cnnq_pc_qdq_bcorr_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, int relu_first, void* ws,
+                         double* sums, float* bias, int allow_single_launch, void* stream) {
+    if (h_stats_check(N, C, HW, dtype)) return CNNQ_EINVAL;
+    if (!x || !y || x == y || !qp || !ws || !bias || misaligned(ws, 8) || misaligned(sums, 8) || misaligned(qp, 4) || misaligned(bias, 4))
+        return CNNQ_EINVAL;
+    double* part3 = static_cast<double*>(ws);
+    if (dtype == CNNQ_DTYPE_F32) {
+        if (misaligned(x, 4) || misaligned(y, 4)) return CNNQ_EINVAL;
+        const int G = cnnq_pc_groups(N, C, HW, al16(x));
+        if (G <= 0) return g_error(G);
+        const float* xf = static_cast<const float*>(x);
+        int rc = cnnq_pc_qdq_bcorr_sums(xf, N, C, HW, qp, relu_first, part3, stream);
+        if (!rc) rc = cnnq_pc_bcorr_bias(part3, G, C, sums, bias, stream);
+        if (!rc) rc = cnnq_pc_qdq_bcorr(xf, static_cast<float*>(y), N, C, HW, qp, bias, 1, stream);
+        return rc;
+    }
+    if (misaligned(x, 2) || misaligned(y, 2)) return CNNQ_EINVAL;
+    int32_t route[4];
+    if (const int rc = cnnq_pc_route_qdq_bcorr_dt(N, C, HW, dtype, h_align(x, y), allow_single_launch, route)) return rc;
+    const int w = route[0];
+    HGeo g;
+    g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
+    g.ppr = (int)(HW / w);
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+    uint16_t* yh = static_cast<uint16_t*>(y);
+    hipStream_t st = hs(stream);
+    const int relu = relu_first ? 1 : 0;
+    if (route[3] == 1) {
+        g.S = 1; g.cs = 1;
+        with_piece<false>(dtype, w, [&](auto pc) {
+            using P = decltype(pc);
+            if constexpr (P::W > 1)
+                hipLaunchKernelGGL((k_h_bcorr_whole<typename P::T, P::W, h_whole_k<P::W>()>), dim3((unsigned)C), dim3(HTPB), 0, st, xh, yh, g, relu, qp,
+                                   sums, bias);
+        });
+        return launch_status();
+    }
+    g.S = route[1]; g.cs = route[2];
+    const int G = g.S * g.cs;
+    with_piece<false>(dtype, w, [&](auto pc) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_h_bcorr_sums<typename P::T, P::W>), dim3((unsigned)(C * G)), dim3(TPB), 0, st, xh, g, relu, qp, part3);
+    });
+    int rc = launch_status();
+    if (!rc) rc = cnnq_pc_bcorr_bias(part3, G, C, sums, bias, stream);
+    if (rc) return rc;
+    g.S = h_splits(N, C, HW, H_QDQ_ELEMS, N);
+    g.cs = 1;
+    with_piece<false>(dtype, w, [&](auto pc) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_h_qdq_bias<typename P::T, P::W>), dim3((unsigned)(C * g.S)), dim3(TPB), 0, st, xh, yh, g, qp, bias);
+    });
+    return launch_status();
 }
 
 int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream) {

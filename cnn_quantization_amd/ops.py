@@ -95,7 +95,8 @@ def _half_only(what, reason):
 
 # switches, read ONCE at import (not per hot call); reload_switches() re-reads them after the environment changed (tests, tools)
 def reload_switches():
-    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC
+    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC, _HALF_TABLE
+    _HALF_TABLE = os.environ.get('CNNQ_HALF_TABLE', '1') != '0'        # 0: calibrated per-channel half activations take the upcast route (A/B)
     _NHWC = os.environ.get('CNNQ_NHWC', '1') != '0'                    # 0: channels_last tensors take the NCHW copy route (A/B)
     _ACIQ_SINGLE = os.environ.get('CNNQ_ACIQ_SINGLE', '1') != '0'      # 0: the ACIQ path always takes the five-launch chain (A/B)
     _XRANK_ON = D.xrank_mode() != '0'                                  # opt-in (CNNQ_XRANK=1 / auto, D.set_xrank_mode): sharded config 2 exchanges INSIDE the single launch
@@ -209,7 +210,7 @@ _NHWC_WS = {'nhwc': 'cnnq_pc_nhwc_workspace', 'aciq_nhwc': 'cnnq_pc_aciq_nhwc_wo
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
     arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc', 'stats_nhwc': N = rows; 'rows':
-    N = rows, C = their length; 'pt_clip': N = elements; 'stats_half': the dtype code).  0 from the library: no plan for the geometry."""
+    N = rows, C = their length; 'pt_clip': N = elements; 'stats_half', 'bcorr_half': the dtype code).  0 from the library: no plan for the geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
@@ -225,10 +226,11 @@ def _ws_bytes(kind, N, C, HW, arg=0):
                 raise L.CnnqError('cnnq_pt_clip_workspace(%d, %d): bad arguments' % (N, arg))
         elif kind == 'aciq':
             nbytes = lib.cnnq_pc_aciq_workspace(N, C, HW, arg)
-        elif kind == 'stats_half':
-            nbytes = lib.cnnq_pc_stats_dt_workspace(N, C, HW, arg)
+        elif kind in ('stats_half', 'bcorr_half'):
+            fn = 'cnnq_pc_stats_dt_workspace' if kind == 'stats_half' else 'cnnq_pc_qdq_bcorr_dt_workspace'
+            nbytes = getattr(lib, fn)(N, C, HW, arg)
             if nbytes == 0:
-                L.check(min(lib.cnnq_pc_groups(N, C, HW, 0), -1), 'cnnq_pc_stats_dt_workspace(%d,%d,%d,%d)' % (N, C, HW, arg))
+                L.check(min(lib.cnnq_pc_groups(N, C, HW, 0), -1), '%s(%d,%d,%d,%d)' % (fn, N, C, HW, arg))
         else:
             nbytes = lib.cnnq_pc_minmax_qdq_workspace(N, C, HW) if kind == 'cfg2' else lib.cnnq_pc_stats_workspace(N, C, HW, arg)
             if nbytes == 0:
@@ -1930,6 +1932,75 @@ def qdq_bias_corrected_nhwc(x, qp, relu_first, out=None, want_parts=False):
     rc = L.load().cnnq_pc_qdq_bcorr_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, qp.data_ptr(), int(bool(relu_first)), ws, sp, bp, st)
     if rc:
         L.check(rc, 'cnnq_pc_qdq_bcorr_nhwc')
+    return _result(y, parts=dict(sums=sums, bias=bias) if want_parts else None)
+
+
+_TABLE_HALF_NATIVE = {}
+
+
+def _table_half_native(N, C, HW, dtype):
+    """The route word of cnnq_pc_route_qdq_bcorr_dt's report for this class of contiguous bf16 / fp16 layer: 1 - the table-driven
+    Q/DQ with the bias correction in one launch, 2 - in two passes, 0 - a class that measured slower native than through the upcast
+    and is sent back there (a function of N, C, HW and the dtype alone), asked once per class with alignment 16.  The quantizer
+    (_half_table) and the tests patch the function and empty the cache by name."""
+    key = (N, C, HW, dtype)
+    v = _TABLE_HALF_NATIVE.get(key)
+    if v is None:
+        out = (ctypes.c_int32 * 4)()
+        L.check(L.load().cnnq_pc_route_qdq_bcorr_dt(N, C, HW, _DTYPE_CODES.get(dtype, -1), 16, 1, out), 'cnnq_pc_route_qdq_bcorr_dt')
+        v = _TABLE_HALF_NATIVE[key] = int(out[3])
+    return v
+
+
+def qdq_bias_corrected_half(x, qp, relu_first, out=None, want_parts=False, single_launch=None):
+    """qdq_bias_corrected on a contiguous 4-D bf16 / fp16 activation, on the storage as it is (-sm use with
+    -bca): cnnq_pc_qdq_bcorr_dt - the per-channel sums over (channel, batch split) workgroups, the bias, the fused quantize +
+    correct pass, 6 B/elem; or all three in one launch, 4 B/elem, where a channel's batch population fits one workgroup's registers
+    - one host call, one cached workspace.  y has x's dtype; want_parts: (y, dict(sums [3, C] float64 = {sum x', sum q,
+    count(x' > 0)}, bias [C])).  single_launch: None - the route function's choice; True / False - the single launch (raises where
+    the channel does not fit) / the two passes, for tests and A/B.  One GPU: the sums are this tensor's.  Anything else - a CPU
+    tensor, float32, not 4-D, not contiguous, a qp that is not a float32 [NQP, C] device table - raises: nothing is copied or upcast
+    here."""
+    what = 'qdq_bias_corrected_half'
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise L.CnnqError('%s: x must be a CUDA/HIP tensor (there is no CPU path)' % what)
+    if x.dtype not in _HALF_DTYPES:
+        raise L.CnnqError('%s: x must be bfloat16 or float16, got %s (float32 takes qdq_bias_corrected)' % (what, x.dtype))
+    if x.dim() != 4:
+        _not_4d(x, what)
+    if not x.is_contiguous() or x.numel() == 0:
+        raise L.CnnqError('%s: x must be a non-empty contiguous tensor (no copy is made here)' % what)
+    if x.device.index != torch.cuda.current_device():
+        raise L.CnnqError('%s: x is on %s but the current device is cuda:%d' % (what, x.device, torch.cuda.current_device()))
+    if x.requires_grad:
+        x = x.detach()
+    N, C, HW = geometry(x)
+    if not _is_table(qp, torch.float32, (L.NQP, C), x.device):
+        raise L.CnnqError('%s: qp must be a contiguous float32 [%d, %d] device table' % (what, L.NQP, C))
+    dt = _HALF_DTYPES[x.dtype]
+    st = _raw_stream(x.device.index)
+    y = _out_like(x, out)
+    allow = 1 if single_launch is None else (2 if single_launch else 0)
+    if single_launch:
+        route = (ctypes.c_int32 * 4)()
+        bits = x.data_ptr() | y.data_ptr() | 16
+        align = bits & -bits                 # the alignment x and y share, 16 at most
+        L.check(L.load().cnnq_pc_route_qdq_bcorr_dt(N, C, HW, dt, align, 2, route), 'cnnq_pc_route_qdq_bcorr_dt')
+        if route[3] != 1:
+            raise L.CnnqError('%s: no single launch for [%d, %d, %d] at piece width %d' % (what, N, C, HW, route[0]))
+    nbytes = _ws_bytes('bcorr_half', N, C, HW, dt)
+    if want_parts:
+        sums = torch.empty((3, C), dtype=torch.float64, device=x.device)
+        bias = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws, sp, bp = _scratch(x, 'bcorr_half', nbytes, st).data_ptr(), sums.data_ptr(), bias.data_ptr()
+    else:
+        # the bias nobody outside the call reads follows the records in the cached workspace
+        ws = _scratch(x, 'bcorr_half', nbytes + C * 4, st).data_ptr()
+        sp, bp = None, ws + nbytes
+    rc = L.load().cnnq_pc_qdq_bcorr_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, qp.data_ptr(), int(bool(relu_first)), ws, sp, bp,
+                                       allow, st)
+    if rc:
+        L.check(rc, 'cnnq_pc_qdq_bcorr_dt')
     return _result(y, parts=dict(sums=sums, bias=bias) if want_parts else None)
 
 

@@ -101,7 +101,9 @@ class IntQuantizer:
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
         if (isinstance(tensor, torch.Tensor) and tensor.dtype in HALF_DTYPES
-                and not self._half_native(tensor, override_att, stat_id) and not self._nhwc_midtread(tensor, self._att(override_att))
+                and not self._half_native(tensor, override_att, stat_id)
+                and not self._half_table(tensor, self._att(override_att)('clipping'), stat_id, self._att(override_att))
+                and not self._nhwc_midtread(tensor, self._att(override_att))
                 and not self._nhwc_entropy(tensor, self._att(override_att)) and not self._flat_clip(tensor, self._att(override_att))
                 and not self._flat_midtread(tensor, self._att(override_att)) and not self._flat_kld(tensor, self._att(override_att))):
             return upcast_fallback(self.__call__, tensor, id, tag, stat_id, override_att)
@@ -236,6 +238,34 @@ class IntQuantizer:
         return (bool(get('kld')) and getattr(tensor, 'is_cuda', False) and tensor.dtype in HALF_DTYPES
                 and (tensor.is_contiguous() or _dense_nhwc(tensor)))
 
+    def _half_table(self, tensor, clip_type, stat_id, att=None):
+        """The per-channel activation branches quantize a contiguous bf16 / fp16 tensor from the calibration table where it lies
+        (DESIGN.md section 24): stat_id given (everything dynamic keeps its route), min/max, Laplace or Gaussian clipping, with or
+        without bit allocation and a pending bias correction (ops.qdq_bias_corrected_half, else ops.pc_qdq), no mid-tread, KLD or
+        entropy measurement, one GPU's own data, the switch CNNQ_HALF_TABLE on and a class of layer the route function keeps
+        native.  Kept apart from _half_native, whose answers are pinned by tests; shape, strides and attributes only."""
+        att = att or (lambda k: getattr(self, k))
+        if not (stat_id is not None and getattr(tensor, 'is_cuda', False) and tensor.dtype in HALF_DTYPES and tensor.dim() == 4
+                and tensor.is_contiguous() and tensor.numel() > 0):
+            return False
+        if not (bool(att('pcq_a')) and _is_pc_act(tensor) and clip_type in ('no', 'laplace', 'gaus')
+                and not (clip_type == 'no' and att('pcq_w')) and not att('mtd_quant') and not att('kld')
+                and not att('measure_entropy') and self._one_gpu() and ops._HALF_TABLE):
+            return False
+        N, C, HW = ops.geometry(tensor)
+        return ops._table_half_native(N, C, HW, tensor.dtype) != 0
+
+    def _table_half(self, tensor, table, clip_type, prior_b):
+        """The _half_table route: the parameters of the calibration table, then Q/DQ - with a pending correction folded in - where
+        the tensor lies."""
+        use_ba = bool(self.bit_alloc_act) and self.num_bits <= 4
+        qp, _ = ops.pc_params(table, self.num_bits, self._positive, clip_type, use_ba, prior_b, self.bit_alloc_target_act,
+                              self.bit_alloc_round)
+        if self.fuse_bcorr is not None:
+            return ops.qdq_bias_corrected_half(tensor, qp, bool(self._take_bcorr()))
+        N, C, HW = ops.geometry(tensor)
+        return ops.pc_qdq(tensor, N, C, HW, qp)
+
     def _bcorr_nhwc(self, tensor, table, clip_type, prior_b):
         """The _nhwc_bcorr route: the parameters of the calibration table, then Q/DQ and correction where the tensor lies."""
         use_ba = bool(self.bit_alloc_act) and self.num_bits <= 4
@@ -306,6 +336,9 @@ class IntQuantizer:
             table = self._stats_table(stat_id, C, tensor.device, rows)
             if self._nhwc_bcorr(tensor, 'no', stat_id):
                 return self._bcorr_nhwc(tensor, table, 'no', prior_b)
+            if (use_ba or self.fuse_bcorr is not None) and self._half_table(tensor, 'no', stat_id):
+                # (plain min/max from the table without a correction: act_qdq_per_channel's own half route below)
+                return self._table_half(tensor, table, 'no', prior_b)
         out = ops.act_qdq_per_channel(tensor, self.num_bits, positive=self._positive, clip='no',
                                       bit_alloc=self.bit_alloc_act, prior_is_b=prior_b,
                                       target=self.bit_alloc_target_act, round_mode=self.bit_alloc_round,
@@ -331,6 +364,8 @@ class IntQuantizer:
                 table = self._stats_table(stat_id, C, tensor.device, rows)
                 if self._nhwc_bcorr(tensor, clip_type, stat_id):
                     return self._bcorr_nhwc(tensor, table, clip_type, prior_b)
+                if self._half_table(tensor, clip_type, stat_id):
+                    return self._table_half(tensor, table, clip_type, prior_b)
             if self._nhwc_aciq(tensor, clip_type):
                 # a dense channels_last activation: quantized where it lies, the result keeps layout and dtype
                 return ops.aciq_qdq_nhwc(tensor, self.num_bits, positive=self._positive, clip=clip_type,

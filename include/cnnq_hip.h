@@ -753,6 +753,40 @@ int cnnq_pc_route_stats_dt(int64_t N, int64_t C, int64_t HW, int dtype, int alig
 int cnnq_pc_stats_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, int need_b, int need_kurt, int need_relu, void* ws,
                      double* mom, float* stats, void* stream);
 
+/* Activation bias correction (iqm.py:180-196) fused into the table-driven Q/DQ - `-sm use ... -bca` - on CONTIGUOUS bf16 / fp16
+ * activations x[N][C][HW], on the storage as it lies: no fp32 copy, 6 B/elem (x read twice, y written once), or 4 B/elem in one
+ * launch where a channel's whole batch population fits one workgroup's registers.  Counterpart of cnnq_pc_qdq_bcorr_sums +
+ * cnnq_pc_bcorr_bias + cnnq_pc_qdq_bcorr behind ONE call.  The rows are cut into pieces as for cnnq_pc_stats_dt (W = 8 / 4 / 2 / 1
+ * from HW and the alignment x and y share: every (HW, alignment) has a route); a workgroup owns one channel.  Two routes:
+ *   2. three launches: per channel sum x', sum q, count(x' > 0) over S batch splits x `column splits` (cnnq_pc_stats_dt's
+ *      partition) with q = the fp32 Q/DQ of x from qp[CNNQ_NQP][C] (the IEEE divide) and x' = relu(x) when relu_first != 0, into
+ *      ws (read-only pass over x); cnnq_pc_bcorr_bias on those records: bias[c] = ((float)sum x' - (float)sum q) /
+ *      ((float)count + 1e-8f) and - sums != NULL - the merged sums[3][C] (doubles); y = q + (q > 0) * bias[c], rounded once into
+ *      the element type;
+ *   1. one launch, one 1024-lane workgroup per channel that keeps the channel in registers: the same sums, bias and y.  Only
+ *      where N * HW <= 131072 and W >= 2.
+ * The values of a piece are added in fp32 (pairs, then halves), the pieces in fp64, in an order fixed by (N, C, HW, alignment,
+ * route) alone: run after run the same bits, no atomics, but not the fp32 chain's order.  Promised: the sums within the statistics
+ * tier of fp64 (the count exact), and given them bias and y bit for bit.  CNNQ_DTYPE_F32 forwards to the three fp32 calls named
+ * above (its workspace: their records at either alignment).
+ * cnnq_pc_qdq_bcorr_dt_workspace: bytes of `ws` - doubles part3[G][3][C] with G = S * column splits, which do not depend on the
+ * alignment or the route (0 on bad arguments or a geometry beyond cnnq_pc_groups' limits).
+ * cnnq_pc_route_qdq_bcorr_dt (host only, nothing enqueued): out = {piece width W, batch splits S, column splits, route}; route 1
+ * / 2 as above, 0 - a class of layer that did not measure faster than the upcast route and is left there by callers that have
+ * the choice (cnnq_pc_qdq_bcorr_dt itself runs every class, on route 2).  allow_single_launch: 0 - never route 1; 1 - route 1
+ * for the classes where it measured faster than route 2 (C == 256 with N * HW >= 32768: one full round of workgroups on the
+ * device); 2 - route 1 wherever the channel fits (tests, A/B).  A function of its
+ * arguments alone; fp32: {0, cnnq_pc_groups' records, 1, 2}; align_bytes: the power of two that divides x and y (<= 16 is what
+ * matters). */
+size_t cnnq_pc_qdq_bcorr_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype);
+int cnnq_pc_route_qdq_bcorr_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int allow_single_launch, int32_t out[4]);
+/* bias[C] is an OUTPUT; sums[3][C] may be NULL.  ws: cnnq_pc_qdq_bcorr_dt_workspace bytes, 8-byte aligned, as sums (route 1 does
+ * not touch ws).  A bad dtype, N, C or HW < 1, a NULL x / y / qp / ws / bias, a misaligned ws / sums / qp / bias, an x or y not
+ * aligned to its element size, or x == y returns CNNQ_EINVAL, a geometry beyond cnnq_pc_groups' limits that function's code -
+ * before anything touches the device.  Re-entrant, allocates nothing, no host synchronisation, graph-capturable. */
+int cnnq_pc_qdq_bcorr_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, int relu_first, void* ws,
+                         double* sums, float* bias, int allow_single_launch, void* stream);
+
 /* The statistics of FEW, VERY LONG rows over flat storage - the per-tensor calibration table of statistic_manager.py:55-96
  * (rows = 1: the whole tensor) and the per-sample sums of squares of distance_stats.py:22-33 (rows = N: the samples) - for fp32 /
  * bf16 / fp16 elements, on the storage as it lies: x is viewed as [rows][len], every row contiguous and the rows back to back.
