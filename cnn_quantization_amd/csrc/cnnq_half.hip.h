@@ -14,6 +14,11 @@
 // of 8 / 4 / 2 / 1 that divides HW and both pointers' alignment: 16-byte pieces (W = 8) for every row length that is a multiple
 // of 8 on a 16-byte aligned tensor, 8-byte pieces for 14x14 (HW = 196), 2-byte elements for 7x7 (49), odd lengths and views at an
 // odd element offset.  The lanes walk the workgroup's (row, piece) pairs with a carry, no division in the loop.
+//
+// What the contiguous bf16 / fp16 family shares lives here (cnnq_half_stats.hip.h and cnnq_half_bcorr.hip.h hold their own
+// arithmetic only): the piece load / store (piece_ld / piece_st_nt, the channels_last kernels' pair too), the partition of the
+// grid (HGeo, HPart, h_part), the walk and the read-only piece loop (HWalk, h_pieces), the table row (h_qp), the workgroup folds
+// (h_fold_mm, h_fold_sums) and the resident tile of the single-launch kernels (HTile).
 #pragma once
 #include "cnnq_common.hip.h"
 #include "cnnq_qdq.hip.h"
@@ -37,17 +42,14 @@ __device__ __forceinline__ uint16_t h_down(HF16, float f) {
     return __builtin_bit_cast(uint16_t, (_Float16)f);
 }
 
-// W consecutive 2-byte elements: one global load / store of 2 W bytes (W = 8: dwordx4)
-template <int W>
-struct HPiece {
-    typedef uint16_t vec_t __attribute__((ext_vector_type(W)));
-};
-template <int W, bool NT>
-__device__ __forceinline__ void h_ld(const uint16_t* __restrict__ p, uint16_t (&e)[W]) {
+// W consecutive elements of type E: one global load / store of W * sizeof(E) bytes, 16 at most (dwordx4) - the one pair every
+// bf16 / fp16 and channels_last kernel loads and stores through
+template <class E, int W, bool NT>
+__device__ __forceinline__ void piece_ld(const E* __restrict__ p, E (&e)[W]) {
     if constexpr (W == 1) {
         e[0] = NT ? __builtin_nontemporal_load(p) : *p;
     } else {
-        typedef typename HPiece<W>::vec_t V;
+        typedef E V __attribute__((ext_vector_type(W)));
         V v;
         if constexpr (NT) v = __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
         else v = *reinterpret_cast<const V*>(p);
@@ -55,26 +57,59 @@ __device__ __forceinline__ void h_ld(const uint16_t* __restrict__ p, uint16_t (&
         for (int i = 0; i < W; ++i) e[i] = v[i];
     }
 }
-template <int W>
-__device__ __forceinline__ void h_st_nt(uint16_t* __restrict__ p, const uint16_t (&e)[W]) {
+template <class E, int W>
+__device__ __forceinline__ void piece_st_nt(E* __restrict__ p, const E (&e)[W]) {
     if constexpr (W == 1) {
         __builtin_nontemporal_store(e[0], p);
     } else {
-        typedef typename HPiece<W>::vec_t V;
+        typedef E V __attribute__((ext_vector_type(W)));
         V v;
 #pragma unroll
         for (int i = 0; i < W; ++i) v[i] = e[i];
         __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
     }
 }
+template <int W, bool NT>
+__device__ __forceinline__ void h_ld(const uint16_t* __restrict__ p, uint16_t (&e)[W]) { piece_ld<uint16_t, W, NT>(p, e); }
+template <int W>
+__device__ __forceinline__ void h_st_nt(uint16_t* __restrict__ p, const uint16_t (&e)[W]) { piece_st_nt<uint16_t, W>(p, e); }
 
-// the launch geometry of the row walk: grid = C * S workgroups, workgroup b = s * C + c owns channel c, samples [n0, n1) of
-// split s (adjacent workgroups: adjacent rows in memory)
+// the launch geometry of the row walk: grid = C * S * cs workgroups, workgroup b = s * C + c owns channel c and part s (h_part)
+// (adjacent workgroups: adjacent rows in memory)
 struct HGeo {
     int N, C, HW, S;
     int ppr;        // pieces per row, HW / W
-    int cs;         // k_h_minmax: column splits per row (split s = batch split s / cs, pieces [p0, p1) of part s % cs)
+    int cs;         // column splits per row (part s = batch split s / cs, pieces [p0, p1) of column part s % cs); 1: whole rows
 };
+inline HGeo h_geo(int64_t N, int64_t C, int64_t HW, int w, int S, int cs) {
+    return HGeo{(int)N, (int)C, (int)HW, S, (int)(HW / w), cs};
+}
+
+// what the workgroup `bid` of a C * S * cs grid owns: channel c, part s = samples [n0, n1) of batch split s / cs and pw pieces
+// from p0 of each of their rows; off: the element offset of its first piece.  COLS = false: the form for cs == 1 (whole rows),
+// without the divisions
+struct HPart {
+    int c, s, rows, pw;
+    size_t off;
+};
+template <int W, bool COLS = true>
+__device__ __forceinline__ HPart h_part(const HGeo& g, int bid) {
+    HPart t;
+    t.c = bid % g.C;
+    t.s = bid / g.C;
+    int sn = t.s, p0 = 0;
+    t.pw = g.ppr;
+    if constexpr (COLS) {
+        sn = t.s / g.cs;
+        const int sp = t.s - sn * g.cs;
+        p0 = (int)(((int64_t)sp * g.ppr) / g.cs);
+        t.pw = (int)(((int64_t)(sp + 1) * g.ppr) / g.cs) - p0;
+    }
+    const int n0 = (int)(((int64_t)sn * g.N) / g.S), n1 = (int)(((int64_t)(sn + 1) * g.N) / g.S);
+    t.rows = n1 - n0;
+    t.off = (size_t)n0 * ((size_t)g.C * (size_t)g.HW) + (size_t)t.c * g.HW + (size_t)p0 * W;
+    return t;
+}
 
 // (row, piece) of this lane's first pair and the per-step advance of the walk (TPB pairs per step)
 struct HWalk {
@@ -94,9 +129,65 @@ __device__ __forceinline__ void h_step(HWalk& w, int ppr) {
     w.p += w.dp;
     if (w.p >= ppr) { w.p -= ppr; ++w.r; }
 }
-__device__ __forceinline__ void h_split(const HGeo& g, int s, int& n0, int& n1) {
-    n0 = (int)(((int64_t)s * g.N) / g.S);
-    n1 = (int)(((int64_t)(s + 1) * g.N) / g.S);
+
+// The one piece loop of the read-only kernels: the lanes walk the (row, piece) pairs of part t, load each piece and hand it to
+// f(e).  x points at the part (tensor + t.off).  U: the unroll count.  The trip count is a run-time one: no inline asm in f
+// (cnnq_common.hip.h, hadd).  The two storing kernels (k_h_qdq, k_h_qdq_bias) keep their loop written out: through this
+// template k_h_qdq_bias<T, 8> took 57 VGPRs for 37 and the two-pass correction measured 1-2 % slower.
+template <int W, int U, class F>
+__device__ __forceinline__ void h_pieces(const uint16_t* x, const HGeo& g, const HPart& t, F&& f) {
+    const size_t P = (size_t)g.C * (size_t)g.HW;
+    HWalk w = h_walk(t.pw);
+#pragma unroll U
+    for (; w.r < t.rows; h_step(w, t.pw)) {
+        uint16_t e[W];
+        h_ld<W, false>(x + (size_t)w.r * P + (size_t)w.p * W, e);
+        f(e);
+    }
+}
+
+// the row qp[CNNQ_NQP][C] holds for channel c
+__device__ __forceinline__ void h_qp(const float* __restrict__ qp, int C, int c, float& sc, float& zp, float& qm) {
+    sc = qp[(size_t)CNNQ_QP_SCALE * C + c];
+    zp = qp[(size_t)CNNQ_QP_ZP * C + c];
+    qm = qp[(size_t)CNNQ_QP_QMAX * C + c];
+}
+
+// The workgroup folds: the lanes' values -> the workgroup's, in every lane.  The fixed xor tree 32 ... 1 inside the wave, then
+// the NW waves in wave order through LDS (the sums from 0.0): an order that follows from the launch alone.  One barrier; the LDS
+// is the caller's and is not free again on return.
+// Extrema: v_min / v_max drop a NaN, so a lane that saw one has poisoned its pair BEFORE the fold; pmin / pmax carry it on.
+template <int NW>
+__device__ __forceinline__ void h_fold_mm(float (&l_mn)[NW], float (&l_mx)[NW], float& mn, float& mx) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { mn = pmin(mn, shfl_xor_f(mn, m)); mx = pmax(mx, shfl_xor_f(mx, m)); }
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { l_mn[wv] = mn; l_mx[wv] = mx; }
+    __syncthreads();
+    mn = l_mn[0];
+    mx = l_mx[0];
+    for (int i = 1; i < NW; ++i) { mn = pmin(mn, l_mn[i]); mx = pmax(mx, l_mx[i]); }
+}
+// NV fp64 sums at once
+template <int NW, int NV>
+__device__ __forceinline__ void h_fold_sums(double (&l)[NV][NW], double (&v)[NV]) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) v[j] += shfl_xor_d(v[j], m);
+    }
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) l[j][wv] = v[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = 0.;
+    for (int i = 0; i < NW; ++i) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) v[j] += l[j][i];
+    }
 }
 
 // scale / zero point / qmax of a channel from its exact extrema: k_minmax_params' arithmetic (iq.py:559-572), the same bits
@@ -151,41 +242,27 @@ __device__ __forceinline__ void h_qdq_piece(uint16_t (&e)[W], bool fast, float s
 // exact per-channel {min, max} of one split -> pmm[s][2][C] (the layout k_minmax_params / k_minmax_reduce merge): plain stores,
 // every entry written exactly once.  v_min / v_max drop a NaN: a lane that saw one poisons its result (torch.min / max propagate it)
 template <class T, int W>
+__device__ __forceinline__ void h_mm_piece(const uint16_t (&e)[W], float& mn, float& mx, bool& nan) {
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        const float v = h_up(T{}, e[i]);
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+        nan |= v != v;
+    }
+}
+template <class T, int W>
 __global__ void __launch_bounds__(TPB) k_h_minmax(const uint16_t* __restrict__ x, const HGeo g, float* __restrict__ pmm) {
     __shared__ float l_mn[TPB / 64], l_mx[TPB / 64];
-    const int c = (int)blockIdx.x % g.C, s = (int)blockIdx.x / g.C;
-    const int sn = s / g.cs, sp = s - sn * g.cs;
-    int n0, n1;
-    h_split(g, sn, n0, n1);
-    const int rows = n1 - n0;
-    const int p0 = (int)(((int64_t)sp * g.ppr) / g.cs), pw = (int)(((int64_t)(sp + 1) * g.ppr) / g.cs) - p0;
-    const size_t P = (size_t)g.C * (size_t)g.HW;
-    const uint16_t* base = x + (size_t)n0 * P + (size_t)c * g.HW + (size_t)p0 * W;
+    const HPart t = h_part<W>(g, (int)blockIdx.x);
     float mn = INFINITY, mx = -INFINITY;
     bool nan = false;
-    HWalk w = h_walk(pw);
-#pragma unroll 4
-    for (; w.r < rows; h_step(w, pw)) {
-        uint16_t e[W];
-        h_ld<W, false>(base + (size_t)w.r * P + (size_t)w.p * W, e);
-#pragma unroll
-        for (int i = 0; i < W; ++i) {
-            const float v = h_up(T{}, e[i]);
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-            nan |= v != v;
-        }
-    }
+    h_pieces<W, 4>(x + t.off, g, t, [&](const uint16_t (&e)[W]) { h_mm_piece<T, W>(e, mn, mx, nan); });
     if (nan) { mn = NAN; mx = NAN; }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { mn = pmin(mn, shfl_xor_f(mn, m)); mx = pmax(mx, shfl_xor_f(mx, m)); }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { l_mn[wv] = mn; l_mx[wv] = mx; }
-    __syncthreads();
+    h_fold_mm(l_mn, l_mx, mn, mx);
     if (threadIdx.x == 0) {
-        for (int i = 1; i < TPB / 64; ++i) { mn = pmin(mn, l_mn[i]); mx = pmax(mx, l_mx[i]); }
-        pmm[(size_t)(2 * s) * g.C + c] = mn;
-        pmm[(size_t)(2 * s + 1) * g.C + c] = mx;
+        pmm[(size_t)(2 * t.s) * g.C + t.c] = mn;
+        pmm[(size_t)(2 * t.s + 1) * g.C + t.c] = mx;
     }
 }
 
@@ -201,11 +278,8 @@ __global__ void __launch_bounds__(TPB) k_h_minmax(const uint16_t* __restrict__ x
 template <class T, int W>
 __global__ void __launch_bounds__(TPB) k_h_qdq(const uint16_t* __restrict__ x, uint16_t* __restrict__ y, const HGeo g,
                                                const float* __restrict__ qp, const float* __restrict__ pmm, const HArgs ha) {
-    const int bid = (int)gridDim.x - 1 - (int)blockIdx.x;
-    const int c = bid % g.C, s = bid / g.C;
-    int n0, n1;
-    h_split(g, s, n0, n1);
-    const int rows = n1 - n0;
+    const HPart t = h_part<W, false>(g, (int)gridDim.x - 1 - (int)blockIdx.x);
+    const int c = t.c;
     float sc, zp, qm;
     bool fast = false;
     if (pmm) {
@@ -216,19 +290,16 @@ __global__ void __launch_bounds__(TPB) k_h_qdq(const uint16_t* __restrict__ x, u
         }
         h_params(mn, mx, ha.num_bits, ha.positive, sc, zp, qm);
         fast = qdq_fast_domain(mn, mx, sc);
-        if (s == 0 && threadIdx.x == 0) h_publish(ha, g.C, c, mn, mx, sc, zp, qm);
+        if (t.s == 0 && threadIdx.x == 0) h_publish(ha, g.C, c, mn, mx, sc, zp, qm);
     } else {
-        sc = qp[(size_t)CNNQ_QP_SCALE * g.C + c];
-        zp = qp[(size_t)CNNQ_QP_ZP * g.C + c];
-        qm = qp[(size_t)CNNQ_QP_QMAX * g.C + c];
+        h_qp(qp, g.C, c, sc, zp, qm);
     }
     const bool ufast = __builtin_amdgcn_readfirstlane((int)fast) != 0;
     const float rs = ufast ? uniform_f(1.0f / sc) : 0.f;
     const size_t P = (size_t)g.C * (size_t)g.HW;
-    const size_t off0 = (size_t)n0 * P + (size_t)c * g.HW;
     HWalk w = h_walk(g.ppr);
-    for (; w.r < rows; h_step(w, g.ppr)) {
-        const size_t off = off0 + (size_t)w.r * P + (size_t)w.p * W;
+    for (; w.r < t.rows; h_step(w, g.ppr)) {
+        const size_t off = t.off + (size_t)w.r * P + (size_t)w.p * W;
         uint16_t e[W];
         h_ld<W, true>(x + off, e);
         h_qdq_piece<T, W>(e, ufast, sc, rs, zp, qm);
@@ -241,68 +312,102 @@ __global__ void __launch_bounds__(TPB) k_h_qdq(const uint16_t* __restrict__ x, u
 // elements per workgroup of an fp32 tile of the same registers, doubled.  Extrema (workgroup reduction), parameters (h_params),
 // Q/DQ out of the registers, store.  One workgroup per channel; no exchange, no workspace.  qp and mm are written.
 constexpr int HTPB = 1024;
+
+// The resident tile of the single-launch kernels: one channel's whole batch population in the registers of one HTPB-lane
+// workgroup, K pieces of W >= 2 elements per lane, kept as loaded (packed).  Every phase walks the same (row, piece) pairs again
+// from the lane's first pair: the K offsets are not kept (K more 64-bit registers).
+template <int W, int K>
+struct HTile {
+    static_assert(W >= 2, "the resident tile keeps packed pieces");
+    typedef uint16_t S __attribute__((ext_vector_type(W)));
+    S t[K];
+    HWalk w0;
+    int N, ppr;
+    size_t P;
+    __device__ __forceinline__ explicit HTile(const HGeo& g)
+        : w0(h_walk<HTPB>(g.ppr)), N(g.N), ppr(g.ppr), P((size_t)g.C * (size_t)g.HW) {}
+    // f(k, the pair) for the pairs this lane holds; at(channel, pair): where the pair's piece lies
+    template <class F>
+    __device__ __forceinline__ void walk(HWalk w, F&& f) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (w.r < N) f(k, w);
+            h_step(w, ppr);
+        }
+    }
+    template <class Q>
+    __device__ __forceinline__ Q* at(Q* c, const HWalk& w) const { return c + (size_t)w.r * P + (size_t)w.p * W; }
+    static __device__ __forceinline__ void unpack(const S& s, uint16_t (&e)[W]) {
+#pragma unroll
+        for (int i = 0; i < W; ++i) e[i] = (uint16_t)s[i];
+    }
+    // the non-temporal load of the tile from channel xc; f(e) on each piece as it arrives
+    template <class F>
+    __device__ __forceinline__ void load(const uint16_t* xc, F&& f) {
+        walk(w0, [&](int k, const HWalk& w) {
+            t[k] = __builtin_nontemporal_load(reinterpret_cast<const S*>(at(xc, w)));
+            uint16_t e[W];
+            unpack(t[k], e);
+            f(e);
+        });
+    }
+    __device__ __forceinline__ void load(const uint16_t* xc) {
+        load(xc, [](const uint16_t (&)[W]) {});
+    }
+    // f(e) on each held piece
+    template <class F>
+    __device__ __forceinline__ void each(F&& f) {
+        walk(w0, [&](int k, const HWalk&) {
+            uint16_t e[W];
+            unpack(t[k], e);
+            f(e);
+        });
+    }
+    // what f leaves of each held piece -> channel yc, non-temporally.  The walk starts from an opaque copy of the first pair, or
+    // the compiler keeps the offsets of the phases before alive across the reduction in between.  OPAQUE: the piece too is
+    // unpacked from an opaque copy (k_h_bcorr_whole says why).
+    template <bool OPAQUE, class F>
+    __device__ __forceinline__ void store(uint16_t* yc, F&& f) {
+        HWalk w = w0;
+        asm volatile("" : "+v"(w.r), "+v"(w.p));
+        walk(w, [&](int k, const HWalk& wk) {
+            uint16_t e[W];
+            if constexpr (OPAQUE) {
+                S tk = t[k];
+                asm volatile("" : "+v"(tk));
+                unpack(tk, e);
+            } else {
+                // element by element, not through unpack's reference: k_h_whole<HF16, 2, 64> spills 56 VGPRs that way
+                // (profiles/half_shared.md lists the resident instances' registers, to compare after a compiler change)
+#pragma unroll
+                for (int i = 0; i < W; ++i) e[i] = (uint16_t)t[k][i];
+            }
+            f(e);
+            S o;
+#pragma unroll
+            for (int i = 0; i < W; ++i) o[i] = e[i];
+            __builtin_nontemporal_store(o, reinterpret_cast<S*>(at(yc, wk)));
+        });
+    }
+};
+
 template <class T, int W, int K>
 __global__ void __launch_bounds__(HTPB) k_h_whole(const uint16_t* __restrict__ x, uint16_t* __restrict__ y, const HGeo g,
                                                   const HArgs ha) {
-    static_assert(W >= 2, "k_h_whole keeps packed pieces");
-    typedef typename HPiece<W>::vec_t S;
     __shared__ float l_mn[HTPB / 64], l_mx[HTPB / 64];
     const int c = (int)blockIdx.x;
-    const size_t P = (size_t)g.C * (size_t)g.HW;
-    const uint16_t* xc = x + (size_t)c * g.HW;
-    uint16_t* yc = y + (size_t)c * g.HW;
-    S t[K];
+    HTile<W, K> tile(g);
     float mn = INFINITY, mx = -INFINITY;
     bool nan = false;
-    const HWalk w0 = h_walk<HTPB>(g.ppr);
-    HWalk w = w0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (w.r < g.N) {
-            t[k] = __builtin_nontemporal_load(reinterpret_cast<const S*>(xc + (size_t)w.r * P + (size_t)w.p * W));
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                const float v = h_up(T{}, (uint16_t)t[k][i]);
-                mn = fminf(mn, v);
-                mx = fmaxf(mx, v);
-                nan |= v != v;
-            }
-        }
-        h_step(w, g.ppr);
-    }
+    tile.load(x + (size_t)c * g.HW, [&](const uint16_t (&e)[W]) { h_mm_piece<T, W>(e, mn, mx, nan); });
     if (nan) { mn = NAN; mx = NAN; }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { mn = pmin(mn, shfl_xor_f(mn, m)); mx = pmax(mx, shfl_xor_f(mx, m)); }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { l_mn[wv] = mn; l_mx[wv] = mx; }
-    __syncthreads();
-    mn = l_mn[0];
-    mx = l_mx[0];
-    for (int i = 1; i < HTPB / 64; ++i) { mn = pmin(mn, l_mn[i]); mx = pmax(mx, l_mx[i]); }
+    h_fold_mm(l_mn, l_mx, mn, mx);
     float sc, zp, qm;
     h_params(mn, mx, ha.num_bits, ha.positive, sc, zp, qm);
     if (threadIdx.x == 0) h_publish(ha, g.C, c, mn, mx, sc, zp, qm);
     const bool ufast = __builtin_amdgcn_readfirstlane((int)qdq_fast_domain(mn, mx, sc)) != 0;
     const float rs = ufast ? uniform_f(1.0f / sc) : 0.f;
-    // the walk again (its offsets are not kept across the reduction: K more 64-bit registers)
-    w = w0;
-    asm volatile("" : "+v"(w.r), "+v"(w.p));
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (w.r < g.N) {
-            uint16_t e[W];
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                e[i] = (uint16_t)t[k][i];
-            }
-            h_qdq_piece<T, W>(e, ufast, sc, rs, zp, qm);
-            S o;
-#pragma unroll
-            for (int i = 0; i < W; ++i) o[i] = e[i];
-            __builtin_nontemporal_store(o, reinterpret_cast<S*>(yc + (size_t)w.r * P + (size_t)w.p * W));
-        }
-        h_step(w, g.ppr);
-    }
+    tile.template store<false>(y + (size_t)c * g.HW, [&](uint16_t (&e)[W]) { h_qdq_piece<T, W>(e, ufast, sc, rs, zp, qm); });
 }
 // K of the resident tile for a piece width: 64 VGPRs of packed elements
 // Not for W = 1 (2-byte elements, one per VGPR): measured slower than the two launches on the 7x7 layers of ResNet-50 b512

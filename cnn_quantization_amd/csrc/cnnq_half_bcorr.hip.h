@@ -9,11 +9,13 @@
 // every output bit for bit - bias is k_bcorr_bias' arithmetic (bcorr_bias_of), y is k_qdq_bias' expression on the exactly
 // upconverted values with one round-to-nearest-even into the element type at the end (h_down).
 //
-// Tiling: the row walk of cnnq_half.hip.h (HGeo, HWalk, h_piece) and the partition of cnnq_half_stats.hip.h (h_part: batch splits
-// S, column splits cs).  A workgroup owns ONE channel, so scale / zero point / qmax / bias are uniform.  Sums: the W values of one
-// piece are added in fp32 - pairs, then the two halves, h_mom_piece's order - and the piece sums are accumulated in fp64; a single
-// element (W = 1) goes into fp64 as it is.  The order of every addition follows from HGeo alone: the xor tree inside the wave, the
-// waves in order through LDS, every record entry stored once by one lane - no atomics, run after run the same bits.
+// The partition (h_part: batch splits S, column splits cs), the piece loop (h_pieces), the table row (h_qp), the fold of the sums
+// (h_fold_sums) and the resident tile (HTile) are the family's shared ones in cnnq_half.hip.h; this header holds the arithmetic
+// of the correction and its routes.  A workgroup owns ONE channel, so scale / zero point / qmax / bias are uniform.  Sums: the W
+// values of one piece are added in fp32 - pairs, then the two halves, h_mom_piece's order - and the piece sums are accumulated in
+// fp64; a single element (W = 1) goes into fp64 as it is.  The order of every addition follows from HGeo alone: the xor tree
+// inside the wave, the waves in order through LDS, every record entry stored once by one lane - no atomics, run after run the
+// same bits.
 #pragma once
 #include "cnnq_half_stats.hip.h"
 #include "cnnq_corrections.hip.h"
@@ -59,47 +61,27 @@ __device__ __forceinline__ void h_bc_piece(const uint16_t (&e)[W], const bool re
     }
 }
 
-// the lanes' sums -> the workgroup's, in every lane: the fixed xor tree inside the wave, then the NW waves in wave order through
-// LDS.  The count is an integer below 2^53: exact in fp64 whatever the order.
-template <int NW>
-__device__ __forceinline__ void h_bc_fold(double (&l_x)[NW], double (&l_q)[NW], double (&l_c)[NW], double& sx, double& sq, double& sc) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { sx += shfl_xor_d(sx, m); sq += shfl_xor_d(sq, m); sc += shfl_xor_d(sc, m); }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { l_x[wv] = sx; l_q[wv] = sq; l_c[wv] = sc; }
-    __syncthreads();
-    sx = 0.; sq = 0.; sc = 0.;
-    for (int i = 0; i < NW; ++i) { sx += l_x[i]; sq += l_q[i]; sc += l_c[i]; }
-}
-
 // pass 1, read-only: record s of channel c -> part3[s][3][C] = {sum x', sum q, count(x' > 0)}, the arithmetic of
 // k_bcorr_sums<FROMX> and k_cl_bcorr_sums.  Workgroups ascend; the second pass descends and re-reads first what was read last.
+// The count is an integer below 2^53: exact in fp64 whatever the order of the fold.
 template <class T, int W>
 __global__ void __launch_bounds__(TPB) k_h_bcorr_sums(const uint16_t* __restrict__ x, const HGeo g, const int relu_first,
                                                       const float* __restrict__ qp, double* __restrict__ part3) {
-    __shared__ double l_x[TPB / 64], l_q[TPB / 64], l_c[TPB / 64];
-    const HPart t = h_part<W>(x, g, (int)blockIdx.x);
-    const size_t P = (size_t)g.C * (size_t)g.HW;
-    const float sc = qp[(size_t)CNNQ_QP_SCALE * g.C + t.c];
-    const float zp = qp[(size_t)CNNQ_QP_ZP * g.C + t.c];
-    const float qm = qp[(size_t)CNNQ_QP_QMAX * g.C + t.c];
+    __shared__ double l_v[3][TPB / 64];
+    const HPart t = h_part<W>(g, (int)blockIdx.x);
+    float sc, zp, qm;
+    h_qp(qp, g.C, t.c, sc, zp, qm);
     const bool relu = relu_first != 0;
     double sx = 0., sq = 0.;
-    unsigned cn = 0u;                        // exact: a lane reads fewer than 2^32 elements (at most H_ST_MAX_RECORDS-th of a channel)
-    HWalk w = h_walk(t.pw);
-#pragma unroll 2
-    for (; w.r < t.rows; h_step(w, t.pw)) {
-        uint16_t e[W];
-        h_ld<W, false>(t.base + (size_t)w.r * P + (size_t)w.p * W, e);
-        h_bc_piece<T, W>(e, relu, sc, zp, qm, sx, sq, cn);
-    }
-    double dc = (double)cn;
-    h_bc_fold<TPB / 64>(l_x, l_q, l_c, sx, sq, dc);
+    unsigned cn = 0u;          // exact: a lane reads fewer than 2^32 elements (at most H_ST_MAX_RECORDS-th of a channel)
+    h_pieces<W, 2>(x + t.off, g, t, [&](const uint16_t (&e)[W]) { h_bc_piece<T, W>(e, relu, sc, zp, qm, sx, sq, cn); });
+    double v[3] = {sx, sq, (double)cn};
+    h_fold_sums(l_v, v);
     if (threadIdx.x == 0) {
         double* p = part3 + (size_t)t.s * 3 * g.C + t.c;
-        p[0] = sx;
-        p[(size_t)g.C] = sq;
-        p[(size_t)2 * g.C] = dc;
+        p[0] = v[0];
+        p[(size_t)g.C] = v[1];
+        p[(size_t)2 * g.C] = v[2];
     }
 }
 
@@ -118,20 +100,14 @@ __device__ __forceinline__ void h_qdq_bias_piece(uint16_t (&e)[W], const float s
 template <class T, int W>
 __global__ void __launch_bounds__(TPB) k_h_qdq_bias(const uint16_t* __restrict__ x, uint16_t* __restrict__ y, const HGeo g,
                                                     const float* __restrict__ qp, const float* __restrict__ bias) {
-    const int bid = (int)gridDim.x - 1 - (int)blockIdx.x;
-    const int c = bid % g.C, s = bid / g.C;
-    int n0, n1;
-    h_split(g, s, n0, n1);
-    const int rows = n1 - n0;
-    const float sc = qp[(size_t)CNNQ_QP_SCALE * g.C + c];
-    const float zp = qp[(size_t)CNNQ_QP_ZP * g.C + c];
-    const float qm = qp[(size_t)CNNQ_QP_QMAX * g.C + c];
-    const float qb = bias[c];
+    const HPart t = h_part<W, false>(g, (int)gridDim.x - 1 - (int)blockIdx.x);
+    float sc, zp, qm;
+    h_qp(qp, g.C, t.c, sc, zp, qm);
+    const float qb = bias[t.c];
     const size_t P = (size_t)g.C * (size_t)g.HW;
-    const size_t off0 = (size_t)n0 * P + (size_t)c * g.HW;
     HWalk w = h_walk(g.ppr);
-    for (; w.r < rows; h_step(w, g.ppr)) {
-        const size_t off = off0 + (size_t)w.r * P + (size_t)w.p * W;
+    for (; w.r < t.rows; h_step(w, g.ppr)) {
+        const size_t off = t.off + (size_t)w.r * P + (size_t)w.p * W;
         uint16_t e[W];
         h_ld<W, true>(x + off, e);
         h_qdq_bias_piece<T, W>(e, sc, zp, qm, qb);
@@ -140,73 +116,33 @@ __global__ void __launch_bounds__(TPB) k_h_qdq_bias(const uint16_t* __restrict__
 }
 
 // Both passes in ONE launch and ONE read of x (4 B/elem) for channels whose whole batch population fits one workgroup's
-// registers; k_h_whole's tile: HTPB lanes, K pieces of W >= 2 elements each, kept as loaded.  The three sums out of the registers
-// (the piece arithmetic above, the same fold: the xor tree, then the 16 waves in order), the bias in every lane (bcorr_bias_of),
-// quantize + correct out of the registers, store.  One workgroup per channel; no exchange, no workspace.  Lane 0 publishes
-// sums[3][C] (may be null) and bias[c].
+// registers, on k_h_whole's resident tile (HTile): the three sums out of the registers (the piece arithmetic above, the same
+// fold: the xor tree, then the 16 waves in order), the bias in every lane (bcorr_bias_of), quantize + correct out of the
+// registers, store.  One workgroup per channel; no exchange, no workspace.  Lane 0 publishes sums[3][C] (may be null) and bias[c].
 template <class T, int W, int K>
 __global__ void __launch_bounds__(HTPB) k_h_bcorr_whole(const uint16_t* __restrict__ x, uint16_t* __restrict__ y, const HGeo g,
                                                         const int relu_first, const float* __restrict__ qp,
                                                         double* __restrict__ sums, float* __restrict__ bias) {
-    static_assert(W >= 2, "k_h_bcorr_whole keeps packed pieces");
-    typedef typename HPiece<W>::vec_t S;
-    __shared__ double l_x[HTPB / 64], l_q[HTPB / 64], l_c[HTPB / 64];
+    __shared__ double l_v[3][HTPB / 64];
     const int c = (int)blockIdx.x;
-    const size_t P = (size_t)g.C * (size_t)g.HW;
-    const uint16_t* xc = x + (size_t)c * g.HW;
-    uint16_t* yc = y + (size_t)c * g.HW;
-    const float sc = qp[(size_t)CNNQ_QP_SCALE * g.C + c];
-    const float zp = qp[(size_t)CNNQ_QP_ZP * g.C + c];
-    const float qm = qp[(size_t)CNNQ_QP_QMAX * g.C + c];
+    float sc, zp, qm;
+    h_qp(qp, g.C, c, sc, zp, qm);
     const bool relu = relu_first != 0;
-    S t[K];
-    const HWalk w0 = h_walk<HTPB>(g.ppr);
-    HWalk w = w0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (w.r < g.N) t[k] = __builtin_nontemporal_load(reinterpret_cast<const S*>(xc + (size_t)w.r * P + (size_t)w.p * W));
-        h_step(w, g.ppr);
-    }
+    HTile<W, K> tile(g);
+    tile.load(x + (size_t)c * g.HW);
     double sx = 0., sq = 0.;
     unsigned cn = 0u;
-    w = w0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (w.r < g.N) {
-            uint16_t e[W];
-#pragma unroll
-            for (int i = 0; i < W; ++i) e[i] = (uint16_t)t[k][i];
-            h_bc_piece<T, W>(e, relu, sc, zp, qm, sx, sq, cn);
-        }
-        h_step(w, g.ppr);
-    }
-    double dc = (double)cn;
-    h_bc_fold<HTPB / 64>(l_x, l_q, l_c, sx, sq, dc);
-    const float qb = bcorr_bias_of(sx, sq, dc);
+    tile.each([&](const uint16_t (&e)[W]) { h_bc_piece<T, W>(e, relu, sc, zp, qm, sx, sq, cn); });
+    double v[3] = {sx, sq, (double)cn};
+    h_fold_sums(l_v, v);
+    const float qb = bcorr_bias_of(v[0], v[1], v[2]);
     if (threadIdx.x == 0) {
-        if (sums) { sums[c] = sx; sums[(size_t)g.C + c] = sq; sums[(size_t)2 * g.C + c] = dc; }
+        if (sums) { sums[c] = v[0]; sums[(size_t)g.C + c] = v[1]; sums[(size_t)2 * g.C + c] = v[2]; }
         bias[c] = qb;
     }
-    // the walk again (its offsets are not kept across the reduction: K more 64-bit registers), and the upconversions again: from
-    // an opaque copy of the piece, or the compiler keeps the 128 fp32 values of the sums phase alive across the fold
-    w = w0;
-    asm volatile("" : "+v"(w.r), "+v"(w.p));
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if (w.r < g.N) {
-            S tk = t[k];
-            asm volatile("" : "+v"(tk));
-            uint16_t e[W];
-#pragma unroll
-            for (int i = 0; i < W; ++i) e[i] = (uint16_t)tk[i];
-            h_qdq_bias_piece<T, W>(e, sc, zp, qm, qb);
-            S o;
-#pragma unroll
-            for (int i = 0; i < W; ++i) o[i] = e[i];
-            __builtin_nontemporal_store(o, reinterpret_cast<S*>(yc + (size_t)w.r * P + (size_t)w.p * W));
-        }
-        h_step(w, g.ppr);
-    }
+    // the upconversions again, from an opaque copy of each piece: or the compiler keeps the 128 fp32 values of the sums phase
+    // alive across the fold
+    tile.template store<true>(y + (size_t)c * g.HW, [&](uint16_t (&e)[W]) { h_qdq_bias_piece<T, W>(e, sc, zp, qm, qb); });
 }
 
 // ---- host side: which classes of layer run where (cnnq_pc_route_qdq_bcorr_dt's route word), functions of N, C, HW and the dtype

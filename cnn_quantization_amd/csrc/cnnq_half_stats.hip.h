@@ -2,9 +2,12 @@
 // that fill the seven rows of the calibration table (smpc.py:45-79), read where the tensor lies - two reads of x, 4 B/elem, no
 // fp32 copy.  Part of the single translation unit cnnq_kernels.hip (see its header for the design).
 //
-// Tiling: the row walk of cnnq_half.hip.h (HGeo, HWalk, h_piece).  A workgroup owns ONE channel and a range of samples, or - short
-// batches - a range of the pieces of its rows (k_h_minmax's column splits); workgroup b = s * C + c, s = batch split * cs + column
-// part.  Every element is upconverted exactly (h_up), so the extrema are the fp32 path's extrema on x.float().
+// The partition (h_part), the piece loop (h_pieces) and the workgroup folds (h_fold_mm, h_fold_sums) are the family's shared
+// ones in cnnq_half.hip.h; this header holds the arithmetic of the two passes and their plan.
+//
+// Tiling: a workgroup owns ONE channel and a range of samples, or - short batches - a range of the pieces of its rows
+// (k_h_minmax's column splits); workgroup b = s * C + c, s = batch split * cs + column part.  Every element is upconverted
+// exactly (h_up), so the extrema are the fp32 path's extrema on x.float().
 //
 // Sums: the W values of one piece are added in fp32 - packed pairs, then the two halves, the order of
 // Mom::add8 / add4p - and the piece sums are accumulated in fp64; a single element (W = 1) goes into fp64 as it is.  Pass B forms
@@ -17,26 +20,6 @@
 #include "cnnq_stats.hip.h"
 
 namespace {
-
-// what the workgroup `bid` of a C * S * cs grid owns: channel c, record s, rows [0, rows) from `base`, pw pieces of each
-struct HPart {
-    int c, s, rows, pw;
-    const uint16_t* base;
-};
-template <int W>
-__device__ __forceinline__ HPart h_part(const uint16_t* __restrict__ x, const HGeo& g, int bid) {
-    HPart t;
-    t.c = bid % g.C;
-    t.s = bid / g.C;
-    const int sn = t.s / g.cs, sp = t.s - sn * g.cs;
-    int n0, n1;
-    h_split(g, sn, n0, n1);
-    t.rows = n1 - n0;
-    const int p0 = (int)(((int64_t)sp * g.ppr) / g.cs);
-    t.pw = (int)(((int64_t)(sp + 1) * g.ppr) / g.cs) - p0;
-    t.base = x + (size_t)n0 * ((size_t)g.C * (size_t)g.HW) + (size_t)t.c * g.HW + (size_t)p0 * W;
-    return t;
-}
 
 // one piece into the running record.  fminf / fmaxf drop a NaN; the sum of squares keeps it (squares do not cancel, inf * inf is
 // inf), so a lane whose sum of squares came out NaN saw one and poisons its pair afterwards - k_h_minmax's rule, k_moments' test.
@@ -86,40 +69,26 @@ __device__ __forceinline__ void h_mom_piece(Mom& m, const uint16_t (&e)[W]) {
     }
 }
 
-// pass A: record s of channel c -> part[s][CNNQ_NMOM][C]; the count is the exact number of elements the workgroup read
+// pass A: record s of channel c -> part[s][CNNQ_NMOM][C]; the count is the exact number of elements the workgroup read.  The
+// lanes' records meet in the shared folds (h_fold_mm, h_fold_sums): Mom::wave_reduce / merge in the same order, addition by addition
 template <class T, int W, bool RELU>
 __global__ void __launch_bounds__(TPB) k_h_moments(const uint16_t* __restrict__ x, const HGeo g, double* __restrict__ part) {
+    constexpr int NV = RELU ? 4 : 2;
     __shared__ float l_mn[TPB / 64], l_mx[TPB / 64];
-    __shared__ double l_s[TPB / 64], l_ss[TPB / 64], l_rs[RELU ? TPB / 64 : 1], l_rss[RELU ? TPB / 64 : 1];
-    const HPart t = h_part<W>(x, g, (int)blockIdx.x);
-    const size_t P = (size_t)g.C * (size_t)g.HW;
+    __shared__ double l_v[NV][TPB / 64];
+    const HPart t = h_part<W>(g, (int)blockIdx.x);
     Mom m;
     m.init();
-    HWalk w = h_walk(t.pw);
-#pragma unroll 4
-    for (; w.r < t.rows; h_step(w, t.pw)) {
-        uint16_t e[W];
-        h_ld<W, false>(t.base + (size_t)w.r * P + (size_t)w.p * W, e);
-        h_mom_piece<T, W, RELU>(m, e);
-    }
+    h_pieces<W, 4>(x + t.off, g, t, [&](const uint16_t (&e)[W]) { h_mom_piece<T, W, RELU>(m, e); });
     if (m.ss != m.ss) { m.mn = NAN; m.mx = NAN; }
-    m.template wave_reduce<RELU>();
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        l_mn[wv] = m.mn; l_mx[wv] = m.mx; l_s[wv] = m.s; l_ss[wv] = m.ss;
-        if constexpr (RELU) { l_rs[wv] = m.rs; l_rss[wv] = m.rss; }
-    }
-    __syncthreads();
+    h_fold_mm(l_mn, l_mx, m.mn, m.mx);
+    double v[NV] = {m.s, m.ss};
+    if constexpr (RELU) { v[2] = m.rs; v[3] = m.rss; }
+    h_fold_sums(l_v, v);
     if (threadIdx.x == 0) {
-        Mom r;
-        r.init();
-        for (int i = 0; i < TPB / 64; ++i) {     // the four wave records in wave order
-            Mom o;
-            o.mn = l_mn[i]; o.mx = l_mx[i]; o.s = l_s[i]; o.ss = l_ss[i];
-            if constexpr (RELU) { o.rs = l_rs[i]; o.rss = l_rss[i]; }
-            r.template merge<RELU>(o);
-        }
-        write_mom<RELU>(part, t.s, g.C, t.c, r, (double)t.rows * (double)t.pw * W);
+        m.s = v[0]; m.ss = v[1];
+        if constexpr (RELU) { m.rs = v[2]; m.rss = v[3]; }
+        write_mom<RELU>(part, t.s, g.C, t.c, m, (double)t.rows * (double)t.pw * W);
     }
 }
 
@@ -132,17 +101,13 @@ template <class T, int W, bool KURT>
 __global__ void __launch_bounds__(TPB) k_h_absdev(const uint16_t* __restrict__ x, const HGeo g, const float* __restrict__ stats,
                                                   double* __restrict__ part2) {
     typedef float f2 __attribute__((ext_vector_type(2)));
-    __shared__ double l_a[TPB / 64], l_k[KURT ? TPB / 64 : 1];
-    const HPart t = h_part<W>(x, g, (int)gridDim.x - 1 - (int)blockIdx.x);
-    const size_t P = (size_t)g.C * (size_t)g.HW;
+    constexpr int NV = KURT ? 2 : 1;
+    __shared__ double l_v[NV][TPB / 64];
+    const HPart t = h_part<W>(g, (int)gridDim.x - 1 - (int)blockIdx.x);
     const float mean = stats[(size_t)CNNQ_STAT_MEAN * g.C + t.c];
     const float sd = KURT ? 1.f / stats[(size_t)CNNQ_STAT_STD * g.C + t.c] : 0.f;
     double sa0 = 0., sa1 = 0., sk0 = 0., sk1 = 0.;
-    HWalk w = h_walk(t.pw);
-#pragma unroll 4
-    for (; w.r < t.rows; h_step(w, t.pw)) {
-        uint16_t e[W];
-        h_ld<W, false>(t.base + (size_t)w.r * P + (size_t)w.p * W, e);
+    h_pieces<W, 4>(x + t.off, g, t, [&](const uint16_t (&e)[W]) {
         if constexpr (W == 1) {
             const float d = h_up(T{}, e[0]) - mean;
             sa0 += (double)fabsf(d);
@@ -167,22 +132,14 @@ __global__ void __launch_bounds__(TPB) k_h_absdev(const uint16_t* __restrict__ x
                 }
             }
         }
-    }
-    double sa = sa0 + sa1, sk = sk0 + sk1;
-#pragma unroll
-    for (int msk = 32; msk >= 1; msk >>= 1) {
-        sa += shfl_xor_d(sa, msk);
-        if constexpr (KURT) sk += shfl_xor_d(sk, msk);
-    }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { l_a[wv] = sa; if constexpr (KURT) l_k[wv] = sk; }
-    __syncthreads();
+    });
+    double v[NV] = {sa0 + sa1};
+    if constexpr (KURT) v[1] = sk0 + sk1;
+    h_fold_sums(l_v, v);
     if (threadIdx.x == 0) {
-        double ra = 0., rk = 0.;
-        for (int i = 0; i < TPB / 64; ++i) { ra += l_a[i]; if constexpr (KURT) rk += l_k[i]; }
         double* p = part2 + (size_t)t.s * CNNQ_NDEV * g.C + t.c;
-        p[(size_t)CNNQ_DEV_ABS * g.C] = ra;
-        p[(size_t)CNNQ_DEV_Z4 * g.C] = KURT ? rk : 0.;
+        p[(size_t)CNNQ_DEV_ABS * g.C] = v[0];
+        p[(size_t)CNNQ_DEV_Z4 * g.C] = KURT ? v[NV - 1] : 0.;
     }
 }
 

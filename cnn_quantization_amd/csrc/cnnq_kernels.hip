@@ -182,6 +182,18 @@ inline int cl_launch(int dtype, int w, const void* x, F&& f) {
     return cl_launch(dtype, w, x, nullptr, [&](auto pc, auto* xr, auto*) { f(pc, xr); });
 }
 
+// The same for the contiguous bf16 / fp16 kernels (cnnq_half*.hip.h), whose elements are 2-byte words whatever the type:
+// f(Piece<T, W>, const uint16_t* x, uint16_t* y), or f(Piece<T, W>, const uint16_t* x); the launch's status
+template <class F>
+inline int h_launch(int dtype, int w, const void* x, void* y, F&& f) {
+    with_piece<false>(dtype, w, [&](auto pc) { f(pc, static_cast<const uint16_t*>(x), static_cast<uint16_t*>(y)); });
+    return launch_status();
+}
+template <class F>
+inline int h_launch(int dtype, int w, const void* x, F&& f) {
+    return h_launch(dtype, w, x, nullptr, [&](auto pc, const uint16_t* xh, uint16_t*) { f(pc, xh); });
+}
+
 inline bool dtype_ok(int dtype) { return dtype >= 0 && dtype < CNNQ_NDTYPE; }
 
 inline int cl_check(int64_t R, int64_t C, int dtype) {
@@ -1544,6 +1556,13 @@ static int h_align(const void* x, const void* y) {
     return (int)(a & (~a + 1));
 }
 
+// the fp32 plan's record count at either alignment (what bounds the extrema's partials, and what the fp32 correction chain
+// writes); <= 0: cnnq_pc_groups' code
+static int h_records_f32(int64_t N, int64_t C, int64_t HW) {
+    const int g1 = cnnq_pc_groups(N, C, HW, 1), g0 = cnnq_pc_groups(N, C, HW, 0);
+    return g1 > g0 ? g1 : g0;
+}
+
 // config 2's route for a bf16 / fp16 tensor: out = {1: the single launch k_h_whole / 2: the chain, piece width W, pieces per lane K
 // (0 for the chain), workgroups of the Q/DQ launch}
 static int h_route(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_single_launch, int32_t out[4]) {
@@ -1560,44 +1579,34 @@ static int h_route(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_
 
 // the statistics half of the chain: per-split extrema into pmm[S][2][C], S <= the fp32 plan's G (the callers' workspace rule)
 static int h_minmax(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, float* pmm, int* S, hipStream_t st) {
-    const int g1 = cnnq_pc_groups(N, C, HW, 1), g0 = cnnq_pc_groups(N, C, HW, 0);
-    const int G = g1 > g0 ? g1 : g0;
+    const int G = h_records_f32(N, C, HW);
     if (G <= 0) return g_error(G);
-    HGeo g;
-    g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
     const int w = h_piece(HW, (uintptr_t)x, 0);
-    g.ppr = (int)(HW / w);
     // ~H_MM_ELEMS per workgroup: batch splits first, then (short batches: config 1's rows, N = 1) column splits of the rows
     const int total = h_splits(N * HW, C, 1, H_MM_ELEMS, G);
-    g.S = total < N ? total : (int)N;
-    g.cs = total / g.S < g.ppr ? total / g.S : g.ppr;
-    const uint16_t* xh = static_cast<const uint16_t*>(x);
-    with_piece<false>(dtype, w, [&](auto pc) {
+    const int bs = total < N ? total : (int)N, ppr = (int)(HW / w);
+    const HGeo g = h_geo(N, C, HW, w, bs, total / bs < ppr ? total / bs : ppr);
+    *S = g.S * g.cs;
+    return h_launch(dtype, w, x, [&](auto pc, const uint16_t* xh) {
         using P = decltype(pc);
         hipLaunchKernelGGL((k_h_minmax<typename P::T, P::W>), dim3((unsigned)(C * g.S * g.cs)), dim3(TPB), 0, st, xh, g, pmm);
     });
-    *S = g.S * g.cs;
-    return launch_status();
 }
+
+// the element-wise pass of every chain: ~H_QDQ_ELEMS per workgroup, whole rows
+static HGeo h_geo_qdq(int64_t N, int64_t C, int64_t HW, int w) { return h_geo(N, C, HW, w, h_splits(N, C, HW, H_QDQ_ELEMS, N), 1); }
 
 // pmm == NULL: the parameters from the table qp; else from the statistics partials pmm (published to ha.qp / ha.mm, k_h_qdq)
 static int h_qdq(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, const float* pmm, const HArgs& ha,
                  hipStream_t st) {
     const int rc = cnnq_pc_groups(N, C, HW, 0);    // the fp32 entry points' geometry limits
     if (rc <= 0) return g_error(rc);
-    HGeo g;
-    g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
-    g.S = h_splits(N, C, HW, H_QDQ_ELEMS, N);
-    g.cs = 1;
     const int w = h_piece(HW, (uintptr_t)x, (uintptr_t)y);
-    g.ppr = (int)(HW / w);
-    const uint16_t* xh = static_cast<const uint16_t*>(x);
-    uint16_t* yh = static_cast<uint16_t*>(y);
-    with_piece<false>(dtype, w, [&](auto pc) {
+    const HGeo g = h_geo_qdq(N, C, HW, w);
+    return h_launch(dtype, w, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
         using P = decltype(pc);
         hipLaunchKernelGGL((k_h_qdq<typename P::T, P::W>), dim3((unsigned)(C * g.S)), dim3(TPB), 0, st, xh, yh, g, qp, pmm, ha);
     });
-    return launch_status();
 }
 
 int cnnq_pc_route_dt(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_single_launch, int32_t out[4]) {
@@ -1619,18 +1628,14 @@ int cnnq_pc_minmax_qdq_auto_dt(const void* x, void* y, int dtype, int64_t N, int
     int rc = h_route(N, C, HW, h_align(x, y), allow_single_launch, route);
     if (rc) return rc;
     if (route[0] == 1) {
-        HGeo g;
-        g.N = (int)N; g.C = (int)C; g.HW = (int)HW; g.S = 1; g.cs = 1;
-        g.ppr = (int)(HW / route[1]);
+        const HGeo g = h_geo(N, C, HW, route[1], 1, 1);
         const HArgs ha{0, num_bits, positive ? 1 : 0, qp, mm};
-        const uint16_t* xh = static_cast<const uint16_t*>(x);
-        uint16_t* yh = static_cast<uint16_t*>(y);
-        with_piece<false>(dtype, route[1] >= 4 ? route[1] : 2, [&](auto pc) {      // (no whole-tensor instance of single elements)
+        const int w = route[1] >= 4 ? route[1] : 2;      // (no whole-tensor instance of single elements)
+        return h_launch(dtype, w, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
             using P = decltype(pc);
             if constexpr (P::W > 1)
                 hipLaunchKernelGGL((k_h_whole<typename P::T, P::W, h_whole_k<P::W>()>), dim3((unsigned)C), dim3(HTPB), 0, st, xh, yh, g, ha);
         });
-        return launch_status();
     }
     int S = 0;
     rc = h_minmax(x, dtype, N, C, HW, pmm, &S, st);
@@ -1660,45 +1665,44 @@ int cnnq_pc_minmax_local_dt(const void* x, int dtype, int64_t N, int64_t C, int6
 }
 
 // ---- `-sm collect` on contiguous bf16 / fp16 activations (cnnq_half_stats.hip.h) ------------------------------------------------
-// What the three entry points derive from (N, C, HW) after their argument checks: the fp32 entry points' geometry limits, then
-// the batch splits S and the column splits cs of the two statistics launches (S * cs records per channel)
-static int h_stats_plan(int64_t N, int64_t C, int64_t HW, int* S, int* cs) {
-    const int rc = cnnq_pc_groups(N, C, HW, 0);
-    if (rc <= 0) return g_error(rc);
-    h_stats_splits(N, C, HW, S, cs);
-    return 0;
-}
-static int h_stats_check(int64_t N, int64_t C, int64_t HW, int dtype) { return (!dtype_ok(dtype) || N < 1 || C < 1 || HW < 1) ? CNNQ_EINVAL : 0; }
+// What the entry points, the workspace and the route functions of this section and the next open with: the checks of the shape
+// and the dtype (ok: the function's own, refused with them), then - bf16 / fp16, and fp32 where f32_too - the fp32 entry points'
+// geometry limits and the plan: the batch splits S and the column splits cs of the read-only launches (G = S * cs records per
+// channel; h_stats_splits).  rc: what a refused call returns.
+struct HPlan {
+    int rc, S = 0, cs = 0;
+    HPlan(int64_t N, int64_t C, int64_t HW, int dtype, bool ok, bool f32_too = false)
+        : rc((!dtype_ok(dtype) || N < 1 || C < 1 || HW < 1 || !ok) ? CNNQ_EINVAL : 0) {
+        if (rc || (dtype == CNNQ_DTYPE_F32 && !f32_too)) return;
+        const int G0 = cnnq_pc_groups(N, C, HW, 0);
+        if (G0 <= 0) rc = g_error(G0);
+        else h_stats_splits(N, C, HW, &S, &cs);
+    }
+    int G() const { return S * cs; }
+};
 
 // ws, doubles: part[G][CNNQ_NMOM][C], mom[CNNQ_NMOM][C], part2[G][CNNQ_NDEV][C] (AciqWs without the table) with G = S * cs; fp32:
 // what cnnq_pc_stats takes at either alignment
 size_t cnnq_pc_stats_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype) {
-    if (h_stats_check(N, C, HW, dtype)) return 0;
+    const HPlan p(N, C, HW, dtype, true);
+    if (p.rc) return 0;
     if (dtype == CNNQ_DTYPE_F32) {
         const size_t a = cnnq_pc_stats_workspace(N, C, HW, 1), b = cnnq_pc_stats_workspace(N, C, HW, 0);
         return a > b ? a : b;
     }
-    int S, cs;
-    if (h_stats_plan(N, C, HW, &S, &cs)) return 0;
-    return AciqWs::bytes((size_t)S * cs, C, false);
+    return AciqWs::bytes((size_t)p.G(), C, false);
 }
 
 // Which launches cnnq_pc_stats_dt makes for this geometry (host only): out = {piece width W, batch splits S, column splits,
 // 1 - the native launches / 0 - a class of layer that did not win against the upcast route and stays there: h_stats_native, with
 // the figures next to the rule}.  fp32: {0, the records of cnnq_pc_stats' own plan, 1, 1}.  cnnq_pc_stats_dt itself runs every class.
 int cnnq_pc_route_stats_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int32_t out[4]) {
-    if (h_stats_check(N, C, HW, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
-    int S, cs;
-    if (const int rc = h_stats_plan(N, C, HW, &S, &cs)) return rc;
-    if (dtype == CNNQ_DTYPE_F32) {
-        out[0] = 0;
-        out[1] = cnnq_pc_groups(N, C, HW, align_bytes >= 16);
-        out[2] = 1;
-    } else {
-        out[0] = h_piece(HW, (uintptr_t)align_bytes, 0);
-        out[1] = S;
-        out[2] = cs;
-    }
+    const HPlan p(N, C, HW, dtype, out && pow2(align_bytes), true);
+    if (p.rc) return p.rc;
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    out[0] = f32 ? 0 : h_piece(HW, (uintptr_t)align_bytes, 0);
+    out[1] = f32 ? cnnq_pc_groups(N, C, HW, align_bytes >= 16) : p.S;
+    out[2] = f32 ? 1 : p.cs;
     out[3] = h_stats_native(N, C, HW, dtype);
     return 0;
 }
@@ -1707,85 +1711,61 @@ int cnnq_pc_route_stats_dt(int64_t N, int64_t C, int64_t HW, int dtype, int alig
 // k_combine_dev(want_kurt); need_b or need_kurt), two or four launches
 int cnnq_pc_stats_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, int need_b, int need_kurt, int need_relu, void* ws,
                      double* mom, float* stats, void* stream) {
-    if (h_stats_check(N, C, HW, dtype)) return CNNQ_EINVAL;
-    if (!x || !ws || !stats || misaligned(ws, 8) || misaligned(mom, 8)) return CNNQ_EINVAL;
-    if (dtype == CNNQ_DTYPE_F32)
-        return cnnq_pc_stats(static_cast<const float*>(x), N, C, HW, need_b, need_kurt, need_relu, ws, mom, stats, stream);
-    if (misaligned(x, 2)) return CNNQ_EINVAL;
-    HGeo g;
-    if (const int rc = h_stats_plan(N, C, HW, &g.S, &g.cs)) return rc;
-    g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
-    const int w = h_piece(HW, (uintptr_t)x, 0);
-    g.ppr = (int)(HW / w);
-    const int G = g.S * g.cs;
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    const HPlan p(N, C, HW, dtype, x && ws && stats && !misaligned(ws, 8) && !misaligned(mom, 8) && (f32 || !misaligned(x, 2)));
+    if (p.rc) return p.rc;
+    if (f32) return cnnq_pc_stats(static_cast<const float*>(x), N, C, HW, need_b, need_kurt, need_relu, ws, mom, stats, stream);
+    const int w = h_piece(HW, (uintptr_t)x, 0), G = p.G();
+    const HGeo g = h_geo(N, C, HW, w, p.S, p.cs);
     const AciqWs a(ws, G, C);
     double* rec = mom ? mom : a.mom;
     const dim3 grid((unsigned)(C * G));
-    const uint16_t* xh = static_cast<const uint16_t*>(x);
     hipStream_t st = hs(stream);
-    with_piece<false>(dtype, w, [&](auto pc) {
+    int rc = h_launch(dtype, w, x, [&](auto pc, const uint16_t* xh) {
         with_bool(need_relu != 0, [&](auto relu) {
             using P = decltype(pc);
             hipLaunchKernelGGL((k_h_moments<typename P::T, P::W, decltype(relu)::value>), grid, dim3(TPB), 0, st, xh, g, a.part);
         });
     });
-    int rc = launch_status();
     if (!rc) rc = cnnq_pc_combine(a.part, G, C, need_relu ? 1 : 0, rec, stats, stream);
     if (rc || !(need_b || need_kurt)) return rc;
-    with_piece<false>(dtype, w, [&](auto pc) {
+    rc = h_launch(dtype, w, x, [&](auto pc, const uint16_t* xh) {
         with_bool(need_kurt != 0, [&](auto kurt) {
             using P = decltype(pc);
             hipLaunchKernelGGL((k_h_absdev<typename P::T, P::W, decltype(kurt)::value>), grid, dim3(TPB), 0, st, xh, g, stats, a.part2);
         });
     });
-    rc = launch_status();
     if (!rc) rc = cnnq_pc_combine_dev(a.part2, G, C, rec, need_kurt ? 1 : 0, nullptr, stats, stream);
     return rc;
 }
 
 // ---- `-sm use ... -bca` on contiguous bf16 / fp16 activations (cnnq_half_bcorr.hip.h) -------------------------------------------
-// the fp32 chain's record count at either alignment (what cnnq_pc_qdq_bcorr_sums writes); <= 0: cnnq_pc_groups' code
-static int bcorr_groups_f32(int64_t N, int64_t C, int64_t HW) {
-    const int g1 = cnnq_pc_groups(N, C, HW, 1), g0 = cnnq_pc_groups(N, C, HW, 0);
-    return g1 > g0 ? g1 : g0;
-}
-
 // ws, doubles: part3[G][3][C] with G = S * column splits (h_stats_splits: not the alignment's); fp32: the chain's records
 size_t cnnq_pc_qdq_bcorr_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype) {
-    if (h_stats_check(N, C, HW, dtype)) return 0;
-    int64_t G;
-    if (dtype == CNNQ_DTYPE_F32) {
-        G = bcorr_groups_f32(N, C, HW);
-        if (G <= 0) return 0;
-    } else {
-        int S, cs;
-        if (h_stats_plan(N, C, HW, &S, &cs)) return 0;
-        G = (int64_t)S * cs;
-    }
-    return (size_t)G * 3 * (size_t)C * sizeof(double);
+    const HPlan p(N, C, HW, dtype, true);
+    const int64_t G = p.rc ? 0 : dtype == CNNQ_DTYPE_F32 ? h_records_f32(N, C, HW) : p.G();
+    return G <= 0 ? 0 : (size_t)G * 3 * (size_t)C * sizeof(double);
+}
+
+// the route word of a bf16 / fp16 tensor at piece width w: 1 - k_h_bcorr_whole / 2 - the two passes and the bias between them /
+// 0 - a class of layer that did not win against the upcast route and stays there (h_bcorr_native; the call itself runs every class)
+static int h_bcorr_route(int64_t N, int64_t C, int64_t HW, int dtype, int w, int allow_single_launch) {
+    const bool wins = allow_single_launch > 1 || h_bcorr_whole_wins(N, C, HW, dtype);
+    if (allow_single_launch && h_bcorr_whole_fits(N, HW, w) && wins) return 1;
+    return h_bcorr_native(N, C, HW, dtype) ? 2 : 0;
 }
 
 // Which launches cnnq_pc_qdq_bcorr_dt makes for this geometry with allow_single_launch 0 / 1 (host only): out = {piece width W,
-// batch splits S, column splits of the sums pass, route}; route 1 - k_h_bcorr_whole / 2 - the two passes and the bias between them
-// / 0 - a class of layer that did not win against the upcast route and stays there (h_bcorr_native; the call itself runs every
-// class).  fp32: {0, the chain's records, 1, 2}.
+// batch splits S, column splits of the sums pass, route (h_bcorr_route)}.  fp32: {0, the chain's records, 1, 2}.
 int cnnq_pc_route_qdq_bcorr_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int allow_single_launch, int32_t out[4]) {
-    if (h_stats_check(N, C, HW, dtype) || !out || !pow2(align_bytes)) return CNNQ_EINVAL;
-    int S, cs;
-    if (const int rc = h_stats_plan(N, C, HW, &S, &cs)) return rc;
-    if (dtype == CNNQ_DTYPE_F32) {
-        out[0] = 0;
-        out[1] = bcorr_groups_f32(N, C, HW);
-        out[2] = 1;
-        out[3] = 2;
-        return 0;
-    }
-    const int w = h_piece(HW, (uintptr_t)align_bytes, 0);
+    const HPlan p(N, C, HW, dtype, out && pow2(align_bytes), true);
+    if (p.rc) return p.rc;
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    const int w = f32 ? 0 : h_piece(HW, (uintptr_t)align_bytes, 0);
     out[0] = w;
-    out[1] = S;
-    out[2] = cs;
-    if (allow_single_launch && h_bcorr_whole_fits(N, HW, w) && (allow_single_launch > 1 || h_bcorr_whole_wins(N, C, HW, dtype))) out[3] = 1;
-    else out[3] = h_bcorr_native(N, C, HW, dtype) ? 2 : 0;
+    out[1] = f32 ? h_records_f32(N, C, HW) : p.S;
+    out[2] = f32 ? 1 : p.cs;
+    out[3] = f32 ? 2 : h_bcorr_route(N, C, HW, dtype, w, allow_single_launch);
     return 0;
 }
 
@@ -1793,12 +1773,14 @@ int cnnq_pc_route_qdq_bcorr_dt(int64_t N, int64_t C, int64_t HW, int dtype, int 
 // or k_h_bcorr_sums (ascending) -> k_bcorr_bias on its S * cs records -> k_h_qdq_bias (descending)
 int cnnq_pc_qdq_bcorr_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, int relu_first, void* ws,
                          double* sums, float* bias, int allow_single_launch, void* stream) {
-    if (h_stats_check(N, C, HW, dtype)) return CNNQ_EINVAL;
-    if (!x || !y || x == y || !qp || !ws || !bias || misaligned(ws, 8) || misaligned(sums, 8) || misaligned(qp, 4) || misaligned(bias, 4))
-        return CNNQ_EINVAL;
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    const uintptr_t es = f32 ? 4 : 2;
+    const bool ok = x && y && x != y && qp && ws && bias && !misaligned(ws, 8) && !misaligned(sums, 8) && !misaligned(qp, 4) &&
+                    !misaligned(bias, 4) && !misaligned(x, es) && !misaligned(y, es);
+    const HPlan p(N, C, HW, dtype, ok);
+    if (p.rc) return p.rc;
     double* part3 = static_cast<double*>(ws);
-    if (dtype == CNNQ_DTYPE_F32) {
-        if (misaligned(x, 4) || misaligned(y, 4)) return CNNQ_EINVAL;
+    if (f32) {
         const int G = cnnq_pc_groups(N, C, HW, al16(x));
         if (G <= 0) return g_error(G);
         const float* xf = static_cast<const float*>(x);
@@ -1807,43 +1789,30 @@ int cnnq_pc_qdq_bcorr_dt(const void* x, void* y, int dtype, int64_t N, int64_t C
         if (!rc) rc = cnnq_pc_qdq_bcorr(xf, static_cast<float*>(y), N, C, HW, qp, bias, 1, stream);
         return rc;
     }
-    if (misaligned(x, 2) || misaligned(y, 2)) return CNNQ_EINVAL;
-    int32_t route[4];
-    if (const int rc = cnnq_pc_route_qdq_bcorr_dt(N, C, HW, dtype, h_align(x, y), allow_single_launch, route)) return rc;
-    const int w = route[0];
-    HGeo g;
-    g.N = (int)N; g.C = (int)C; g.HW = (int)HW;
-    g.ppr = (int)(HW / w);
-    const uint16_t* xh = static_cast<const uint16_t*>(x);
-    uint16_t* yh = static_cast<uint16_t*>(y);
+    const int w = h_piece(HW, (uintptr_t)h_align(x, y), 0);
     hipStream_t st = hs(stream);
     const int relu = relu_first ? 1 : 0;
-    if (route[3] == 1) {
-        g.S = 1; g.cs = 1;
-        with_piece<false>(dtype, w, [&](auto pc) {
+    if (h_bcorr_route(N, C, HW, dtype, w, allow_single_launch) == 1) {
+        const HGeo g = h_geo(N, C, HW, w, 1, 1);
+        return h_launch(dtype, w, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
             using P = decltype(pc);
             if constexpr (P::W > 1)
                 hipLaunchKernelGGL((k_h_bcorr_whole<typename P::T, P::W, h_whole_k<P::W>()>), dim3((unsigned)C), dim3(HTPB), 0, st, xh, yh, g, relu, qp,
                                    sums, bias);
         });
-        return launch_status();
     }
-    g.S = route[1]; g.cs = route[2];
-    const int G = g.S * g.cs;
-    with_piece<false>(dtype, w, [&](auto pc) {
+    const int G = p.G();
+    const HGeo gs = h_geo(N, C, HW, w, p.S, p.cs), gq = h_geo_qdq(N, C, HW, w);
+    int rc = h_launch(dtype, w, x, [&](auto pc, const uint16_t* xh) {
         using P = decltype(pc);
-        hipLaunchKernelGGL((k_h_bcorr_sums<typename P::T, P::W>), dim3((unsigned)(C * G)), dim3(TPB), 0, st, xh, g, relu, qp, part3);
+        hipLaunchKernelGGL((k_h_bcorr_sums<typename P::T, P::W>), dim3((unsigned)(C * G)), dim3(TPB), 0, st, xh, gs, relu, qp, part3);
     });
-    int rc = launch_status();
     if (!rc) rc = cnnq_pc_bcorr_bias(part3, G, C, sums, bias, stream);
     if (rc) return rc;
-    g.S = h_splits(N, C, HW, H_QDQ_ELEMS, N);
-    g.cs = 1;
-    with_piece<false>(dtype, w, [&](auto pc) {
+    return h_launch(dtype, w, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
         using P = decltype(pc);
-        hipLaunchKernelGGL((k_h_qdq_bias<typename P::T, P::W>), dim3((unsigned)(C * g.S)), dim3(TPB), 0, st, xh, yh, g, qp, bias);
+        hipLaunchKernelGGL((k_h_qdq_bias<typename P::T, P::W>), dim3((unsigned)(C * gq.S)), dim3(TPB), 0, st, xh, yh, gq, qp, bias);
     });
-    return launch_status();
 }
 
 int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream) {
@@ -1866,15 +1835,13 @@ static int pt_qdq_launch(const void* x, void* y, int dtype, int64_t n, const flo
         });
         return launch_status();
     }
-    with_piece<false>(dtype, vec ? 8 : 1, [&](auto pc) {
+    return h_launch(dtype, vec ? 8 : 1, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
         with_bool(noise != nullptr, [&](auto nz) {
             using P = decltype(pc);
             if constexpr (P::W == 8 || P::W == 1)
-                hipLaunchKernelGGL((k_h_pt_qdq<typename P::T, P::W, decltype(nz)::value>), grid, block, 0, hs(stream), static_cast<const uint16_t*>(x),
-                                   static_cast<uint16_t*>(y), n, ptp, noise);
+                hipLaunchKernelGGL((k_h_pt_qdq<typename P::T, P::W, decltype(nz)::value>), grid, block, 0, hs(stream), xh, yh, n, ptp, noise);
         });
     });
-    return launch_status();
 }
 
 // ---- dense channels_last activations (cnnq_nhwc.hip.h): x and y [R = N*H*W][C], C innermost; fp32 tables ----------------------

@@ -41,32 +41,11 @@ __device__ __forceinline__ float cl_down(CF32, float v) { return v; }
 __device__ __forceinline__ uint16_t cl_down(HBf16 t, float v) { return h_down(t, v); }
 __device__ __forceinline__ uint16_t cl_down(HF16 t, float v) { return h_down(t, v); }
 
-// W consecutive elements: one global load / store of W * sizeof(E) bytes (at most 16)
+// W consecutive elements: one global load / store of W * sizeof(E) bytes (at most 16) - the pair of cnnq_half.hip.h
 template <class E, int W, bool NT>
-__device__ __forceinline__ void cl_ld(const E* __restrict__ p, E (&e)[W]) {
-    if constexpr (W == 1) {
-        e[0] = NT ? __builtin_nontemporal_load(p) : *p;
-    } else {
-        typedef E V __attribute__((ext_vector_type(W)));
-        V v;
-        if constexpr (NT) v = __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
-        else v = *reinterpret_cast<const V*>(p);
-#pragma unroll
-        for (int i = 0; i < W; ++i) e[i] = v[i];
-    }
-}
+__device__ __forceinline__ void cl_ld(const E* __restrict__ p, E (&e)[W]) { piece_ld<E, W, NT>(p, e); }
 template <class E, int W>
-__device__ __forceinline__ void cl_st_nt(E* __restrict__ p, const E (&e)[W]) {
-    if constexpr (W == 1) {
-        __builtin_nontemporal_store(e[0], p);
-    } else {
-        typedef E V __attribute__((ext_vector_type(W)));
-        V v;
-#pragma unroll
-        for (int i = 0; i < W; ++i) v[i] = e[i];
-        __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
-    }
-}
+__device__ __forceinline__ void cl_st_nt(E* __restrict__ p, const E (&e)[W]) { piece_st_nt<E, W>(p, e); }
 
 // the launch geometry: grid = S * nb workgroups, workgroup b' = s * nb + b owns column block b and rows [s * rpw, (s + 1) * rpw)
 struct ClGeo {

@@ -441,21 +441,47 @@ def pc_stats_nhwc(x, need_b=False, need_kurt=False, need_relu=False):
     return stats, mom
 
 
+# What the entry points on contiguous bf16 / fp16 activations (pc_stats_half, qdq_bias_corrected_half) share on the host: who runs
+# native (_half_route_word behind _stats_half_native / _table_half_native) and how a tensor is admitted (_admit_half).
+def _half_route_word(cache, cast, fn, N, C, HW, dtype, *extra):
+    """cast(the last word of the report of the route function `fn`) for this class of contiguous layer - a function of N, C, HW
+    and the dtype alone - asked once per class with alignment 16 and kept in `cache`."""
+    key = (N, C, HW, dtype)
+    v = cache.get(key)
+    if v is None:
+        out = (ctypes.c_int32 * 4)()
+        L.check(getattr(L.load(), fn)(N, C, HW, _DTYPE_CODES.get(dtype, -1), 16, *extra, out), fn)
+        v = cache[key] = cast(out[3])
+    return v
+
+
+def _admit_half(x, what, f32_name):
+    """(x, N, C, HW, dtype code, raw stream) of a non-empty contiguous 4-D bf16 / fp16 tensor on the current device, as the
+    *_half entry points take it; anything else raises (f32_name: the function float32 takes): nothing is copied or upcast."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise L.CnnqError('%s: x must be a CUDA/HIP tensor (there is no CPU path)' % what)
+    if x.dtype not in _HALF_DTYPES:
+        raise L.CnnqError('%s: x must be bfloat16 or float16, got %s (float32 takes %s)' % (what, x.dtype, f32_name))
+    if x.dim() != 4:
+        _not_4d(x, what)
+    if not x.is_contiguous() or x.numel() == 0:
+        raise L.CnnqError('%s: x must be a non-empty contiguous tensor (no copy is made here)' % what)
+    if x.device.index != torch.cuda.current_device():
+        raise L.CnnqError('%s: x is on %s but the current device is cuda:%d' % (what, x.device, torch.cuda.current_device()))
+    if x.requires_grad:
+        x = x.detach()
+    N, C, HW = geometry(x)
+    return x, N, C, HW, _HALF_DTYPES[x.dtype], _raw_stream(x.device.index)
+
+
 _STATS_HALF_NATIVE = {}
 
 
 def _stats_half_native(N, C, HW, dtype):
     """Whether this class of layer collects its statistics on the contiguous bf16 / fp16 kernels: the "native" word of
-    cnnq_pc_route_stats_dt's report (0: a class that measured slower native than through the upcast is sent back there; a function
-    of N, C, HW and the dtype alone), asked once per class with alignment 16.  The statistics manager (collects_native_half) and
-    the tests patch the function and empty the cache by name."""
-    key = (N, C, HW, dtype)
-    v = _STATS_HALF_NATIVE.get(key)
-    if v is None:
-        out = (ctypes.c_int32 * 4)()
-        L.check(L.load().cnnq_pc_route_stats_dt(N, C, HW, _DTYPE_CODES.get(dtype, -1), 16, out), 'cnnq_pc_route_stats_dt')
-        v = _STATS_HALF_NATIVE[key] = bool(out[3])
-    return v
+    cnnq_pc_route_stats_dt's report (0: a class that measured slower native than through the upcast is sent back there).  The
+    statistics manager (collects_native_half) and the tests patch the function and empty the cache by name."""
+    return _half_route_word(_STATS_HALF_NATIVE, bool, 'cnnq_pc_route_stats_dt', N, C, HW, dtype)
 
 
 def pc_stats_half(x, need_b=False, need_kurt=False, need_relu=False):
@@ -465,21 +491,7 @@ def pc_stats_half(x, need_b=False, need_kurt=False, need_relu=False):
     [NMOM, C] f64) as pc_stats; rows nobody asked for are zero (B comes with pass B: need_b or need_kurt, as in pc_stats).  One
     GPU: the statistics are this tensor's.  Anything else - a CPU tensor, float32, not 4-D, not contiguous - raises: nothing is
     copied or upcast here."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise L.CnnqError('pc_stats_half: x must be a CUDA/HIP tensor (there is no CPU path)')
-    if x.dtype not in _HALF_DTYPES:
-        raise L.CnnqError('pc_stats_half: x must be bfloat16 or float16, got %s (float32 takes pc_stats)' % x.dtype)
-    if x.dim() != 4:
-        _not_4d(x, 'pc_stats_half')
-    if not x.is_contiguous() or x.numel() == 0:
-        raise L.CnnqError('pc_stats_half: x must be a non-empty contiguous tensor (no copy is made here)')
-    if x.device.index != torch.cuda.current_device():
-        raise L.CnnqError('pc_stats_half: x is on %s but the current device is cuda:%d' % (x.device, torch.cuda.current_device()))
-    if x.requires_grad:
-        x = x.detach()
-    N, C, HW = geometry(x)
-    dt = _HALF_DTYPES[x.dtype]
-    st = _raw_stream(x.device.index)
+    x, N, C, HW, dt, st = _admit_half(x, 'pc_stats_half', 'pc_stats')
     stats = torch.empty((L.NSTAT, C), dtype=torch.float32, device=x.device)
     mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
     ws = _scratch(x, 'stats_half', _ws_bytes('stats_half', N, C, HW, dt), st)
@@ -1921,18 +1933,11 @@ def qdq_bias_corrected_nhwc(x, qp, relu_first, out=None, want_parts=False):
         raise L.CnnqError('qdq_bias_corrected_nhwc: qp must be a contiguous float32 [%d, %d] device table' % (L.NQP, C))
     nbytes = _ws_bytes('bcorr_nhwc', R, C, 1, dt)
     y = _out_like(x, out)
-    if want_parts:
-        sums = torch.empty((3, C), dtype=torch.float64, device=x.device)
-        bias = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws, sp, bp = _scratch(x, 'bcorr_nhwc', nbytes, st).data_ptr(), sums.data_ptr(), bias.data_ptr()
-    else:
-        # the bias nobody outside the call reads follows the records in the cached workspace
-        ws = _scratch(x, 'bcorr_nhwc', nbytes + C * 4, st).data_ptr()
-        sp, bp = None, ws + nbytes
+    ws, sp, bp, parts = _bcorr_buffers(x, 'bcorr_nhwc', nbytes, C, want_parts, st)
     rc = L.load().cnnq_pc_qdq_bcorr_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, qp.data_ptr(), int(bool(relu_first)), ws, sp, bp, st)
     if rc:
         L.check(rc, 'cnnq_pc_qdq_bcorr_nhwc')
-    return _result(y, parts=dict(sums=sums, bias=bias) if want_parts else None)
+    return _result(y, parts=parts)
 
 
 _TABLE_HALF_NATIVE = {}
@@ -1941,15 +1946,8 @@ _TABLE_HALF_NATIVE = {}
 def _table_half_native(N, C, HW, dtype):
     """The route word of cnnq_pc_route_qdq_bcorr_dt's report for this class of contiguous bf16 / fp16 layer: 1 - the table-driven
     Q/DQ with the bias correction in one launch, 2 - in two passes, 0 - a class that measured slower native than through the upcast
-    and is sent back there (a function of N, C, HW and the dtype alone), asked once per class with alignment 16.  The quantizer
-    (_half_table) and the tests patch the function and empty the cache by name."""
-    key = (N, C, HW, dtype)
-    v = _TABLE_HALF_NATIVE.get(key)
-    if v is None:
-        out = (ctypes.c_int32 * 4)()
-        L.check(L.load().cnnq_pc_route_qdq_bcorr_dt(N, C, HW, _DTYPE_CODES.get(dtype, -1), 16, 1, out), 'cnnq_pc_route_qdq_bcorr_dt')
-        v = _TABLE_HALF_NATIVE[key] = int(out[3])
-    return v
+    and is sent back there.  The quantizer (_half_table) and the tests patch the function and empty the cache by name."""
+    return _half_route_word(_TABLE_HALF_NATIVE, int, 'cnnq_pc_route_qdq_bcorr_dt', N, C, HW, dtype, 1)
 
 
 def qdq_bias_corrected_half(x, qp, relu_first, out=None, want_parts=False, single_launch=None):
@@ -1962,23 +1960,9 @@ def qdq_bias_corrected_half(x, qp, relu_first, out=None, want_parts=False, singl
     tensor, float32, not 4-D, not contiguous, a qp that is not a float32 [NQP, C] device table - raises: nothing is copied or upcast
     here."""
     what = 'qdq_bias_corrected_half'
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise L.CnnqError('%s: x must be a CUDA/HIP tensor (there is no CPU path)' % what)
-    if x.dtype not in _HALF_DTYPES:
-        raise L.CnnqError('%s: x must be bfloat16 or float16, got %s (float32 takes qdq_bias_corrected)' % (what, x.dtype))
-    if x.dim() != 4:
-        _not_4d(x, what)
-    if not x.is_contiguous() or x.numel() == 0:
-        raise L.CnnqError('%s: x must be a non-empty contiguous tensor (no copy is made here)' % what)
-    if x.device.index != torch.cuda.current_device():
-        raise L.CnnqError('%s: x is on %s but the current device is cuda:%d' % (what, x.device, torch.cuda.current_device()))
-    if x.requires_grad:
-        x = x.detach()
-    N, C, HW = geometry(x)
+    x, N, C, HW, dt, st = _admit_half(x, what, 'qdq_bias_corrected')
     if not _is_table(qp, torch.float32, (L.NQP, C), x.device):
         raise L.CnnqError('%s: qp must be a contiguous float32 [%d, %d] device table' % (what, L.NQP, C))
-    dt = _HALF_DTYPES[x.dtype]
-    st = _raw_stream(x.device.index)
     y = _out_like(x, out)
     allow = 1 if single_launch is None else (2 if single_launch else 0)
     if single_launch:
@@ -1989,19 +1973,24 @@ def qdq_bias_corrected_half(x, qp, relu_first, out=None, want_parts=False, singl
         if route[3] != 1:
             raise L.CnnqError('%s: no single launch for [%d, %d, %d] at piece width %d' % (what, N, C, HW, route[0]))
     nbytes = _ws_bytes('bcorr_half', N, C, HW, dt)
-    if want_parts:
-        sums = torch.empty((3, C), dtype=torch.float64, device=x.device)
-        bias = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws, sp, bp = _scratch(x, 'bcorr_half', nbytes, st).data_ptr(), sums.data_ptr(), bias.data_ptr()
-    else:
-        # the bias nobody outside the call reads follows the records in the cached workspace
-        ws = _scratch(x, 'bcorr_half', nbytes + C * 4, st).data_ptr()
-        sp, bp = None, ws + nbytes
+    ws, sp, bp, parts = _bcorr_buffers(x, 'bcorr_half', nbytes, C, want_parts, st)
     rc = L.load().cnnq_pc_qdq_bcorr_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, qp.data_ptr(), int(bool(relu_first)), ws, sp, bp,
                                        allow, st)
     if rc:
         L.check(rc, 'cnnq_pc_qdq_bcorr_dt')
-    return _result(y, parts=dict(sums=sums, bias=bias) if want_parts else None)
+    return _result(y, parts=parts)
+
+
+def _bcorr_buffers(x, tag, nbytes, C, want_parts, st):
+    """(workspace, sums, bias, parts) of a one-call bias correction: the pointers its C call takes and what the caller returns as
+    parts.  want_parts: sums [3, C] float64 and bias [C] are fresh tensors beside the cached workspace of nbytes; else nobody
+    outside the call reads the bias, which follows the records in the cached workspace, and no sums are published."""
+    if want_parts:
+        sums = torch.empty((3, C), dtype=torch.float64, device=x.device)
+        bias = torch.empty(C, dtype=torch.float32, device=x.device)
+        return _scratch(x, tag, nbytes, st).data_ptr(), sums.data_ptr(), bias.data_ptr(), dict(sums=sums, bias=bias)
+    ws = _scratch(x, tag, nbytes + C * 4, st).data_ptr()
+    return ws, None, ws + nbytes, None
 
 
 def _bcorr_bias(x, part3, group, sums_out=None):

@@ -80,6 +80,53 @@ def test_every_branch_against_fp64(case, dtype):
     np.testing.assert_allclose(mom[L.MOM_SUMSQ_RELU].cpu(), (t.clamp(min=0) ** 2).sum(1), rtol=1e-7, atol=1e-6)
 
 
+# ---- 1b. the extrema's partials (k_h_minmax) on the same partition: batch splits, column splits, every piece width
+def minmax_plan(N, HW, W, G):
+    """(batch splits, column splits) of the extrema launch, h_minmax of csrc/cnnq_kernels.hip restated: ~H_MM_ELEMS elements per
+    workgroup and at most the fp32 plan's G records per channel; batch splits first, then at most HW / W parts of a row."""
+    total = max(1, min(-(-N * HW // HC.H_MM_ELEMS), N * HW, G))
+    S = min(total, N)
+    return S, min(total // S, HW // W)
+
+
+def minmax_local(x):
+    """([2, C] = {min, max} per channel, which records of pmm hold no NaN) through cnnq_pc_minmax_local_dt; pmm is sized by the
+    fp32 plan's record count, as ops.tensor_row_stats sizes it, and filled with NaN first: a clean input writes none."""
+    L, ops = mods()
+    N, C, HW = ops.geometry(x)
+    pmm = torch.full((ops._groups(N, C, HW, None), 2, C), float('nan'), dtype=torch.float32, device=x.device)
+    local = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    torch.cuda.synchronize()
+    L.check(L.load().cnnq_pc_minmax_local_dt(x.data_ptr(), ops._DTYPE_CODES[x.dtype], N, C, HW, pmm.data_ptr(), local.data_ptr(),
+                                             None), 'cnnq_pc_minmax_local_dt')
+    torch.cuda.synchronize()
+    return local.cpu(), (~torch.isnan(pmm)).all(2).all(1).cpu().tolist()
+
+
+@pytest.mark.parametrize('dtype', DTYPES, ids=IDS)
+@pytest.mark.parametrize('case', HC.CASES, ids=HC.IDS)
+def test_minmax_partials_on_every_branch(case, dtype):
+    _, ops = mods()
+    x = case_input(case, dtype)
+    N, C, HW = ops.geometry(x)
+    W, S, cs = case[2]
+    # the extrema launch has a plan of its own; on these cases it cuts as the statistics launches do, so the branch the case
+    # is named for is the branch k_h_minmax takes - restated here, and read back from the records the launch wrote
+    G = ops._groups(N, C, HW, None)
+    assert minmax_plan(N, HW, W, G) == (S, cs) and S * cs < G
+    clean, written = minmax_local(x)
+    assert written == [True] * (S * cs) + [False] * (G - S * cs)
+    xf = x.float().cpu()
+    assert torch.equal(clean[0], xf.amin((0, 2, 3))) and torch.equal(clean[1], xf.amax((0, 2, 3)))
+    # a NaN in one channel: both of its entries NaN, no other entry changed
+    c = C // 2
+    x[-1, c, -1, -1] = float('nan')
+    got, _ = minmax_local(x)
+    assert torch.isnan(got[:, c]).all()
+    keep = [i for i in range(C) if i != c]
+    assert torch.equal(got[:, keep], clean[:, keep])
+
+
 # ---- 2. against the existing route: the upcast and the fp32 chain
 @pytest.mark.parametrize('dtype', DTYPES, ids=IDS)
 @pytest.mark.parametrize('case', HC.CASES, ids=HC.IDS)
