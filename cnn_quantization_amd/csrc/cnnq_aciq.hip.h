@@ -99,10 +99,37 @@ __device__ __forceinline__ double wg_sum1(double v, double* l_s) {
     return ((l_s[0] + l_s[1]) + l_s[2]) + l_s[3];
 }
 
+// k_fused_flat: lane l of wave 0 adds the sums of members l, l + 64, ... to tsum in MEMBER order, whatever the arrival order
+// was - window by window (4 members), and only once the window is complete.  The 8-byte words at `src` are slots (POLL:
+// complemented, zero = not arrived; slot_wait of cnnq_group.hip.h) or plain doubles (the cold path's recomputed table): the
+// identical order of additions.  False: the wait expired (POLL only: the table form waits for nothing, ignores tmo and
+// always returns true).
+template <bool POLL>
+__device__ __forceinline__ bool flat_member_sums(const unsigned long long* src, int Gs, long long tmo, double& tsum) {
+    const int tid = threadIdx.x;
+    SlotWait sw;
+    for (int w0 = 0; w0 * 64 < Gs; w0 += 4) {
+        const unsigned long long* p = src + tid + 64 * w0;
+        const unsigned mine = slot_window<4>(true, tid + 64 * w0, 64, Gs);
+        unsigned long long v[4] = {0ull, 0ull, 0ull, 0ull};
+        if constexpr (POLL) {
+            if (!slot_wait<false>(sw, p, 64, mine, tmo, v, [](int, unsigned long long) {})) return false;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if ((mine >> i) & 1u) tsum += sum_of_slot(v[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if ((mine >> i) & 1u)
+                    tsum += __longlong_as_double((long long)__hip_atomic_load(p + 64 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        }
+    }
+    return true;
+}
+
 // The slot meeting of k_fused_flat (slots_meet of cnnq_group.hip.h for sums): wave 0 stores the member's partial sum and
-// polls the group's slots; lane l watches members l, l + 64, ... in windows of 4 and adds a window's values in member
-// order once the whole window has arrived.  Returns 0, or 1 (a wait expired) / 2 (the test hook), meaningful in thread 0;
-// tsum: the lane's share (0 outside wave 0).
+// meets the group.  Returns 0, or 1 (a wait expired) / 2 (the test hook), meaningful in thread 0; tsum: the lane's share (0
+// outside wave 0).
 __device__ __forceinline__ int slots_meet_sum(unsigned long long* slots, int member, int Gs, double msum, unsigned flags,
                                               long long timeout_ticks, double& tsum) {
     const int tid = threadIdx.x;
@@ -110,52 +137,7 @@ __device__ __forceinline__ int slots_meet_sum(unsigned long long* slots, int mem
     if (tid >= 64) return 0;
     if (tid == 0) __hip_atomic_store(slots + member, slot_of_sum(msum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (flags & MMQ_FLAG_TEST_HOOK) return 2;
-    long long t0 = 0;
-    int spins = 0;
-    for (int w0 = 0; w0 * 64 < Gs; w0 += 4) {
-        const unsigned long long* p = slots + tid + 64 * w0;
-        unsigned pend = 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pend |= (tid + 64 * (w0 + i) < Gs) ? (1u << i) : 0u;
-        const unsigned mine = pend;
-        unsigned long long v[4] = {0ull, 0ull, 0ull, 0ull};
-        for (;; ++spins) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if ((pend >> i) & 1u) {
-                    v[i] = __hip_atomic_load(p + 64 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (v[i]) pend &= ~(1u << i);
-                }
-            if (__ballot(pend != 0u) == 0ull) break;
-            int expired = 0;
-            if ((spins & 31) == 31 || spins > GRP_TIMEOUT_SPINS) {
-                const long long now = wall_clock64();
-                if (t0 == 0) t0 = now;
-                expired = (now - t0 > timeout_ticks || spins > GRP_TIMEOUT_SPINS) ? 1 : 0;
-            }
-            if (__builtin_amdgcn_readfirstlane(expired)) return 1;
-            if (spins < 2) __builtin_amdgcn_s_sleep(8);
-            else if (spins < 6) __builtin_amdgcn_s_sleep(32);
-            else __builtin_amdgcn_s_sleep(64);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if ((mine >> i) & 1u) tsum += sum_of_slot(v[i]);      // member order, whatever the arrival order was
-    }
-    return 0;
-}
-
-// the same fold over plain member sums (the cold path's table, uncached memory): identical order of additions
-__device__ __forceinline__ double fold_member_sums(const unsigned long long* ms, int Gs) {
-    const int tid = threadIdx.x;
-    double tsum = 0.;
-    if (tid < 64)
-        for (int w0 = 0; w0 * 64 < Gs; w0 += 4)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (tid + 64 * (w0 + i) < Gs)
-                    tsum += __longlong_as_double((long long)__hip_atomic_load(ms + tid + 64 * (w0 + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    return tsum;
+    return flat_member_sums<true>(slots, Gs, timeout_ticks, tsum) ? 0 : 1;
 }
 
 // ---- mid-tread arithmetic of the single-launch kernels (MODE 1) ---------------------------------------------------------
@@ -434,7 +416,8 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_fused_fl
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        tsum = fold_member_sums(tab, g.Gs);
+        tsum = 0.;
+        if (tid < 64) (void)flat_member_sums<false>(tab, g.Gs, 0, tsum);
     }
     if (tid < 64) {
 #pragma unroll
@@ -596,10 +579,7 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_fused_fl
     }
     // ---- leave the group; the last member out re-arms the group's slots
     __syncthreads();
-    if (tid == 0) sh_timed_out = grp_depart_last(grp_lines(ws.cnt, c, g.Gs, 0, 1), member, g.Gs) ? 1 : 0;
-    __syncthreads();
-    if (sh_timed_out)
-        for (int m = tid; m < g.Gs; m += TPB) __hip_atomic_store(slots + m, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    slots_leave(grp_lines(ws.cnt, c, g.Gs, 0, 1), member, g.Gs, slots, g.Gs, &sh_timed_out);
 }
 
 // ---- row-piece tiles (the geometry of k_mmq_group: a member is <= 256 float4 columns x <= K samples) ----------------
@@ -671,54 +651,32 @@ __device__ __forceinline__ void wg_channel_sums(const Geo& g, const Blk& b, bool
 }
 
 // The group's sums from its members' partial sums, [member][kk] 8-byte words at `src`: slots (POLL: complemented, zero =
-// not arrived) or plain doubles (the cold path's recomputed table).  Lane (ch, j) = (tid / L, tid % L) adds the values of
-// channel ch of members j, j + L, ... in member order, window by window and only once a window is complete; the L lanes
-// of a channel sit in one wave and fold by a fixed xor tree.  Writes sh_sum[ch] (kk > 1), or returns the lane's share in
-// tsum (whole_wg: one channel, all 256 lanes take part; the caller folds).  A wave whose wait expired ORs 1 into *sh_code.
+// not arrived) or plain doubles (the cold path's recomputed table).  Lane (ch, j) = (tid / L, tid % L), L = meet_lanes(kk),
+// adds the values of channel ch of members j, j + L, ... in member order, window by window and only once a window is
+// complete; the L lanes of a channel sit in one wave and fold by a fixed xor tree.  Writes sh_sum[ch] (kk > 1), or returns
+// the lane's share in tsum (whole_wg: one channel, all 256 lanes take part; the caller folds).  A wave whose wait expired
+// ORs 1 into *sh_code.
 template <int W, bool POLL>
 __device__ __forceinline__ void group_fold_sums(const unsigned long long* src, int Gs, int kk, int nch, bool whole_wg,
                                                 long long timeout_ticks, double* sh_sum, int* sh_code, double& tsum) {
     const int tid = threadIdx.x;
-    int L = 1;
-    while (L < 64 && 2 * L * kk <= TPB) L <<= 1;
-    if (whole_wg) L = TPB;
+    int L = meet_lanes(kk);
+    if (whole_wg) L = TPB;      // (assigned over, not selected: as a select two K = 32 instances spilled five registers)
     const int ch = tid / L, j = tid - ch * L;
     const bool active = ch < nch;
     tsum = 0.;
-    long long t0 = 0;
-    int spins = 0;
+    SlotWait sw;
     for (int w0 = 0; w0 * L < Gs; w0 += W) {
         const unsigned long long* p = src + (unsigned)((j + L * w0) * kk + ch);
         const unsigned step = (unsigned)(L * kk);
-        unsigned pend = 0u;
-#pragma unroll
-        for (int i = 0; i < W; ++i) pend |= (active && j + L * (w0 + i) < Gs) ? (1u << i) : 0u;
-        const unsigned mine = pend;
+        const unsigned mine = slot_window<W>(active, j + L * w0, L, Gs);
         unsigned long long v[W];
 #pragma unroll
         for (int i = 0; i < W; ++i) v[i] = 0ull;
         if constexpr (POLL) {
-            for (;; ++spins) {
-#pragma unroll
-                for (int i = 0; i < W; ++i)
-                    if ((pend >> i) & 1u) {
-                        v[i] = __hip_atomic_load(p + i * step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (v[i]) pend &= ~(1u << i);
-                    }
-                if (__ballot(pend != 0u) == 0ull) break;
-                int expired = 0;
-                if ((spins & 31) == 31 || spins > GRP_TIMEOUT_SPINS) {
-                    const long long now = wall_clock64();
-                    if (t0 == 0) t0 = now;
-                    expired = (now - t0 > timeout_ticks || spins > GRP_TIMEOUT_SPINS) ? 1 : 0;
-                }
-                if (__builtin_amdgcn_readfirstlane(expired)) {
-                    if ((tid & 63) == 0) atomicOr(sh_code, 1);
-                    return;
-                }
-                if (spins < 2) __builtin_amdgcn_s_sleep(8);
-                else if (spins < 6) __builtin_amdgcn_s_sleep(32);
-                else __builtin_amdgcn_s_sleep(64);
+            if (!slot_wait<false>(sw, p, step, mine, timeout_ticks, v, [](int, unsigned long long) {})) {
+                if ((tid & 63) == 0) atomicOr(sh_code, 1);
+                return;
             }
 #pragma unroll
             for (int i = 0; i < W; ++i)
@@ -1051,10 +1009,7 @@ __global__ void __launch_bounds__(TPB, (fused_group_waves<K, OUT, MODE, XR>())) 
     }
     __syncthreads();
     // ---- leave the group; the last member out re-arms the group's slots
-    if (tid == 0) sh_timed_out = grp_depart_last(grp_lines(ws.cnt, rb.group, Gs, 0, 1), rb.member, Gs) ? 1 : 0;
-    __syncthreads();
-    if (sh_timed_out)
-        for (int m = tid; m < Gs * kk; m += TPB) __hip_atomic_store(slots + m, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    slots_leave(grp_lines(ws.cnt, rb.group, Gs, 0, 1), rb.member, Gs, slots, Gs * kk, &sh_timed_out);
 }
 
 }  // namespace

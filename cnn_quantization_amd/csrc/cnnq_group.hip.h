@@ -331,9 +331,104 @@ __device__ __forceinline__ unsigned long long slot_of(float mn, float mx) {
     return ~pack_pair(nn ? NAN : mn, nn ? NAN : mx);
 }
 
-// Wave 0 of the member does the meeting (no barrier inside the wait: the other waves sit at the caller's barrier): lane l
-// watches members l, l + 64, ... (12 at most, in windows of 4).  Returns 0, or 1 (a wait expired) / 2 (the test hook),
-// meaningful in thread 0; tn / tx: this lane's share of the fold (identities outside wave 0).
+// The bounded wait of the slot meetings of configs 2, 3 and 5 (the {min, max} pairs here, the sums of cnnq_aciq.hip.h; the
+// statistics kernels of cnnq_stats1.hip.h keep a wait of their own, see profiles/slot_wait.md).  A lane watches its members
+// W at a time - a window: word i of the window is p[i * step], bit i of `pend` says that the lane is still waiting for
+// it - and slot_wait polls one window (relaxed agent-scope loads) until every
+// lane of the WAVE has all of its words; word i lands in v[i], and arrive(i, word) runs once per word, when it is first seen
+// non-zero.  The {min, max} meetings fold in arrive and never look at v again; the sum meetings do nothing in arrive and
+// add v[i] in member order once the window is complete.  No barrier inside: every wave waits on its own.  The wait is
+// bounded twice (tmo ticks of the 100 MHz clock, 2^20 polls) over all the windows of a meeting - the caller carries the
+// SlotWait from one window to the next - and returns false, wave-uniformly, when it expired.
+struct SlotWait {
+    long long t0 = 0;
+    int spins = 0;
+};
+
+template <bool TOGETHER, int W, typename S, typename F>
+__device__ __forceinline__ bool slot_wait(SlotWait& sw, const unsigned long long* p, S step, unsigned pend, long long tmo,
+                                          unsigned long long (&v)[W], F arrive) {
+    for (;; ++sw.spins) {
+        // each load goes straight into its word of v, under its pending bit (a lane that is not waiting for word i keeps what
+        // it has: the word as it arrived).  The two forms are the ones the meetings had before they shared this function:
+        // TOGETHER - the {min, max} meetings - the window's loads go out back to back and are looked at afterwards, one
+        // round trip per poll; otherwise - the sum meetings - a word is tested behind its own load, W round trips.
+#pragma unroll
+        for (int i = 0; i < W; ++i)
+            if ((pend >> i) & 1u) {
+                v[i] = __hip_atomic_load(p + i * step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (!TOGETHER) {
+                    if (v[i]) {
+                        arrive(i, v[i]);
+                        pend &= ~(1u << i);
+                    }
+                }
+            }
+        if constexpr (TOGETHER) {
+#pragma unroll
+            for (int i = 0; i < W; ++i)
+                if (((pend >> i) & 1u) && v[i]) {
+                    arrive(i, v[i]);
+                    pend &= ~(1u << i);
+                }
+        }
+        if (__ballot(pend != 0u) == 0ull) return true;
+        // the clock is a scalar-memory round trip of its own: consulted every 32 polls
+        int expired = 0;
+        if ((sw.spins & 31) == 31 || sw.spins > GRP_TIMEOUT_SPINS) {
+            const long long now = wall_clock64();
+            if (sw.t0 == 0) sw.t0 = now;
+            expired = (now - sw.t0 > tmo || sw.spins > GRP_TIMEOUT_SPINS) ? 1 : 0;
+        }
+        if (__builtin_amdgcn_readfirstlane(expired)) return false;
+        if (sw.spins < 2) __builtin_amdgcn_s_sleep(8);
+        else if (sw.spins < 6) __builtin_amdgcn_s_sleep(32);
+        else __builtin_amdgcn_s_sleep(64);
+    }
+}
+
+// the window's `pend`: bit i is up when member m0 + i * L exists and the lane takes part
+template <int W>
+__device__ __forceinline__ unsigned slot_window(bool active, int m0, int L, int Gs) {
+    unsigned pend = 0u;
+#pragma unroll
+    for (int i = 0; i < W; ++i) pend |= (active && m0 + L * i < Gs) ? (1u << i) : 0u;
+    return pend;
+}
+
+// Lanes per watched value of a meeting with kk values per member: the largest power of two <= min(64, TPB / kk), so that
+// a value's watchers sit in one wave and fold with shuffles.
+__device__ __forceinline__ int meet_lanes(int kk) {
+    int L = 1;
+    while (L < 64 && 2 * L * kk <= TPB) L <<= 1;
+    return L;
+}
+
+// A lane's share of one {min, max} slot meeting, slots [member][kk]: the pairs of value ch of members j, j + L, ... folded
+// into tn / tx as they arrive (the order does not matter to pmin / pmax; keeping a window's words to fold them afterwards
+// cost the K = 16 / 8 kernels a wave of occupancy).  Windows of W members per lane - the tile's registers are live across
+// the wait - so one window unless Gs > W L.  False: the wait expired.
+template <int W>
+__device__ __forceinline__ bool slots_lane_minmax(const unsigned long long* slots, int Gs, int L, int kk, int ch, int j, bool active,
+                                                  long long tmo, float& tn, float& tx) {
+    SlotWait sw;
+    for (int w0 = 0; w0 * L < Gs; w0 += W) {
+        unsigned long long v[W];
+        const bool met = slot_wait<true>(sw, slots + (unsigned)((j + L * w0) * kk + ch), (unsigned)(L * kk),
+                                   slot_window<W>(active, j + L * w0, L, Gs), tmo, v, [&](int, unsigned long long word) {
+                                       float u, w;
+                                       unpack_pair(~word, u, w);
+                                       tn = pmin(tn, u);
+                                       tx = pmax(tx, w);
+                                   });
+        if (!met) return false;
+    }
+    return true;
+}
+
+// k_mmq_flat: wave 0 of the member does the meeting (the other waves sit at the caller's barrier): lane l watches members
+// l, l + 64, ... (12 at most).  Returns 0, or 1 (a wait expired) / 2 (the test hook), meaningful in thread 0; tn / tx: this
+// lane's share of the fold (identities outside wave 0).
 __device__ __forceinline__ int slots_meet(unsigned long long* slots, int member, int Gs, float cmn, float cmx, unsigned flags,
                                           long long timeout_ticks, float& tn, float& tx) {
     static_assert(GRP_GS_BIG <= 12 * 64, "a lane of wave 0 watches at most 12 members (three windows of 4)");
@@ -343,102 +438,40 @@ __device__ __forceinline__ int slots_meet(unsigned long long* slots, int member,
     if (tid >= 64) return 0;
     if (tid == 0) __hip_atomic_store(slots + member, slot_of(cmn, cmx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (flags & MMQ_FLAG_TEST_HOOK) return 2;
-    long long t0 = 0;
-    int spins = 0;
-    // windows of 4 members per lane (the tile's registers are live across the wait: 8 values in flight per lane cost the
-    // K = 16 / 8 kernels a wave of occupancy); one window unless the group has more than 256 members
-    for (int w0 = 0; w0 * 64 < Gs; w0 += 4) {
-        const unsigned long long* p = slots + tid + 64 * w0;
-        unsigned pend = 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pend |= (tid + 64 * (w0 + i) < Gs) ? (1u << i) : 0u;
-        for (;; ++spins) {
-            unsigned long long v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = ((pend >> i) & 1u) ? __hip_atomic_load(p + 64 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (((pend >> i) & 1u) && v[i]) {
-                    float u, w;
-                    unpack_pair(~v[i], u, w);
-                    tn = pmin(tn, u);
-                    tx = pmax(tx, w);
-                    pend &= ~(1u << i);
-                }
-            if (__ballot(pend != 0u) == 0ull) break;
-            int expired = 0;
-            if ((spins & 31) == 31 || spins > GRP_TIMEOUT_SPINS) {
-                const long long now = wall_clock64();
-                if (t0 == 0) t0 = now;
-                expired = (now - t0 > timeout_ticks || spins > GRP_TIMEOUT_SPINS) ? 1 : 0;
-            }
-            if (__builtin_amdgcn_readfirstlane(expired)) return 1;
-            if (spins < 2) __builtin_amdgcn_s_sleep(8);
-            else if (spins < 6) __builtin_amdgcn_s_sleep(32);
-            else __builtin_amdgcn_s_sleep(64);
-        }
-    }
-    return 0;
+    return slots_lane_minmax<4>(slots, Gs, 64, 1, 0, tid, true, timeout_ticks, tn, tx) ? 0 : 1;
 }
 
-// The slot meeting of k_mmq_group: `kk` pairs per member, slots [member][kk].  Lane (ch, j) = (tid / L, tid % L) watches channel
-// ch of members j, j + L, ...; L = the largest power of two <= min(64, 256 / kk), so a channel's watchers sit in one wave
-// and fold with shuffles.  Every wave polls on its own (no barrier inside the wait); a wave whose wait expired ORs 1 into
-// *sh_code.  Writes the group's extrema of channel ch < nch to sh_mn / sh_mx (kk > 1), or returns the lane's share in tn / tx
-// (whole_wg - mode 1, kk == 1: one channel, all 256 lanes watch).  The caller's barrier comes after.
+// k_mmq_group: `kk` pairs per member.  Lane (ch, j) = (tid / L, tid % L), L = meet_lanes(kk), watches channel ch of members
+// j, j + L, ...; a wave whose wait expired ORs 1 into *sh_code.  Writes the group's extrema of channel ch < nch to sh_mn /
+// sh_mx (kk > 1), or returns the lane's share in tn / tx (whole_wg - mode 1, kk == 1: one channel, all 256 lanes watch).
+// The caller's barrier comes after.
 template <int W>
 __device__ __forceinline__ void slots_meet_group(const unsigned long long* slots, int Gs, int kk, int nch, bool whole_wg, long long timeout_ticks,
                                                  float* sh_mn, float* sh_mx, int* sh_code, float& tn, float& tx) {
     const int tid = threadIdx.x;
-    int L = 1;
-    while (L < 64 && 2 * L * kk <= TPB) L <<= 1;
-    if (whole_wg) L = TPB;      // mode 1: one channel per group, the caller folds the 256 shares (kk == 1)
+    const int L = whole_wg ? TPB : meet_lanes(kk);      // mode 1: one channel per group, the caller folds the 256 shares
     const int ch = tid / L, j = tid - ch * L;
     const bool active = ch < nch;
     tn = INFINITY;
     tx = -INFINITY;
-    long long t0 = 0;
-    int spins = 0;
-    for (int w0 = 0; w0 * L < Gs; w0 += W) {        // windows of W members per lane (one window unless Gs > W L)
-        const unsigned long long* p = slots + (unsigned)((j + L * w0) * kk + ch);
-        const unsigned step = (unsigned)(L * kk);
-        unsigned pend = 0u;
-#pragma unroll
-        for (int i = 0; i < W; ++i) pend |= (active && j + L * (w0 + i) < Gs) ? (1u << i) : 0u;
-        for (;; ++spins) {
-            unsigned long long v[W];
-#pragma unroll
-            for (int i = 0; i < W; ++i)
-                v[i] = ((pend >> i) & 1u) ? __hip_atomic_load(p + i * step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-#pragma unroll
-            for (int i = 0; i < W; ++i)
-                if (((pend >> i) & 1u) && v[i]) {
-                    float u, w;
-                    unpack_pair(~v[i], u, w);
-                    tn = pmin(tn, u);
-                    tx = pmax(tx, w);
-                    pend &= ~(1u << i);
-                }
-            if (__ballot(pend != 0u) == 0ull) break;
-            int expired = 0;
-            if ((spins & 31) == 31 || spins > GRP_TIMEOUT_SPINS) {
-                const long long now = wall_clock64();
-                if (t0 == 0) t0 = now;
-                expired = (now - t0 > timeout_ticks || spins > GRP_TIMEOUT_SPINS) ? 1 : 0;
-            }
-            if (__builtin_amdgcn_readfirstlane(expired)) {
-                if ((tid & 63) == 0) atomicOr(sh_code, 1);
-                return;
-            }
-            if (spins < 2) __builtin_amdgcn_s_sleep(8);
-            else if (spins < 6) __builtin_amdgcn_s_sleep(32);
-            else __builtin_amdgcn_s_sleep(64);
-        }
+    if (!slots_lane_minmax<W>(slots, Gs, L, kk, ch, j, active, timeout_ticks, tn, tx)) {
+        if ((tid & 63) == 0) atomicOr(sh_code, 1);
+        return;
     }
     if (!whole_wg) {
         for (int m = L >> 1; m >= 1; m >>= 1) { tn = pmin(tn, shfl_xor_f(tn, m)); tx = pmax(tx, shfl_xor_f(tx, m)); }
         if (active && j == 0) { sh_mn[ch] = tn; sh_mx[ch] = tx; }
     }
+}
+
+// The departure of a slot meeting: counted (word [1] of the counter lines); the last member out - every other member has
+// read the slots by then - zeroes the meeting's `nwords` words again.
+__device__ __forceinline__ void slots_leave(unsigned* cnt_lines, int member, int Gs, unsigned long long* slots, int nwords, int* sh_flag) {
+    const int tid = threadIdx.x;
+    if (tid == 0) *sh_flag = grp_depart_last(cnt_lines, member, Gs) ? 1 : 0;
+    __syncthreads();
+    if (*sh_flag)
+        for (int m = tid; m < nwords; m += TPB) __hip_atomic_store(slots + m, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ws: [0] status word, [256 ..) 16384 arrival/departure counters, one per group and per 256-byte line (a fixed
@@ -675,12 +708,8 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_grou
     //      counter line re-arms it for the next launch
     GRP_STAMP(6);
 #if !(FLAT_ABL & 2)
-    if (use_slots) {
-        if (tid == 0) sh_timed_out = grp_depart_last(grp_lines(ws.cnt, rb.group, Gs, 0, 1), rb.member, Gs) ? 1 : 0;
-        __syncthreads();
-        if (sh_timed_out)      // the last member out re-arms the group's slots: every other member has read them
-            for (int m = tid; m < Gs * kk; m += TPB) __hip_atomic_store(slots + m, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (tid == 0) grp_depart(grp_lines(ws.cnt, rb.group, Gs, 0, 1), rb.member, Gs);
+    if (use_slots) slots_leave(grp_lines(ws.cnt, rb.group, Gs, 0, 1), rb.member, Gs, slots, Gs * kk, &sh_timed_out);
+    else if (tid == 0) grp_depart(grp_lines(ws.cnt, rb.group, Gs, 0, 1), rb.member, Gs);
 #endif
 #ifdef GRP_TRACE
     if (g_grp_trace) {
@@ -1063,12 +1092,8 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_flat
     }
     GRP_STAMP(6);
 #if !(FLAT_ABL & 2)
-    if (use_slots) {
-        if (tid == 0) sh_timed_out = grp_depart_last(grp_lines(ws.cnt, c, g.Gs, 0, 1), member, g.Gs) ? 1 : 0;
-        __syncthreads();
-        if (sh_timed_out)      // the last member out re-arms the group's slots: every other member has read them
-            for (int m = tid; m < g.Gs; m += TPB) __hip_atomic_store(slots + m, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (tid == 0) grp_depart(grp_lines(ws.cnt, c, g.Gs, 0, 1), member, g.Gs);
+    if (use_slots) slots_leave(grp_lines(ws.cnt, c, g.Gs, 0, 1), member, g.Gs, slots, g.Gs, &sh_timed_out);
+    else if (tid == 0) grp_depart(grp_lines(ws.cnt, c, g.Gs, 0, 1), member, g.Gs);
 #endif
 #ifdef GRP_TRACE
     if (g_grp_trace) {

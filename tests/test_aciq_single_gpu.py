@@ -96,12 +96,30 @@ def test_single_launch_equals_the_oracle_on_its_own_statistics(ops, shape, half,
     assert ops.group_status(xd) == 0
 
 
-@pytest.mark.parametrize('shape', SHAPES)
+# The bounded wait carries its clock and poll count from one window of members to the next.  A lane of k_fused_flat takes
+# 4 x 64 members per window: a flat group of more than 256 members needs two.  (k_fused_group's windows are 2 members x
+# meet_lanes(k) lanes: (130, 24, 7, 7) - 33 members, k = 20, 8 lanes - takes three.)
+SECOND_WINDOW = (680, 1, 112, 112)
+
+
+@pytest.mark.parametrize('shape', SHAPES + [SECOND_WINDOW])
 def test_recompute_path_and_reruns_give_the_same_bits(ops, shape):
     """The sum exchange is deterministic: meeting == forced recompute (flag 1) == IEEE divide (flag 2) == a second run."""
     from cnn_quantization_amd import _lib as L
     N, C = shape[:2]
     HW = shape[2] * shape[3]
+    if shape == SECOND_WINDOW:
+        d = describe(N, C, HW)[1]
+        assert d['mode'] == 3 and d['Gs'] > 256, d          # (a planner change must not silently un-test the second window)
+    if shape == (130, 24, 7, 7):
+        # k_fused_group: lane (channel, j) watches members j, j + L, ..., L = the largest power of two <= min(64, 256 / k), two
+        # members per window below K = 32.  (The config-2 plan; the sum kernels cap the tile height of straddling rows at 16
+        # instead of 32: the same plan wherever K is below 16.)
+        from cnn_quantization_amd import _lib
+        d, geo = describe(N, C, HW)[1], (ctypes.c_int32 * 12)()
+        assert _lib.load().cnnq_plan_describe(N, C, HW, 1, 0, geo) == 0
+        lanes = max(l for l in (1, 2, 4, 8, 16, 32, 64) if l == 1 or l * geo[6] <= 256)
+        assert d['mode'] == 2 and d['K'] < 16 and d['Gs'] > 2 * lanes, (d, geo[6])
     xd = acts(shape, 99 + C, relu=False).cuda()
     ops.group_status(xd, clear=True)
     y0, p0 = ops.aciq_qdq_single(xd, N, C, HW, 4, False, True, None, True, want_parts=True)

@@ -76,7 +76,12 @@ SHAPES = [
     (9, 4, 56, 56), (70, 6, 56, 56),                         # a channel row wider than a workgroup: slices x splits
     (66, 3, 112, 112), (260, 2, 112, 112),                   # two-level arrival (more than 16 members per group)
     (130, 2, 40, 36), (1, 1100, 2, 2), (4, 260, 1, 4), (2, 3, 64, 80), (600, 2, 8, 8),
+    (680, 1, 112, 112),                                      # a flat group of more than 256 members: a lane's second window
 ]
+# The bounded wait carries its clock and poll count from one window of members to the next.  A lane of k_mmq_flat takes
+# 4 x 64 members per window: SECOND_WINDOW is the shape whose group needs two.  (The row-piece kernel's windows are
+# 2 or 4 members x meet_lanes(k) lanes: (70, 40, 7, 7), (300, 24, 7, 7) and (600, 2, 8, 8) above need 2 to 5.)
+SECOND_WINDOW = (680, 1, 112, 112)
 
 
 @pytest.mark.parametrize('shape', SHAPES)
@@ -86,6 +91,8 @@ def test_group_equals_chain_and_oracle(ops, shape, half):
     N, C, H, W = shape
     rc, d = describe(N, C, H * W)
     assert rc == 0
+    if shape == SECOND_WINDOW:
+        assert d['mode'] == 3 and d['Gs'] > 256, d          # (a planner change must not silently un-test the second window)
     yc = None
     ops.group_status(torch.empty(1, device='cuda'), clear=True)
     for rnd in range(3):          # a different tensor every launch, the same (never re-zeroed) workspace
@@ -116,6 +123,20 @@ def test_group_plans_cover_one_and_two_level_arrival():
     assert levels >= {(3, 1), (3, 2), (2, 1), (2, 2)}, levels
     assert describe(512, 256, 3136)[1]['mode'] == 3 and describe(512, 1024, 196)[1]['mode'] == 2
     assert describe(512, 64, 112 * 112)[1]['Gs'] == 196          # 512 * 3136 float4 / (256 * 32)
+
+
+def test_row_piece_shapes_reach_a_second_window():
+    """k_mmq_group: lane (channel, j) watches members j, j + L, ... with L = meet_lanes(k) (the largest power of two with
+    L k <= 256, 64 at most), 2 members per window below K = 32: these SHAPES give a lane more than one window."""
+    from cnn_quantization_amd import _lib
+    for shape in ((70, 40, 7, 7), (300, 24, 7, 7), (600, 2, 8, 8)):
+        assert shape in SHAPES
+        rc, d = describe(shape[0], shape[1], shape[2] * shape[3])
+        out = (ctypes.c_int32 * 12)()
+        assert rc == 0 and _lib.load().cnnq_plan_describe(shape[0], shape[1], shape[2] * shape[3], 1, 0, out) == 0
+        k = out[6]
+        lanes = max(l for l in (1, 2, 4, 8, 16, 32, 64) if l == 1 or l * k <= 256)
+        assert d['mode'] == 2 and d['K'] < 32 and d['Gs'] > 2 * lanes, (shape, d, k)
 
 
 def test_group_nan_inf_follow_torch(ops):

@@ -159,10 +159,42 @@ def check_statistics(ops, shape, need):
     assert ops.group_status(xd) == 0
 
 
-@pytest.mark.parametrize('shape', SHAPES[:4] + GROUP_SHAPES + BIG_GROUP_SHAPES[1:])
+# The bounded wait carries its clock and poll count from one window of members to the next.  A lane of k_stats_flat takes
+# 4 x 32 members per window: a flat group of more than 128 members needs two.  (k_stats_group's windows are 4 members x
+# meet_lanes(planes x k) lanes (below): (300, 8, 7, 7) - 75 members, 2 and 4 lanes in the two phases - takes ten and five.)
+SECOND_WINDOW = (340, 1, 112, 112)
+
+
+def describe(N, C, HW):
+    """The plan of the config-2 single launch and the channels k a row-piece workgroup owns.  The statistics kernels plan with a
+    lower cap on the tile height of straddling rows (16 instead of 32): the same plan wherever K is below 16."""
+    from cnn_quantization_amd import _lib
+    out, geo = (ctypes.c_int32 * 8)(), (ctypes.c_int32 * 12)()
+    rc = _lib.load().cnnq_pc_group_describe(N, C, HW, out)
+    d = dict(zip(('A', 'K', 'mode', 'S', 'ncb', 'Gs', 'groups', 'wgs'), list(out)))
+    if rc == 0 and d['mode'] == 2:
+        assert _lib.load().cnnq_plan_describe(N, C, HW, 1, 0, geo) == 0
+        d['k'] = geo[6]
+    return rc, d
+
+
+def meet_lanes(values):
+    """the lane layout of sg_fold: lanes per watched value, the largest power of two <= min(64, 256 / values)"""
+    return max(l for l in (1, 2, 4, 8, 16, 32, 64) if l == 1 or l * min(values, 256) <= 256)
+
+
+@pytest.mark.parametrize('shape', SHAPES[:4] + GROUP_SHAPES + BIG_GROUP_SHAPES[1:] + [SECOND_WINDOW])
 def test_recompute_path_and_reruns_give_the_same_bits(ops, shape):
     N, C = shape[:2]
     HW = shape[2] * shape[3]
+    if shape == SECOND_WINDOW:
+        from cnn_quantization_amd import _lib
+        rc, d = describe(N, C, HW)
+        assert rc == 0 and d['mode'] == 3 and d['Gs'] > 128, d      # (a planner change must not silently un-test the second window)
+        assert _lib.load().cnnq_pc_stats_route(N, C, HW, 1, ops.GROUP_WS_BYTES, 0) == 1      # ... through k_stats_flat
+    if shape == (300, 8, 7, 7):
+        rc, d = describe(N, C, HW)      # k_stats_group: 5 k values per member in phase 1, 2 k in phase 2; windows of 4 members per lane
+        assert rc == 0 and d['mode'] == 2 and d['K'] < 16 and d['Gs'] > 4 * meet_lanes(2 * d['k']) >= 4 * meet_lanes(5 * d['k']), d
     xd = acts(shape, 21 + C).cuda()
     ops.group_status(xd, clear=True)
     st0, mom0 = ops.pc_stats_single(xd, N, C, HW, True, True, True)
