@@ -52,6 +52,7 @@
 #include "cnnq_half.hip.h"
 #include "cnnq_half_stats.hip.h"
 #include "cnnq_half_bcorr.hip.h"
+#include "cnnq_half_aciq.hip.h"
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_nhwc_collect.hip.h"
@@ -1813,6 +1814,101 @@ int cnnq_pc_qdq_bcorr_dt(const void* x, void* y, int dtype, int64_t N, int64_t C
         using P = decltype(pc);
         hipLaunchKernelGGL((k_h_qdq_bias<typename P::T, P::W>), dim3((unsigned)(C * gq.S)), dim3(TPB), 0, st, xh, yh, gq, qp, bias);
     });
+}
+
+// ---- dynamic ACIQ clipping (config 3) on contiguous bf16 / fp16 activations (cnnq_half_aciq.hip.h) ------------------------------
+// ws, doubles: part[G][CNNQ_NMOM][C], mom[CNNQ_NMOM][C], part2[G][CNNQ_NDEV][C] with G = S * column splits - cnnq_pc_stats_dt's
+// (the table stays outside); fp32: what cnnq_pc_aciq_qdq takes at either alignment
+size_t cnnq_pc_aciq_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype) {
+    if (dtype == CNNQ_DTYPE_F32) {
+        const size_t a = cnnq_pc_aciq_workspace(N, C, HW, 1), b = cnnq_pc_aciq_workspace(N, C, HW, 0);
+        return a > b ? a : b;
+    }
+    return cnnq_pc_stats_dt_workspace(N, C, HW, dtype);
+}
+
+// what config 3's entry points on contiguous tensors check of their configuration, before any launch
+static bool h_aciq_cfg_ok(const cnnq_params_cfg* cfg) {
+    return cfg && !check_cfg(cfg) && !cfg->direct_range && (cfg->clip == 1 || cfg->clip == 2);
+}
+
+// the route word of a bf16 / fp16 tensor at piece width w: 1 - k_h_aciq_whole alone (no bit allocation in effect) / 3 - pass A,
+// merge and k_bitalloc, then k_h_aciq_whole<TABLE> (bit allocation on the std prior) / 2 - the chain (also: bit allocation on the
+// b prior, which needs every channel's b before any channel's parameters) / 0 - a class of layer that did not win against the
+// upcast route and stays there (h_aciq_native; the call itself runs every class, on the chain)
+static int h_aciq_route(int64_t N, int64_t C, int64_t HW, int dtype, int w, const cnnq_params_cfg* cfg, int allow_single_launch) {
+    const bool ba = cfg_bit_alloc(cfg);
+    if (allow_single_launch && !(ba && cfg->prior_is_b) && h_aciq_whole_fits(N, HW, w) &&
+        (allow_single_launch > 1 || h_aciq_whole_wins(N, C, HW, dtype, ba)))
+        return ba ? 3 : 1;
+    return h_aciq_native(N, C, HW, dtype) ? 2 : 0;
+}
+
+// Which launches cnnq_pc_aciq_qdq_dt makes for this geometry and configuration (host only): out = {piece width W, batch splits S,
+// column splits of the statistics launches, route (h_aciq_route)}.  fp32: {0, the chain's records, 1, 2}.
+int cnnq_pc_route_aciq_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, const cnnq_params_cfg* cfg, int allow_single_launch,
+                          int32_t out[4]) {
+    const HPlan p(N, C, HW, dtype, out && pow2(align_bytes) && h_aciq_cfg_ok(cfg), true);
+    if (p.rc) return p.rc;
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    const int w = f32 ? 0 : h_piece(HW, (uintptr_t)align_bytes, 0);
+    out[0] = w;
+    out[1] = f32 ? h_records_f32(N, C, HW) : p.S;
+    out[2] = f32 ? 1 : p.cs;
+    out[3] = f32 ? 2 : h_aciq_route(N, C, HW, dtype, w, cfg, allow_single_launch);
+    return 0;
+}
+
+// int_quantizer.py:327-352 (statistics, ACIQ clipping, bit allocation) + 409-451, 557-603 (parameters, Q/DQ) on x[N][C][HW] of
+// bf16 / fp16 with dynamic statistics: k_h_aciq_whole (route 1), or k_h_moments -> k_combine -> k_bitalloc -> k_h_aciq_whole<TABLE>
+// (route 3), or the chain k_h_moments -> k_combine (-> k_h_absdev -> k_combine_dev) -> k_params -> k_h_qdq (route 2)
+int cnnq_pc_aciq_qdq_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws,
+                        float* stats, float* qp, float* diag, int allow_single_launch, void* stream) {
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    const uintptr_t es = f32 ? 4 : 2;
+    const bool ok = x && y && x != y && ws && stats && qp && !misaligned(ws, 8) && !misaligned(stats, 4) && !misaligned(qp, 4) &&
+                    !misaligned(diag, 4) && !misaligned(x, es) && !misaligned(y, es) && h_aciq_cfg_ok(cfg) &&
+                    !(cfg_bit_alloc(cfg) && !diag);                                   // the bit table lives in diag
+    const HPlan p(N, C, HW, dtype, ok);
+    if (p.rc) return p.rc;
+    hipStream_t st = hs(stream);
+    if (f32) {
+        const float* xf = static_cast<const float*>(x);
+        const int G = cnnq_pc_groups(N, C, HW, al16(xf) ? 1 : 0);
+        if (G <= 0) return g_error(G);
+        const int rc = cnnq_pc_aciq_qdq(xf, static_cast<float*>(y), N, C, HW, cfg, ws, qp, diag, stream);
+        if (rc) return rc;
+        // the chain keeps its table behind its records: the caller's copy
+        if (hipMemcpyAsync(stats, AciqWs(ws, G, C).stats, (size_t)CNNQ_NSTAT * (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return launch_status();
+        return 0;
+    }
+    const int w = h_piece(HW, (uintptr_t)h_align(x, y), 0);
+    const int route = h_aciq_route(N, C, HW, dtype, w, cfg, allow_single_launch);
+    const bool need_b = cfg->clip == 1 || (cfg_bit_alloc(cfg) && cfg->prior_is_b);
+    if (route == 1 || route == 3) {
+        HAciqArgs a{*cfg, nullptr, stats, qp, diag};
+        if (route == 3) {
+            int rc = cnnq_pc_stats_dt(x, dtype, N, C, HW, 0, 0, 0, ws, nullptr, stats, stream);
+            float* bits = nullptr;
+            if (!rc) rc = launch_bitalloc(stats, C, cfg, diag, &bits, st);
+            if (rc) return rc;
+            a.bits = bits;
+        }
+        const HGeo g = h_geo(N, C, HW, w, 1, 1);
+        return h_launch(dtype, w, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
+            with_bool(route == 3, [&](auto table) {
+                using P = decltype(pc);
+                if constexpr (P::W > 1)
+                    hipLaunchKernelGGL((k_h_aciq_whole<typename P::T, P::W, h_whole_k<P::W>(), decltype(table)::value>), dim3((unsigned)C),
+                                       dim3(HTPB), 0, st, xh, yh, g, a);
+            });
+        });
+    }
+    int rc = cnnq_pc_stats_dt(x, dtype, N, C, HW, need_b ? 1 : 0, 0, 0, ws, nullptr, stats, stream);
+    if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
+    if (rc) return rc;
+    return h_qdq(x, y, dtype, N, C, HW, qp, nullptr, HArgs{}, st);
 }
 
 int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream) {

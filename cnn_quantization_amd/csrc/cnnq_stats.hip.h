@@ -379,6 +379,9 @@ __device__ __forceinline__ float std_of(const MomSum& r) {
     if (var < 0.) var = 0.;
     return (float)sqrt(var);
 }
+// b = mean |x - mean| from the merged pass-B sum: the one expression of k_combine_all, k_combine_dev and the resident bf16 / fp16
+// kernel (cnnq_half_aciq.hip.h), as mean_of / std_of are for pass A
+__device__ __forceinline__ float b_of(double sa, double cnt) { return (float)(sa / cnt); }
 
 // merge G records per channel; mseg_of(G, C) lanes per channel (grid: ceil(C / merge_cpw(G, C)))
 __global__ void __launch_bounds__(TPB) k_combine(const double* __restrict__ part, int G, int C, int has_relu,
@@ -573,7 +576,7 @@ __global__ void __launch_bounds__(TPB) k_combine_all(const double* __restrict__ 
         std_pos = (float)sqrt(rv);
     }
     stats[(size_t)CNNQ_STAT_STD_POS * C + c] = std_pos;   // every row is written: no memset in front of the chain
-    stats[(size_t)CNNQ_STAT_B * C + c] = (float)(sa / r.cnt);
+    stats[(size_t)CNNQ_STAT_B * C + c] = b_of(sa, r.cnt);
     stats[(size_t)CNNQ_STAT_KURT * C + c] = want_kurt ? (float)(sk / r.cnt - 3.) : 0.f;
 }
 
@@ -591,7 +594,7 @@ __global__ void __launch_bounds__(TPB) k_combine_dev(const double* __restrict__ 
     }
     if (stats) {
         const double cnt = mom[(size_t)CNNQ_MOM_COUNT * C + c];
-        stats[(size_t)CNNQ_STAT_B * C + c] = (float)(sa / cnt);
+        stats[(size_t)CNNQ_STAT_B * C + c] = b_of(sa, cnt);
         if (want_kurt) stats[(size_t)CNNQ_STAT_KURT * C + c] = (float)(sk / cnt - 3.);
     }
 }

@@ -274,6 +274,9 @@ class TruncationOpManagerInference:
             raise NotImplementedError('quantizer family %r' % family)
         q = int_quantizer(qtype, qparams[family] if family in qparams else {})
         q.group = self.group
+        # the product's quantizers quantize contiguous bf16 / fp16 activations under dynamic ACIQ clipping where they lie
+        # (IntQuantizer._half_aciq)
+        q.half_dynamic = True
         return q
 
     def _fill(self, qtype, qparams, qweight):

@@ -95,7 +95,8 @@ def _half_only(what, reason):
 
 # switches, read ONCE at import (not per hot call); reload_switches() re-reads them after the environment changed (tests, tools)
 def reload_switches():
-    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC, _HALF_TABLE
+    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC, _HALF_TABLE, _HALF_ACIQ
+    _HALF_ACIQ = os.environ.get('CNNQ_HALF_ACIQ', '1') != '0'          # 0: dynamic ACIQ on contiguous half activations takes the upcast route (A/B)
     _HALF_TABLE = os.environ.get('CNNQ_HALF_TABLE', '1') != '0'        # 0: calibrated per-channel half activations take the upcast route (A/B)
     _NHWC = os.environ.get('CNNQ_NHWC', '1') != '0'                    # 0: channels_last tensors take the NCHW copy route (A/B)
     _ACIQ_SINGLE = os.environ.get('CNNQ_ACIQ_SINGLE', '1') != '0'      # 0: the ACIQ path always takes the five-launch chain (A/B)
@@ -207,10 +208,15 @@ _NHWC_WS = {'nhwc': 'cnnq_pc_nhwc_workspace', 'aciq_nhwc': 'cnnq_pc_aciq_nhwc_wo
             'rows': 'cnnq_rows_stats_workspace'}
 
 
+_HALF_WS = {'stats_half': 'cnnq_pc_stats_dt_workspace', 'bcorr_half': 'cnnq_pc_qdq_bcorr_dt_workspace',
+            'aciq_half': 'cnnq_pc_aciq_dt_workspace'}
+
+
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
     arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc', 'stats_nhwc': N = rows; 'rows':
-    N = rows, C = their length; 'pt_clip': N = elements; 'stats_half', 'bcorr_half': the dtype code).  0 from the library: no plan for the geometry."""
+    N = rows, C = their length; 'pt_clip': N = elements; 'stats_half', 'bcorr_half', 'aciq_half': the dtype code).  0 from the library: no plan for
+    the geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
@@ -226,8 +232,8 @@ def _ws_bytes(kind, N, C, HW, arg=0):
                 raise L.CnnqError('cnnq_pt_clip_workspace(%d, %d): bad arguments' % (N, arg))
         elif kind == 'aciq':
             nbytes = lib.cnnq_pc_aciq_workspace(N, C, HW, arg)
-        elif kind in ('stats_half', 'bcorr_half'):
-            fn = 'cnnq_pc_stats_dt_workspace' if kind == 'stats_half' else 'cnnq_pc_qdq_bcorr_dt_workspace'
+        elif kind in _HALF_WS:
+            fn = _HALF_WS[kind]
             nbytes = getattr(lib, fn)(N, C, HW, arg)
             if nbytes == 0:
                 L.check(min(lib.cnnq_pc_groups(N, C, HW, 0), -1), '%s(%d,%d,%d,%d)' % (fn, N, C, HW, arg))
@@ -1863,6 +1869,58 @@ def aciq_qdq_nhwc(x, num_bits, positive=False, clip='laplace', bit_alloc=False, 
         L.check(rc, 'cnnq_pc_aciq_qdq_nhwc')
     return _result(y, entropy=_replica_entropy(x, hist, ent_batched, st) if want_entropy else None,
                    parts=dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:]) if want_parts else None)
+
+
+_ACIQ_HALF_NATIVE = {}
+
+
+def _aciq_half_native(N, C, HW, dtype, bit_alloc=False, prior_is_b=False):
+    """The route word of cnnq_pc_route_aciq_dt's report for this class of contiguous bf16 / fp16 layer and bit allocation
+    (bit_alloc: in effect, i.e. at 4 bits or fewer): 1 - dynamic ACIQ in one launch, 3 - pass A and the bit allocation in front of
+    it, 2 - the chain, 0 - a class that measured slower native than through the upcast and is sent back there.  The quantizer
+    (_half_aciq) and the tests patch the function and empty the cache by name."""
+    cfg = _params_cfg(4, False, 'laplace', bit_alloc, prior_is_b, None, True, False)
+    cache = _ACIQ_HALF_NATIVE.setdefault((bool(bit_alloc), bool(prior_is_b)), {})
+    return _half_route_word(cache, int, 'cnnq_pc_route_aciq_dt', N, C, HW, dtype, ctypes.byref(cfg), 1)
+
+
+def aciq_qdq_half(x, num_bits, positive=False, clip='laplace', bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
+                  stats=None, out=None, want_parts=False, single_launch=None):
+    """Config 3 (iq.py:327-352 -> 409-451: ACIQ clipping 'laplace' / 'gaus', optionally bit allocation) on a contiguous 4-D bf16 /
+    fp16 activation, on the storage as it is: cnnq_pc_aciq_qdq_dt - the statistics, the parameters and the
+    Q/DQ in one launch where a channel's batch population fits one workgroup's registers (behind pass A and the bit allocation
+    with -baa), else the chain of cnnq_pc_stats_dt, cnnq_pc_params and cnnq_pc_qdq_dt; one host call, one cached workspace - or,
+    with `stats` ([NSTAT, C], -sm use), pc_params and the table-driven Q/DQ.  y has x's dtype; want_parts: (y, dict(stats, qp,
+    diag)).  single_launch: None - the route function's choice; 0 - the chain; 2 - the resident form wherever the channel fits (the
+    chain elsewhere), for tests and A/B.  One GPU: the statistics are this tensor's.  Anything else - a CPU tensor, float32, not
+    4-D, not contiguous - raises: nothing is copied or upcast here."""
+    what = 'aciq_qdq_half'
+    if clip not in ('laplace', 'gaus'):
+        raise L.CnnqError("%s: clip must be 'laplace' or 'gaus', got %r" % (what, clip))
+    x, N, C, HW, dt, st = _admit_half(x, what, 'act_qdq_per_channel')
+    use_ba = bool(bit_alloc) and num_bits <= 4
+    if stats is not None:
+        if not _is_table(stats, torch.float32, (L.NSTAT, C), x.device):
+            raise L.CnnqError('%s: stats must be a contiguous float32 [%d, %d] device table' % (what, L.NSTAT, C))
+        qp, diag = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
+        return _result(pc_qdq(x, N, C, HW, qp, out=out), parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
+    if single_launch not in (None, 0, 1, 2):
+        raise L.CnnqError('%s: single_launch must be None, 0, 1 or 2, got %r' % (what, single_launch))
+    cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
+    nbytes = _ws_bytes('aciq_half', N, C, HW, dt)
+    y = _out_like(x, out)
+    if want_parts:
+        tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, C, dtype=torch.float32, device=x.device)
+        ws, tp = _scratch(x, 'aciq_half', nbytes, st).data_ptr(), tabs.data_ptr()
+    else:
+        # the tables nobody outside the call reads follow the records in the cached workspace
+        ws = _scratch(x, 'aciq_half', nbytes + (L.NSTAT + L.NQP + L.NDIAG) * C * 4, st).data_ptr()
+        tp = ws + nbytes
+    rc = L.load().cnnq_pc_aciq_qdq_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                      tp + (L.NSTAT + L.NQP) * C * 4, 1 if single_launch is None else int(single_launch), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_aciq_qdq_dt')
+    return _result(y, parts=dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:]) if want_parts else None)
 
 
 def weight_correction(w, w_q, vcorr=False, bcorr=False):

@@ -97,12 +97,17 @@ class IntQuantizer:
         # into its own passes resets it to None and raises bcorr_fused, otherwise the layer corrects after
         self.fuse_bcorr = None
         self.bcorr_fused = False
+        # dynamic ACIQ clipping of a contiguous bf16 / fp16 activation where it lies (_half_aciq): opt-in
+        # per quantizer object - the inference manager sets it on the quantizers it builds; one constructed directly keeps the
+        # upcast route
+        self.half_dynamic = False
 
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
         if (isinstance(tensor, torch.Tensor) and tensor.dtype in HALF_DTYPES
                 and not self._half_native(tensor, override_att, stat_id)
                 and not self._half_table(tensor, self._att(override_att)('clipping'), stat_id, self._att(override_att))
+                and not self._half_aciq(tensor, self._att(override_att)('clipping'), stat_id, self._att(override_att))
                 and not self._nhwc_midtread(tensor, self._att(override_att))
                 and not self._nhwc_entropy(tensor, self._att(override_att)) and not self._flat_clip(tensor, self._att(override_att))
                 and not self._flat_midtread(tensor, self._att(override_att)) and not self._flat_kld(tensor, self._att(override_att))):
@@ -255,6 +260,24 @@ class IntQuantizer:
         N, C, HW = ops.geometry(tensor)
         return ops._table_half_native(N, C, HW, tensor.dtype) != 0
 
+    def _half_aciq(self, tensor, clip_type, stat_id, att=None):
+        """gemmlowpClippingQuantize quantizes a contiguous bf16 / fp16 tensor with DYNAMIC statistics where it lies
+        (ops.aciq_qdq_half): half_dynamic set on this object, no stat_id (calibrated statistics are
+        _half_table's), Laplace or Gaussian clipping with or without bit allocation, no mid-tread, KLD or entropy measurement, no
+        bias correction to fold in, one GPU's own data, the switch CNNQ_HALF_ACIQ on and a class of layer the route function keeps
+        native.  Kept apart from _half_native, whose answers are pinned by tests; shape, strides and attributes only."""
+        att = att or (lambda k: getattr(self, k))
+        if not (self.half_dynamic and stat_id is None and getattr(tensor, 'is_cuda', False) and tensor.dtype in HALF_DTYPES
+                and tensor.dim() == 4 and tensor.is_contiguous() and tensor.numel() > 0):
+            return False
+        if not (bool(att('pcq_a')) and _is_pc_act(tensor) and clip_type in ('laplace', 'gaus') and not att('mtd_quant')
+                and not att('kld') and not att('measure_entropy') and self.fuse_bcorr is None and self._one_gpu()
+                and ops._HALF_ACIQ):
+            return False
+        N, C, HW = ops.geometry(tensor)
+        use_ba = bool(att('bit_alloc_act')) and att('num_bits') <= 4
+        return ops._aciq_half_native(N, C, HW, tensor.dtype, use_ba, use_ba and att('bit_alloc_prior') != 'gaus') != 0
+
     def _table_half(self, tensor, table, clip_type, prior_b):
         """The _half_table route: the parameters of the calibration table, then Q/DQ - with a pending correction folded in - where
         the tensor lies."""
@@ -371,6 +394,11 @@ class IntQuantizer:
                 return ops.aciq_qdq_nhwc(tensor, self.num_bits, positive=self._positive, clip=clip_type,
                                          bit_alloc=self.bit_alloc_act, prior_is_b=prior_b, target=self.bit_alloc_target_act,
                                          round_mode=self.bit_alloc_round, stats=table)
+            if self._half_aciq(tensor, clip_type, stat_id):
+                # a contiguous bf16 / fp16 activation, dynamic statistics: quantized where it lies, the result keeps the dtype
+                return ops.aciq_qdq_half(tensor, self.num_bits, positive=self._positive, clip=clip_type,
+                                         bit_alloc=self.bit_alloc_act, prior_is_b=prior_b, target=self.bit_alloc_target_act,
+                                         round_mode=self.bit_alloc_round)
             out = ops.act_qdq_per_channel(tensor, self.num_bits, positive=self._positive, clip=clip_type,
                                           bit_alloc=self.bit_alloc_act, prior_is_b=prior_b,
                                           target=self.bit_alloc_target_act, round_mode=self.bit_alloc_round,

@@ -787,6 +787,44 @@ int cnnq_pc_route_qdq_bcorr_dt(int64_t N, int64_t C, int64_t HW, int dtype, int 
 int cnnq_pc_qdq_bcorr_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, int relu_first, void* ws,
                          double* sums, float* bias, int allow_single_launch, void* stream);
 
+/* Dynamic ACIQ clipping (config 3: -c laplace / gaus, optionally -baa; int_quantizer.py:327-352 statistics, clipping and bit
+ * allocation, 409-451 and 557-603 parameters and Q/DQ) on CONTIGUOUS bf16 / fp16 activations x[N][C][HW], on the storage as it
+ * lies: no fp32 copy.  Counterpart of cnnq_pc_aciq_qdq behind ONE call; the rows are cut into pieces as for cnnq_pc_stats_dt
+ * (W = 8 / 4 / 2 / 1 from HW and the alignment x and y share: every (HW, alignment) has a route); a workgroup owns one channel.
+ * Routes:
+ *   2. the chain: cnnq_pc_stats_dt's launches (pass A, merge; pass B and its merge when b is needed: Laplace clipping, or bit
+ *      allocation on the b prior), cnnq_pc_params, cnnq_pc_qdq_dt's launch - 8 B/elem with b, 6 without;
+ *   1. one launch, one 1024-lane workgroup per channel that keeps the channel in registers: moments, (b,) parameters, Q/DQ -
+ *      4 B/elem.  Only where N * HW <= 131072 and W >= 2, and only without bit allocation in effect (which couples all
+ *      channels through their std);
+ *   3. pass A, merge and the bit allocation on the std prior, then route 1's launch reading its table - 6 B/elem;
+ * The values of a piece are added in fp32 (pairs, then halves), the pieces in fp64, in an order fixed by (N, C, HW, alignment,
+ * route) alone: run after run the same bits, no atomics, but not the fp32 chain's order.  Promised: stats[CNNQ_NSTAT][C] is
+ * written completely (KURT and STD_POS zero, B zero unless b was needed), rows MIN / MAX exact (a NaN element makes them NaN),
+ * MEAN / STD / B within the statistics tier of fp64; given that table, qp[CNNQ_NQP][C] and diag[CNNQ_NDIAG][C] are cnnq_pc_params'
+ * and y is cnnq_pc_qdq_dt's on qp, bit for bit, on every route.  CNNQ_DTYPE_F32 forwards to cnnq_pc_aciq_qdq (stats: a copy of
+ * its table).
+ * cnnq_pc_aciq_dt_workspace: bytes of `ws` - cnnq_pc_stats_dt's records, which do not depend on the alignment or the route (fp32:
+ * cnnq_pc_aciq_workspace at either alignment; 0 on bad arguments or a geometry beyond cnnq_pc_groups' limits).
+ * cnnq_pc_route_aciq_dt (host only, nothing enqueued): out = {piece width W, batch splits S, column splits, route}; route 1 / 2 /
+ * 3 as above, 0 - a class of layer that did not measure faster than the upcast route and is left there by callers that have the
+ * choice (cnnq_pc_aciq_qdq_dt itself runs every class, on route 2): rows of an odd HW with N * HW >= 6272.  allow_single_launch:
+ * 0 - never route 1 / 3; 1 - where they measured faster than route 2 (at least 128 channels and, from N * HW >= 65536 on, at
+ * most 512 with bit allocation, 1024 without; from 25088 on, 256 channels, without bit allocation up to 512); 2 - wherever the
+ * channel fits (tests, A/B).  A function of its arguments alone; fp32: {0,
+ * cnnq_pc_groups' records, 1, 2}; align_bytes: the power of two that divides x and y (<= 16 is what matters). */
+size_t cnnq_pc_aciq_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype);
+int cnnq_pc_route_aciq_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, const cnnq_params_cfg* cfg, int allow_single_launch,
+                          int32_t out[4]);
+/* stats, qp and diag are OUTPUTS; diag may be NULL without bit allocation in effect.  ws: cnnq_pc_aciq_dt_workspace bytes, 8-byte
+ * aligned (route 1 does not touch it).  A bad dtype, N, C or HW < 1, a NULL x / y / cfg / ws / stats / qp, a misaligned ws / stats /
+ * qp / diag, an x or y not aligned to its element size, x == y, a cfg cnnq_pc_params refuses, direct_range, a clip other than
+ * Laplace / Gaussian (1 / 2) or bit allocation without diag returns CNNQ_EINVAL, a geometry beyond cnnq_pc_groups' limits that
+ * function's code - before anything touches the device.  Re-entrant, allocates nothing, no host synchronisation,
+ * graph-capturable. */
+int cnnq_pc_aciq_qdq_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws,
+                        float* stats, float* qp, float* diag, int allow_single_launch, void* stream);
+
 /* The statistics of FEW, VERY LONG rows over flat storage - the per-tensor calibration table of statistic_manager.py:55-96
  * (rows = 1: the whole tensor) and the per-sample sums of squares of distance_stats.py:22-33 (rows = N: the samples) - for fp32 /
  * bf16 / fp16 elements, on the storage as it lies: x is viewed as [rows][len], every row contiguous and the rows back to back.
