@@ -8,6 +8,7 @@ with no transposed copies, no elementwise temporaries and no host synchronisatio
 
 Only the arithmetic lives on the device; there is no CPU path (CPU tensors raise)."""
 import math
+from functools import partial
 
 import numpy as np
 import torch
@@ -16,10 +17,9 @@ from .. import _lib as L
 from .. import distributed as D
 from .. import ops
 
-# bf16 / fp16 activations.  Configs 1 and 2 (per-tensor and per-channel min/max, dynamic or from a statistics file) run on
-# their half-precision kernels.  Every other path that meets a half tensor goes through upcast_fallback, the ONE place that
-# upcasts: it computes on x.float() and returns .to(x.dtype), and counts the call (HALF_FALLBACKS) so that tests can prove
-# configs 1 and 2 never arrive there.
+# bf16 / fp16 activations.  A tensor whose route (IntQuantizer._route) has a name is quantized where it lies.
+# Every other path that meets a half tensor goes through upcast_fallback, the ONE place that upcasts: it computes on x.float() and
+# returns .to(x.dtype), and counts the call (HALF_FALLBACKS) so that tests can prove the native routes never arrive there.
 HALF_DTYPES = (torch.bfloat16, torch.float16)
 HALF_FALLBACKS = 0
 
@@ -49,11 +49,25 @@ def _dense_nhwc(t):
     return t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last) and ops._NHWC
 
 
+def _storage(t):
+    """The storage class of the per-channel routes: 'nhwc' - dense channels_last with the switch on, 'half' - a contiguous non-empty
+    4-D bf16 / fp16 tensor on the device, None - neither.  The costly fact: a route asks it once, after its attributes."""
+    return 'nhwc' if _dense_nhwc(t) else 'half' if (getattr(t, 'is_cuda', False) and t.dtype in HALF_DTYPES and t.dim() == 4
+                                                    and t.is_contiguous() and t.numel() > 0) else None
+
+
 def _to_f32_vec(v, C):
     a = np.asarray(v, dtype=np.float32).reshape(-1)
     if a.size == 1 and C > 1:
         a = np.repeat(a, C)
     return torch.from_numpy(np.ascontiguousarray(a))
+
+
+# the rows of the calibration table every ACIQ clipping reads (per channel, per tensor and -c mix)
+ACIQ_ROWS = {L.STAT_MIN: ('min', 'mean'), L.STAT_MAX: ('max', 'mean'), L.STAT_MEAN: ('mean', 'mean'), L.STAT_B: ('b', 'mean'),
+             L.STAT_STD: ('std', 'mean')}
+# the routes _half_native answers for: configs 1 and 2, config 3 on channels_last, a correction folded in on channels_last
+HALF_NATIVE_ROUTES = frozenset(('minmax_pt', 'minmax_pc', 'half_minmax', 'nhwc_aciq', 'nhwc_bcorr'))
 
 
 class IntQuantizer:
@@ -97,204 +111,180 @@ class IntQuantizer:
         # into its own passes resets it to None and raises bcorr_fused, otherwise the layer corrects after
         self.fuse_bcorr = None
         self.bcorr_fused = False
-        # dynamic ACIQ clipping of a contiguous bf16 / fp16 activation where it lies (_half_aciq): opt-in
-        # per quantizer object - the inference manager sets it on the quantizers it builds; one constructed directly keeps the
-        # upcast route
+        # the route 'half_aciq' (dynamic ACIQ on a contiguous bf16 / fp16 activation) is opt-in per object:
+        # the inference manager sets this on the quantizers it builds; one constructed directly keeps the upcast route
         self.half_dynamic = False
 
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
+        att = self._att(override_att)
+        branch = self._branch(att, tensor)
         if (isinstance(tensor, torch.Tensor) and tensor.dtype in HALF_DTYPES
-                and not self._half_native(tensor, override_att, stat_id)
-                and not self._half_table(tensor, self._att(override_att)('clipping'), stat_id, self._att(override_att))
-                and not self._half_aciq(tensor, self._att(override_att)('clipping'), stat_id, self._att(override_att))
-                and not self._nhwc_midtread(tensor, self._att(override_att))
-                and not self._nhwc_entropy(tensor, self._att(override_att)) and not self._flat_clip(tensor, self._att(override_att))
-                and not self._flat_midtread(tensor, self._att(override_att)) and not self._flat_kld(tensor, self._att(override_att))):
+                and self._route(branch, tensor, stat_id, att) is None):
             return upcast_fallback(self.__call__, tensor, id, tag, stat_id, override_att)
         if override_att is not None:
             orig_att = getattr(self, override_att[0])
             setattr(self, override_att[0], override_att[1])
         try:
-            if self.kld:
-                res = self.gemmlowpKldQuantize(tensor, tag, stat_id=stat_id)
-            elif self.clipping != 'no':
-                if self.mtd_quant:
-                    res = self.mid_tread_quantize_activation(tensor, id)
-                else:
-                    res = self.gemmlowpClippingQuantize(tensor, id, tag, stat_id=stat_id, clip_type=self.clipping)
-            elif self.pcq_w:
-                if self.mtd_quant:
-                    res = self.mid_tread_quantize_weights_per_channel(tensor, id)
-                else:
-                    res = self.gemmlowpQuantizeWeightsPerChannel(tensor, id)
-            elif self.pcq_a and _is_pc_act(tensor):
-                if self.mtd_quant:
-                    res = self.mid_tread_quantize_activation_per_channel(tensor, id)
-                else:
-                    res = self.gemmlowpQuantizeActivationPerChannel(tensor, id, tag, stat_id=stat_id)
-            else:
-                res = self.gemmlowpMinMaxQuantize(tensor, tag, stat_id=stat_id)
+            return BRANCH_CALLS[branch](self, tensor, id, tag, stat_id)
         finally:
             if override_att is not None:
                 setattr(self, override_att[0], orig_att)
-        return res
 
     def _att(self, override_att=None):
-        """The attribute lookup the dispatch predicates share: __call__'s override_att pair wins over the attribute."""
-        return lambda k: override_att[1] if override_att is not None and override_att[0] == k else getattr(self, k)
+        """The attribute lookup the route decision reads through: __call__'s override_att pair wins over the attribute."""
+        return partial(getattr, self) if override_att is None else \
+            lambda k: override_att[1] if override_att[0] == k else getattr(self, k)
 
     def _one_gpu(self):
         """Replicated data excluded (group is not False), a batch that is not sharded, no forced exchange."""
         return self.group is not False and D.world_size(self.group) == 1 and not D.forced_exchange()
 
-    def _half_native(self, tensor, override_att=None, stat_id=None):
-        """Whether a bf16 / fp16 tensor takes a path with half kernels: config 2 (gemmlowpQuantizeActivationPerChannel without
-        clipping, bit allocation, entropy, a bias correction to fold in or a sharded batch), config 1 (gemmlowpMinMaxQuantize),
-        config 3 on a dense channels_last tensor (_nhwc_aciq: gemmlowpClippingQuantize's native route), or - stat_id given - a
-        pending bias correction on a dense channels_last tensor (_nhwc_bcorr).  Config 5 on a dense channels_last tensor has half
-        kernels too, but is asked separately (_nhwc_midtread): the answers given here for mtd_quant are pinned by tests."""
-        att = self._att(override_att)
+    # The route decision (table: DESIGN.md section 26).  Level 1, _branch: the branch method __call__ hands the tensor to.  Level 2,
+    # one function per branch: the name of the native route its method takes, None - its fp32 code, which a half tensor reaches
+    # through the upcast.  Shape, strides and attributes (att: the lookup of _att) only; nothing stored; before _take_bcorr.
+    def _branch(self, att, tensor):
+        """iq.py:92-122's ladder."""
         if att('kld'):
-            return False
-        if self._nhwc_bcorr(tensor, att('clipping'), stat_id, att):
-            return True
+            return 'kld'
         if att('clipping') != 'no':
-            return not att('mtd_quant') and self._nhwc_aciq(tensor, att('clipping'), att)
+            return 'midtread' if att('mtd_quant') else 'clip'
         if att('pcq_w'):
-            return False
+            return 'midtread_w' if att('mtd_quant') else 'weights'
         if att('pcq_a') and _is_pc_act(tensor):
-            return (not att('mtd_quant') and not att('measure_entropy') and self.fuse_bcorr is None
-                    and not (att('bit_alloc_act') and att('num_bits') <= 4) and self._one_gpu())
-        return True
+            return 'midtread_pc' if att('mtd_quant') else 'pc'
+        return 'minmax'
 
-    # The four channels_last routes.  Each wants a dense channels_last tensor (_dense_nhwc) on the per-channel activation branch and
-    # one GPU's own data (_one_gpu), and reads shape, strides and attributes only; att: the lookup of _att.  _nhwc_midtread and
-    # _nhwc_entropy are kept apart from _half_native, which goes on answering False for mtd_quant and measure_entropy: the tests
-    # of the earlier channels_last routes pin those answers, so __call__ asks all three before it upcasts.
-    def _nhwc_aciq(self, tensor, clip_type, att=None):
-        """gemmlowpClippingQuantize runs on the storage as it is (ops.aciq_qdq_nhwc): Laplace or Gaussian
-        clipping, no entropy measurement, no bias correction to fold in."""
-        att = att or (lambda k: getattr(self, k))
-        return (bool(att('pcq_a')) and _is_pc_act(tensor) and clip_type in ('laplace', 'gaus') and _dense_nhwc(tensor)
-                and not att('measure_entropy') and self.fuse_bcorr is None and self._one_gpu())
+    def _route(self, branch, tensor, stat_id, att):
+        """Level 2 of the branch __call__ takes."""
+        if branch == 'clip':
+            return self._clip_route(tensor, att('clipping'), stat_id, att)
+        if branch == 'pc':
+            return self._pc_route(tensor, stat_id, att)
+        if branch in ('midtread', 'midtread_pc'):
+            return self._midtread_route(tensor, att)
+        if branch == 'kld':
+            return self._kld_route(tensor)
+        return 'minmax_pt' if branch == 'minmax' else None          # config 1 has half and channels_last kernels; weights: none
 
-    def _nhwc_bcorr(self, tensor, clip_type, stat_id, att=None):
-        """The per-channel activation branches (min/max, Laplace or Gaussian clipping) fold a pending bias correction in on the
-        storage as it is (ops.qdq_bias_corrected_nhwc): calibrated statistics (stat_id: the product requests
-        the correction only under -sm use, so only the table-driven form exists; without it False), a pending fuse_bcorr, no
-        entropy measurement."""
-        att = att or (lambda k: getattr(self, k))
-        return (stat_id is not None and self.fuse_bcorr is not None and bool(att('pcq_a')) and _is_pc_act(tensor)
-                and clip_type in ('no', 'laplace', 'gaus') and not (clip_type == 'no' and att('pcq_w')) and _dense_nhwc(tensor)
-                and not att('mtd_quant') and not att('kld') and not att('measure_entropy') and self._one_gpu())
+    def _facts(self, tensor, att):
+        """What the routes of a branch share, computed once: whether the per-channel activation code applies, one GPU's own data,
+        bit allocation in effect, a bias correction pending.  (The storage class, _storage, comes after them: it costs the most.)"""
+        return (bool(att('pcq_a')) and _is_pc_act(tensor), self._one_gpu(), bool(att('bit_alloc_act')) and att('num_bits') <= 4,
+                self.fuse_bcorr is not None)
 
-    def _nhwc_midtread(self, tensor, att=None):
-        """mid_tread_quantize_activation_per_channel runs on the storage as it is (ops.mid_tread_qdq_nhwc):
-        mid-tread quantization with clipping, no KLD, no bias correction to fold in; the entropy measurement may be on or off."""
-        get = att or self._att()
-        return (bool(get('mtd_quant')) and get('clipping') != 'no' and not get('kld')
-                and bool(get('pcq_a')) and _is_pc_act(tensor) and _dense_nhwc(tensor)
-                and self.fuse_bcorr is None and self._one_gpu())
-
-    def _nhwc_entropy(self, tensor, att=None):
-        """gemmlowpQuantizeActivationPerChannel measures the entropy of its codes on the storage as it is (ops.act_qdq_per_channel's
-        counting route): measure_entropy without clipping - no KLD, no weight branch in front of it, no
-        mid-tread, no bit allocation in effect, codes that fit a byte - and no bias correction pending (with -me the layer
-        corrects afterwards); dynamic or with stat_id.  Config 3 with -me is one predicate away (ops.aciq_qdq_nhwc takes
-        want_entropy) and stays on the copy route, as its tests pin it."""
-        get = att or self._att()
-        return (bool(get('measure_entropy')) and bool(get('pcq_a')) and _is_pc_act(tensor)
-                and get('clipping') == 'no' and not get('pcq_w') and not get('mtd_quant') and not get('kld')
-                and not (get('bit_alloc_act') and get('num_bits') <= 4) and get('num_bits') <= 8 and _dense_nhwc(tensor)
-                and self.fuse_bcorr is None and self._one_gpu())
-
-    # The three per-tensor routes over flat storage (DESIGN.md section 22).  One parameter set serves the whole tensor, so the element
-    # order does not matter: a contiguous bf16 / fp16 tensor and a dense channels_last tensor of any of the three dtypes are
-    # quantized where they lie.  A contiguous fp32 tensor keeps ops.act_qdq_per_channel(whole_tensor=True) / ops.mid_tread_qdq: its
-    # dynamic statistics differ from the flat rows' in the last bits.  Kept apart from _half_native for the reason above: tests pin it.
     def _flat_tensor(self, tensor):
-        """On the device and either bf16 / fp16, contiguous or dense channels_last, or fp32 dense channels_last; not empty."""
+        """What the per-tensor routes over flat storage take: on the device and either bf16 / fp16, contiguous
+        or dense channels_last, or fp32 dense channels_last; not empty."""
         if not getattr(tensor, 'is_cuda', False) or tensor.numel() == 0:
             return False
         if tensor.dtype in HALF_DTYPES:
             return tensor.is_contiguous() or _dense_nhwc(tensor)
         return tensor.dtype == torch.float32 and _dense_nhwc(tensor)
 
-    def _flat_clip(self, tensor, att=None):
-        """The per-tensor tail of gemmlowpClippingQuantize runs on ops.clip_qdq_tensor: the clipping branch where -pcq_a does not
-        apply, 'laplace', 'gaus' or '<p>std' (not 'mix': its candidates come from error columns), no mid-tread, no KLD, one GPU."""
+    def _kld_route(self, tensor):
+        """gemmlowpKldQuantize: __gemmlowpQuantize__ hands a half tensor, contiguous or dense channels_last, to ops.pt_qdq's half
+        kernel as it is.  The name routes nothing; it keeps __call__ from upcasting."""
+        return 'kld' if (getattr(tensor, 'is_cuda', False) and tensor.dtype in HALF_DTYPES
+                         and (tensor.is_contiguous() or _dense_nhwc(tensor))) else None
+
+    def _clip_route(self, tensor, clip_type, stat_id, att):
+        """gemmlowpClippingQuantize.  Per channel, Laplace or Gaussian clipping without -me: a pending correction folded in on
+        channels_last, the calibration table on a contiguous half tensor (both need stat_id), ACIQ on channels_last, dynamic ACIQ
+        on a contiguous half tensor (opt-in: half_dynamic).  Per tensor, also '<p>std': the flat route.  'mix' has none."""
+        pc, one_gpu, use_ba, pending = self._facts(tensor, att)
+        if not one_gpu:
+            return None
+        # a mid-tread or KLD object comes here by a direct call only, and only channels_last ACIQ serves it
+        direct = att('mtd_quant') or att('kld')
+        if not pc:
+            clips = clip_type in ('laplace', 'gaus') or (isinstance(clip_type, str) and clip_type.endswith('std'))
+            return 'flat_clip' if clips and not direct and self._flat_tensor(tensor) else None
+        if clip_type not in ('laplace', 'gaus') or att('measure_entropy'):
+            return None
+        storage = _storage(tensor)
+        if stat_id is not None and not direct:
+            if pending and storage == 'nhwc':
+                return 'nhwc_bcorr'
+            if storage == 'half' and ops._HALF_TABLE and ops._table_half_native(*ops.geometry(tensor), tensor.dtype) != 0:
+                return 'half_table'
+        if pending:
+            return None
+        if storage == 'nhwc':
+            return 'nhwc_aciq'
+        if (storage == 'half' and stat_id is None and self.half_dynamic and not direct and ops._HALF_ACIQ
+                and ops._aciq_half_native(*ops.geometry(tensor), tensor.dtype, use_ba,
+                                          use_ba and att('bit_alloc_prior') != 'gaus') != 0):
+            return 'half_aciq'
+        return None
+
+    def _pc_route(self, tensor, stat_id, att):
+        """gemmlowpQuantizeActivationPerChannel.  From the calibration table (stat_id) without -me: a pending correction folded in
+        on channels_last; on a contiguous half tensor the table route under bit allocation or a pending correction, else
+        'half_minmax' (ops.act_qdq_per_channel's own half route).  Then -me on channels_last byte codes, and config 2's kernels."""
+        pc, one_gpu, use_ba, pending = self._facts(tensor, att)
+        if not (pc and one_gpu) or att('mtd_quant') or att('kld') or att('pcq_w'):          # (by a direct call only)
+            return None
+        entropy = att('measure_entropy')
+        if stat_id is not None and not entropy:
+            storage = _storage(tensor)
+            if pending and storage == 'nhwc':
+                return 'nhwc_bcorr'
+            if storage == 'half' and ops._HALF_TABLE and ops._table_half_native(*ops.geometry(tensor), tensor.dtype) != 0:
+                return 'half_table' if use_ba or pending else 'half_minmax'
+        if use_ba or pending:
+            return None
+        if entropy:
+            return 'nhwc_entropy' if att('num_bits') <= 8 and _dense_nhwc(tensor) else None
+        return 'minmax_pc'
+
+    def _midtread_route(self, tensor, att):
+        """The two mid_tread_quantize_activation methods: with clipping (the per-channel one is also __call__'s branch at clipping
+        'no', which has no route) and no KLD, per channel on channels_last with no correction pending, per tensor on flat storage."""
+        pc, one_gpu, _, pending = self._facts(tensor, att)
+        if not (att('mtd_quant') and one_gpu) or att('clipping') == 'no' or att('kld'):
+            return None
+        if pc:
+            return 'nhwc_midtread' if not pending and _dense_nhwc(tensor) else None
+        return 'flat_midtread' if self._flat_tensor(tensor) else None
+
+    # The predicates of the routes, as tests, tools and DESIGN.md know them: each is a view of the decision above.  _asked is the route
+    # __call__ would decide; _nhwc_aciq alone asks level 2 only, so it ignores mtd_quant and kld as gemmlowpClippingQuantize does.
+    def _asked(self, tensor, stat_id=None, att=None, clip_type=None):
+        """The route of __call__(tensor, stat_id=stat_id) under the lookup att, with clip_type (if given) as the clipping."""
         get = att or self._att()
-        clip = get('clipping')
-        return (not get('kld') and not get('mtd_quant') and not (get('pcq_a') and _is_pc_act(tensor))
-                and (clip in ('laplace', 'gaus') or (isinstance(clip, str) and clip.endswith('std')))
-                and self._one_gpu() and self._flat_tensor(tensor))
+        att = get if clip_type is None else lambda k: clip_type if k == 'clipping' else get(k)
+        return self._route(self._branch(att, tensor), tensor, stat_id, att)
+
+    def _half_native(self, tensor, override_att=None, stat_id=None):
+        return self._asked(tensor, stat_id, self._att(override_att)) in HALF_NATIVE_ROUTES
+
+    def _nhwc_aciq(self, tensor, clip_type, att=None):
+        return self._clip_route(tensor, clip_type, None, att or self._att()) == 'nhwc_aciq'
+
+    def _nhwc_bcorr(self, tensor, clip_type, stat_id, att=None):
+        return self._asked(tensor, stat_id, att, clip_type) == 'nhwc_bcorr'
+
+    def _nhwc_midtread(self, tensor, att=None):
+        return self._asked(tensor, None, att) == 'nhwc_midtread'
+
+    def _nhwc_entropy(self, tensor, att=None):
+        return self._asked(tensor, None, att) == 'nhwc_entropy'
+
+    def _flat_clip(self, tensor, att=None):
+        return self._asked(tensor, None, att) == 'flat_clip'
 
     def _flat_midtread(self, tensor, att=None):
-        """mid_tread_quantize_activation without -pcq_a runs on ops.mid_tread_qdq_tensor."""
-        get = att or self._att()
-        return (not get('kld') and bool(get('mtd_quant')) and get('clipping') != 'no' and not (get('pcq_a') and _is_pc_act(tensor))
-                and self._one_gpu() and self._flat_tensor(tensor))
+        return self._asked(tensor, None, att) == 'flat_midtread'
 
     def _flat_kld(self, tensor, att=None):
-        """gemmlowpKldQuantize needs no upcast: __gemmlowpQuantize__ hands a half tensor, contiguous or dense channels_last, to
-        ops.pt_qdq's half kernel as it is.  Nothing is routed by this: it only keeps __call__ from upcasting."""
-        get = att or self._att()
-        return (bool(get('kld')) and getattr(tensor, 'is_cuda', False) and tensor.dtype in HALF_DTYPES
-                and (tensor.is_contiguous() or _dense_nhwc(tensor)))
+        return self._asked(tensor, None, att) == 'kld'
 
     def _half_table(self, tensor, clip_type, stat_id, att=None):
-        """The per-channel activation branches quantize a contiguous bf16 / fp16 tensor from the calibration table where it lies
-        (DESIGN.md section 24): stat_id given (everything dynamic keeps its route), min/max, Laplace or Gaussian clipping, with or
-        without bit allocation and a pending bias correction (ops.qdq_bias_corrected_half, else ops.pc_qdq), no mid-tread, KLD or
-        entropy measurement, one GPU's own data, the switch CNNQ_HALF_TABLE on and a class of layer the route function keeps
-        native.  Kept apart from _half_native, whose answers are pinned by tests; shape, strides and attributes only."""
-        att = att or (lambda k: getattr(self, k))
-        if not (stat_id is not None and getattr(tensor, 'is_cuda', False) and tensor.dtype in HALF_DTYPES and tensor.dim() == 4
-                and tensor.is_contiguous() and tensor.numel() > 0):
-            return False
-        if not (bool(att('pcq_a')) and _is_pc_act(tensor) and clip_type in ('no', 'laplace', 'gaus')
-                and not (clip_type == 'no' and att('pcq_w')) and not att('mtd_quant') and not att('kld')
-                and not att('measure_entropy') and self._one_gpu() and ops._HALF_TABLE):
-            return False
-        N, C, HW = ops.geometry(tensor)
-        return ops._table_half_native(N, C, HW, tensor.dtype) != 0
+        return self._asked(tensor, stat_id, att, clip_type) in ('half_table', 'half_minmax')
 
     def _half_aciq(self, tensor, clip_type, stat_id, att=None):
-        """gemmlowpClippingQuantize quantizes a contiguous bf16 / fp16 tensor with DYNAMIC statistics where it lies
-        (ops.aciq_qdq_half): half_dynamic set on this object, no stat_id (calibrated statistics are
-        _half_table's), Laplace or Gaussian clipping with or without bit allocation, no mid-tread, KLD or entropy measurement, no
-        bias correction to fold in, one GPU's own data, the switch CNNQ_HALF_ACIQ on and a class of layer the route function keeps
-        native.  Kept apart from _half_native, whose answers are pinned by tests; shape, strides and attributes only."""
-        att = att or (lambda k: getattr(self, k))
-        if not (self.half_dynamic and stat_id is None and getattr(tensor, 'is_cuda', False) and tensor.dtype in HALF_DTYPES
-                and tensor.dim() == 4 and tensor.is_contiguous() and tensor.numel() > 0):
-            return False
-        if not (bool(att('pcq_a')) and _is_pc_act(tensor) and clip_type in ('laplace', 'gaus') and not att('mtd_quant')
-                and not att('kld') and not att('measure_entropy') and self.fuse_bcorr is None and self._one_gpu()
-                and ops._HALF_ACIQ):
-            return False
-        N, C, HW = ops.geometry(tensor)
-        use_ba = bool(att('bit_alloc_act')) and att('num_bits') <= 4
-        return ops._aciq_half_native(N, C, HW, tensor.dtype, use_ba, use_ba and att('bit_alloc_prior') != 'gaus') != 0
-
-    def _table_half(self, tensor, table, clip_type, prior_b):
-        """The _half_table route: the parameters of the calibration table, then Q/DQ - with a pending correction folded in - where
-        the tensor lies."""
-        use_ba = bool(self.bit_alloc_act) and self.num_bits <= 4
-        qp, _ = ops.pc_params(table, self.num_bits, self._positive, clip_type, use_ba, prior_b, self.bit_alloc_target_act,
-                              self.bit_alloc_round)
-        if self.fuse_bcorr is not None:
-            return ops.qdq_bias_corrected_half(tensor, qp, bool(self._take_bcorr()))
-        N, C, HW = ops.geometry(tensor)
-        return ops.pc_qdq(tensor, N, C, HW, qp)
-
-    def _bcorr_nhwc(self, tensor, table, clip_type, prior_b):
-        """The _nhwc_bcorr route: the parameters of the calibration table, then Q/DQ and correction where the tensor lies."""
-        use_ba = bool(self.bit_alloc_act) and self.num_bits <= 4
-        qp, _ = ops.pc_params(table, self.num_bits, self._positive, clip_type, use_ba, prior_b, self.bit_alloc_target_act,
-                              self.bit_alloc_round)
-        return ops.qdq_bias_corrected_nhwc(tensor, qp, bool(self._take_bcorr()))
+        return self._asked(tensor, stat_id, att, clip_type) == 'half_aciq'
 
     def __repr__(self):
         # iq.py:124-126, printed by the manager in verbose mode
@@ -319,6 +309,31 @@ class IntQuantizer:
             tab = host.to(device)
             self._table_cache[key] = tab
         return tab
+
+    def _table_params(self, table, clip_type):
+        """The quantization parameters of the calibration table."""
+        return ops.pc_params(table, self.num_bits, self._positive, clip_type, bool(self.bit_alloc_act) and self.num_bits <= 4,
+                             self.bit_alloc_prior != 'gaus', self.bit_alloc_target_act, self.bit_alloc_round)[0]
+
+    def _table_half(self, tensor, table, clip_type):
+        """The 'half_table' route: Q/DQ from the table's parameters - with a pending correction folded in - where the tensor lies."""
+        qp = self._table_params(table, clip_type)
+        if self.fuse_bcorr is not None:
+            return ops.qdq_bias_corrected_half(tensor, qp, bool(self._take_bcorr()))
+        return ops.pc_qdq(tensor, *ops.geometry(tensor), qp)
+
+    def _act_qdq(self, tensor, id, clip_type, table):
+        """ops.act_qdq_per_channel on a per-channel activation - dynamic statistics or `table`, a pending correction folded in -
+        with the entropy of its codes logged where it is measured."""
+        out = ops.act_qdq_per_channel(tensor, self.num_bits, positive=self._positive, clip=clip_type,
+                                      bit_alloc=self.bit_alloc_act, prior_is_b=self.bit_alloc_prior != 'gaus',
+                                      target=self.bit_alloc_target_act, round_mode=self.bit_alloc_round,
+                                      group=self.group, stats=table, want_entropy=self.measure_entropy,
+                                      bcorr=self._take_bcorr())
+        if self.measure_entropy:
+            out, entropy = out
+            self._log_entropy(id, entropy, 'avg.entropy.act', out.numel())
+        return out.view(tensor.shape)
 
     def _take_bcorr(self):
         """The pending bias-correction request, if this call can fold it in (no entropy measurement)."""
@@ -346,78 +361,48 @@ class IntQuantizer:
         if min_ is not None or max_ is not None:
             raise NotImplementedError('explicit min_/max_ are an internal hand-off of the reference '
                                       '(iq.py:352); use gemmlowpClippingQuantize')
-        prior_b = self.bit_alloc_prior != 'gaus'
-        use_ba = bool(self.bit_alloc_act) and self.num_bits <= 4
-        table = None
-        if stat_id is not None:
-            C = tensor.shape[1]
+        route = table = None
+        if stat_id is not None:                                   # (the routes that change the call need the table)
+            route = self._pc_route(tensor, stat_id, self._att())
+            prior_b = self.bit_alloc_prior != 'gaus'
             rows = {L.STAT_MAX: ('max', self.stats_kind)}
             if not self._positive:
                 rows[L.STAT_MIN] = ('min', self.stats_kind)
-            if use_ba:
+            if bool(self.bit_alloc_act) and self.num_bits <= 4:
                 rows[L.STAT_B if prior_b else L.STAT_STD] = ('b' if prior_b else 'std', 'mean')
-            table = self._stats_table(stat_id, C, tensor.device, rows)
-            if self._nhwc_bcorr(tensor, 'no', stat_id):
-                return self._bcorr_nhwc(tensor, table, 'no', prior_b)
-            if (use_ba or self.fuse_bcorr is not None) and self._half_table(tensor, 'no', stat_id):
-                # (plain min/max from the table without a correction: act_qdq_per_channel's own half route below)
-                return self._table_half(tensor, table, 'no', prior_b)
-        out = ops.act_qdq_per_channel(tensor, self.num_bits, positive=self._positive, clip='no',
-                                      bit_alloc=self.bit_alloc_act, prior_is_b=prior_b,
-                                      target=self.bit_alloc_target_act, round_mode=self.bit_alloc_round,
-                                      group=self.group, stats=table, want_entropy=self.measure_entropy,
-                                      bcorr=self._take_bcorr())
-        if self.measure_entropy:
-            out, entropy = out
-            self._log_entropy(id, entropy, 'avg.entropy.act', out.numel())
-        return out.view(tensor.shape)
+            table = self._stats_table(stat_id, tensor.shape[1], tensor.device, rows)
+        if route == 'nhwc_bcorr':
+            return ops.qdq_bias_corrected_nhwc(tensor, self._table_params(table, 'no'), bool(self._take_bcorr()))
+        if route == 'half_table':
+            return self._table_half(tensor, table, 'no')
+        return self._act_qdq(tensor, id, 'no', table)            # 'half_minmax', 'nhwc_entropy', 'minmax_pc': its own routes
 
     def gemmlowpClippingQuantize(self, tensor, id, tag="", stat_id=None, clip_type='laplace'):
         """iq.py:327-359: ACIQ clipping (laplace / gaus / <p>std), per channel when -pcq_a applies,
         otherwise per tensor with scalar statistics."""
-        prior_b = self.bit_alloc_prior != 'gaus'
         if clip_type == 'mix':
-            return self._clipping_mix(tensor, id, stat_id, prior_b)
-        if self.pcq_a and _is_pc_act(tensor):
-            table = None
-            if stat_id is not None:
-                C = tensor.shape[1]
-                rows = {L.STAT_MIN: ('min', 'mean'), L.STAT_MAX: ('max', 'mean'), L.STAT_MEAN: ('mean', 'mean'),
-                        L.STAT_B: ('b', 'mean'), L.STAT_STD: ('std', 'mean')}
-                table = self._stats_table(stat_id, C, tensor.device, rows)
-                if self._nhwc_bcorr(tensor, clip_type, stat_id):
-                    return self._bcorr_nhwc(tensor, table, clip_type, prior_b)
-                if self._half_table(tensor, clip_type, stat_id):
-                    return self._table_half(tensor, table, clip_type, prior_b)
-            if self._nhwc_aciq(tensor, clip_type):
-                # a dense channels_last activation: quantized where it lies, the result keeps layout and dtype
-                return ops.aciq_qdq_nhwc(tensor, self.num_bits, positive=self._positive, clip=clip_type,
-                                         bit_alloc=self.bit_alloc_act, prior_is_b=prior_b, target=self.bit_alloc_target_act,
-                                         round_mode=self.bit_alloc_round, stats=table)
-            if self._half_aciq(tensor, clip_type, stat_id):
-                # a contiguous bf16 / fp16 activation, dynamic statistics: quantized where it lies, the result keeps the dtype
-                return ops.aciq_qdq_half(tensor, self.num_bits, positive=self._positive, clip=clip_type,
-                                         bit_alloc=self.bit_alloc_act, prior_is_b=prior_b, target=self.bit_alloc_target_act,
-                                         round_mode=self.bit_alloc_round)
-            out = ops.act_qdq_per_channel(tensor, self.num_bits, positive=self._positive, clip=clip_type,
-                                          bit_alloc=self.bit_alloc_act, prior_is_b=prior_b,
-                                          target=self.bit_alloc_target_act, round_mode=self.bit_alloc_round,
-                                          group=self.group, stats=table, want_entropy=self.measure_entropy,
-                                          bcorr=self._take_bcorr())
-            if self.measure_entropy:
-                out, entropy = out
-                self._log_entropy(id, entropy, 'avg.entropy.act', out.numel())
-            return out.view(tensor.shape)
-        # per-tensor branch (iq.py:353-357): the whole tensor is ONE channel; bit allocation does not
-        # apply (iq.py:236 requires per_channel) and delta is the range itself
-        table = None
-        if stat_id is not None:
-            rows = {L.STAT_MIN: ('min', 'mean'), L.STAT_MAX: ('max', 'mean'), L.STAT_MEAN: ('mean', 'mean'),
-                    L.STAT_B: ('b', 'mean'), L.STAT_STD: ('std', 'mean')}
-            table = self._stats_table(stat_id, 1, tensor.device, rows)
-        if self._flat_clip(tensor, self._att(('clipping', clip_type))):
+            return self._clipping_mix(tensor, id, stat_id, self.bit_alloc_prior != 'gaus')
+        route = self._clip_route(tensor, clip_type, stat_id, self._att())
+        # per tensor (iq.py:353-357) the whole tensor is ONE channel; bit allocation does not apply (iq.py:236 requires per_channel)
+        # and delta is the range itself
+        pc = route != 'flat_clip' and (route is not None or (self.pcq_a and _is_pc_act(tensor)))    # (every other route is per channel)
+        table = None if stat_id is None else self._stats_table(stat_id, tensor.shape[1] if pc else 1, tensor.device, ACIQ_ROWS)
+        if route == 'nhwc_bcorr':
+            return ops.qdq_bias_corrected_nhwc(tensor, self._table_params(table, clip_type), bool(self._take_bcorr()))
+        if route == 'half_table':
+            return self._table_half(tensor, table, clip_type)
+        if route in ('nhwc_aciq', 'half_aciq'):
+            # a dense channels_last activation, or a contiguous bf16 / fp16 one with dynamic statistics: quantized where it lies
+            kw = dict(positive=self._positive, clip=clip_type, bit_alloc=self.bit_alloc_act, prior_is_b=self.bit_alloc_prior != 'gaus',
+                      target=self.bit_alloc_target_act, round_mode=self.bit_alloc_round)
+            if route == 'half_aciq':
+                return ops.aciq_qdq_half(tensor, self.num_bits, **kw)
+            return ops.aciq_qdq_nhwc(tensor, self.num_bits, stats=table, **kw)
+        if route == 'flat_clip':
             # half or dense channels_last: quantized where it lies, the result keeps dtype and layout
             return ops.clip_qdq_tensor(tensor, self.num_bits, positive=self._positive, clip=clip_type, stats=table)
+        if pc:
+            return self._act_qdq(tensor, id, clip_type, table)
         out = ops.act_qdq_per_channel(tensor, self.num_bits, positive=self._positive, clip=clip_type,
                                       bit_alloc=False, group=self.group, stats=table, whole_tensor=True)
         return out.view(tensor.shape)
@@ -431,9 +416,7 @@ class IntQuantizer:
             raise ValueError("clipping 'mix' needs a statistics file (-sm use): int_quantizer.py:311-313 reads mse_* by stat_id")
         pc = self.pcq_a and _is_pc_act(tensor)
         C = tensor.shape[1] if pc else 1
-        rows = {L.STAT_MIN: ('min', 'mean'), L.STAT_MAX: ('max', 'mean'), L.STAT_MEAN: ('mean', 'mean'),
-                L.STAT_B: ('b', 'mean'), L.STAT_STD: ('std', 'mean')}
-        table = self._stats_table(stat_id, C, tensor.device, rows)
+        table = self._stats_table(stat_id, C, tensor.device, ACIQ_ROWS)
         mse = torch.full((3, C), float('nan'), dtype=torch.float32)
         for r, name in enumerate(('mse_laplace', 'mse_gaus', 'mse_lowp')):
             try:
@@ -524,7 +507,7 @@ class IntQuantizer:
         """iq.py:158-168."""
         if self.pcq_a and _is_pc_act(tensor):
             return self.mid_tread_quantize_activation_per_channel(tensor, id)
-        if self._flat_midtread(tensor):
+        if self._midtread_route(tensor, self._att()) == 'flat_midtread':
             return ops.mid_tread_qdq_tensor(tensor, self.bit_alloc_target_act, sym=not self._positive)
         out, _ = ops.mid_tread_qdq(tensor, self.bit_alloc_target_act, clip=True, sym=not self._positive,
                                    whole_tensor=True, group=self.group, want_entropy=self.measure_entropy)
@@ -532,7 +515,7 @@ class IntQuantizer:
 
     def mid_tread_quantize_activation_per_channel(self, tensor, id):
         """iq.py:170-183."""
-        if self._nhwc_midtread(tensor):
+        if self._midtread_route(tensor, self._att()) == 'nhwc_midtread':
             # a dense channels_last activation: quantized where it lies, the result keeps layout and dtype
             out, entropy = ops.mid_tread_qdq_nhwc(tensor, self.bit_alloc_target_act, sym=not self._positive,
                                                   want_entropy=self.measure_entropy)
@@ -542,6 +525,18 @@ class IntQuantizer:
             out = out.view(tensor.shape)
         self._log_entropy(id, entropy, 'avg.entropy.act', tensor.numel())
         return out
+
+
+# how iq.py:92-122 calls the branch method of each of _branch's answers
+BRANCH_CALLS = {
+    'kld': lambda q, t, id, tag, stat_id: q.gemmlowpKldQuantize(t, tag, stat_id=stat_id),
+    'midtread': lambda q, t, id, tag, stat_id: q.mid_tread_quantize_activation(t, id),
+    'clip': lambda q, t, id, tag, stat_id: q.gemmlowpClippingQuantize(t, id, tag, stat_id=stat_id, clip_type=q.clipping),
+    'midtread_w': lambda q, t, id, tag, stat_id: q.mid_tread_quantize_weights_per_channel(t, id),
+    'weights': lambda q, t, id, tag, stat_id: q.gemmlowpQuantizeWeightsPerChannel(t, id),
+    'midtread_pc': lambda q, t, id, tag, stat_id: q.mid_tread_quantize_activation_per_channel(t, id),
+    'pc': lambda q, t, id, tag, stat_id: q.gemmlowpQuantizeActivationPerChannel(t, id, tag, stat_id=stat_id),
+    'minmax': lambda q, t, id, tag, stat_id: q.gemmlowpMinMaxQuantize(t, tag, stat_id=stat_id)}
 
 
 def int_quantizer(qtype, quant_params):

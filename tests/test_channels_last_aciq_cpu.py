@@ -7,6 +7,7 @@ import ctypes
 import pytest
 import torch
 
+import _quantizer as Q
 from test_channels_last_cpu import BAD, EINVAL, CHANNELS, cl, ctype_of, header_decls
 
 ACIQ_FUNCS = ['cnnq_pc_aciq_nhwc_workspace', 'cnnq_pc_route_aciq_nhwc', 'cnnq_pc_aciq_qdq_nhwc']
@@ -111,12 +112,7 @@ def test_every_geometry_has_a_route_and_its_slabs_cover_the_rows(dtype, align):
 
 
 def quantizer(**kw):
-    from cnn_quantization_amd.qtypes.int_quantizer import IntQuantizer
-    params = dict(clipping='laplace', pcq_weights=False, pcq_act=True, bit_alloc_act=True, bit_alloc_weight=False, bcorr_act=False,
-                  bcorr_weight=False, vcorr_weight=False, bit_alloc_rmode='round', bit_alloc_prior='gaus',
-                  bit_alloc_target_act=None, bit_alloc_target_weight=None, measure_entropy=False, logger=None, mtd_quant=False)
-    params.update(kw)
-    return IntQuantizer(4, params)
+    return Q.quantizer(**dict(dict(clipping='laplace', pcq_act=True, bit_alloc_act=True), **kw))
 
 
 def test_dispatch_conditions_on_cpu_tensors():

@@ -14,6 +14,7 @@ import torch
 from hypothesis import HealthCheck, given, settings
 from hypothesis import strategies as st
 
+import _quantizer as Q
 from _direct import aciq_on_table
 from test_channels_last_gpu import DTYPES, IDS, cl, is_cl, same, values
 
@@ -154,12 +155,7 @@ def test_other_clippings_raise():
 
 
 def quantizer(**kw):
-    from cnn_quantization_amd.qtypes.int_quantizer import IntQuantizer
-    params = dict(clipping='laplace', pcq_weights=False, pcq_act=True, bit_alloc_act=True, bit_alloc_weight=False, bcorr_act=False,
-                  bcorr_weight=False, vcorr_weight=False, bit_alloc_rmode='round', bit_alloc_prior='gaus',
-                  bit_alloc_target_act=None, bit_alloc_target_weight=None, measure_entropy=False, logger=None, mtd_quant=False)
-    params.update(kw)
-    return IntQuantizer(4, params)
+    return Q.quantizer(**dict(dict(clipping='laplace', pcq_act=True, bit_alloc_act=True), **kw))
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=IDS)

@@ -7,6 +7,7 @@ import ctypes
 import pytest
 import torch
 
+import _quantizer as Q
 from test_channels_last_cpu import BAD, EINVAL, CHANNELS, cl, ctype_of, header_decls
 
 BCORR_FUNCS = ['cnnq_pc_qdq_bcorr_nhwc_workspace', 'cnnq_pc_qdq_bcorr_nhwc']
@@ -72,12 +73,7 @@ def test_workspace_holds_the_records_of_every_piece_width(dtype):
 
 
 def quantizer(**kw):
-    from cnn_quantization_amd.qtypes.int_quantizer import IntQuantizer
-    params = dict(clipping='laplace', pcq_weights=False, pcq_act=True, bit_alloc_act=True, bit_alloc_weight=False, bcorr_act=True,
-                  bcorr_weight=False, vcorr_weight=False, bit_alloc_rmode='round', bit_alloc_prior='gaus',
-                  bit_alloc_target_act=None, bit_alloc_target_weight=None, measure_entropy=False, logger=None, mtd_quant=False)
-    params.update(kw)
-    return IntQuantizer(4, params)
+    return Q.quantizer(**dict(dict(clipping='laplace', pcq_act=True, bit_alloc_act=True, bcorr_act=True), **kw))
 
 
 def nhwc_bf16():

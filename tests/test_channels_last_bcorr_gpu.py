@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import _quantizer as Q
 from oracle import quant_oracle as O
 from test_channels_last_gpu import DTYPES, IDS, cl, is_cl, same, values
 
@@ -325,12 +326,7 @@ def test_ab_switch_and_nchw_take_the_existing_op(monkeypatch, dtype):
 
 
 def quantizer(**kw):
-    from cnn_quantization_amd.qtypes.int_quantizer import IntQuantizer
-    params_ = dict(clipping='laplace', pcq_weights=False, pcq_act=True, bit_alloc_act=True, bit_alloc_weight=False, bcorr_act=True,
-                   bcorr_weight=False, vcorr_weight=False, bit_alloc_rmode='round', bit_alloc_prior='gaus',
-                   bit_alloc_target_act=None, bit_alloc_target_weight=None, measure_entropy=False, logger=None, mtd_quant=False)
-    params_.update(kw)
-    return IntQuantizer(4, params_)
+    return Q.quantizer(**dict(dict(clipping='laplace', pcq_act=True, bit_alloc_act=True, bcorr_act=True), **kw))
 
 
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32], ids=['bf16', 'f32'])

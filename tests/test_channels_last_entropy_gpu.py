@@ -14,6 +14,7 @@ import importlib
 import pytest
 import torch
 
+import _quantizer as Q
 from test_channels_last_aciq_gpu import check_table
 from test_channels_last_gpu import DTYPES, IDS, cl, is_cl, same, values
 
@@ -393,12 +394,7 @@ class Logger:
 
 
 def quantizer(**kw):
-    from cnn_quantization_amd.qtypes.int_quantizer import IntQuantizer
-    params = dict(clipping='no', pcq_weights=False, pcq_act=True, bit_alloc_act=False, bit_alloc_weight=False, bcorr_act=False,
-                  bcorr_weight=False, vcorr_weight=False, bit_alloc_rmode='round', bit_alloc_prior='gaus',
-                  bit_alloc_target_act=None, bit_alloc_target_weight=None, measure_entropy=True, logger=None, mtd_quant=False)
-    params.update(kw)
-    return IntQuantizer(4, params)
+    return Q.quantizer(**dict(dict(pcq_act=True, measure_entropy=True), **kw))
 
 
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32], ids=['bf16', 'f32'])

@@ -8,6 +8,7 @@ import os
 import pytest
 import torch
 
+import _quantizer as Q
 from test_channels_last_cpu import BAD, EINVAL, CHANNELS, cl, ctype_of, header_decls
 
 MT_FUNCS = ['cnnq_pc_route_midtread_nhwc', 'cnnq_pc_midtread_qdq_nhwc', 'cnnq_pc_midtread_nhwc']
@@ -119,12 +120,7 @@ def test_plan_is_config_3s_for_the_statistics_and_the_workspace_covers_it(dtype,
 
 
 def quantizer(**kw):
-    from cnn_quantization_amd.qtypes.int_quantizer import IntQuantizer
-    params = dict(clipping='laplace', pcq_weights=False, pcq_act=True, bit_alloc_act=True, bit_alloc_weight=False, bcorr_act=False,
-                  bcorr_weight=False, vcorr_weight=False, bit_alloc_rmode='round', bit_alloc_prior='gaus',
-                  bit_alloc_target_act=5.3, bit_alloc_target_weight=None, measure_entropy=True, logger=None, mtd_quant=True)
-    params.update(kw)
-    return IntQuantizer(4, params)
+    return Q.quantizer(**dict(dict(clipping='laplace', pcq_act=True, bit_alloc_act=True, bit_alloc_target_act=5.3, measure_entropy=True, mtd_quant=True), **kw))
 
 
 def nhwc_bf16():

@@ -18,6 +18,7 @@ import torch
 from hypothesis import HealthCheck, assume, given, settings
 from hypothesis import strategies as st
 
+import _quantizer as Q
 from test_channels_last_aciq_gpu import WIDTH_CASES, check_table
 from test_channels_last_gpu import DTYPES, IDS, cl, is_cl, same, values
 
@@ -378,12 +379,7 @@ class Logger:
 
 
 def quantizer(**kw):
-    from cnn_quantization_amd.qtypes.int_quantizer import IntQuantizer
-    params = dict(clipping='laplace', pcq_weights=False, pcq_act=True, bit_alloc_act=True, bit_alloc_weight=False, bcorr_act=False,
-                  bcorr_weight=False, vcorr_weight=False, bit_alloc_rmode='round', bit_alloc_prior='gaus',
-                  bit_alloc_target_act=5.3, bit_alloc_target_weight=None, measure_entropy=False, logger=None, mtd_quant=True)
-    params.update(kw)
-    return IntQuantizer(4, params)
+    return Q.quantizer(**dict(dict(clipping='laplace', pcq_act=True, bit_alloc_act=True, bit_alloc_target_act=5.3, mtd_quant=True), **kw))
 
 
 @pytest.mark.parametrize('me', [False, True], ids=['plain', 'me'])

@@ -9,8 +9,9 @@ import pytest
 import torch
 
 import _half_aciq as HA
+import _quantizer as Q
 from test_channels_last_collect_cpu import ctype_of, header_decls
-from test_half_collect_cpu import FakeCuda
+from _quantizer import FakeCuda, act
 
 FUNCS = ['cnnq_pc_aciq_dt_workspace', 'cnnq_pc_route_aciq_dt', 'cnnq_pc_aciq_qdq_dt']
 BAD = 0x1000   # a non-null pointer value that is never dereferenced: the argument checks come first
@@ -158,19 +159,10 @@ def test_float32_answers_the_chain():
 
 # ---- the quantizer's predicate
 def quantizer(half_dynamic=True, **kw):
-    from cnn_quantization_amd.qtypes.int_quantizer import IntQuantizer
-    params = dict(clipping='laplace', pcq_weights=False, pcq_act=True, bit_alloc_act=True, bit_alloc_weight=False, bcorr_act=False,
-                  bcorr_weight=False, vcorr_weight=False, bit_alloc_rmode='round', bit_alloc_prior='gaus',
-                  bit_alloc_target_act=None, bit_alloc_target_weight=None, measure_entropy=False, logger=None, mtd_quant=False)
-    params.update(kw)
-    q = IntQuantizer(4, params)
+    q = Q.quantizer(**dict(dict(clipping='laplace', pcq_act=True, bit_alloc_act=True), **kw))
     assert q.half_dynamic is False                          # opt-in: the constructor leaves it off
     q.half_dynamic = half_dynamic
     return q
-
-
-def act(dtype=torch.bfloat16, shape=(2, 8, 4, 4)):
-    return FakeCuda(torch.zeros(shape, dtype=dtype))
 
 
 def test_predicate_truth_table(monkeypatch):

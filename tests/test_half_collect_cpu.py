@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import _half_collect as HC
+from _quantizer import FakeCuda, act
 from test_channels_last_collect_cpu import ctype_of, header_decls
 
 FUNCS = ['cnnq_pc_stats_dt_workspace', 'cnnq_pc_route_stats_dt', 'cnnq_pc_stats_dt']
@@ -136,21 +137,6 @@ def test_float32_forwards_to_the_chain():
 class FakeManager:
     def __init__(self, batch_avg=False, collect_err=False, group=None):
         self.batch_avg, self.collect_err, self.group = batch_avg, collect_err, group
-
-
-class FakeCuda(torch.Tensor):
-    """A CPU tensor that says it lives on the device: the predicate reads shape, strides and attributes only."""
-    @staticmethod
-    def __new__(cls, t):
-        return torch.Tensor._make_subclass(cls, t)
-
-    @property
-    def is_cuda(self):
-        return True
-
-
-def act(dtype=torch.bfloat16, shape=(2, 8, 4, 4)):
-    return FakeCuda(torch.zeros(shape, dtype=dtype))
 
 
 def test_predicate_truth_table(monkeypatch):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import _quantizer as Q
 from test_channels_last_collect_cpu import BAD, EINVAL, ERANGE, ctype_of, header_decls, lib
 
 FUNCS = ['cnnq_flat_qdq', 'cnnq_flat_midtread_qdq', 'cnnq_pt_clip_workspace', 'cnnq_pt_clip_qdq', 'cnnq_pt_midtread']
@@ -156,23 +157,11 @@ def test_workspace_is_the_flat_row_statistics(dtype):
 
 
 # ---- the quantizer's predicates
-class OnDevice(torch.Tensor):
-    """A CPU tensor that says it is on the device: the predicates read shape, strides, dtype and this flag only."""
-    is_cuda = property(lambda self: True)
-
-
-def on_device(t):
-    return t.as_subclass(OnDevice)
+on_device = Q.FakeCuda
 
 
 def quantizer(**kw):
-    from cnn_quantization_amd.qtypes.int_quantizer import IntQuantizer
-    params = dict(clipping='laplace', pcq_weights=False, pcq_act=False, bit_alloc_act=False, bit_alloc_weight=False, bcorr_act=False,
-                  bcorr_weight=False, vcorr_weight=False, bit_alloc_rmode='round', bit_alloc_prior='gaus',
-                  bit_alloc_target_act=None, bit_alloc_target_weight=None, measure_entropy=False, logger=None, mtd_quant=False)
-    params.update(kw)
-    bits = params.pop('bits', 4)
-    return IntQuantizer(bits, params)
+    return Q.quantizer(**dict(dict(clipping='laplace'), **kw))
 
 
 def tensors():
