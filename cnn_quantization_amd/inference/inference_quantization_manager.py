@@ -34,8 +34,8 @@ from .. import ops
 from ..qtypes import DummyQuantizer, int_quantizer
 from ..qtypes.int_quantizer import upcast_fallback
 from ..utils.misc import Singleton
-from .statistic_manager import StatisticManager, collects_native_flat
-from .statistic_manager_perchannel import StatisticManagerPerChannel, collects_native_half, collects_native_nhwc
+from .statistic_manager import StatisticManager
+from .statistic_manager_perchannel import StatisticManagerPerChannel
 
 FUSED_RELU_ARCHS = ('alexnet', 'vgg16', 'vgg16_bn', 'inception_v3')
 
@@ -60,7 +60,7 @@ class MeasureStatistics:
 
     def save_measure(self, tensor, id):
         t = tensor.detach()
-        if t.is_cuda and t.dim() > 0 and t.numel() > 0 and (t.dtype in ops._HALF_DTYPES or (t.dtype == torch.float32 and ops._NHWC and ops._layout(t) == 'nhwc')):
+        if t.numel() > 0 and ops.row_sumsq_native(t):
             # bf16 / fp16 and dense channels_last outputs: ops.row_sumsq reads them where they lie
             d = ops.row_sumsq(t, t.shape[0]).cpu().numpy().astype(np.float64)
         else:
@@ -99,19 +99,12 @@ def _route(layer, out, out_id, tag, *, shifted=False, half_range=False, collect_
         if isinstance(qm.stats_manager, StatisticManagerPerChannel) and qm.stats_manager.collect_err:
             # the error columns measure the candidates of the quantizer that `-sm use` will run on this output
             kw.update(half_range=half_range, err_settings=qm.err_settings(out_id, '' if shifted else tag, half_range))
-        if isinstance(qm.stats_manager, StatisticManagerPerChannel) and collects_native_nhwc(qm.stats_manager, out, force_global):
-            # a dense channels_last output the manager reads where it lies, in its own dtype: nothing to upcast
-            qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, **kw)
-            return out
-        if isinstance(qm.stats_manager, StatisticManagerPerChannel) and collects_native_half(qm.stats_manager, out, force_global):
-            # a contiguous bf16 / fp16 output the manager reads in its own dtype: nothing to upcast
-            qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, **kw)
-            return out
-        if isinstance(qm.stats_manager, StatisticManager) and collects_native_flat(qm.stats_manager, out):
-            # a bf16 / fp16 or dense channels_last output the per-tensor manager reads where it lies: nothing to upcast
-            qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, **kw)
-            return out
-        upcast_fallback(qm.stats_manager.save_tensor_stats, out, tag if collect_tag is None else collect_tag, out_id, **kw)
+        route = qm.stats_manager.collect_route(out, force_global)
+        if route is not None:
+            # an output the manager reads where it lies, in its own dtype and layout: nothing to upcast, nothing to decide again
+            qm.stats_manager.save_tensor_stats(out, tag if collect_tag is None else collect_tag, out_id, route=route, **kw)
+        else:
+            upcast_fallback(qm.stats_manager.save_tensor_stats, out, tag if collect_tag is None else collect_tag, out_id, **kw)
         return out
     stat_id = out_id if qm.stats_mode is StatsMode.use_stats else None
     if shifted:

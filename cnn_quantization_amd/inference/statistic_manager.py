@@ -5,12 +5,12 @@ id).  Serves the per-tensor quantizers (pooling, classifier, linear) in `-sm use
 
 The scalar statistics of a batch are one pass of the device kernels over the tensor viewed as a
 single channel; a bf16 / fp16 tensor and a dense channels_last one are read where they lie, in their
-own dtype (collects_native_flat, ops.tensor_stats).  `kld_threshold=True` adds the `kld_th` column (statistic_manager.py:80-82: the
+own dtype (collect_route answers 'flat': ops.tensor_stats).  `kld_threshold=True` adds the `kld_th` column (statistic_manager.py:80-82: the
 maximum over the batch's samples of the KLD-optimal clipping threshold) from the device
 histogram + search kernels (ops.kld_thresholds).  The error columns (mse_*/cos_*,
 statistic_manager.py:22-30) exist in the reference's files but no caller ever passes the quantized
 tensors they need (`tensors_q`), so they always hold NaN there; `collect_err=True` reproduces
-those columns, a non-empty `tensors_q` is rejected."""
+those columns, a non-empty `tensors_q` is rejected.  What this manager and the per-channel one share is defined here, once."""
 import os
 import shutil
 from pathlib import Path
@@ -29,25 +29,72 @@ def base_dir():
     return os.path.join(str(Path.home()), 'mxt-sim')
 
 
-def collects_native_flat(manager, tensor):
-    """Whether save_tensor_stats takes this tensor on its storage as it lies (ops.tensor_stats: no layout copy, no upcast): a
-    CUDA tensor of fp32 / bf16 / fp16 that is contiguous and not float32, or dense channels_last with the channels_last switch
-    on; one process and no forced exchange; and not a half tensor when the KLD threshold is collected (its histogram has no half
-    kernel).  A contiguous float32 tensor and every sharded run answer False and take the code they took.  Shape, strides, dtype
-    and attributes only: nothing touches the device.  No class of tensor measured slower native than through the copy
-    (profiles/tensor_collect.md), so the route function is not asked."""
+def collect_route(manager, tensor, force_global_min_max=False):
+    """How save_tensor_stats takes this tensor: 'flat' - on its storage as it lies (ops.tensor_stats: no
+    layout copy, no upcast): a CUDA tensor of fp32 / bf16 / fp16 that is contiguous and not float32, or dense channels_last with
+    the channels_last switch on; one process and no forced exchange; and not a half tensor when the KLD threshold is collected
+    (its histogram has no half kernel) - or None: a contiguous float32 tensor and every sharded run take the code they took.
+    Shape, strides, dtype and attributes only: nothing touches the device.  No class of tensor measured slower native than
+    through the copy (profiles/tensor_collect.md), so no route function is asked."""
     if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype in ops._ACT_DTYPES and tensor.numel() > 0):
-        return False
+        return None
     half = tensor.dtype != torch.float32
     layout = ops._layout(tensor)
     if not ((layout == 'nchw' and half) or (layout == 'nhwc' and ops._NHWC)):
-        return False
+        return None
     if D.world_size(manager.group) != 1 or D.forced_exchange():
-        return False
-    return not (manager.kld_threshold and half)
+        return None
+    return None if manager.kld_threshold and half else 'flat'
 
 
-class StatisticManager(metaclass=Singleton):
+def collects_native_flat(manager, tensor):
+    """Whether collect_route answers 'flat'."""
+    return collect_route(manager, tensor) == 'flat'
+
+
+# ---- what the per-tensor and the per-channel manager share
+def checkpointed(launch, group):
+    """launch()'s result; in a sharded run, after a wait of the in-launch exchange expired on some rank (the table is NaN there and
+    the group is on the collective now): launch()'s result again, before anything of it is recorded."""
+    out = launch()
+    if D.world_size(group) > 1 and not D.xrank_checkpoint(group):
+        out = launch()
+    return out
+
+
+def batch_extrema_sums(rows, N, group):
+    """For the mean over the batch of the per-sample extrema, from the per-sample table `rows` ([.., N * C], sample-major): a
+    float64 device record [3, C] - the samples' maxima summed, their minima summed, the sample count.  With several ranks the sums
+    and counts travel: every rank holds those of the GLOBAL batch.  The caller divides (per channel on the device, per tensor on
+    the host)."""
+    smax = rows[L.STAT_MAX].view(N, -1).double().sum(dim=0)
+    smin = rows[L.STAT_MIN].view(N, -1).double().sum(dim=0)
+    rec = torch.stack([smax, smin, torch.full_like(smax, float(N))])
+    if D.world_size(group) > 1:
+        rec = D.all_gather_records(rec, group).sum(dim=0)
+    return rec
+
+
+def summary_columns(names):
+    return ['%s_%s' % (kind, c) for c in names for kind in ('min', 'mean', 'max')]
+
+
+class Collector:
+    """The way out of both managers: every rank holds the same (global) statistics, so rank 0 writes, the others wait for the files."""
+
+    def __exit__(self, *args):
+        if not self.save_stats:
+            return
+        world = D.world_size(self.group)
+        if world == 1 or D.rank(self.group) == 0:
+            self._write()
+        if world > 1:
+            torch.distributed.barrier(group=self.group)
+
+
+class StatisticManager(Collector, metaclass=Singleton):
+    collect_route = collect_route       # the face inference_quantization_manager._route asks
+
     def __init__(self, folder, load_stats, stats=('max', 'min', 'std', 'mean', 'kurtosis', 'mean_abs', 'b', 'dim'),
                  batch_avg=False, kld_threshold=False, collect_err=False, group=None):
         self.name = folder
@@ -71,10 +118,11 @@ class StatisticManager(metaclass=Singleton):
         else:
             self.stats_df = None
 
-    def save_tensor_stats(self, tensor, tag, id, tensors_q={}, force_global_min_max=False):
+    def save_tensor_stats(self, tensor, tag, id, tensors_q={}, force_global_min_max=False, *, route=None):
+        """route: collect_route's answer, from a caller that has asked already (None: ask here)."""
         if len(tensors_q) > 0:
             raise NotImplementedError('error columns from quantized tensors: no caller in the reference')
-        native = collects_native_flat(self, tensor)
+        native = (route or collect_route(self, tensor)) == 'flat'
         x = tensor.detach() if native else tensor.detach().contiguous()
         n = x.numel()
         # with several ranks x is this rank's batch shard: the moment records travel (ops.pc_stats), every rank
@@ -84,10 +132,8 @@ class StatisticManager(metaclass=Singleton):
             # bf16 / fp16 and dense channels_last tensors, one process: the flat-row kernels on the storage as it lies
             table, mom = ops.tensor_stats(x, 1)
         else:
-            table, mom = ops.pc_stats(x, 1, 1, n, need_b=True, need_kurt=True, need_relu=True, group=self.group)
-        if world > 1 and not D.xrank_checkpoint(self.group):
-            # a wait of the in-launch exchange expired on some rank: the group is on the collective now - the table again
-            table, mom = ops.pc_stats(x, 1, 1, n, need_b=True, need_kurt=True, need_relu=True, group=self.group)
+            table, mom = checkpointed(lambda: ops.pc_stats(x, 1, 1, n, need_b=True, need_kurt=True, need_relu=True,
+                                                           group=self.group), self.group)
         host = table.cpu().numpy()[:, 0]
         m = mom.cpu().numpy()[:, 0]
         total = m[L.MOM_COUNT]      # elements of the global batch (== n on one rank)
@@ -99,11 +145,7 @@ class StatisticManager(metaclass=Singleton):
                 rows = ops.tensor_row_stats(x, x.shape[0])
             else:
                 rows, _ = ops.pc_stats(x, 1, x.shape[0], n // x.shape[0], local_only=True)
-            rec = torch.stack([rows[L.STAT_MAX].double().sum(), rows[L.STAT_MIN].double().sum(),
-                               torch.tensor(float(x.shape[0]), dtype=torch.float64, device=x.device)]).view(3, 1)
-            if world > 1:           # sums and sample counts travel: the mean over the global batch
-                rec = D.all_gather_records(rec, self.group).sum(dim=0)
-            r = rec.cpu().numpy()[:, 0]
+            r = batch_extrema_sums(rows, x.shape[0], self.group).cpu().numpy()[:, 0]
             vals['max'] = np.float32(r[0] / r[2])
             vals['min'] = np.float32(r[1] / r[2])
         for s in self.stats_names:
@@ -133,17 +175,6 @@ class StatisticManager(metaclass=Singleton):
         return tuple(self.stats_df.loc[id, '%s_%s' % (kind.get(s, 'mean'), s)]
                      for s in ('min', 'max', 'mean', 'std', 'mean_abs', 'b'))
 
-    def __exit__(self, *args):
-        if not self.save_stats:
-            return
-        if D.world_size(self.group) > 1:
-            # every rank holds the same (global) statistics: rank 0 writes, the others wait for the files
-            if D.rank(self.group) == 0:
-                self._write()
-            torch.distributed.barrier(group=self.group)
-            return
-        self._write()
-
     def _write(self):
         if os.path.exists(self.folder):
             shutil.rmtree(self.folder)
@@ -153,10 +184,7 @@ class StatisticManager(metaclass=Singleton):
             df = pd.DataFrame(columns=self.stats_names, data=self.stats[s_id])
             df.to_csv(os.path.join(self.folder, '%s.csv' % s_id), index=False)
             frames[s_id] = df
-        columns = []
-        for c in self.stats_names:
-            columns += ['min_%s' % c, 'mean_%s' % c, 'max_%s' % c]
-        summary = pd.DataFrame(columns=['internal_name'] + columns)
+        summary = pd.DataFrame(columns=['internal_name'] + summary_columns(self.stats_names))
         for s_id in sorted_nicely(frames.keys()):
             summary.loc[s_id, 'internal_name'] = self.metadata[s_id]
             for c in self.stats_names:

@@ -9,10 +9,10 @@ The seven statistics of one batch come from two coalesced passes over the activa
 device (cnnq_pc_moments + cnnq_pc_absdev) and ONE device->host copy of a [7, C] table, instead
 of a transposed copy, nine full-tensor reductions and seven synchronising copies
 (smpc.py:51-79,112).
-A dense channels_last activation of fp32 / bf16 / fp16 is read where it lies (ops.pc_stats_nhwc, DESIGN.md section 18: no
-layout copy, no upcast) whenever collects_native_nhwc says so, a contiguous bf16 / fp16 activation in its own dtype
-(ops.pc_stats_half) whenever collects_native_half does; every other tensor takes the NCHW kernels on a
-contiguous float32 copy.
+collect_route decides once per tensor how it is taken: 'nhwc' - a dense channels_last activation of fp32 /
+bf16 / fp16 is read where it lies (ops.pc_stats_nhwc, DESIGN.md section 18: no layout copy, no upcast); 'half' - a contiguous
+bf16 / fp16 activation is read in its own dtype (ops.pc_stats_half); None - every other tensor takes the
+NCHW kernels on a contiguous float32 copy.  collects_native_nhwc and collects_native_half are its boolean views.
 
 `collect_err=True` adds the six clipping-error columns the reference declares (smpc.py:24-32: mse_lowp, mse_gaus,
 mse_laplace, cos_lowp, cos_gaus, cos_laplace; formulas smpc.py:80-100) - the columns `-sm use -c mix` (iq.py:310-323)
@@ -26,7 +26,6 @@ sharded over ranks is not supported with collect_err."""
 import os
 import pickle
 import shutil
-from pathlib import Path
 
 import numpy as np
 import pandas as pd
@@ -36,6 +35,7 @@ from .. import _lib as L
 from .. import distributed as D
 from .. import ops
 from ..utils.misc import Singleton
+from .statistic_manager import Collector, base_dir, batch_extrema_sums, checkpointed, summary_columns
 
 SAVE_FULL_STATS = False
 _ROW = {'max': L.STAT_MAX, 'min': L.STAT_MIN, 'std': L.STAT_STD, 'mean': L.STAT_MEAN,
@@ -45,41 +45,44 @@ _ROW = {'max': L.STAT_MAX, 'min': L.STAT_MIN, 'std': L.STAT_STD, 'mean': L.STAT_
 ERR_NAMES = ('mse_lowp', 'mse_gaus', 'mse_laplace', 'cos_lowp', 'cos_gaus', 'cos_laplace')
 
 
-def base_dir():
-    return os.path.join(str(Path.home()), 'mxt-sim')
+def collect_route(manager, tensor, force_global_min_max=False):
+    """How save_tensor_stats takes this tensor: 'nhwc' - on its channels_last storage (ops.pc_stats_nhwc),
+    'half' - contiguous, in its own dtype (ops.pc_stats_half) - or None: ops.pc_stats on a contiguous float32 copy.  Each fact
+    once, in this order: the manager - no error columns, the extrema of the whole batch (batch_avg off, or the caller forces
+    them); the storage class - 'nhwc': dense channels_last and not contiguous, a dtype the kernels have, the channels_last switch
+    on; 'half': a contiguous non-empty 4-D bf16 / fp16 CUDA activation with a spatial extent; the group - one process, no forced
+    exchange; last the class's route function.  Shape, strides and attributes only: nothing touches the device."""
+    if manager.collect_err or (manager.batch_avg and not force_global_min_max) or not isinstance(tensor, torch.Tensor):
+        return None
+    if tensor.dtype in ops._ACT_DTYPES and ops._NHWC and ops._layout(tensor) == 'nhwc':
+        route = 'nhwc'
+    elif (tensor.is_cuda and tensor.dtype in ops._HALF_DTYPES and tensor.dim() == 4 and tensor.numel() > 0 and tensor.is_contiguous()
+            and (tensor.shape[2] > 1 or tensor.shape[3] > 1)):
+        route = 'half'
+    else:
+        return None
+    if D.world_size(manager.group) > 1 or D.forced_exchange():
+        return None
+    if route == 'nhwc':
+        native = ops._stats_nhwc_native(tensor.numel() // tensor.shape[1], tensor.shape[1], tensor.dtype)
+    else:
+        native = ops._stats_half_native(*ops.geometry(tensor), tensor.dtype)
+    return route if native else None
 
 
 def collects_native_nhwc(manager, tensor, force_global_min_max=False):
-    """Whether save_tensor_stats takes this tensor on its channels_last storage (ops.pc_stats_nhwc: no layout copy, no upcast):
-    a dense channels_last activation that is not contiguous, of a dtype the kernels have, with the channels_last switch on, one
-    process and no forced exchange, no error columns, the extrema of the whole batch (batch_avg off, or the caller forces them),
-    and a class of layer the route function keeps native.  Shape, strides and attributes only: nothing touches the device."""
-    if manager.collect_err or (manager.batch_avg and not force_global_min_max):
-        return False
-    if not (isinstance(tensor, torch.Tensor) and tensor.dtype in ops._ACT_DTYPES and ops._NHWC and ops._layout(tensor) == 'nhwc'):
-        return False
-    if D.world_size(manager.group) > 1 or D.forced_exchange():
-        return False
-    return ops._stats_nhwc_native(tensor.numel() // tensor.shape[1], tensor.shape[1], tensor.dtype)
+    """Whether collect_route answers 'nhwc'."""
+    return collect_route(manager, tensor, force_global_min_max) == 'nhwc'
 
 
 def collects_native_half(manager, tensor, force_global_min_max=False):
-    """Whether save_tensor_stats takes this tensor in its own dtype (ops.pc_stats_half: no upcast, no fp32 temporary): a contiguous
-    bf16 / fp16 CUDA activation with a spatial extent, one process and no forced exchange, no error columns, the extrema of the
-    whole batch (batch_avg off, or the caller forces them), and a class of layer the route function keeps native.  Shape, strides
-    and attributes only: nothing touches the device."""
-    if manager.collect_err or (manager.batch_avg and not force_global_min_max):
-        return False
-    if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype in ops._HALF_DTYPES and tensor.dim() == 4
-            and tensor.numel() > 0 and tensor.is_contiguous() and (tensor.shape[2] > 1 or tensor.shape[3] > 1)):
-        return False
-    if D.world_size(manager.group) > 1 or D.forced_exchange():
-        return False
-    N, C, HW = ops.geometry(tensor)
-    return ops._stats_half_native(N, C, HW, tensor.dtype)
+    """Whether collect_route answers 'half'."""
+    return collect_route(manager, tensor, force_global_min_max) == 'half'
 
 
-class StatisticManagerPerChannel(metaclass=Singleton):
+class StatisticManagerPerChannel(Collector, metaclass=Singleton):
+    collect_route = collect_route       # the face inference_quantization_manager._route asks
+
     def __init__(self, folder, load_stats, stats=('max', 'min', 'std', 'mean', 'kurtosis', 'b', 'std_pos'),
                  batch_avg=False, collect_err=False, group=None, err_settings=None):
         self.name = folder
@@ -105,55 +108,40 @@ class StatisticManagerPerChannel(metaclass=Singleton):
             self.stats = {}
 
     def save_tensor_stats(self, tensor, tag, id, tensors_q={}, force_global_min_max=False, half_range=False,
-                          err_settings=None):
+                          err_settings=None, *, route=None):
         """smpc.py:45-125.  half_range / err_settings matter with collect_err only: err_settings (a dict, see __init__)
-        overrides the manager's own for this call; a callable provider is asked with (tag, half_range)."""
+        overrides the manager's own for this call; a callable provider is asked with (tag, half_range).  route: collect_route's
+        answer, from a caller that has asked already (None: ask here)."""
         # FC and 1x1-spatial outputs are not per-channel quantized (smpc.py:47-48)
         if len(tensor.shape) < 3 or (tensor.shape[2] == 1 and tensor.shape[3] == 1):
             return
-        if collects_native_nhwc(self, tensor, force_global_min_max):
-            # dense channels_last, fp32 / bf16 / fp16: the table from the storage as it lies (DESIGN.md section 18)
-            table, _ = ops.pc_stats_nhwc(tensor.detach(), need_b='b' in self.stats_names, need_kurt='kurtosis' in self.stats_names,
-                                         need_relu='std_pos' in self.stats_names)
-            return self._record(id, table)
-        if collects_native_half(self, tensor, force_global_min_max):
-            # contiguous bf16 / fp16: the table from the tensor in its own dtype (DESIGN.md section 23)
-            table, _ = ops.pc_stats_half(tensor.detach(), need_b='b' in self.stats_names, need_kurt='kurtosis' in self.stats_names,
-                                         need_relu='std_pos' in self.stats_names)
+        need = dict(need_b='b' in self.stats_names or self.collect_err, need_kurt='kurtosis' in self.stats_names,
+                    need_relu='std_pos' in self.stats_names)
+        route = route or collect_route(self, tensor, force_global_min_max)
+        if route:
+            # the table from the channels_last storage as it lies (DESIGN.md section 18), or from the tensor in its own dtype (23)
+            table, _ = (ops.pc_stats_nhwc if route == 'nhwc' else ops.pc_stats_half)(tensor.detach(), **need)
             return self._record(id, table)
         N, C = tensor.shape[0], tensor.shape[1]
         HW = tensor.numel() // (N * C)
         x = tensor.detach().contiguous()
         settings = self._err_settings(tag, half_range, err_settings) if self.collect_err else None
-        table, _ = ops.pc_stats(x, N, C, HW, need_b='b' in self.stats_names or self.collect_err,
-                                need_kurt='kurtosis' in self.stats_names,
-                                need_relu='std_pos' in self.stats_names, group=self.group)
-        if D.world_size(self.group) > 1 and not D.xrank_checkpoint(self.group):
-            # sharded: a wait of the in-launch exchange expired on some rank (the table is NaN there); the group is on the
-            # collective now - this layer's table again, before anything of it is recorded
-            table, _ = ops.pc_stats(x, N, C, HW, need_b='b' in self.stats_names or self.collect_err,
-                                    need_kurt='kurtosis' in self.stats_names, need_relu='std_pos' in self.stats_names,
-                                    group=self.group)
-        if self.batch_avg and not force_global_min_max:
-            # mean over the batch of the per-sample extrema (smpc.py:72,78): rows = (n, c) pairs; with several ranks
-            # the sums and the sample counts travel, so every rank holds the mean over the GLOBAL batch
+        table, _ = checkpointed(lambda: ops.pc_stats(x, N, C, HW, group=self.group, **need), self.group)
+        batch_mean = self.batch_avg and not force_global_min_max
+        if batch_mean:
+            # mean over the batch of the per-sample extrema (smpc.py:72,78): rows = (n, c) pairs, fp64 sums divided per channel
+            # on the device
             rows, _ = ops.pc_stats(x, 1, N * C, HW, local_only=True)
+            smax, smin, cnt = batch_extrema_sums(rows, N, self.group)
             table = table.clone()
-            smax = rows[L.STAT_MAX].view(N, C).double().sum(dim=0)
-            smin = rows[L.STAT_MIN].view(N, C).double().sum(dim=0)
-            cnt = torch.full_like(smax, float(N))
-            if D.world_size(self.group) > 1:
-                rec = D.all_gather_records(torch.stack([smax, smin, cnt]), self.group).sum(dim=0)
-                smax, smin, cnt = rec[0], rec[1], rec[2]
             table[L.STAT_MAX] = (smax / cnt).float()
             table[L.STAT_MIN] = (smin / cnt).float()
         if self.collect_err:
             # the three quantizations `-sm use -c mix` chooses between, from THIS batch's table; rows in ERR_NAMES' order.
             # The table's min / max rows are x's exact extrema unless batch_avg replaced them.
-            exact = not (self.batch_avg and not force_global_min_max)
             qp_l, qp_g, qp_p = ops.mix_candidates(table, **settings)
             err = ops.pc_quant_errors(x, N, C, HW, (qp_p, qp_g, qp_l),
-                                      mm=table[[L.STAT_MIN, L.STAT_MAX]] if exact else None)
+                                      mm=None if batch_mean else table[[L.STAT_MIN, L.STAT_MAX]])
             table = torch.cat([table, err])
         self._record(id, table)
 
@@ -182,19 +170,6 @@ class StatisticManagerPerChannel(metaclass=Singleton):
             return self.stats[id]['%s_%s' % (kind, stat)]
         return None
 
-    def __exit__(self, *args):
-        if not self.save_stats:
-            return
-        if D.world_size(self.group) > 1:
-            # every rank holds the same (global) statistics: rank 0 writes, the others wait for the files
-            if D.rank(self.group) != 0:
-                torch.distributed.barrier(group=self.group)
-                return
-            self._write()
-            torch.distributed.barrier(group=self.group)
-            return
-        self._write()
-
     def _write(self):
         if os.path.exists(self.folder):
             shutil.rmtree(self.folder)
@@ -206,9 +181,7 @@ class StatisticManagerPerChannel(metaclass=Singleton):
 
     def _save_summary(self):
         """min / mean / max over the collected batches per channel (smpc.py:152-174)."""
-        columns = []
-        for c in self.stats_names:
-            columns += ['min_%s' % c, 'mean_%s' % c, 'max_%s' % c]
+        columns = summary_columns(self.stats_names)
         summary = {}
         for layer in self.stats:
             df = pd.DataFrame(columns=columns)

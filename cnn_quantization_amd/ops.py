@@ -2389,15 +2389,20 @@ def kld_thresholds(x, rows=None, want_parts=False):
     return out
 
 
+def row_sumsq_native(x, rows=None):
+    """Whether row_sumsq reads x where it lies: a bf16 / fp16 device tensor, or a dense channels_last float32 one (with the
+    channels_last switch on) whose rows are its samples (rows None: they are).  Shape, strides and dtype only."""
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() > 0 and
+            (x.dtype in _HALF_DTYPES or (x.dtype == torch.float32 and _NHWC and _layout(x) == 'nhwc' and rows in (None, x.shape[0]))))
+
+
 def row_sumsq(x, rows=None):
     """Per-sample sum of squares, the runtime distance measure of distance_stats.py:22-33
     (`torch.sum(t**2, dim=-1)` on [N, -1]): the moments kernel with N = 1, C = rows (fp64 sums) for a contiguous float32
     tensor; a bf16 / fp16 tensor, and a dense channels_last one with rows = its samples, take tensor_stats where they lie."""
-    if isinstance(x, torch.Tensor) and x.is_cuda and x.dim() > 0:
-        n = int(rows if rows is not None else x.shape[0])
-        if x.dtype in _HALF_DTYPES or (x.dtype == torch.float32 and _NHWC and _layout(x) == 'nhwc' and n == x.shape[0]):
-            # bf16 / fp16, and the samples of a dense channels_last tensor: the flat-row kernels on the storage as it lies
-            return tensor_stats(x, n, need_dev=False)[1][L.MOM_SUMSQ].to(torch.float32)
+    if row_sumsq_native(x, rows):
+        # bf16 / fp16, and the samples of a dense channels_last tensor: the flat-row kernels on the storage as it lies
+        return tensor_stats(x, int(rows if rows is not None else x.shape[0]), need_dev=False)[1][L.MOM_SUMSQ].to(torch.float32)
     x = _dev(x, 'x')
     rows = int(rows if rows is not None else x.shape[0])
     _, mom = pc_stats(x, 1, rows, x.numel() // rows, local_only=True)
