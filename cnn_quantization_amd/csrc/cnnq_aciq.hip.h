@@ -313,70 +313,29 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_fused_fl
     __shared__ int sh_timed_out;
     const unsigned st0 = threadIdx.x == 0 ? __hip_atomic_load(ws.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     const int tid = threadIdx.x;
-    int c, member;
-    if (g.cb <= 1) {
-        c = (int)blockIdx.x / g.Gs;
-        member = (int)blockIdx.x - c * g.Gs;
-    } else {
-        const int per = g.cb * g.Gs, blk = (int)blockIdx.x / per, r = (int)blockIdx.x - blk * per;
-        const int c0 = blk * g.cb, cbl = min(g.cb, g.C - c0);
-        member = r / cbl;
-        c = c0 + (r - member * cbl);
-    }
+    using T = FTile<K, KL>;
+    T t;
+    t.place(g);
+    const int c = t.c, member = t.member;
     // the channel's statistics of pass A (uniform addresses: scalar loads), in flight next to the tile
     const float vmin = fa.stats[(size_t)CNNQ_STAT_MIN * g.C + c], vmax = fa.stats[(size_t)CNNQ_STAT_MAX * g.C + c];
     const float vmean = fa.stats[(size_t)CNNQ_STAT_MEAN * g.C + c], vstd = fa.stats[(size_t)CNNQ_STAT_STD * g.C + c];
     const float bits = ba ? fa.bits[c] : (float)cfg.num_bits;
 
-    const unsigned f0 = (unsigned)member * (256u * (K + KL));   // < total
-    const unsigned n_first = f0 / g.cpc;
-    const unsigned u = f0 + (unsigned)tid;
-    const unsigned n = u / g.cpc;
-    FWalk w0;
-    w0.ro = (n - n_first) * g.rs;
-    w0.co = (u - n * g.cpc) * 16u;
-    const unsigned long long lim64 = (unsigned long long)((unsigned)g.N - n_first) * g.rs;
-    const unsigned lim = lim64 > 0xffffffffull ? 0xffffffffu : (unsigned)lim64;   // row offsets below it are inside the batch
-    const size_t base = ((size_t)n_first * (size_t)g.P + (size_t)c * (size_t)g.HW) * 4;
-    const char* xb = reinterpret_cast<const char*>(x) + base;
-    char* yb = reinterpret_cast<char*>(y) + base;
-    uint8_t* cbb = (MODE == 0 && OUT == 1 && xo.codes) ? xo.codes + base / 4 : nullptr;
+    char* yb = reinterpret_cast<char*>(y) + t.base;
+    uint8_t* cbb = (MODE == 0 && OUT == 1 && xo.codes) ? xo.codes + t.base / 4 : nullptr;
 
-    // ---- the tile: K 16-byte loads per lane, back to back, then the last KL steps straight into LDS (LDS-DMA).  Round 6: the
-    //      register steps first and the LDS-DMA behind the compiler's back (lds_dma16_behind, cnnq_common.hip.h) - with the
-    //      builtin in flight it waited for vmcnt(0) before the first use of any register step
+    // ---- the tile (FTile::load: the order of its loads and why), then the lane's sum of |x - mean| over its steps inside the
+    //      channel: the register steps and the LDS steps apart (FTile)
     float v[K][4];
-    FWalk w = w0;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const unsigned off = w.ro < lim ? w.ro + w.co : 0u;
-        ldv_nt<4>(reinterpret_cast<const float*>(xb + off), v[j]);
-        w.step(g);
-    }
-    if constexpr (KL > 0) {
-#pragma unroll
-        for (int l = 0; l < KL; ++l) {
-            const unsigned off = w.ro < lim ? w.ro + w.co : 0u;
-            lds_dma16_behind(xb, off, sh_x + (l * TPB + (tid & ~63)) * 4);
-            w.step(g);
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    // steps of this lane inside the channel: u + 256 s < total.  Two accumulators, the register steps and the LDS steps, each
-    // in step order, added at the end: the order does not depend on what landed first (the cold path does the same)
-    const int nvalid = u < g.total ? (int)((g.total - u + 255u) / 256u) : 0;
+    t.load(g, x, v, sh_x);
+    const int nvalid = t.nvalid(g);
     double sa = 0.;
-#pragma unroll
-    for (int j = 0; j < K; ++j) absdev_step(v[j], vmean, j < nvalid, sa);
+    T::template steps<FT_REG>(v, sh_x, [&](const float (&q)[4], int s) { absdev_step(q, vmean, s < nvalid, sa); });
     if constexpr (KL > 0) {
         lds_dma_landed(sa);
         double sl = 0.;
-#pragma unroll
-        for (int l = 0; l < KL; ++l) {
-            const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
-            const float t[4] = {q.x, q.y, q.z, q.w};
-            absdev_step(t, vmean, K + l < nvalid, sl);
-        }
+        T::template steps<FT_LDS>(v, sh_x, [&](const float (&q)[4], int s) { absdev_step(q, vmean, s < nvalid, sl); });
         sa = sa + sl;
     }
     const double msum = wg_sum1(sa, l_s);
@@ -398,17 +357,14 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_fused_fl
         // pair region (unused by the slot meeting; every workgroup that lands here writes the same values), then the same fold
         unsigned long long* tab = ws.part + (size_t)c * ws.gstride;
         for (int m = 0; m < g.Gs; ++m) {
-            const unsigned mf0 = (unsigned)m * (256u * (K + KL)), mu = mf0 + (unsigned)tid;
-            const int mvalid = mu < g.total ? (int)((g.total - mu + 255u) / 256u) : 0;
             double s2 = 0., sl2 = 0.;
             for (int s = 0; s < K + KL; ++s) {
-                const bool in = s < mvalid;
-                const unsigned ee = in ? mu + 256u * (unsigned)s : mf0;
-                const unsigned nn = ee / g.cpc;
-                float t[4];
-                ldv<4>(x + (size_t)nn * (size_t)g.P + (size_t)c * (size_t)g.HW + (size_t)(ee - nn * g.cpc) * 4, t);
-                if (s >= K) absdev_step(t, vmean, in, sl2);
-                else absdev_step(t, vmean, in, s2);
+                size_t off;
+                const bool in = T::cold_step(g, c, m, s, off);
+                float q[4];
+                ldv<4>(x + off, q);
+                if (s >= K) absdev_step(q, vmean, in, sl2);
+                else absdev_step(q, vmean, in, s2);
             }
             if constexpr (KL > 0) s2 = s2 + sl2;
             const double ms = wg_sum1(s2, l_s);
@@ -434,8 +390,7 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_fused_fl
     double cnt = fa.count;
     if constexpr (XR) cnt = fa.count_dev[c];          // (uniform address: a scalar load)
     const float vb = (float)(sh_tot / cnt);
-    w = w0;
-    asm volatile("" : "+v"(w.ro), "+v"(w.co));      // the walk repeated and hidden from the optimiser, as in k_mmq_flat
+    FWalk w = t.rewalk();      // the store phase on a fresh walk
     if constexpr (MODE == 0) {
         const ChanParams cp = channel_params(cfg, ba, bits, vmin, vmax, vmean, vstd, vb);
         const float sc = cp.scale, zp = cp.zp, qm = cp.qmax;
@@ -455,48 +410,21 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_fused_fl
         // ---- Q/DQ out of LDS and registers
         const float zpa[1] = {zp};
         unsigned nzp[1] = {0u};
-        if (__builtin_amdgcn_readfirstlane((int)fast)) {
-            const float s_sc = uniform_f(sc), s_rs = uniform_f(1.0f / sc), s_zp = uniform_f(zp), s_qm = uniform_f(qm);
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
+        // isfast: the exact quotient without the divide, parameters in scalar registers
+        const auto store = [&](auto isfast, float a_sc, float a_rs, float a_zp, float a_qm) {
+            T::steps_walk(g, v, sh_x, w, [&](const float (&q)[4], int) {
                 float o[4], cd[4];
-                qdq4_fast(v[j], s_sc, s_rs, s_zp, s_qm, o, cd);
-                if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, nullptr, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
-                w.step(g);
-            }
-            if constexpr (KL > 0) {
+                if constexpr (decltype(isfast)::value) {
+                    qdq4_fast(q, a_sc, a_rs, a_zp, a_qm, o, cd);
+                } else {
 #pragma unroll
-                for (int l = 0; l < KL; ++l) {
-                    const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
-                    const float t[4] = {q.x, q.y, q.z, q.w};
-                    float o[4], cd[4];
-                    qdq4_fast(t, s_sc, s_rs, s_zp, s_qm, o, cd);
-                    if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, nullptr, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
-                    w.step(g);
+                    for (int e = 0; e < 4; ++e) o[e] = qdq1(q[e], a_sc, a_zp, a_qm, cd[e]);
                 }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                float o[4], cd[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = qdq1(v[j][e], sc, zp, qm, cd[e]);
-                if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, nullptr, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
-                w.step(g);
-            }
-            if constexpr (KL > 0) {
-#pragma unroll
-                for (int l = 0; l < KL; ++l) {
-                    const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
-                    const float t[4] = {q.x, q.y, q.z, q.w};
-                    float o[4], cd[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = qdq1(t[e], sc, zp, qm, cd[e]);
-                    if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, nullptr, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
-                    w.step(g);
-                }
-            }
-        }
+                if (t.inside(w)) xstore<OUT, 1>(xo, yb, cbb, nullptr, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
+            });
+        };
+        if (__builtin_amdgcn_readfirstlane((int)fast)) store(std::true_type{}, uniform_f(sc), uniform_f(1.0f / sc), uniform_f(zp), uniform_f(qm));
+        else store(std::false_type{}, sc, 0.f, zp, qm);
         if constexpr (OUT == 1) {
             if (xo.hist) xhist_flush<1>(sh_hist, xo.hist, nbins, zpa, nzp);
         }
@@ -516,15 +444,15 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_fused_fl
         const bool hi_ni = hi != rintf(hi), lo_ni = lo != rintf(lo);     // a non-integer bound is a value of its own
         unsigned nlo = 0u, nhi = 0u, nni = 0u;
         const int hoff = (tid & (MTF_REP - 1)) - wstart * MTF_REP;
-        auto emit = [&](const float (&t)[4], bool isfast, float rd) {
+        auto emit = [&](const float (&q)[4], bool isfast, float rd) {
             float o[4], cd[4];
             if (isfast) {
-                mt_qdq4_fast(t, d, rd, lo, hi, o, cd);
+                mt_qdq4_fast(q, d, rd, lo, hi, o, cd);
             } else {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = mt_qdq1<false>(t[e], d, rd, lo, hi, cd[e]);
+                for (int e = 0; e < 4; ++e) o[e] = mt_qdq1<false>(q[e], d, rd, lo, hi, cd[e]);
             }
-            if (w.ro < lim) {
+            if (t.inside(w)) {
                 stv_nt<4>(reinterpret_cast<float*>(yb + (w.ro + w.co)), o);
                 if constexpr (OUT == 1) {
                     if (want_hist) {
@@ -538,31 +466,12 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_fused_fl
                     }
                 }
             }
-            w.step(g);
         };
         if (__builtin_amdgcn_readfirstlane((int)fast)) {
             const float rd = uniform_f(1.0f / d);
-#pragma unroll
-            for (int j = 0; j < K; ++j) emit(v[j], true, rd);
-            if constexpr (KL > 0) {
-#pragma unroll
-                for (int l = 0; l < KL; ++l) {
-                    const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
-                    const float t[4] = {q.x, q.y, q.z, q.w};
-                    emit(t, true, rd);
-                }
-            }
+            T::steps_walk(g, v, sh_x, w, [&](const float (&q)[4], int) { emit(q, true, rd); });
         } else {
-#pragma unroll
-            for (int j = 0; j < K; ++j) emit(v[j], false, 0.f);
-            if constexpr (KL > 0) {
-#pragma unroll
-                for (int l = 0; l < KL; ++l) {
-                    const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
-                    const float t[4] = {q.x, q.y, q.z, q.w};
-                    emit(t, false, 0.f);
-                }
-            }
+            T::steps_walk(g, v, sh_x, w, [&](const float (&q)[4], int) { emit(q, false, 0.f); });
         }
         if constexpr (OUT == 1) {
             if (want_hist) {

@@ -35,6 +35,7 @@
 //     While bit 0 is up (cnnq_group_ws_status_clear lowers it) the bound is 0.5 ms instead of 20: a device shared with
 //     another process's workgroups loses 20 ms per expiry otherwise, and a meeting that works takes 10-40 us.
 #pragma once
+#include <type_traits>
 #include "cnnq_common.hip.h"
 #include "cnnq_qdq.hip.h"
 #include "cnnq_xrank.hip.h"
@@ -743,12 +744,146 @@ struct FGeo {
 
 struct FWalk {
     unsigned ro, co;      // row offset and column offset, bytes
-    __device__ __forceinline__ void step(const FGeo& g) {
-        co += g.r16;
-        ro += g.q256 * g.rs;
+    // q rows and r16 bytes of columns further (a stride's q, r16: stride / cpc and (stride % cpc) * 16)
+    __device__ __forceinline__ void step(const FGeo& g, unsigned q, unsigned r16) {
+        co += r16;
+        ro += q * g.rs;
         const bool wrap = co >= g.cpc * 16u;
         co -= wrap ? g.cpc * 16u : 0u;
         ro += wrap ? g.rs : 0u;
+    }
+    __device__ __forceinline__ void step(const FGeo& g) { step(g, g.q256, g.r16); }      // 256 float4: one step of the tile
+};
+
+// The flat tile of the fp32 single launches (k_mmq_flat, k_fused_flat; k_stats_flat spells the same tile out itself, see
+// there): member `member` of channel `c` is the 256 * (K + KL) consecutive float4 from f0 of the channel's flattened space;
+// lane t's step s is element f0 + 256 s + t.  Steps 0 .. K-1 live in registers (v[j]), steps K .. K+KL-1 in LDS (sh_x,
+// KL * 256 float4, lane-linear per step: filled by LDS-DMA - no staging registers - and read back by the lane that owns
+// them: 160 instead of 128 KB per workgroup at the same register budget).  The tile owns the placement, the load, the iteration over its
+// steps and the recompute address of the cold paths; a kernel owns what it does with a step's four values, its accumulators (the
+// register steps and the LDS steps accumulate SEPARATELY, each in step order, and are added at the end: the order of the
+// additions does not depend on what landed first, and the cold paths do the same), and its meeting.
+enum { FT_REG = 1, FT_LDS = 2, FT_ALL = 3 };      // which steps: those in registers, those in LDS, all (in step order)
+template <int K, int KL>
+struct FTile {
+    int c, member;
+    unsigned f0, n_first;     // first float4 of the tile in the channel (< total) and the sample it lies in
+    unsigned u;               // this lane's first float4
+    unsigned lim;             // row offsets (FWalk::ro, relative to sample n_first) below it are inside the batch
+    FWalk w0;                 // this lane's walk at step 0
+    size_t base;              // bytes from the tensor's start to channel c's row of sample n_first
+
+    // steps of a lane whose first float4 is e that lie inside the channel: e + 256 s < total
+    static __device__ __forceinline__ int valid_steps(const FGeo& g, unsigned e) {
+        return e < g.total ? (int)((g.total - e + 255u) / 256u) : 0;
+    }
+    // the walk at float4 i of the tile
+    __device__ __forceinline__ FWalk walk_at(const FGeo& g, unsigned i) const {
+        const unsigned e = f0 + i, n = e / g.cpc;
+        FWalk w;
+        w.ro = (n - n_first) * g.rs;
+        w.co = (e - n * g.cpc) * 16u;
+        return w;
+    }
+    // (c, member) of this workgroup and the tile's origin
+    __device__ __forceinline__ void place(const FGeo& g) {
+        if (g.cb <= 1) {
+            c = (int)blockIdx.x / g.Gs;
+            member = (int)blockIdx.x - c * g.Gs;
+        } else {
+            // consecutive workgroups hold the SAME member tile of cb adjacent channels: per sample they read one run of
+            // cb channel rows together
+            const int per = g.cb * g.Gs, blk = (int)blockIdx.x / per, r = (int)blockIdx.x - blk * per;
+            const int c0 = blk * g.cb, cbl = min(g.cb, g.C - c0);
+            member = r / cbl;
+            c = c0 + (r - member * cbl);
+        }
+        f0 = (unsigned)member * (256u * (K + KL));
+        n_first = f0 / g.cpc;
+        u = f0 + (unsigned)threadIdx.x;
+        w0 = walk_at(g, (unsigned)threadIdx.x);
+        const unsigned long long lim64 = (unsigned long long)((unsigned)g.N - n_first) * g.rs;
+        lim = lim64 > 0xffffffffull ? 0xffffffffu : (unsigned)lim64;
+        base = ((size_t)n_first * (size_t)g.P + (size_t)c * (size_t)g.HW) * 4;
+    }
+    __device__ __forceinline__ int nvalid(const FGeo& g) const { return valid_steps(g, u); }
+
+    // The load: K nontemporal 16-byte loads per lane back to back, then the KL LDS-DMA steps, each wave's 64 x 16 bytes
+    // lane-linear at its own 1 KB slot.  Past the end of the channel a lane re-reads the tile base's row start (an element of
+    // the same channel: harmless for extrema, masked out of sums by nvalid, never stored).  The order is the point:
+    // - the register loads first, the LDS-DMA behind them and behind the compiler's back (lds_dma16_behind, cnnq_common.hip.h):
+    //   with the builtin, which had to be issued FIRST, the compiler waited for vmcnt(0) before the first use of any register step;
+    // - nothing that consumes a loaded value may be scheduled in between the loads (the scheduler otherwise folds the first steps
+    //   into the accumulators while it still has loads to issue, and waits for them first): the scheduling barrier;
+    // - the reader of the LDS steps waits for them itself: lds_dma_landed(dep) in front of steps<FT_LDS>, dep a value that the
+    //   register steps produced.
+    __device__ __forceinline__ void load(const FGeo& g, const float* __restrict__ x, float (&v)[K][4], const float* sh_x) const {
+        const char* xb = reinterpret_cast<const char*>(x) + base;
+        FWalk w = w0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const unsigned off = w.ro < lim ? w.ro + w.co : 0u;
+#if FLAT_ABL & 4
+            for (int e = 0; e < 4; ++e) v[j][e] = (float)(int)((off >> 4) + (unsigned)e) * 1e-4f - 3.f;      // no loads: synthetic values
+            (void)xb;
+#else
+            ldv_nt<4>(reinterpret_cast<const float*>(xb + off), v[j]);
+#endif
+            w.step(g);
+        }
+        if constexpr (KL > 0) {
+#pragma unroll
+            for (int l = 0; l < KL; ++l) {
+                const unsigned off = w.ro < lim ? w.ro + w.co : 0u;
+                lds_dma16_behind(xb, off, sh_x + (l * TPB + ((int)threadIdx.x & ~63)) * 4);
+                w.step(g);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // The walk for the store phase: derived again and hidden from the optimiser, which would otherwise keep the K + KL offsets
+    // of the load alive across the meeting (that many more registers than the tile leaves: spills)
+    __device__ __forceinline__ FWalk rewalk() const {
+        FWalk w = w0;
+        asm volatile("" : "+v"(w.ro), "+v"(w.co));
+        return w;
+    }
+    __device__ __forceinline__ bool inside(const FWalk& w) const { return w.ro < lim; }
+
+    // f(t, s) for the tile's steps in step order: t the four values of step s, out of v or read back from sh_x
+    template <int PART = FT_ALL, class F>
+    static __device__ __forceinline__ void steps(const float (&v)[K][4], const float* sh_x, F&& f) {
+        if constexpr ((PART & FT_REG) != 0) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) f(v[j], j);
+        }
+        if constexpr ((PART & FT_LDS) != 0 && KL > 0) {
+#pragma unroll
+            for (int l = 0; l < KL; ++l) {
+                const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + (int)threadIdx.x) * 4);
+                const float t[4] = {q.x, q.y, q.z, q.w};
+                f(t, K + l);
+            }
+        }
+    }
+    // ... with w at step s during f(t, s): the store phases
+    template <class F>
+    static __device__ __forceinline__ void steps_walk(const FGeo& g, const float (&v)[K][4], const float* sh_x, FWalk& w, F&& f) {
+        steps(v, sh_x, [&](const float (&t)[4], int s) {
+            f(t, s);
+            w.step(g);
+        });
+    }
+    // The cold paths recompute every member of the channel with that member's own lane mapping: this lane's step s of member m
+    // of channel c - the float offset of its four values in x, and whether the step is inside the channel (outside, the
+    // member's first float4: loaded, not counted)
+    static __device__ __forceinline__ bool cold_step(const FGeo& g, int c, int m, int s, size_t& off) {
+        const unsigned mf0 = (unsigned)m * (256u * (K + KL)), mu = mf0 + (unsigned)threadIdx.x;
+        const bool in = s < valid_steps(g, mu);
+        const unsigned ee = in ? mu + 256u * (unsigned)s : mf0;
+        const unsigned nn = ee / g.cpc;
+        off = (size_t)nn * (size_t)g.P + (size_t)c * (size_t)g.HW + (size_t)(ee - nn * g.cpc) * 4;
+        return in;
     }
 };
 
@@ -769,39 +904,32 @@ __device__ __forceinline__ void wg_minmax1(float tn, float tx, float* l_mn, floa
 // consecutive pieces: a wave's store instruction covers 128 * PKL contiguous bytes (inside a row), like a store of y.
 // Rows are whole groups of PKL float4 and sit on 2 * PKL byte boundaries of the stream (H*W % (4 * PKL) == 0 and an
 // aligned buffer: the caller checked).
-template <int K, int PKL, bool NT>
-__device__ __forceinline__ void flat_pk_flush(const FGeo& g, const uint16_t* sh_pk, uint8_t* pbb, unsigned f0, unsigned n_first,
-                                              unsigned lim) {
+template <int K, int KL, int PKL, bool NT>
+__device__ __forceinline__ void flat_pk_flush(const FGeo& g, const FTile<K, KL>& t, const uint16_t* sh_pk, uint8_t* pbb) {
     static_assert(PKL == 8 || PKL == 4, "16- or 8-byte stores");
     const unsigned i0 = (unsigned)threadIdx.x * PKL;           // first word of this lane's piece in pass 0
-    const unsigned u2 = f0 + i0;
-    const unsigned n2 = u2 / g.cpc;
-    unsigned ro2 = (n2 - n_first) * g.rs, co2 = (u2 - n2 * g.cpc) * 16u;
+    FWalk w = t.walk_at(g, i0);
     constexpr unsigned stepf = 256u * PKL;                     // float4 between two passes
     const unsigned sq = stepf / g.cpc, sr16 = (stepf % g.cpc) * 16u;
 #pragma unroll
-    for (int r = 0; r < K / PKL; ++r) {
+    for (int r = 0; r < (K + KL) / PKL; ++r) {
         const uint16_t* src = sh_pk + (r * stepf + i0);
         if constexpr (PKL == 8) {
             typedef unsigned u4v __attribute__((ext_vector_type(4)));
             const u4v q = *reinterpret_cast<const u4v*>(src);
-            if (ro2 < lim) {
-                if (NT) __builtin_nontemporal_store(q, reinterpret_cast<u4v*>(pbb + (ro2 + co2) / 8));
-                else *reinterpret_cast<u4v*>(pbb + (ro2 + co2) / 8) = q;
+            if (t.inside(w)) {
+                if (NT) __builtin_nontemporal_store(q, reinterpret_cast<u4v*>(pbb + (w.ro + w.co) / 8));
+                else *reinterpret_cast<u4v*>(pbb + (w.ro + w.co) / 8) = q;
             }
         } else {
             typedef unsigned u2v __attribute__((ext_vector_type(2)));
             const u2v q = *reinterpret_cast<const u2v*>(src);
-            if (ro2 < lim) {
-                if (NT) __builtin_nontemporal_store(q, reinterpret_cast<u2v*>(pbb + (ro2 + co2) / 8));
-                else *reinterpret_cast<u2v*>(pbb + (ro2 + co2) / 8) = q;
+            if (t.inside(w)) {
+                if (NT) __builtin_nontemporal_store(q, reinterpret_cast<u2v*>(pbb + (w.ro + w.co) / 8));
+                else *reinterpret_cast<u2v*>(pbb + (w.ro + w.co) / 8) = q;
             }
         }
-        co2 += sr16;
-        ro2 += sq * g.rs;
-        const bool wrap = co2 >= g.cpc * 16u;
-        co2 -= wrap ? g.cpc * 16u : 0u;
-        ro2 += wrap ? g.rs : 0u;
+        w.step(g, sq, sr16);
     }
 }
 
@@ -829,79 +957,28 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_flat
     const unsigned st0 = threadIdx.x == 0 ? __hip_atomic_load(ws.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     GRP_STAMP(0);
     const int tid = threadIdx.x;
-    int c, member;
-    if (g.cb <= 1) {
-        c = (int)blockIdx.x / g.Gs;
-        member = (int)blockIdx.x - c * g.Gs;
-    } else {
-        // consecutive workgroups hold the SAME member tile of cb adjacent channels: per sample they read one run of
-        // cb channel rows together
-        const int per = g.cb * g.Gs, blk = (int)blockIdx.x / per, r = (int)blockIdx.x - blk * per;
-        const int c0 = blk * g.cb, cbl = min(g.cb, g.C - c0);
-        member = r / cbl;
-        c = c0 + (r - member * cbl);
-    }
-    const unsigned f0 = (unsigned)member * (256u * (K + KL));   // < total
-    const unsigned n_first = f0 / g.cpc;
-    const unsigned u = f0 + (unsigned)tid;
-    const unsigned n = u / g.cpc;
-    FWalk w0;
-    w0.ro = (n - n_first) * g.rs;
-    w0.co = (u - n * g.cpc) * 16u;
-    const unsigned long long lim64 = (unsigned long long)((unsigned)g.N - n_first) * g.rs;
-    const unsigned lim = lim64 > 0xffffffffull ? 0xffffffffu : (unsigned)lim64;   // row offsets below it are inside the batch
-    const size_t base = ((size_t)n_first * (size_t)g.P + (size_t)c * (size_t)g.HW) * 4;
-    const char* xb = reinterpret_cast<const char*>(x) + base;
-    char* yb = reinterpret_cast<char*>(y) + base;
-    uint8_t* cbb = (OUT == 1 && xo.codes) ? xo.codes + base / 4 : nullptr;     // the tile's bases of the other outputs
-    uint8_t* pbb = (OUT == 2) ? xo.packed + base / 8 : nullptr;
+    using T = FTile<K, KL>;
+    T t;
+    t.place(g);
+    const int c = t.c, member = t.member;
+    char* yb = reinterpret_cast<char*>(y) + t.base;
+    uint8_t* cbb = (OUT == 1 && xo.codes) ? xo.codes + t.base / 4 : nullptr;     // the tile's bases of the other outputs
+    uint8_t* pbb = (OUT == 2) ? xo.packed + t.base / 8 : nullptr;
     // lanes per wide packed store: 8 (16 bytes) when rows are whole groups of 8 float4 and sit on 16-byte boundaries of
     // the stream, 4 (8 bytes) for rows of whole groups of 4 (28x28), else 1 (the 2-byte store per float4)
     const int pkl = (OUT != 2 || (flags & MMQ_FLAG_PK_NARROW)) ? 1 : (g.cpc % 8u == 0u) ? 8 : (g.cpc % 4u == 0u) ? 4 : 1;
 
-    // ---- the tile: K 16-byte loads per lane, back to back; past the end of the channel a lane re-reads the tile
-    //      base's row start (an element of the same channel: harmless for the extrema, never stored)
+    // ---- the tile (FTile::load: the order of its loads and why)
     float v[K][4];
-    FWalk w = w0;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const unsigned off = w.ro < lim ? w.ro + w.co : 0u;
-#if FLAT_ABL & 4
-        for (int e = 0; e < 4; ++e) v[j][e] = (float)(int)((off >> 4) + (unsigned)e) * 1e-4f - 3.f;      // no loads: synthetic values
-        (void)xb;
-#else
-        ldv_nt<4>(reinterpret_cast<const float*>(xb + off), v[j]);
-#endif
-        w.step(g);
-    }
-    if constexpr (KL > 0) {
-        // the tile's LAST KL steps go straight into LDS: each wave's 64 x 16 bytes land lane-linear at its own 1 KB slot.  Round 6:
-        // as asm behind the register loads (lds_dma16_behind, cnnq_common.hip.h) - with the builtin, which had to be issued
-        // FIRST, the compiler waited for vmcnt(0) before the first use of any register step
-#pragma unroll
-        for (int l = 0; l < KL; ++l) {
-            const unsigned off = w.ro < lim ? w.ro + w.co : 0u;
-            lds_dma16_behind(xb, off, sh_x + (l * TPB + (tid & ~63)) * 4);
-            w.step(g);
-        }
-    }
-    // nothing that consumes a loaded value may be scheduled in between the loads (the scheduler otherwise folds the
-    // first rows into the extrema while it still has loads to issue, and waits for them first)
-    __builtin_amdgcn_sched_barrier(0);
+    t.load(g, x, v, sh_x);
     GRP_STAMP(1);
     float mn[1] = {INFINITY}, mx[1] = {-INFINITY};
     bool nan = false;
-#pragma unroll
-    for (int j = 0; j < K; ++j) lane_acc<1>(v[j], mn, mx, nan);
+    const auto acc = [&](const float (&q)[4], int) { lane_acc<1>(q, mn, mx, nan); };
+    T::template steps<FT_REG>(v, sh_x, acc);
     if constexpr (KL > 0) {
         lds_dma_landed(mn[0]);
-#pragma unroll
-        for (int l = 0; l < KL; ++l) {
-            float t[4];
-            const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
-            t[0] = q.x; t[1] = q.y; t[2] = q.z; t[3] = q.w;
-            lane_acc<1>(t, mn, mx, nan);
-        }
+        T::template steps<FT_LDS>(v, sh_x, acc);
     }
     if (nan) { mn[0] = NAN; mx[0] = NAN; }
     float cmn, cmx;
@@ -1000,81 +1077,37 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_flat
     }
     GRP_STAMP(5);
 
-    // ---- Q/DQ out of the registers.  The walk is repeated, and hidden from the optimiser: it would otherwise keep the
-    //      K offsets of the load phase alive across the meeting (K more registers than the tile leaves: spills)
-    w = w0;
-    asm volatile("" : "+v"(w.ro), "+v"(w.co));
+    // ---- Q/DQ out of the registers and LDS, on a fresh walk (FTile::rewalk)
+    FWalk w = t.rewalk();
     const float zpa[1] = {zp};
     unsigned nzp[1] = {0u};
-    if (__builtin_amdgcn_readfirstlane((int)fast)) {
-        // the channel's values are inside qdq_fast_domain: the exact quotient without the divide, parameters in
-        // scalar registers (one channel per workgroup)
-        const float s_sc = uniform_f(sc), s_rs = uniform_f(1.0f / sc), s_zp = uniform_f(zp);
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
+    // isfast: the channel's values are inside qdq_fast_domain - the exact quotient without the divide, parameters in scalar
+    // registers (one channel per workgroup)
+    const auto store = [&](auto isfast, float a_sc, float a_rs, float a_zp) {
+        constexpr bool FAST = decltype(isfast)::value;
+        T::steps_walk(g, v, sh_x, w, [&](const float (&q)[4], int s) {
             float o[4], cd[4];
+            if constexpr (FAST) {
 #if FLAT_ABL & 8
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { o[e] = v[j][e]; cd[e] = 0.f; }
+                for (int e = 0; e < 4; ++e) { o[e] = q[e]; cd[e] = 0.f; }
 #else
-            qdq4_fast(v[j], s_sc, s_rs, s_zp, qm, o, cd);
+                qdq4_fast(q, a_sc, a_rs, a_zp, qm, o, cd);
 #endif
-            if constexpr (OUT == 2) {
-                if (pkl > 1) sh_pk[j * 256 + tid] = pack4_fast(cd);
-                else if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
             } else {
-                if (w.ro < lim FLAT_ABL_NOSTORE(o)) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = qdq1(q[e], a_sc, a_zp, qm, cd[e]);
             }
-            w.step(g);
-        }
-        if constexpr (KL > 0) {
-#pragma unroll
-            for (int l = 0; l < KL; ++l) {
-                const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
-                const float t[4] = {q.x, q.y, q.z, q.w};
-                float o[4], cd[4];
-                qdq4_fast(t, s_sc, s_rs, s_zp, qm, o, cd);
-                if constexpr (OUT == 2) {
-                    if (pkl > 1) sh_pk[(K + l) * 256 + tid] = pack4_fast(cd);
-                    else if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
-                } else {
-                    if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
-                }
-                w.step(g);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            float o[4], cd[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = qdq1(v[j][e], sc, zp, qm, cd[e]);
             if constexpr (OUT == 2) {
-                if (pkl > 1) sh_pk[j * 256 + tid] = pack4_of(cd);
-                else if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
+                if (pkl > 1) sh_pk[s * 256 + tid] = FAST ? pack4_fast(cd) : pack4_of(cd);
+                else if (t.inside(w)) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
             } else {
-                if (w.ro < lim FLAT_ABL_NOSTORE(o)) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
+                if (t.inside(w) FLAT_ABL_NOSTORE(o)) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
             }
-            w.step(g);
-        }
-        if constexpr (KL > 0) {
-#pragma unroll
-            for (int l = 0; l < KL; ++l) {
-                const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
-                const float t[4] = {q.x, q.y, q.z, q.w};
-                float o[4], cd[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = qdq1(t[e], sc, zp, qm, cd[e]);
-                if constexpr (OUT == 2) {
-                    if (pkl > 1) sh_pk[(K + l) * 256 + tid] = pack4_of(cd);
-                    else if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
-                } else {
-                    if (w.ro < lim) xstore<OUT, 1>(xo, yb, cbb, pbb, w.ro + w.co, o, cd, sh_hist, zpa, nzp);
-                }
-                w.step(g);
-            }
-        }
-    }
+        });
+    };
+    if (__builtin_amdgcn_readfirstlane((int)fast)) store(std::true_type{}, uniform_f(sc), uniform_f(1.0f / sc), uniform_f(zp));
+    else store(std::false_type{}, sc, 0.f, zp);
     if constexpr (OUT == 1) {
         if (xo.hist) xhist_flush<1>(sh_hist, xo.hist, 1 << (num_bits < 8 ? num_bits : 8), zpa, nzp);
     }
@@ -1082,11 +1115,11 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_flat
         if (pkl > 1) {
             __syncthreads();
             if (flags & MMQ_FLAG_PK_PLAIN) {
-                if (pkl == 8) flat_pk_flush<K + KL, 8, false>(g, sh_pk, pbb, f0, n_first, lim);
-                else flat_pk_flush<K + KL, 4, false>(g, sh_pk, pbb, f0, n_first, lim);
+                if (pkl == 8) flat_pk_flush<K, KL, 8, false>(g, t, sh_pk, pbb);
+                else flat_pk_flush<K, KL, 4, false>(g, t, sh_pk, pbb);
             } else {
-                if (pkl == 8) flat_pk_flush<K + KL, 8, true>(g, sh_pk, pbb, f0, n_first, lim);
-                else flat_pk_flush<K + KL, 4, true>(g, sh_pk, pbb, f0, n_first, lim);
+                if (pkl == 8) flat_pk_flush<K, KL, 8, true>(g, t, sh_pk, pbb);
+                else flat_pk_flush<K, KL, 4, true>(g, t, sh_pk, pbb);
             }
         }
     }

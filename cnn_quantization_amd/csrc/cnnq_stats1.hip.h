@@ -178,7 +178,10 @@ __global__ void __launch_bounds__(TPB, (KR + KL == 32 ? GRP_K32_WAVES : 1)) k_st
     }
     if (tid == 0) sh_code = ((flags & MMQ_FLAG_TEST_HOOK) ? 2 : 0) | ((st0 & 1u) ? 4 : 0);
 
-    // ---- the tile: K 16-byte loads per lane, back to back (k_mmq_flat's walk)
+    // ---- the tile: K 16-byte loads per lane, back to back.  This is FTile<KR, KL> of cnnq_group.hip.h (placement, load, steps,
+    //      cold step; the reasons for the order of the loads are written there) in its own words: this kernel's register
+    //      budget moves with every spelling - through FTile its K = 8 instances lose four VGPRs and its 24 + 8 instances gain
+    //      one to seven (profiles/flat_tile.md) - so its text stays as it was measured.  A fix to the tile is made there AND here
     const unsigned f0 = (unsigned)member * (256u * K);
     const unsigned n_first = f0 / g.cpc;
     const unsigned u = f0 + (unsigned)tid;

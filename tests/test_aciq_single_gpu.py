@@ -58,9 +58,19 @@ from _direct import aciq_on_table as oracle_from_device_stats      # noqa: E402 
 
 # flat tiles (56x56, 28x28: one channel per group), row pieces (32x32: cpc = 256), whole channels per workgroup with the
 # exchange over the batch splits (14x14), straddling float4s (7x7), two-level departure counters (many members), row
-# pieces of one channel (64x64: four workgroups per sample row)
+# pieces of one channel (64x64: four workgroups per sample row); (48, 3, 56, 56): the smallest flat plan with K = 32 - five
+# members, the last partly empty, three channels in dispatch blocks of four (the others plan K = 8 and 16)
+K32_FLAT = (48, 3, 56, 56)
 SHAPES = [(40, 6, 56, 56), (33, 5, 28, 28), (24, 3, 32, 32), (70, 12, 14, 14), (130, 24, 7, 7), (8, 4, 112, 112), (64, 37, 14, 14),
-          (6, 3, 64, 64)]
+          (6, 3, 64, 64), K32_FLAT]
+
+
+def test_the_small_shapes_reach_every_flat_tile_height():
+    """(a planner change must not silently un-test a tile height of k_fused_flat)"""
+    ks = {d['K'] for rc, d in (describe(s[0], s[1], s[2] * s[3]) for s in SHAPES) if rc == 0 and d['mode'] == 3}
+    assert ks >= {8, 16, 32}, ks
+    d = describe(K32_FLAT[0], K32_FLAT[1], K32_FLAT[2] * K32_FLAT[3])[1]
+    assert d['mode'] == 3 and d['K'] == 32 and d['Gs'] == 5 and 48 * 784 % (256 * 32) != 0, d
 
 
 @pytest.mark.parametrize('shape', SHAPES)

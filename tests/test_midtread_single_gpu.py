@@ -84,7 +84,10 @@ def hist_counts(hist, mt, C):
     return out
 
 
-SHAPES = [(40, 6, 56, 56), (33, 5, 28, 28), (24, 3, 32, 32), (70, 12, 14, 14), (8, 4, 112, 112), (64, 37, 14, 14), (6, 3, 64, 64)]
+# (48, 3, 56, 56): the smallest flat plan with K = 32 (five members, the last partly empty; tests/test_aciq_single_gpu.py checks
+# the plan) - the other flat shapes here plan K = 8 and 16
+SHAPES = [(40, 6, 56, 56), (33, 5, 28, 28), (24, 3, 32, 32), (70, 12, 14, 14), (8, 4, 112, 112), (64, 37, 14, 14), (6, 3, 64, 64),
+          (48, 3, 56, 56)]
 
 
 @pytest.mark.parametrize('shape', SHAPES)
