@@ -53,6 +53,7 @@
 #include "cnnq_half_stats.hip.h"
 #include "cnnq_half_bcorr.hip.h"
 #include "cnnq_half_aciq.hip.h"
+#include "cnnq_half_midtread.hip.h"
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_nhwc_collect.hip.h"
@@ -1909,6 +1910,103 @@ int cnnq_pc_aciq_qdq_dt(const void* x, void* y, int dtype, int64_t N, int64_t C,
     if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
     if (rc) return rc;
     return h_qdq(x, y, dtype, N, C, HW, qp, nullptr, HArgs{}, st);
+}
+
+// ---- config 5 (mid-tread, bin allocation, entropy) on contiguous bf16 / fp16 activations (cnnq_half_midtread.hip.h) ------------
+// ws, doubles: cnnq_pc_stats_dt's records (the tables stay outside); fp32 has no plan here: 0
+size_t cnnq_pc_midtread_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype) {
+    return dtype == CNNQ_DTYPE_F32 ? 0 : cnnq_pc_stats_dt_workspace(N, C, HW, dtype);
+}
+
+// the route word of a bf16 / fp16 tensor at piece width w: 3 - pass A, merge and k_mt_params<GUESS>, then k_h_mt_whole / 2 - the
+// chain / 0 - a class of layer that did not win against the upcast route and stays there (h_mt_native; the call itself runs
+// every class, on the chain)
+static int h_mt_route(int64_t N, int64_t C, int64_t HW, int dtype, int w, bool hist, int allow_single_launch) {
+    if (allow_single_launch && h_mt_whole_fits(N, HW, w) && (allow_single_launch > 1 || h_mt_whole_wins(N, C, HW, dtype, hist))) return 3;
+    return h_mt_native(N, C, HW, dtype, hist) ? 2 : 0;
+}
+
+// Which launches cnnq_pc_midtread_dt makes for this geometry (host only): out = {piece width W, batch splits S, column splits of
+// the statistics launches, route (h_mt_route)}.  fp32: CNNQ_ENOTSUP, as the call.
+int cnnq_pc_route_midtread_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int hist, int allow_single_launch,
+                              int32_t out[4]) {
+    const HPlan p(N, C, HW, dtype, out && pow2(align_bytes));
+    if (p.rc) return p.rc;
+    if (dtype == CNNQ_DTYPE_F32) return CNNQ_ENOTSUP;
+    const int w = h_piece(HW, (uintptr_t)align_bytes, 0);
+    out[0] = w;
+    out[1] = p.S;
+    out[2] = p.cs;
+    out[3] = h_mt_route(N, C, HW, dtype, w, hist != 0, allow_single_launch);
+    return 0;
+}
+
+static int h_mt_qdq(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, int w, const float* mt, uint64_t* hist,
+                    hipStream_t st) {
+    const HGeo g = h_geo_mt(N, C, HW, w, hist != nullptr);
+    return h_launch(dtype, w, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
+        with_bool(hist != nullptr, [&](auto h) {
+            using P = decltype(pc);
+            hipLaunchKernelGGL((k_h_mt_qdq<typename P::T, P::W, decltype(h)::value>), dim3((unsigned)(C * g.S)), dim3(TPB), 0, st, xh, yh, g,
+                               mt, u64p(hist));
+        });
+    });
+}
+
+// iq.py:202-224 on x[N][C][HW] of bf16 / fp16 with a given table mt (cnnq_pc_midtread_params, clip = 1), and the codes counted
+// into hist (zeroed by the caller): one launch
+int cnnq_pc_midtread_qdq_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* mt, uint64_t* hist,
+                            void* stream) {
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    const uintptr_t es = f32 ? 4 : 2;
+    const HPlan p(N, C, HW, dtype, x && y && x != y && mt && !misaligned(mt, 4) && !misaligned(hist, 8) && !misaligned(x, es) &&
+                                       !misaligned(y, es));
+    if (p.rc) return p.rc;
+    if (f32) return cnnq_pc_midtread_qdq(static_cast<const float*>(x), static_cast<float*>(y), N, C, HW, mt, 1, nullptr, hist, stream);
+    return h_mt_qdq(x, y, dtype, N, C, HW, h_piece(HW, (uintptr_t)h_align(x, y), 0), mt, hist, hs(stream));
+}
+
+// iq.py:170-225 (per-channel statistics, bin allocation eq. 10, Laplace clipping, mid-tread Q/DQ) on x[N][C][HW] of bf16 / fp16:
+// k_h_moments -> k_combine -> k_h_absdev -> k_combine_dev -> k_mt_params -> k_h_mt_qdq (route 2), or k_h_moments -> k_combine ->
+// k_mt_params<GUESS> -> k_h_mt_whole (route 3)
+int cnnq_pc_midtread_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, double target, int sym, const double* tables,
+                        int ntab, void* ws, float* stats, float* mt, uint64_t* hist, int allow_single_launch, void* stream) {
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    const uintptr_t es = f32 ? 4 : 2;
+    const bool ok = x && y && x != y && tables && ntab >= 2 && ws && stats && mt && !misaligned(ws, 8) && !misaligned(tables, 8) &&
+                    !misaligned(stats, 4) && !misaligned(mt, 4) && !misaligned(hist, 8) && !misaligned(x, es) && !misaligned(y, es) &&
+                    target - target == 0.;                                            // (not NaN or infinite)
+    const HPlan p(N, C, HW, dtype, ok);
+    if (p.rc) return p.rc;
+    if (f32) return CNNQ_ENOTSUP;                    // fp32 callers have cnnq_pc_midtread_qdq_single and the chain
+    hipStream_t st = hs(stream);
+    const int w = h_piece(HW, (uintptr_t)h_align(x, y), 0);
+    const int route = h_mt_route(N, C, HW, dtype, w, hist != nullptr, allow_single_launch);
+    if (hist) {
+        const size_t words = (size_t)CNNQ_MT_HIST_WORDS(C);
+        hipLaunchKernelGGL(k_h_mt_zero, dim3((unsigned)((words + 4 * TPB - 1) / (4 * TPB))), dim3(TPB), 0, st, u64p(hist), words);
+        if (const int rc = launch_status()) return rc;
+    }
+    const MtCfg mcfg{target, 1, sym ? 1 : 0};
+    if (route == 3) {
+        int rc = cnnq_pc_stats_dt(x, dtype, N, C, HW, 0, 0, 0, ws, nullptr, stats, stream);
+        if (!rc) rc = launch_mt_guess(stats, C, mcfg, tables, ntab, mt, st);
+        if (rc) return rc;
+        const HGeo g = h_geo(N, C, HW, w, 1, 1);
+        const HMtArgs a{mcfg, stats, mt, u64p(hist)};
+        return h_launch(dtype, w, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
+            with_bool(hist != nullptr, [&](auto h) {
+                using P = decltype(pc);
+                if constexpr (P::W > 1)
+                    hipLaunchKernelGGL((k_h_mt_whole<typename P::T, P::W, h_whole_k<P::W>(), decltype(h)::value>), dim3((unsigned)C),
+                                       dim3(HTPB), 0, st, xh, yh, g, a);
+            });
+        });
+    }
+    int rc = cnnq_pc_stats_dt(x, dtype, N, C, HW, 1, 0, 0, ws, nullptr, stats, stream);
+    if (!rc) rc = cnnq_pc_midtread_params(stats, C, target, 1, sym, tables, ntab, mt, stream);
+    if (rc) return rc;
+    return h_mt_qdq(x, y, dtype, N, C, HW, w, mt, hist, st);
 }
 
 int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream) {

@@ -270,6 +270,8 @@ class TruncationOpManagerInference:
         # the product's quantizers quantize contiguous bf16 / fp16 activations under dynamic ACIQ clipping where they lie
         # (IntQuantizer._half_aciq)
         q.half_dynamic = True
+        # ... and under mid-tread quantization (IntQuantizer._midtread_route)
+        q.half_midtread = True
         return q
 
     def _fill(self, qtype, qparams, qweight):

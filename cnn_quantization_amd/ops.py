@@ -95,7 +95,8 @@ def _half_only(what, reason):
 
 # switches, read ONCE at import (not per hot call); reload_switches() re-reads them after the environment changed (tests, tools)
 def reload_switches():
-    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC, _HALF_TABLE, _HALF_ACIQ
+    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC, _HALF_TABLE, _HALF_ACIQ, _HALF_MIDTREAD
+    _HALF_MIDTREAD = os.environ.get('CNNQ_HALF_MIDTREAD', '1') != '0'  # 0: mid-tread on contiguous half activations takes the upcast route (A/B)
     _HALF_ACIQ = os.environ.get('CNNQ_HALF_ACIQ', '1') != '0'          # 0: dynamic ACIQ on contiguous half activations takes the upcast route (A/B)
     _HALF_TABLE = os.environ.get('CNNQ_HALF_TABLE', '1') != '0'        # 0: calibrated per-channel half activations take the upcast route (A/B)
     _NHWC = os.environ.get('CNNQ_NHWC', '1') != '0'                    # 0: channels_last tensors take the NCHW copy route (A/B)
@@ -209,13 +210,13 @@ _NHWC_WS = {'nhwc': 'cnnq_pc_nhwc_workspace', 'aciq_nhwc': 'cnnq_pc_aciq_nhwc_wo
 
 
 _HALF_WS = {'stats_half': 'cnnq_pc_stats_dt_workspace', 'bcorr_half': 'cnnq_pc_qdq_bcorr_dt_workspace',
-            'aciq_half': 'cnnq_pc_aciq_dt_workspace'}
+            'aciq_half': 'cnnq_pc_aciq_dt_workspace', 'midtread_half': 'cnnq_pc_midtread_dt_workspace'}
 
 
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
     arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc', 'stats_nhwc': N = rows; 'rows':
-    N = rows, C = their length; 'pt_clip': N = elements; 'stats_half', 'bcorr_half', 'aciq_half': the dtype code).  0 from the library: no plan for
+    N = rows, C = their length; 'pt_clip': N = elements; 'stats_half', 'bcorr_half', 'aciq_half', 'midtread_half': the dtype code).  0 from the library: no plan for
     the geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
@@ -2184,6 +2185,68 @@ def mid_tread_qdq_nhwc(x, target, sym, want_entropy=False, stats=None, out=None,
                                        ws, tp, tp + L.NSTAT * C * 4, _ptr(hist), st)
         if rc:
             L.check(rc, 'cnnq_pc_midtread_nhwc')
+    return _mt_result(y, _mt_entropy_here(x, hist, mt, C, st) if want_entropy else None,
+                      parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
+
+
+_MIDTREAD_HALF_NATIVE = {}
+
+
+def _midtread_half_native(N, C, HW, dtype, hist=False):
+    """The route word of cnnq_pc_route_midtread_dt's report for this class of contiguous bf16 / fp16 layer, with (hist) or without
+    the code histogram: 3 - pass A and the bin allocation in front of the resident launch, 2 - the chain, 0 - a class that measured
+    slower native than through the upcast and is sent back there.  The quantizer (_midtread_route) and the tests patch the function
+    and empty the cache by name."""
+    return _half_route_word(_MIDTREAD_HALF_NATIVE.setdefault(bool(hist), {}), int, 'cnnq_pc_route_midtread_dt', N, C, HW, dtype,
+                            int(bool(hist)), 1)
+
+
+def mid_tread_qdq_half(x, target, sym, want_entropy=False, stats=None, out=None, want_parts=False, single_launch=None):
+    """Config 5 with clipping (iq.py:170-225: mid-tread quantization with per-channel bin allocation; want_entropy: the entropy of
+    the codes, -me) on a contiguous 4-D bf16 / fp16 activation, on the storage as it is:
+    cnnq_pc_midtread_dt - pass A, the bin allocation and one launch that keeps a channel in registers for b, the step size, the
+    clamp bounds and the Q/DQ with the code histogram where the channel's batch population fits, else the chain of
+    cnnq_pc_stats_dt, cnnq_pc_midtread_params and cnnq_pc_midtread_qdq_dt; one host call, one cached workspace - or, with `stats`
+    ([NSTAT, C]), cnnq_pc_midtread_params on that table and the table-driven pass.  8 B/elem as a chain, 6 resident.  y has x's
+    dtype.  Returns what mid_tread_qdq_nhwc returns: (y, entropy or None [, dict(stats, mt, hist)]); inside an entropy_batch block
+    the entropy is filled by the block's one launch.  single_launch: None - the route function's choice; 0 - the chain; 2 - the
+    resident form wherever the channel fits (the chain elsewhere), for tests and A/B.  One GPU: the statistics are this tensor's.
+    Anything else - a CPU tensor, float32, not 4-D, not contiguous - raises: nothing is copied or upcast here."""
+    what = 'mid_tread_qdq_half'
+    x, N, C, HW, dt, st = _admit_half(x, what, 'mid_tread_qdq')
+    lib = L.load()
+    tabs = _midtread_tables(x.device)
+    if stats is not None:
+        if not _is_table(stats, torch.float32, (L.NSTAT, C), x.device):
+            raise L.CnnqError('%s: stats must be a contiguous float32 [%d, %d] device table' % (what, L.NSTAT, C))
+        y = _out_like(x, out)
+        mt = torch.empty((L.NMT, C), dtype=torch.float32, device=x.device)
+        L.check(lib.cnnq_pc_midtread_params(_ptr(stats), C, float(target), 1, int(bool(sym)), _ptr(tabs), tabs.shape[1], _ptr(mt), st),
+                'cnnq_pc_midtread_params')
+        hist = torch.zeros(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None
+        rc = lib.cnnq_pc_midtread_qdq_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, _ptr(mt), _ptr(hist), st)
+        if rc:
+            L.check(rc, 'cnnq_pc_midtread_qdq_dt')
+    else:
+        if single_launch not in (None, 0, 1, 2):
+            raise L.CnnqError('%s: single_launch must be None, 0, 1 or 2, got %r' % (what, single_launch))
+        y = _out_like(x, out)
+        nbytes = _ws_bytes('midtread_half', N, C, HW, dt)
+        hist = torch.empty(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None     # zeroed by the call
+        if want_parts or want_entropy:
+            # (the entropy launch reads mt behind the call - at the end of the block inside an entropy_batch)
+            out_tabs = torch.empty((L.NSTAT + L.NMT, C), dtype=torch.float32, device=x.device)
+            stats, mt = out_tabs[:L.NSTAT], out_tabs[L.NSTAT:]
+            ws, tp = _scratch(x, 'midtread_half', nbytes, st).data_ptr(), out_tabs.data_ptr()
+        else:
+            # the tables nobody outside the call reads follow the records in the cached workspace
+            ws = _scratch(x, 'midtread_half', nbytes + (L.NSTAT + L.NMT) * C * 4, st).data_ptr()
+            tp = ws + nbytes
+            mt = None
+        rc = lib.cnnq_pc_midtread_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, float(target), int(bool(sym)), _ptr(tabs), tabs.shape[1],
+                                     ws, tp, tp + L.NSTAT * C * 4, _ptr(hist), 1 if single_launch is None else int(single_launch), st)
+        if rc:
+            L.check(rc, 'cnnq_pc_midtread_dt')
     return _mt_result(y, _mt_entropy_here(x, hist, mt, C, st) if want_entropy else None,
                       parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
 

@@ -114,6 +114,9 @@ class IntQuantizer:
         # the route 'half_aciq' (dynamic ACIQ on a contiguous bf16 / fp16 activation) is opt-in per object:
         # the inference manager sets this on the quantizers it builds; one constructed directly keeps the upcast route
         self.half_dynamic = False
+        # the route 'half_midtread' (mid-tread on a contiguous bf16 / fp16 activation): opt-in per object in
+        # the same way, and for the same reason
+        self.half_midtread = False
 
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
@@ -240,12 +243,20 @@ class IntQuantizer:
 
     def _midtread_route(self, tensor, att):
         """The two mid_tread_quantize_activation methods: with clipping (the per-channel one is also __call__'s branch at clipping
-        'no', which has no route) and no KLD, per channel on channels_last with no correction pending, per tensor on flat storage."""
+        'no', which has no route) and no KLD, per channel with no correction pending on channels_last or on a contiguous half tensor
+        (opt-in: half_midtread), per tensor on flat storage."""
         pc, one_gpu, _, pending = self._facts(tensor, att)
         if not (att('mtd_quant') and one_gpu) or att('clipping') == 'no' or att('kld'):
             return None
         if pc:
-            return 'nhwc_midtread' if not pending and _dense_nhwc(tensor) else None
+            if pending:
+                return None
+            if _dense_nhwc(tensor):
+                return 'nhwc_midtread'
+            if (self.half_midtread and ops._HALF_MIDTREAD and _storage(tensor) == 'half'
+                    and ops._midtread_half_native(*ops.geometry(tensor), tensor.dtype, bool(att('measure_entropy'))) != 0):
+                return 'half_midtread'
+            return None
         return 'flat_midtread' if self._flat_tensor(tensor) else None
 
     # The predicates of the routes, as tests, tools and DESIGN.md know them: each is a view of the decision above.  _asked is the route
@@ -515,9 +526,14 @@ class IntQuantizer:
 
     def mid_tread_quantize_activation_per_channel(self, tensor, id):
         """iq.py:170-183."""
-        if self._midtread_route(tensor, self._att()) == 'nhwc_midtread':
+        route = self._midtread_route(tensor, self._att())
+        if route == 'nhwc_midtread':
             # a dense channels_last activation: quantized where it lies, the result keeps layout and dtype
             out, entropy = ops.mid_tread_qdq_nhwc(tensor, self.bit_alloc_target_act, sym=not self._positive,
+                                                  want_entropy=self.measure_entropy)
+        elif route == 'half_midtread':
+            # a contiguous bf16 / fp16 activation: quantized where it lies, the result keeps the dtype
+            out, entropy = ops.mid_tread_qdq_half(tensor, self.bit_alloc_target_act, sym=not self._positive,
                                                   want_entropy=self.measure_entropy)
         else:
             out, entropy = ops.mid_tread_qdq(tensor, self.bit_alloc_target_act, clip=True, sym=not self._positive,

@@ -825,6 +825,47 @@ int cnnq_pc_route_aciq_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align
 int cnnq_pc_aciq_qdq_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws,
                         float* stats, float* qp, float* diag, int allow_single_launch, void* stream);
 
+/* Config 5 (mid-tread quantization with per-channel bin allocation and Laplace clipping, optionally the histogram of its codes:
+ * -c laplace -baa -mtq [-me]; int_quantizer.py:170-183 statistics and dispatch, 128-145 and 185-214 bin allocation, step sizes
+ * and clamp bounds, 202-224 Q/DQ) on CONTIGUOUS bf16 / fp16 activations x[N][C][HW], on the storage as it lies: no fp32 copy.
+ * Counterpart of cnnq_pc_midtread_nhwc; the rows are cut into pieces as for cnnq_pc_stats_dt (W = 8 / 4 / 2 / 1 from HW and the
+ * alignment x and y share: every (HW, alignment) has a route); a workgroup owns one channel.
+ * cnnq_pc_midtread_qdq_dt (iq.py:202-224): the table-driven pass with mt from cnnq_pc_midtread_params (clip = 1), one launch.
+ * hist: NULL, or CNNQ_MT_HIST_WORDS(C) words ZEROED BY THE CALLER, read by cnnq_midtread_entropy[_batch].  Given mt, y and every
+ * word of hist but the split of the window counts over the replica tables are, bit for bit, cnnq_pc_midtread_qdq's (clip = 1) on
+ * x.float(), y rounded once into the element type.  CNNQ_DTYPE_F32 forwards to cnnq_pc_midtread_qdq(..., clip = 1, codes = NULL, ...).
+ * cnnq_pc_midtread_dt (iq.py:170-225): ONE host call; stats[CNNQ_NSTAT][C] and mt[CNNQ_NMT][C] are OUTPUTS, hist is NULL or is
+ * zeroed here.  Routes:
+ *   2. the chain: cnnq_pc_stats_dt with b (four launches), cnnq_pc_midtread_params, the table-driven pass - 8 B/elem;
+ *   3. pass A and its merge, omega and the clipping multiplier from the std alone, then one launch of one 1024-lane workgroup
+ *      per channel that keeps the channel in registers: b, step size, clamp bounds, Q/DQ (and the histogram) - 6 B/elem.  Only
+ *      where N * HW <= 131072 and W >= 2.  There is no route without pass A: the bin allocation couples all channels.
+ * Promised on both routes: stats is written completely (KURT and STD_POS zero), rows MIN / MAX exact (a NaN element makes them
+ * NaN), MEAN / STD / B within the statistics tier of fp64; given that table, rows OMEGA / ALPHA / DELTA / CMIN / CMAX of mt are
+ * cnnq_pc_midtread_params', and y and hist are cnnq_pc_midtread_qdq_dt's on mt, bit for bit.  Row WSTART: route 2
+ * cnnq_pc_midtread_params'; route 3 the bound a Laplace channel (b = std / sqrt 2) would have - an integer, >= -CNNQ_MT_HIST_BINS / 2,
+ * the same in every channel; only the speed of the histogram depends on it.  CNNQ_DTYPE_F32: CNNQ_ENOTSUP, nothing enqueued
+ * (fp32 has cnnq_pc_midtread_qdq_single and the chain).
+ * cnnq_pc_midtread_dt_workspace: bytes of `ws` - cnnq_pc_stats_dt's records, which do not depend on the alignment or the route (0
+ * on bad arguments, fp32, or a geometry beyond cnnq_pc_groups' limits).
+ * cnnq_pc_route_midtread_dt (host only, nothing enqueued, a function of its arguments alone): out = {piece width W, batch splits S,
+ * column splits of the statistics launches, route}; route 2 / 3 as above, 0 - a class of layer that did not measure faster than
+ * the upcast route and is left there by callers that have the choice (cnnq_pc_midtread_dt itself runs every class, on route 2).
+ * hist: whether the codes are counted.  allow_single_launch: 0 - never route 3; 1 - where it measured faster than route 2; 2 -
+ * wherever the channel fits (tests, A/B).  align_bytes: the power of two that divides x and y (<= 16 is what matters).  fp32:
+ * CNNQ_ENOTSUP.
+ * A bad dtype, N, C or HW < 1, a NULL x / y / mt (/ tables / ws / stats), ntab < 2, a target that is not finite, a misaligned ws /
+ * tables / stats / mt / hist, an x or y not aligned to its element size, x == y, a NULL out or an align_bytes that is not a power
+ * of two return CNNQ_EINVAL, a geometry beyond cnnq_pc_groups' limits that function's code - before anything touches the device.
+ * Re-entrant, allocate nothing, no host synchronisation, graph-capturable. */
+size_t cnnq_pc_midtread_dt_workspace(int64_t N, int64_t C, int64_t HW, int dtype);
+int cnnq_pc_route_midtread_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int hist, int allow_single_launch,
+                              int32_t out[4]);
+int cnnq_pc_midtread_qdq_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* mt, uint64_t* hist,
+                            void* stream);
+int cnnq_pc_midtread_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, double target, int sym, const double* tables,
+                        int ntab, void* ws, float* stats, float* mt, uint64_t* hist, int allow_single_launch, void* stream);
+
 /* The statistics of FEW, VERY LONG rows over flat storage - the per-tensor calibration table of statistic_manager.py:55-96
  * (rows = 1: the whole tensor) and the per-sample sums of squares of distance_stats.py:22-33 (rows = N: the samples) - for fp32 /
  * bf16 / fp16 elements, on the storage as it lies: x is viewed as [rows][len], every row contiguous and the rows back to back.
