@@ -166,10 +166,7 @@ __device__ __forceinline__ bool mt_fast_domain(float vmin, float vmax, float del
 // one element: code (iq.py:202-214) and dequantized value (iq.py:224)
 template <bool FAST>
 __device__ __forceinline__ float mt_qdq1(float x, float d, float rd, float lo, float hi, float& code) {
-    float t = rintf(FAST ? mt_quot_fast(x, d, rd) : x / d);
-    // torch.min(t, hi) = t < hi ? t : hi and torch.max(t, lo) = t > lo ? t : lo, NaN kept (the bound wins ties)
-    t = (t < hi || t != t) ? t : hi;
-    t = (t > lo || t != t) ? t : lo;
+    const float t = mt_code<true>(FAST ? mt_quot_fast(x, d, rd) : x / d, lo, hi);
     code = t;
     return t * d;
 }
@@ -263,25 +260,11 @@ __device__ __forceinline__ void mt_counts_of(unsigned nni, unsigned nhi_raw, boo
     nlo = nni - nhi;                                // what is not an integer and not hi was clamped to lo
 }
 inline __device__ bool mt_count_fast_ok(float lo, float hi) { return fabsf(lo) < 0x1p24f && fabsf(hi) < 0x1p24f; }
-// end of the workgroup: the LDS window into the replica window (blockIdx picks the replica)
+// end of the workgroup: the LDS window into the replica window (blockIdx picks the replica) - k_mt_qdq's fold over MTF_REP copies
 __device__ __forceinline__ void mt_flush(unsigned* sh_hist, unsigned long long* hist, int C, int wstart) {
-    const int tid = threadIdx.x;
     __syncthreads();
     if (MT_CNT_ABL & 2) return;
-    unsigned long long* rep = hist + MT_NB + 2 + 2 * (size_t)C + (size_t)(blockIdx.x & (MT_GR - 1)) * MT_W;
-    for (int i = tid; i < MT_W; i += TPB) {
-        unsigned tot = 0;
-#pragma unroll 8
-        for (int r = 0; r < MTF_REP; ++r) tot += sh_hist[(unsigned)i * MTF_REP + ((unsigned)(r + tid) & (MTF_REP - 1))];
-        if (tot) {
-            if (wstart + i < MT_NB / 2) {
-                atomicAdd(&rep[i], (unsigned long long)tot);
-            } else {
-                atomicAdd(&hist[MT_NB + 1], (unsigned long long)tot);
-                atomicAdd(&hist[mt_flag_word(C)], 1ull);
-            }
-        }
-    }
+    mt_hist_fold<TPB, MTF_REP>(sh_hist, hist, C, wstart, (int)blockIdx.x);
 }
 
 // ---- flat tiles (the geometry of k_mmq_flat: a group is ONE channel, a member 256 (K + KL) consecutive float4 of it) -----

@@ -41,65 +41,34 @@ struct HMtCount {
     unsigned nzero = 0, nhi = 0, nlo = 0;
 };
 
-constexpr int H_MT_WORDS = MT_W * MT_REP;
-__device__ __forceinline__ unsigned h_mt_hidx(unsigned kk, int tid) { return kk * MT_REP + (unsigned)(tid & (MT_REP - 1)); }
-
-// the workgroup's LDS table of the window bins and its two clamp counters, zeroed (one barrier)
+// the workgroup's LDS table of the window bins (mt_hist_zero) and its two clamp counters, zeroed (one barrier)
 template <int NT>
-__device__ __forceinline__ void h_mt_hist_init(unsigned (&sh_hist)[H_MT_WORDS], unsigned (&sh_c)[2]) {
-    for (int i = (int)threadIdx.x; i < H_MT_WORDS; i += NT) sh_hist[i] = 0u;
+__device__ __forceinline__ void h_mt_hist_init(unsigned (&sh_hist)[MT_WORDS], unsigned (&sh_c)[2]) {
+    mt_hist_zero<NT>(sh_hist);
     if (threadIdx.x < 2) sh_c[threadIdx.x] = 0u;
     __syncthreads();
 }
 
 // one piece through y = clamp(rint(x / delta), c_min, c_max) * delta (iq.py:202-224) on the upconverted value, rounded once into
-// the element type: k_mt_qdq<CLIP = true>'s arithmetic, statement for statement.  HIST: its update too - an integer code inside
-// the window is one LDS atomic, code 0 and the clamps to a non-integer bound are carry adds in registers, everything else (rare)
-// goes to global memory at once.  The copy is kept for the reason cnnq_nhwc_midtread.hip.h gives: who changes one changes the
-// others, and tests/test_half_midtread_gpu.py compares the histograms word for word.
+// the element type.  The code and, with HIST, its count are k_mt_qdq<CLIP = true>'s own definitions (mt_code, mt_hist_count in
+// cnnq_midtread.hip.h); a NaN goes to the channel's c_min counter, here the lane's own.
 template <class T, int W, bool HIST>
 __device__ __forceinline__ void h_mt_piece(uint16_t (&e)[W], const HMtChan& ch, HMtCount& n, unsigned* __restrict__ sh_hist,
                                            unsigned long long* __restrict__ hist, int C) {
-    const int tid = (int)threadIdx.x;
 #pragma unroll
     for (int i = 0; i < W; ++i) {
-        float t = rintf(h_up(T{}, e[i]) / ch.d);                 // iq.py:202-203
-        // torch.min(t, hi) = t < hi ? t : hi and torch.max(t, lo) = t > lo ? t : lo, NaN kept (the bound wins ties:
-        // max(-0, +0) is +0, iq.py:213-214)
-        t = (t < ch.hi || t != t) ? t : ch.hi;
-        t = (t > ch.lo || t != t) ? t : ch.lo;
+        const float t = mt_code<true>(h_up(T{}, e[i]) / ch.d, ch.lo, ch.hi);
         e[i] = h_down(T{}, t * ch.d);                            // iq.py:224
-        if constexpr (HIST) {
-            const bool z = (t == 0.f);
-            const bool at_hi = ch.hi_ni && t == ch.hi;
-            const bool at_lo = ch.lo_ni && t == ch.lo && !at_hi;   // (c_min == c_max: ONE value, counted once)
-            n.nzero += z ? 1u : 0u;
-            n.nhi += at_hi ? 1u : 0u;
-            n.nlo += at_lo ? 1u : 0u;
-            const int k = (int)t;                                // saturating; NaN -> 0
-            const unsigned kk = (unsigned)(k - ch.wstart);
-            const bool fast = ((float)k == t) && kk < (unsigned)MT_W;
-            if (fast && !z) {
-                atomicAdd(&sh_hist[h_mt_hidx(kk, tid)], 1u);
-            } else if (!(z || at_hi || at_lo)) {                 // rare
-                if (t == rintf(t)) {                             // integer code outside the window (or inf)
-                    if (t >= (float)(-MT_NB / 2) && t < (float)(MT_NB / 2)) atomicAdd(&hist[(int)t + MT_NB / 2], 1ull);
-                    else atomicAdd(&hist[t < 0.f ? MT_NB : MT_NB + 1], 1ull);
-                    atomicAdd(&hist[mt_flag_word(C)], 1ull);     // the global bins are in use
-                } else {
-                    n.nlo += 1u;                                 // NaN: the channel's c_min counter
-                }
-            }
-        }
+        if constexpr (HIST)
+            mt_hist_count<true>(t, ch.lo, ch.hi, ch.lo_ni, ch.hi_ni, ch.wstart, sh_hist, hist, C, n.nzero, n.nhi, n.nlo, [&] { n.nlo += 1u; });
     }
 }
 
-// What a workgroup of NT lanes hands over at its end (k_mt_qdq's flush rules): its count of code 0 into the window (or, outside
-// it, the global bins and the flag word), one atomic per live window bin into replica table `rep`, and - the workgroup lies in
-// one channel, so the lanes' two clamp counters are folded: the xor tree inside the wave, the waves through LDS - one atomic per
-// bound that was hit.
+// What a workgroup of NT lanes hands over at its end: its count of code 0 and the live window bins into replica table `rep`
+// (mt_hist_zero_code, mt_hist_fold), and - the workgroup lies in one channel, so the lanes' two clamp counters are folded: the xor
+// tree inside the wave, the waves through LDS - one atomic per bound that was hit.
 template <int NT>
-__device__ __forceinline__ void h_mt_flush(unsigned (&sh_hist)[H_MT_WORDS], unsigned (&sh_c)[2], HMtCount n, const HMtChan& ch, int c, int C,
+__device__ __forceinline__ void h_mt_flush(unsigned (&sh_hist)[MT_WORDS], unsigned (&sh_c)[2], HMtCount n, const HMtChan& ch, int c, int C,
                                            unsigned long long* __restrict__ hist, int rep_id) {
     const int tid = (int)threadIdx.x;
 #pragma unroll
@@ -111,35 +80,13 @@ __device__ __forceinline__ void h_mt_flush(unsigned (&sh_hist)[H_MT_WORDS], unsi
         if (n.nlo) atomicAdd(&sh_c[0], n.nlo);
         if (n.nhi) atomicAdd(&sh_c[1], n.nhi);
     }
-    if (n.nzero) {
-        const int kk = -ch.wstart;
-        if (kk >= 0 && kk < MT_W) {
-            atomicAdd(&sh_hist[h_mt_hidx((unsigned)kk, tid)], n.nzero);
-        } else {
-            // code 0 lies outside the window: its count goes to the global bins, and the flag word must say so
-            atomicAdd(&hist[MT_NB / 2], (unsigned long long)n.nzero);
-            atomicAdd(&hist[mt_flag_word(C)], 1ull);
-        }
-    }
+    mt_hist_zero_code(sh_hist, hist, C, ch.wstart, n.nzero);
     __syncthreads();
     if (tid == 0) {
         if (sh_c[0]) atomicAdd(&hist[MT_NB + 2 + c], (unsigned long long)sh_c[0]);
         if (sh_c[1]) atomicAdd(&hist[MT_NB + 2 + C + c], (unsigned long long)sh_c[1]);
     }
-    unsigned long long* rep = hist + MT_NB + 2 + 2 * (size_t)C + (size_t)(rep_id & (MT_GR - 1)) * MT_W;
-    for (int i = tid; i < MT_W; i += NT) {
-        unsigned tot = 0;
-#pragma unroll
-        for (int r = 0; r < MT_REP; ++r) tot += sh_hist[h_mt_hidx((unsigned)i, r + tid)];
-        if (tot) {
-            if (ch.wstart + i < MT_NB / 2) {
-                atomicAdd(&rep[i], (unsigned long long)tot);
-            } else {
-                atomicAdd(&hist[MT_NB + 1], (unsigned long long)tot);
-                atomicAdd(&hist[mt_flag_word(C)], 1ull);
-            }
-        }
-    }
+    mt_hist_fold<NT>(sh_hist, hist, C, ch.wstart, rep_id);
 }
 
 // The table-driven pass: k_h_qdq's tiling - a workgroup is one (channel, batch split) of whole rows, W = 8 / 4 / 2 / 1, x read and
@@ -149,7 +96,7 @@ __device__ __forceinline__ void h_mt_flush(unsigned (&sh_hist)[H_MT_WORDS], unsi
 template <class T, int W, bool HIST>
 __global__ void __launch_bounds__(TPB) k_h_mt_qdq(const uint16_t* __restrict__ x, uint16_t* __restrict__ y, const HGeo g,
                                                   const float* __restrict__ mt, unsigned long long* __restrict__ hist) {
-    __shared__ unsigned sh_hist[HIST ? H_MT_WORDS : 1];
+    __shared__ unsigned sh_hist[HIST ? MT_WORDS : 1];
     __shared__ unsigned sh_c[2];
     if constexpr (HIST) h_mt_hist_init<TPB>(sh_hist, sh_c);
     const HPart t = h_part<W, false>(g, (int)gridDim.x - 1 - (int)blockIdx.x);
@@ -196,7 +143,7 @@ template <class T, int W, int K, bool HIST>
 __global__ void __launch_bounds__(HTPB) k_h_mt_whole(const uint16_t* __restrict__ x, uint16_t* __restrict__ y, const HGeo g,
                                                      const HMtArgs a) {
     __shared__ double l_b[1][HTPB / 64];
-    __shared__ unsigned sh_hist[HIST ? H_MT_WORDS : 1];
+    __shared__ unsigned sh_hist[HIST ? MT_WORDS : 1];
     __shared__ unsigned sh_c[2];
     const int c = (int)blockIdx.x;
     const int C = g.C;

@@ -127,19 +127,114 @@ __global__ void __launch_bounds__(PTPB) k_mt_params(const float* __restrict__ st
 // register) and a flush of one atomic per live bin into one of MT_GR replica tables (by workgroup id), which keeps
 // the same-address chains short.  Codes outside the window go to the global bins directly (correct, slow, rare: the
 // window starts at the tensor's smallest clamp bound and a channel has ~2^target bins).
+//
+// These rules are written once, below, for every kernel that counts into this histogram from short tiles - k_mt_qdq here,
+// k_cl_mt_qdq (cnnq_nhwc_midtread.hip.h), k_h_mt_qdq / k_h_mt_whole (cnnq_half_midtread.hip.h): mt_code is the code of one
+// element, mt_hist_count its count, mt_hist_zero / mt_hist_zero_code / mt_hist_fold the LDS table's life.  What differs per
+// layout - where a lane's clamp counters are handed over, and where a NaN is counted - stays with each kernel.
+
+// the code of the quotient q = x / delta (iq.py:202-214); the caller multiplies by delta (iq.py:224)
+template <bool CLIP>
+__device__ __forceinline__ float mt_code(float q, float lo, float hi) {
+    float t = rintf(q);                              // iq.py:202-203
+    if constexpr (CLIP) {
+        // torch.min(t, hi) = t < hi ? t : hi and torch.max(t, lo) = t > lo ? t : lo, NaN kept
+        // (the bound wins ties: max(-0, +0) is +0, iq.py:213-214)
+        t = (t < hi || t != t) ? t : hi;
+        t = (t > lo || t != t) ? t : lo;
+    }
+    return t;
+}
+
+// the workgroup's LDS table of the window bins: MT_REP copies of a bin, by lane
+constexpr int MT_WORDS = MT_W * MT_REP;
+template <int REP = MT_REP>
+__device__ __forceinline__ unsigned mt_hidx(unsigned kk, int tid) { return kk * REP + (unsigned)(tid & (REP - 1)); }
+template <int NT>
+__device__ __forceinline__ void mt_hist_zero(unsigned* sh_hist) {
+    for (int i = (int)threadIdx.x; i < MT_WORDS; i += NT) sh_hist[i] = 0u;
+}
+
+// One code t of a channel with bounds lo / hi (lo_ni / hi_ni: the bound is not an integer code, a value of its own) into the
+// histogram.  Branch-free for everything common: zero and "clamped to a non-integer bound" are counted in the caller's
+// registers (carry adds), an integer code inside the window is one LDS atomic under the lane mask.  The if / else-if chain
+// this replaces executed all its arms on nearly every step (some lane always takes each): 2.2x the VALU and 3.3x the SALU
+// instructions of the kernel without histogram.  nan(): a NaN counts with the channel's c_min - the caller says where.
+template <bool CLIP, class NaN>
+__device__ __forceinline__ void mt_hist_count(float t, float lo, float hi, bool lo_ni, bool hi_ni, int wstart, unsigned* sh_hist,
+                                              unsigned long long* __restrict__ hist, int C, unsigned& nzero, unsigned& nhi,
+                                              unsigned& nlo, NaN&& nan) {
+    const int tid = (int)threadIdx.x;
+    const bool z = (t == 0.f);
+    const bool at_hi = CLIP && hi_ni && t == hi;
+    const bool at_lo = CLIP && lo_ni && t == lo && !at_hi;   // (c_min == c_max, a constant channel: ONE value, counted once - round 6)
+    nzero += z ? 1u : 0u;
+    if constexpr (CLIP) { nhi += at_hi ? 1u : 0u; nlo += at_lo ? 1u : 0u; }
+    const int k = (int)t;                       // saturating; NaN -> 0
+    const unsigned kk = (unsigned)(k - wstart);
+    const bool fast = ((float)k == t) && kk < (unsigned)MT_W;
+    if (fast && !z) {
+        atomicAdd(&sh_hist[mt_hidx(kk, tid)], 1u);
+    } else if (!(z || at_hi || at_lo)) {        // rare
+        if (t == rintf(t)) {                    // integer code outside the window (or inf)
+            if (t >= (float)(-MT_NB / 2) && t < (float)(MT_NB / 2)) atomicAdd(&hist[(int)t + MT_NB / 2], 1ull);
+            else atomicAdd(&hist[t < 0.f ? MT_NB : MT_NB + 1], 1ull);
+            atomicAdd(&hist[mt_flag_word(C)], 1ull);   // the global bins are in use
+        } else {
+            nan();
+        }
+    }
+}
+
+// The end of a workgroup, before its barrier: the lane's count of code 0 into the window.
+__device__ __forceinline__ void mt_hist_zero_code(unsigned* sh_hist, unsigned long long* __restrict__ hist, int C, int wstart,
+                                                  unsigned nzero) {
+    if (nzero) {
+        const int kk = -wstart;
+        if (kk >= 0 && kk < MT_W) {
+            atomicAdd(&sh_hist[mt_hidx((unsigned)kk, (int)threadIdx.x)], nzero);
+        } else {
+            // code 0 lies outside the window (a symmetric range with more than 2 * MT_W bins): its count goes to the
+            // global bins, and the flag word must say so - k_mt_entropy reads those bins only when it is raised
+            atomicAdd(&hist[MT_NB / 2], (unsigned long long)nzero);
+            atomicAdd(&hist[mt_flag_word(C)], 1ull);
+        }
+    }
+}
+// ... and behind it: the workgroup of NT lanes folds the REP copies of every window bin and hands each live bin over with one
+// atomic, into replica table rep_id & (MT_GR - 1); a window bin that stands for no integer code (at or past MT_NB / 2) goes
+// to the "above" word and raises the flag.
+template <int NT, int REP = MT_REP>
+__device__ __forceinline__ void mt_hist_fold(const unsigned* sh_hist, unsigned long long* __restrict__ hist, int C, int wstart,
+                                             int rep_id) {
+    const int tid = (int)threadIdx.x;
+    unsigned long long* rep = hist + MT_NB + 2 + 2 * (size_t)C + (size_t)(rep_id & (MT_GR - 1)) * MT_W;
+    for (int i = tid; i < MT_W; i += NT) {
+        unsigned tot = 0;
+#pragma unroll 8
+        for (int r = 0; r < REP; ++r) tot += sh_hist[mt_hidx<REP>((unsigned)i, r + tid)];
+        if (tot) {
+            if (wstart + i < MT_NB / 2) {
+                atomicAdd(&rep[i], (unsigned long long)tot);
+            } else {
+                atomicAdd(&hist[MT_NB + 1], (unsigned long long)tot);
+                atomicAdd(&hist[mt_flag_word(C)], 1ull);
+            }
+        }
+    }
+}
+
 // The kernel walks tiles id = blockIdx.x, blockIdx.x + gridDim.x, ... of `total` (launched with one workgroup per tile).
 template <int VEC, int A, int J, bool CLIP, bool HIST, bool CODES>
 __global__ void __launch_bounds__(TPB) k_mt_qdq(const float* __restrict__ x, float* __restrict__ y, const Geo g,
                                                 const float* __restrict__ mt, float* __restrict__ codes,
                                                 unsigned long long* __restrict__ hist, const int total) {
-    constexpr int MT_WORDS = MT_W * MT_REP;
-    auto hidx = [](unsigned kk, int tid) -> unsigned { return kk * MT_REP + (unsigned)(tid & (MT_REP - 1)); };
     __shared__ float sh_d[MAXCH], sh_lo[MAXCH], sh_hi[MAXCH];
     __shared__ unsigned sh_hist[HIST ? MT_WORDS : 1];
     __shared__ unsigned sh_clo[HIST ? MAXCH : 1], sh_chi[HIST ? MAXCH : 1];
     const int tid = threadIdx.x;
     if constexpr (HIST) {
-        for (int i = tid; i < MT_WORDS; i += TPB) sh_hist[i] = 0u;
+        mt_hist_zero<TPB>(sh_hist);
         for (int i = tid; i < MAXCH; i += TPB) { sh_clo[i] = 0u; sh_chi[i] = 0u; }
         __syncthreads();
     }
@@ -194,13 +289,7 @@ __global__ void __launch_bounds__(TPB) k_mt_qdq(const float* __restrict__ x, flo
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
                     const int a = (A == 1 ? 0 : e);
-                    float t = rintf(v[j][e] / d[j][a]);          // iq.py:202-203
-                    if constexpr (CLIP) {
-                        // torch.min(t, hi) = t < hi ? t : hi and torch.max(t, lo) = t > lo ? t : lo, NaN kept
-                        // (the bound wins ties: max(-0, +0) is +0, iq.py:213-214)
-                        t = (t < hi[j][a] || t != t) ? t : hi[j][a];
-                        t = (t > lo[j][a] || t != t) ? t : lo[j][a];
-                    }
+                    const float t = mt_code<CLIP>(v[j][e] / d[j][a], lo[j][a], hi[j][a]);
                     q[e] = t;
                     o[e] = t * d[j][a];                          // iq.py:224
                 }
@@ -211,35 +300,9 @@ __global__ void __launch_bounds__(TPB) k_mt_qdq(const float* __restrict__ x, flo
 #pragma unroll
                         for (int e = 0; e < VEC; ++e) {
                             const int a = (A == 1 ? 0 : e);
-                            const float t = q[e];
-                            // Branch-free for everything common: zero and "clamped to a non-integer bound" are
-                            // counted in registers (carry adds), an integer code inside the window is one LDS
-                            // atomic under the lane mask.  The if / else-if chain this replaces executed all its
-                            // arms on nearly every step (some lane always takes each): 2.2x the VALU and 3.3x the
-                            // SALU instructions of the kernel without histogram.
-                            const bool z = (t == 0.f);
-                            const bool at_hi = CLIP && hi_ni[j][a] && t == hi[j][a];
-                            const bool at_lo = CLIP && lo_ni[j][a] && t == lo[j][a] && !at_hi;   // (c_min == c_max, a constant channel: ONE value, counted once - round 6)
-                            nzero += z ? 1u : 0u;
-                            if constexpr (CLIP) { nhi[j][a] += at_hi ? 1u : 0u; nlo[j][a] += at_lo ? 1u : 0u; }
-                            const int k = (int)t;                       // saturating; NaN -> 0
-                            const unsigned kk = (unsigned)(k - wstart);
-                            const bool fast = ((float)k == t) && kk < (unsigned)MT_W;
-                            if (fast && !z) {
-#ifdef MT_EXP_NOATOMIC
-                                nzero += kk;
-#else
-                                atomicAdd(&sh_hist[hidx(kk, tid)], 1u);
-#endif
-                            } else if (!(z || at_hi || at_lo)) {        // rare
-                                if (t == rintf(t)) {                    // integer code outside the window (or inf)
-                                    if (t >= (float)(-MT_NB / 2) && t < (float)(MT_NB / 2)) atomicAdd(&hist[(int)t + MT_NB / 2], 1ull);
-                                    else atomicAdd(&hist[t < 0.f ? MT_NB : MT_NB + 1], 1ull);
-                                    atomicAdd(&hist[mt_flag_word(g.C)], 1ull);   // the global bins are in use
-                                } else {
-                                    atomicAdd(&sh_clo[chl[j][a]], 1u);  // NaN
-                                }
-                            }
+                            // (the bounds' flags exist only with CLIP; a NaN goes to the channel's c_min counter in LDS)
+                            mt_hist_count<CLIP>(q[e], lo[j][a], hi[j][a], CLIP && lo_ni[j][a], CLIP && hi_ni[j][a], wstart, sh_hist,
+                                                hist, g.C, nzero, nhi[j][a], nlo[j][a], [&] { atomicAdd(&sh_clo[chl[j][a]], 1u); });
                         }
                     }
                 }
@@ -264,32 +327,9 @@ __global__ void __launch_bounds__(TPB) k_mt_qdq(const float* __restrict__ x, flo
         }
     }
     if constexpr (HIST) {
-        if (nzero) {
-            const int kk = -wstart;
-            if (kk >= 0 && kk < MT_W) {
-                atomicAdd(&sh_hist[hidx((unsigned)kk, tid)], nzero);
-            } else {
-                // code 0 lies outside the window (a symmetric range with more than 2 * MT_W bins): its count goes to the
-                // global bins, and the flag word must say so - k_mt_entropy reads those bins only when it is raised
-                atomicAdd(&hist[MT_NB / 2], (unsigned long long)nzero);
-                atomicAdd(&hist[mt_flag_word(g.C)], 1ull);
-            }
-        }
+        mt_hist_zero_code(sh_hist, hist, g.C, wstart, nzero);
         __syncthreads();
-        unsigned long long* rep = hist + MT_NB + 2 + 2 * (size_t)g.C + (size_t)(blockIdx.x & (MT_GR - 1)) * MT_W;
-        for (int i = tid; i < MT_W; i += TPB) {
-            unsigned tot = 0;
-#pragma unroll
-            for (int r = 0; r < MT_REP; ++r) tot += sh_hist[hidx((unsigned)i, r + tid)];
-            if (tot) {
-                if (wstart + i < MT_NB / 2) {
-                    atomicAdd(&rep[i], (unsigned long long)tot);
-                } else {
-                    atomicAdd(&hist[MT_NB + 1], (unsigned long long)tot);
-                    atomicAdd(&hist[mt_flag_word(g.C)], 1ull);
-                }
-            }
-        }
+        mt_hist_fold<TPB>(sh_hist, hist, g.C, wstart, (int)blockIdx.x);
     }
 }
 

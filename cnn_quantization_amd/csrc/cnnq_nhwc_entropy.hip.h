@@ -19,16 +19,15 @@ namespace {
 // y = dequant(quant(x)) per channel with qdq1 (the IEEE divide) on the upconverted value, rounded once into the element type:
 // the bits of k_cl_qdq in both of its branches (inside qdq_fast_domain the divide-free quotient is the divide's).  x read and y
 // written non-temporally, workgroups in descending address order, as k_cl_qdq.
-// The counting is k_qdq<HIST>'s, copied (xhist_add / xhist_flush are the same statements): the table is nbins x HREP words of
-// dynamic LDS, replica = lane & (HREP - 1); the zero point's code (about half of a post-ReLU layer) is counted in a register
+// The counting is k_qdq<HIST>'s own definitions (xhist_add, xhist_add_zp, xhist_fold in cnnq_qdq.hip.h): the table is nbins x
+// HREP words of dynamic LDS, replica = lane & (HREP - 1); the zero point's code (about half of a post-ReLU layer) is counted in a register
 // per channel of the lane's piece - the lane's channels never change, so W counters serve the whole slab - and added to the
 // table once at the end; after the barrier one thread per bin folds the replicas and issues at most one global atomic, into
 // replica table (workgroup id & (XHIST_REPLICAS - 1)).  A code indexes the table as code & (nbins - 1): the host passes
 // nbins > qmax of every channel (2^num_bits where it derived the table from num_bits itself, 256 otherwise), so the mask only
 // keeps a caller's mistaken nbins inside the table.  NaN takes k_qdq's path: its code is NaN, differs from the zero point, and
 // (int)NaN == 0 counts it in bin 0; +inf clamps to qmax and -inf to 0 before the count.
-// The copy is deliberate (as k_cl_mt_qdq's): k_qdq's body is measured and moving it behind a call was not re-measured; who
-// changes one copy changes the other, and tests/test_channels_last_entropy_gpu.py compares the two histograms word for word.
+// tests/test_channels_last_entropy_gpu.py compares the two histograms word for word.
 // A workgroup's flush is up to nbins global atomics, so the launch takes the long slabs of cl_geo_hist, not cl_geo_qdq's.
 template <class T, int W>
 __global__ void __launch_bounds__(TPB) k_cl_qdq_hist(const typename ClRaw<T>::type* __restrict__ x, typename ClRaw<T>::type* __restrict__ y,
@@ -62,22 +61,14 @@ __global__ void __launch_bounds__(TPB) k_cl_qdq_hist(const typename ClRaw<T>::ty
             for (int i = 0; i < W; ++i) {
                 float cd;
                 e[i] = cl_down(T{}, qdq1(cl_up(T{}, e[i]), sc[i], zp[i], qm[i], cd));
-                if (cd == zp[i]) ++nzp[i];
-                else atomicAdd(&sh_hist[((unsigned)(int)cd & mask) * HREP + (tid & (HREP - 1))], 1u);
+                xhist_add(sh_hist, cd, zp[i], nzp[i], mask);
             }
             cl_st_nt<E, W>(y + off, e);
         }
-#pragma unroll
-        for (int i = 0; i < W; ++i)
-            if (nzp[i]) atomicAdd(&sh_hist[((unsigned)(int)zp[i] & mask) * HREP + (tid & (HREP - 1))], nzp[i]);
+        xhist_add_zp<W>(sh_hist, zp, nzp, mask);
     }
     __syncthreads();
-    if (tid < nbins) {
-        unsigned tot = 0;
-#pragma unroll 8
-        for (int r = 0; r < HREP; ++r) tot += sh_hist[tid * HREP + ((r + tid) & (HREP - 1))];
-        if (tot) atomicAdd(&hist[(size_t)(blockIdx.x & (XHIST_REPLICAS - 1)) * 256 + tid], (unsigned long long)tot);
-    }
+    if (tid < nbins) xhist_fold(sh_hist, hist, xhist_replica());
 }
 
 }  // namespace

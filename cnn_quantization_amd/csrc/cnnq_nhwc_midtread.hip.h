@@ -26,23 +26,19 @@ namespace {
 // window bin into replica table (workgroup id % MT_GR), and - the RS lanes that share a piece folded through LDS first - one
 // atomic per channel and bound that was hit.  Every workgroup of a tensor of up to TPB * W channels hits the same 2 * C clamp
 // counters, so the histogram variant runs on the long slabs of cl_geo_hist (cnnq_nhwc.hip.h).
-// The update and the flush are k_mt_qdq's, copied: the contract needs both to stay the same for good, and shared __device__
-// helpers would make that structural.  They are not shared yet because k_mt_qdq's speed is measured (the note above it: the
-// branch-free update was worth 2.2x the VALU instructions) and moving its body behind a call was not re-measured; who changes
-// one copy changes the other, and tests/test_channels_last_midtread_gpu.py compares the two histograms word for word.
+// The code, its count and the LDS table's zeroing and fold are k_mt_qdq's own definitions (mt_code, mt_hist_count, mt_hist_zero,
+// mt_hist_zero_code, mt_hist_fold in cnnq_midtread.hip.h); tests/test_channels_last_midtread_gpu.py compares the two histograms.
 template <class T, int W, bool HIST>
 __global__ void __launch_bounds__(TPB) k_cl_mt_qdq(const typename ClRaw<T>::type* __restrict__ x, typename ClRaw<T>::type* __restrict__ y,
                                                    const ClGeo g, const float* __restrict__ mt, unsigned long long* __restrict__ hist) {
     typedef typename ClRaw<T>::type E;
-    constexpr int MT_WORDS = MT_W * MT_REP;
-    auto hidx = [](unsigned kk, int tid) -> unsigned { return kk * MT_REP + (unsigned)(tid & (MT_REP - 1)); };
     __shared__ unsigned sh_hist[HIST ? MT_WORDS : 1];
     __shared__ unsigned sh_clo[HIST ? TPB * W : 1], sh_chi[HIST ? TPB * W : 1];
     const int tid = (int)threadIdx.x;
     const int bid = (int)gridDim.x - 1 - (int)blockIdx.x;
     const int cols = g.CP * W;                       // the workgroup's channels
     if constexpr (HIST) {
-        for (int i = tid; i < MT_WORDS; i += TPB) sh_hist[i] = 0u;
+        mt_hist_zero<TPB>(sh_hist);
         for (int i = tid; i < cols; i += TPB) { sh_clo[i] = 0u; sh_chi[i] = 0u; }
         __syncthreads();
     }
@@ -76,34 +72,12 @@ __global__ void __launch_bounds__(TPB) k_cl_mt_qdq(const typename ClRaw<T>::type
             cl_ld<E, W, true>(x + off, e);
 #pragma unroll
             for (int i = 0; i < W; ++i) {
-                float t = rintf(cl_up(T{}, e[i]) / d[i]);            // iq.py:202-203
-                // torch.min(t, hi) = t < hi ? t : hi and torch.max(t, lo) = t > lo ? t : lo, NaN kept (the bound wins ties:
-                // max(-0, +0) is +0, iq.py:213-214)
-                t = (t < hi[i] || t != t) ? t : hi[i];
-                t = (t > lo[i] || t != t) ? t : lo[i];
+                const float t = mt_code<true>(cl_up(T{}, e[i]) / d[i], lo[i], hi[i]);
                 e[i] = cl_down(T{}, t * d[i]);                       // iq.py:224
                 if constexpr (HIST) {
-                    // k_mt_qdq's update, statement for statement
-                    const bool z = (t == 0.f);
-                    const bool at_hi = ((hi_ni >> i) & 1u) && t == hi[i];
-                    const bool at_lo = ((lo_ni >> i) & 1u) && t == lo[i] && !at_hi;   // (c_min == c_max: ONE value, counted once)
-                    nzero += z ? 1u : 0u;
-                    nhi[i] += at_hi ? 1u : 0u;
-                    nlo[i] += at_lo ? 1u : 0u;
-                    const int k = (int)t;                            // saturating; NaN -> 0
-                    const unsigned kk = (unsigned)(k - wstart);
-                    const bool fast = ((float)k == t) && kk < (unsigned)MT_W;
-                    if (fast && !z) {
-                        atomicAdd(&sh_hist[hidx(kk, tid)], 1u);
-                    } else if (!(z || at_hi || at_lo)) {             // rare
-                        if (t == rintf(t)) {                         // integer code outside the window (or inf)
-                            if (t >= (float)(-MT_NB / 2) && t < (float)(MT_NB / 2)) atomicAdd(&hist[(int)t + MT_NB / 2], 1ull);
-                            else atomicAdd(&hist[t < 0.f ? MT_NB : MT_NB + 1], 1ull);
-                            atomicAdd(&hist[mt_flag_word(g.C)], 1ull);   // the global bins are in use
-                        } else {
-                            nlo[i] += 1u;                            // NaN: the channel's c_min counter
-                        }
-                    }
+                    // (a NaN goes to the channel's c_min counter, here the lane's own)
+                    mt_hist_count<true>(t, lo[i], hi[i], (lo_ni >> i) & 1u, (hi_ni >> i) & 1u, wstart, sh_hist, hist, g.C, nzero, nhi[i],
+                                        nlo[i], [&] { nlo[i] += 1u; });
                 }
             }
             cl_st_nt<E, W>(y + off, e);
@@ -119,16 +93,7 @@ __global__ void __launch_bounds__(TPB) k_cl_mt_qdq(const typename ClRaw<T>::type
         }
     }
     if constexpr (HIST) {
-        if (nzero) {
-            const int kk = -wstart;
-            if (kk >= 0 && kk < MT_W) {
-                atomicAdd(&sh_hist[hidx((unsigned)kk, tid)], nzero);
-            } else {
-                // code 0 lies outside the window: its count goes to the global bins, and the flag word must say so
-                atomicAdd(&hist[MT_NB / 2], (unsigned long long)nzero);
-                atomicAdd(&hist[mt_flag_word(g.C)], 1ull);
-            }
-        }
+        mt_hist_zero_code(sh_hist, hist, g.C, wstart, nzero);
         __syncthreads();
         const int cbase = (bid % g.nb) * cols;
         for (int j = tid; j < cols; j += TPB) {
@@ -137,20 +102,7 @@ __global__ void __launch_bounds__(TPB) k_cl_mt_qdq(const typename ClRaw<T>::type
             if (sh_clo[j]) atomicAdd(&hist[MT_NB + 2 + c], (unsigned long long)sh_clo[j]);
             if (sh_chi[j]) atomicAdd(&hist[MT_NB + 2 + g.C + c], (unsigned long long)sh_chi[j]);
         }
-        unsigned long long* rep = hist + MT_NB + 2 + 2 * (size_t)g.C + (size_t)(bid & (MT_GR - 1)) * MT_W;
-        for (int i = tid; i < MT_W; i += TPB) {
-            unsigned tot = 0;
-#pragma unroll
-            for (int r = 0; r < MT_REP; ++r) tot += sh_hist[hidx((unsigned)i, r + tid)];
-            if (tot) {
-                if (wstart + i < MT_NB / 2) {
-                    atomicAdd(&rep[i], (unsigned long long)tot);
-                } else {
-                    atomicAdd(&hist[MT_NB + 1], (unsigned long long)tot);
-                    atomicAdd(&hist[mt_flag_word(g.C)], 1ull);
-                }
-            }
-        }
+        mt_hist_fold<TPB>(sh_hist, hist, g.C, wstart, bid);
     }
 }
 

@@ -248,11 +248,35 @@ inline size_t xhist_lds_bytes(int out, const void* hist, int nbins) { return (ou
 __device__ __forceinline__ void xhist_zero(unsigned* sh_hist, int nbins) {
     for (int i = threadIdx.x; i < nbins * HREP; i += blockDim.x) sh_hist[i] = 0u;
 }
+// The counting of every kernel that fills this histogram - k_qdq<HIST>, k_cl_qdq_hist (cnnq_nhwc_entropy.hip.h) and the
+// single-launch kernels - is the functions below.  mask: a code indexes the table as code & mask - 255 where the table has
+// 256 bins or the codes are known to stay below nbins, nbins - 1 where the table is nbins bins and nbins is the caller's say.
 // the zero point (the code of x == 0, about half of a post-ReLU layer) is counted in a register
-__device__ __forceinline__ void xhist_add(unsigned* sh_hist, float cd, float zp, unsigned& nzp) {
+__device__ __forceinline__ void xhist_add(unsigned* sh_hist, float cd, float zp, unsigned& nzp, unsigned mask) {
     if (cd == zp) ++nzp;
-    else atomicAdd(&sh_hist[((unsigned)(int)cd & 255u) * HREP + (threadIdx.x & (HREP - 1))], 1u);
+    else atomicAdd(&sh_hist[((unsigned)(int)cd & (unsigned)mask) * HREP + (threadIdx.x & (HREP - 1))], 1u);
 }
+// the end of a workgroup, before its barrier: the lane's register counts of its A zero points' codes into the table
+template <int A>
+__device__ __forceinline__ void xhist_add_zp(unsigned* sh_hist, const float (&zp)[A], const unsigned (&nzp)[A], unsigned mask) {
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+        if (nzp[a]) atomicAdd(&sh_hist[((unsigned)(int)zp[a] & (unsigned)mask) * HREP + (threadIdx.x & (HREP - 1))], nzp[a]);
+}
+// ... and behind it: this thread folds the replicas of bin threadIdx.x and issues at most one global atomic, into the table
+// that starts at word `first` of hist
+__device__ __forceinline__ void xhist_fold(const unsigned* sh_hist, unsigned long long* hist, size_t first) {
+    const int tid = threadIdx.x;
+    unsigned tot = 0;
+#pragma unroll 8
+    for (int r = 0; r < HREP; ++r) tot += sh_hist[tid * HREP + ((r + tid) & (HREP - 1))];
+    if (tot) atomicAdd(&hist[first + tid], (unsigned long long)tot);
+}
+// the replica table of this workgroup, for the kernels that write XHIST_REPLICAS tables
+__device__ __forceinline__ size_t xhist_replica() { return (size_t)(blockIdx.x & (XHIST_REPLICAS - 1)) * 256; }
+// The single-launch kernels' end of a workgroup: xhist_add_zp, the barrier, xhist_fold into this workgroup's replica table - in
+// its own text: composed of the two calls it moved the text of every kernel that calls it (profiles/code_hist.md), and those
+// kernels are measured.  Who changes the parts changes this.
 template <int A>
 __device__ __forceinline__ void xhist_flush(unsigned* sh_hist, unsigned long long* hist, int nbins, const float (&zp)[A],
                                             const unsigned (&nzp)[A]) {
@@ -297,7 +321,7 @@ __device__ __forceinline__ void xstore(const XOut& xo, char* __restrict__ yb, ui
         }
         if (xo.hist) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) xhist_add(sh_hist, cd[e], zp[A == 1 ? 0 : e], nzp[A == 1 ? 0 : e]);
+            for (int e = 0; e < 4; ++e) xhist_add(sh_hist, cd[e], zp[A == 1 ? 0 : e], nzp[A == 1 ? 0 : e], 255u);
         }
     }
     if constexpr (OUT == 2) {
@@ -460,8 +484,7 @@ __global__ void __launch_bounds__(TPB) k_qdq(const float* __restrict__ x, float*
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {
                         const int a = (A == 1 ? 0 : e);
-                        if (cd[e] == zp[j][a]) ++nzp[j][a];
-                        else atomicAdd(&sh_hist[((unsigned)(int)cd[e] & 255u) * HREP + (tid & (HREP - 1))], 1u);
+                        xhist_add(sh_hist, cd[e], zp[j][a], nzp[j][a], 255u);
                     }
                 }
                 if constexpr (CODES) {
@@ -479,15 +502,9 @@ __global__ void __launch_bounds__(TPB) k_qdq(const float* __restrict__ x, float*
     }
     if constexpr (HIST) {
 #pragma unroll
-        for (int j = 0; j < J; ++j)
-#pragma unroll
-            for (int a = 0; a < A; ++a)
-                if (nzp[j][a]) atomicAdd(&sh_hist[((unsigned)(int)zp[j][a] & 255u) * HREP + (tid & (HREP - 1))], nzp[j][a]);
+        for (int j = 0; j < J; ++j) xhist_add_zp<A>(sh_hist, zp[j], nzp[j], 255u);
         __syncthreads();
-        unsigned tot = 0;
-#pragma unroll 8
-        for (int r = 0; r < HREP; ++r) tot += sh_hist[tid * HREP + ((r + tid) & (HREP - 1))];
-        if (tot) atomicAdd(&hist[tid], (unsigned long long)tot);
+        xhist_fold(sh_hist, hist, 0);  // 256 bins, every thread one bin, ONE table
     }
 }
 

@@ -1,5 +1,5 @@
-"""The kernels that COUNT codes (k_mt_qdq<HIST>, the channels_last mid-tread pass, k_qdq<HIST>, k_cl_qdq_hist) on inputs whose
-histogram is known without the device.
+"""The kernels that COUNT codes (k_mt_qdq<HIST>, the channels_last mid-tread pass, the contiguous bf16 / fp16 mid-tread pass,
+k_qdq<HIST>, k_cl_qdq_hist) on inputs whose histogram is known without the device.
 
 The parameter tables are hand-built with a step of 1 or 0.5 and the inputs are exact multiples of the step, so x / step is an
 integer before the clamps: no rounding tie, no divide to trust, and one numpy expression gives every code (the kernels' own
@@ -7,7 +7,7 @@ codes output is compared with it where there is one).  From the codes numpy deri
 window bins summed over the replicas, every global bin, the two out-of-range words, every clamp counter, whether the flag word is
 raised - and the fp64 entropy (tests/_entropy.py) that cnnq_midtread_entropy / cnnq_entropy must then report within the tier
 2e-5 * max(1, H).  All counts are compared exactly.  The values used are exact in bf16 and fp16 (asserted), so the channels_last
-kernels see the same numbers in every element type and must write the NCHW kernel's histogram.
+and the contiguous half kernels see the same numbers in every element type and must write the NCHW kernel's histogram.
 
 NaN inputs are left out: the kernel counts a NaN code into the channel's c_min counter while torch.unique keeps NaNs apart, and
 nothing in the reference depends on either.  Needs an MI355X: `pytest -m gpu`."""
@@ -164,9 +164,24 @@ def run_nhwc(x, mt, dtype):
     return h.cpu().numpy(), hist_entropy(h, md, C, x.size)
 
 
+def run_half(x, mt, dtype):
+    """cnnq_pc_midtread_qdq_dt on the same values as contiguous [N, C, H, W] of bf16 / fp16 (the histogram zeroed by the caller, as
+    ops.mid_tread_qdq_half does) -> (words, entropy); y is checked against the codes * delta rounded into the dtype"""
+    N, C, H, Wd = x.shape
+    assert exact_in(x, dtype)
+    xd, md = torch.from_numpy(x).to(dtype).cuda(), torch.from_numpy(mt).cuda()
+    y = torch.empty_like(xd)
+    h = torch.zeros(E.mt_hist_words(C), dtype=torch.int64, device='cuda')
+    _lib.check(_lib.load().cnnq_pc_midtread_qdq_dt(ops._ptr(xd), ops._ptr(y), ops._DTYPE_CODES[dtype], N, C, H * Wd, ops._ptr(md), ops._ptr(h),
+                                                   ops._stream(xd)), 'cnnq_pc_midtread_qdq_dt')
+    want_y = torch.from_numpy((mt_codes(x, mt, 1) * mt[E.MT_DELTA][None, :, None, None]).astype(np.float32)).to(dtype)
+    assert torch.equal(y.cpu(), want_y), dtype
+    return h.cpu().numpy(), hist_entropy(h, md, C, x.size)
+
+
 def check_all_layouts(x, mt, what, dtypes=DTYPES):
-    """clip = 1: the NCHW kernel, then the channels_last kernel in every element type, against numpy and region by region against
-    each other"""
+    """clip = 1: the NCHW kernel, then the channels_last kernel in every element type and the contiguous bf16 / fp16 pass, against
+    numpy and region by region against the NCHW kernel"""
     t = mt_codes(x, mt, 1)
     h64 = codes_entropy(t)
     codes, words, ent = run_nchw(x, mt, 1)
@@ -180,6 +195,12 @@ def check_all_layouts(x, mt, what, dtypes=DTYPES):
         for r in ('win', 'glob', 'below', 'above', 'clo', 'chi'):
             assert np.array_equal(got[r], ref[r]), (what, dt, r)
         assert abs(e2 - h64) <= E.tier(h64), (what, dt)
+    for dt in (torch.bfloat16, torch.float16):
+        w3, e3 = run_half(x, mt, dt)
+        got = check_hist(w3, t, mt, 1, (what, 'contiguous', dt))
+        for r in ('win', 'glob', 'below', 'above', 'clo', 'chi'):
+            assert np.array_equal(got[r], ref[r]), (what, 'contiguous', dt, r)
+        assert abs(e3 - h64) <= E.tier(h64), (what, 'contiguous', dt)
     return ref
 
 
