@@ -158,6 +158,10 @@ SIGNATURES = {
     'cnnq_pc_route_midtread_dt': (_I, [_L, _L, _L, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
     'cnnq_pc_midtread_qdq_dt': (_I, [_P, _P, _I, _L, _L, _L, _P, _P, _P]),
     'cnnq_pc_midtread_dt': (_I, [_P, _P, _I, _L, _L, _L, ctypes.c_double, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
+    'cnnq_pc_route_qdq_hist_dt': (_I, [_L, _L, _L, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_pc_qdq_hist_dt': (_I, [_P, _P, _I, _L, _L, _L, _P, _I, _P, _P]),
+    'cnnq_pc_minmax_qdq_hist_dt': (_I, [_P, _P, _I, _L, _L, _L, _I, _I, _P, _P, _P, _P, _I, _P]),
+    'cnnq_pc_aciq_qdq_hist_dt': (_I, [_P, _P, _I, _L, _L, _L, ctypes.POINTER(ParamsCfg), _P, _P, _P, _P, _P, _P]),
     'cnnq_rows_stats_workspace': (ctypes.c_size_t, [_L, _L, _I]),
     'cnnq_rows_stats_route': (_I, [_L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
     'cnnq_rows_stats': (_I, [_P, _I, _L, _L, _I, _P, _P, _P, _P]),

@@ -54,6 +54,7 @@
 #include "cnnq_half_bcorr.hip.h"
 #include "cnnq_half_aciq.hip.h"
 #include "cnnq_half_midtread.hip.h"
+#include "cnnq_half_entropy.hip.h"
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_nhwc_collect.hip.h"
@@ -71,6 +72,7 @@ namespace {
 inline bool nt_loads(int64_t bytes) { return bytes > NT_BYTES; }      // beyond the Infinity Cache: non-temporal loads
 inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }   // a: a power of two (NULL is aligned)
 inline bool pow2(int v) { return v > 0 && !(v & (v - 1)); }
+inline bool hist_bins_ok(int nbins) { return nbins >= 2 && nbins <= 256 && pow2(nbins); }   // the bins of a counting pass
 inline int g_error(int G) { return G ? G : CNNQ_EINVAL; }             // what a group count G <= 0 says: the plan's error
 inline hipStream_t hs(void* stream) { return (hipStream_t)stream; }
 inline unsigned long long* u64p(uint64_t* p) { return reinterpret_cast<unsigned long long*>(p); }
@@ -1579,15 +1581,20 @@ static int h_route(int64_t N, int64_t C, int64_t HW, int align_bytes, int allow_
     return 0;
 }
 
+// the statistics launch of config 2 at piece width w, G the fp32 plan's record count: ~H_MM_ELEMS per workgroup - batch splits
+// first, then (short batches: config 1's rows, N = 1) column splits of the rows
+static HGeo h_geo_mm(int64_t N, int64_t C, int64_t HW, int w, int G) {
+    const int total = h_splits(N * HW, C, 1, H_MM_ELEMS, G);
+    const int bs = total < N ? total : (int)N, ppr = (int)(HW / w);
+    return h_geo(N, C, HW, w, bs, total / bs < ppr ? total / bs : ppr);
+}
+
 // the statistics half of the chain: per-split extrema into pmm[S][2][C], S <= the fp32 plan's G (the callers' workspace rule)
 static int h_minmax(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, float* pmm, int* S, hipStream_t st) {
     const int G = h_records_f32(N, C, HW);
     if (G <= 0) return g_error(G);
     const int w = h_piece(HW, (uintptr_t)x, 0);
-    // ~H_MM_ELEMS per workgroup: batch splits first, then (short batches: config 1's rows, N = 1) column splits of the rows
-    const int total = h_splits(N * HW, C, 1, H_MM_ELEMS, G);
-    const int bs = total < N ? total : (int)N, ppr = (int)(HW / w);
-    const HGeo g = h_geo(N, C, HW, w, bs, total / bs < ppr ? total / bs : ppr);
+    const HGeo g = h_geo_mm(N, C, HW, w, G);
     *S = g.S * g.cs;
     return h_launch(dtype, w, x, [&](auto pc, const uint16_t* xh) {
         using P = decltype(pc);
@@ -2009,6 +2016,101 @@ int cnnq_pc_midtread_dt(const void* x, void* y, int dtype, int64_t N, int64_t C,
     return h_mt_qdq(x, y, dtype, N, C, HW, w, mt, hist, st);
 }
 
+// ---- the uniform Q/DQ that counts its codes (-me) on contiguous bf16 / fp16 activations (cnnq_half_entropy.hip.h) ----------------
+// the route word of a bf16 / fp16 tensor at piece width w: 1 - k_h_whole_hist alone / 2 - k_h_minmax, then k_h_qdq_hist / 0 - a
+// class of layer that did not win against the upcast route and stays there (h_ent_native; the calls themselves run every class,
+// on route 2)
+static int h_ent_route(int64_t N, int64_t C, int64_t HW, int dtype, int w, int nbins, int allow_single_launch) {
+    if (allow_single_launch && h_ent_whole_fits(N, HW, w) && (allow_single_launch > 1 || h_ent_whole_wins(N, C, HW, dtype, nbins))) return 1;
+    return h_ent_native(N, C, HW, dtype, nbins) ? 2 : 0;
+}
+
+// Which launches cnnq_pc_minmax_qdq_hist_dt makes for this geometry (host only): out = {piece width W, batch splits S of the
+// counting launch, column splits of the statistics launch, route (h_ent_route)}.  fp32: CNNQ_ENOTSUP, as the calls.
+int cnnq_pc_route_qdq_hist_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int nbins, int allow_single_launch,
+                              int32_t out[4]) {
+    const HPlan p(N, C, HW, dtype, out && pow2(align_bytes) && hist_bins_ok(nbins));
+    if (p.rc) return p.rc;
+    if (dtype == CNNQ_DTYPE_F32) return CNNQ_ENOTSUP;
+    const int w = h_piece(HW, (uintptr_t)align_bytes, 0);
+    out[0] = w;
+    out[1] = h_geo_hist(N, C, HW, w).S;
+    out[2] = h_geo_mm(N, C, HW, w, h_records_f32(N, C, HW)).cs;
+    out[3] = h_ent_route(N, C, HW, dtype, w, nbins, allow_single_launch);
+    return 0;
+}
+
+// pmm == NULL: the parameters from the table qp; else from the statistics partials pmm (published to ha.qp / ha.mm)
+static int h_qdq_hist(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, int w, const float* qp, const float* pmm,
+                      const HArgs& ha, int nbins, uint64_t* hist_rep, hipStream_t st) {
+    const HGeo g = h_geo_hist(N, C, HW, w);
+    return h_launch(dtype, w, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_h_qdq_hist<typename P::T, P::W>), dim3((unsigned)(C * g.S)), dim3(TPB), h_hist_lds(nbins), st, xh, yh, g, qp,
+                           pmm, ha, nbins, u64p(hist_rep));
+    });
+}
+
+// int_quantizer.py:573-592 on x[N][C][HW] of bf16 / fp16 with a given table, and the codes of 586-587 counted into hist_rep: one
+// launch
+int cnnq_pc_qdq_hist_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, int nbins,
+                        uint64_t* hist_rep, void* stream) {
+    const HPlan p(N, C, HW, dtype, x && y && x != y && qp && hist_rep && !misaligned(hist_rep, 8) && hist_bins_ok(nbins));
+    if (p.rc) return p.rc;
+    if (dtype == CNNQ_DTYPE_F32) return CNNQ_ENOTSUP;
+    return h_qdq_hist(x, y, dtype, N, C, HW, h_piece(HW, (uintptr_t)h_align(x, y), 0), qp, nullptr, HArgs{}, nbins, hist_rep, hs(stream));
+}
+
+// int_quantizer.py:409-451, 557-603 with 586-587 on x[N][C][HW] of bf16 / fp16: k_h_whole_hist (route 1), or k_h_minmax ->
+// k_h_qdq_hist (route 2), 2^num_bits bins
+int cnnq_pc_minmax_qdq_hist_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, int num_bits, int positive,
+                               float* ws, float* qp, float* mm, uint64_t* hist_rep, int allow_single_launch, void* stream) {
+    const bool ok = x && y && x != y && ws && qp && hist_rep && !misaligned(ws, 4) && !misaligned(hist_rep, 8) && num_bits >= 1 &&
+                    num_bits <= 8;                                                    // the codes fit a byte, the bins 256
+    const HPlan p(N, C, HW, dtype, ok);
+    if (p.rc) return p.rc;
+    if (dtype == CNNQ_DTYPE_F32) return CNNQ_ENOTSUP;
+    hipStream_t st = hs(stream);
+    const int nbins = 1 << num_bits;
+    const int w = h_piece(HW, (uintptr_t)h_align(x, y), 0);
+    if (h_ent_route(N, C, HW, dtype, w, nbins, allow_single_launch) == 1) {
+        const HGeo g = h_geo(N, C, HW, w, 1, 1);
+        const HArgs ha{0, num_bits, positive ? 1 : 0, qp, mm};
+        return h_launch(dtype, w, x, y, [&](auto pc, const uint16_t* xh, uint16_t* yh) {
+            using P = decltype(pc);
+            if constexpr (P::W > 1)
+                hipLaunchKernelGGL((k_h_whole_hist<typename P::T, P::W, h_whole_k<P::W>()>), dim3((unsigned)C), dim3(HTPB), h_hist_lds(nbins),
+                                   st, xh, yh, g, ha, nbins, u64p(hist_rep));
+        });
+    }
+    float* const pmm = MmWs(ws, C).pmm;              // where cnnq_pc_minmax_qdq_auto_dt keeps its partials
+    int S = 0;
+    const int rc = h_minmax(x, dtype, N, C, HW, pmm, &S, st);
+    if (rc) return rc;
+    return h_qdq_hist(x, y, dtype, N, C, HW, w, qp, pmm, HArgs{S, num_bits, positive ? 1 : 0, qp, mm}, nbins, hist_rep, st);
+}
+
+// int_quantizer.py:327-352 + 409-451, 557-603 with 586-587 on x[N][C][HW] of bf16 / fp16: cnnq_pc_aciq_qdq_dt's route 2 with the
+// counting pass last - k_h_moments -> k_combine (-> k_h_absdev -> k_combine_dev) -> k_params -> k_h_qdq_hist; 256 bins under bit
+// allocation (the channels' qmax is decided on the device), else 2^num_bits
+int cnnq_pc_aciq_qdq_hist_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws,
+                             float* stats, float* qp, float* diag, uint64_t* hist_rep, void* stream) {
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    const uintptr_t es = f32 ? 4 : 2;
+    const bool ok = x && y && x != y && ws && stats && qp && hist_rep && !misaligned(ws, 8) && !misaligned(stats, 4) && !misaligned(qp, 4) &&
+                    !misaligned(diag, 4) && !misaligned(hist_rep, 8) && !misaligned(x, es) && !misaligned(y, es) && h_aciq_cfg_ok(cfg) &&
+                    cfg->num_bits <= 8 && !(cfg_bit_alloc(cfg) && !diag);             // the bit table lives in diag
+    const HPlan p(N, C, HW, dtype, ok);
+    if (p.rc) return p.rc;
+    if (f32) return CNNQ_ENOTSUP;
+    const bool need_b = cfg->clip == 1 || (cfg_bit_alloc(cfg) && cfg->prior_is_b);
+    int rc = cnnq_pc_stats_dt(x, dtype, N, C, HW, need_b ? 1 : 0, 0, 0, ws, nullptr, stats, stream);
+    if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
+    if (rc) return rc;
+    return h_qdq_hist(x, y, dtype, N, C, HW, h_piece(HW, (uintptr_t)h_align(x, y), 0), qp, nullptr, HArgs{}, cfg_bit_alloc(cfg) ? 256 : 1 << cfg->num_bits,
+                      hist_rep, hs(stream));
+}
+
 int cnnq_pt_qdq_dt(const void* x, void* y, int dtype, int64_t n, const float* ptp, const float* noise, void* stream) {
     if (!dtype_ok(dtype)) return CNNQ_EINVAL;
     return pt_qdq_launch(x, y, dtype, n, ptp, noise, stream);
@@ -2281,7 +2383,6 @@ int cnnq_pc_midtread_nhwc(const void* x, void* y, int dtype, int64_t R, int64_t 
 }
 
 // ---- the uniform Q/DQ that counts its codes (-me) on dense channels_last activations (cnnq_nhwc_entropy.hip.h) ------------------
-static bool hist_bins_ok(int nbins) { return nbins >= 2 && nbins <= 256 && pow2(nbins); }
 static size_t cl_hist_lds(int nbins) { return (size_t)nbins * HREP * sizeof(unsigned); }
 
 // Which launch the counting pass makes for this geometry (host only): out = {elements per load W, workgroups of the counting

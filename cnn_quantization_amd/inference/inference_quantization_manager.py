@@ -272,6 +272,8 @@ class TruncationOpManagerInference:
         q.half_dynamic = True
         # ... and under mid-tread quantization (IntQuantizer._midtread_route)
         q.half_midtread = True
+        # ... and with the entropy of a uniform quantizer's codes, -me (IntQuantizer._half_entropy)
+        q.half_entropy = True
         return q
 
     def _fill(self, qtype, qparams, qweight):

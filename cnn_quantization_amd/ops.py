@@ -95,7 +95,8 @@ def _half_only(what, reason):
 
 # switches, read ONCE at import (not per hot call); reload_switches() re-reads them after the environment changed (tests, tools)
 def reload_switches():
-    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC, _HALF_TABLE, _HALF_ACIQ, _HALF_MIDTREAD
+    global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC, _HALF_TABLE, _HALF_ACIQ, _HALF_MIDTREAD, _HALF_ENTROPY
+    _HALF_ENTROPY = os.environ.get('CNNQ_HALF_ENTROPY', '1') != '0'    # 0: -me on contiguous half activations takes the upcast route (A/B)
     _HALF_MIDTREAD = os.environ.get('CNNQ_HALF_MIDTREAD', '1') != '0'  # 0: mid-tread on contiguous half activations takes the upcast route (A/B)
     _HALF_ACIQ = os.environ.get('CNNQ_HALF_ACIQ', '1') != '0'          # 0: dynamic ACIQ on contiguous half activations takes the upcast route (A/B)
     _HALF_TABLE = os.environ.get('CNNQ_HALF_TABLE', '1') != '0'        # 0: calibrated per-channel half activations take the upcast route (A/B)
@@ -1185,12 +1186,15 @@ def minmax_qdq_fused(x, N, C, HW, num_bits, positive=False, want_codes=False, wa
 
 def _minmax_qdq_half(x, N, C, HW, num_bits, positive, want_codes, want_entropy, out, want_parts, group):
     """Config 2 on a bf16 / fp16 tensor on one GPU (cnnq_pc_minmax_qdq_auto_dt: one launch when a channel fits a workgroup,
-    else exact extrema of the 2-byte elements then the Q/DQ; the result rounded back into the input type).  Codes, entropy, the parts and the sharded
-    exchange have no half kernels: the quantizer computes those on x.float()."""
-    if want_codes or want_entropy or want_parts:
-        _half_only('minmax_qdq_fused', 'codes / entropy / parts')
+    else exact extrema of the 2-byte elements then the Q/DQ; the result rounded back into the input type).  want_entropy (codes
+    that fit a byte): _minmax_qdq_half_entropy.  Codes, the parts, wider codes' entropy and the sharded exchange have no half
+    kernels: the quantizer computes those on x.float()."""
+    if want_codes or want_parts or (want_entropy and num_bits > 8):
+        _half_only('minmax_qdq_fused', "codes / parts / the entropy of codes wider than a byte")
     if _sharded(group):
         _half_only('minmax_qdq_fused', 'the sharded exchange')
+    if want_entropy:
+        return _minmax_qdq_half_entropy(x, N, C, HW, num_bits, positive, out)
     lib = L.load()
     nbytes = _ws_bytes('cfg2', N, C, HW)
     y = _out_like(x, out)
@@ -1201,6 +1205,61 @@ def _minmax_qdq_half(x, N, C, HW, num_bits, positive, want_codes, want_entropy, 
     if rc:
         L.check(rc, 'cnnq_pc_minmax_qdq_auto_dt')
     return y
+
+
+_ENTROPY_HALF_NATIVE = {}
+
+
+def _entropy_half_native(N, C, HW, dtype, nbins=256):
+    """The route word of cnnq_pc_route_qdq_hist_dt's report for this class of contiguous bf16 / fp16 layer:
+    1 - config 2 with the entropy of its codes in one launch, 2 - the statistics launch and the counting pass, 0 - a class that
+    measured slower native than through the upcast and is sent back there.  The quantizer (_pc_route, _clip_route) and the tests
+    patch the function and empty the cache by name."""
+    return _half_route_word(_ENTROPY_HALF_NATIVE.setdefault(int(nbins), {}), int, 'cnnq_pc_route_qdq_hist_dt', N, C, HW, dtype,
+                            int(nbins), 1)
+
+
+def _half_hist_slot(x, what, st):
+    """The replica tables a counting pass over a contiguous bf16 / fp16 x counts into, as _entropy_slot gives them: (tables, result
+    or None).  There is no other route for a half tensor here, so a call that can have no table - first use under a stream
+    capture - raises, and names the remedy."""
+    slot = _entropy_slot(x, st)
+    if slot[0] is None:
+        raise L.CnnqError('%s: no replica table for the code histogram on this stream yet, and none can be made under a stream '
+                          'capture: make one eager want_entropy call on the stream first' % what)
+    return slot
+
+
+def _minmax_qdq_half_entropy(x, N, C, HW, num_bits, positive, out, single_launch=None):
+    """Config 2 with the entropy of its codes on a contiguous bf16 / fp16 tensor on one GPU (cnnq_pc_minmax_qdq_hist_dt, DESIGN.md
+    section 29): one launch that keeps a channel in registers where the route function says so, else the exact extrema of the 2-byte
+    elements and the counting Q/DQ pass; 2^num_bits bins.  (y, entropy); inside an entropy_batch block the entropy is filled by
+    the block's one launch.  single_launch: None - the route function's choice; 0 - the two launches; 2 - the resident form
+    wherever the channel fits (tests, A/B)."""
+    lib = L.load()
+    nbytes = _ws_bytes('cfg2', N, C, HW)
+    y = _out_like(x, out)
+    st = _raw_stream(x.device.index)
+    hist, ent_batched = _half_hist_slot(x, 'act_qdq_per_channel', st)
+    ws = _scratch(x, 'cfg2', nbytes, st).data_ptr()
+    allow = (1 if _RESIDENT else 0) if single_launch is None else int(single_launch)
+    rc = lib.cnnq_pc_minmax_qdq_hist_dt(x.data_ptr(), y.data_ptr(), _HALF_DTYPES[x.dtype], N, C, HW, int(num_bits),
+                                        1 if positive else 0, ws, ws, ws + L.NQP * C * 4, hist.data_ptr(), allow, st)
+    if rc:
+        L.check(rc, 'cnnq_pc_minmax_qdq_hist_dt')
+    return y, _replica_entropy(x, hist, ent_batched, st)
+
+
+def _pc_qdq_half_entropy(x, N, C, HW, qp, nbins, out):
+    """pc_qdq on a contiguous bf16 / fp16 x with the table qp, the codes counted in nbins bins (cnnq_pc_qdq_hist_dt): (y, entropy)."""
+    y = _out_like(x, out)
+    st = _raw_stream(x.device.index)
+    hist, ent_batched = _half_hist_slot(x, 'pc_qdq', st)
+    rc = L.load().cnnq_pc_qdq_hist_dt(x.data_ptr(), y.data_ptr(), _HALF_DTYPES[x.dtype], N, C, HW, qp.data_ptr(), int(nbins),
+                                      hist.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_qdq_hist_dt')
+    return y, _replica_entropy(x, hist, ent_batched, st)
 
 
 _LOCAL_PLAN = {}    # per (N, C, HW): (workspace bytes, whether the one-GPU hot call hands the C side the group workspace)
@@ -1745,13 +1804,16 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
         qp, _ = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
         return _pc_qdq_nhwc(x, qp, out)
     if x.dtype != torch.float32:
-        # bf16 / fp16: config 2, dynamic or from a statistics table - min/max parameters, no clipping, no bit allocation
-        if (clip != 'no' or use_ba or whole_tensor or per_channel_dim != 1 or bcorr is not None or want_codes or want_entropy
-                or want_parts):
+        # bf16 / fp16: config 2, dynamic or from a statistics table - min/max parameters, no clipping, no bit allocation; with the
+        # entropy of its codes where they fit a byte, on one GPU
+        if (clip != 'no' or use_ba or whole_tensor or per_channel_dim != 1 or bcorr is not None or want_codes or want_parts
+                or (want_entropy and (num_bits > 8 or _sharded(group)))):
             _half_only('act_qdq_per_channel', 'clipping / bit allocation / whole-tensor / weights / bias correction / codes')
         if stats is None:
-            return minmax_qdq_fused(x, N, C, HW, num_bits, positive, out=out, group=group, _checked=True)
+            return minmax_qdq_fused(x, N, C, HW, num_bits, positive, want_entropy=want_entropy, out=out, group=group, _checked=True)
         qp, _ = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, direct_range=whole_tensor)
+        if want_entropy:
+            return _pc_qdq_half_entropy(x, N, C, HW, qp, _hist_bins(num_bits, use_ba), out)
         return pc_qdq(x, N, C, HW, qp, out=out)
     if bcorr is not None and (want_codes or want_entropy or want_parts or whole_tensor or per_channel_dim != 1):
         raise L.CnnqError('bcorr combines only with the plain per-channel activation Q/DQ')
@@ -1886,7 +1948,7 @@ def _aciq_half_native(N, C, HW, dtype, bit_alloc=False, prior_is_b=False):
 
 
 def aciq_qdq_half(x, num_bits, positive=False, clip='laplace', bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
-                  stats=None, out=None, want_parts=False, single_launch=None):
+                  stats=None, out=None, want_parts=False, single_launch=None, want_entropy=False):
     """Config 3 (iq.py:327-352 -> 409-451: ACIQ clipping 'laplace' / 'gaus', optionally bit allocation) on a contiguous 4-D bf16 /
     fp16 activation, on the storage as it is: cnnq_pc_aciq_qdq_dt - the statistics, the parameters and the
     Q/DQ in one launch where a channel's batch population fits one workgroup's registers (behind pass A and the bit allocation
@@ -1894,16 +1956,24 @@ def aciq_qdq_half(x, num_bits, positive=False, clip='laplace', bit_alloc=False, 
     with `stats` ([NSTAT, C], -sm use), pc_params and the table-driven Q/DQ.  y has x's dtype; want_parts: (y, dict(stats, qp,
     diag)).  single_launch: None - the route function's choice; 0 - the chain; 2 - the resident form wherever the channel fits (the
     chain elsewhere), for tests and A/B.  One GPU: the statistics are this tensor's.  Anything else - a CPU tensor, float32, not
-    4-D, not contiguous - raises: nothing is copied or upcast here."""
+    4-D, not contiguous - raises: nothing is copied or upcast here.
+    want_entropy: the Q/DQ pass counts its codes (cnnq_pc_aciq_qdq_hist_dt - the chain, whatever
+    single_launch says - or cnnq_pc_qdq_hist_dt with `stats`) and the entropy follows y as aciq_qdq_nhwc returns it - y, entropy
+    [, parts]; inside an entropy_batch block it is filled by the block's one launch."""
     what = 'aciq_qdq_half'
     if clip not in ('laplace', 'gaus'):
         raise L.CnnqError("%s: clip must be 'laplace' or 'gaus', got %r" % (what, clip))
+    if want_entropy and num_bits > 8:
+        raise L.CnnqError('%s: the ACIQ factor tables end at 8 bits' % what)
     x, N, C, HW, dt, st = _admit_half(x, what, 'act_qdq_per_channel')
     use_ba = bool(bit_alloc) and num_bits <= 4
     if stats is not None:
         if not _is_table(stats, torch.float32, (L.NSTAT, C), x.device):
             raise L.CnnqError('%s: stats must be a contiguous float32 [%d, %d] device table' % (what, L.NSTAT, C))
         qp, diag = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
+        if want_entropy:
+            y, entropy = _pc_qdq_half_entropy(x, N, C, HW, qp, _hist_bins(num_bits, use_ba), out)
+            return _result(y, entropy=entropy, parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
         return _result(pc_qdq(x, N, C, HW, qp, out=out), parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
     if single_launch not in (None, 0, 1, 2):
         raise L.CnnqError('%s: single_launch must be None, 0, 1 or 2, got %r' % (what, single_launch))
@@ -1917,11 +1987,17 @@ def aciq_qdq_half(x, num_bits, positive=False, clip='laplace', bit_alloc=False, 
         # the tables nobody outside the call reads follow the records in the cached workspace
         ws = _scratch(x, 'aciq_half', nbytes + (L.NSTAT + L.NQP + L.NDIAG) * C * 4, st).data_ptr()
         tp = ws + nbytes
-    rc = L.load().cnnq_pc_aciq_qdq_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
-                                      tp + (L.NSTAT + L.NQP) * C * 4, 1 if single_launch is None else int(single_launch), st)
+    hist = ent_batched = None
+    if want_entropy:
+        hist, ent_batched = _half_hist_slot(x, what, st)
+        rc = L.load().cnnq_pc_aciq_qdq_hist_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                               tp + (L.NSTAT + L.NQP) * C * 4, hist.data_ptr(), st)
+    else:
+        rc = L.load().cnnq_pc_aciq_qdq_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                          tp + (L.NSTAT + L.NQP) * C * 4, 1 if single_launch is None else int(single_launch), st)
     if rc:
         L.check(rc, 'cnnq_pc_aciq_qdq_dt')
-    return _result(y, parts=dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:]) if want_parts else None)
+    return _result(y, entropy=_replica_entropy(x, hist, ent_batched, st) if want_entropy else None, parts=dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:]) if want_parts else None)
 
 
 def weight_correction(w, w_q, vcorr=False, bcorr=False):

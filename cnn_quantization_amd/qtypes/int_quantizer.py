@@ -117,6 +117,9 @@ class IntQuantizer:
         # the route 'half_midtread' (mid-tread on a contiguous bf16 / fp16 activation): opt-in per object in
         # the same way, and for the same reason
         self.half_midtread = False
+        # the route 'half_entropy' (-me with a uniform quantizer on a contiguous bf16 / fp16 activation):
+        # opt-in per object in the same way, and for the same reason
+        self.half_entropy = False
 
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
@@ -194,7 +197,8 @@ class IntQuantizer:
     def _clip_route(self, tensor, clip_type, stat_id, att):
         """gemmlowpClippingQuantize.  Per channel, Laplace or Gaussian clipping without -me: a pending correction folded in on
         channels_last, the calibration table on a contiguous half tensor (both need stat_id), ACIQ on channels_last, dynamic ACIQ
-        on a contiguous half tensor (opt-in: half_dynamic).  Per tensor, also '<p>std': the flat route.  'mix' has none."""
+        on a contiguous half tensor (opt-in: half_dynamic).  With -me: 'half_entropy' on a contiguous half tensor, dynamic or
+        from the table (opt-in: half_entropy).  Per tensor, also '<p>std': the flat route.  'mix' has none."""
         pc, one_gpu, use_ba, pending = self._facts(tensor, att)
         if not one_gpu:
             return None
@@ -203,8 +207,11 @@ class IntQuantizer:
         if not pc:
             clips = clip_type in ('laplace', 'gaus') or (isinstance(clip_type, str) and clip_type.endswith('std'))
             return 'flat_clip' if clips and not direct and self._flat_tensor(tensor) else None
-        if clip_type not in ('laplace', 'gaus') or att('measure_entropy'):
+        if clip_type not in ('laplace', 'gaus'):
             return None
+        if att('measure_entropy'):
+            # -me: the chain with the counting pass last, dynamic or from the table (opt-in: half_entropy)
+            return 'half_entropy' if not pending and not direct and self._half_entropy(tensor, att, use_ba) else None
         storage = _storage(tensor)
         if stat_id is not None and not direct:
             if pending and storage == 'nhwc':
@@ -224,7 +231,8 @@ class IntQuantizer:
     def _pc_route(self, tensor, stat_id, att):
         """gemmlowpQuantizeActivationPerChannel.  From the calibration table (stat_id) without -me: a pending correction folded in
         on channels_last; on a contiguous half tensor the table route under bit allocation or a pending correction, else
-        'half_minmax' (ops.act_qdq_per_channel's own half route).  Then -me on channels_last byte codes, and config 2's kernels."""
+        'half_minmax' (ops.act_qdq_per_channel's own half route).  Then -me on channels_last byte codes or on a contiguous half
+        tensor (opt-in: half_entropy), and config 2's kernels."""
         pc, one_gpu, use_ba, pending = self._facts(tensor, att)
         if not (pc and one_gpu) or att('mtd_quant') or att('kld') or att('pcq_w'):          # (by a direct call only)
             return None
@@ -238,8 +246,17 @@ class IntQuantizer:
         if use_ba or pending:
             return None
         if entropy:
-            return 'nhwc_entropy' if att('num_bits') <= 8 and _dense_nhwc(tensor) else None
+            if att('num_bits') <= 8 and _dense_nhwc(tensor):
+                return 'nhwc_entropy'
+            return 'half_entropy' if self._half_entropy(tensor, att, False) else None
         return 'minmax_pc'
+
+    def _half_entropy(self, tensor, att, use_ba):
+        """What the two 'half_entropy' routes share behind their own conditions: codes that fit a byte, the object's flag, the
+        switch, a contiguous half tensor and a class of layer the route function keeps native (256 bins under bit allocation)."""
+        bits = att('num_bits')
+        return bool(bits <= 8 and self.half_entropy and ops._HALF_ENTROPY and _storage(tensor) == 'half'
+                    and ops._entropy_half_native(*ops.geometry(tensor), tensor.dtype, 256 if use_ba else 1 << bits) != 0)
 
     def _midtread_route(self, tensor, att):
         """The two mid_tread_quantize_activation methods: with clipping (the per-channel one is also __call__'s branch at clipping
@@ -386,7 +403,7 @@ class IntQuantizer:
             return ops.qdq_bias_corrected_nhwc(tensor, self._table_params(table, 'no'), bool(self._take_bcorr()))
         if route == 'half_table':
             return self._table_half(tensor, table, 'no')
-        return self._act_qdq(tensor, id, 'no', table)            # 'half_minmax', 'nhwc_entropy', 'minmax_pc': its own routes
+        return self._act_qdq(tensor, id, 'no', table)            # 'half_minmax', 'nhwc_entropy', 'half_entropy', 'minmax_pc': its own routes
 
     def gemmlowpClippingQuantize(self, tensor, id, tag="", stat_id=None, clip_type='laplace'):
         """iq.py:327-359: ACIQ clipping (laplace / gaus / <p>std), per channel when -pcq_a applies,
@@ -409,6 +426,13 @@ class IntQuantizer:
             if route == 'half_aciq':
                 return ops.aciq_qdq_half(tensor, self.num_bits, **kw)
             return ops.aciq_qdq_nhwc(tensor, self.num_bits, stats=table, **kw)
+        if route == 'half_entropy':
+            # a contiguous bf16 / fp16 activation with -me: the chain where it lies, its last pass counting the codes
+            out, entropy = ops.aciq_qdq_half(tensor, self.num_bits, positive=self._positive, clip=clip_type, bit_alloc=self.bit_alloc_act,
+                                             prior_is_b=self.bit_alloc_prior != 'gaus', target=self.bit_alloc_target_act,
+                                             round_mode=self.bit_alloc_round, stats=table, want_entropy=True)
+            self._log_entropy(id, entropy, 'avg.entropy.act', out.numel())
+            return out
         if route == 'flat_clip':
             # half or dense channels_last: quantized where it lies, the result keeps dtype and layout
             return ops.clip_qdq_tensor(tensor, self.num_bits, positive=self._positive, clip=clip_type, stats=table)

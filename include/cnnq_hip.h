@@ -866,6 +866,48 @@ int cnnq_pc_midtread_qdq_dt(const void* x, void* y, int dtype, int64_t N, int64_
 int cnnq_pc_midtread_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, double target, int sym, const double* tables,
                         int ntab, void* ws, float* stats, float* mt, uint64_t* hist, int allow_single_launch, void* stream);
 
+/* The uniform per-channel Q/DQ with the histogram of its codes (-me: int_quantizer.py:586-587, the codes exist in the reference
+ * only as the argument of shannon_entropy, 445) on CONTIGUOUS bf16 / fp16 activations x[N][C][HW], on the storage as it lies: no
+ * fp32 copy.  Counterpart of the cnnq_pc_*_hist_nhwc entries; the rows are cut into pieces as for cnnq_pc_qdq_dt (W = 8 / 4 / 2 / 1
+ * from HW and the alignment x and y share: every (HW, alignment) has a route); a workgroup owns one channel.
+ * Given the table qp[CNNQ_NQP][C], y is cnnq_pc_qdq_dt's bit for bit, and the counts are, word for word once the replica tables
+ * are summed, the histogram cnnq_pc_qdq fills on x.float().
+ * hist_rep: cnnq_hist_replica_bytes() bytes, 8-byte aligned, zero at rest - the contract of the single-launch kernels: the calls
+ * ADD to it, cnnq_entropy_replicas[_batch] and cnnq_hist_replicas_fold consume it and leave it zero.
+ * nbins: the bins the counting workgroups keep, a power of two in [2, 256] above every channel's qmax (a code is counted in bin
+ * code & (nbins - 1)); the dynamic forms choose it: 2^num_bits, 256 under bit allocation.
+ * cnnq_pc_qdq_hist_dt (int_quantizer.py:573-592 with 586-587; counterpart of cnnq_pc_qdq with hist): the table-driven pass, one
+ * launch.
+ * cnnq_pc_minmax_qdq_hist_dt (int_quantizer.py:409-451, 557-603 with 586-587; config 2, dynamic; counterpart of
+ * cnnq_pc_minmax_qdq_single with hist_rep), 2^num_bits bins.  Routes:
+ *   1. one launch of one 1024-lane workgroup per channel that keeps the channel in registers: extrema, parameters, Q/DQ and the
+ *      count - 4 B/elem.  Only where N * HW <= 131072 and W >= 2;
+ *   2. cnnq_pc_minmax_qdq_auto_dt's statistics launch, then the counting pass, which merges the partials in its prologue - 6 B/elem.
+ *   Both routes give the same bits.  ws: cnnq_pc_minmax_qdq_workspace bytes, 4-byte aligned (the partials live behind the tables'
+ *   place in it); qp[CNNQ_NQP][C] and mm[2][C] (may be NULL) are OUTPUTS, written as cnnq_pc_minmax_qdq_auto_dt writes its own.
+ * cnnq_pc_aciq_qdq_hist_dt (int_quantizer.py:327-352 + 409-451, 557-603 with 586-587; config 3, dynamic; counterpart of
+ * cnnq_pc_aciq_qdq_single with hist_rep): cnnq_pc_aciq_qdq_dt's route 2 - cnnq_pc_stats_dt, cnnq_pc_params - with the counting
+ * pass last; 256 bins under bit allocation, else 2^num_bits.  ws: cnnq_pc_aciq_dt_workspace bytes, 8-byte aligned; cfg, stats,
+ * qp, diag as cnnq_pc_aciq_qdq_dt, whose refusals and promises apply; on top of them: num_bits > 8.
+ * cnnq_pc_route_qdq_hist_dt (host only, nothing enqueued, a function of its arguments alone): out = {piece width W, batch splits
+ * S of the counting launch (C * S workgroups), column splits of config 2's statistics launch, route}; route 1 / 2 as above, 0 - a
+ * class of layer that did not measure faster than the upcast route and is left there by callers that have the choice (the calls
+ * themselves run every class, on route 2).  allow_single_launch: 0 - never route 1; 1 - where it measured faster than route 2;
+ * 2 - wherever the channel fits (tests, A/B).  align_bytes: the power of two that divides x and y (<= 16 is what matters).
+ * A bad dtype, N, C or HW < 1, a NULL required pointer (hist_rep included), a misaligned ws / hist_rep, x == y, an nbins that is
+ * not a power of two in [2, 256], num_bits outside [1, 8], a NULL out or an align_bytes that is not a power of two return
+ * CNNQ_EINVAL, a geometry beyond cnnq_pc_groups' limits that function's code - before anything touches the device.
+ * CNNQ_DTYPE_F32: CNNQ_ENOTSUP, nothing enqueued (fp32 has cnnq_pc_qdq with hist and the single-launch kernels).
+ * Re-entrant, allocate nothing, no host synchronisation, graph-capturable.  cnnq_pc_qdq_dt keeps its contract: hist must be NULL. */
+int cnnq_pc_route_qdq_hist_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int nbins, int allow_single_launch,
+                              int32_t out[4]);
+int cnnq_pc_qdq_hist_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, int nbins,
+                        uint64_t* hist_rep, void* stream);
+int cnnq_pc_minmax_qdq_hist_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, int num_bits, int positive,
+                               float* ws, float* qp, float* mm, uint64_t* hist_rep, int allow_single_launch, void* stream);
+int cnnq_pc_aciq_qdq_hist_dt(const void* x, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws,
+                             float* stats, float* qp, float* diag, uint64_t* hist_rep, void* stream);
+
 /* The statistics of FEW, VERY LONG rows over flat storage - the per-tensor calibration table of statistic_manager.py:55-96
  * (rows = 1: the whole tensor) and the per-sample sums of squares of distance_stats.py:22-33 (rows = N: the samples) - for fp32 /
  * bf16 / fp16 elements, on the storage as it lies: x is viewed as [rows][len], every row contiguous and the rows back to back.
