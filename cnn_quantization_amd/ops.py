@@ -205,40 +205,33 @@ def _groups(N, C, HW, aligned=None):
     return G
 
 
-_NHWC_WS = {'nhwc': 'cnnq_pc_nhwc_workspace', 'aciq_nhwc': 'cnnq_pc_aciq_nhwc_workspace',
-            'bcorr_nhwc': 'cnnq_pc_qdq_bcorr_nhwc_workspace', 'stats_nhwc': 'cnnq_pc_stats_nhwc_workspace',
-            'rows': 'cnnq_rows_stats_workspace'}
-
-
-_HALF_WS = {'stats_half': 'cnnq_pc_stats_dt_workspace', 'bcorr_half': 'cnnq_pc_qdq_bcorr_dt_workspace',
-            'aciq_half': 'cnnq_pc_aciq_dt_workspace', 'midtread_half': 'cnnq_pc_midtread_dt_workspace'}
+_WS_FN = {  # kind: (workspace function of a storage form's one-call entry points, geometry words it takes in front of the dtype code)
+    'pt_clip': ('cnnq_pt_clip_workspace', 1), 'rows': ('cnnq_rows_stats_workspace', 2),
+    'nhwc': ('cnnq_pc_nhwc_workspace', 2), 'aciq_nhwc': ('cnnq_pc_aciq_nhwc_workspace', 2),
+    'bcorr_nhwc': ('cnnq_pc_qdq_bcorr_nhwc_workspace', 2), 'stats_nhwc': ('cnnq_pc_stats_nhwc_workspace', 2),
+    'stats_half': ('cnnq_pc_stats_dt_workspace', 3), 'bcorr_half': ('cnnq_pc_qdq_bcorr_dt_workspace', 3),
+    'aciq_half': ('cnnq_pc_aciq_dt_workspace', 3), 'midtread_half': ('cnnq_pc_midtread_dt_workspace', 3)}
 
 
 def _ws_bytes(kind, N, C, HW, arg=0):
     """Workspace bytes of a one-call entry point, asked once and rounded up to 16 so that tables may follow in one scratch buffer.
-    arg: x is 16-byte aligned ('stats', 'aciq'), the dtype code ('nhwc', 'aciq_nhwc', 'bcorr_nhwc', 'stats_nhwc': N = rows; 'rows':
-    N = rows, C = their length; 'pt_clip': N = elements; 'stats_half', 'bcorr_half', 'aciq_half', 'midtread_half': the dtype code).  0 from the library: no plan for
-    the geometry."""
+    arg: x is 16-byte aligned ('stats', 'aciq'), else the dtype code - of the kinds of _WS_FN, which take the first 1 (N = elements),
+    2 (N = rows, C = their length or the channels) or 3 (N, C, HW) of the geometry words.  0 from the library: no plan for the
+    geometry."""
     key = (kind, N, C, HW, arg)
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
         lib = L.load()
-        if kind in _NHWC_WS:
-            fn = _NHWC_WS[kind]
-            nbytes = getattr(lib, fn)(N, C, arg)
+        if kind in _WS_FN:
+            fn, words = _WS_FN[kind]
+            args = (N, C, HW)[:words] + (arg,)
+            nbytes = getattr(lib, fn)(*args)
+            if nbytes == 0 and words < 3:
+                raise L.CnnqError('%s(%s): bad arguments' % (fn, ', '.join('%d' % a for a in args)))
             if nbytes == 0:
-                raise L.CnnqError('%s(%d, %d, %d): bad arguments' % (fn, N, C, arg))
-        elif kind == 'pt_clip':
-            nbytes = lib.cnnq_pt_clip_workspace(N, arg)
-            if nbytes == 0:
-                raise L.CnnqError('cnnq_pt_clip_workspace(%d, %d): bad arguments' % (N, arg))
+                L.check(min(lib.cnnq_pc_groups(N, C, HW, 0), -1), '%s(%d,%d,%d,%d)' % ((fn,) + args))
         elif kind == 'aciq':
             nbytes = lib.cnnq_pc_aciq_workspace(N, C, HW, arg)
-        elif kind in _HALF_WS:
-            fn = _HALF_WS[kind]
-            nbytes = getattr(lib, fn)(N, C, HW, arg)
-            if nbytes == 0:
-                L.check(min(lib.cnnq_pc_groups(N, C, HW, 0), -1), '%s(%d,%d,%d,%d)' % (fn, N, C, HW, arg))
         else:
             nbytes = lib.cnnq_pc_minmax_qdq_workspace(N, C, HW) if kind == 'cfg2' else lib.cnnq_pc_stats_workspace(N, C, HW, arg)
             if nbytes == 0:
@@ -344,10 +337,49 @@ def pc_stats(x, N, C, HW, need_b=False, need_kurt=False, need_relu=False, group=
     return stats, mom
 
 
-# ------------------------------------------------------------------------------------- the channels_last front
-# what the *_nhwc entry points share on the host - who runs native (_nhwc_native) and how a tensor is
-# admitted, with the geometry its C calls take (_admit_nhwc).  The hot calls keep their pointer arithmetic inline: a helper
-# per call costs more host time than it saves lines (profiles/host_overhead_nhwc.md).
+# ------------------------------------------------------------------------------------- the native front
+# what the entry points on the two native storage forms - dense channels_last (*_nhwc) and contiguous
+# bf16 / fp16 (*_half) - share on the host.  An admission (_admit_nhwc, _admit_half) hands back a site:
+#     (layout, geo, C, dtype code, raw stream)
+# geo, the geometry words the layout's C calls take, is splatted into them: (R, C) or (N, C, HW).  layout is one of the two
+# tables below: what differs between the storage forms, written once.  Every operation is one body of (site, its own arguments)
+# - _pc_stats_native, _aciq_qdq_native, _qdq_bias_corrected_native, _mid_tread_qdq_native, _qdq_native - behind two public
+# wrappers that keep what is their layout's own: the argument checks, the fallback of a channels_last tensor that does not run
+# native, single_launch, and where the counting pass of a want_entropy call counts (_nhwc_hist_slot may send the tensor to the
+# copy route, _half_hist_slot raises).  One Python call more per entry than a body written into its wrapper, and no more: the
+# bodies keep their pointer arithmetic inline, a helper per call costs more host time than it saves lines
+# (profiles/host_overhead_nhwc.md, profiles/host_overhead_native.md).
+# The config-2 pair stays apart (_minmax_qdq_nhwc against _minmax_qdq_half / _minmax_qdq_half_entropy): their workspaces are
+# laid out differently, and the half one runs the C code float32 runs.
+_NHWC_LAYOUT = {    # operation: (C function [, its counting or table-driven form], the _ws_bytes / _scratch kind)
+    'stats': ('cnnq_pc_stats_nhwc', 'stats_nhwc'),
+    'aciq': ('cnnq_pc_aciq_qdq_nhwc', 'cnnq_pc_aciq_qdq_hist_nhwc', 'aciq_nhwc'),
+    'bcorr': ('cnnq_pc_qdq_bcorr_nhwc', 'bcorr_nhwc'),
+    'midtread': ('cnnq_pc_midtread_nhwc', 'cnnq_pc_midtread_qdq_nhwc', 'aciq_nhwc'),
+    'qdq': ('cnnq_pc_qdq_nhwc', (), 'cnnq_pc_qdq_hist_nhwc'),       # (the words between qp and the stream of the plain form)
+    'ws_pad': (1,),     # _ws_bytes is keyed by (N, C, HW): the HW of the kinds that take rows
+    'single': False}    # whether the calls of 'aciq', 'bcorr' and 'midtread' end in an allow_single_launch word
+_HALF_LAYOUT = {
+    'stats': ('cnnq_pc_stats_dt', 'stats_half'),
+    'aciq': ('cnnq_pc_aciq_qdq_dt', 'cnnq_pc_aciq_qdq_hist_dt', 'aciq_half'),
+    'bcorr': ('cnnq_pc_qdq_bcorr_dt', 'bcorr_half'),
+    'midtread': ('cnnq_pc_midtread_dt', 'cnnq_pc_midtread_qdq_dt', 'midtread_half'),
+    'qdq': ('cnnq_pc_qdq_dt', (None, None, 0), 'cnnq_pc_qdq_hist_dt'),
+    'ws_pad': (),
+    'single': True}
+
+
+def _route_word(cache, key, cast, fn, geo, dtype, extra=(), words=4, word=3):
+    """cast(word `word` of the `words` the route function `fn` reports) for a class of layer - a function of its geometry words geo
+    and the dtype alone - asked once per `key` with alignment 16 (extra: fn's arguments behind align_bytes) and kept in `cache`."""
+    v = cache.get(key)
+    if v is None:
+        out = (ctypes.c_int32 * words)()
+        L.check(getattr(L.load(), fn)(*geo, _DTYPE_CODES.get(dtype, -1), 16, *extra, out), fn)
+        v = cache[key] = cast(out[word])
+    return v
+
+
 _NHWC_ROUTES = {    # kind: (route function, its arguments behind align_bytes, words of out, the word that says "native")
     'stats': ('cnnq_pc_route_stats_nhwc', (), 4, 3),
     'hist': ('cnnq_pc_route_qdq_hist_nhwc', (256,), 4, 3),
@@ -358,21 +390,13 @@ _NHWC_NATIVE = {}
 def _nhwc_native(kind, R, C, dtype):
     """Whether this class of layer runs on the channels_last kernels of `kind`: the "native" word of its route function's report
     (0: a class that measured slower native than copied is sent back to the copy route there; a function of R, C and the dtype
-    alone), asked once per (kind, R, C, dtype) with alignment 16.  'stats' is kept under its own name: _stats_nhwc_native."""
+    alone), asked once per (kind, R, C, dtype).  'stats' is kept under its own name: _stats_nhwc_native.  (On the hot path of
+    _admit_nhwc: a class that has asked costs no further call.)"""
     if kind == 'stats':
         return _stats_nhwc_native(R, C, dtype)
-    key = (kind, R, C, dtype)
-    v = _NHWC_NATIVE.get(key)
-    if v is None:
-        v = _NHWC_NATIVE[key] = _ask_route(kind, R, C, dtype)
-    return v
-
-
-def _ask_route(kind, R, C, dtype):
-    fn, extra, words, word = _NHWC_ROUTES[kind]
-    out = (ctypes.c_int32 * words)()
-    L.check(getattr(L.load(), fn)(R, C, _DTYPE_CODES.get(dtype, -1), 16, *extra, out), fn)
-    return bool(out[word])
+    v = _NHWC_NATIVE.get((kind, R, C, dtype))
+    return v if v is not None else _route_word(_NHWC_NATIVE, (kind, R, C, dtype), bool, _NHWC_ROUTES[kind][0], (R, C), dtype,
+                                               *_NHWC_ROUTES[kind][1:])
 
 
 _STATS_NHWC_NATIVE = {}
@@ -381,18 +405,15 @@ _STATS_NHWC_NATIVE = {}
 def _stats_nhwc_native(R, C, dtype):
     """The 'stats' answer under the name, and with the cache, that the statistics manager (collects_native_nhwc) and the tests
     of the collect family use: they patch the function and empty the cache by name."""
-    key = (R, C, dtype)
-    v = _STATS_NHWC_NATIVE.get(key)
-    if v is None:
-        v = _STATS_NHWC_NATIVE[key] = _ask_route('stats', R, C, dtype)
-    return v
+    v = _STATS_NHWC_NATIVE.get((R, C, dtype))
+    return v if v is not None else _route_word(_STATS_NHWC_NATIVE, (R, C, dtype), bool, _NHWC_ROUTES['stats'][0], (R, C), dtype)
 
 
 def _admit_nhwc(x, what, route=None, half_reason=None, dev_first=False):
-    """(x, geo) - x as a channels_last entry point takes it, and geo = (C, R = N*H*W, dtype code, raw stream), what its C call
-    takes, when x runs native: a dense channels_last 4-D CUDA tensor of fp32 / bf16 / fp16 with CNNQ_NHWC on and - route - a class
-    of layer the route function keeps.  Otherwise geo is None and x the contiguous copy _dev makes and counts, for the caller's
-    fallback.  Two orders, chosen by the caller:
+    """(x, site) - x as a channels_last entry point takes it, and its site, geo = (R = N*H*W, C), when x runs native: a dense
+    channels_last 4-D CUDA tensor of fp32 / bf16 / fp16 with CNNQ_NHWC on and - route - a class of layer the route function keeps.
+    Otherwise the site is None and x the contiguous copy _dev makes and counts, for the caller's fallback.  Two orders, chosen by
+    the caller:
       dev_first=False: the 4-D check, the decision, then - half_reason: the fallback is float32 only - the error of a half tensor
         before anything is copied or counted, then _dev;
       dev_first=True: _dev's checks and its copy, then the 4-D check; no route, no half error (the caller raises its own)."""
@@ -413,7 +434,7 @@ def _admit_nhwc(x, what, route=None, half_reason=None, dev_first=False):
     if not native:
         return x, None
     C = x.shape[1]
-    return x, (C, x.numel() // C, _DTYPE_CODES[x.dtype], _raw_stream(x.device.index))
+    return x, (_NHWC_LAYOUT, (x.numel() // C, C), C, _DTYPE_CODES[x.dtype], _raw_stream(x.device.index))
 
 
 def _not_4d(x, what):
@@ -426,46 +447,39 @@ def _is_table(t, dtype, shape, device):
             and tuple(t.shape) == tuple(shape))
 
 
-def pc_stats_nhwc(x, need_b=False, need_kurt=False, need_relu=False):
-    """pc_stats of a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is (DESIGN.md section 18; -sm
-    collect, smpc.py:45-79): cnnq_pc_stats_nhwc - pass A over slabs of rows, the merge, pass B when b or the kurtosis is asked
-    for, its merge - one host call, one cached workspace, 8 B/elem in fp32 and 4 in bf16 / fp16 for the full table.  Returns
-    (stats [NSTAT, C] f32, mom [NMOM, C] f64) as pc_stats; rows nobody asked for are zero (B comes with pass B: need_b or
-    need_kurt, as in pc_stats).  One GPU: the statistics are this tensor's.  A tensor that is not dense channels_last (or
-    CNNQ_NHWC=0, or a class of layer the route function sends back: copied, counted) takes pc_stats, which is float32 only - a
-    half tensor raises before anything is copied."""
-    x, geo = _admit_nhwc(x, 'pc_stats_nhwc', 'stats', 'the statistics of a tensor that does not take the channels_last kernels')
-    if geo is None:
-        N, C, HW = geometry(x)
-        return pc_stats(x, N, C, HW, need_b, need_kurt, need_relu, group=False)
-    C, R, dt, st = geo
+def _pc_stats_native(site, x, need_b, need_kurt, need_relu):
+    """The -sm collect table of a tensor on its site in one host call with one cached workspace (cnnq_pc_stats_nhwc /
+    cnnq_pc_stats_dt): pass A, the merge, pass B when b or the kurtosis is asked for, its merge.  (stats [NSTAT, C] f32, mom
+    [NMOM, C] f64) as pc_stats; rows nobody asked for are zero (B comes with pass B: need_b or need_kurt, as in pc_stats).  One
+    GPU: the statistics are this tensor's."""
+    layout, geo, C, dt, st = site
+    fn, kind = layout['stats']
     stats = torch.empty((L.NSTAT, C), dtype=torch.float32, device=x.device)
     mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
-    ws = _scratch(x, 'stats_nhwc', _ws_bytes('stats_nhwc', R, C, 1, dt), st)
-    rc = L.load().cnnq_pc_stats_nhwc(x.data_ptr(), dt, R, C, int(bool(need_b)), int(bool(need_kurt)), int(bool(need_relu)),
-                                     ws.data_ptr(), mom.data_ptr(), stats.data_ptr(), st)
+    ws = _scratch(x, kind, _ws_bytes(kind, *geo, *layout['ws_pad'], dt), st)
+    rc = getattr(L.load(), fn)(x.data_ptr(), dt, *geo, int(bool(need_b)), int(bool(need_kurt)), int(bool(need_relu)),
+                               ws.data_ptr(), mom.data_ptr(), stats.data_ptr(), st)
     if rc:
-        L.check(rc, 'cnnq_pc_stats_nhwc')
+        L.check(rc, fn)
     return stats, mom
 
 
-# What the entry points on contiguous bf16 / fp16 activations (pc_stats_half, qdq_bias_corrected_half) share on the host: who runs
-# native (_half_route_word behind _stats_half_native / _table_half_native) and how a tensor is admitted (_admit_half).
-def _half_route_word(cache, cast, fn, N, C, HW, dtype, *extra):
-    """cast(the last word of the report of the route function `fn`) for this class of contiguous layer - a function of N, C, HW
-    and the dtype alone - asked once per class with alignment 16 and kept in `cache`."""
-    key = (N, C, HW, dtype)
-    v = cache.get(key)
-    if v is None:
-        out = (ctypes.c_int32 * 4)()
-        L.check(getattr(L.load(), fn)(N, C, HW, _DTYPE_CODES.get(dtype, -1), 16, *extra, out), fn)
-        v = cache[key] = cast(out[3])
-    return v
+def pc_stats_nhwc(x, need_b=False, need_kurt=False, need_relu=False):
+    """pc_stats of a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is (DESIGN.md section 18; -sm
+    collect, smpc.py:45-79): _pc_stats_native over slabs of rows, 8 B/elem in fp32 and 4 in bf16 / fp16 for the full table.  A
+    tensor that is not dense channels_last (or CNNQ_NHWC=0, or a class of layer the route function sends back: copied, counted)
+    takes pc_stats, which is float32 only - a half tensor raises before anything is copied."""
+    x, site = _admit_nhwc(x, 'pc_stats_nhwc', 'stats', 'the statistics of a tensor that does not take the channels_last kernels')
+    if site is None:
+        N, C, HW = geometry(x)
+        return pc_stats(x, N, C, HW, need_b, need_kurt, need_relu, group=False)
+    return _pc_stats_native(site, x, need_b, need_kurt, need_relu)
 
 
 def _admit_half(x, what, f32_name):
-    """(x, N, C, HW, dtype code, raw stream) of a non-empty contiguous 4-D bf16 / fp16 tensor on the current device, as the
-    *_half entry points take it; anything else raises (f32_name: the function float32 takes): nothing is copied or upcast."""
+    """(x, site) of a non-empty contiguous 4-D bf16 / fp16 tensor on the current device, as the *_half entry points take it, geo =
+    (N, C, HW); anything else raises (f32_name: the function float32 takes): nothing is copied or upcast, so there is no fallback
+    and the site is never None."""
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise L.CnnqError('%s: x must be a CUDA/HIP tensor (there is no CPU path)' % what)
     if x.dtype not in _HALF_DTYPES:
@@ -479,7 +493,7 @@ def _admit_half(x, what, f32_name):
     if x.requires_grad:
         x = x.detach()
     N, C, HW = geometry(x)
-    return x, N, C, HW, _HALF_DTYPES[x.dtype], _raw_stream(x.device.index)
+    return x, (_HALF_LAYOUT, (N, C, HW), C, _HALF_DTYPES[x.dtype], _raw_stream(x.device.index))
 
 
 _STATS_HALF_NATIVE = {}
@@ -489,25 +503,15 @@ def _stats_half_native(N, C, HW, dtype):
     """Whether this class of layer collects its statistics on the contiguous bf16 / fp16 kernels: the "native" word of
     cnnq_pc_route_stats_dt's report (0: a class that measured slower native than through the upcast is sent back there).  The
     statistics manager (collects_native_half) and the tests patch the function and empty the cache by name."""
-    return _half_route_word(_STATS_HALF_NATIVE, bool, 'cnnq_pc_route_stats_dt', N, C, HW, dtype)
+    return _route_word(_STATS_HALF_NATIVE, (N, C, HW, dtype), bool, 'cnnq_pc_route_stats_dt', (N, C, HW), dtype)
 
 
 def pc_stats_half(x, need_b=False, need_kurt=False, need_relu=False):
     """pc_stats of a contiguous 4-D bf16 / fp16 activation, on the storage as it is (-sm collect,
-    smpc.py:45-79): cnnq_pc_stats_dt - pass A over (channel, batch split) workgroups, the merge, pass B when b or the kurtosis is
-    asked for, its merge - one host call, one cached workspace, 4 B/elem for the full table.  Returns (stats [NSTAT, C] f32, mom
-    [NMOM, C] f64) as pc_stats; rows nobody asked for are zero (B comes with pass B: need_b or need_kurt, as in pc_stats).  One
-    GPU: the statistics are this tensor's.  Anything else - a CPU tensor, float32, not 4-D, not contiguous - raises: nothing is
-    copied or upcast here."""
-    x, N, C, HW, dt, st = _admit_half(x, 'pc_stats_half', 'pc_stats')
-    stats = torch.empty((L.NSTAT, C), dtype=torch.float32, device=x.device)
-    mom = torch.empty((L.NMOM, C), dtype=torch.float64, device=x.device)
-    ws = _scratch(x, 'stats_half', _ws_bytes('stats_half', N, C, HW, dt), st)
-    rc = L.load().cnnq_pc_stats_dt(x.data_ptr(), dt, N, C, HW, int(bool(need_b)), int(bool(need_kurt)), int(bool(need_relu)),
-                                   ws.data_ptr(), mom.data_ptr(), stats.data_ptr(), st)
-    if rc:
-        L.check(rc, 'cnnq_pc_stats_dt')
-    return stats, mom
+    smpc.py:45-79): _pc_stats_native over (channel, batch split) workgroups, 4 B/elem for the full table.  Anything else - a CPU
+    tensor, float32, not 4-D, not contiguous - raises: nothing is copied or upcast here."""
+    x, site = _admit_half(x, 'pc_stats_half', 'pc_stats')
+    return _pc_stats_native(site, x, need_b, need_kurt, need_relu)
 
 
 def _xrank_plan(kind, x, N, C, HW, group, xr=None):
@@ -772,23 +776,29 @@ def pc_qdq(x, N, C, HW, qp, want_codes=False, out=None, hist=None, reverse=False
     return (y, codes) if want_codes else y
 
 
-def _pc_qdq_nhwc(x, qp, out, nbins=0, slot=None, st=None):
-    """pc_qdq on a dense channels_last x with the table qp (cnnq_pc_qdq_nhwc: the IEEE divide); y has x's layout.  slot (the
-    replica tables of _nhwc_hist_slot, st the stream they belong to): the pass also counts its codes into them, nbins bins
-    (cnnq_pc_qdq_hist_nhwc): (y, entropy)."""
-    C = x.shape[1]
+def _qdq_native(site, x, qp, out, nbins=0, slot=None):
+    """pc_qdq of a tensor on its site with the table qp (cnnq_pc_qdq_nhwc / cnnq_pc_qdq_dt: the IEEE divide); y has x's layout and
+    dtype.  slot (the replica tables of _nhwc_hist_slot / _half_hist_slot, on the site's stream): the pass also counts its codes
+    into them, nbins bins (cnnq_pc_qdq_hist_nhwc / cnnq_pc_qdq_hist_dt): (y, entropy)."""
+    layout, geo, C, dt, st = site
+    fn, mid, fn_hist = layout['qdq']
     y = _out_like(x, out)
     if slot is None:
-        rc = L.load().cnnq_pc_qdq_nhwc(x.data_ptr(), y.data_ptr(), _DTYPE_CODES[x.dtype], x.numel() // C, C, qp.data_ptr(),
-                                       _raw_stream(x.device.index))
+        rc = getattr(L.load(), fn)(x.data_ptr(), y.data_ptr(), dt, *geo, qp.data_ptr(), *mid, st)
         if rc:
-            L.check(rc, 'cnnq_pc_qdq_nhwc')
+            L.check(rc, fn)
         return y
-    rc = L.load().cnnq_pc_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), _DTYPE_CODES[x.dtype], x.numel() // C, C, qp.data_ptr(), nbins,
-                                        slot[0].data_ptr(), st)
+    rc = getattr(L.load(), fn_hist)(x.data_ptr(), y.data_ptr(), dt, *geo, qp.data_ptr(), int(nbins), slot[0].data_ptr(), st)
     if rc:
-        L.check(rc, 'cnnq_pc_qdq_hist_nhwc')
+        L.check(rc, fn_hist)
     return y, _replica_entropy(x, slot[0], slot[1], st)
+
+
+def _pc_qdq_nhwc(x, qp, out, nbins=0, slot=None, st=None):
+    """_qdq_native on a dense channels_last x that came through _dev_act_layout (st: the stream of the slot's tables)."""
+    C = x.shape[1]
+    return _qdq_native((_NHWC_LAYOUT, (x.numel() // C, C), C, _DTYPE_CODES[x.dtype], _raw_stream(x.device.index) if st is None else st),
+                       x, qp, out, nbins, slot)
 
 
 def _minmax_qdq_nhwc(x, num_bits, positive, out, slot=None, st=None):
@@ -1215,8 +1225,8 @@ def _entropy_half_native(N, C, HW, dtype, nbins=256):
     1 - config 2 with the entropy of its codes in one launch, 2 - the statistics launch and the counting pass, 0 - a class that
     measured slower native than through the upcast and is sent back there.  The quantizer (_pc_route, _clip_route) and the tests
     patch the function and empty the cache by name."""
-    return _half_route_word(_ENTROPY_HALF_NATIVE.setdefault(int(nbins), {}), int, 'cnnq_pc_route_qdq_hist_dt', N, C, HW, dtype,
-                            int(nbins), 1)
+    return _route_word(_ENTROPY_HALF_NATIVE.setdefault(int(nbins), {}), (N, C, HW, dtype), int, 'cnnq_pc_route_qdq_hist_dt',
+                       (N, C, HW), dtype, (int(nbins), 1))
 
 
 def _half_hist_slot(x, what, st):
@@ -1251,15 +1261,9 @@ def _minmax_qdq_half_entropy(x, N, C, HW, num_bits, positive, out, single_launch
 
 
 def _pc_qdq_half_entropy(x, N, C, HW, qp, nbins, out):
-    """pc_qdq on a contiguous bf16 / fp16 x with the table qp, the codes counted in nbins bins (cnnq_pc_qdq_hist_dt): (y, entropy)."""
-    y = _out_like(x, out)
+    """_qdq_native on a contiguous bf16 / fp16 x that came through _dev_act, the codes counted in nbins bins: (y, entropy)."""
     st = _raw_stream(x.device.index)
-    hist, ent_batched = _half_hist_slot(x, 'pc_qdq', st)
-    rc = L.load().cnnq_pc_qdq_hist_dt(x.data_ptr(), y.data_ptr(), _HALF_DTYPES[x.dtype], N, C, HW, qp.data_ptr(), int(nbins),
-                                      hist.data_ptr(), st)
-    if rc:
-        L.check(rc, 'cnnq_pc_qdq_hist_dt')
-    return y, _replica_entropy(x, hist, ent_batched, st)
+    return _qdq_native((_HALF_LAYOUT, (N, C, HW), C, _HALF_DTYPES[x.dtype], st), x, qp, out, nbins, _half_hist_slot(x, 'pc_qdq', st))
 
 
 _LOCAL_PLAN = {}    # per (N, C, HW): (workspace bytes, whether the one-GPU hot call hands the C side the group workspace)
@@ -1879,59 +1883,70 @@ def act_qdq_per_channel(x, num_bits, positive=False, clip='no', bit_alloc=False,
     return _result(y, codes, entropy, dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
 
 
+def _aciq_qdq_native(site, x, what, num_bits, positive, clip, bit_alloc, prior_is_b, target, round_mode, stats, out, want_parts, slot,
+                     allow=1):
+    """Config 3 (iq.py:327-352 -> 409-451: ACIQ clipping 'laplace' / 'gaus', optionally bit allocation) of a tensor on its site:
+    the statistics, the parameters and the Q/DQ in one host call with one cached workspace (cnnq_pc_aciq_qdq_nhwc /
+    cnnq_pc_aciq_qdq_dt; allow: the allow_single_launch word of a layout that takes one) - or, with `stats` (a float32 [NSTAT, C]
+    device table, -sm use), pc_params and the table-driven Q/DQ.  y has x's layout and dtype; want_parts: (y, dict(stats, qp,
+    diag)).  One GPU: the statistics are this tensor's.  slot (the replica tables of a want_entropy call): the Q/DQ pass counts its
+    codes into them (cnnq_pc_aciq_qdq_hist_*, or cnnq_pc_qdq_hist_* with `stats`) and the entropy follows y as
+    act_qdq_per_channel returns it - y, entropy [, parts]; inside an entropy_batch block it is filled by the block's one launch."""
+    layout, geo, C, dt, st = site
+    use_ba = bool(bit_alloc) and num_bits <= 4
+    if stats is not None:
+        if not _is_table(stats, torch.float32, (L.NSTAT, C), x.device):
+            raise L.CnnqError('%s: stats must be a contiguous float32 [%d, %d] device table' % (what, L.NSTAT, C))
+        qp, diag = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
+        parts = dict(stats=stats, qp=qp, diag=diag) if want_parts else None
+        if slot is None:
+            return _result(_qdq_native(site, x, qp, out), parts=parts)
+        y, entropy = _qdq_native(site, x, qp, out, _hist_bins(num_bits, use_ba), slot)
+        return _result(y, entropy=entropy, parts=parts)
+    fn, fn_hist, kind = layout['aciq']
+    cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
+    nbytes = _ws_bytes(kind, *geo, *layout['ws_pad'], dt)
+    y = _out_like(x, out)
+    if want_parts:
+        tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, C, dtype=torch.float32, device=x.device)
+        ws, tp = _scratch(x, kind, nbytes, st).data_ptr(), tabs.data_ptr()
+        parts = dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:])
+    else:
+        # the tables nobody outside the call reads follow the records in the cached workspace
+        ws = _scratch(x, kind, nbytes + (L.NSTAT + L.NQP + L.NDIAG) * C * 4, st).data_ptr()
+        tp, parts = ws + nbytes, None
+    if slot is not None:
+        rc = getattr(L.load(), fn_hist)(x.data_ptr(), y.data_ptr(), dt, *geo, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                        tp + (L.NSTAT + L.NQP) * C * 4, slot[0].data_ptr(), st)
+    else:
+        rc = getattr(L.load(), fn)(x.data_ptr(), y.data_ptr(), dt, *geo, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                   tp + (L.NSTAT + L.NQP) * C * 4, *((allow,) if layout['single'] else ()), st)
+    if rc:
+        L.check(rc, fn)
+    return _result(y, entropy=_replica_entropy(x, slot[0], slot[1], st) if slot is not None else None, parts=parts)
+
+
 def aciq_qdq_nhwc(x, num_bits, positive=False, clip='laplace', bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
                   stats=None, out=None, want_parts=False, want_entropy=False):
-    """Config 3 (iq.py:327-352 -> 409-451: ACIQ clipping 'laplace' / 'gaus', optionally bit allocation) on a dense channels_last
-    activation of fp32 / bf16 / fp16, on the storage as it is: cnnq_pc_aciq_qdq_nhwc - statistics over
-    slabs of rows, parameters, Q/DQ, one host call, one cached workspace - or, with `stats` ([NSTAT, C], -sm use), pc_params and
-    the table-driven Q/DQ.  y has x's layout and dtype; want_parts: (y, dict(stats, qp, diag)).  One GPU: the statistics are this
-    tensor's.  A tensor that is not dense channels_last (or CNNQ_NHWC=0: copied, counted) takes act_qdq_per_channel.
-    want_entropy: the Q/DQ pass counts its codes (cnnq_pc_aciq_qdq_hist_nhwc, or cnnq_pc_qdq_hist_nhwc
-    with `stats`) and the entropy follows y as act_qdq_per_channel returns it - y, entropy [, parts]; inside an entropy_batch
-    block it is filled by the block's one launch.  Who takes the counted copy instead: _nhwc_hist_slot."""
+    """_aciq_qdq_native on a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is:
+    the statistics over slabs of rows.  A tensor that is not dense channels_last (or CNNQ_NHWC=0: copied, counted) takes
+    act_qdq_per_channel, `stats` as it is.  want_entropy: who takes the counted copy instead of counting
+    native: _nhwc_hist_slot."""
     if clip not in ('laplace', 'gaus'):
         raise L.CnnqError("aciq_qdq_nhwc: clip must be 'laplace' or 'gaus', got %r" % (clip,))
     if want_entropy and num_bits > 8:
         raise L.CnnqError('aciq_qdq_nhwc: the ACIQ factor tables end at 8 bits')
-    x, geo = _admit_nhwc(x, 'aciq_qdq_nhwc', dev_first=True)
-    use_ba = bool(bit_alloc) and num_bits <= 4
-    hist = ent_batched = None
-    if want_entropy and geo is not None:
-        x, slot = _nhwc_hist_slot(x, 'aciq_qdq_nhwc', geo[3])
+    x, site = _admit_nhwc(x, 'aciq_qdq_nhwc', dev_first=True)
+    slot = None
+    if want_entropy and site is not None:
+        x, slot = _nhwc_hist_slot(x, 'aciq_qdq_nhwc', site[4])
         if slot is None:
-            geo = None
-        else:
-            hist, ent_batched = slot
-    if geo is None:
+            site = None
+    if site is None:
         return act_qdq_per_channel(x, num_bits, positive, clip, bit_alloc, prior_is_b, target, round_mode, group=False,
                                    want_parts=want_parts, stats=stats, out=out, want_entropy=want_entropy)
-    C, R, dt, st = geo
-    if stats is not None:
-        qp, diag = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
-        if want_entropy:
-            y, entropy = _pc_qdq_nhwc(x, qp, out, _hist_bins(num_bits, use_ba), slot, st)
-            return _result(y, entropy=entropy, parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
-        return _result(_pc_qdq_nhwc(x, qp, out), parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
-    cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
-    nbytes = _ws_bytes('aciq_nhwc', R, C, 1, dt)
-    y = _out_like(x, out)
-    if want_parts:
-        tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, C, dtype=torch.float32, device=x.device)
-        ws, tp = _scratch(x, 'aciq_nhwc', nbytes, st).data_ptr(), tabs.data_ptr()
-    else:
-        # the tables nobody outside the call reads follow the records in the cached workspace
-        ws = _scratch(x, 'aciq_nhwc', nbytes + (L.NSTAT + L.NQP + L.NDIAG) * C * 4, st).data_ptr()
-        tp = ws + nbytes
-    if want_entropy:
-        rc = L.load().cnnq_pc_aciq_qdq_hist_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
-                                                 tp + (L.NSTAT + L.NQP) * C * 4, hist.data_ptr(), st)
-    else:
-        rc = L.load().cnnq_pc_aciq_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
-                                            tp + (L.NSTAT + L.NQP) * C * 4, st)
-    if rc:
-        L.check(rc, 'cnnq_pc_aciq_qdq_nhwc')
-    return _result(y, entropy=_replica_entropy(x, hist, ent_batched, st) if want_entropy else None,
-                   parts=dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:]) if want_parts else None)
+    return _aciq_qdq_native(site, x, 'aciq_qdq_nhwc', num_bits, positive, clip, bit_alloc, prior_is_b, target, round_mode, stats, out,
+                            want_parts, slot)
 
 
 _ACIQ_HALF_NATIVE = {}
@@ -1944,60 +1959,29 @@ def _aciq_half_native(N, C, HW, dtype, bit_alloc=False, prior_is_b=False):
     (_half_aciq) and the tests patch the function and empty the cache by name."""
     cfg = _params_cfg(4, False, 'laplace', bit_alloc, prior_is_b, None, True, False)
     cache = _ACIQ_HALF_NATIVE.setdefault((bool(bit_alloc), bool(prior_is_b)), {})
-    return _half_route_word(cache, int, 'cnnq_pc_route_aciq_dt', N, C, HW, dtype, ctypes.byref(cfg), 1)
+    return _route_word(cache, (N, C, HW, dtype), int, 'cnnq_pc_route_aciq_dt', (N, C, HW), dtype, (ctypes.byref(cfg), 1))
 
 
 def aciq_qdq_half(x, num_bits, positive=False, clip='laplace', bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
                   stats=None, out=None, want_parts=False, single_launch=None, want_entropy=False):
-    """Config 3 (iq.py:327-352 -> 409-451: ACIQ clipping 'laplace' / 'gaus', optionally bit allocation) on a contiguous 4-D bf16 /
-    fp16 activation, on the storage as it is: cnnq_pc_aciq_qdq_dt - the statistics, the parameters and the
-    Q/DQ in one launch where a channel's batch population fits one workgroup's registers (behind pass A and the bit allocation
-    with -baa), else the chain of cnnq_pc_stats_dt, cnnq_pc_params and cnnq_pc_qdq_dt; one host call, one cached workspace - or,
-    with `stats` ([NSTAT, C], -sm use), pc_params and the table-driven Q/DQ.  y has x's dtype; want_parts: (y, dict(stats, qp,
-    diag)).  single_launch: None - the route function's choice; 0 - the chain; 2 - the resident form wherever the channel fits (the
-    chain elsewhere), for tests and A/B.  One GPU: the statistics are this tensor's.  Anything else - a CPU tensor, float32, not
-    4-D, not contiguous - raises: nothing is copied or upcast here.
-    want_entropy: the Q/DQ pass counts its codes (cnnq_pc_aciq_qdq_hist_dt - the chain, whatever
-    single_launch says - or cnnq_pc_qdq_hist_dt with `stats`) and the entropy follows y as aciq_qdq_nhwc returns it - y, entropy
-    [, parts]; inside an entropy_batch block it is filled by the block's one launch."""
+    """_aciq_qdq_native on a contiguous 4-D bf16 / fp16 activation, on the storage as it is: the statistics,
+    the parameters and the Q/DQ in one launch where a channel's batch population fits one workgroup's registers (behind pass A and
+    the bit allocation with -baa), else the chain of cnnq_pc_stats_dt, cnnq_pc_params and cnnq_pc_qdq_dt.  single_launch: None -
+    the route function's choice; 0 - the chain; 2 - the resident form wherever the channel fits (the chain elsewhere), for tests
+    and A/B.  Anything else - a CPU tensor, float32, not 4-D, not contiguous - raises: nothing is copied or upcast here.
+    want_entropy: the counting pass is the chain's, whatever single_launch says."""
     what = 'aciq_qdq_half'
     if clip not in ('laplace', 'gaus'):
         raise L.CnnqError("%s: clip must be 'laplace' or 'gaus', got %r" % (what, clip))
     if want_entropy and num_bits > 8:
         raise L.CnnqError('%s: the ACIQ factor tables end at 8 bits' % what)
-    x, N, C, HW, dt, st = _admit_half(x, what, 'act_qdq_per_channel')
-    use_ba = bool(bit_alloc) and num_bits <= 4
-    if stats is not None:
-        if not _is_table(stats, torch.float32, (L.NSTAT, C), x.device):
-            raise L.CnnqError('%s: stats must be a contiguous float32 [%d, %d] device table' % (what, L.NSTAT, C))
-        qp, diag = pc_params(stats, num_bits, positive, clip, use_ba, prior_is_b, target, round_mode)
-        if want_entropy:
-            y, entropy = _pc_qdq_half_entropy(x, N, C, HW, qp, _hist_bins(num_bits, use_ba), out)
-            return _result(y, entropy=entropy, parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
-        return _result(pc_qdq(x, N, C, HW, qp, out=out), parts=dict(stats=stats, qp=qp, diag=diag) if want_parts else None)
-    if single_launch not in (None, 0, 1, 2):
+    x, site = _admit_half(x, what, 'act_qdq_per_channel')
+    if stats is None and single_launch not in (None, 0, 1, 2):
         raise L.CnnqError('%s: single_launch must be None, 0, 1 or 2, got %r' % (what, single_launch))
-    cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
-    nbytes = _ws_bytes('aciq_half', N, C, HW, dt)
-    y = _out_like(x, out)
-    if want_parts:
-        tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, C, dtype=torch.float32, device=x.device)
-        ws, tp = _scratch(x, 'aciq_half', nbytes, st).data_ptr(), tabs.data_ptr()
-    else:
-        # the tables nobody outside the call reads follow the records in the cached workspace
-        ws = _scratch(x, 'aciq_half', nbytes + (L.NSTAT + L.NQP + L.NDIAG) * C * 4, st).data_ptr()
-        tp = ws + nbytes
-    hist = ent_batched = None
-    if want_entropy:
-        hist, ent_batched = _half_hist_slot(x, what, st)
-        rc = L.load().cnnq_pc_aciq_qdq_hist_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
-                                               tp + (L.NSTAT + L.NQP) * C * 4, hist.data_ptr(), st)
-    else:
-        rc = L.load().cnnq_pc_aciq_qdq_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
-                                          tp + (L.NSTAT + L.NQP) * C * 4, 1 if single_launch is None else int(single_launch), st)
-    if rc:
-        L.check(rc, 'cnnq_pc_aciq_qdq_dt')
-    return _result(y, entropy=_replica_entropy(x, hist, ent_batched, st) if want_entropy else None, parts=dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:]) if want_parts else None)
+    # (the counting pass of a table-driven call reports a missing replica table under pc_qdq's name)
+    slot = _half_hist_slot(x, what if stats is None else 'pc_qdq', site[4]) if want_entropy else None
+    return _aciq_qdq_native(site, x, what, num_bits, positive, clip, bit_alloc, prior_is_b, target, round_mode, stats, out, want_parts,
+                            slot, 1 if single_launch is None or stats is not None else int(single_launch))
 
 
 def weight_correction(w, w_q, vcorr=False, bcorr=False):
@@ -2051,28 +2035,36 @@ def qdq_bias_corrected(x, N, C, HW, qp, relu_first, group=None, out=None, want_p
     return _result(y, parts=dict(sums=sums, bias=bias) if want_parts else None)
 
 
+def _qdq_bias_corrected_native(site, x, what, qp, relu_first, out, want_parts, allow=1):
+    """qdq_bias_corrected of a tensor on its site in one host call with one cached workspace (cnnq_pc_qdq_bcorr_nhwc /
+    cnnq_pc_qdq_bcorr_dt; allow: the allow_single_launch word of a layout that takes one): the per-channel sums, the bias, the
+    fused quantize + correct pass.  qp: a float32 [NQP, C] device table.  y has x's layout and dtype; want_parts: (y, dict(sums
+    [3, C] float64 = {sum x', sum q, count(x' > 0)}, bias [C])).  One GPU: the sums are this tensor's."""
+    layout, geo, C, dt, st = site
+    if not _is_table(qp, torch.float32, (L.NQP, C), x.device):
+        raise L.CnnqError('%s: qp must be a contiguous float32 [%d, %d] device table' % (what, L.NQP, C))
+    fn, kind = layout['bcorr']
+    nbytes = _ws_bytes(kind, *geo, *layout['ws_pad'], dt)
+    y = _out_like(x, out)
+    ws, sp, bp, parts = _bcorr_buffers(x, kind, nbytes, C, want_parts, st)
+    rc = getattr(L.load(), fn)(x.data_ptr(), y.data_ptr(), dt, *geo, qp.data_ptr(), int(bool(relu_first)), ws, sp, bp,
+                               *((allow,) if layout['single'] else ()), st)
+    if rc:
+        L.check(rc, fn)
+    return _result(y, parts=parts)
+
+
 def qdq_bias_corrected_nhwc(x, qp, relu_first, out=None, want_parts=False):
-    """qdq_bias_corrected on a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is (DESIGN.md section
-    15): cnnq_pc_qdq_bcorr_nhwc - the per-channel sums over slabs of rows, the bias, the fused quantize + correct pass; one host
-    call, one cached workspace - 12 B/elem in fp32, 6 in bf16 / fp16.  y has x's layout and dtype; want_parts: (y, dict(sums
-    [3, C] float64 = {sum x', sum q, count(x' > 0)}, bias [C])).  One GPU: the sums are this tensor's.  A tensor that is not
-    dense channels_last (or CNNQ_NHWC=0: copied, counted) takes qdq_bias_corrected, which is float32 only."""
-    x, geo = _admit_nhwc(x, 'qdq_bias_corrected_nhwc', dev_first=True)
-    if geo is None:
+    """_qdq_bias_corrected_native on a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is (DESIGN.md
+    section 15): the sums over slabs of rows, 12 B/elem in fp32, 6 in bf16 / fp16.  A tensor that is not dense channels_last (or
+    CNNQ_NHWC=0: copied, counted) takes qdq_bias_corrected, which is float32 only."""
+    x, site = _admit_nhwc(x, 'qdq_bias_corrected_nhwc', dev_first=True)
+    if site is None:
         if x.dtype != torch.float32:
             _half_only('qdq_bias_corrected_nhwc', 'the bias correction of a tensor that is not dense channels_last')
         N, C, HW = geometry(x)
         return qdq_bias_corrected(x, N, C, HW, qp, relu_first, out=out, want_parts=want_parts)
-    C, R, dt, st = geo
-    if not _is_table(qp, torch.float32, (L.NQP, C), x.device):
-        raise L.CnnqError('qdq_bias_corrected_nhwc: qp must be a contiguous float32 [%d, %d] device table' % (L.NQP, C))
-    nbytes = _ws_bytes('bcorr_nhwc', R, C, 1, dt)
-    y = _out_like(x, out)
-    ws, sp, bp, parts = _bcorr_buffers(x, 'bcorr_nhwc', nbytes, C, want_parts, st)
-    rc = L.load().cnnq_pc_qdq_bcorr_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, qp.data_ptr(), int(bool(relu_first)), ws, sp, bp, st)
-    if rc:
-        L.check(rc, 'cnnq_pc_qdq_bcorr_nhwc')
-    return _result(y, parts=parts)
+    return _qdq_bias_corrected_native(site, x, 'qdq_bias_corrected_nhwc', qp, relu_first, out, want_parts)
 
 
 _TABLE_HALF_NATIVE = {}
@@ -2082,38 +2074,27 @@ def _table_half_native(N, C, HW, dtype):
     """The route word of cnnq_pc_route_qdq_bcorr_dt's report for this class of contiguous bf16 / fp16 layer: 1 - the table-driven
     Q/DQ with the bias correction in one launch, 2 - in two passes, 0 - a class that measured slower native than through the upcast
     and is sent back there.  The quantizer (_half_table) and the tests patch the function and empty the cache by name."""
-    return _half_route_word(_TABLE_HALF_NATIVE, int, 'cnnq_pc_route_qdq_bcorr_dt', N, C, HW, dtype, 1)
+    return _route_word(_TABLE_HALF_NATIVE, (N, C, HW, dtype), int, 'cnnq_pc_route_qdq_bcorr_dt', (N, C, HW), dtype, (1,))
 
 
 def qdq_bias_corrected_half(x, qp, relu_first, out=None, want_parts=False, single_launch=None):
-    """qdq_bias_corrected on a contiguous 4-D bf16 / fp16 activation, on the storage as it is (-sm use with
-    -bca): cnnq_pc_qdq_bcorr_dt - the per-channel sums over (channel, batch split) workgroups, the bias, the fused quantize +
-    correct pass, 6 B/elem; or all three in one launch, 4 B/elem, where a channel's batch population fits one workgroup's registers
-    - one host call, one cached workspace.  y has x's dtype; want_parts: (y, dict(sums [3, C] float64 = {sum x', sum q,
-    count(x' > 0)}, bias [C])).  single_launch: None - the route function's choice; True / False - the single launch (raises where
-    the channel does not fit) / the two passes, for tests and A/B.  One GPU: the sums are this tensor's.  Anything else - a CPU
-    tensor, float32, not 4-D, not contiguous, a qp that is not a float32 [NQP, C] device table - raises: nothing is copied or upcast
-    here."""
+    """_qdq_bias_corrected_native on a contiguous 4-D bf16 / fp16 activation, on the storage as it is (-sm
+    use with -bca): the sums over (channel, batch split) workgroups and the fused pass, 6 B/elem; or all three steps in one launch,
+    4 B/elem, where a channel's batch population fits one workgroup's registers.  single_launch: None - the route function's
+    choice; True / False - the single launch (raises where the channel does not fit) / the two passes, for tests and A/B.
+    Anything else - a CPU tensor, float32, not 4-D, not contiguous - raises: nothing is copied or upcast here."""
     what = 'qdq_bias_corrected_half'
-    x, N, C, HW, dt, st = _admit_half(x, what, 'qdq_bias_corrected')
-    if not _is_table(qp, torch.float32, (L.NQP, C), x.device):
-        raise L.CnnqError('%s: qp must be a contiguous float32 [%d, %d] device table' % (what, L.NQP, C))
-    y = _out_like(x, out)
-    allow = 1 if single_launch is None else (2 if single_launch else 0)
+    x, site = _admit_half(x, what, 'qdq_bias_corrected')
     if single_launch:
+        out = _out_like(x, out)              # (the forced form asks its route at the alignment the pair has)
         route = (ctypes.c_int32 * 4)()
-        bits = x.data_ptr() | y.data_ptr() | 16
+        bits = x.data_ptr() | out.data_ptr() | 16
         align = bits & -bits                 # the alignment x and y share, 16 at most
-        L.check(L.load().cnnq_pc_route_qdq_bcorr_dt(N, C, HW, dt, align, 2, route), 'cnnq_pc_route_qdq_bcorr_dt')
+        L.check(L.load().cnnq_pc_route_qdq_bcorr_dt(*site[1], site[3], align, 2, route), 'cnnq_pc_route_qdq_bcorr_dt')
         if route[3] != 1:
-            raise L.CnnqError('%s: no single launch for [%d, %d, %d] at piece width %d' % (what, N, C, HW, route[0]))
-    nbytes = _ws_bytes('bcorr_half', N, C, HW, dt)
-    ws, sp, bp, parts = _bcorr_buffers(x, 'bcorr_half', nbytes, C, want_parts, st)
-    rc = L.load().cnnq_pc_qdq_bcorr_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, qp.data_ptr(), int(bool(relu_first)), ws, sp, bp,
-                                       allow, st)
-    if rc:
-        L.check(rc, 'cnnq_pc_qdq_bcorr_dt')
-    return _result(y, parts=parts)
+            raise L.CnnqError('%s: no single launch for [%d, %d, %d] at piece width %d' % ((what,) + site[1] + (route[0],)))
+    return _qdq_bias_corrected_native(site, x, what, qp, relu_first, out, want_parts,
+                                      1 if single_launch is None else (2 if single_launch else 0))
 
 
 def _bcorr_buffers(x, tag, nbytes, C, want_parts, st):
@@ -2214,55 +2195,62 @@ def mid_tread_qdq_single(x, N, C, HW, target, sym, tabs, want_entropy=False, wan
                       parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
 
 
-def mid_tread_qdq_nhwc(x, target, sym, want_entropy=False, stats=None, out=None, want_parts=False):
+def _mid_tread_qdq_native(site, x, what, target, sym, want_entropy, stats, out, want_parts, allow=1):
     """Config 5 with clipping (iq.py:170-225: mid-tread quantization with per-channel bin allocation; want_entropy: the entropy of
-    the codes, -me) on a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is:
-    cnnq_pc_midtread_nhwc - statistics over slabs of rows, step sizes and clamp bounds, Q/DQ with the code histogram, one host
-    call, one cached workspace - or, with `stats` ([NSTAT, C]), cnnq_pc_midtread_params on that table and the table-driven pass.
-    16 B/elem in fp32, 8 in bf16 / fp16.  y has x's layout and dtype.  Returns what mid_tread_qdq returns: (y, entropy or None
-    [, dict(stats, mt, hist)]); inside an entropy_batch block the entropy is filled by the block's one launch.  One GPU: the
-    statistics are this tensor's.  A tensor that is not dense channels_last (or CNNQ_NHWC=0, or a class of layer the route function
-    sends back: copied, counted) takes mid_tread_qdq, which is float32 only - a half tensor raises before anything is copied -
-    and knows neither `stats` nor `out`."""
-    x, geo = _admit_nhwc(x, 'mid_tread_qdq_nhwc', 'midtread',
-                         'the mid-tread quantization of a tensor that does not take the channels_last kernels')
-    if geo is None:
-        if stats is not None or out is not None:
-            raise L.CnnqError('mid_tread_qdq_nhwc: stats= and out= need a dense channels_last tensor')
-        return mid_tread_qdq(x, target, clip=True, sym=sym, group=False, want_entropy=want_entropy, want_parts=want_parts)
+    the codes, -me) of a tensor on its site: the statistics, the step sizes and clamp bounds and the Q/DQ with the code histogram
+    in one host call with one cached workspace (cnnq_pc_midtread_nhwc / cnnq_pc_midtread_dt; allow: the allow_single_launch word
+    of a layout that takes one) - or, with `stats` (a float32 [NSTAT, C] device table), cnnq_pc_midtread_params on that table and
+    the table-driven pass.  y has x's layout and dtype.  Returns what mid_tread_qdq returns: (y, entropy or None [, dict(stats,
+    mt, hist)]); inside an entropy_batch block the entropy is filled by the block's one launch.  One GPU: the statistics are this
+    tensor's."""
+    layout, geo, C, dt, st = site
+    fn, fn_table, kind = layout['midtread']
     lib = L.load()
-    C, R, dt, st = geo
     tabs = _midtread_tables(x.device)
+    if stats is not None and not _is_table(stats, torch.float32, (L.NSTAT, C), x.device):
+        raise L.CnnqError('%s: stats must be a contiguous float32 [%d, %d] device table' % (what, L.NSTAT, C))
     y = _out_like(x, out)
     if stats is not None:
-        if not _is_table(stats, torch.float32, (L.NSTAT, C), x.device):
-            raise L.CnnqError('mid_tread_qdq_nhwc: stats must be a contiguous float32 [%d, %d] device table' % (L.NSTAT, C))
         mt = torch.empty((L.NMT, C), dtype=torch.float32, device=x.device)
         L.check(lib.cnnq_pc_midtread_params(_ptr(stats), C, float(target), 1, int(bool(sym)), _ptr(tabs), tabs.shape[1], _ptr(mt), st),
                 'cnnq_pc_midtread_params')
         hist = torch.zeros(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None
-        rc = lib.cnnq_pc_midtread_qdq_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, _ptr(mt), _ptr(hist), st)
+        rc = getattr(lib, fn_table)(x.data_ptr(), y.data_ptr(), dt, *geo, _ptr(mt), _ptr(hist), st)
         if rc:
-            L.check(rc, 'cnnq_pc_midtread_qdq_nhwc')
+            L.check(rc, fn_table)
     else:
-        nbytes = _ws_bytes('aciq_nhwc', R, C, 1, dt)
+        nbytes = _ws_bytes(kind, *geo, *layout['ws_pad'], dt)
         hist = torch.empty(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None     # zeroed by the call
         if want_parts or want_entropy:
             # (the entropy launch reads mt behind the call - at the end of the block inside an entropy_batch)
             out_tabs = torch.empty((L.NSTAT + L.NMT, C), dtype=torch.float32, device=x.device)
             stats, mt = out_tabs[:L.NSTAT], out_tabs[L.NSTAT:]
-            ws, tp = _scratch(x, 'aciq_nhwc', nbytes, st).data_ptr(), out_tabs.data_ptr()
+            ws, tp = _scratch(x, kind, nbytes, st).data_ptr(), out_tabs.data_ptr()
         else:
             # the tables nobody outside the call reads follow the records in the cached workspace
-            ws = _scratch(x, 'aciq_nhwc', nbytes + (L.NSTAT + L.NMT) * C * 4, st).data_ptr()
+            ws = _scratch(x, kind, nbytes + (L.NSTAT + L.NMT) * C * 4, st).data_ptr()
             tp = ws + nbytes
             mt = None
-        rc = lib.cnnq_pc_midtread_nhwc(x.data_ptr(), y.data_ptr(), dt, R, C, float(target), int(bool(sym)), _ptr(tabs), tabs.shape[1],
-                                       ws, tp, tp + L.NSTAT * C * 4, _ptr(hist), st)
+        rc = getattr(lib, fn)(x.data_ptr(), y.data_ptr(), dt, *geo, float(target), int(bool(sym)), _ptr(tabs), tabs.shape[1],
+                              ws, tp, tp + L.NSTAT * C * 4, _ptr(hist), *((allow,) if layout['single'] else ()), st)
         if rc:
-            L.check(rc, 'cnnq_pc_midtread_nhwc')
+            L.check(rc, fn)
     return _mt_result(y, _mt_entropy_here(x, hist, mt, C, st) if want_entropy else None,
                       parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
+
+
+def mid_tread_qdq_nhwc(x, target, sym, want_entropy=False, stats=None, out=None, want_parts=False):
+    """_mid_tread_qdq_native on a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it is (DESIGN.md section
+    16): the statistics over slabs of rows, 16 B/elem in fp32, 8 in bf16 / fp16.  A tensor that is not dense channels_last (or
+    CNNQ_NHWC=0, or a class of layer the route function sends back: copied, counted) takes mid_tread_qdq, which is float32 only -
+    a half tensor raises before anything is copied - and knows neither `stats` nor `out`."""
+    x, site = _admit_nhwc(x, 'mid_tread_qdq_nhwc', 'midtread',
+                          'the mid-tread quantization of a tensor that does not take the channels_last kernels')
+    if site is None:
+        if stats is not None or out is not None:
+            raise L.CnnqError('mid_tread_qdq_nhwc: stats= and out= need a dense channels_last tensor')
+        return mid_tread_qdq(x, target, clip=True, sym=sym, group=False, want_entropy=want_entropy, want_parts=want_parts)
+    return _mid_tread_qdq_native(site, x, 'mid_tread_qdq_nhwc', target, sym, want_entropy, stats, out, want_parts)
 
 
 _MIDTREAD_HALF_NATIVE = {}
@@ -2273,58 +2261,23 @@ def _midtread_half_native(N, C, HW, dtype, hist=False):
     the code histogram: 3 - pass A and the bin allocation in front of the resident launch, 2 - the chain, 0 - a class that measured
     slower native than through the upcast and is sent back there.  The quantizer (_midtread_route) and the tests patch the function
     and empty the cache by name."""
-    return _half_route_word(_MIDTREAD_HALF_NATIVE.setdefault(bool(hist), {}), int, 'cnnq_pc_route_midtread_dt', N, C, HW, dtype,
-                            int(bool(hist)), 1)
+    return _route_word(_MIDTREAD_HALF_NATIVE.setdefault(bool(hist), {}), (N, C, HW, dtype), int, 'cnnq_pc_route_midtread_dt',
+                       (N, C, HW), dtype, (int(bool(hist)), 1))
 
 
 def mid_tread_qdq_half(x, target, sym, want_entropy=False, stats=None, out=None, want_parts=False, single_launch=None):
-    """Config 5 with clipping (iq.py:170-225: mid-tread quantization with per-channel bin allocation; want_entropy: the entropy of
-    the codes, -me) on a contiguous 4-D bf16 / fp16 activation, on the storage as it is:
-    cnnq_pc_midtread_dt - pass A, the bin allocation and one launch that keeps a channel in registers for b, the step size, the
-    clamp bounds and the Q/DQ with the code histogram where the channel's batch population fits, else the chain of
-    cnnq_pc_stats_dt, cnnq_pc_midtread_params and cnnq_pc_midtread_qdq_dt; one host call, one cached workspace - or, with `stats`
-    ([NSTAT, C]), cnnq_pc_midtread_params on that table and the table-driven pass.  8 B/elem as a chain, 6 resident.  y has x's
-    dtype.  Returns what mid_tread_qdq_nhwc returns: (y, entropy or None [, dict(stats, mt, hist)]); inside an entropy_batch block
-    the entropy is filled by the block's one launch.  single_launch: None - the route function's choice; 0 - the chain; 2 - the
-    resident form wherever the channel fits (the chain elsewhere), for tests and A/B.  One GPU: the statistics are this tensor's.
-    Anything else - a CPU tensor, float32, not 4-D, not contiguous - raises: nothing is copied or upcast here."""
+    """_mid_tread_qdq_native on a contiguous 4-D bf16 / fp16 activation, on the storage as it is: pass A, the
+    bin allocation and one launch that keeps a channel in registers for b, the step size, the clamp bounds and the Q/DQ with the
+    code histogram where the channel's batch population fits, else the chain of cnnq_pc_stats_dt, cnnq_pc_midtread_params and
+    cnnq_pc_midtread_qdq_dt.  8 B/elem as a chain, 6 resident.  single_launch: None - the route function's choice; 0 - the chain;
+    2 - the resident form wherever the channel fits (the chain elsewhere), for tests and A/B.  Anything else - a CPU tensor,
+    float32, not 4-D, not contiguous - raises: nothing is copied or upcast here."""
     what = 'mid_tread_qdq_half'
-    x, N, C, HW, dt, st = _admit_half(x, what, 'mid_tread_qdq')
-    lib = L.load()
-    tabs = _midtread_tables(x.device)
-    if stats is not None:
-        if not _is_table(stats, torch.float32, (L.NSTAT, C), x.device):
-            raise L.CnnqError('%s: stats must be a contiguous float32 [%d, %d] device table' % (what, L.NSTAT, C))
-        y = _out_like(x, out)
-        mt = torch.empty((L.NMT, C), dtype=torch.float32, device=x.device)
-        L.check(lib.cnnq_pc_midtread_params(_ptr(stats), C, float(target), 1, int(bool(sym)), _ptr(tabs), tabs.shape[1], _ptr(mt), st),
-                'cnnq_pc_midtread_params')
-        hist = torch.zeros(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None
-        rc = lib.cnnq_pc_midtread_qdq_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, _ptr(mt), _ptr(hist), st)
-        if rc:
-            L.check(rc, 'cnnq_pc_midtread_qdq_dt')
-    else:
-        if single_launch not in (None, 0, 1, 2):
-            raise L.CnnqError('%s: single_launch must be None, 0, 1 or 2, got %r' % (what, single_launch))
-        y = _out_like(x, out)
-        nbytes = _ws_bytes('midtread_half', N, C, HW, dt)
-        hist = torch.empty(L.mt_hist_words(C), dtype=torch.int64, device=x.device) if want_entropy else None     # zeroed by the call
-        if want_parts or want_entropy:
-            # (the entropy launch reads mt behind the call - at the end of the block inside an entropy_batch)
-            out_tabs = torch.empty((L.NSTAT + L.NMT, C), dtype=torch.float32, device=x.device)
-            stats, mt = out_tabs[:L.NSTAT], out_tabs[L.NSTAT:]
-            ws, tp = _scratch(x, 'midtread_half', nbytes, st).data_ptr(), out_tabs.data_ptr()
-        else:
-            # the tables nobody outside the call reads follow the records in the cached workspace
-            ws = _scratch(x, 'midtread_half', nbytes + (L.NSTAT + L.NMT) * C * 4, st).data_ptr()
-            tp = ws + nbytes
-            mt = None
-        rc = lib.cnnq_pc_midtread_dt(x.data_ptr(), y.data_ptr(), dt, N, C, HW, float(target), int(bool(sym)), _ptr(tabs), tabs.shape[1],
-                                     ws, tp, tp + L.NSTAT * C * 4, _ptr(hist), 1 if single_launch is None else int(single_launch), st)
-        if rc:
-            L.check(rc, 'cnnq_pc_midtread_dt')
-    return _mt_result(y, _mt_entropy_here(x, hist, mt, C, st) if want_entropy else None,
-                      parts=dict(stats=stats, mt=mt, hist=hist) if want_parts else None)
+    x, site = _admit_half(x, what, 'mid_tread_qdq')
+    if stats is None and single_launch not in (None, 0, 1, 2):
+        raise L.CnnqError('%s: single_launch must be None, 0, 1 or 2, got %r' % (what, single_launch))
+    return _mid_tread_qdq_native(site, x, what, target, sym, want_entropy, stats, out, want_parts,
+                                 1 if single_launch is None or stats is not None else int(single_launch))
 
 
 def _mt_entropy_here(x, hist, mt, C, st):

@@ -1,6 +1,7 @@
 """Host microseconds per call of the ops entry points on tensors so small that the GPU work hides behind the host's: what the
 Python layer itself costs (argument checks, cached plans and workspaces, the ctypes call).  One line per leg; the NCHW legs on a
-contiguous [2, 8, 4, 4] tensor, the channels_last legs on the same shape in channels_last storage, fp32 and bf16.  A leg is timed
+contiguous [2, 8, 4, 4] tensor, the channels_last legs on the same shape in channels_last storage, fp32 and bf16, the half legs on
+the same shape in contiguous bf16.  A leg is timed
 in BLOCKS blocks of CALLS calls; the fastest block is the figure to compare (the host's own noise only ever adds), the median
 says how noisy the run was.
 
@@ -32,6 +33,13 @@ for dtype, tag in ((torch.float32, 'fp32'), (torch.bfloat16, 'bf16')):
              ('nhwc %s mid_tread_qdq_nhwc' % tag, lambda xc=xc: ops.mid_tread_qdq_nhwc(xc, 4., True)),
              ('nhwc %s pc_stats_nhwc' % tag, lambda xc=xc: ops.pc_stats_nhwc(xc, need_b=True)),
              ('nhwc %s minmax_quantize_packed_nhwc' % tag, lambda xc=xc: ops.minmax_quantize_packed_nhwc(xc, 4))]
+xh = x.to(torch.bfloat16).contiguous()
+qph, _ = ops.pc_params(ops.pc_stats_half(xh, need_b=True)[0], 4, clip='laplace')
+legs += [('half bf16 pc_stats_half', lambda: ops.pc_stats_half(xh, need_b=True)),
+         ('half bf16 aciq_qdq_half', lambda: ops.aciq_qdq_half(xh, 4)),
+         ('half bf16 qdq_bias_corrected_half', lambda: ops.qdq_bias_corrected_half(xh, qph, True)),
+         ('half bf16 mid_tread_qdq_half', lambda: ops.mid_tread_qdq_half(xh, 4., True)),
+         ('half bf16 act_qdq_per_channel cfg2', lambda: ops.act_qdq_per_channel(xh, 4))]
 print('%s, %d blocks of %d calls per leg' % (L.load().cnnq_version().decode(), BLOCKS, CALLS))
 for name, fn in legs:
     for _ in range(50):
