@@ -474,35 +474,7 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_fused_fl
     slots_leave(grp_lines(ws.cnt, c, g.Gs, 0, 1), member, g.Gs, slots, g.Gs, &sh_timed_out);
 }
 
-// ---- row-piece tiles (the geometry of k_mmq_group: a member is <= 256 float4 columns x <= K samples) ----------------
-// (group, member) -> tile, for any workgroup (the cold path walks every member of its group)
-__device__ __forceinline__ RBlk rblk_at(const Geo& g, int group, int member) {
-    RBlk r;
-    r.group = group;
-    r.member = member;
-    int s;
-    if (g.mode == 1) {
-        const int cpc = g.HW / 4;
-        s = member / g.nb;
-        const int bb = member - s * g.nb;
-        const int c = g.cbeg + group;
-        r.b.c0 = c;
-        r.b.c1 = c + 1;
-        r.b.col0 = c * cpc + bb * g.w;
-        r.b.col1 = min(r.b.col0 + g.w, (c + 1) * cpc);
-    } else {
-        s = member;
-        r.b.c0 = g.cbeg + group * g.k;
-        r.b.c1 = min(g.cbeg + g.Cn, r.b.c0 + g.k);
-        r.b.col0 = (int)(((int64_t)r.b.c0 * g.HW) / 4);
-        r.b.col1 = (int)(((int64_t)r.b.c1 * g.HW) / 4);
-    }
-    r.b.n0 = (int)(((int64_t)s * g.N) / g.S);
-    r.b.n1 = (int)(((int64_t)(s + 1) * g.N) / g.S);
-    r.b.grp = s;
-    return r;
-}
-
+// ---- row-piece tiles (RTile, cnnq_group.hip.h: a member is <= 256 float4 columns x <= K samples) ---------------------
 // per-lane sums -> per-channel sums of the workgroup's tile in sh_sum[c1 - c0], in a fixed order (the layout of
 // wg_channel_minmax: mode 1 - one channel, all lanes; mode 2 - epc LDS entries per channel)
 template <int A>
@@ -624,48 +596,41 @@ __global__ void __launch_bounds__(TPB, (fused_group_waves<K, OUT, MODE, XR>())) 
     const Blk& b = rb.b;
     const int tid = threadIdx.x;
     const int nch = b.c1 - b.c0;
-    const int col = b.col0 + tid;
-    const bool ok = col < b.col1;
-    const unsigned colc = (unsigned)(ok ? col : b.col0);   // idle lanes re-read the block's first column; results discarded
-    const int nrows = b.n1 - b.n0;        // 1 .. K
-    const size_t base = (size_t)b.n0 * (size_t)g.P + (size_t)colc * 4;
+    RTile<K> t;
+    t.place(g, b, tid);
     // the means of the block's channels (one per lane, issued in front of the tile; MAXCH <= TPB)
     static_assert(MAXCH <= TPB, "one staging lane per channel");
     const float r_mean = tid < nch ? aa.stats[(size_t)CNNQ_STAT_MEAN * g.C + b.c0 + tid] : 0.f;
 
-    // ---- the tile: K 16-byte loads per lane, issued back to back (rows past the tile re-read its last row)
+    // ---- the tile (RTile::load)
     float v[K][4];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const int r = j < nrows ? j : nrows - 1;
-        ldv_nt<4>(x + base + (size_t)r * (size_t)g.P, v[j]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
+    t.template load<true>(g, x, v);
     if (tid < nch) sh_mean[tid] = r_mean;
     __syncthreads();
-    float mean[A];
+    // a row of a tile placed at this workgroup's block or at another member's: sum |x - mean| per channel of the lane
+    const auto absdev_row = [&](const float (&q)[4], const float (&mean)[A], double (&sa)[A]) {
+        if constexpr (A == 1) {
+            absdev_step(q, mean[0], true, sa[0]);
+        } else {
 #pragma unroll
-    for (int a = 0; a < A; ++a) mean[a] = sh_mean[(int)((colc * 4u + (unsigned)a) / (unsigned)g.HW) - b.c0];
+            for (int e = 0; e < 4; ++e) sa[e] += (double)fabsf(q[e] - mean[e]);
+        }
+    };
+    float mean[A];
     double sa[A];
 #pragma unroll
-    for (int a = 0; a < A; ++a) sa[a] = 0.;
-    // (a uniform branch per step, not a select: 32 lane masks held in scalar registers next to the tile made the
-    //  allocator spill the tile itself)
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        if (j < nrows) {
-            if constexpr (A == 1) {
-                absdev_step(v[j], mean[0], true, sa[0]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sa[e] += (double)fabsf(v[j][e] - mean[e]);
-            }
-        }
+    for (int a = 0; a < A; ++a) {
+        mean[a] = sh_mean[t.chan(g, b, a)];
+        sa[a] = 0.;
     }
-    wg_channel_sums<A>(g, b, ok, sa, l_a, sh_sum);
+    // (the iteration of RTile::rows, spelled out: through it the two K = 32 instances with the cross-rank stage spilled five registers)
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (j < t.nrows) absdev_row(v[j], mean, sa);
+    wg_channel_sums<A>(g, b, t.ok, sa, l_a, sh_sum);
 
     // ---- publish this workgroup's sums (a sum IS the arrival), wait for the group
-    const int kk = (g.mode == 1) ? 1 : g.k;
+    const int kk = t.kk(g);
     unsigned long long* slots = ws.slots + (size_t)rb.group * ws.gstride;    // zero at rest
     for (int ch = tid; ch < nch; ch += TPB)
         __hip_atomic_store(slots + (size_t)rb.member * kk + ch, slot_of_sum(sh_sum[ch]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -690,30 +655,17 @@ __global__ void __launch_bounds__(TPB, (fused_group_waves<K, OUT, MODE, XR>())) 
         unsigned long long* tab = ws.part + (size_t)rb.group * ws.gstride;
         for (int m = 0; m < Gs; ++m) {
             const RBlk mb = rblk_at(g, rb.group, m);
-            const int mcol = mb.b.col0 + tid;
-            const bool mok = mcol < mb.b.col1;
-            const int mcolc = mok ? mcol : mb.b.col0;
-            const int mrows = mb.b.n1 - mb.b.n0;
+            RTile<K> mt;
+            mt.place(g, mb.b, tid);
             float mmean[A];
-#pragma unroll
-            for (int a = 0; a < A; ++a) mmean[a] = sh_mean[(int)(((unsigned)mcolc * 4u + (unsigned)a) / (unsigned)g.HW) - mb.b.c0];
             double s2[A];
 #pragma unroll
-            for (int a = 0; a < A; ++a) s2[a] = 0.;
-            for (int j = 0; j < K; ++j) {
-                const int r = j < mrows ? j : mrows - 1;
-                float t[4];
-                ldv<4>(x + ((size_t)(mb.b.n0 + r) * (size_t)g.P + (size_t)mcolc * 4), t);
-                if (j < mrows) {
-                    if constexpr (A == 1) {
-                        absdev_step(t, mmean[0], true, s2[0]);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) s2[e] += (double)fabsf(t[e] - mmean[e]);
-                    }
-                }
+            for (int a = 0; a < A; ++a) {
+                mmean[a] = sh_mean[mt.chan(g, mb.b, a)];
+                s2[a] = 0.;
             }
-            wg_channel_sums<A>(g, mb.b, mok, s2, l_a, sh_sum);
+            mt.rows_from_x(g, x, [&](const float (&q)[4], int) { absdev_row(q, mmean, s2); });
+            wg_channel_sums<A>(g, mb.b, mt.ok, s2, l_a, sh_sum);
             for (int ch = tid; ch < nch; ch += TPB)
                 __hip_atomic_store(tab + (size_t)m * kk + ch, (unsigned long long)__double_as_longlong(sh_sum[ch]), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
@@ -784,20 +736,11 @@ __global__ void __launch_bounds__(TPB, (fused_group_waves<K, OUT, MODE, XR>())) 
         }
     }
     __syncthreads();
-    // the lane's channel indices again, hidden from the optimiser: kept alive across the meeting next to the tile they
-    // cost registers the K = 32 tile does not leave (spills)
-    int tidq = threadIdx.x;
-    asm volatile("" : "+v"(tidq));
-    // ... and the row count: the compiler otherwise keeps the K results of `j < nrows` of the first phase as 64-bit masks for this
-    // one - 64 scalar registers, spilled into lanes of two vector registers the tile needs (round 6)
-    int nrows_q = nrows;
-    asm volatile("" : "+s"(nrows_q));
-    const bool okq = b.col0 + tidq < b.col1;
-    const unsigned colq = (unsigned)(okq ? b.col0 + tidq : b.col0);
-    const size_t baseq = (size_t)b.n0 * (size_t)g.P + (size_t)colq * 4;
+    // the store phase places the tile again (RTile::replace: why)
+    const int tidq = t.replace(g, b);
     int chl[A];
 #pragma unroll
-    for (int a = 0; a < A; ++a) chl[a] = (int)((colq * 4u + (unsigned)a) / (unsigned)g.HW) - b.c0;
+    for (int a = 0; a < A; ++a) chl[a] = t.chan(g, b, a);
     float sc[A], zp[A], qm[A];
 #pragma unroll
     for (int a = 0; a < A; ++a) {
@@ -816,33 +759,9 @@ __global__ void __launch_bounds__(TPB, (fused_group_waves<K, OUT, MODE, XR>())) 
             float rs[A];
 #pragma unroll
             for (int a = 0; a < A; ++a) rs[a] = sh_rs[chl[a]];
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                if (j < nrows_q) {
-                    float o[4], cd[4];
-                    if constexpr (A == 1) {
-                        qdq4_fast(v[j], sc[0], rs[0], zp[0], qm[0], o, cd);      // two elements per instruction, the same bits
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = qdq1_fast(v[j][e], sc[e], rs[e], zp[e], qm[e], cd[e]);
-                    }
-                    if (okq)
-                        xstore<OUT, A>(xo, reinterpret_cast<char*>(y), xo.codes, nullptr, (baseq + (size_t)j * (size_t)g.P) * 4, o, cd, sh_hist,
-                                       zp, nzp);
-                }
-            }
+            t.template rows_qdq_fast<OUT>(g, v, sc, rs, zp, qm, xo, y, sh_hist, nzp);
         } else {
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                if (j < nrows_q) {
-                    float o[4], cd[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = qdq1(v[j][e], sc[A == 1 ? 0 : e], zp[A == 1 ? 0 : e], qm[A == 1 ? 0 : e], cd[e]);
-                    if (okq)
-                        xstore<OUT, A>(xo, reinterpret_cast<char*>(y), xo.codes, nullptr, (baseq + (size_t)j * (size_t)g.P) * 4, o, cd, sh_hist,
-                                       zp, nzp);
-                }
-            }
+            t.template rows_qdq_general<OUT>(g, v, sc, zp, qm, xo, y, sh_hist, nzp);
         }
         if constexpr (OUT == 1) {
             if (xo.hist) xhist_flush<A>(sh_hist, xo.hist, nbins, zp, nzp);
@@ -859,30 +778,27 @@ __global__ void __launch_bounds__(TPB, (fused_group_waves<K, OUT, MODE, XR>())) 
         //  allocator spilled the tile - 528 bytes of scratch)
         auto rows_out = [&](auto isfast_t) {
             constexpr bool ISFAST = decltype(isfast_t)::value;
+            t.rows(v, [&](const float (&q)[4], int j) {
+                float o[4], cd[4];
+                if constexpr (ISFAST) {
+                    mt_qdq4_fast(q, d, rd, lo, hi, o, cd);
+                } else {
 #pragma unroll
-            for (int j = 0; j < K; ++j) {
-                if (j < nrows_q) {
-                    float o[4], cd[4];
-                    if constexpr (ISFAST) {
-                        mt_qdq4_fast(v[j], d, rd, lo, hi, o, cd);
-                    } else {
+                    for (int e = 0; e < 4; ++e) o[e] = mt_qdq1<false>(q[e], d, rd, lo, hi, cd[e]);
+                }
+                if (t.ok) {
+                    stv_nt<4>(y + t.row(g, j), o);
+                    if constexpr (OUT == 1) {
+                        if (want_hist) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = mt_qdq1<false>(v[j][e], d, rd, lo, hi, cd[e]);
-                    }
-                    if (okq) {
-                        stv_nt<4>(y + baseq + (size_t)j * (size_t)g.P, o);
-                        if constexpr (OUT == 1) {
-                            if (want_hist) {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) {
-                                    if constexpr (ISFAST) mt_count_fast(cd[e], hi, hoff, sh_hist, aa.hist, g.C, nni, nhi);
-                                    else mt_count(cd[e], lo, hi, lo_ni, hi_ni, wstart, sh_hist, &sh_clo[chl[0]], aa.hist, g.C, nlo, nhi);
-                                }
+                            for (int e = 0; e < 4; ++e) {
+                                if constexpr (ISFAST) mt_count_fast(cd[e], hi, hoff, sh_hist, aa.hist, g.C, nni, nhi);
+                                else mt_count(cd[e], lo, hi, lo_ni, hi_ni, wstart, sh_hist, &sh_clo[chl[0]], aa.hist, g.C, nlo, nhi);
                             }
                         }
                     }
                 }
-            }
+            });
         };
         if (fastq) rows_out(std::true_type{});
         else rows_out(std::false_type{});

@@ -75,6 +75,17 @@ __device__ unsigned long long* g_grp_trace = nullptr;   // [workgroup][16]: 0-6 
 #else
 #define GRP_STAMP(i)
 #endif
+#ifndef FLAT_ABL
+#define FLAT_ABL 0        // development builds only (tools/runs/r4_ablate.sh; timing, WRONG results): bit 0 - the stores of y compiled out,
+                          // bit 1 - the meeting compiled out (every workgroup uses its own tile's extrema),
+                          // bit 2 - the loads of k_mmq_flat compiled out (synthetic values), bit 3 - the Q/DQ arithmetic of
+                          // k_mmq_flat compiled out (y = x): with bit 1 the kernel is the bare copy of its own address stream
+#endif
+#if FLAT_ABL & 1
+#define FLAT_ABL_NOSTORE(o) && (o)[0] == 3.0e38f      // never true; the arithmetic stays
+#else
+#define FLAT_ABL_NOSTORE(o)
+#endif
 
 __device__ __forceinline__ unsigned long long pack_pair(float mn, float mx) {
     return (unsigned long long)__float_as_uint(mn) | ((unsigned long long)__float_as_uint(mx) << 32);
@@ -89,25 +100,24 @@ struct RBlk {
     int group, member;
 };
 
-// blockIdx -> (group, member) -> tile.  Members of a group are consecutive workgroups.
-__device__ __forceinline__ RBlk rblk_of(const Geo& g, int Gs) {
+// (group, member) -> block, for any workgroup (the cold paths walk every member of their group)
+__device__ __forceinline__ RBlk rblk_at(const Geo& g, int group, int member) {
     RBlk r;
-    const int bid = (int)blockIdx.x;
-    r.group = bid / Gs;
-    r.member = bid - r.group * Gs;
+    r.group = group;
+    r.member = member;
     int s;
     if (g.mode == 1) {
         const int cpc = g.HW / 4;
-        s = r.member / g.nb;
-        const int bb = r.member - s * g.nb;
-        const int c = g.cbeg + r.group;
+        s = member / g.nb;
+        const int bb = member - s * g.nb;
+        const int c = g.cbeg + group;
         r.b.c0 = c;
         r.b.c1 = c + 1;
         r.b.col0 = c * cpc + bb * g.w;
         r.b.col1 = min(r.b.col0 + g.w, (c + 1) * cpc);
     } else {
-        s = r.member;
-        r.b.c0 = g.cbeg + r.group * g.k;
+        s = member;
+        r.b.c0 = g.cbeg + group * g.k;
         r.b.c1 = min(g.cbeg + g.Cn, r.b.c0 + g.k);
         r.b.col0 = (int)(((int64_t)r.b.c0 * g.HW) / 4);
         r.b.col1 = (int)(((int64_t)r.b.c1 * g.HW) / 4);
@@ -117,6 +127,131 @@ __device__ __forceinline__ RBlk rblk_of(const Geo& g, int Gs) {
     r.b.grp = s;
     return r;
 }
+// ... of this workgroup: members of a group are consecutive workgroups
+__device__ __forceinline__ RBlk rblk_of(const Geo& g, int Gs) {
+    const int bid = (int)blockIdx.x, group = bid / Gs;
+    return rblk_at(g, group, bid - group * Gs);
+}
+
+// The row-piece tile of the fp32 single launches (k_mmq_group, k_minmax_group, k_fused_group, k_stats_group): a lane's share of
+// a block - one float4 column, the block's n1 - n0 <= K consecutive samples of it, row j in v[j].  The tile owns the placement
+// of a lane (in this workgroup's block or, on the cold paths, in another member's), the load, the iteration over the lane's
+// rows, the lane's channels and the uniform Q/DQ of the rows out of the registers; a kernel owns what it does with a row's four
+// values, its accumulators and workgroup reductions, its meeting and its outputs.  Every instance of the four kernels keeps the
+// registers, scratch (none) and LDS it had before the tile existed; where a kernel's did not hold with a part of the tile, the
+// kernel spells that part out and says so (k_mmq_group: the load, the pair fold, the Q/DQ row loops; k_fused_group: the rows of its first phase;
+// k_stats_group: its load with the LDS rows and its pairs of rows) - profiles/row_tile.md has the combinations tried.
+template <int K>
+struct RTile {
+    bool ok;            // the lane holds a column of the block
+    int colc;           // ... this float4 column; an idle lane re-reads the block's first one, results discarded
+    int n0, nrows;      // the block's first sample and its samples: 1 .. K
+    size_t base;        // floats from the tensor's start to row 0 of the lane's column
+
+    __device__ __forceinline__ void place(const Geo& g, const Blk& b, int tid) {
+        const int col = b.col0 + tid;
+        ok = col < b.col1;
+        colc = ok ? col : b.col0;
+        n0 = b.n0;
+        nrows = b.n1 - b.n0;
+        base = (size_t)b.n0 * (size_t)g.P + (size_t)colc * 4;
+    }
+    // The placement again, for the store phase, hidden from the optimiser; returns the thread index it placed.  Kept alive across
+    // the meeting next to the tile, the lane's column and channel indices cost registers the K = 32 tile does not leave (spills) ...
+    __device__ __forceinline__ int replace(const Geo& g, const Blk& b) {
+        int tidq = threadIdx.x;
+        asm volatile("" : "+v"(tidq));
+        place(g, b, tidq);
+        // ... and the row count: the compiler otherwise keeps the K results of `j < nrows` of the first phase as 64-bit masks for this
+        // one - 64 scalar registers, spilled into lanes of two vector registers the tile needs
+        asm volatile("" : "+s"(nrows));
+        return tidq;
+    }
+    // floats from the tensor's start to row j of the lane's column, and where a load of row j reads: rows past the tile re-read
+    // its last row
+    __device__ __forceinline__ size_t row(const Geo& g, int j) const { return base + (size_t)j * (size_t)g.P; }
+    __device__ __forceinline__ const float* rowc(const Geo& g, const float* x, int j) const {
+        const int r = j < nrows ? j : nrows - 1;
+        return x + base + (size_t)r * (size_t)g.P;
+    }
+    // ... the same address as the cold paths form it, from the sample up (with it, not with rowc, the registers of k_stats_group hold)
+    __device__ __forceinline__ const float* rowx(const Geo& g, const float* x, int j) const {
+        const int r = j < nrows ? j : nrows - 1;
+        return x + ((size_t)(n0 + r) * (size_t)g.P + (size_t)colc * 4);
+    }
+    // the block-local channel of element a of the lane's float4 (one channel per lane: a = 0), and the words per member
+    __device__ __forceinline__ int chan(const Geo& g, const Blk& b, int a) const {
+        return (int)(((unsigned)colc * 4u + (unsigned)a) / (unsigned)g.HW) - b.c0;
+    }
+    static __device__ __forceinline__ int kk(const Geo& g) { return g.mode == 1 ? 1 : g.k; }
+
+    // The load: K 16-byte loads per lane, issued back to back (NT: non-temporal).  Nothing that consumes a loaded value may be
+    // scheduled in between the loads (as in FTile::load: the scheduler otherwise starts folding after ~10 loads and issues the
+    // rest one by one as earlier ones land): the scheduling barrier.
+    template <bool NT>
+    __device__ __forceinline__ void load(const Geo& g, const float* x, float (&v)[K][4]) const {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if constexpr (NT) ldv_nt<4>(rowc(g, x, j), v[j]);
+            else ldv<4>(rowc(g, x, j), v[j]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // f(v[j], j) for the tile's rows.  (A uniform branch per row, not a select: 32 lane masks held in scalar registers next to
+    // the tile made the allocator spill the tile itself.)
+    template <class F>
+    __device__ __forceinline__ void rows(const float (&v)[K][4], F&& f) const {
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (j < nrows) f(v[j], j);
+    }
+    // ... of a member's tile read from x again, row by row (the cold paths)
+    template <class F>
+    __device__ __forceinline__ void rows_from_x(const Geo& g, const float* x, F&& f) const {
+        for (int j = 0; j < K; ++j) {
+            float t[4];
+            ldv<4>(rowx(g, x, j), t);
+            if (j < nrows) f(t, j);
+        }
+    }
+    // The uniform Q/DQ of the tile's rows out of the registers to y and the codes (k_fused_group MODE 0; k_mmq_group spells the
+    // same loops out with one qmax per block and the packed output): FAST - every channel of the block inside the fast domain,
+    // the exact quotient without the divide (rs = 1 / sc; A == 1: two elements per instruction, the same bits) - or the general
+    // form, which has no rs.  The parameters per element of the float4 (A == 4) or one set (A == 1).  (FLAT_ABL bit 0 compiles
+    // these stores out as well: a development build with it times k_fused_group without its stores too.)
+    template <int OUT, int A>
+    __device__ __forceinline__ void rows_qdq_fast(const Geo& g, const float (&v)[K][4], const float (&sc)[A], const float (&rs)[A],
+                                                  const float (&zp)[A], const float (&qm)[A], const XOut& xo, float* y,
+                                                  unsigned* sh_hist, unsigned (&nzp)[A]) const {
+        rows_qdq_out<OUT, true>(g, v, sc, rs, zp, qm, xo, y, sh_hist, nzp);
+    }
+    template <int OUT, int A>
+    __device__ __forceinline__ void rows_qdq_general(const Geo& g, const float (&v)[K][4], const float (&sc)[A], const float (&zp)[A],
+                                                     const float (&qm)[A], const XOut& xo, float* y, unsigned* sh_hist,
+                                                     unsigned (&nzp)[A]) const {
+        rows_qdq_out<OUT, false>(g, v, sc, sc, zp, qm, xo, y, sh_hist, nzp);      // (no rs in the general form: any array stands in)
+    }
+    template <int OUT, bool FAST, int A>
+    __device__ __forceinline__ void rows_qdq_out(const Geo& g, const float (&v)[K][4], const float (&sc)[A], const float (&rs)[A],
+                                                 const float (&zp)[A], const float (&qm)[A], const XOut& xo, float* y,
+                                                 unsigned* sh_hist, unsigned (&nzp)[A]) const {
+        rows(v, [&](const float (&q)[4], int j) {
+            float o[4], cd[4];
+            if constexpr (FAST && A == 1) {
+                qdq4_fast(q, sc[0], rs[0], zp[0], qm[0], o, cd);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int a = A == 1 ? 0 : e;
+                    if constexpr (FAST) o[e] = qdq1_fast(q[e], sc[a], rs[a], zp[a], qm[a], cd[e]);
+                    else o[e] = qdq1(q[e], sc[a], zp[a], qm[a], cd[e]);
+                }
+            }
+            if (ok FLAT_ABL_NOSTORE(o))
+                xstore<OUT, A>(xo, reinterpret_cast<char*>(y), xo.codes, nullptr, row(g, j) * 4, o, cd, sh_hist, zp, nzp);
+        });
+    }
+};
 
 // per-lane accumulators -> per-channel extrema of the workgroup's tile in sh_mn / sh_mx [c1 - c0]
 template <int A>
@@ -486,17 +621,35 @@ struct GWs {
     int gstride;   // pairs per group block
 };
 
-#ifndef FLAT_ABL
-#define FLAT_ABL 0        // development builds only (tools/runs/r4_ablate.sh; timing, WRONG results): bit 0 - the stores of y compiled out,
-                          // bit 1 - the meeting compiled out (every workgroup uses its own tile's extrema),
-                          // bit 2 - the loads of k_mmq_flat compiled out (synthetic values), bit 3 - the Q/DQ arithmetic of
-                          // k_mmq_flat compiled out (y = x): with bit 1 the kernel is the bare copy of its own address stream
-#endif
-#if FLAT_ABL & 1
-#define FLAT_ABL_NOSTORE(o) && (o)[0] == 3.0e38f      // never true; the arithmetic stays
-#else
-#define FLAT_ABL_NOSTORE(o)
-#endif
+// The fold of a group's packed {min, max} pairs, [member][kk] at blk, once every member's are in (the counter meeting of
+// k_mmq_group, the last arrival of k_minmax_group).  Row pieces of one channel (mode 1): the lanes share the members and the
+// result lands in sh_mn[0] / sh_mx[0] through the one-channel reduction; else lane ch folds channel ch: put(ch, min, max).
+template <class F>
+__device__ __forceinline__ void group_fold_pairs(const Geo& g, const Blk& b, const unsigned long long* blk, int Gs, int kk, float* l_mn,
+                                                 float* l_mx, float* sh_mn, float* sh_mx, F&& put) {
+    const int tid = threadIdx.x;
+    const auto fold = [&](const unsigned long long* p, float& tn, float& tx) {
+        float a, c;
+        unpack_pair(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a, c);
+        tn = pmin(tn, a);
+        tx = pmax(tx, c);
+    };
+    if (g.mode == 1) {
+        float tn = INFINITY, tx = -INFINITY;
+        for (int m = tid; m < Gs; m += TPB) fold(blk + m, tn, tx);
+        const float one_n[1] = {tn}, one_x[1] = {tx};
+        wg_channel_minmax<1>(g, b, true, one_n, one_x, l_mn, l_mx, sh_mn, sh_mx);
+        if (tid == 0) put(0, sh_mn[0], sh_mx[0]);
+    } else {
+        for (int ch = tid; ch < b.c1 - b.c0; ch += TPB) {
+            float tn = INFINITY, tx = -INFINITY;
+#pragma unroll 8
+            for (int s = 0; s < Gs; ++s) fold(blk + ((size_t)s * kk + ch), tn, tx);
+            put(ch, tn, tx);
+        }
+    }
+}
+
 template <int A, int K, int OUT = 0, bool XR = false>
 __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_group(
     const float* __restrict__ x, float* __restrict__ y, const Geo g, const int Gs, const int num_bits, const int positive,
@@ -518,21 +671,19 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_grou
     const RBlk rb = rblk_of(g, Gs);
     const Blk& b = rb.b;
     const int tid = threadIdx.x;
-    const int col = b.col0 + tid;
-    const bool ok = col < b.col1;
-    const int colc = ok ? col : b.col0;   // idle lanes re-read the block's first column; results discarded
-    const int nrows = b.n1 - b.n0;        // 1 .. K
-    const size_t base = (size_t)b.n0 * (size_t)g.P + (size_t)colc * 4;
+    RTile<K> t;
+    t.place(g, b, tid);
 
-    // ---- the tile: K 16-byte loads per lane, issued back to back (rows past the tile re-read its last row)
+    // ---- the tile, all K rows folded: a row past the tile is a copy of its last row.  This kernel keeps its own text of three
+    //      parts of the tile, on its registers' evidence (profiles/row_tile.md section 1.2): the load here (RTile::load: the
+    //      order of the loads and why; a change there is made here too), the fold of the pairs behind the counter meeting
+    //      (group_fold_pairs) and the Q/DQ row loops (RTile::rows_qdq_out)
     float v[K][4];
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-        const int r = j < nrows ? j : nrows - 1;
-        ldv_nt<4>(x + base + (size_t)r * (size_t)g.P, v[j]);
+        const int r = j < t.nrows ? j : t.nrows - 1;
+        ldv_nt<4>(x + t.base + (size_t)r * (size_t)g.P, v[j]);
     }
-    // nothing that consumes a loaded value may be scheduled in between the loads (as in k_mmq_flat: the scheduler otherwise
-    // starts folding after ~10 loads and issues the rest one by one as earlier ones land)
     __builtin_amdgcn_sched_barrier(0);
     GRP_STAMP(1);
     float mn[A], mx[A];
@@ -542,13 +693,13 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_grou
 #pragma unroll
     for (int j = 0; j < K; ++j) lane_acc<A>(v[j], mn, mx, nan);
     if (A == 1 && nan) { mn[0] = NAN; mx[0] = NAN; }
-    wg_channel_minmax<A>(g, b, ok, mn, mx, l_mn, l_mx, sh_mn, sh_mx);
+    wg_channel_minmax<A>(g, b, t.ok, mn, mx, l_mn, l_mx, sh_mn, sh_mx);
     const int nch = b.c1 - b.c0;
     GRP_STAMP(2);
 
     // ---- publish this workgroup's pairs (write-through), arrive, wait for the group
     unsigned long long* blk = ws.part + (size_t)rb.group * ws.gstride;
-    const int kk = (g.mode == 1) ? 1 : g.k;
+    const int kk = t.kk(g);
     const bool use_slots = (flags & MMQ_FLAG_SLOTS) != 0;
     unsigned long long* slots = ws.slots + (size_t)rb.group * ws.gstride;    // the slot meeting's blocks: zero at rest
     if (use_slots) {
@@ -603,7 +754,7 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_grou
             const float one_n[1] = {sn}, one_x[1] = {sx};
             wg_channel_minmax<1>(g, b, true, one_n, one_x, l_mn, l_mx, sh_mn, sh_mx);   // the one-channel reduction
         }
-    } else if (g.mode == 1) {
+    } else if (g.mode == 1) {          // (the counter meeting: the fold of group_fold_pairs, this kernel's own text)
         float tn = INFINITY, tx = -INFINITY;
         for (int m = tid; m < Gs; m += TPB) {
             float a, c;
@@ -613,7 +764,7 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_grou
         }
         const float one_n[1] = {tn}, one_x[1] = {tx};
         wg_channel_minmax<1>(g, b, true, one_n, one_x, l_mn, l_mx, sh_mn, sh_mx);   // the one-channel reduction
-    } else {
+    } else {                           // (... its form for whole channels per workgroup)
         for (int ch = tid; ch < nch; ch += TPB) {
             float tn = INFINITY, tx = -INFINITY;
 #pragma unroll 8
@@ -656,27 +807,22 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_grou
     float sc[A], zp[A];
 #pragma unroll
     for (int a = 0; a < A; ++a) {
-        const unsigned e = (unsigned)colc * 4u + (unsigned)a;
-        const int ch = (int)(e / (unsigned)g.HW) - b.c0;
-        sc[a] = sh_sc[ch];
-        zp[a] = sh_zp[ch];
+        sc[a] = sh_sc[t.chan(g, b, a)];
+        zp[a] = sh_zp[t.chan(g, b, a)];
     }
 
-    // ---- Q/DQ out of the registers
+    // ---- Q/DQ out of the registers (the row loops of RTile::rows_qdq_out, this kernel's own text)
     unsigned nzp[A];
 #pragma unroll
     for (int a = 0; a < A; ++a) nzp[a] = 0u;
     if (!__builtin_amdgcn_readfirstlane(sh_slow)) {
-        // every channel of the block inside qdq_fast_domain: the exact quotient without the divide
+        // every channel of the block inside qdq_fast_domain
         float rs[A];
 #pragma unroll
-        for (int a = 0; a < A; ++a) {
-            const unsigned e = (unsigned)colc * 4u + (unsigned)a;
-            rs[a] = sh_rs[(int)(e / (unsigned)g.HW) - b.c0];
-        }
+        for (int a = 0; a < A; ++a) rs[a] = sh_rs[t.chan(g, b, a)];
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            if (j < nrows) {
+            if (j < t.nrows) {
                 float o[4], cd[4];
                 if constexpr (A == 1) {
                     qdq4_fast(v[j], sc[0], rs[0], zp[0], qm, o, cd);          // two elements per instruction, the same bits (as k_mmq_flat)
@@ -684,20 +830,20 @@ __global__ void __launch_bounds__(TPB, (K == 32 ? GRP_K32_WAVES : 1)) k_mmq_grou
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = qdq1_fast(v[j][e], sc[e], rs[e], zp[e], qm, cd[e]);
                 }
-                if (ok FLAT_ABL_NOSTORE(o))
-                    xstore<OUT, A>(xo, reinterpret_cast<char*>(y), xo.codes, xo.packed, (base + (size_t)j * (size_t)g.P) * 4, o,
+                if (t.ok FLAT_ABL_NOSTORE(o))
+                    xstore<OUT, A>(xo, reinterpret_cast<char*>(y), xo.codes, xo.packed, (t.base + (size_t)j * (size_t)g.P) * 4, o,
                                    cd, sh_hist, zp, nzp);
             }
         }
     } else {
 #pragma unroll
         for (int j = 0; j < K; ++j) {
-            if (j < nrows) {
+            if (j < t.nrows) {
                 float o[4], cd[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = qdq1(v[j][e], sc[A == 1 ? 0 : e], zp[A == 1 ? 0 : e], qm, cd[e]);
-                if (ok FLAT_ABL_NOSTORE(o))
-                    xstore<OUT, A>(xo, reinterpret_cast<char*>(y), xo.codes, xo.packed, (base + (size_t)j * (size_t)g.P) * 4, o,
+                if (t.ok FLAT_ABL_NOSTORE(o))
+                    xstore<OUT, A>(xo, reinterpret_cast<char*>(y), xo.codes, xo.packed, (t.base + (size_t)j * (size_t)g.P) * 4, o,
                                    cd, sh_hist, zp, nzp);
             }
         }
@@ -1155,18 +1301,10 @@ __global__ void __launch_bounds__(TPB) k_minmax_group(const float* __restrict__ 
     const RBlk rb = rblk_of(g, Gs);
     const Blk& b = rb.b;
     const int tid = threadIdx.x;
-    const int col = b.col0 + tid;
-    const bool ok = col < b.col1;
-    const int colc = ok ? col : b.col0;
-    const int nrows = b.n1 - b.n0;
-    const size_t base = (size_t)b.n0 * (size_t)g.P + (size_t)colc * 4;
+    RTile<K> t;
+    t.place(g, b, tid);
     float v[K][4];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        const int r = j < nrows ? j : nrows - 1;
-        ldv<4>(x + base + (size_t)r * (size_t)g.P, v[j]);
-    }
-    __builtin_amdgcn_sched_barrier(0);      // the whole tile in flight before the first value is consumed
+    t.template load<false>(g, x, v);
     float mn[A], mx[A];
     bool nan = false;
 #pragma unroll
@@ -1174,10 +1312,10 @@ __global__ void __launch_bounds__(TPB) k_minmax_group(const float* __restrict__ 
 #pragma unroll
     for (int j = 0; j < K; ++j) lane_acc<A>(v[j], mn, mx, nan);
     if (A == 1 && nan) { mn[0] = NAN; mx[0] = NAN; }
-    wg_channel_minmax<A>(g, b, ok, mn, mx, l_mn, l_mx, sh_mn, sh_mx);
+    wg_channel_minmax<A>(g, b, t.ok, mn, mx, l_mn, l_mx, sh_mn, sh_mx);
     const int nch = b.c1 - b.c0;
     unsigned long long* blk = ws.part + (size_t)rb.group * ws.gstride;
-    const int kk = (g.mode == 1) ? 1 : g.k;
+    const int kk = t.kk(g);
     for (int ch = tid; ch < nch; ch += TPB)
         __hip_atomic_store(blk + (size_t)rb.member * kk + ch, pack_pair(sh_mn[ch], sh_mx[ch]), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
@@ -1186,31 +1324,11 @@ __global__ void __launch_bounds__(TPB) k_minmax_group(const float* __restrict__ 
     if (tid == 0) sh_last = grp_arrive_last(grp_lines(ws.cnt, rb.group, Gs, 0, 1), rb.member, Gs) ? 1 : 0;
     __syncthreads();
     if (!sh_last) return;
-    if (g.mode == 1) {
-        float tn = INFINITY, tx = -INFINITY;
-        for (int m = tid; m < Gs; m += TPB) {
-            float a, c;
-            unpack_pair(__hip_atomic_load(blk + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a, c);
-            tn = pmin(tn, a);
-            tx = pmax(tx, c);
-        }
-        const float one_n[1] = {tn}, one_x[1] = {tx};
-        wg_channel_minmax<1>(g, b, true, one_n, one_x, l_mn, l_mx, sh_mn, sh_mx);
-        if (tid == 0) { out[b.c0] = sh_mn[0]; out[g.C + b.c0] = sh_mx[0]; }
-    } else {
-        for (int ch = tid; ch < nch; ch += TPB) {
-            float tn = INFINITY, tx = -INFINITY;
-#pragma unroll 8
-            for (int s = 0; s < Gs; ++s) {
-                float a, c;
-                unpack_pair(__hip_atomic_load(blk + ((size_t)s * kk + ch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a, c);
-                tn = pmin(tn, a);
-                tx = pmax(tx, c);
-            }
-            out[b.c0 + ch] = tn;
-            out[g.C + b.c0 + ch] = tx;
-        }
-    }
+    const auto put = [&](int ch, float tn, float tx) {
+        out[b.c0 + ch] = tn;
+        out[g.C + b.c0 + ch] = tx;
+    };
+    group_fold_pairs(g, b, blk, Gs, kk, l_mn, l_mx, sh_mn, sh_mx, put);
 }
 
 }  // namespace

@@ -721,30 +721,28 @@ __global__ void __launch_bounds__(TPB, (KR + KL == 32 ? GRP_K32_WAVES : 1)) k_st
     const Blk& b = rb.b;
     const int tid = threadIdx.x;
     const int nch = b.c1 - b.c0;
-    const bool ok = b.col0 + tid < b.col1;
-    const unsigned colc = (unsigned)(ok ? b.col0 + tid : b.col0);      // idle lanes re-read the block's first column; results discarded
-    const int nrows = b.n1 - b.n0;                                     // 1 .. K
-    const size_t base = (size_t)b.n0 * (size_t)g.P + (size_t)colc * 4;
-    const int kk = (g.mode == 1) ? 1 : g.k;
+    RTile<KR> t;                                       // the register rows; the tile's KL last rows live in LDS (below)
+    t.place(g, b, tid);
+    const bool ok = t.ok;
+    const int nrows = t.nrows;                         // 1 .. K
+    const int kk = t.kk(g);
     const int NPK = SG_NP * kk;
     if (tid == 0) sh_code = ((flags & MMQ_FLAG_TEST_HOOK) ? 2 : 0) | ((st0 & 1u) ? 4 : 0);
 
     // ---- the tile: K 16-byte loads per lane back to back, the LAST KL of them straight into LDS (as asm behind the register
-    //      loads: lds_dma16_behind - the pairs of phase 1 start as their own loads land)
+    //      loads: lds_dma16_behind - the pairs of phase 1 start as their own loads land).  The load of RTile::load, spelled out
+    //      here because the LDS rows go in between the register loads and the scheduling barrier (see there for the order).
     static_assert(KR % 2 == 0 && KL % 2 == 0, "rows in pairs");
     float v[KR][4];
 #pragma unroll
-    for (int j = 0; j < KR; ++j) {
-        const int r = j < nrows ? j : nrows - 1;
-        ldv_nt<4>(x + base + (size_t)r * (size_t)g.P, v[j]);
-    }
+    for (int j = 0; j < KR; ++j) ldv_nt<4>(t.rowc(g, x, j), v[j]);
     if constexpr (KL > 0) {
         // (tiles with LDS rows are one-channel-per-lane tiles of whole K-row splits or less: offsets fit 32 bits from the tile's base)
         const char* xt = reinterpret_cast<const char*>(x + (size_t)b.n0 * (size_t)g.P);
 #pragma unroll
         for (int l = 0; l < KL; ++l) {
             const int r = KR + l < nrows ? KR + l : nrows - 1;
-            lds_dma16_behind(xt, (unsigned)(((size_t)r * (size_t)g.P + (size_t)colc * 4) * 4), sh_x + (l * TPB + (tid & ~63)) * 4);
+            lds_dma16_behind(xt, (unsigned)(((size_t)r * (size_t)g.P + (size_t)t.colc * 4) * 4), sh_x + (l * TPB + (tid & ~63)) * 4);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -760,28 +758,25 @@ __global__ void __launch_bounds__(TPB, (KR + KL == 32 ? GRP_K32_WAVES : 1)) k_st
         for (int l = 0; l < KL; l += 2) {
             const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
             const float4 q1 = *reinterpret_cast<const float4*>(sh_x + ((l + 1) * TPB + tid) * 4);
-            const float t[4] = {q.x, q.y, q.z, q.w}, t1[4] = {q1.x, q1.y, q1.z, q1.w};
-            ac.add_rows(t, t1, KR + l, nrows);
+            const float u[4] = {q.x, q.y, q.z, q.w}, u1[4] = {q1.x, q1.y, q1.z, q1.w};
+            ac.add_rows(u, u1, KR + l, nrows);
         }
     }
     sg_reduce1<A, RELU>(g, b, ok, ac, l_a, sh_mn, sh_mx, sh_q);
 
     // a member's tile from x again (the cold path), with that member's own lane mapping
     auto cold_phase1 = [&](const RBlk& mb) {
-        const int mcol = mb.b.col0 + tid;
-        const bool mok = mcol < mb.b.col1;
-        const int mcolc = mok ? mcol : mb.b.col0;
-        const int mrows = mb.b.n1 - mb.b.n0;
+        RTile<K> mt;
+        mt.place(g, mb.b, tid);
         SgAcc<A, RELU> a2;
         a2.init();
         for (int jj = 0; jj < K; jj += 2) {
-            float t[4], t1[4];
-            const int r = jj < mrows ? jj : mrows - 1, r1 = jj + 1 < mrows ? jj + 1 : mrows - 1;
-            ldv<4>(x + ((size_t)(mb.b.n0 + r) * (size_t)g.P + (size_t)mcolc * 4), t);
-            ldv<4>(x + ((size_t)(mb.b.n0 + r1) * (size_t)g.P + (size_t)mcolc * 4), t1);
-            a2.add_rows(t, t1, jj, mrows);
+            float q[4], q1[4];
+            ldv<4>(mt.rowx(g, x, jj), q);
+            ldv<4>(mt.rowx(g, x, jj + 1), q1);
+            a2.add_rows(q, q1, jj, mt.nrows);
         }
-        sg_reduce1<A, RELU>(g, mb.b, mok, a2, l_a, sh_mn, sh_mx, sh_q);
+        sg_reduce1<A, RELU>(g, mb.b, mt.ok, a2, l_a, sh_mn, sh_mx, sh_q);
     };
     // the tile's per-channel words of planes [p0, p0 + np) out of the LDS tables into a member's block at dst
     auto emit = [&](unsigned long long* dst, int p0, int np) {
@@ -926,13 +921,14 @@ __global__ void __launch_bounds__(TPB, (KR + KL == 32 ? GRP_K32_WAVES : 1)) k_st
         if (!cold) {
             // out of the registers.  (On the cold path the tile is NOT used again: its registers are free there.)
             int tidq = threadIdx.x;
-            asm volatile("" : "+v"(tidq));             // the lane's channel indices again, not carried across the meeting
-            const unsigned colq = (unsigned)(b.col0 + tidq < b.col1 ? b.col0 + tidq : b.col0);
+            asm volatile("" : "+v"(tidq));             // the lane's channel indices again, not carried across the meeting (as
+            RTile<KR> tq;                              // RTile::replace; the row count stays: this kernel's registers hold with it)
+            tq.place(g, b, tidq);
             float mean[A], isd[A];
             double da[A], dk[A];
 #pragma unroll
             for (int a = 0; a < A; ++a) {
-                const int chl = (int)((colq * 4u + (unsigned)a) / (unsigned)g.HW) - b.c0;
+                const int chl = tq.chan(g, b, a);
                 mean[a] = sh_mean[chl];
                 isd[a] = sh_isd[chl];
                 da[a] = 0.;
@@ -945,8 +941,8 @@ __global__ void __launch_bounds__(TPB, (KR + KL == 32 ? GRP_K32_WAVES : 1)) k_st
                 for (int l = 0; l < KL; l += 2) {
                     const float4 q = *reinterpret_cast<const float4*>(sh_x + (l * TPB + tid) * 4);
                     const float4 q1 = *reinterpret_cast<const float4*>(sh_x + ((l + 1) * TPB + tid) * 4);
-                    const float t[4] = {q.x, q.y, q.z, q.w}, t1[4] = {q1.x, q1.y, q1.z, q1.w};
-                    dev_rows(t, t1, KR + l, nrows, mean, isd, da, dk);
+                    const float u[4] = {q.x, q.y, q.z, q.w}, u1[4] = {q1.x, q1.y, q1.z, q1.w};
+                    dev_rows(u, u1, KR + l, nrows, mean, isd, da, dk);
                 }
             }
             reduce2(b, ok, da, dk);
@@ -954,28 +950,25 @@ __global__ void __launch_bounds__(TPB, (KR + KL == 32 ? GRP_K32_WAVES : 1)) k_st
         } else {
             for (int m = 0; m < Gs; ++m) {
                 const RBlk mb = rblk_at(g, rb.group, m);
-                const int mcol = mb.b.col0 + tid;
-                const bool mok = mcol < mb.b.col1;
-                const int mcolc = mok ? mcol : mb.b.col0;
-                const int mrows = mb.b.n1 - mb.b.n0;
+                RTile<K> mt;
+                mt.place(g, mb.b, tid);
                 float mean[A], isd[A];
                 double da[A], dk[A];
 #pragma unroll
                 for (int a = 0; a < A; ++a) {
-                    const int chl = (int)(((unsigned)mcolc * 4u + (unsigned)a) / (unsigned)g.HW) - mb.b.c0;
+                    const int chl = mt.chan(g, mb.b, a);
                     mean[a] = sh_mean[chl];
                     isd[a] = sh_isd[chl];
                     da[a] = 0.;
                     dk[a] = 0.;
                 }
                 for (int jj = 0; jj < K; jj += 2) {
-                    float t[4], t1[4];
-                    const int r = jj < mrows ? jj : mrows - 1, r1 = jj + 1 < mrows ? jj + 1 : mrows - 1;
-                    ldv<4>(x + ((size_t)(mb.b.n0 + r) * (size_t)g.P + (size_t)mcolc * 4), t);
-                    ldv<4>(x + ((size_t)(mb.b.n0 + r1) * (size_t)g.P + (size_t)mcolc * 4), t1);
-                    dev_rows(t, t1, jj, mrows, mean, isd, da, dk);
+                    float q[4], q1[4];
+                    ldv<4>(mt.rowx(g, x, jj), q);
+                    ldv<4>(mt.rowx(g, x, jj + 1), q1);
+                    dev_rows(q, q1, jj, mt.nrows, mean, isd, da, dk);
                 }
-                reduce2(mb.b, mok, da, dk);
+                reduce2(mb.b, mt.ok, da, dk);
                 emit(tab + (size_t)m * NPK, 5, 2);
                 if (m == rb.member) emit(lines + (size_t)rb.member * NPK, 5, 2);    // its own words go out like everybody's
                 __syncthreads();

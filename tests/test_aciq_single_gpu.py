@@ -61,8 +61,11 @@ from _direct import aciq_on_table as oracle_from_device_stats      # noqa: E402 
 # pieces of one channel (64x64: four workgroups per sample row); (48, 3, 56, 56): the smallest flat plan with K = 32 - five
 # members, the last partly empty, three channels in dispatch blocks of four (the others plan K = 8 and 16)
 K32_FLAT = (48, 3, 56, 56)
+# tall row-piece tiles from small tensors (tests/test_group_gpu.py: one group of 257 or 258 members, the last split ragged): one
+# channel per lane at K = 8 / 16 / 32, straddling float4s at K = 8 / 16 (the sum kernels cap those at 16)
+ROW_TALL = [(2050, 2, 8, 8), (4100, 2, 8, 8), (8200, 2, 8, 8), (2060, 4, 7, 7), (4100, 4, 7, 7)]
 SHAPES = [(40, 6, 56, 56), (33, 5, 28, 28), (24, 3, 32, 32), (70, 12, 14, 14), (130, 24, 7, 7), (8, 4, 112, 112), (64, 37, 14, 14),
-          (6, 3, 64, 64), K32_FLAT]
+          (6, 3, 64, 64), K32_FLAT] + ROW_TALL
 
 
 def test_the_small_shapes_reach_every_flat_tile_height():
@@ -71,6 +74,24 @@ def test_the_small_shapes_reach_every_flat_tile_height():
     assert ks >= {8, 16, 32}, ks
     d = describe(K32_FLAT[0], K32_FLAT[1], K32_FLAT[2] * K32_FLAT[3])[1]
     assert d['mode'] == 3 and d['K'] == 32 and d['Gs'] == 5 and 48 * 784 % (256 * 32) != 0, d
+
+
+def test_the_small_shapes_reach_every_row_piece_tile_height():
+    """(a planner change must not silently un-test a tile height of k_fused_group MODE 0.  The config-2 plan: the sum kernels'
+    differs only in capping straddling rows at K = 16, where (8200, 4, 7, 7) - K = 32 there - has no single launch at all)"""
+    got = {(d['A'], d['K']) for rc, d in (describe(s[0], s[1], s[2] * s[3]) for s in SHAPES) if rc == 0 and d['mode'] != 3}
+    assert got >= {(1, 4), (1, 8), (1, 16), (1, 32), (4, 4), (4, 8), (4, 16)}, got
+    from cnn_quantization_amd import _lib, ops
+    for shape in ROW_TALL:
+        d = describe(shape[0], shape[1], shape[2] * shape[3])[1]
+        assert d['mode'] == 2 and d['groups'] == 1 and d['Gs'] in (257, 258) and shape[0] % d['K'] != 0, (shape, d)
+        # ... and through the sum kernels' own planner (plan_sums, which cnnq_pc_stats_route asks; 2: it has a row-piece plan).
+        # It doubles K from 4 only until the group has at most 512 members, so a plan it accepts with 257 or 258 members of a
+        # batch of N has K = ceil(N / members) rounded up to a power of two: the K above
+        assert _lib.load().cnnq_pc_stats_route(shape[0], shape[1], shape[2] * shape[3], 1, ops.GROUP_WS_BYTES, 8) == 2, shape
+        assert (shape[0] + d['K'] - 1) // d['K'] == d['Gs'] and (shape[0] + d['K'] // 2 - 1) // (d['K'] // 2) > 512, (shape, d)
+    # the cap binds where plan_group says K = 32 for straddling rows: no row-piece plan of the sum kernels
+    assert describe(8200, 4, 49)[1]['K'] == 32 and _lib.load().cnnq_pc_stats_route(8200, 4, 49, 1, ops.GROUP_WS_BYTES, 8) == 0
 
 
 @pytest.mark.parametrize('shape', SHAPES)

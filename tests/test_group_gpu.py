@@ -77,6 +77,11 @@ SHAPES = [
     (66, 3, 112, 112), (260, 2, 112, 112),                   # two-level arrival (more than 16 members per group)
     (130, 2, 40, 36), (1, 1100, 2, 2), (4, 260, 1, 4), (2, 3, 64, 80), (600, 2, 8, 8),
     (680, 1, 112, 112),                                      # a flat group of more than 256 members: a lane's second window
+    # tall row-piece tiles from small tensors: a channel group stays co-resident (512 members at most), so a long batch of
+    # short rows forces K = 8 / 16 / 32 - one group of 257 or 258 members, the last split ragged (rows past the tile's end)
+    (2050, 2, 8, 8), (4100, 2, 8, 8), (8200, 2, 8, 8),      # one channel per lane
+    (2060, 4, 7, 7), (4100, 4, 7, 7), (8200, 4, 7, 7),      # straddling float4s
+    (1030, 1, 32, 64),                                       # row pieces of one channel (mode 1), K = 8
 ]
 # The bounded wait carries its clock and poll count from one window of members to the next.  A lane of k_mmq_flat takes
 # 4 x 64 members per window: SECOND_WINDOW is the shape whose group needs two.  (The row-piece kernel's windows are
@@ -123,6 +128,20 @@ def test_group_plans_cover_one_and_two_level_arrival():
     assert levels >= {(3, 1), (3, 2), (2, 1), (2, 2)}, levels
     assert describe(512, 256, 3136)[1]['mode'] == 3 and describe(512, 1024, 196)[1]['mode'] == 2
     assert describe(512, 64, 112 * 112)[1]['Gs'] == 196          # 512 * 3136 float4 / (256 * 32)
+
+
+def test_the_small_shapes_reach_every_row_piece_tile_height():
+    """(a planner change must not silently un-test a tile height of k_mmq_group)"""
+    got = set()
+    for N, C, H, W in SHAPES:
+        rc, d = describe(N, C, H * W)
+        if rc == 0 and d['mode'] != 3 and N * C * H * W * 4 <= 10 << 20:
+            got.add((d['A'], d['K'], d['mode']))
+            assert (d['S'] - 1) * d['K'] < N <= d['S'] * d['K'], d
+    assert got >= {(a, k, 2) for a in (1, 4) for k in (4, 8, 16, 32)} | {(1, 4, 1), (1, 8, 1)}, got
+    for shape in SHAPES[-7:]:      # the tall ones: one group, the last split ragged
+        d = describe(shape[0], shape[1], shape[2] * shape[3])[1]
+        assert d['groups'] == 1 and d['Gs'] in (257, 258) and shape[0] % d['K'] != 0, (shape, d)
 
 
 def test_row_piece_shapes_reach_a_second_window():

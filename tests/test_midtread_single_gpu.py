@@ -86,8 +86,24 @@ def hist_counts(hist, mt, C):
 
 # (48, 3, 56, 56): the smallest flat plan with K = 32 (five members, the last partly empty; tests/test_aciq_single_gpu.py checks
 # the plan) - the other flat shapes here plan K = 8 and 16
+# ROW_TALL: tall row-piece tiles from small tensors (tests/test_group_gpu.py: one group of 257 members, the last split ragged),
+# K = 8 / 16 / 32 of k_fused_group MODE 1
+ROW_TALL = [(2050, 2, 8, 8), (4100, 2, 8, 8), (8200, 2, 8, 8)]
 SHAPES = [(40, 6, 56, 56), (33, 5, 28, 28), (24, 3, 32, 32), (70, 12, 14, 14), (8, 4, 112, 112), (64, 37, 14, 14), (6, 3, 64, 64),
-          (48, 3, 56, 56)]
+          (48, 3, 56, 56)] + ROW_TALL
+
+
+def test_the_small_shapes_reach_every_row_piece_tile_height():
+    """(a planner change must not silently un-test a tile height of k_fused_group MODE 1: one channel per lane only)"""
+    from cnn_quantization_amd import _lib
+    got = set()
+    for N, C, H, W in SHAPES:
+        d = (ctypes.c_int32 * 8)()
+        if _lib.load().cnnq_pc_group_describe(N, C, H * W, d) == 0 and d[2] != 3:
+            got.add((d[0], d[1]))
+            if (N, C, H, W) in ROW_TALL:
+                assert d[2] == 2 and d[5] == 257 and N % d[1] != 0, list(d)
+    assert got == {(1, 4), (1, 8), (1, 16), (1, 32)}, got
 
 
 @pytest.mark.parametrize('shape', SHAPES)
@@ -132,7 +148,7 @@ def test_single_launch_equals_the_pinned_kernels_on_its_own_statistics(ops, shap
     assert abs(float(ent) - ref['entropy']) <= 2e-5 * max(1., ref['entropy']), (float(ent), ref['entropy'])
 
 
-@pytest.mark.parametrize('shape', SHAPES[:5])
+@pytest.mark.parametrize('shape', SHAPES[:5] + ROW_TALL)
 def test_recompute_path_and_reruns_give_the_same_bits(ops, shape):
     N, C = shape[:2]
     HW = shape[2] * shape[3]

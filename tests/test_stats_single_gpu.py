@@ -54,7 +54,10 @@ SHAPES = [(40, 6, 56, 56), (33, 5, 28, 28), (8, 4, 112, 112), (300, 3, 56, 56), 
 # that is a whole multiple of the workgroup (64x64: column blocks of one channel), ragged sample splits, and the tile heights
 # the planner picks at full size (K = 16: [512,160,14,14] and - straddling rows take at most K = 16 since round 6, their K = 32
 # instances spilled - [512,640,7,7]; K = 32 with eight rows in LDS: [512,320,14,14])
-GROUP_SHAPES = [(12, 24, 14, 14), (70, 12, 14, 14), (64, 37, 14, 14), (40, 44, 7, 7), (33, 12, 7, 7), (6, 3, 64, 64), (300, 8, 7, 7), (130, 20, 14, 14)]
+# (2050, 2, 8, 8), (2060, 4, 7, 7): K = 8 from small tensors - a long batch of short rows, one group of 257 / 258 members (more
+# than the default route takes: flags bit 3, which ops.pc_stats_single sets), the last split ragged
+GROUP_SHAPES = [(12, 24, 14, 14), (70, 12, 14, 14), (64, 37, 14, 14), (40, 44, 7, 7), (33, 12, 7, 7), (6, 3, 64, 64), (300, 8, 7, 7), (130, 20, 14, 14),
+                (2050, 2, 8, 8), (2060, 4, 7, 7)]
 BIG_GROUP_SHAPES = [(512, 160, 14, 14), (512, 320, 14, 14), (512, 640, 7, 7)]
 
 
@@ -195,6 +198,11 @@ def test_recompute_path_and_reruns_give_the_same_bits(ops, shape):
     if shape == (300, 8, 7, 7):
         rc, d = describe(N, C, HW)      # k_stats_group: 5 k values per member in phase 1, 2 k in phase 2; windows of 4 members per lane
         assert rc == 0 and d['mode'] == 2 and d['K'] < 16 and d['Gs'] > 4 * meet_lanes(2 * d['k']) >= 4 * meet_lanes(5 * d['k']), d
+    if shape in ((2050, 2, 8, 8), (2060, 4, 7, 7)):
+        from cnn_quantization_amd import _lib
+        rc, d = describe(N, C, HW)      # k_stats_group at K = 8, rows past the end of the last split; one launch only when asked (bit 3)
+        assert rc == 0 and d['mode'] == 2 and d['K'] == 8 and d['Gs'] > 256 and N % 8 != 0, d
+        assert _lib.load().cnnq_pc_stats_route(N, C, HW, 1, ops.GROUP_WS_BYTES, 8) == 2
     xd = acts(shape, 21 + C).cuda()
     ops.group_status(xd, clear=True)
     st0, mom0 = ops.pc_stats_single(xd, N, C, HW, True, True, True)
