@@ -63,6 +63,7 @@
 #include "cnnq_nhwc_entropy.hip.h"
 #include "cnnq_nhwc_packed.hip.h"
 #include "cnnq_qerr.hip.h"
+#include "cnnq_nhwc_qerr.hip.h"
 #include "cnnq_rows.hip.h"
 #include "cnnq_flat.hip.h"
 
@@ -2329,6 +2330,58 @@ int cnnq_pc_stats_nhwc(const void* x, int dtype, int64_t R, int64_t C, int need_
     const ClPlan p(R, C, dtype, h_align(x, x));
     if (const int rc = p.range(true)) return rc;
     return cl_table(x, dtype, R, C, p, need_b != 0, need_kurt != 0, need_relu != 0, ws, mom, stats, stream);
+}
+
+// ---- `-sm collect -ce` on dense channels_last activations (cnnq_nhwc_qerr.hip.h): x [N][HW][C], C innermost ------------------------
+// the argument checks the three functions share: 0 - the plan exists (the grid N * S * nb and the fold's N stay in 32 bits)
+static int cl_qe_check(int64_t N, int64_t HW, int64_t C, int K, int dtype) {
+    if (!dtype_ok(dtype) || K < 1 || K > 3 || N < 1 || HW < 1 || C < 1 || C > CL_C_MAX) return CNNQ_EINVAL;
+    if (N >= ((int64_t)1 << 31) || HW >= ((int64_t)1 << 31)) return CNNQ_ERANGE;      // k_qerr_fold takes both as int
+    const int64_t nbmax = (C + TPB - 1) / TPB;      // column blocks of the narrowest piece
+    return N * cl_qe_slabs(N, HW, C) * nbmax >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
+}
+
+size_t cnnq_pc_qerr_nhwc_workspace(int64_t N, int64_t HW, int64_t C, int K, int dtype) {
+    if (cl_qe_check(N, HW, C, K, dtype)) return 0;
+    return (size_t)N * (size_t)cl_qe_slabs(N, HW, C) * (size_t)QE_NV(K) * (size_t)C * sizeof(double);
+}
+
+// Which launch cnnq_pc_qerr_nhwc makes for this geometry (host only): out = {elements per load W, slabs per sample nb, rows per
+// slab, 1 - the native launch}.  out[3] is 1 throughout: no class of layer is sent back to the copy route; one that measures slower
+// native than through the copy (tools/bench_channels_last_qerr.py) goes back here, with the figures next to the rule.
+int cnnq_pc_route_qerr_nhwc(int64_t N, int64_t HW, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
+    if (!out || !pow2(align_bytes)) return CNNQ_EINVAL;
+    if (const int rc = cl_qe_check(N, HW, C, 1, dtype)) return rc;
+    const ClGeo g = cl_geo_qe(N, HW, C, cl_qe_piece(C, cl_esize(dtype), align_bytes));
+    out[0] = g.P ? (int32_t)(C / g.P) : 0;
+    out[1] = g.S;
+    out[2] = (int32_t)(g.rpw < INT32_MAX ? g.rpw : INT32_MAX);
+    out[3] = 1;
+    return 0;
+}
+
+// smpc.py:80-100 on [N][HW][C]: k_cl_qerr -> k_qerr_fold, the fold of cnnq_pc_qerr on the same row records
+int cnnq_pc_qerr_nhwc(const void* x, int dtype, int64_t N, int64_t HW, int64_t C, const float* qp, int K, const float* mm, void* ws,
+                      float* err, void* stream) {
+    if (!x || !qp || !ws || !err || misaligned(ws, 8)) return CNNQ_EINVAL;
+    if (const int rc = cl_qe_check(N, HW, C, K, dtype)) return rc;
+    const ClGeo g = cl_geo_qe(N, HW, C, cl_qe_piece(C, cl_esize(dtype), h_align(x, x)));
+    hipStream_t st = hs(stream);
+    double* rec = reinterpret_cast<double*>(ws);
+    const dim3 grid((unsigned)(N * g.S * g.nb));
+    const int rc = cl_launch(dtype, (int)(C / g.P), x, [&](auto pc, auto* xr) {
+        using P = decltype(pc);
+        if constexpr (P::W <= CL_QE_WMAX)
+            with_int<1, 2, 3>(K, [&](auto k) {
+                hipLaunchKernelGGL((k_cl_qerr<typename P::T, P::W, decltype(k)::value>), grid, dim3(TPB), 0, st, xr, g, qp, mm, rec);
+            });
+    });
+    if (rc) return rc;
+    with_int<1, 2, 3>(K, [&](auto k) {
+        hipLaunchKernelGGL((k_qerr_fold<decltype(k)::value>), dim3((unsigned)((C + QF_CH - 1) / QF_CH)), dim3(TPB), 0, st, rec, (int)N, g.S, (int)C,
+                           (int)HW, err);
+    });
+    return launch_status();
 }
 
 // ---- config 5 on dense channels_last activations (cnnq_nhwc_midtread.hip.h) ----------------------------------------------------

@@ -274,6 +274,9 @@ class TruncationOpManagerInference:
         q.half_midtread = True
         # ... and with the entropy of a uniform quantizer's codes, -me (IntQuantizer._half_entropy)
         q.half_entropy = True
+        # ... and `-sm use -c mix` on channels_last or contiguous bf16 / fp16 activations (IntQuantizer._clip_route's row 'mix',
+        # DESIGN.md section 30)
+        q.native_mix = True
         return q
 
     def _fill(self, qtype, qparams, qweight):
@@ -350,7 +353,7 @@ class QuantizationManagerInference(metaclass=Singleton):
             if args.per_channel_quant_act:
                 self.stats_manager = StatisticManagerPerChannel(sf, load_stats=False, batch_avg=args.stats_batch_avg,
                                                                 collect_err=bool(getattr(args, 'collect_err', False)),
-                                                                group=group)
+                                                                group=group, native_err=True)
             else:
                 self.stats_manager = StatisticManager(sf, load_stats=False, batch_avg=args.stats_batch_avg,
                                                       kld_threshold=args.kld_threshold)

@@ -13,6 +13,8 @@ collect_route decides once per tensor how it is taken: 'n
 bf16 / fp16 is read where it lies (ops.pc_stats_nhwc, DESIGN.md section 18: no layout copy, no upcast); 'half' - a contiguous
 bf16 / fp16 activation is read in its own dtype (ops.pc_stats_half); None - every other tensor takes the
 NCHW kernels on a contiguous float32 copy.  collects_native_nhwc and collects_native_half are its boolean views.
+With collect_err the answer is None unless the manager opted in (native_err, which the inference manager sets): then a channels_last
+activation answers 'nhwc' and its error columns come from the same storage too (ops.pc_quant_errors_nhwc).
 
 `collect_err=True` adds the six clipping-error columns the reference declares (smpc.py:24-32: mse_lowp, mse_gaus,
 mse_laplace, cos_lowp, cos_gaus, cos_laplace; formulas smpc.py:80-100) - the columns `-sm use -c mix` (iq.py:310-323)
@@ -48,14 +50,18 @@ ERR_NAMES = ('mse_lowp', 'mse_gaus', 'mse_laplace', 'cos_lowp', 'cos_gaus', 'cos
 def collect_route(manager, tensor, force_global_min_max=False):
     """How save_tensor_stats takes this tensor: 'nhwc' - on its channels_last storage (ops.pc_stats_nhwc),
     'half' - contiguous, in its own dtype (ops.pc_stats_half) - or None: ops.pc_stats on a contiguous float32 copy.  Each fact
-    once, in this order: the manager - no error columns, the extrema of the whole batch (batch_avg off, or the caller forces
-    them); the storage class - 'nhwc': dense channels_last and not contiguous, a dtype the kernels have, the channels_last switch
+    once, in this order: the manager - no error columns (with native_err: 'nhwc' measures them too, 'half' does not), the extrema
+    of the whole batch (batch_avg off, or the caller forces them); the storage class - 'nhwc': dense channels_last and not contiguous, a dtype the kernels have, the channels_last switch
     on; 'half': a contiguous non-empty 4-D bf16 / fp16 CUDA activation with a spatial extent; the group - one process, no forced
     exchange; last the class's route function.  Shape, strides and attributes only: nothing touches the device."""
-    if manager.collect_err or (manager.batch_avg and not force_global_min_max) or not isinstance(tensor, torch.Tensor):
+    err = manager.collect_err
+    if (err and not getattr(manager, 'native_err', False)) or (manager.batch_avg and not force_global_min_max) \
+            or not isinstance(tensor, torch.Tensor):
         return None
     if tensor.dtype in ops._ACT_DTYPES and ops._NHWC and ops._layout(tensor) == 'nhwc':
         route = 'nhwc'
+    elif err:
+        return None
     elif (tensor.is_cuda and tensor.dtype in ops._HALF_DTYPES and tensor.dim() == 4 and tensor.numel() > 0 and tensor.is_contiguous()
             and (tensor.shape[2] > 1 or tensor.shape[3] > 1)):
         route = 'half'
@@ -64,7 +70,10 @@ def collect_route(manager, tensor, force_global_min_max=False):
     if D.world_size(manager.group) > 1 or D.forced_exchange():
         return None
     if route == 'nhwc':
-        native = ops._stats_nhwc_native(tensor.numel() // tensor.shape[1], tensor.shape[1], tensor.dtype)
+        N, C = tensor.shape[0], tensor.shape[1]
+        native = ops._stats_nhwc_native(tensor.numel() // C, C, tensor.dtype)
+        if native and err:
+            native = ops._qerr_nhwc_native(N, tensor.numel() // (N * C), C, tensor.dtype)
     else:
         native = ops._stats_half_native(*ops.geometry(tensor), tensor.dtype)
     return route if native else None
@@ -84,7 +93,7 @@ class StatisticManagerPerChannel(Collector, metaclass=Singleton):
     collect_route = collect_route       # the face inference_quantization_manager._route asks
 
     def __init__(self, folder, load_stats, stats=('max', 'min', 'std', 'mean', 'kurtosis', 'b', 'std_pos'),
-                 batch_avg=False, collect_err=False, group=None, err_settings=None):
+                 batch_avg=False, collect_err=False, group=None, err_settings=None, native_err=False):
         self.name = folder
         self.folder = os.path.join(base_dir(), 'statistics/per_channel', folder)
         self.stats_names = list(stats)
@@ -93,6 +102,8 @@ class StatisticManagerPerChannel(Collector, metaclass=Singleton):
                 raise NotImplementedError('collect_err with a batch sharded over ranks (the row records are local to a sample)')
             self.stats_names += [n for n in ERR_NAMES if n not in self.stats_names]   # smpc.py:24-32, in that order
         self.collect_err = collect_err
+        # the route 'nhwc' with collect_err: opt-in per object; the inference manager opts in
+        self.native_err = native_err
         # what the three candidates need besides the table: a dict {num_bits, positive, bit_alloc, prior_is_b, target,
         # round_mode} (the arguments of ops.mix_candidates) or a callable (tag, half_range) -> such a dict
         self.err_settings = err_settings
@@ -121,6 +132,12 @@ class StatisticManagerPerChannel(Collector, metaclass=Singleton):
         if route:
             # the table from the channels_last storage as it lies, or from the tensor in its own dtype (23)
             table, _ = (ops.pc_stats_nhwc if route == 'nhwc' else ops.pc_stats_half)(tensor.detach(), **need)
+            if self.collect_err:
+                # the same three candidates as below, measured on the channels_last storage; the table's
+                # min / max rows are x's exact extrema (no batch_avg on this route)
+                qp_l, qp_g, qp_p = ops.mix_candidates(table, **self._err_settings(tag, half_range, err_settings))
+                err = ops.pc_quant_errors_nhwc(tensor.detach(), (qp_p, qp_g, qp_l), mm=table[[L.STAT_MIN, L.STAT_MAX]])
+                table = torch.cat([table, err])
             return self._record(id, table)
         N, C = tensor.shape[0], tensor.shape[1]
         HW = tensor.numel() // (N * C)

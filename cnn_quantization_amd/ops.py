@@ -732,6 +732,64 @@ def pc_quant_errors(x, N, C, HW, qps, mm=None):
     return err
 
 
+_QERR_NHWC_NATIVE = {}
+
+
+def _qerr_nhwc_native(N, HW, C, dtype):
+    """Whether this class of layer measures its error columns on the channels_last kernel: the "native" word of
+    cnnq_pc_route_qerr_nhwc's report (0: a class that measured slower native than through the copy is sent back there).  The
+    statistics manager (collect_route with native_err) and the tests patch the function and empty the cache by name."""
+    return _route_word(_QERR_NHWC_NATIVE, (N, HW, C, dtype), bool, 'cnnq_pc_route_qerr_nhwc', (N, HW, C), dtype)
+
+
+def pc_quant_errors_nhwc(x, qps, mm=None):
+    """pc_quant_errors of a dense channels_last 4-D activation of fp32 / bf16 / fp16, on the storage as it lies (DESIGN.md section
+    30; cnnq_pc_qerr_nhwc): [2K, C] float32, the columns of x.float() - one read of x, 4 B/elem in fp32 and 2 in bf16 / fp16, no
+    quantized tensor.  qps, mm: as pc_quant_errors (the result does not depend on mm).  Anything else - a CPU tensor, another dtype,
+    not 4-D, contiguous, not dense - raises: nothing is copied or upcast here."""
+    lib = L.load()
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise L.CnnqError('pc_quant_errors_nhwc: x must be a CUDA/HIP tensor (there is no CPU path)')
+    if x.dtype not in _ACT_DTYPES:
+        raise L.CnnqError('pc_quant_errors_nhwc: x must be float32, bfloat16 or float16, got %s' % x.dtype)
+    if x.dim() != 4:
+        _not_4d(x, 'pc_quant_errors_nhwc')
+    if _layout(x) != 'nhwc' or x.numel() == 0:
+        raise L.CnnqError('pc_quant_errors_nhwc: x must be a non-empty dense channels_last tensor that is not contiguous (no copy '
+                          'is made here; pc_quant_errors takes contiguous float32)')
+    if x.device.index != torch.cuda.current_device():
+        raise L.CnnqError('pc_quant_errors_nhwc: x is on %s but the current device is cuda:%d' % (x.device, torch.cuda.current_device()))
+    if x.requires_grad:
+        x = x.detach()
+    N, C = x.shape[0], x.shape[1]
+    HW = x.numel() // (N * C)
+    qps = list(qps)
+    K = len(qps)
+    if not 1 <= K <= 3:
+        raise L.CnnqError('pc_quant_errors_nhwc: 1..3 candidate tables, got %d' % K)
+    for q in qps:
+        if not (isinstance(q, torch.Tensor) and q.device == x.device and q.dtype == torch.float32 and tuple(q.shape) == (L.NQP, C)):
+            raise L.CnnqError('pc_quant_errors_nhwc: every table must be a float32 [%d, %d] tensor on %s' % (L.NQP, C, x.device))
+    qp = torch.stack(qps).contiguous()
+    if mm is not None:
+        mm = mm.to(device=x.device, dtype=torch.float32).contiguous()
+        if tuple(mm.shape) != (2, C):
+            raise L.CnnqError('pc_quant_errors_nhwc: mm must be [2, %d]' % C)
+    dt = _DTYPE_CODES[x.dtype]
+    key = ('qerr_nhwc', N, HW, C, K, dt)
+    nbytes = _WS_BYTES.get(key)
+    if nbytes is None:
+        nbytes = lib.cnnq_pc_qerr_nhwc_workspace(N, HW, C, K, dt)
+        if nbytes == 0:
+            raise L.CnnqError('cnnq_pc_qerr_nhwc_workspace(%d, %d, %d, %d): no plan for these sizes' % (N, HW, C, K))
+        _WS_BYTES[key] = nbytes
+    st = _raw_stream(x.device.index)
+    err = torch.empty((2 * K, C), dtype=torch.float32, device=x.device)
+    L.check(lib.cnnq_pc_qerr_nhwc(_ptr(x), dt, N, HW, C, _ptr(qp), K, _ptr(mm), _ptr(_scratch(x, 'qerr', nbytes, st)), _ptr(err), st),
+            'cnnq_pc_qerr_nhwc')
+    return err
+
+
 def act_qdq_mix(x, num_bits, stats, mse, positive=False, bit_alloc=False, prior_is_b=False, target=None, round_mode=True,
                 whole_tensor=False, want_codes=False, want_entropy=False, out=None):
     """clip_type == 'mix' of the `-sm use` route (iq.py:310-323 + 327-359): per channel the Gaussian clipping value where
@@ -739,8 +797,11 @@ def act_qdq_mix(x, num_bits, stats, mse, positive=False, bit_alloc=False, prior_
     comparisons with NaN are False, so a file whose error columns are NaN - all the reference's own collection writes -
     gives plain Laplace clipping.  stats [NSTAT, C]: the file's mean_{min, max, mean, b, std} rows; mse [3, C]: rows
     laplace, gaus, lowp.  Everything downstream of the clipping value is per channel and elementwise, so the three
-    candidates' parameter tables (mix_candidates) are merged per channel, then one fused Q/DQ."""
-    x = _dev(x, 'x')
+    candidates' parameter tables (mix_candidates) are merged per channel, then one fused Q/DQ.  Per channel without codes or
+    entropy x is admitted as pc_qdq admits it - a dense channels_last tensor of fp32 / bf16 / fp16 or a contiguous bf16 / fp16
+    one is quantized where it lies, and y keeps its dtype and layout; every other combination takes a
+    contiguous float32 x."""
+    x = _dev(x, 'x') if (whole_tensor or want_codes or want_entropy) else _dev_act_layout(x, 'x')
     N, C, HW = (1, 1, x.numel()) if whole_tensor else geometry(x)
     stats = stats.to(device=x.device, dtype=torch.float32)
     mse = torch.as_tensor(mse, dtype=torch.float32, device=x.device).view(3, C)

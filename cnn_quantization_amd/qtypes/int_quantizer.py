@@ -120,6 +120,9 @@ class IntQuantizer:
         # the route 'half_entropy' (-me with a uniform quantizer on a contiguous bf16 / fp16 activation):
         # opt-in per object in the same way, and for the same reason
         self.half_entropy = False
+        # the route 'mix' (-sm use -c mix on a dense channels_last or contiguous bf16 / fp16 activation):
+        # opt-in per object in the same way, and for the same reason
+        self.native_mix = False
 
     # ------------------------------------------------------------------ dispatch, iq.py:92-122
     def __call__(self, tensor, id, tag="", stat_id=None, override_att=None):
@@ -198,7 +201,8 @@ class IntQuantizer:
         """gemmlowpClippingQuantize.  Per channel, Laplace or Gaussian clipping without -me: a pending correction folded in on
         channels_last, the calibration table on a contiguous half tensor (both need stat_id), ACIQ on channels_last, dynamic ACIQ
         on a contiguous half tensor (opt-in: half_dynamic).  With -me: 'half_entropy' on a contiguous half tensor, dynamic or
-        from the table (opt-in: half_entropy).  Per tensor, also '<p>std': the flat route.  'mix' has none."""
+        from the table (opt-in: half_entropy).  Per tensor, also '<p>std': the flat route.  'mix': per channel from the statistics
+        file, without -me or a pending correction, on either storage class (opt-in: native_mix)."""
         pc, one_gpu, use_ba, pending = self._facts(tensor, att)
         if not one_gpu:
             return None
@@ -207,6 +211,11 @@ class IntQuantizer:
         if not pc:
             clips = clip_type in ('laplace', 'gaus') or (isinstance(clip_type, str) and clip_type.endswith('std'))
             return 'flat_clip' if clips and not direct and self._flat_tensor(tensor) else None
+        if clip_type == 'mix':
+            # -c mix from the statistics file: ops.act_qdq_mix merges the candidates' tables and ends in ops.pc_qdq, which has
+            # kernels for both storage classes (opt-in: native_mix).  The name routes nothing; it keeps __call__ from upcasting.
+            return 'mix' if (stat_id is not None and not att('measure_entropy') and not pending and self.native_mix
+                             and _storage(tensor) is not None) else None
         if clip_type not in ('laplace', 'gaus'):
             return None
         if att('measure_entropy'):

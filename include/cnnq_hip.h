@@ -726,6 +726,27 @@ int cnnq_pc_route_stats_nhwc(int64_t R, int64_t C, int dtype, int align_bytes, i
 int cnnq_pc_stats_nhwc(const void* x, int dtype, int64_t R, int64_t C, int need_b, int need_kurt, int need_relu, void* ws,
                        double* mom, float* stats, void* stream);
 
+/* `-sm collect -ce` - the per-channel clipping-error columns of smpc.py:80-100 (declared at smpc.py:24-32, consumed by
+ * iq.py:310-323), counterpart of cnnq_pc_qerr - on dense channels_last activations x[N][HW][C] of fp32 / bf16 / fp16, on the
+ * storage as it lies: ONE read of x, no layout copy, no upcast, no quantized tensor written.  qp, K, mm and err are
+ * cnnq_pc_qerr's: K = 1..3 tables [K][CNNQ_NQP][C]; mm (optional) the channel extrema [2][C], on which the result does not
+ * depend; err [2K][C] fp32, rows mse_0..K-1 then cos_0..K-1.  The columns are those of the exactly upconverted x: q_k is the
+ * fp32 value cnnq_pc_qdq_nhwc computes with table k BEFORE it converts to x's dtype, every term is one fp32 operation, the
+ * sums are fp64 row records (per sample and slab of its HW rows, folded by cnnq_pc_qerr's own fold), rounded once; against fp64
+ * sums of the same terms within 2e-6.  The order of the additions is fixed by (N, HW, C, dtype, alignment) alone: no atomics,
+ * bit-identical run after run - not the NCHW kernel's order.
+ * cnnq_pc_qerr_nhwc_workspace: bytes of `ws` = N * nb * (1 + 3K) * C * 8 with nb the slabs per sample of the route's report
+ * (they do not depend on the alignment); 0 on sizes it has no plan for.
+ * cnnq_pc_route_qerr_nhwc (host only, nothing enqueued): out = {elements per load W (at most 2), slabs per sample nb, rows
+ * per slab, 1 - the native launch (0 would say: this class of layer goes back to the copy route; none does)}.
+ * ws: 8-byte aligned.  A bad dtype, K outside 1..3, N / HW / C < 1, a NULL x / qp / ws / err or a misaligned ws returns
+ * CNNQ_EINVAL, N or HW of 2^31 or a grid of 2^31 workgroups CNNQ_ERANGE, before anything touches the device.  Two launches,
+ * no host synchronisation, no allocation, graph-capturable. */
+size_t cnnq_pc_qerr_nhwc_workspace(int64_t N, int64_t HW, int64_t C, int K, int dtype);
+int cnnq_pc_route_qerr_nhwc(int64_t N, int64_t HW, int64_t C, int dtype, int align_bytes, int32_t out[4]);
+int cnnq_pc_qerr_nhwc(const void* x, int dtype, int64_t N, int64_t HW, int64_t C, const float* qp, int K,
+                      const float* mm /* or NULL */, void* ws, float* err, void* stream);
+
 /* `-sm collect` - the same table - on CONTIGUOUS bf16 / fp16 activations x[N][C][HW], on the storage as it lies: no fp32 copy, x is
  * read once per pass (4 B/elem for the full table).  A row x[n][c][0 .. HW) is cut into pieces of W elements (the widest of 8 / 4 /
  * 2 / 1 that divides HW and x's alignment: every (HW, alignment) has a route); a 256-lane workgroup owns one channel and one of S
