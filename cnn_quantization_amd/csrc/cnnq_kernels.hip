@@ -64,6 +64,7 @@
 #include "cnnq_nhwc_packed.hip.h"
 #include "cnnq_qerr.hip.h"
 #include "cnnq_nhwc_qerr.hip.h"
+#include "cnnq_half_qerr.hip.h"
 #include "cnnq_rows.hip.h"
 #include "cnnq_flat.hip.h"
 
@@ -1747,6 +1748,71 @@ int cnnq_pc_stats_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW,
     });
     if (!rc) rc = cnnq_pc_combine_dev(a.part2, G, C, rec, need_kurt ? 1 : 0, nullptr, stats, stream);
     return rc;
+}
+
+// ---- `-sm collect -ce` on contiguous bf16 / fp16 activations (cnnq_half_qerr.hip.h) -----------------------------------------------
+// the argument checks the three functions share, HPlan's with K: 0 - the plan exists (bf16 / fp16: N and C * HW below 2^31, so
+// k_qerr_fold takes N, nb, C and HW as int and the grid C * S * nb stays in 32 bits by h_qe_splits)
+static int h_qe_check(int64_t N, int64_t C, int64_t HW, int K, int dtype, bool ok) {
+    return HPlan(N, C, HW, dtype, ok && K >= 1 && K <= 3).rc;
+}
+
+// ws, doubles: rec[N * nb][QE_NV(K)][C] with nb = h_qe_parts, not the alignment's; fp32: what cnnq_pc_qerr takes
+size_t cnnq_pc_qerr_dt_workspace(int64_t N, int64_t C, int64_t HW, int K, int dtype) {
+    if (h_qe_check(N, C, HW, K, dtype, true)) return 0;
+    if (dtype == CNNQ_DTYPE_F32) return cnnq_pc_qerr_workspace(N, C, HW, K);
+    return (size_t)N * (size_t)h_qe_parts(N, C, HW) * (size_t)QE_NV(K) * (size_t)C * sizeof(double);
+}
+
+// Which launch cnnq_pc_qerr_dt makes for this geometry (host only): out = {piece width W, column parts per row nb, rows a workgroup
+// takes per step (TPB / the lanes of a row), 1 - the native launch / 0 - a class of layer that did not win against the upcast
+// route and stays there: h_qerr_native, with the figures next to the rule}.  fp32: cnnq_pc_qerr's plan - {elements per load, slices per row, 1, 1}.
+int cnnq_pc_route_qerr_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int32_t out[4]) {
+    if (const int rc = h_qe_check(N, C, HW, 1, dtype, out && pow2(align_bytes))) return rc;
+    if (dtype == CNNQ_DTYPE_F32) {
+        Variant v;
+        Geo g;
+        if (const int rc = qerr_plan(N, C, HW, align_bytes >= 16, &v, &g)) return rc;
+        out[0] = v.vec;
+        out[1] = g.mode == 1 ? g.nb : 1;
+        out[2] = 1;
+        out[3] = 1;
+        return 0;
+    }
+    out[0] = h_piece(HW, (uintptr_t)align_bytes, 0);
+    out[1] = h_qe_parts(N, C, HW);
+    out[2] = TPB / h_qe_seg(HW, out[0], out[1]);
+    out[3] = h_qerr_native(N, C, HW, dtype);
+    return 0;
+}
+
+// smpc.py:80-100 (the cosine: utils/misc.py:23-34) on x[N][C][HW] of bf16 / fp16: k_h_qerr -> k_qerr_fold, the fold of
+// cnnq_pc_qerr on the same row records
+int cnnq_pc_qerr_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, int K, const float* mm, void* ws,
+                    float* err, void* stream) {
+    const bool f32 = dtype == CNNQ_DTYPE_F32;
+    if (const int rc = h_qe_check(N, C, HW, K, dtype, x && qp && ws && err && !misaligned(ws, 8) && (f32 || !misaligned(x, 2)))) return rc;
+    if (f32) return cnnq_pc_qerr(static_cast<const float*>(x), N, C, HW, qp, K, mm, ws, err, stream);
+    const int w = h_piece(HW, (uintptr_t)x, 0), nb = h_qe_parts(N, C, HW), seg = h_qe_seg(HW, w, nb);
+    const HGeo g = h_geo(N, C, HW, w, h_qe_splits(N, C, HW, nb, seg), nb);
+    hipStream_t st = hs(stream);
+    double* rec = reinterpret_cast<double*>(ws);
+    const dim3 grid((unsigned)(C * g.S * nb));
+    const int rc = h_launch(dtype, w, x, [&](auto pc, const uint16_t* xh) {
+        with_int<1, 2, 3>(K, [&](auto k) {
+            with_bool(mm != nullptr, [&](auto m) {
+                using P = decltype(pc);
+                hipLaunchKernelGGL((k_h_qerr<typename P::T, P::W, decltype(k)::value, decltype(m)::value>), grid, dim3(TPB), 0, st, xh, g, seg,
+                                   qp, mm, rec);
+            });
+        });
+    });
+    if (rc) return rc;
+    with_int<1, 2, 3>(K, [&](auto k) {
+        hipLaunchKernelGGL((k_qerr_fold<decltype(k)::value>), dim3((unsigned)((C + QF_CH - 1) / QF_CH)), dim3(TPB), 0, st, rec, (int)N, nb, (int)C,
+                           (int)HW, err);
+    });
+    return launch_status();
 }
 
 // ---- `-sm use ... -bca` on contiguous bf16 / fp16 activations (cnnq_half_bcorr.hip.h) -------------------------------------------

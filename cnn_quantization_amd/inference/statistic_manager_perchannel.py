@@ -14,7 +14,9 @@ bf16 / fp16 is read where it lies (ops.pc_stats_nhwc, DESIGN.md section 18: no l
 bf16 / fp16 activation is read in its own dtype (ops.pc_stats_half); None - every other tensor takes the
 NCHW kernels on a contiguous float32 copy.  collects_native_nhwc and collects_native_half are its boolean views.
 With collect_err the answer is None unless the manager opted in (native_err, which the inference manager sets): then a channels_last
-activation answers 'nhwc' and its error columns come from the same storage too (ops.pc_quant_errors_nhwc).
+activation answers 'nhwc' and its error columns come from the same storage too (ops.pc_quant_errors_nhwc, DESIGN.md section 30);
+with native_err_half on top (the inference manager sets both) a contiguous bf16 / fp16 activation answers 'half' and its error
+columns are measured in its own dtype (ops.pc_quant_errors_half).
 
 `collect_err=True` adds the six clipping-error columns the reference declares (smpc.py:24-32: mse_lowp, mse_gaus,
 mse_laplace, cos_lowp, cos_gaus, cos_laplace; formulas smpc.py:80-100) - the columns `-sm use -c mix` (iq.py:310-323)
@@ -50,7 +52,7 @@ ERR_NAMES = ('mse_lowp', 'mse_gaus', 'mse_laplace', 'cos_lowp', 'cos_gaus', 'cos
 def collect_route(manager, tensor, force_global_min_max=False):
     """How save_tensor_stats takes this tensor: 'nhwc' - on its channels_last storage (ops.pc_stats_nhwc),
     'half' - contiguous, in its own dtype (ops.pc_stats_half) - or None: ops.pc_stats on a contiguous float32 copy.  Each fact
-    once, in this order: the manager - no error columns (with native_err: 'nhwc' measures them too, 'half' does not), the extrema
+    once, in this order: the manager - no error columns (with native_err: 'nhwc' measures them too, 'half' with native_err_half as well), the extrema
     of the whole batch (batch_avg off, or the caller forces them); the storage class - 'nhwc': dense channels_last and not contiguous, a dtype the kernels have, the channels_last switch
     on; 'half': a contiguous non-empty 4-D bf16 / fp16 CUDA activation with a spatial extent; the group - one process, no forced
     exchange; last the class's route function.  Shape, strides and attributes only: nothing touches the device."""
@@ -60,7 +62,7 @@ def collect_route(manager, tensor, force_global_min_max=False):
         return None
     if tensor.dtype in ops._ACT_DTYPES and ops._NHWC and ops._layout(tensor) == 'nhwc':
         route = 'nhwc'
-    elif err:
+    elif err and not getattr(manager, 'native_err_half', False):
         return None
     elif (tensor.is_cuda and tensor.dtype in ops._HALF_DTYPES and tensor.dim() == 4 and tensor.numel() > 0 and tensor.is_contiguous()
             and (tensor.shape[2] > 1 or tensor.shape[3] > 1)):
@@ -76,6 +78,8 @@ def collect_route(manager, tensor, force_global_min_max=False):
             native = ops._qerr_nhwc_native(N, tensor.numel() // (N * C), C, tensor.dtype)
     else:
         native = ops._stats_half_native(*ops.geometry(tensor), tensor.dtype)
+        if native and err:
+            native = ops._qerr_half_native(*ops.geometry(tensor), tensor.dtype)
     return route if native else None
 
 
@@ -93,7 +97,8 @@ class StatisticManagerPerChannel(Collector, metaclass=Singleton):
     collect_route = collect_route       # the face inference_quantization_manager._route asks
 
     def __init__(self, folder, load_stats, stats=('max', 'min', 'std', 'mean', 'kurtosis', 'b', 'std_pos'),
-                 batch_avg=False, collect_err=False, group=None, err_settings=None, native_err=False):
+                 batch_avg=False, collect_err=False, group=None, err_settings=None, native_err=False,
+                 native_err_half=False):
         self.name = folder
         self.folder = os.path.join(base_dir(), 'statistics/per_channel', folder)
         self.stats_names = list(stats)
@@ -104,6 +109,8 @@ class StatisticManagerPerChannel(Collector, metaclass=Singleton):
         self.collect_err = collect_err
         # the route 'nhwc' with collect_err: opt-in per object; the inference manager opts in
         self.native_err = native_err
+        # the route 'half' with collect_err: opt-in per object on top of native_err
+        self.native_err_half = native_err_half
         # what the three candidates need besides the table: a dict {num_bits, positive, bit_alloc, prior_is_b, target,
         # round_mode} (the arguments of ops.mix_candidates) or a callable (tag, half_range) -> such a dict
         self.err_settings = err_settings
@@ -133,10 +140,12 @@ class StatisticManagerPerChannel(Collector, metaclass=Singleton):
             # the table from the channels_last storage as it lies, or from the tensor in its own dtype (23)
             table, _ = (ops.pc_stats_nhwc if route == 'nhwc' else ops.pc_stats_half)(tensor.detach(), **need)
             if self.collect_err:
-                # the same three candidates as below, measured on the channels_last storage; the table's
-                # min / max rows are x's exact extrema (no batch_avg on this route)
+                # the same three candidates as below, measured on the channels_last storage or on the
+                # contiguous tensor in its own dtype (31); the table's min / max rows are x's exact extrema (no batch_avg on
+                # these routes)
                 qp_l, qp_g, qp_p = ops.mix_candidates(table, **self._err_settings(tag, half_range, err_settings))
-                err = ops.pc_quant_errors_nhwc(tensor.detach(), (qp_p, qp_g, qp_l), mm=table[[L.STAT_MIN, L.STAT_MAX]])
+                errors = ops.pc_quant_errors_nhwc if route == 'nhwc' else ops.pc_quant_errors_half
+                err = errors(tensor.detach(), (qp_p, qp_g, qp_l), mm=table[[L.STAT_MIN, L.STAT_MAX]])
                 table = torch.cat([table, err])
             return self._record(id, table)
         N, C = tensor.shape[0], tensor.shape[1]

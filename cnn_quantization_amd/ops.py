@@ -747,7 +747,6 @@ def pc_quant_errors_nhwc(x, qps, mm=None):
     30; cnnq_pc_qerr_nhwc): [2K, C] float32, the columns of x.float() - one read of x, 4 B/elem in fp32 and 2 in bf16 / fp16, no
     quantized tensor.  qps, mm: as pc_quant_errors (the result does not depend on mm).  Anything else - a CPU tensor, another dtype,
     not 4-D, contiguous, not dense - raises: nothing is copied or upcast here."""
-    lib = L.load()
     if not isinstance(x, torch.Tensor) or not x.is_cuda:
         raise L.CnnqError('pc_quant_errors_nhwc: x must be a CUDA/HIP tensor (there is no CPU path)')
     if x.dtype not in _ACT_DTYPES:
@@ -762,32 +761,56 @@ def pc_quant_errors_nhwc(x, qps, mm=None):
     if x.requires_grad:
         x = x.detach()
     N, C = x.shape[0], x.shape[1]
-    HW = x.numel() // (N * C)
+    return _quant_errors_native('pc_quant_errors_nhwc', 'cnnq_pc_qerr_nhwc', x, (N, x.numel() // (N * C), C), C, _DTYPE_CODES[x.dtype],
+                                _raw_stream(x.device.index), qps, mm)
+
+
+def _quant_errors_native(what, fn, x, geo, C, dt, st, qps, mm):
+    """The error columns [2K, C] of an admitted tensor on its native storage in one host call with one cached workspace (fn:
+    cnnq_pc_qerr_nhwc with geo = (N, HW, C), cnnq_pc_qerr_dt with geo = (N, C, HW)): the table and mm checks, the row records, the
+    kernel and the fold."""
+    lib = L.load()
     qps = list(qps)
     K = len(qps)
     if not 1 <= K <= 3:
-        raise L.CnnqError('pc_quant_errors_nhwc: 1..3 candidate tables, got %d' % K)
+        raise L.CnnqError('%s: 1..3 candidate tables, got %d' % (what, K))
     for q in qps:
         if not (isinstance(q, torch.Tensor) and q.device == x.device and q.dtype == torch.float32 and tuple(q.shape) == (L.NQP, C)):
-            raise L.CnnqError('pc_quant_errors_nhwc: every table must be a float32 [%d, %d] tensor on %s' % (L.NQP, C, x.device))
+            raise L.CnnqError('%s: every table must be a float32 [%d, %d] tensor on %s' % (what, L.NQP, C, x.device))
     qp = torch.stack(qps).contiguous()
     if mm is not None:
         mm = mm.to(device=x.device, dtype=torch.float32).contiguous()
         if tuple(mm.shape) != (2, C):
-            raise L.CnnqError('pc_quant_errors_nhwc: mm must be [2, %d]' % C)
-    dt = _DTYPE_CODES[x.dtype]
-    key = ('qerr_nhwc', N, HW, C, K, dt)
+            raise L.CnnqError('%s: mm must be [2, %d]' % (what, C))
+    key = (fn, *geo, K, dt)
     nbytes = _WS_BYTES.get(key)
     if nbytes is None:
-        nbytes = lib.cnnq_pc_qerr_nhwc_workspace(N, HW, C, K, dt)
+        nbytes = getattr(lib, fn + '_workspace')(*geo, K, dt)
         if nbytes == 0:
-            raise L.CnnqError('cnnq_pc_qerr_nhwc_workspace(%d, %d, %d, %d): no plan for these sizes' % (N, HW, C, K))
+            raise L.CnnqError('%s_workspace(%d, %d, %d, %d): no plan for these sizes' % (fn, *geo, K))
         _WS_BYTES[key] = nbytes
-    st = _raw_stream(x.device.index)
     err = torch.empty((2 * K, C), dtype=torch.float32, device=x.device)
-    L.check(lib.cnnq_pc_qerr_nhwc(_ptr(x), dt, N, HW, C, _ptr(qp), K, _ptr(mm), _ptr(_scratch(x, 'qerr', nbytes, st)), _ptr(err), st),
-            'cnnq_pc_qerr_nhwc')
+    L.check(getattr(lib, fn)(_ptr(x), dt, *geo, _ptr(qp), K, _ptr(mm), _ptr(_scratch(x, 'qerr', nbytes, st)), _ptr(err), st), fn)
     return err
+
+
+_QERR_HALF_NATIVE = {}
+
+
+def _qerr_half_native(N, C, HW, dtype):
+    """Whether this class of layer measures its error columns on the contiguous bf16 / fp16 kernel: the "native" word of
+    cnnq_pc_route_qerr_dt's report (0: a class that measured slower native than through the upcast is sent back there).  The
+    statistics manager (collect_route with native_err_half) and the tests patch the function and empty the cache by name."""
+    return _route_word(_QERR_HALF_NATIVE, (N, C, HW, dtype), bool, 'cnnq_pc_route_qerr_dt', (N, C, HW), dtype)
+
+
+def pc_quant_errors_half(x, qps, mm=None):
+    """pc_quant_errors of a contiguous 4-D bf16 / fp16 activation, on the storage as it lies (DESIGN.md section 31;
+    cnnq_pc_qerr_dt): [2K, C] float32, the columns of x.float() - one read of x, 2 B/elem, no quantized tensor.  qps, mm: as
+    pc_quant_errors (the result does not depend on mm).  Anything else - a CPU tensor, float32, not 4-D, not contiguous - raises:
+    nothing is copied or upcast here."""
+    x, (_, geo, C, dt, st) = _admit_half(x, 'pc_quant_errors_half', 'pc_quant_errors')
+    return _quant_errors_native('pc_quant_errors_half', 'cnnq_pc_qerr_dt', x, geo, C, dt, st, qps, mm)
 
 
 def act_qdq_mix(x, num_bits, stats, mse, positive=False, bit_alloc=False, prior_is_b=False, target=None, round_mode=True,

@@ -774,6 +774,32 @@ int cnnq_pc_route_stats_dt(int64_t N, int64_t C, int64_t HW, int dtype, int alig
 int cnnq_pc_stats_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, int need_b, int need_kurt, int need_relu, void* ws,
                      double* mom, float* stats, void* stream);
 
+/* `-sm collect -ce` - the per-channel clipping-error columns of smpc.py:80-100 with the cosine of utils/misc.py:23-34 (declared at
+ * smpc.py:24-32, consumed by iq.py:310-323), counterpart of cnnq_pc_qerr - on CONTIGUOUS bf16 / fp16 activations x[N][C][HW], on
+ * the storage as it lies: ONE read of x in its own dtype (2 B/elem), no fp32 copy, no quantized tensor written.  qp, K, mm and
+ * err are cnnq_pc_qerr's: K = 1..3 tables [K][CNNQ_NQP][C]; mm (optional) the channel extrema [2][C], on which the result does
+ * not depend; err [2K][C] fp32, rows mse_0..K-1 then cos_0..K-1.  The columns are those of the exactly upconverted x: q_k is the
+ * fp32 value cnnq_pc_qdq_dt computes with table k BEFORE it converts to x's dtype, every term is one fp32 operation, the terms of
+ * a piece of W elements (cnnq_pc_stats_dt's pieces) are added in fp32 (pairs, then halves), the pieces in fp64 row records (per
+ * sample and column part of its row, folded by cnnq_pc_qerr's own fold), rounded once; against fp64 sums of the same terms
+ * within 2e-6.  The order of the additions is fixed by (N, C, HW, alignment) alone: no atomics, bit-identical run after run -
+ * not the fp32 kernel's order.  CNNQ_DTYPE_F32 forwards to cnnq_pc_qerr.
+ * cnnq_pc_qerr_dt_workspace: bytes of `ws` = N * nb * (1 + 3K) * C * 8 with nb the column parts per row of the route's report
+ * (a function of N, C, HW and the dtype, never of the alignment; fp32: cnnq_pc_qerr_workspace); 0 on bad arguments or sizes it
+ * has no plan for.
+ * cnnq_pc_route_qerr_dt (host only, nothing enqueued): out = {piece width W, column parts per row nb, rows a workgroup takes per
+ * step, 1 - the native launch / 0 - a class of layer that did not measure faster than the upcast route beyond the run's spread and
+ * is left there by callers that have the choice: HW no multiple of 8 with N * HW >= 16384 and N * C * HW < 2^26 (cnnq_pc_qerr_dt
+ * itself runs every class)}; fp32: cnnq_pc_qerr's plan as {elements per load, slices per row, 1, 1}; align_bytes: the power of two
+ * that divides x (<= 16 is what matters).
+ * ws: 8-byte aligned.  A bad dtype, K outside 1..3, N / C / HW < 1, a NULL x / qp / ws / err, a misaligned ws or an x not aligned
+ * to its element size returns CNNQ_EINVAL, a geometry beyond cnnq_pc_groups' limits (N or C * HW of 2^31) CNNQ_ERANGE, before
+ * anything touches the device.  Two launches, no host synchronisation, no allocation, graph-capturable. */
+size_t cnnq_pc_qerr_dt_workspace(int64_t N, int64_t C, int64_t HW, int K, int dtype);
+int cnnq_pc_route_qerr_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int32_t out[4]);
+int cnnq_pc_qerr_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, int K,
+                    const float* mm /* or NULL */, void* ws, float* err, void* stream);
+
 /* Activation bias correction (iqm.py:180-196) fused into the table-driven Q/DQ - `-sm use ... -bca` - on CONTIGUOUS bf16 / fp16
  * activations x[N][C][HW], on the storage as it lies: no fp32 copy, 6 B/elem (x read twice, y written once), or 4 B/elem in one
  * launch where a channel's whole batch population fits one workgroup's registers.  Counterpart of cnnq_pc_qdq_bcorr_sums +
