@@ -50,7 +50,7 @@ struct MtChan {
 };
 __device__ __forceinline__ MtChan mt_channel(const MtCfg& cfg, float omega, float am, float vmin, float vmax, float mu, float vb) {
     MtChan r;
-    const float mu0 = fmaxf(mu, 0.f);
+    const float mu0 = pmax(mu, 0.f);  // torch.max (iq.py:194, :208) propagates NaN, fmaxf would drop it: a NaN mean stays visible
     float rng;
     if (cfg.clip) rng = cfg.sym ? (2.f * am) * vb : mu0 + am * vb;
     else rng = cfg.sym ? vmax - vmin : vmax;

@@ -547,6 +547,13 @@ int cnnq_pc_bcorr_apply(float* y, int64_t N, int64_t C, int64_t HW, const float*
  *       (`tables` = device fp64 [2][ntab], omega row then alpha row; iq.py:41-51,137-145),
  *       range = 2*alpha*b (sym) or max(mean,0)+alpha*b, Delta = range/omega, clamp bounds around the
  *       quantized mean; clip == 0 (weights): range = max-min (sym) or max.  One workgroup.
+ *       Where the reference raises IndexError the library chooses: omega beyond the last knot
+ *       extrapolates along the last segment; a NaN omega - one NaN / negative std, or every channel constant
+ *       (sum == 0) - gives a NaN multiplier and NaN bounds with Delta = FLT_MAX in EVERY channel; below the first
+ *       knot the segment wraps to the last entry, as numpy's index -1 does.  clip == 0: rows ALPHA 0, CMIN / CMAX
+ *       -inf / +inf.  Row WSTART: floor of the smallest c_min (each clamped to +-1e9, NaN as -1e9), not below
+ *       -CNNQ_MT_HIST_BINS / 2; -CNNQ_MT_HIST_WINDOW / 2 without clipping.  Refuses ntab < 2, null pointers,
+ *       C <= 0 and C >= 2^31 with CNNQ_EINVAL and writes nothing.
  *   cnnq_pc_midtread_qdq     y = clamp(round(x/Delta[c]), c_min[c], c_max[c]) * Delta[c] in one pass;
  *       `codes` (optional) fp32 codes; `hist` (optional, zeroed by the caller,
  *       CNNQ_MT_HIST_WORDS(C) uint64 words) the code histogram.  A NaN code (a NaN in x) is counted in
