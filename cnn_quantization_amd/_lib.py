@@ -134,6 +134,7 @@ SIGNATURES = {
     'cnnq_xrank_free': (_I, [_P]),
     'cnnq_kld_hist': (_I, [_P, _L, _L, _P, _P, _P]),
     'cnnq_kld_search': (_I, [_P, _L, _P, _P, _P, _P]),
+    'cnnq_kld_hist_dt': (_I, [_P, _I, _L, _L, _P, _P, _P]),
     'cnnq_pc_route_dt': (_I, [_L, _L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
     'cnnq_pc_nhwc_workspace': (ctypes.c_size_t, [_L, _L, _I]),
     'cnnq_pc_route_nhwc': (_I, [_L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),

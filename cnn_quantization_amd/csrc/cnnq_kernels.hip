@@ -55,6 +55,7 @@
 #include "cnnq_half_aciq.hip.h"
 #include "cnnq_half_midtread.hip.h"
 #include "cnnq_half_entropy.hip.h"
+#include "cnnq_half_kld.hip.h"
 #include "cnnq_nhwc.hip.h"
 #include "cnnq_nhwc_aciq.hip.h"
 #include "cnnq_nhwc_collect.hip.h"
@@ -1531,6 +1532,24 @@ int cnnq_kld_hist(const float* x, int64_t rows, int64_t len, const float* rowmm,
         hipLaunchKernelGGL((k_kld_hist<4>), grid, block, 0, st, x, len, rowmm, (int)rows, hist);
     else
         hipLaunchKernelGGL((k_kld_hist<1>), grid, block, 0, st, x, len, rowmm, (int)rows, hist);
+    return launch_status();
+}
+
+// bf16 / fp16 rows where they lie (cnnq_half_kld.hip.h): cnnq_kld_hist's checks, zeroing and grid
+int cnnq_kld_hist_dt(const void* x, int dtype, int64_t rows, int64_t len, const float* rowmm, uint32_t* hist, void* stream) {
+    if (!dtype_ok(dtype)) return CNNQ_EINVAL;
+    if (dtype == CNNQ_DTYPE_F32) return cnnq_kld_hist(static_cast<const float*>(x), rows, len, rowmm, hist, stream);
+    if (!x || !rowmm || !hist || rows <= 0 || len <= 0) return CNNQ_EINVAL;
+    if (rows > 65535 || len >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    if (misaligned(x, 2)) return CNNQ_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(hist, 0, (size_t)rows * KB * sizeof(uint32_t), st) != hipSuccess) return launch_status();
+    const dim3 grid((unsigned)((len + KCHUNK - 1) / KCHUNK), (unsigned)rows), block(TPB);
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+    if (dtype == CNNQ_DTYPE_BF16)
+        hipLaunchKernelGGL((k_h_kld_hist<HBf16>), grid, block, 0, st, xh, len, rowmm, (int)rows, hist);
+    else
+        hipLaunchKernelGGL((k_h_kld_hist<HF16>), grid, block, 0, st, xh, len, rowmm, (int)rows, hist);
     return launch_status();
 }
 

@@ -55,6 +55,28 @@ __device__ __forceinline__ double kld_edge(const KldRange& r, int k) {
     return k == KB ? r.last : (double)k * r.step + r.first;
 }
 
+// one element into replica `rep` of the workgroup's table: the count both histogram kernels (k_kld_hist here, k_h_kld_hist in
+// cnnq_half_kld.hip.h) make
+__device__ __forceinline__ void kld_count(const KldRange& r, float v, unsigned* sh, int rep) {
+    const double a = (double)v;
+    if (!(a >= r.first && a <= r.last)) return;   // NaN (numpy keeps only first <= a <= last)
+    int idx = (int)((a - r.first) * r.scale);
+    idx = min(max(idx, 0), KB - 1);
+    if (a < kld_edge(r, idx)) --idx;
+    if (idx != KB - 1 && a >= kld_edge(r, idx + 1)) ++idx;
+    idx = min(max(idx, 0), KB - 1);
+    atomicAdd(&sh[idx * KREP + rep], 1u);
+}
+// a row's table of a finished workgroup into hist: the replicas summed, non-zero counts only
+__device__ __forceinline__ void kld_flush(const unsigned* sh, unsigned* __restrict__ hr) {
+    for (int b = threadIdx.x; b < KB; b += TPB) {
+        unsigned c = 0;
+#pragma unroll
+        for (int q = 0; q < KREP; ++q) c += sh[b * KREP + q];
+        if (c) atomicAdd(&hr[b], c);
+    }
+}
+
 template <int VEC>
 __global__ void __launch_bounds__(TPB) k_kld_hist(const float* __restrict__ x, int64_t len,
                                                   const float* __restrict__ rowmm, int rows,
@@ -69,16 +91,7 @@ __global__ void __launch_bounds__(TPB) k_kld_hist(const float* __restrict__ x, i
     const int64_t end = min(beg + (int64_t)KCHUNK, len);
     const float* __restrict__ xr = x + (int64_t)row * len;
     const int rep = tid & (KREP - 1);
-    auto put = [&](float v) {
-        const double a = (double)v;
-        if (!(a >= r.first && a <= r.last)) return;   // NaN (numpy keeps only first <= a <= last)
-        int idx = (int)((a - r.first) * r.scale);
-        idx = min(max(idx, 0), KB - 1);
-        if (a < kld_edge(r, idx)) --idx;
-        if (idx != KB - 1 && a >= kld_edge(r, idx + 1)) ++idx;
-        idx = min(max(idx, 0), KB - 1);
-        atomicAdd(&sh[idx * KREP + rep], 1u);
-    };
+    auto put = [&](float v) { kld_count(r, v, sh, rep); };
     if constexpr (VEC == 4) {
         for (int64_t i = beg + (int64_t)tid * 4; i < end; i += TPB * 4) {
             if (i + 4 <= end) {
@@ -94,13 +107,7 @@ __global__ void __launch_bounds__(TPB) k_kld_hist(const float* __restrict__ x, i
         for (int64_t i = beg + tid; i < end; i += TPB) put(xr[i]);
     }
     __syncthreads();
-    unsigned* __restrict__ hr = hist + (size_t)row * KB;
-    for (int b = tid; b < KB; b += TPB) {
-        unsigned c = 0;
-#pragma unroll
-        for (int q = 0; q < KREP; ++q) c += sh[b * KREP + q];
-        if (c) atomicAdd(&hr[b], c);
-    }
+    kld_flush(sh, hist + (size_t)row * KB);
 }
 
 __global__ void __launch_bounds__(TPB) k_kld_search(const unsigned* __restrict__ hist, double* __restrict__ div) {

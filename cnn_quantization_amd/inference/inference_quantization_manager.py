@@ -356,7 +356,7 @@ class QuantizationManagerInference(metaclass=Singleton):
                                                                 group=group, native_err=True, native_err_half=True)
             else:
                 self.stats_manager = StatisticManager(sf, load_stats=False, batch_avg=args.stats_batch_avg,
-                                                      kld_threshold=args.kld_threshold)
+                                                      kld_threshold=args.kld_threshold, native_kld=True)
         elif args.stats_mode == 'use':
             self.stats_mode = StatsMode.use_stats
             if args.per_channel_quant_act:

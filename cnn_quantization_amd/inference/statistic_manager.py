@@ -7,7 +7,8 @@ The scalar statistics of a batch are one pass of the device kernels over the ten
 single channel; a bf16 / fp16 tensor and a dense channels_last one are read where they lie, in their
 own dtype (collect_route answers 'flat': ops.tensor_stats).  `kld_threshold=True` adds the `kld_th` column (statistic_manager.py:80-82: the
 maximum over the batch's samples of the KLD-optimal clipping threshold) from the device
-histogram + search kernels (ops.kld_thresholds).  The error columns (mse_*/cos_*,
+histogram + search kernels (ops.kld_thresholds; with `native_kld=True` a bf16 / fp16 tensor that collect_route takes stays where it
+lies there too: ops.kld_thresholds_half, the same bits).  The error columns (mse_*/cos_*,
 statistic_manager.py:22-30) exist in the reference's files but no caller ever passes the quantized
 tensors they need (`tensors_q`), so they always hold NaN there; `collect_err=True` reproduces
 those columns, a non-empty `tensors_q` is rejected.  What this manager and the per-channel one share is defined here, once."""
@@ -32,10 +33,12 @@ def base_dir():
 def collect_route(manager, tensor, force_global_min_max=False):
     """How save_tensor_stats takes this tensor: 'flat' - on its storage as it lies (ops.tensor_stats: no
     layout copy, no upcast): a CUDA tensor of fp32 / bf16 / fp16 that is contiguous and not float32, or dense channels_last with
-    the channels_last switch on; one process and no forced exchange; and not a half tensor when the KLD threshold is collected
-    (its histogram has no half kernel) - or None: a contiguous float32 tensor and every sharded run take the code they took.
+    the channels_last switch on; one process and no forced exchange; and not a half tensor when the KLD threshold is collected,
+    unless the manager opted in with `native_kld` (ops.kld_thresholds_half: DESIGN.md section 32) and the route word
+    ops._kld_half_native, asked last, keeps the class native - or None: a contiguous float32 tensor and every sharded run take the
+    code they took.
     Shape, strides, dtype and attributes only: nothing touches the device.  No class of tensor measured slower native than
-    through the copy (profiles/tensor_collect.md), so no route function is asked."""
+    through the copy (profiles/tensor_collect.md), so no route function is asked but the KLD one (profiles/half_kld.md)."""
     if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.dtype in ops._ACT_DTYPES and tensor.numel() > 0):
         return None
     half = tensor.dtype != torch.float32
@@ -44,7 +47,12 @@ def collect_route(manager, tensor, force_global_min_max=False):
         return None
     if D.world_size(manager.group) != 1 or D.forced_exchange():
         return None
-    return None if manager.kld_threshold and half else 'flat'
+    if manager.kld_threshold and half:
+        if not getattr(manager, 'native_kld', False):
+            return None
+        rows = tensor.shape[0] if tensor.dim() > 1 else 1       # save_tensor_stats' rows
+        return 'flat' if ops._kld_half_native(rows, tensor.numel() // rows, tensor.dtype) else None
+    return 'flat'
 
 
 def collects_native_flat(manager, tensor):
@@ -96,7 +104,7 @@ class StatisticManager(Collector, metaclass=Singleton):
     collect_route = collect_route       # the face inference_quantization_manager._route asks
 
     def __init__(self, folder, load_stats, stats=('max', 'min', 'std', 'mean', 'kurtosis', 'mean_abs', 'b', 'dim'),
-                 batch_avg=False, kld_threshold=False, collect_err=False, group=None):
+                 batch_avg=False, kld_threshold=False, collect_err=False, group=None, native_kld=False):
         self.name = folder
         self.group = group          # process group of a batch-sharded run (None: the default group, if any)
         self.folder = os.path.join(base_dir(), 'statistics', folder)
@@ -105,6 +113,7 @@ class StatisticManager(Collector, metaclass=Singleton):
         if collect_err:
             self.stats_names += ['mse_lowp', 'mse_gaus', 'mse_laplace', 'cos_lowp', 'cos_gaus', 'cos_laplace']
         self.kld_threshold = kld_threshold
+        self.native_kld = native_kld    # opt-in: the histogram of a bf16 / fp16 tensor on its storage (collect_route)
         if kld_threshold:
             self.stats_names.append('kld_th')
         self.batch_avg = batch_avg
@@ -152,7 +161,9 @@ class StatisticManager(Collector, metaclass=Singleton):
             if s.startswith('mse_') or s.startswith('cos_'):
                 vals[s] = np.nan
         if self.kld_threshold:
-            th = ops.kld_thresholds(x, x.shape[0] if x.dim() > 1 else 1)[:, 0].max().view(1, 1)
+            # a half tensor arrives here natively only through native_kld (collect_route); its threshold is the upcast copy's
+            kld = ops.kld_thresholds_half if native and x.dtype != torch.float32 else ops.kld_thresholds
+            th = kld(x, x.shape[0] if x.dim() > 1 else 1)[:, 0].max().view(1, 1)
             if world > 1:           # the maximum over the samples of every rank
                 th = D.all_gather_records(th, self.group).max().view(1, 1)
             vals['kld_th'] = float(th.item())

@@ -2565,6 +2565,68 @@ def kld_thresholds(x, rows=None, want_parts=False):
     return out
 
 
+_KLD_HALF_NATIVE = {}
+
+
+def _kld_half_native(rows, length, dtype):
+    """Whether this class of tensor - rows samples of `length` elements - collects its KLD threshold on the bf16 / fp16 histogram
+    (kld_thresholds_half) or stays on the upcast route: the last question of the per-tensor manager's collect_route.  Host only,
+    a function of the shape and the dtype, cached; the tests patch the function and empty the cache by name.
+    The yardstick is tools/bench_half_kld.py (MI355X, ResNet-50 conv outputs at batch 512, the routes alternating step by step,
+    us per call, mean (min-max) of ten steps; profiles/half_kld.md has every figure): the search takes 4.86 ms at 512 rows whatever
+    the rows hold, and the two smallest classes did not win beyond its spread in any of the four runs - [512,256,14,14] bf16
+    4912.6 (4896.2-4928.0) against 4940.5 (4917.3-4954.9), [512,512,7,7] 4900.6 (4882.6-4929.6) against 4913.9 (4900.7-4928.1) -
+    while [512,128,28,28], [512,512,14,14] and [512,2048,7,7] (2^25.6 elements) and everything larger did.  So 512 rows or more
+    of fewer than 2^25 elements in all stay on the upcast route; fewer rows were not measured and stay native."""
+    key = (rows, length, dtype)
+    v = _KLD_HALF_NATIVE.get(key)
+    if v is None:
+        v = _KLD_HALF_NATIVE[key] = not (rows >= 512 and rows * length < (1 << 25))
+    return v
+
+
+def kld_thresholds_half(x, rows=None, want_parts=False):
+    """kld_thresholds of a bf16 / fp16 tensor on the storage as it lies (-sm collect -kld): x viewed as
+    [rows, numel/rows] (rows None: its samples) -> kld_thresholds' result, float64 [rows, 3], with want_parts (out, hist, div) -
+    bit for bit what kld_thresholds gives on x.float(): the upconversion is exact, so the histogram is that copy's, count for
+    count, and the search sees nothing else.  tensor_row_stats (cnnq_pc_minmax_local_dt), cnnq_kld_hist_dt, cnnq_kld_search:
+    two reads of x at 2 B/elem.  Taken: a non-empty tensor on the current device that is contiguous, or 4-D dense channels_last
+    with rows in (1, N) - a sample is one contiguous block, and a histogram does not depend on the order of its elements.
+    Anything else - a CPU tensor, float32 (kld_thresholds takes it), an empty or non-dense tensor, channels_last with other rows
+    or with CNNQ_NHWC=0, rows that do not divide the elements - raises: nothing is copied or upcast here."""
+    what = 'kld_thresholds_half'
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise L.CnnqError('%s: x must be a CUDA/HIP tensor (there is no CPU path)' % what)
+    if x.dtype not in _HALF_DTYPES:
+        raise L.CnnqError('%s: x must be bfloat16 or float16, got %s (float32 takes kld_thresholds)' % (what, x.dtype))
+    if rows is None:
+        rows = x.shape[0] if x.dim() > 1 else 1
+    rows = int(rows)
+    layout = _layout(x)
+    if layout == 'copy' or x.numel() == 0:
+        raise L.CnnqError('%s: x must be a non-empty contiguous or dense channels_last tensor (no copy is made here)' % what)
+    if layout == 'nhwc' and not (_NHWC and rows in (1, x.shape[0])):
+        raise L.CnnqError('%s: a channels_last tensor is read as it lies for rows = 1 or its samples, with the channels_last '
+                          'switch on (no copy is made here); got rows = %d' % (what, rows))
+    if x.device.index != torch.cuda.current_device():
+        raise L.CnnqError('%s: x is on %s but the current device is cuda:%d' % (what, x.device, torch.cuda.current_device()))
+    if rows < 1 or x.numel() % rows:
+        raise L.CnnqError('%s: %d elements do not make %d rows' % (what, x.numel(), rows))
+    if x.requires_grad:
+        x = x.detach()
+    lib = L.load()
+    length = x.numel() // rows
+    rowmm = tensor_row_stats(x, rows)
+    hist = torch.empty((rows, L.KLD_BINS), dtype=torch.int32, device=x.device)
+    div = torch.empty((rows, L.KLD_NCAND), dtype=torch.float64, device=x.device)
+    out = torch.empty((rows, 3), dtype=torch.float64, device=x.device)
+    L.check(lib.cnnq_kld_hist_dt(_ptr(x), _HALF_DTYPES[x.dtype], rows, length, _ptr(rowmm), _ptr(hist), _stream(x)), 'cnnq_kld_hist_dt')
+    L.check(lib.cnnq_kld_search(_ptr(hist), rows, _ptr(rowmm), _ptr(div), _ptr(out), _stream(x)), 'cnnq_kld_search')
+    if want_parts:
+        return out, hist, div
+    return out
+
+
 def row_sumsq_native(x, rows=None):
     """Whether row_sumsq reads x where it lies: a bf16 / fp16 device tensor, or a dense channels_last float32 one (with the
     channels_last switch on) whose rows are its samples (rows None: they are).  Shape, strides and dtype only."""

@@ -640,6 +640,14 @@ int cnnq_kld_search(const uint32_t* hist, int64_t rows, const float* rowmm, doub
  * touches the device; CNNQ_ENOTSUP: nothing was enqueued. */
 enum { CNNQ_DTYPE_F32 = 0, CNNQ_DTYPE_BF16 = 1, CNNQ_DTYPE_F16 = 2, CNNQ_NDTYPE = 3 };
 
+/* cnnq_kld_hist on rows of another element type (`-kld` with `-sm collect --dtype bfloat16 / float16`; kld_threshold.py:19-23
+ * on the activation as the model produced it): x is [rows][len] of `dtype`, rows back to back, 2-byte aligned; the arguments,
+ * the zeroing of hist and the status codes are cnnq_kld_hist's (CNNQ_EINVAL: a NULL pointer, rows <= 0, len <= 0; CNNQ_ERANGE:
+ * rows > 65535, len >= 2^31), plus CNNQ_EINVAL for a dtype outside the enum.  BF16 / F16: hist is, count for count,
+ * cnnq_kld_hist's on the exactly upconverted rows, so cnnq_kld_search behind it gives that route's bits; the rows are read once,
+ * 2 B/elem, in 16-byte loads whatever their alignment (single elements up to the first boundary and behind the last). */
+int cnnq_kld_hist_dt(const void* x, int dtype, int64_t rows, int64_t len, const float* rowmm, uint32_t* hist, void* stream);
+
 /* Config 2 behind one call (iq.py:409-451,557-603; counterpart of cnnq_pc_minmax_qdq_auto, same `ws` of
  * cnnq_pc_minmax_qdq_workspace(N, C, HW) bytes; qp[CNNQ_NQP][C] and mm[2][C] are written).  BF16 / F16, two routes:
  *   - allow_single_launch != 0 and a channel's N*HW elements fit one workgroup's registers (131072) and the rows
