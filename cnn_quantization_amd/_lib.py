@@ -155,6 +155,11 @@ SIGNATURES = {
     'cnnq_pc_qerr_dt_workspace': (ctypes.c_size_t, [_L, _L, _L, _I, _I]),
     'cnnq_pc_route_qerr_dt': (_I, [_L, _L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
     'cnnq_pc_qerr_dt': (_I, [_P, _I, _L, _L, _L, _P, _I, _P, _P, _P, _P]),
+    'cnnq_pc_route_sample_extrema_dt': (_I, [_L, _L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_pc_sample_extrema_dt': (_I, [_P, _I, _L, _L, _L, _P, _P]),
+    'cnnq_pc_sample_extrema_nhwc_workspace': (ctypes.c_size_t, [_L, _L, _L, _I]),
+    'cnnq_pc_route_sample_extrema_nhwc': (_I, [_L, _L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_pc_sample_extrema_nhwc': (_I, [_P, _I, _L, _L, _L, _P, _P, _P]),
     'cnnq_pc_qdq_bcorr_dt_workspace': (ctypes.c_size_t, [_L, _L, _L, _I]),
     'cnnq_pc_route_qdq_bcorr_dt': (_I, [_L, _L, _L, _I, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
     'cnnq_pc_qdq_bcorr_dt': (_I, [_P, _P, _I, _L, _L, _L, _P, _I, _P, _P, _P, _I, _P]),

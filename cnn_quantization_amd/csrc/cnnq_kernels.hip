@@ -66,6 +66,7 @@
 #include "cnnq_qerr.hip.h"
 #include "cnnq_nhwc_qerr.hip.h"
 #include "cnnq_half_qerr.hip.h"
+#include "cnnq_sample_extrema.hip.h"
 #include "cnnq_rows.hip.h"
 #include "cnnq_flat.hip.h"
 
@@ -2466,6 +2467,98 @@ int cnnq_pc_qerr_nhwc(const void* x, int dtype, int64_t N, int64_t HW, int64_t C
         hipLaunchKernelGGL((k_qerr_fold<decltype(k)::value>), dim3((unsigned)((C + QF_CH - 1) / QF_CH)), dim3(TPB), 0, st, rec, (int)N, g.S, (int)C,
                            (int)HW, err);
     });
+    return launch_status();
+}
+
+// ---- `-sm collect -sba`: the per-sample channel extrema (cnnq_sample_extrema.hip.h) -------------------------------------------------
+// the argument checks of the contiguous bf16 / fp16 form: 0 - the plan exists (the fp32 entry points' geometry limits, N and
+// C * HW below 2^31, and N * C rows below 2^31, which bounds the grid too).  fp32 has no kernel here: CNNQ_ENOTSUP.
+static int h_se_check(int64_t N, int64_t C, int64_t HW, int dtype, bool ok) {
+    if (!dtype_ok(dtype) || N < 1 || C < 1 || HW < 1 || !ok) return CNNQ_EINVAL;
+    if (dtype == CNNQ_DTYPE_F32) return CNNQ_ENOTSUP;
+    const int G0 = cnnq_pc_groups(N, C, HW, 0);
+    if (G0 <= 0) return g_error(G0);
+    return N * C >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
+}
+
+// Which launch cnnq_pc_sample_extrema_dt makes for this geometry (host only; smpc.py:72-78): out = {lanes per row seg, rows per
+// workgroup (whole steps of TPB / seg rows), workgroups, 1 - the native launch / 0 - a class of layer that did not win against the
+// former route and stays there: h_sample_extrema_native}.  The plan does not depend on the alignment: the kernel finds every
+// row's 16-byte boundary itself.
+int cnnq_pc_route_sample_extrema_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int32_t out[4]) {
+    if (const int rc = h_se_check(N, C, HW, dtype, out && pow2(align_bytes))) return rc;
+    const int64_t rows = N * C;
+    const int seg = h_se_seg(HW), rpw = h_se_steps(rows, HW, seg) * (TPB / seg);
+    out[0] = seg;
+    out[1] = rpw;
+    out[2] = (int32_t)((rows + rpw - 1) / rpw);
+    out[3] = h_sample_extrema_native(N, C, HW, dtype);
+    return 0;
+}
+
+// smpc.py:72-78 (the per-sample extrema behind the batch mean) on x[N][C][HW] of bf16 / fp16: k_h_sample_extrema, one launch
+int cnnq_pc_sample_extrema_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, float* ext, void* stream) {
+    if (const int rc = h_se_check(N, C, HW, dtype, x && ext && !misaligned(x, 2) && !misaligned(ext, 4))) return rc;
+    const int64_t rows = N * C;
+    const int seg = h_se_seg(HW), steps = h_se_steps(rows, HW, seg);
+    const int64_t rpw = (int64_t)steps * (TPB / seg);
+    const dim3 grid((unsigned)((rows + rpw - 1) / rpw));
+    const uint16_t* xh = static_cast<const uint16_t*>(x);
+    if (dtype == CNNQ_DTYPE_BF16) hipLaunchKernelGGL(k_h_sample_extrema<HBf16>, grid, dim3(TPB), 0, hs(stream), xh, rows, (int)HW, seg, steps, ext);
+    else hipLaunchKernelGGL(k_h_sample_extrema<HF16>, grid, dim3(TPB), 0, hs(stream), xh, rows, (int)HW, seg, steps, ext);
+    return launch_status();
+}
+
+// the argument checks of the channels_last form: 0 - the plan exists (N, HW, N * C and the grid N * S * nb stay in 32 bits)
+static int cl_se_check(int64_t N, int64_t HW, int64_t C, int dtype) {
+    if (!dtype_ok(dtype) || N < 1 || HW < 1 || C < 1 || C > CL_C_MAX) return CNNQ_EINVAL;
+    if (N >= ((int64_t)1 << 31) || HW >= ((int64_t)1 << 31) || N * C >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    const int64_t nbmax = (C + TPB - 1) / TPB;      // column blocks of the narrowest piece
+    return N * cl_se_slabs(N, HW, C, cl_esize(dtype)) * nbmax >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
+}
+
+// ws of cnnq_pc_sample_extrema_nhwc, floats: the partial pairs [N * S][2][C] - N * S * 2 * C * 4 bytes; 0 at S == 1 (no workspace:
+// the one launch stores ext) and on arguments the call refuses
+size_t cnnq_pc_sample_extrema_nhwc_workspace(int64_t N, int64_t HW, int64_t C, int dtype) {
+    if (cl_se_check(N, HW, C, dtype)) return 0;
+    const int S = cl_se_slabs(N, HW, C, cl_esize(dtype));
+    return S == 1 ? 0 : (size_t)N * (size_t)S * 2 * (size_t)C * sizeof(float);
+}
+
+// Which launches cnnq_pc_sample_extrema_nhwc makes for this geometry (host only; smpc.py:72-78): out = {elements per load W, slabs
+// per sample S (1: one launch, no workspace), column blocks nb - the grid is N * S * nb, 1 - the native launches / 0 - a class of
+// layer that did not win against the former route and stays there: cl_sample_extrema_native}
+int cnnq_pc_route_sample_extrema_nhwc(int64_t N, int64_t HW, int64_t C, int dtype, int align_bytes, int32_t out[4]) {
+    if (!out || !pow2(align_bytes)) return CNNQ_EINVAL;
+    if (const int rc = cl_se_check(N, HW, C, dtype)) return rc;
+    const int es = cl_esize(dtype), w = cl_piece(C, es, align_bytes);
+    const ClGeo g = cl_geo_se(N, HW, C, w, es);
+    out[0] = w;
+    out[1] = g.S;
+    out[2] = g.nb;
+    out[3] = cl_sample_extrema_native(N, HW, C, dtype);
+    return 0;
+}
+
+// smpc.py:72-78 on [N][HW][C]: k_cl_sample_extrema (-> k_sample_extrema_fold on its partial pairs, S > 1)
+int cnnq_pc_sample_extrema_nhwc(const void* x, int dtype, int64_t N, int64_t HW, int64_t C, void* ws, float* ext, void* stream) {
+    if (!x || !ext || misaligned(ext, 4) || misaligned(ws, 4)) return CNNQ_EINVAL;
+    if (const int rc = cl_se_check(N, HW, C, dtype)) return rc;
+    const int es = cl_esize(dtype);
+    if (misaligned(x, (uintptr_t)es)) return CNNQ_EINVAL;
+    const int w = cl_piece(C, es, h_align(x, x));
+    const ClGeo g = cl_geo_se(N, HW, C, w, es);
+    if (g.S > 1 && !ws) return CNNQ_EINVAL;
+    hipStream_t st = hs(stream);
+    float* part = static_cast<float*>(ws);
+    const dim3 grid((unsigned)(N * g.S * g.nb));
+    const int rc = cl_launch(dtype, w, x, [&](auto pc, auto* xr) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_cl_sample_extrema<typename P::T, P::W>), grid, dim3(TPB), 0, st, xr, g, (int)N, part, ext);
+    });
+    if (rc || g.S == 1) return rc;
+    const int64_t NC = N * C;
+    hipLaunchKernelGGL(k_sample_extrema_fold, dim3((unsigned)((NC + TPB - 1) / TPB)), dim3(TPB), 0, st, part, NC, (int)C, g.S, ext);
     return launch_status();
 }
 

@@ -353,7 +353,7 @@ class QuantizationManagerInference(metaclass=Singleton):
             if args.per_channel_quant_act:
                 self.stats_manager = StatisticManagerPerChannel(sf, load_stats=False, batch_avg=args.stats_batch_avg,
                                                                 collect_err=bool(getattr(args, 'collect_err', False)),
-                                                                group=group, native_err=True, native_err_half=True)
+                                                                group=group, native_err=True, native_err_half=True, native_batch_avg=True)
             else:
                 self.stats_manager = StatisticManager(sf, load_stats=False, batch_avg=args.stats_batch_avg,
                                                       kld_threshold=args.kld_threshold, native_kld=True)

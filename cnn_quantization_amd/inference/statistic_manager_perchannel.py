@@ -17,6 +17,9 @@ With collect_err the answer is None unless the manager opted in (native_err, whi
 activation answers 'nhwc' and its error columns come from the same storage too (ops.pc_quant_errors_nhwc, DESIGN.md section 30);
 with native_err_half on top (the inference manager sets both) a contiguous bf16 / fp16 activation answers 'half' and its error
 columns are measured in its own dtype (ops.pc_quant_errors_half).
+With batch_avg (-sba: a channel's max / min is the mean over the batch of the per-sample extrema, smpc.py:72-78) the answer is None
+unless the manager opted in (native_batch_avg, which the inference manager sets) and collect_err is off: then both routes take the
+(n, c) extrema from one more read of the same storage (ops.pc_sample_extrema_nhwc / ops.pc_sample_extrema_half).
 
 `collect_err=True` adds the six clipping-error columns the reference declares (smpc.py:24-32: mse_lowp, mse_gaus,
 mse_laplace, cos_lowp, cos_gaus, cos_laplace; formulas smpc.py:80-100) - the columns `-sm use -c mix` (iq.py:310-323)
@@ -53,11 +56,14 @@ def collect_route(manager, tensor, force_global_min_max=False):
     """How save_tensor_stats takes this tensor: 'nhwc' - on its channels_last storage (ops.pc_stats_nhwc),
     'half' - contiguous, in its own dtype (ops.pc_stats_half) - or None: ops.pc_stats on a contiguous float32 copy.  Each fact
     once, in this order: the manager - no error columns (with native_err: 'nhwc' measures them too, 'half' with native_err_half as well), the extrema
-    of the whole batch (batch_avg off, or the caller forces them); the storage class - 'nhwc': dense channels_last and not contiguous, a dtype the kernels have, the channels_last switch
+    of the whole batch (batch_avg off, or the caller forces them - or, with native_batch_avg, ops._SBA_NATIVE on and no error columns, the
+    per-sample extrema of ops.pc_sample_extrema_*, whose route word is asked after the others); the storage class - 'nhwc': dense channels_last and not contiguous, a dtype the kernels have, the channels_last switch
     on; 'half': a contiguous non-empty 4-D bf16 / fp16 CUDA activation with a spatial extent; the group - one process, no forced
     exchange; last the class's route function.  Shape, strides and attributes only: nothing touches the device."""
     err = manager.collect_err
-    if (err and not getattr(manager, 'native_err', False)) or (manager.batch_avg and not force_global_min_max) \
+    sba = manager.batch_avg and not force_global_min_max
+    if (err and not getattr(manager, 'native_err', False)) \
+            or (sba and (err or not getattr(manager, 'native_batch_avg', False) or not ops._SBA_NATIVE)) \
             or not isinstance(tensor, torch.Tensor):
         return None
     if tensor.dtype in ops._ACT_DTYPES and ops._NHWC and ops._layout(tensor) == 'nhwc':
@@ -76,10 +82,14 @@ def collect_route(manager, tensor, force_global_min_max=False):
         native = ops._stats_nhwc_native(tensor.numel() // C, C, tensor.dtype)
         if native and err:
             native = ops._qerr_nhwc_native(N, tensor.numel() // (N * C), C, tensor.dtype)
+        if native and sba:
+            native = ops._sample_extrema_nhwc_native(N, tensor.numel() // (N * C), C, tensor.dtype)
     else:
         native = ops._stats_half_native(*ops.geometry(tensor), tensor.dtype)
         if native and err:
             native = ops._qerr_half_native(*ops.geometry(tensor), tensor.dtype)
+        if native and sba:
+            native = ops._sample_extrema_half_native(*ops.geometry(tensor), tensor.dtype)
     return route if native else None
 
 
@@ -98,7 +108,7 @@ class StatisticManagerPerChannel(Collector, metaclass=Singleton):
 
     def __init__(self, folder, load_stats, stats=('max', 'min', 'std', 'mean', 'kurtosis', 'b', 'std_pos'),
                  batch_avg=False, collect_err=False, group=None, err_settings=None, native_err=False,
-                 native_err_half=False):
+                 native_err_half=False, native_batch_avg=False):
         self.name = folder
         self.folder = os.path.join(base_dir(), 'statistics/per_channel', folder)
         self.stats_names = list(stats)
@@ -111,6 +121,8 @@ class StatisticManagerPerChannel(Collector, metaclass=Singleton):
         self.native_err = native_err
         # the route 'half' with collect_err: opt-in per object on top of native_err
         self.native_err_half = native_err_half
+        # batch_avg on the routes 'nhwc' and 'half' (DESIGN.md section 33): opt-in per object; the inference manager opts in
+        self.native_batch_avg = native_batch_avg
         # what the three candidates need besides the table: a dict {num_bits, positive, bit_alloc, prior_is_b, target,
         # round_mode} (the arguments of ops.mix_candidates) or a callable (tag, half_range) -> such a dict
         self.err_settings = err_settings
@@ -139,6 +151,13 @@ class StatisticManagerPerChannel(Collector, metaclass=Singleton):
         if route:
             # the table from the channels_last storage as it lies, or from the tensor in its own dtype (23)
             table, _ = (ops.pc_stats_nhwc if route == 'nhwc' else ops.pc_stats_half)(tensor.detach(), **need)
+            if self.batch_avg and not force_global_min_max:
+                # mean over the batch of the per-sample extrema (smpc.py:72,78), the (n, c) extrema from one more read of the storage
+                # (DESIGN.md section 33); the fp64 sums and the division are the expressions of the fp32 branch below: the same bits
+                rows = (ops.pc_sample_extrema_nhwc if route == 'nhwc' else ops.pc_sample_extrema_half)(tensor.detach())
+                smax, smin, cnt = batch_extrema_sums(rows, tensor.shape[0], self.group)
+                table[L.STAT_MAX] = (smax / cnt).float()
+                table[L.STAT_MIN] = (smin / cnt).float()
             if self.collect_err:
                 # the same three candidates as below, measured on the channels_last storage or on the
                 # contiguous tensor in its own dtype (31); the table's min / max rows are x's exact extrema (no batch_avg on

@@ -96,6 +96,8 @@ def _half_only(what, reason):
 # switches, read ONCE at import (not per hot call); reload_switches() re-reads them after the environment changed (tests, tools)
 def reload_switches():
     global _RESIDENT, _SINGLE_CODES, _DIRECT_RCCL, _PT_FUSED, _XRANK_ON, _ACIQ_SINGLE, _NHWC, _HALF_TABLE, _HALF_ACIQ, _HALF_MIDTREAD, _HALF_ENTROPY
+    global _SBA_NATIVE
+    _SBA_NATIVE = os.environ.get('CNNQ_SBA_NATIVE', '1') != '0'        # 0: -sm collect -sba per channel takes the former route, upcast and copy (A/B)
     _HALF_ENTROPY = os.environ.get('CNNQ_HALF_ENTROPY', '1') != '0'    # 0: -me on contiguous half activations takes the upcast route (A/B)
     _HALF_MIDTREAD = os.environ.get('CNNQ_HALF_MIDTREAD', '1') != '0'  # 0: mid-tread on contiguous half activations takes the upcast route (A/B)
     _HALF_ACIQ = os.environ.get('CNNQ_HALF_ACIQ', '1') != '0'          # 0: dynamic ACIQ on contiguous half activations takes the upcast route (A/B)
@@ -512,6 +514,63 @@ def pc_stats_half(x, need_b=False, need_kurt=False, need_relu=False):
     tensor, float32, not 4-D, not contiguous - raises: nothing is copied or upcast here."""
     x, site = _admit_half(x, 'pc_stats_half', 'pc_stats')
     return _pc_stats_native(site, x, need_b, need_kurt, need_relu)
+
+
+_SAMPLE_EXTREMA_HALF_NATIVE = {}
+_SAMPLE_EXTREMA_NHWC_NATIVE = {}
+
+
+def _sample_extrema_half_native(N, C, HW, dtype):
+    """Whether this class of layer takes its per-sample extrema (-sba) on the contiguous bf16 / fp16 kernel: the "native" word of
+    cnnq_pc_route_sample_extrema_dt's report (0: a class that did not measure faster than the former route is sent back there).
+    The statistics manager (collect_route with native_batch_avg) and the tests patch the function and empty the cache by name."""
+    return _route_word(_SAMPLE_EXTREMA_HALF_NATIVE, (N, C, HW, dtype), bool, 'cnnq_pc_route_sample_extrema_dt', (N, C, HW), dtype)
+
+
+def _sample_extrema_nhwc_native(N, HW, C, dtype):
+    """The same for the channels_last kernel: the "native" word of cnnq_pc_route_sample_extrema_nhwc's report."""
+    return _route_word(_SAMPLE_EXTREMA_NHWC_NATIVE, (N, HW, C, dtype), bool, 'cnnq_pc_route_sample_extrema_nhwc', (N, HW, C), dtype)
+
+
+def pc_sample_extrema_half(x):
+    """The per-sample channel extrema of a contiguous 4-D bf16 / fp16 activation, on the storage as it lies (DESIGN.md section 33;
+    -sm collect -sba, smpc.py:72-78; cnnq_pc_sample_extrema_dt): the float32 device table [2, N * C], sample-major, row STAT_MIN the
+    minima and row STAT_MAX the maxima of x.float() - what tensor_row_stats returns and statistic_manager.batch_extrema_sums
+    reads.  One read of x, 2 B/elem, one launch, no workspace.  Anything else - a CPU tensor, float32, not 4-D, not contiguous -
+    raises: nothing is copied or upcast here."""
+    x, (_, geo, C, dt, st) = _admit_half(x, 'pc_sample_extrema_half', 'tensor_row_stats')
+    ext = torch.empty((2, geo[0] * C), dtype=torch.float32, device=x.device)
+    rc = L.load().cnnq_pc_sample_extrema_dt(x.data_ptr(), dt, *geo, ext.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_sample_extrema_dt')
+    return ext
+
+
+def pc_sample_extrema_nhwc(x):
+    """The per-sample channel extrema of a dense channels_last activation of fp32 / bf16 / fp16, on the storage as it lies
+    (-sm collect -sba, smpc.py:72-78; cnnq_pc_sample_extrema_nhwc): the float32 device table [2, N * C] of
+    pc_sample_extrema_half.  One read of x, 4 B/elem in fp32 and 2 in bf16 / fp16; one launch, or - small batches of large images
+    - two with a cached workspace of partial pairs.  A tensor that is not dense channels_last (or CNNQ_NHWC=0: copied, counted)
+    takes tensor_row_stats on its (n, c) rows, which is float32 only here - a half tensor raises before anything is copied."""
+    x, site = _admit_nhwc(x, 'pc_sample_extrema_nhwc', None, 'the per-sample extrema of a tensor that does not take the channels_last kernels')
+    N, C = x.shape[0], x.shape[1]
+    if site is None:
+        return tensor_row_stats(x, N * C)
+    _, (R, _), _, dt, st = site
+    HW = R // N
+    lib = L.load()
+    key = ('sample_extrema_nhwc', N, HW, C, dt)
+    nbytes = _WS_BYTES.get(key)
+    if nbytes is None:
+        out = (ctypes.c_int32 * 4)()
+        L.check(lib.cnnq_pc_route_sample_extrema_nhwc(N, HW, C, dt, 16, out), 'cnnq_pc_route_sample_extrema_nhwc')   # (0 bytes is a plan too)
+        nbytes = _WS_BYTES[key] = lib.cnnq_pc_sample_extrema_nhwc_workspace(N, HW, C, dt)
+    ws = _scratch(x, 'sample_extrema', nbytes, st).data_ptr() if nbytes else None
+    ext = torch.empty((2, N * C), dtype=torch.float32, device=x.device)
+    rc = lib.cnnq_pc_sample_extrema_nhwc(x.data_ptr(), dt, N, HW, C, ws, ext.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_sample_extrema_nhwc')
+    return ext
 
 
 def _xrank_plan(kind, x, N, C, HW, group, xr=None):

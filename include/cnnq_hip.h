@@ -815,6 +815,47 @@ int cnnq_pc_route_qerr_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align
 int cnnq_pc_qerr_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, int K,
                     const float* mm /* or NULL */, void* ws, float* err, void* stream);
 
+/* `-sm collect -sba` - the per-sample channel extrema behind smpc.py:72-78, where a channel's max / min is the MEAN over the batch
+ * of the samples' own max / min - on activations read where they lie: ONE read of x, no layout copy, no upcast.  Both forms write
+ * ext[2][N * C] fp32, sample-major (n * C + c): row CNNQ_STAT_MIN the minima, row CNNQ_STAT_MAX the maxima.  Promised: ext
+ * equals, as values, the min / max over HW of the exactly upconverted x; an (n, c) row that holds a NaN gives NaN in BOTH entries;
+ * the sign of a zero extremum is not pinned.  No atomics - every entry is stored once by one lane - and extrema do not depend on
+ * the order of the elements: bit-identical run after run.  No host synchronisation, no allocation, graph-capturable.
+ *
+ * CONTIGUOUS bf16 / fp16 x[N][C][HW] (smpc.py:72-78): the N * C rows lie back to back; `seg` lanes (a power of two <= 64, from HW
+ * alone) own one row at a time and a 256-lane workgroup takes 256 / seg rows per step: one launch, no workspace, no LDS.  A row is
+ * read in 16-byte loads from its first 16-byte boundary on and element by element in front of it and behind the last whole load,
+ * so every alignment of x (2 bytes at least) and every HW takes the same route.  CNNQ_DTYPE_F32 is REFUSED with CNNQ_ENOTSUP by
+ * both functions (contiguous fp32 keeps cnnq_pc_minmax + cnnq_pc_minmax_reduce with N = 1, C = the rows, which need a workspace
+ * this call does not take).
+ * cnnq_pc_route_sample_extrema_dt (host only, nothing enqueued): out = {seg, rows per workgroup (whole steps of 256 / seg rows),
+ * workgroups, 1 - the native launch / 0 - a class of layer that did not measure faster than the former route (upcast +
+ * cnnq_pc_stats on the (n, c) rows) beyond the run's spread and is left there by callers that have the choice: HW no multiple of
+ * 8 with N * HW >= 16384 and N * C * HW < 2^25 (cnnq_pc_sample_extrema_dt itself runs every class)}; align_bytes: a power of two,
+ * on which the plan does not depend.
+ * A bad dtype, N / C / HW < 1, a NULL x / ext, an x not aligned to 2 bytes or an ext not aligned to 4 returns CNNQ_EINVAL, a
+ * geometry beyond cnnq_pc_groups' limits (N or C * HW of 2^31) or N * C of 2^31 CNNQ_ERANGE, before anything touches the device. */
+int cnnq_pc_route_sample_extrema_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int32_t out[4]);
+int cnnq_pc_sample_extrema_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, float* ext, void* stream);
+/* Dense CHANNELS_LAST fp32 / bf16 / fp16, storage x[N][HW][C] (smpc.py:72-78): cnnq_pc_qerr_nhwc's tiling - a sample's HW rows are
+ * cut into S slabs, the grid is N * S * nb workgroups, a lane keeps one piece of W consecutive channels (the widest of 16 / 8 / 4 /
+ * 2 / 1 bytes that divides C and x's alignment) and the lanes of a workgroup meet once through LDS.  S == 1: one launch stores
+ * ext, ws is not touched and may be NULL.  S > 1 (small batches of large images): the partial pairs go to ws[N * S][2][C] and a
+ * second launch, one thread per (n, c), writes ext.
+ * cnnq_pc_sample_extrema_nhwc_workspace (smpc.py:72-78): bytes of `ws` = N * S * 2 * C * 4 with S of the route's report, which
+ * does not depend on the alignment; 0 at S == 1 and on arguments the call refuses.
+ * cnnq_pc_route_sample_extrema_nhwc (host only, nothing enqueued; smpc.py:72-78): out = {elements per load W, slabs per sample S,
+ * column blocks nb, 1 - the native launches / 0 - a class of layer that did not measure faster than the former route (upcast,
+ * layout copy, cnnq_pc_stats on the (n, c) rows) beyond the run's spread and is left there by callers that have the choice; none
+ * so far}; align_bytes: the power of two that divides x (<= 16 is what matters).
+ * A bad dtype, N / HW / C < 1, C > 2^26, a NULL x / ext, a NULL ws at S > 1, a misaligned ws / ext or an x not aligned to its
+ * element size returns CNNQ_EINVAL; N, HW or N * C of 2^31 or a grid of 2^31 workgroups CNNQ_ERANGE, before anything touches the
+ * device. */
+size_t cnnq_pc_sample_extrema_nhwc_workspace(int64_t N, int64_t HW, int64_t C, int dtype);
+int cnnq_pc_route_sample_extrema_nhwc(int64_t N, int64_t HW, int64_t C, int dtype, int align_bytes, int32_t out[4]);
+int cnnq_pc_sample_extrema_nhwc(const void* x, int dtype, int64_t N, int64_t HW, int64_t C, void* ws /* or NULL at S == 1 */,
+                                float* ext, void* stream);
+
 /* Activation bias correction (iqm.py:180-196) fused into the table-driven Q/DQ - `-sm use ... -bca` - on CONTIGUOUS bf16 / fp16
  * activations x[N][C][HW], on the storage as it lies: no fp32 copy, 6 B/elem (x read twice, y written once), or 4 B/elem in one
  * launch where a channel's whole batch population fits one workgroup's registers.  Counterpart of cnnq_pc_qdq_bcorr_sums +
