@@ -202,6 +202,11 @@ SIGNATURES = {
     'cnnq_pc_qdq_dt': (_I, [_P, _P, _I, _L, _L, _L, _P, _P, _P, _I, _P]),
     'cnnq_pc_minmax_local_dt': (_I, [_P, _I, _L, _L, _L, _P, _P, _P]),
     'cnnq_pt_qdq_dt': (_I, [_P, _P, _I, _L, _P, _P, _P]),
+    'cnnq_pc_route_packed_dt': (_I, [_L, _L, _L, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_pc_quantize_packed_dt': (_I, [_P, _I, _L, _L, _L, _P, _P, _P, _P, _P]),
+    'cnnq_pc_dequantize_packed_dt': (_I, [_P, _P, _I, _L, _L, _L, _P, _P, _P, _P]),
+    'cnnq_pc_minmax_quantize_packed_dt': (_I, [_P, _I, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P]),
+    'cnnq_pc_aciq_quantize_packed_dt': (_I, [_P, _I, _L, _L, _L, ctypes.POINTER(ParamsCfg), _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -63,6 +63,7 @@
 #include "cnnq_nhwc_midtread.hip.h"
 #include "cnnq_nhwc_entropy.hip.h"
 #include "cnnq_nhwc_packed.hip.h"
+#include "cnnq_half_packed.hip.h"
 #include "cnnq_qerr.hip.h"
 #include "cnnq_nhwc_qerr.hip.h"
 #include "cnnq_half_qerr.hip.h"
@@ -2811,6 +2812,129 @@ int cnnq_pc_aciq_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int64
     int rc = cl_aciq_front(x, dtype, R, C, p, cfg, ws, stats, qp, diag, stream);
     if (!rc) rc = cnnq_pc_packed_layout_nhwc(ba ? diag + (size_t)CNNQ_DIAG_BITS * C : nullptr, ba ? 0 : cfg->num_bits, C, coloff, stream);
     if (!rc) rc = cl_pack(x, dtype, R, C, p, qp, nullptr, coloff, packed, ba ? -1 : cfg->num_bits, hs(stream));
+    return rc;
+}
+
+// ---- integer codes as the stored format of contiguous bf16 / fp16 activations (cnnq_half_packed.hip.h) ---------------------------
+// Whether the pack launch beats the upcast route (x.float(), then cnnq_pc_quantize_packed) for this class of layer beyond the
+// run's spread (tools/bench_half_packed.py, profiles/half_packed.md): a class that does not goes back to 0 here.  Measured on the
+// ResNet-50 b512 conv outputs, bf16 and fp16 alike: ten classes won (native's maximum under the upcast route's minimum, 0.42-0.66
+// of its time); the two 7x7 classes - 2-byte pieces, W = 1 whatever the alignment - did not (2048x7x7 586 us against 448,
+// 512x7x7 294 against 190).  So: rows of an odd number of elements with N * HW >= 16384 report 0; smaller populations were not
+// measured and stay native.
+static int h_pk_native(int64_t N, int64_t C, int64_t HW, int dtype) {
+    (void)C; (void)dtype;
+    return !(HW % 2 != 0 && N * HW >= 16384);
+}
+
+// what the entry points of this section check before anything touches the device: the shape, the dtype, their own `ok`; then the
+// fp32 entry points' geometry limits (cnnq_pc_qdq_dt's) and a sample's rows at 8 bits per code inside rowoff's 32 bits
+static int h_pk_check(int64_t N, int64_t C, int64_t HW, int dtype, bool ok) {
+    if (!dtype_ok(dtype) || N < 1 || C < 1 || HW < 1 || !ok) return CNNQ_EINVAL;
+    const int rc = cnnq_pc_groups(N, C, HW, 0);
+    if (rc <= 0) return g_error(rc);
+    return C * 4 * ((HW * 8 + 31) / 32) >= ((int64_t)1 << 32) ? CNNQ_ERANGE : 0;
+}
+static bool h_pk_elem_ok(const void* p, int dtype) { return p && !misaligned(p, dtype == CNNQ_DTYPE_F32 ? 4 : 2); }
+
+// the pack launch: pmm == NULL - the table qp, the widths bits and their layout rowoff; else the partials pmm, the uniform width
+// ha.num_bits, and rowoff an output (k_h_pack)
+static int h_pack(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, const float* bits, uint32_t* rowoff,
+                  uint8_t* packed, const float* pmm, const HArgs& ha, hipStream_t st) {
+    const int w = h_piece(HW, (uintptr_t)x, 0);
+    const HGeo g = h_geo_pack(N, C, HW, w);
+    const int rps = h_pk_rps(HW, w);
+    uint32_t* out = reinterpret_cast<uint32_t*>(packed);
+    return h_launch(dtype, w, x, [&](auto pc, const uint16_t* xh) {
+        with_bool(pmm != nullptr, [&](auto part) {
+            using P = decltype(pc);
+            hipLaunchKernelGGL((k_h_pack<typename P::T, P::W, decltype(part)::value>), dim3((unsigned)(C * g.S)), dim3(TPB), 0, st, xh, out, g, rps,
+                               qp, bits, rowoff, pmm, ha);
+        });
+    });
+}
+
+// Which launch cnnq_pc_quantize_packed_dt makes for this geometry (host only): out = {piece width W, workgroups of the pack launch,
+// rows per step (0: long rows), 1 - native / 0 - a class of layer that did not win against the upcast route and stays there
+// (h_pk_native; the entry points themselves run every class)}.  fp32: {0, 0, 0, 1}.
+int cnnq_pc_route_packed_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int32_t out[4]) {
+    if (const int rc = h_pk_check(N, C, HW, dtype, out && pow2(align_bytes))) return rc;
+    out[0] = out[1] = out[2] = 0;
+    out[3] = 1;
+    if (dtype == CNNQ_DTYPE_F32) return 0;
+    const int w = h_piece(HW, (uintptr_t)align_bytes, 0);
+    out[0] = w;
+    out[1] = (int32_t)(C * h_geo_pack(N, C, HW, w).S);
+    out[2] = h_pk_rps(HW, w);
+    out[3] = h_pk_native(N, C, HW, dtype);
+    return 0;
+}
+
+// int_quantizer.py:573-587 on x[N][C][HW] of bf16 / fp16 with the codes kept (the reference keeps them as floats): k_h_pack
+int cnnq_pc_quantize_packed_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, const float* bits,
+                               const uint32_t* rowoff, uint8_t* packed, void* stream) {
+    if (const int rc = h_pk_check(N, C, HW, dtype, h_pk_elem_ok(x, dtype) && qp && bits && rowoff && packed && !misaligned(packed, 4))) return rc;
+    if (dtype == CNNQ_DTYPE_F32) return cnnq_pc_quantize_packed(static_cast<const float*>(x), packed, N, C, HW, qp, bits, rowoff, stream);
+    return h_pack(x, dtype, N, C, HW, qp, bits, const_cast<uint32_t*>(rowoff), packed, nullptr, HArgs{}, hs(stream));
+}
+
+// int_quantizer.py:591-592 from the stored codes into bf16 / fp16: k_h_unpack
+int cnnq_pc_dequantize_packed_dt(const uint8_t* packed, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp,
+                                 const float* bits, const uint32_t* rowoff, void* stream) {
+    if (const int rc = h_pk_check(N, C, HW, dtype, h_pk_elem_ok(y, dtype) && qp && bits && rowoff && packed && !misaligned(packed, 4))) return rc;
+    if (dtype == CNNQ_DTYPE_F32) return cnnq_pc_dequantize_packed(packed, static_cast<float*>(y), N, C, HW, qp, bits, rowoff, stream);
+    const int w = h_piece(HW, (uintptr_t)y, 0);
+    const HGeo g = h_geo_qdq(N, C, HW, w);
+    const uint32_t* in = reinterpret_cast<const uint32_t*>(packed);
+    return h_launch(dtype, w, nullptr, y, [&](auto pc, const uint16_t*, uint16_t* yh) {
+        using P = decltype(pc);
+        hipLaunchKernelGGL((k_h_unpack<typename P::T, P::W>), dim3((unsigned)(C * g.S)), dim3(TPB), 0, hs(stream), in, yh, g, qp, bits, rowoff);
+    });
+}
+
+// int_quantizer.py:409-451, 557-587 on x[N][C][HW] of bf16 / fp16, the codes kept: k_h_minmax -> k_h_pack on the partials (uniform
+// width num_bits, rowoff an output).  ws: cnnq_pc_minmax_qdq_workspace bytes (the partials; fp32: the width table too)
+int cnnq_pc_minmax_quantize_packed_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, int num_bits, int positive, float* ws,
+                                      float* qp, uint32_t* rowoff, uint8_t* packed, void* stream) {
+    const bool ok = h_pk_elem_ok(x, dtype) && ws && !misaligned(ws, 4) && qp && rowoff && packed && !misaligned(packed, 4) && num_bits >= 1 &&
+                    num_bits <= 8;
+    if (const int rc = h_pk_check(N, C, HW, dtype, ok)) return rc;
+    hipStream_t st = hs(stream);
+    const MmWs w(ws, C);
+    if (dtype == CNNQ_DTYPE_F32) {
+        const float* xf = static_cast<const float*>(x);
+        const int G = cnnq_pc_groups(N, C, HW, al16(xf) ? 1 : 0);
+        if (G <= 0) return g_error(G);
+        hipLaunchKernelGGL(k_h_fill_width, dim3(1), dim3(PTPB), 0, st, w.mm, (int)C, (float)num_bits);
+        int rc = launch_status();
+        if (!rc) rc = cnnq_pc_minmax(xf, N, C, HW, w.pmm, stream);
+        if (!rc) rc = cnnq_pc_minmax_params(w.pmm, G, C, num_bits, positive, qp, stream);
+        if (!rc) rc = cnnq_pc_packed_layout(w.mm, C, HW, rowoff, stream);
+        if (!rc) rc = cnnq_pc_quantize_packed(xf, packed, N, C, HW, qp, w.mm, rowoff, stream);
+        return rc;
+    }
+    int S = 0;
+    const int rc = h_minmax(x, dtype, N, C, HW, w.pmm, &S, st);
+    if (rc) return rc;
+    return h_pack(x, dtype, N, C, HW, nullptr, nullptr, rowoff, packed, w.pmm, HArgs{S, num_bits, positive ? 1 : 0, qp, w.mm}, st);
+}
+
+// int_quantizer.py:327-352 + 409-451, 557-587 on x[N][C][HW] of bf16 / fp16, the codes kept: the statistics and parameter launches of
+// route 2 of cnnq_pc_aciq_qdq_dt (k_h_moments -> k_combine (-> k_h_absdev -> k_combine_dev) -> k_params), k_packed_layout on
+// diag[CNNQ_DIAG_BITS] (the allocated widths; without bit allocation k_params writes cfg->num_bits there), k_h_pack on the table.
+// diag is required: the width table lives in it.
+int cnnq_pc_aciq_quantize_packed_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg, void* ws,
+                                    float* stats, float* qp, float* diag, uint32_t* rowoff, uint8_t* packed, void* stream) {
+    const bool ok = h_pk_elem_ok(x, dtype) && ws && !misaligned(ws, 8) && stats && qp && diag && !misaligned(stats, 4) && !misaligned(qp, 4) &&
+                    !misaligned(diag, 4) && rowoff && packed && !misaligned(packed, 4) && h_aciq_cfg_ok(cfg) && cfg->num_bits >= 1 &&
+                    cfg->num_bits <= 8;
+    if (const int rc = h_pk_check(N, C, HW, dtype, ok)) return rc;
+    const bool need_b = cfg->clip == 1 || (cfg_bit_alloc(cfg) && cfg->prior_is_b);
+    const float* bits = diag + (size_t)CNNQ_DIAG_BITS * C;
+    int rc = cnnq_pc_stats_dt(x, dtype, N, C, HW, need_b ? 1 : 0, 0, 0, ws, nullptr, stats, stream);
+    if (!rc) rc = cnnq_pc_params(stats, C, cfg, qp, diag, stream);
+    if (!rc) rc = cnnq_pc_packed_layout(bits, C, HW, rowoff, stream);
+    if (!rc) rc = cnnq_pc_quantize_packed_dt(x, dtype, N, C, HW, qp, bits, rowoff, packed, stream);
     return rc;
 }
 

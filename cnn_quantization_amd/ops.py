@@ -1875,6 +1875,147 @@ def aciq_quantize_packed_nhwc(x, num_bits, positive=False, clip='laplace', bit_a
     return packed, dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:], coloff=coloff)
 
 
+# ------------------------------------------------------------------------------------- stored codes on contiguous bf16 / fp16
+# quantize_packed's format - row (n, c) a little-endian stream of H*W codes of bits[c] bits, padded to whole
+# dwords, at byte n * rowoff[C] + rowoff[c] - written from and decoded into a contiguous 4-D bf16 / fp16 tensor on the storage as
+# it is.  These functions take what _admit_half takes or raise: no copy, no upcast (LAYOUT_COPIES never moves here).
+_PACKED_HALF_NATIVE = {}
+
+
+def _packed_half_native(N, C, HW, dtype):
+    """Whether this class of contiguous bf16 / fp16 layer packs faster on its own storage than through x.float() and
+    quantize_packed: the "native" word of cnnq_pc_route_packed_dt's report.  A caller that has the choice stays on the upcast
+    route where it says 0; the *_packed_half functions themselves run every class."""
+    return _route_word(_PACKED_HALF_NATIVE, (N, C, HW, dtype), bool, 'cnnq_pc_route_packed_dt', (N, C, HW), dtype)
+
+
+def _half_widths(bits, C, device, what):
+    """(the float32 device table [C] the C side reads, the uniform width or None) of `bits`: a table or an integer 0..8."""
+    uni = _uniform_width(bits, what)
+    if uni is not None:
+        return torch.full((C,), float(uni), dtype=torch.float32, device=device), uni
+    return _packed_table(bits, 'bits', torch.float32, (C,), device), None
+
+
+def _half_rowbytes(bits, HW):
+    return (int(bits) * HW + 31) // 32 * 4
+
+
+def quantize_packed_half(x, qp, bits, out=None, rowoff=None):
+    """A contiguous 4-D bf16 / fp16 x + parameter table qp [NQP, C] + widths -> (packed uint8, rowoff int32 [C + 1])
+    (cnnq_pc_quantize_packed_dt, one launch on the storage as it is): the bytes quantize_packed(x.float(), qp, bits) writes.
+    bits: an integer 0..8 for every channel - the buffer is sized exactly on the host - or a float32 device table [C]
+    (diag[DIAG_BITS]): sizing it exactly takes one host read of rowoff[C], as in quantize_packed.  out: a 4-byte aligned uint8
+    buffer of at least packed_capacity(x.shape) bytes, returned whole (the used prefix is N * rowoff[C] bytes); nothing
+    synchronises then.  rowoff: packed_layout(bits, H * W) when the caller already has it (one launch less)."""
+    lib = L.load()
+    what = 'quantize_packed_half'
+    x, (_, geo, C, dt, st) = _admit_half(x, what, 'quantize_packed')
+    N, _, HW = geo
+    qp = _packed_table(qp, 'qp', torch.float32, (L.NQP, C), x.device)
+    bits, uni = _half_widths(bits, C, x.device, what)
+    if rowoff is None:
+        rowoff = torch.empty(C + 1, dtype=torch.int32, device=x.device)
+        L.check(lib.cnnq_pc_packed_layout(bits.data_ptr(), C, HW, rowoff.data_ptr(), st), 'cnnq_pc_packed_layout')
+    else:
+        rowoff = _packed_table(rowoff, 'rowoff', torch.int32, (C + 1,), x.device)
+    if out is not None:
+        nbytes = packed_capacity(x.shape)
+    else:
+        nbytes = N * (C * _half_rowbytes(uni, HW) if uni is not None else int(rowoff[C].item()))
+    buf, packed = _packed_buffer(out, nbytes, x.device, what)
+    L.check(lib.cnnq_pc_quantize_packed_dt(x.data_ptr(), dt, N, C, HW, qp.data_ptr(), bits.data_ptr(), rowoff.data_ptr(),
+                                           buf.data_ptr(), st), 'cnnq_pc_quantize_packed_dt')
+    return packed, rowoff
+
+
+def dequantize_packed_half(packed, shape, dtype, qp, bits, rowoff, out=None):
+    """Inverse of quantize_packed_half (cnnq_pc_dequantize_packed_dt): a contiguous tensor of `shape` and `dtype` (bfloat16 /
+    float16) holding (code - zp) * scale rounded once into dtype - dequantize_packed's floats .to(dtype), bit for bit.  The buffer
+    may as well come from quantize_packed on a float32 tensor: there is one format."""
+    lib = L.load()
+    what = 'dequantize_packed_half'
+    if not isinstance(packed, torch.Tensor) or not packed.is_cuda:
+        raise L.CnnqError('%s: packed must be a CUDA/HIP tensor (there is no CPU path)' % what)
+    if dtype not in _HALF_DTYPES:
+        raise L.CnnqError('%s: dtype must be bfloat16 or float16, got %s (float32 takes dequantize_packed)' % (what, dtype))
+    shape = tuple(int(d) for d in shape)
+    if len(shape) != 4 or min(shape) < 1:
+        raise L.CnnqError('%s: shape must be that of a non-empty 4-D activation' % what)
+    if not (packed.dtype == torch.uint8 and packed.is_contiguous() and packed.data_ptr() % 4 == 0):
+        raise L.CnnqError('%s: packed must be a contiguous, 4-byte aligned uint8 buffer' % what)
+    if packed.device.index != torch.cuda.current_device():
+        raise L.CnnqError('%s: packed is on %s but the current device is cuda:%d' % (what, packed.device, torch.cuda.current_device()))
+    C = shape[1]
+    qp = _packed_table(qp, 'qp', torch.float32, (L.NQP, C), packed.device)
+    bits, _ = _half_widths(bits, C, packed.device, what)
+    rowoff = _packed_table(rowoff, 'rowoff', torch.int32, (C + 1,), packed.device)
+    if out is None:
+        y = torch.empty(shape, dtype=dtype, device=packed.device)
+    else:
+        y = out
+        if not (isinstance(y, torch.Tensor) and y.is_cuda and y.device == packed.device and y.dtype == dtype and tuple(y.shape) == shape
+                and y.is_contiguous()):
+            raise L.CnnqError('%s: out must be a contiguous %s tensor of the given shape' % (what, str(dtype).replace('torch.', '')))
+    N, C, HW = geometry(y)
+    # an empty buffer (every width 0) has no address; nothing is read through the pointer then
+    L.check(lib.cnnq_pc_dequantize_packed_dt(ctypes.c_void_p(packed.data_ptr() or y.data_ptr()), y.data_ptr(), _HALF_DTYPES[dtype], N, C, HW,
+                                             qp.data_ptr(), bits.data_ptr(), rowoff.data_ptr(), _raw_stream(y.device.index)),
+            'cnnq_pc_dequantize_packed_dt')
+    return y
+
+
+def minmax_quantize_packed_half(x, num_bits=4, positive=False, out=None):
+    """Config 2 straight into the stored format (cnnq_pc_minmax_quantize_packed_dt, two launches): the exact per-channel min / max
+    of a contiguous bf16 / fp16 x, the parameter table, the uniform num_bits (1..8) layout and the packed codes, one host call ->
+    (packed uint8 [N * C * 4 * ceil(num_bits * H*W / 32)], rowoff int32 [C + 1], qp [NQP, C])."""
+    lib = L.load()
+    what = 'minmax_quantize_packed_half'
+    x, (_, geo, C, dt, st) = _admit_half(x, what, 'quantize_packed')
+    if isinstance(num_bits, bool) or not isinstance(num_bits, int) or not 1 <= num_bits <= 8:
+        raise L.CnnqError('%s: num_bits must be an integer in 1..8, got %r' % (what, num_bits))
+    N, _, HW = geo
+    ws = _scratch(x, 'cfg2', _ws_bytes('cfg2', N, C, HW), st).data_ptr()
+    qp = torch.empty(L.NQP, C, dtype=torch.float32, device=x.device)
+    rowoff = torch.empty(C + 1, dtype=torch.int32, device=x.device)
+    buf, packed = _packed_buffer(out, N * C * _half_rowbytes(num_bits, HW), x.device, what)
+    rc = lib.cnnq_pc_minmax_quantize_packed_dt(x.data_ptr(), dt, N, C, HW, num_bits, 1 if positive else 0, ws, qp.data_ptr(),
+                                               rowoff.data_ptr(), buf.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_minmax_quantize_packed_dt')
+    return packed, rowoff, qp
+
+
+def aciq_quantize_packed_half(x, num_bits, positive=False, clip='laplace', bit_alloc=False, prior_is_b=False, target=None,
+                              round_mode=True, out=None):
+    """Config 3 straight into the stored format (cnnq_pc_aciq_quantize_packed_dt): the statistics and parameters of aciq_qdq_half's
+    chain on a contiguous bf16 / fp16 x, then the packed codes instead of y, one host call -> (packed uint8, rowoff int32 [C + 1],
+    dict(stats, qp, diag)) - the parts of aciq_qdq_half(want_parts=True).  With bit allocation the widths are diag[DIAG_BITS] and a
+    buffer of packed_capacity(x.shape) bytes comes back, of which N * rowoff[C] are used, and nothing synchronises; without it the
+    width is num_bits (<= 8) and the buffer exact."""
+    what = 'aciq_quantize_packed_half'
+    if clip not in ('laplace', 'gaus'):
+        raise L.CnnqError("%s: clip must be 'laplace' or 'gaus', got %r" % (what, clip))
+    lib = L.load()
+    x, (_, geo, C, dt, st) = _admit_half(x, what, 'quantize_packed')
+    if isinstance(num_bits, bool) or not isinstance(num_bits, int) or not 1 <= num_bits <= 8:
+        raise L.CnnqError('%s: num_bits must be an integer in 1..8, got %r' % (what, num_bits))
+    N, _, HW = geo
+    use_ba = bool(bit_alloc) and num_bits <= 4
+    cfg = _params_cfg(num_bits, positive, clip, use_ba, prior_is_b, target, round_mode, False)
+    ws = _scratch(x, 'aciq_half', _ws_bytes('aciq_half', N, C, HW, dt), st).data_ptr()
+    tabs = torch.empty(L.NSTAT + L.NQP + L.NDIAG, C, dtype=torch.float32, device=x.device)
+    rowoff = torch.empty(C + 1, dtype=torch.int32, device=x.device)
+    nbytes = packed_capacity(x.shape) if use_ba else N * C * _half_rowbytes(num_bits, HW)
+    buf, packed = _packed_buffer(out, nbytes, x.device, what)
+    tp = tabs.data_ptr()
+    rc = lib.cnnq_pc_aciq_quantize_packed_dt(x.data_ptr(), dt, N, C, HW, ctypes.byref(cfg), ws, tp, tp + L.NSTAT * C * 4,
+                                             tp + (L.NSTAT + L.NQP) * C * 4, rowoff.data_ptr(), buf.data_ptr(), st)
+    if rc:
+        L.check(rc, 'cnnq_pc_aciq_quantize_packed_dt')
+    return packed, rowoff, dict(stats=tabs[:L.NSTAT], qp=tabs[L.NSTAT:L.NSTAT + L.NQP], diag=tabs[L.NSTAT + L.NQP:])
+
+
 def entropy_from_hist(hist):
     """Shannon entropy (bits) of an int64 histogram tensor -> 0-dim float32 tensor on the device."""
     lib = L.load()

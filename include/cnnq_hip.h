@@ -1201,6 +1201,50 @@ int cnnq_pc_minmax_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int
 int cnnq_pc_aciq_quantize_packed_nhwc(const void* x, int dtype, int64_t R, int64_t C, const cnnq_params_cfg* cfg, void* ws,
                                       float* stats, float* qp, float* diag, uint32_t* coloff, uint8_t* packed, void* stream);
 
+/* Integer codes as the STORED format of a contiguous bf16 / fp16 NCHW activation, on the storage as it is:
+ * 2 B read + bits / 8 B written per element, no fp32 copy.
+ *
+ * Format: the stream of cnnq_pc_packed_layout / cnnq_pc_quantize_packed above, unchanged - row (n, c) holds H*W codes of
+ * bits[c] in 0..8 bits, little-endian, padded with zero bits to whole dwords, at byte n * rowoff[C] + rowoff[c]; a 0-bit channel
+ * stores nothing and decodes to (0 - zp) * scale.  A buffer packed from a bf16 / fp16 tensor is byte for byte what
+ * cnnq_pc_quantize_packed writes for the upcast tensor with the same qp, bits and rowoff; cnnq_pc_dequantize_packed decodes it,
+ * and cnnq_pc_dequantize_packed_dt decodes an fp32-packed buffer into bf16 / fp16.  Every code is masked to its channel's width:
+ * a qp whose qmax[c] exceeds 2^bits[c] - 1 is the caller's error and may truncate that channel's codes, never touch a
+ * neighbour's bits.  A NaN code is stored as 0 (what cnnq_pc_quantize_packed stores for it).  A width table entry above 8 counts
+ * as 8, a negative or NaN one as 0.
+ *
+ * cnnq_pc_route_packed_dt (host only, nothing enqueued; int_quantizer.py has no counterpart: the reference keeps codes as floats):
+ *   out = {elements per load W - the widest of 8 / 4 / 2 / 1 that divides H*W and the alignment, workgroups of the pack launch,
+ *   rows per wave step (0: rows of more than 64 pieces, one row per step), 1 - native / 0 - a class of layer that measured no
+ *   faster than the upcast route and whose callers stay there; the entry points themselves run every class}.  fp32: {0, 0, 0, 1}.
+ * cnnq_pc_quantize_packed_dt (int_quantizer.py:573-587, the codes kept): x -> packed, one launch.  Every dword of the
+ *   N * rowoff[C] bytes is written exactly once by a plain store, padding included, no byte beyond them: no atomics on global
+ *   memory, the same bytes run after run.
+ * cnnq_pc_dequantize_packed_dt (int_quantizer.py:591-592): packed -> y = (code - zp) * scale rounded once into dtype, one launch.
+ * cnnq_pc_minmax_quantize_packed_dt (int_quantizer.py:409-451, 557-587): config 2 in one call, two launches - the exact extrema's
+ *   partials, then the pack launch, whose workgroups merge their channel's partials and derive the parameters; the first split
+ *   publishes qp[CNNQ_NQP][C] and the layout.  Uniform width num_bits in 1..8; rowoff[C + 1] is an OUTPUT, filled on the device.
+ *   ws: cnnq_pc_minmax_qdq_workspace bytes.
+ * cnnq_pc_aciq_quantize_packed_dt (int_quantizer.py:327-352, 409-451, 557-587): config 3 in one call - the statistics and
+ *   parameter launches of the chain of cnnq_pc_aciq_qdq_dt without its Q/DQ launch, the layout from diag[CNNQ_DIAG_BITS] (the
+ *   allocated widths; without bit allocation cfg->num_bits, which must be <= 8), the pack launch on the table.  ws:
+ *   cnnq_pc_aciq_dt_workspace bytes, 8-byte aligned; cfg, stats, qp as cnnq_pc_aciq_qdq_dt; diag is required (the width table
+ *   lives there); rowoff[C + 1] is an OUTPUT.
+ * CNNQ_DTYPE_F32 forwards to the fp32 entry points above or their composition.  All of them return CNNQ_EINVAL before anything
+ * touches the device for a NULL required pointer, N, C or HW < 1, a dtype outside cnnq_dtype, x or y not aligned to its element,
+ * a `packed` that is not 4-byte aligned, a misaligned ws, num_bits outside 1..8; CNNQ_ERANGE as cnnq_pc_qdq_dt, and for a sample
+ * of 4 GB of codes and more.  Re-entrant, allocate nothing, no host synchronisation, graph-capturable. */
+int cnnq_pc_route_packed_dt(int64_t N, int64_t C, int64_t HW, int dtype, int align_bytes, int32_t out[4]);
+int cnnq_pc_quantize_packed_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp, const float* bits,
+                               const uint32_t* rowoff, uint8_t* packed, void* stream);
+int cnnq_pc_dequantize_packed_dt(const uint8_t* packed, void* y, int dtype, int64_t N, int64_t C, int64_t HW, const float* qp,
+                                 const float* bits, const uint32_t* rowoff, void* stream);
+int cnnq_pc_minmax_quantize_packed_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, int num_bits, int positive,
+                                      float* ws, float* qp, uint32_t* rowoff, uint8_t* packed, void* stream);
+int cnnq_pc_aciq_quantize_packed_dt(const void* x, int dtype, int64_t N, int64_t C, int64_t HW, const cnnq_params_cfg* cfg,
+                                    void* ws, float* stats, float* qp, float* diag, uint32_t* rowoff, uint8_t* packed,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
