@@ -30,7 +30,11 @@ __device__ __forceinline__ float qdq1(float x, float scale, float zp, float qmax
 //     2^(ex-46) >= 2^-116), so q1 is a faithful and q the correctly rounded quotient (Markstein's theorem: rs is the
 //     correctly rounded reciprocal) - bit-identical to x / s;
 //   * for |x| < 2^-70 (zeros, denormals) the exact quotient and this one are both below 2^-39 in magnitude: q + zp rounds
-//     to zp when zp != 0, and for zp == 0 (zp is never -0) both clamp / round to +0 - the same code and the same y.
+//     to zp when zp != 0, and for zp == 0 both clamp / round to a zero - the same code and the same y.  zp IS -0 for a
+//     channel with 0 < min < scale / 2 (round(0 - 0.125) = -0, as torch.round gives it; the table publishes that bit): such
+//     a channel holds no x <= 0, and a zero code of either sign gives y = (+-0 - -0) * s = +0 on both paths.  A table
+//     handed in (-sm use) can meet x <= 0 with zp = -0, and takes the IEEE divide (k_qdq); the same y
+//     (tests/test_minmax_params_table_gpu.py).
 // No NaN can occur inside the domain, so the clamp is one v_med3_f32 instead of two compare+select pairs.
 // 10 VALU operations per element against 19 (of which one quarter-rate).  tests/test_fastdiv_cpu.py brute-forces the
 // quotient against the C divide; the -m gpu parity tests compare whole tensors with the CPU restatement bit for bit.
