@@ -26,6 +26,7 @@ def mt_hist_words(C):
 KLD_BINS, KLD_QBINS, KLD_NCAND = 2001, 15, 994
 DIAG_BITS, DIAG_ALPHA, DIAG_DELTA, DIAG_OFFSET, NDIAG = 0, 1, 2, 3, 4
 DTYPE_F32, DTYPE_BF16, DTYPE_F16, NDTYPE = 0, 1, 2, 3
+CODES_U8, CODES_PACK4, NCODES = 0, 1, 2
 
 
 class ParamsCfg(ctypes.Structure):
@@ -207,6 +208,10 @@ SIGNATURES = {
     'cnnq_pc_dequantize_packed_dt': (_I, [_P, _P, _I, _L, _L, _L, _P, _P, _P, _P]),
     'cnnq_pc_minmax_quantize_packed_dt': (_I, [_P, _I, _L, _L, _L, _I, _I, _P, _P, _P, _P, _P]),
     'cnnq_pc_aciq_quantize_packed_dt': (_I, [_P, _I, _L, _L, _L, ctypes.POINTER(ParamsCfg), _P, _P, _P, _P, _P, _P, _P]),
+    'cnnq_linear_codes_workspace': (ctypes.c_size_t, [_L, _L, _L, _I, _I, _I]),
+    'cnnq_linear_codes_route': (_I, [_L, _L, _L, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_linear_codes_rowsums': (_I, [_P, _I, _L, _L, _P, _P]),
+    'cnnq_linear_codes': (_I, [_P, _I, _P, _I, _P, _L, _L, _L, _P, _L, _P, _P, _P, _I, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None

@@ -1,7 +1,7 @@
 // cnnq_kernels.hip - gfx950 (MI355X / CDNA4) kernels behind include/cnnq_hip.h.
 //
 // Design: the whole path is HBM-bound elementwise + reduction work, so
-// nothing here is shaped for MFMA.  All streaming kernels share ONE decomposition of the
+// nothing on it is shaped for MFMA (the one contraction, cnnq_linear_codes.hip.h, stands apart).  All streaming kernels share ONE decomposition of the
 // NCHW tensor x[N][C][HW]:
 //
 //   * the C*HW "plane" of one sample is cut into column blocks; a workgroup owns one column
@@ -70,6 +70,7 @@
 #include "cnnq_sample_extrema.hip.h"
 #include "cnnq_rows.hip.h"
 #include "cnnq_flat.hip.h"
+#include "cnnq_linear_codes.hip.h"
 
 namespace {
 
@@ -3063,6 +3064,103 @@ int cnnq_pt_midtread(const void* x, void* y, int dtype, int64_t n, double target
     if (!rc) rc = cnnq_pc_midtread_params(stats, 1, target, 1, sym, tables, ntab, mt, stream);
     if (!rc) rc = flat_launch(true, x, y, dtype, n, mt, stream);
     return rc;
+}
+
+
+// ---- the integer linear layer on the stored codes (cnnq_linear_codes.hip.h): y [M][N] from xq [M][K] and wq [N][K] ----------------
+static bool lc_fmt_ok(int fmt) { return fmt == CNNQ_CODES_U8 || fmt == CNNQ_CODES_PACK4; }
+// the geometry every entry point of the family checks first.  CNNQ_ERANGE: K beyond 131071 (K * 128 * 128 must fit int32), 2^31
+// outputs and more (the epilogue's grid, the partial tiles' size)
+static int lc_check(int64_t M, int64_t N, int64_t K, int fmt_x, int fmt_w, int splits) {
+    if (!lc_fmt_ok(fmt_x) || !lc_fmt_ok(fmt_w) || M < 1 || N < 1 || K < 1 || splits < 0 || splits > LC_MAX_SPLITS) return CNNQ_EINVAL;
+    if (K % 4 || ((fmt_x == CNNQ_CODES_PACK4 || fmt_w == CNNQ_CODES_PACK4) && K % 8)) return CNNQ_EINVAL;
+    if (K > LC_MAX_K || M >= ((int64_t)1 << 31) || N >= ((int64_t)1 << 31) || M * N >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    const LcPlan p = lc_plan(M, N, K, splits);
+    return (int64_t)p.tilesM * p.tilesN * p.splits >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
+}
+// rows of whole 16-byte pieces: K % 16 == 0 and a base aligned to a chunk of 16 codes (16 bytes of u8, 8 of pack4)
+static bool lc_v16(int64_t K, int fmt_x, int fmt_w, uintptr_t ax, uintptr_t aw) {
+    return K % 16 == 0 && ax % (fmt_x == CNNQ_CODES_U8 ? 16 : 8) == 0 && aw % (fmt_w == CNNQ_CODES_U8 ? 16 : 8) == 0;
+}
+
+size_t cnnq_linear_codes_workspace(int64_t M, int64_t N, int64_t K, int fmt_x, int fmt_w, int splits) {
+    if (lc_check(M, N, K, fmt_x, fmt_w, splits)) return 0;
+    return LcWs::bytes(M, N, lc_plan(M, N, K, splits).splits);
+}
+
+// Which launch cnnq_linear_codes makes for this geometry (host only): out = {rows of the macro tile, its columns, splits of k,
+// 1 - 16-byte loads / 0 - the dword path}.  No shape is sent away from the integer route: see DESIGN.md section 35 for what was
+// and was not measured.
+int cnnq_linear_codes_route(int64_t M, int64_t N, int64_t K, int fmt_x, int fmt_w, int splits, int align_bytes, int32_t out[4]) {
+    if (!out || !pow2(align_bytes) || align_bytes < 4) return CNNQ_EINVAL;
+    if (const int rc = lc_check(M, N, K, fmt_x, fmt_w, splits)) return rc;
+    const LcPlan p = lc_plan(M, N, K, splits);
+    out[0] = p.BM;
+    out[1] = p.BN;
+    out[2] = p.splits;
+    out[3] = lc_v16(K, fmt_x, fmt_w, (uintptr_t)align_bytes, (uintptr_t)align_bytes);
+    return 0;
+}
+
+// the launch of k_lc_rowsums over M rows of xq (M may be 0) and Nw rows of wq (Nw may be 0)
+static int lc_rowsums_launch(const uint8_t* xq, int fmt_x, int64_t M, const uint8_t* wq, int fmt_w, int64_t Nw, int64_t K, int* rx, int* rw,
+                             void* stream) {
+    const dim3 grid((unsigned)((M + Nw + TPB / 64 - 1) / (TPB / 64)));
+    hipLaunchKernelGGL(k_lc_rowsums, grid, dim3(TPB), 0, hs(stream), xq, fmt_x, (int)M, wq, fmt_w, (int)Nw, (int)K, rx, rw);
+    return launch_status();
+}
+
+int cnnq_linear_codes_rowsums(const uint8_t* codes, int fmt, int64_t rows, int64_t K, int32_t* sums, void* stream) {
+    if (!lc_fmt_ok(fmt) || rows < 1 || K < 1 || K % (fmt == CNNQ_CODES_U8 ? 4 : 8) || !codes || !sums) return CNNQ_EINVAL;
+    if (misaligned(codes, 4) || misaligned(sums, 4)) return CNNQ_EINVAL;
+    if (K > LC_MAX_K || rows >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    return lc_rowsums_launch(nullptr, fmt, 0, codes, fmt, rows, K, nullptr, sums, stream);
+}
+
+int cnnq_linear_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, int64_t M, int64_t N, int64_t K, const float* qpx,
+                      int64_t Cx, const float* qpw, const float* bias, const int32_t* rw, int splits, void* ws, size_t ws_bytes, void* stream) {
+    if (const int rc = lc_check(M, N, K, fmt_x, fmt_w, splits)) return rc;
+    if (!xq || !wq || !y || !qpx || !qpw || !ws || (Cx != 1 && Cx != M)) return CNNQ_EINVAL;
+    if (misaligned(xq, 4) || misaligned(wq, 4) || misaligned(y, 4) || misaligned(qpx, 4) || misaligned(qpw, 4) || misaligned(bias, 4) ||
+        misaligned(rw, 4) || misaligned(ws, 16))
+        return CNNQ_EINVAL;
+    const LcPlan p = lc_plan(M, N, K, splits);
+    if (ws_bytes < LcWs::bytes(M, N, p.splits)) return CNNQ_EINVAL;
+    const LcWs w(ws, M, N);
+    if (const int rc = lc_rowsums_launch(xq, fmt_x, M, wq, fmt_w, rw ? 0 : N, K, w.rx, w.rw, stream)) return rc;
+    LcArgs a;
+    a.xq = xq;
+    a.wq = wq;
+    a.y = y;
+    a.part = w.part;
+    a.M = (int)M;
+    a.tilesM = p.tilesM;
+    a.tilesN = p.tilesN;
+    a.splits = p.splits;
+    a.e.qpx = qpx;
+    a.e.qpw = qpw;
+    a.e.bias = bias;
+    a.e.rx = w.rx;
+    a.e.rw = rw ? rw : w.rw;
+    a.e.Cx = (int)Cx;
+    a.e.N = (int)N;
+    a.e.K = (int)K;
+    a.e.ox = fmt_x == CNNQ_CODES_U8 ? 128 : 0;
+    a.e.ow = fmt_w == CNNQ_CODES_U8 ? 128 : 0;
+    const dim3 grid((unsigned)((int64_t)p.tilesM * p.tilesN * p.splits));
+    with_int<0, 1, 2>(p.tile, [&](auto t) {
+        with_bool(fmt_x == CNNQ_CODES_PACK4, fmt_w == CNNQ_CODES_PACK4, lc_v16(K, fmt_x, fmt_w, (uintptr_t)xq, (uintptr_t)wq), [&](auto px, auto pw, auto v) {
+            constexpr int T = decltype(t)::value;
+            constexpr int WM = T == 0 ? 1 : 2, WN = T == 0 ? 4 : 2, TM = T == 0 ? 1 : T == 1 ? 2 : 4, TN = T == 0 ? 2 : T == 1 ? 2 : 4;
+            constexpr int FX = decltype(px)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, FW = decltype(pw)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8;
+            hipLaunchKernelGGL((k_lc_gemm<WM, WN, TM, TN, FX, FW, decltype(v)::value>), grid, dim3(TPB), 0, hs(stream), a);
+        });
+    });
+    if (const int rc = launch_status()) return rc;
+    if (p.splits == 1) return 0;
+    const long long MN = (long long)M * N;
+    hipLaunchKernelGGL(k_lc_epilogue, dim3((unsigned)((MN + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.part, p.splits, MN, a.e, y);
+    return launch_status();
 }
 
 }  // extern "C"

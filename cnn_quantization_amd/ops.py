@@ -2845,3 +2845,64 @@ def row_sumsq(x, rows=None):
     rows = int(rows if rows is not None else x.shape[0])
     _, mom = pc_stats(x, 1, rows, x.numel() // rows, local_only=True)
     return mom[L.MOM_SUMSQ].to(torch.float32)
+
+
+# ------------------------------------------------------------------------------------- the integer linear layer on the codes
+_CODE_FORMATS = {'u8': L.CODES_U8, 'pack4': L.CODES_PACK4}
+
+
+def _codes(t, fmt, what):
+    """(tensor, format word, rows, K) of a code matrix: uint8 [rows, K] ('u8') or [rows, K / 2] ('pack4'), contiguous, on the
+    current device.  No copy is made here."""
+    if fmt not in _CODE_FORMATS:
+        raise L.CnnqError("%s: format must be 'u8' or 'pack4', got %r" % (what, fmt))
+    t = _dev(t, what, (torch.uint8,))
+    if t.dim() != 2 or t.numel() == 0:
+        raise L.CnnqError('%s must be a non-empty 2-D uint8 tensor of codes, got shape %s' % (what, tuple(t.shape)))
+    return t, _CODE_FORMATS[fmt], t.shape[0], t.shape[1] * (2 if fmt == 'pack4' else 1)
+
+
+def _lc_table(t, what, dtype, shape, device):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == device and t.dtype == dtype and t.is_contiguous()
+            and tuple(t.shape) in shape):
+        raise L.CnnqError('%s must be a contiguous %s tensor of shape %s on %s'
+                          % (what, str(dtype).replace('torch.', ''), ' or '.join(str(s) for s in shape), device))
+    return t
+
+
+def linear_codes_rowsums(wq, w_format='u8'):
+    """The int32 sum of every row's codes of a code matrix (cnnq_linear_codes_rowsums): Rw of a layer's weight codes, computed once
+    and handed to linear_codes as `rw`."""
+    wq, fmt, rows, K = _codes(wq, w_format, 'wq')
+    sums = torch.empty(rows, dtype=torch.int32, device=wq.device)
+    L.check(L.load().cnnq_linear_codes_rowsums(_ptr(wq), fmt, rows, K, _ptr(sums), _stream(wq)), 'cnnq_linear_codes_rowsums')
+    return sums
+
+
+def linear_codes(xq, wq, qpx, qpw, bias=None, x_format='u8', w_format='u8', rw=None, out=None, splits=0):
+    """The fully-connected layer on the stored codes (cnnq_linear_codes): activation codes xq [M, K] with the
+    table qpx [NQP, 1] (per tensor) or [NQP, M] (per sample), weight codes wq [N, K] with qpw [NQP, N] (per output channel), each
+    operand 'u8' (one byte per code) or 'pack4' (uint8 [rows, K / 2], the even element in the low nibble) ->
+    sum_k ((xq - zx) sx) ((wq - zw) sw) + bias as float32 [M, N]: the integer dot products of the gfx950 int8 matrix instructions,
+    combined in fp64 and rounded once.  rw: linear_codes_rowsums(wq, w_format), held by the caller (None: computed per call);
+    splits: 0 - the plan's split of k, 1..64 forced (the same bits for every count).  On the stream of xq; no host synchronisation."""
+    lib = L.load()
+    xq, fx, M, K = _codes(xq, x_format, 'xq')
+    wq, fw, N, Kw = _codes(wq, w_format, 'wq')
+    if Kw != K or wq.device != xq.device:
+        raise L.CnnqError('linear_codes: xq has K = %d on %s, wq has K = %d on %s' % (K, xq.device, Kw, wq.device))
+    qpx = _lc_table(qpx, 'qpx', torch.float32, ((L.NQP, 1), (L.NQP, M)), xq.device)
+    qpw = _lc_table(qpw, 'qpw', torch.float32, ((L.NQP, N),), xq.device)
+    if bias is not None:
+        bias = _lc_table(bias, 'bias', torch.float32, ((N,),), xq.device)
+    if rw is not None:
+        rw = _lc_table(rw, 'rw', torch.int32, ((N,),), xq.device)
+    y = torch.empty((M, N), dtype=torch.float32, device=xq.device) if out is None else _lc_table(out, 'out', torch.float32, ((M, N),), xq.device)
+    splits = int(splits)
+    nbytes = lib.cnnq_linear_codes_workspace(M, N, K, fx, fw, splits)
+    st = _raw_stream(xq.device.index)
+    ws = _scratch(xq, 'linear_codes', nbytes, st)
+    # a geometry the library refuses sizes no workspace (nbytes == 0): the call below names the error
+    L.check(lib.cnnq_linear_codes(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), M, N, K, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias), _ptr(rw),
+                                  splits, _ptr(ws), nbytes, st), 'cnnq_linear_codes')
+    return y

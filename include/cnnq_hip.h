@@ -1245,6 +1245,48 @@ int cnnq_pc_aciq_quantize_packed_dt(const void* x, int dtype, int64_t N, int64_t
                                     void* ws, float* stats, float* qp, float* diag, uint32_t* rowoff, uint8_t* packed,
                                     void* stream);
 
+/* The integer linear layer ON the stored codes (beyond the reference, which multiplies the dequantized
+ * floats): a fully-connected layer whose input was quantized per tensor (or per sample) and whose weights per output channel,
+ * computed from the integer codes themselves with the gfx950 int8 matrix instructions - no operand is expanded to floats.
+ *
+ *   y[m][n] = sx[m'] sw[n] (S[m][n] - zw[n] Rx[m] - zx[m'] Rw[n] + K zx[m'] zw[n]) + bias[n],     m' = m (Cx == M) or 0 (Cx == 1)
+ *   S = sum_k xq[m][k] wq[n][k],   Rx[m] = sum_k xq[m][k],   Rw[n] = sum_k wq[n][k]
+ *
+ * which is sum_k ((xq - zx) sx) ((wq - zw) sw) under the decode rule of the dequantizers above, (code - zp) * scale, zp any float.
+ * S, Rx and Rw are exact integers; the combination is done in fp64 and rounded ONCE to fp32, so y is within one fp32 rounding (plus
+ * a few fp64 roundings of the four terms) of the exact value, for every split count the same bits, run after run.
+ *
+ * Operands.  xq [M][K] and wq [N][K] (row n: output channel n - what cnnq_pc_quantize_u8 / cnnq_pc_quantize_pack4 write for a
+ * weight seen as [1][N][K]), each in its own cnnq_code_format: CNNQ_CODES_U8 - one byte per code, K % 4 == 0; CNNQ_CODES_PACK4 -
+ * two codes of 0..15 per byte, the even element in the low nibble, K % 8 == 0 (with either operand pack4, K % 8 == 0).  Rows lie
+ * back to back; both code pointers 4-byte aligned (K % 16 == 0 and 16-byte aligned bases - 8 for pack4 - take the 16-byte loads).
+ * qpx[CNNQ_NQP][Cx] with Cx = 1 or M, qpw[CNNQ_NQP][N] (row QMAX is not read), bias[N] fp32 or NULL, y fp32 [M][N] contiguous.
+ * K <= 131071 (K * 128 * 128 fits int32) and M * N < 2^31.  Scales that vary along k (per-channel activation scales of a
+ * convolution's input) have no such form and are not served.
+ *
+ * cnnq_linear_codes_workspace: bytes of `ws` - int32 Rx[M] and Rw[N] (each rounded up to 16 bytes) and, with more than one split,
+ *   the int32 partial tiles [splits][M][N]; splits = 0: for the split count the plan chooses, 1..64: for that count.  0 on a
+ *   geometry cnnq_linear_codes refuses.
+ * cnnq_linear_codes_route (host only, nothing enqueued): out = {rows of the macro tile, its columns, splits of k, 1 - 16-byte
+ *   loads / 0 - the dword path}; align_bytes: a power of two (>= 4) that divides both code pointers.
+ * cnnq_linear_codes_rowsums: sums[rows] = the int32 sum of each row's codes, one launch - Rw of a layer, computed once and handed
+ *   to every later cnnq_linear_codes as `rw`.
+ * cnnq_linear_codes: the row-sum launch (the M rows of xq, and the N rows of wq unless rw is given), the tile launch, and - splits
+ *   > 1 - the launch that adds the splits and finishes; splits == 1 finishes in the tile launch.  splits: 0 - the plan's choice, 1..64
+ *   forced (the result does not depend on it).  ws: at least cnnq_linear_codes_workspace bytes for the same splits, 16-byte
+ *   aligned; its contents need no initialisation and mean nothing afterwards.
+ * All return CNNQ_EINVAL before anything touches the device for a format outside cnnq_code_format, M, N, K or rows < 1, K not a
+ * multiple of 4 (8 with pack4), splits outside 0..64, a NULL required pointer, Cx not 1 or M, a pointer not aligned as above, a
+ * ws_bytes too small; CNNQ_ERANGE for K > 131071 or 2^31 outputs.  Re-entrant, allocate nothing, no atomics, no host
+ * synchronisation, graph-capturable. */
+enum cnnq_code_format { CNNQ_CODES_U8 = 0, CNNQ_CODES_PACK4 = 1, CNNQ_NCODES = 2 };
+size_t cnnq_linear_codes_workspace(int64_t M, int64_t N, int64_t K, int fmt_x, int fmt_w, int splits);
+int cnnq_linear_codes_route(int64_t M, int64_t N, int64_t K, int fmt_x, int fmt_w, int splits, int align_bytes, int32_t out[4]);
+int cnnq_linear_codes_rowsums(const uint8_t* codes, int fmt, int64_t rows, int64_t K, int32_t* sums, void* stream);
+int cnnq_linear_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, int64_t M, int64_t N, int64_t K,
+                      const float* qpx, int64_t Cx, const float* qpw, const float* bias, const int32_t* rw, int splits, void* ws,
+                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
