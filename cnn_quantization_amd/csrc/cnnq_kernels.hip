@@ -71,6 +71,7 @@
 #include "cnnq_rows.hip.h"
 #include "cnnq_flat.hip.h"
 #include "cnnq_linear_codes.hip.h"
+#include "cnnq_conv_codes.hip.h"
 
 namespace {
 
@@ -3160,6 +3161,130 @@ int cnnq_linear_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w
     if (p.splits == 1) return 0;
     const long long MN = (long long)M * N;
     hipLaunchKernelGGL(k_lc_epilogue, dim3((unsigned)((MN + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.part, p.splits, MN, a.e, y);
+    return launch_status();
+}
+
+// ---- the integer convolution on the stored codes (cnnq_conv_codes.hip.h): y [N][OH][OW][Cout] from NHWC xq and OHWI wq ------------------
+// g = {N, H, W, C, Cout, KH, KW, sh, sw, ph, pw} checked and turned into the implicit GEMM's sizes
+struct CcShape {
+    int64_t N, H, W, C, Cout, KH, KW, sh, sw, ph, pw, OH, OW, M, K, pixels, ntab;
+};
+// CNNQ_ERANGE: a size of 2^31 and more, more than 64 taps, and what the linear layer refuses of M x Cout x K
+static int cc_check(const int64_t* g, int fmt_x, int fmt_w, int splits, CcShape& s) {
+    if (!g || !lc_fmt_ok(fmt_x) || !lc_fmt_ok(fmt_w)) return CNNQ_EINVAL;
+    for (int i = 0; i < 11; ++i)
+        if (g[i] < (i < 9 ? 1 : 0)) return CNNQ_EINVAL;
+    for (int i = 0; i < 11; ++i)
+        if (g[i] >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    s.N = g[0], s.H = g[1], s.W = g[2], s.C = g[3], s.Cout = g[4], s.KH = g[5], s.KW = g[6], s.sh = g[7], s.sw = g[8], s.ph = g[9], s.pw = g[10];
+    if (s.H + 2 * s.ph < s.KH || s.W + 2 * s.pw < s.KW) return CNNQ_EINVAL;         // no output pixel
+    if (s.H + 2 * s.ph >= ((int64_t)1 << 31) || s.W + 2 * s.pw >= ((int64_t)1 << 31) || s.KH * s.KW > CC_MAX_TAPS) return CNNQ_ERANGE;
+    if (s.C % 4 || ((fmt_x == CNNQ_CODES_PACK4 || fmt_w == CNNQ_CODES_PACK4) && s.C % 8)) return CNNQ_EINVAL;
+    s.OH = (s.H + 2 * s.ph - s.KH) / s.sh + 1;
+    s.OW = (s.W + 2 * s.pw - s.KW) / s.sw + 1;
+    s.K = s.KH * s.KW * s.C;
+    s.ntab = s.Cout * (s.KH + 1) * (s.KW + 1);
+    // N H W and N OH OW without overflow: every factor is below 2^31
+    if (s.N * s.H >= ((int64_t)1 << 31) || s.N * s.OH >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    s.pixels = s.N * s.H * s.W;
+    s.M = s.N * s.OH * s.OW;
+    if (s.pixels >= ((int64_t)1 << 31) || s.M >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    return lc_check(s.M, s.Cout, s.K, fmt_x, fmt_w, splits);
+}
+// chunks of 16 codes inside one tap: C % 16 == 0 and bases aligned to a chunk
+static bool cc_v16(const CcShape& s, int fmt_x, int fmt_w, uintptr_t ax, uintptr_t aw) { return lc_v16(s.C, fmt_x, fmt_w, ax, aw); }
+
+size_t cnnq_conv_codes_workspace(const int64_t g[11], int fmt_x, int fmt_w, int have_taps, int splits) {
+    CcShape s;
+    if (cc_check(g, fmt_x, fmt_w, splits, s)) return 0;
+    return CcWs::bytes(s.pixels, s.M, have_taps ? 0 : s.ntab, s.Cout, lc_plan(s.M, s.Cout, s.K, splits).splits);
+}
+
+// Which launch cnnq_conv_codes makes for this geometry (host only): out = {rows of the macro tile, its columns, splits of k,
+// 1 - 16-byte loads / 0 - the dword path, OH, OW}
+int cnnq_conv_codes_route(const int64_t g[11], int fmt_x, int fmt_w, int splits, int align_bytes, int32_t out[6]) {
+    if (!out || !pow2(align_bytes) || align_bytes < 4) return CNNQ_EINVAL;
+    CcShape s;
+    if (const int rc = cc_check(g, fmt_x, fmt_w, splits, s)) return rc;
+    const LcPlan p = lc_plan(s.M, s.Cout, s.K, splits);
+    out[0] = p.BM;
+    out[1] = p.BN;
+    out[2] = p.splits;
+    out[3] = cc_v16(s, fmt_x, fmt_w, (uintptr_t)align_bytes, (uintptr_t)align_bytes);
+    out[4] = (int32_t)s.OH;
+    out[5] = (int32_t)s.OW;
+    return 0;
+}
+
+static int cc_tapsums_launch(const uint8_t* wq, int fmt_w, int64_t Cout, int64_t KH, int64_t KW, int64_t Cin, int* taps, void* stream) {
+    hipLaunchKernelGGL(k_cc_tapsums, dim3((unsigned)Cout), dim3(TPB), 0, hs(stream), wq, fmt_w, (int)KH, (int)KW, (int)Cin, taps);
+    return launch_status();
+}
+
+int cnnq_conv_codes_tapsums(const uint8_t* wq, int fmt_w, int64_t Cout, int64_t KH, int64_t KW, int64_t Cin, int32_t* taps, void* stream) {
+    if (!lc_fmt_ok(fmt_w) || Cout < 1 || KH < 1 || KW < 1 || Cin < 1 || Cin % (fmt_w == CNNQ_CODES_U8 ? 4 : 8) || !wq || !taps) return CNNQ_EINVAL;
+    if (misaligned(wq, 4) || misaligned(taps, 4)) return CNNQ_EINVAL;
+    if (Cout >= ((int64_t)1 << 31) || KH > CC_MAX_TAPS || KW > CC_MAX_TAPS || KH * KW > CC_MAX_TAPS || Cin > LC_MAX_K || KH * KW * Cin > LC_MAX_K)
+        return CNNQ_ERANGE;
+    return cc_tapsums_launch(wq, fmt_w, Cout, KH, KW, Cin, taps, stream);
+}
+
+int cnnq_conv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const int64_t g[11], const float* qpx, int64_t Cx,
+                    const float* qpw, const float* bias, const int32_t* taps, int splits, void* ws, size_t ws_bytes, void* stream) {
+    CcShape s;
+    if (const int rc = cc_check(g, fmt_x, fmt_w, splits, s)) return rc;
+    if (!xq || !wq || !y || !qpx || !qpw || !ws || (Cx != 1 && Cx != s.N)) return CNNQ_EINVAL;
+    if (misaligned(xq, 4) || misaligned(wq, 4) || misaligned(y, 4) || misaligned(qpx, 4) || misaligned(qpw, 4) || misaligned(bias, 4) ||
+        misaligned(taps, 4) || misaligned(ws, 16))
+        return CNNQ_EINVAL;
+    const LcPlan p = lc_plan(s.M, s.Cout, s.K, splits);
+    if (ws_bytes < CcWs::bytes(s.pixels, s.M, taps ? 0 : s.ntab, s.Cout, p.splits)) return CNNQ_EINVAL;
+    const CcWs w(ws, s.pixels, s.M, taps ? 0 : s.ntab);
+    CcArgs a;
+    a.xq = xq;
+    a.wq = wq;
+    a.y = y;
+    a.part = w.part;
+    a.M = (int)s.M;
+    a.tilesM = p.tilesM;
+    a.tilesN = p.tilesN;
+    a.splits = p.splits;
+    a.g = CcGeo{(int)s.H, (int)s.W, (int)s.C, (int)s.OW, (int)(s.OH * s.OW), (int)s.KH, (int)s.KW, (int)s.sh, (int)s.sw, (int)s.ph, (int)s.pw};
+    a.e.e.qpx = qpx;
+    a.e.e.qpw = qpw;
+    a.e.e.bias = bias;
+    a.e.e.rx = w.rx;
+    a.e.e.rw = nullptr;
+    a.e.e.Cx = (int)Cx;
+    a.e.e.N = (int)s.Cout;
+    a.e.e.K = (int)s.K;
+    a.e.e.ox = fmt_x == CNNQ_CODES_U8 ? 128 : 0;
+    a.e.e.ow = fmt_w == CNNQ_CODES_U8 ? 128 : 0;
+    a.e.rect = w.rect;
+    a.e.taps = taps ? taps : w.taps;
+    a.e.KW1 = (int)s.KW + 1;
+    a.e.ntab = (int)((s.KH + 1) * (s.KW + 1));
+    a.e.C = (int)s.C;
+    a.e.OHW = a.g.OHW;
+    // the pixels' channel sums (the linear layer's row sums on [N H W][C]), the windows over them, the layer's table unless held
+    if (const int rc = lc_rowsums_launch(xq, fmt_x, s.pixels, nullptr, fmt_w, 0, s.C, w.pix, nullptr, stream)) return rc;
+    hipLaunchKernelGGL(k_cc_winsums, dim3((unsigned)((s.M + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.pix, a.g, a.M, w.rx, w.rect);
+    if (const int rc = launch_status()) return rc;
+    if (!taps)
+        if (const int rc = cc_tapsums_launch(wq, fmt_w, s.Cout, s.KH, s.KW, s.C, w.taps, stream)) return rc;
+    const dim3 grid((unsigned)((int64_t)p.tilesM * p.tilesN * p.splits));
+    with_int<0, 1, 2>(p.tile, [&](auto t) {
+        with_bool(fmt_x == CNNQ_CODES_PACK4, fmt_w == CNNQ_CODES_PACK4, cc_v16(s, fmt_x, fmt_w, (uintptr_t)xq, (uintptr_t)wq), [&](auto px, auto pw, auto v) {
+            constexpr int T = decltype(t)::value;
+            constexpr int WM = T == 0 ? 1 : 2, WN = T == 0 ? 4 : 2, TM = T == 0 ? 1 : T == 1 ? 2 : 4, TN = T == 0 ? 2 : T == 1 ? 2 : 4;
+            constexpr int FX = decltype(px)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, FW = decltype(pw)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8;
+            hipLaunchKernelGGL((k_cc_gemm<WM, WN, TM, TN, FX, FW, decltype(v)::value>), grid, dim3(TPB), 0, hs(stream), a);
+        });
+    });
+    if (const int rc = launch_status()) return rc;
+    if (p.splits == 1) return 0;
+    const long long MN = (long long)s.M * s.Cout;
+    hipLaunchKernelGGL(k_cc_epilogue, dim3((unsigned)((MN + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.part, p.splits, MN, a.e, y);
     return launch_status();
 }
 

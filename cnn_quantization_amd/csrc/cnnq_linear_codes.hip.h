@@ -73,16 +73,19 @@ struct LcArgs {
 };
 
 // S' (signed-domain sum of products) of element (m, n) -> y: exact integers, one fp64 combination, one rounding to fp32
-__device__ __forceinline__ float lc_finish(long long sp, int m, int n, const LcEpi& e) {
-    const long long rx = e.rx[m], rw = e.rw[n];
-    const long long s = sp + e.ow * rx + e.ox * rw - (long long)e.K * e.ox * e.ow;
-    const int mp = e.Cx == 1 ? 0 : m;
+// (lc_combine: the same with the element's code sums rx, rw, its count of codes K and its row mp of qpx given - the convolution of
+// cnnq_conv_codes.hip.h, whose sums run over an output pixel's valid taps, finishes through it too)
+__device__ __forceinline__ float lc_combine(long long sp, long long rx, long long rw, long long K, int mp, int n, const LcEpi& e) {
+    const long long s = sp + e.ow * rx + e.ox * rw - K * e.ox * e.ow;
     const double sx = e.qpx[CNNQ_QP_SCALE * (size_t)e.Cx + mp], zx = e.qpx[CNNQ_QP_ZP * (size_t)e.Cx + mp];
     const double sw = e.qpw[CNNQ_QP_SCALE * (size_t)e.N + n], zw = e.qpw[CNNQ_QP_ZP * (size_t)e.N + n];
-    const double t = (double)s - zw * (double)rx - zx * (double)rw + (double)e.K * (zx * zw);
+    const double t = (double)s - zw * (double)rx - zx * (double)rw + (double)K * (zx * zw);
     double v = (sx * sw) * t;
     if (e.bias) v += (double)e.bias[n];
     return (float)v;
+}
+__device__ __forceinline__ float lc_finish(long long sp, int m, int n, const LcEpi& e) {
+    return lc_combine(sp, e.rx[m], e.rw[n], e.K, e.Cx == 1 ? 0 : m, n, e);
 }
 
 // ---- row sums ---------------------------------------------------------------------------------------------------------------

@@ -2906,3 +2906,72 @@ def linear_codes(xq, wq, qpx, qpw, bias=None, x_format='u8', w_format='u8', rw=N
     L.check(lib.cnnq_linear_codes(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), M, N, K, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias), _ptr(rw),
                                   splits, _ptr(ws), nbytes, st), 'cnnq_linear_codes')
     return y
+
+
+# ------------------------------------------------------------------------------------- the integer convolution on the codes
+def _codes_nhwc(t, fmt, what):
+    """(tensor, format word, channels) of a 4-D code tensor whose last axis is the channels: uint8 [A, B, C, Cin] ('u8') or
+    [A, B, C, Cin / 2] ('pack4'), contiguous, on the current device.  No copy is made here."""
+    if fmt not in _CODE_FORMATS:
+        raise L.CnnqError("%s: format must be 'u8' or 'pack4', got %r" % (what, fmt))
+    t = _dev(t, what, (torch.uint8,))
+    if t.dim() != 4 or t.numel() == 0:
+        raise L.CnnqError('%s must be a non-empty 4-D uint8 tensor of codes, channels last, got shape %s' % (what, tuple(t.shape)))
+    return t, _CODE_FORMATS[fmt], t.shape[3] * (2 if fmt == 'pack4' else 1)
+
+
+def _pair(v, what):
+    v = (v, v) if isinstance(v, int) else tuple(v)
+    if len(v) != 2:
+        raise L.CnnqError('%s must be an int or a pair, got %r' % (what, v))
+    return int(v[0]), int(v[1])
+
+
+def conv_codes_tapsums(wq, w_format='u8'):
+    """The summed-area table of a layer's weight codes wq [Cout, KH, KW, Cin] (cnnq_conv_codes_tapsums): int32
+    [Cout, KH + 1, KW + 1], entry (a, b) the sum of the codes of the taps kh < a, kw < b.  Computed once per layer and handed to
+    conv_codes as `taps`."""
+    wq, fmt, Cin = _codes_nhwc(wq, w_format, 'wq')
+    Cout, KH, KW = wq.shape[:3]
+    taps = torch.empty((Cout, KH + 1, KW + 1), dtype=torch.int32, device=wq.device)
+    L.check(L.load().cnnq_conv_codes_tapsums(_ptr(wq), fmt, Cout, KH, KW, Cin, _ptr(taps), _stream(wq)), 'cnnq_conv_codes_tapsums')
+    return taps
+
+
+def conv_codes(xq, wq, qpx, qpw, bias=None, stride=1, padding=0, x_format='u8', w_format='u8', taps=None, out=None, splits=0):
+    """The 2-D convolution on the stored codes (cnnq_conv_codes): NHWC activation codes xq [N, H, W, Cin] with
+    the table qpx [NQP, 1] (per tensor) or [NQP, N] (per image), OHWI weight codes wq [Cout, KH, KW, Cin] - the bytes of a
+    channels_last weight - with qpw [NQP, Cout], each operand 'u8' or 'pack4' (last axis Cin / 2, the even channel in the low nibble)
+    -> the zero-padded convolution of the decoded operands + bias as float32 [N, Cout, OH, OW] with channels_last strides: integer
+    dot products over each output pixel's valid taps on the gfx950 int8 matrix instructions, combined in fp64 and rounded once.
+    stride, padding: an int or (h, w); dilation and groups are 1.  taps: conv_codes_tapsums(wq, w_format), held by the caller
+    (None: computed per call); out: a float32 [N, Cout, OH, OW] channels_last tensor; splits as in linear_codes.  On the stream
+    of xq; no host synchronisation."""
+    lib = L.load()
+    xq, fx, Cin = _codes_nhwc(xq, x_format, 'xq')
+    wq, fw, Cw = _codes_nhwc(wq, w_format, 'wq')
+    if Cw != Cin or wq.device != xq.device:
+        raise L.CnnqError('conv_codes: xq has Cin = %d on %s, wq has Cin = %d on %s' % (Cin, xq.device, Cw, wq.device))
+    (N, H, W), (Cout, KH, KW) = xq.shape[:3], wq.shape[:3]
+    g = (ctypes.c_int64 * 11)(N, H, W, Cin, Cout, KH, KW, *_pair(stride, 'stride'), *_pair(padding, 'padding'))
+    splits = int(splits)
+    route = (ctypes.c_int32 * 6)()
+    L.check(lib.cnnq_conv_codes_route(g, fx, fw, splits, 4, route), 'cnnq_conv_codes_route')
+    OH, OW = route[4], route[5]
+    qpx = _lc_table(qpx, 'qpx', torch.float32, ((L.NQP, 1), (L.NQP, N)), xq.device)
+    qpw = _lc_table(qpw, 'qpw', torch.float32, ((L.NQP, Cout),), xq.device)
+    if bias is not None:
+        bias = _lc_table(bias, 'bias', torch.float32, ((Cout,),), xq.device)
+    if taps is not None:
+        taps = _lc_table(taps, 'taps', torch.int32, ((Cout, KH + 1, KW + 1),), xq.device)
+    if out is None:
+        y = torch.empty((N, OH, OW, Cout), dtype=torch.float32, device=xq.device)
+    else:       # the caller's [N, Cout, OH, OW] channels_last tensor: its storage is [N, OH, OW, Cout]
+        y = _lc_table(out.permute(0, 2, 3, 1) if isinstance(out, torch.Tensor) and out.dim() == 4 else out, 'out (seen as NHWC)',
+                      torch.float32, ((N, OH, OW, Cout),), xq.device)
+    nbytes = lib.cnnq_conv_codes_workspace(g, fx, fw, int(taps is not None), splits)
+    st = _raw_stream(xq.device.index)
+    ws = _scratch(xq, 'conv_codes', nbytes, st)
+    L.check(lib.cnnq_conv_codes(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), g, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias), _ptr(taps), splits,
+                                _ptr(ws), nbytes, st), 'cnnq_conv_codes')
+    return y.permute(0, 3, 1, 2)

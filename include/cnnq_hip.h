@@ -1287,6 +1287,44 @@ int cnnq_linear_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w
                       const float* qpx, int64_t Cx, const float* qpw, const float* bias, const int32_t* rw, int splits, void* ws,
                       size_t ws_bytes, void* stream);
 
+/* The integer 2-D convolution ON the stored codes: the reference's default granularity - activations per
+ * tensor (or per image), weights per output channel - as an implicit GEMM on the same int8 matrix instructions, rows M = N OH OW,
+ * columns Cout, k = (kh, kw, c).  A padded tap is the real value 0.0, not a code, so every sum runs over the VALID taps of output
+ * pixel m - a rectangle kh0 <= kh < kh1, kw0 <= kw < kw1 that depends on (oh, ow) alone:
+ *
+ *   y[m][n] = sx[m'] sw[n] (S - zw[n] Rx[m] - zx[m'] RwV[m][n] + Kv[m] zx[m'] zw[n]) + bias[n],   m' = image of m (Cx == N) or 0
+ *   S = sum_valid xq wq,  Rx[m] = sum_valid xq,  RwV[m][n] = sum over the valid taps and all channels of wq[n],  Kv[m] = C * #valid taps
+ *
+ * exact integers combined in fp64 and rounded ONCE to fp32 as in cnnq_linear_codes; the same bits for every split count.  A 1 x 1,
+ * stride-1, unpadded call returns the bits of cnnq_linear_codes on the same bytes seen as [M][C].
+ *
+ * Geometry.  g = {N, H, W, C, Cout, KH, KW, sh, sw, ph, pw}: stride >= 1 and zero padding >= 0 per axis, dilation 1, groups 1;
+ * OH = (H + 2 ph - KH) / sh + 1, OW likewise.  Operands.  xq: NHWC codes, [N][H][W][C] bytes (u8) or [N][H][W][C / 2] (pack4, the
+ * even channel in the low nibble), pixels back to back; qpx[CNNQ_NQP][Cx], Cx = 1 or N.  wq: OHWI codes [Cout][KH][KW][C] (C / 2)
+ * - the bytes of a channels_last weight - with qpw[CNNQ_NQP][Cout].  C % 4 == 0, C % 8 == 0 with a pack4 operand (C % 16 == 0 and
+ * 16-byte aligned bases - 8 for pack4 - take the 16-byte loads); K = KH KW C <= 131071; KH KW <= 64; M Cout < 2^31.  y: fp32
+ * [N][OH][OW][Cout], i.e. the channels_last storage of [N][Cout][OH][OW]; bias[Cout] fp32 or NULL.
+ *
+ * cnnq_conv_codes_workspace: bytes of `ws` - int32 pixel sums [N H W], Rx[M], the packed rectangles [M], the tap table unless
+ *   have_taps, and beyond one split the int32 partial tiles [splits][M][Cout], each piece rounded up to 16 bytes.  0 on a geometry
+ *   cnnq_conv_codes refuses.
+ * cnnq_conv_codes_route (host only, nothing enqueued): out = {rows of the macro tile, its columns, splits of k, 1 - 16-byte loads /
+ *   0 - the dword path, OH, OW}; align_bytes as in cnnq_linear_codes_route.
+ * cnnq_conv_codes_tapsums: taps[Cout][KH + 1][KW + 1], the summed-area table of the layer's tap sums (entry (a, b): the codes of
+ *   the taps kh < a, kw < b), one launch - computed once per layer and handed to every later cnnq_conv_codes as `taps`.
+ * cnnq_conv_codes: the pixel-sum launch, the window launch (Rx and the rectangles), the table launch unless taps is given, the tile
+ *   launch, and - splits > 1 - the launch that adds the splits and finishes.  splits, ws: as in cnnq_linear_codes.
+ * All return CNNQ_EINVAL before anything touches the device for what cnnq_linear_codes refuses so, a size below 1, a stride below 1,
+ * a negative padding, a kernel larger than the padded image (no output pixel), C not a multiple of 4 (8 with pack4), Cx not 1 or N;
+ * CNNQ_ERANGE for K > 131071, KH KW > 64, any size or N H W of 2^31 and more, 2^31 outputs.  Re-entrant, allocate nothing, no
+ * atomics, no host synchronisation, graph-capturable. */
+size_t cnnq_conv_codes_workspace(const int64_t g[11], int fmt_x, int fmt_w, int have_taps, int splits);
+int cnnq_conv_codes_route(const int64_t g[11], int fmt_x, int fmt_w, int splits, int align_bytes, int32_t out[6]);
+int cnnq_conv_codes_tapsums(const uint8_t* wq, int fmt_w, int64_t Cout, int64_t KH, int64_t KW, int64_t Cin, int32_t* taps, void* stream);
+int cnnq_conv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const int64_t g[11], const float* qpx,
+                    int64_t Cx, const float* qpw, const float* bias, const int32_t* taps, int splits, void* ws, size_t ws_bytes,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
