@@ -18,6 +18,7 @@
 //   k_cc_winsums   one thread per output pixel: its valid rectangle, packed into a word, and Rx = the valid pixels' sums.
 //   k_cc_gemm      the tiles of S'; k_lc_gemm's schedule with a gathered A operand (below); with one split its tail finishes.
 //   k_cc_epilogue  splits > 1: adds the splits' int32 partial tiles, then the same cc_finish - the same bits for every split count.
+// The Q instances of k_cc_gemm and k_cc_epilogue_q store NHWC codes instead of fp32, as the linear layer's: cnnq_requant_codes.hip.h.
 //
 // The A path.  The rows a thread fetches are the same for every step of a tile: they are decomposed into (image, oh, ow) and the
 // window origin ih0 = oh sh - ph, iw0 = ow sw - pw ONCE, before the k loop (rows beyond M get an origin no tap of which is inside
@@ -55,6 +56,7 @@ struct CcArgs {
     int M, tilesM, tilesN, splits;
     CcGeo g;
     CcEpi e;
+    RqOut q;                // Q instances: the codes' destination instead of y (cnnq_requant_codes.hip.h)
 };
 
 // the valid taps of the window whose origin is (ih0, iw0): kh0 <= kh1, kw0 <= kw1 (an empty rectangle where no tap is inside)
@@ -189,7 +191,8 @@ __device__ __forceinline__ void cc_fetch(const unsigned char* __restrict__ xq, c
 }
 
 // ---- the tiles ------------------------------------------------------------------------------------------------------------------
-template <int WM, int WN, int TM, int TN, int FX, int FW, bool V16>
+// Q: with one split the tail stores codes (a.q) instead of fp32 (a.y): section 37
+template <int WM, int WN, int TM, int TN, int FX, int FW, bool V16, bool Q = false>
 __global__ __launch_bounds__(TPB) void k_cc_gemm(const CcArgs a) {
     static_assert(WM * WN == TPB / 64, "four waves");
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
@@ -292,6 +295,37 @@ __global__ __launch_bounds__(TPB) void k_cc_gemm(const CcArgs a) {
 
     // the lane's results: rows 4 (lane / 16) + r, column lane % 16 of every instruction tile
     int* part = a.splits > 1 ? a.part + (size_t)split * M * N : nullptr;
+    if constexpr (Q) {
+        if (!part) {                                                 // uniform: quantize, stage through the free operand buffers, store
+            unsigned* tile = reinterpret_cast<unsigned*>(&lds[0][0]);
+            static_assert(BM * RqTile<BN>::P * 4 <= (int)sizeof(lds), "the codes of the tile fit the operand buffers");
+            unsigned cd[TM][TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+#pragma unroll
+                for (int j = 0; j < TN; ++j) cd[i][j] = 0u;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int m = m0 + (wm * TM + i) * 16 + fc * 4 + r;
+                    if (m >= M) continue;
+                    const CcRow row = cc_row(m, a.e);
+                    const RqRow qrow = rq_row(a.q, a.q.Cy == 1 ? 0 : m / a.e.OHW);
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const int n = n0 + (wn * TN + j) * 16 + fr;
+                        if (n < N) cd[i][j] |= rq_code(cc_finish(acc[i][j][r], row, n, a.e), a.q, qrow) << (8 * r);
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) rq_stage<BN>(tile, (wm * TM + i) * 16, (wn * TN + j) * 16, lane, cd[i][j]);
+            __syncthreads();
+            rq_store_tile<BM, BN>(tile, a.q, m0, n0, M, N);
+            return;
+        }
+    }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -317,6 +351,27 @@ __global__ __launch_bounds__(TPB) void k_cc_epilogue(const int* __restrict__ par
     long long s = 0;
     for (int i = 0; i < splits; ++i) s += part[(size_t)i * MN + idx];
     y[idx] = cc_finish(s, cc_row((int)(idx / e.e.N), e), (int)(idx % e.e.N), e);
+}
+
+// ... to codes: thread idx owns dword idx of y, 4 (u8) or 8 (pack4) consecutive channels of one output pixel
+template <int FY>
+__global__ __launch_bounds__(TPB) void k_cc_epilogue_q(const int* __restrict__ part, int splits, long long MN, const CcEpi e, const RqOut o) {
+    constexpr int CPD = FY == CNNQ_CODES_U8 ? 4 : 8;
+    const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (idx >= MN / CPD) return;
+    const long long at = idx * CPD;
+    const int m = (int)(at / e.e.N), n = (int)(at % e.e.N);
+    const CcRow row = cc_row(m, e);
+    const RqRow qrow = rq_row(o, o.Cy == 1 ? 0 : m / e.OHW);
+    unsigned w = 0u;
+#pragma unroll
+    for (int c = 0; c < CPD; c += 4) {
+        long long s[4];
+        rq_add_splits(part, splits, MN, at + c, s);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w |= rq_code(cc_finish(s[k], row, n + c + k, e), o, qrow) << ((c + k) * (32 / CPD));
+    }
+    reinterpret_cast<unsigned*>(o.y)[idx] = w;
 }
 
 // ---- the workspace (host) -----------------------------------------------------------------------------------------------------------

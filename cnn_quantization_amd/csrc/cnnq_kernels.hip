@@ -3118,12 +3118,24 @@ int cnnq_linear_codes_rowsums(const uint8_t* codes, int fmt, int64_t rows, int64
     return lc_rowsums_launch(nullptr, fmt, 0, codes, fmt, rows, K, nullptr, sums, stream);
 }
 
-int cnnq_linear_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, int64_t M, int64_t N, int64_t K, const float* qpx,
-                      int64_t Cx, const float* qpw, const float* bias, const int32_t* rw, int splits, void* ws, size_t ws_bytes, void* stream) {
-    if (const int rc = lc_check(M, N, K, fmt_x, fmt_w, splits)) return rc;
-    if (!xq || !wq || !y || !qpx || !qpw || !ws || (Cx != 1 && Cx != M)) return CNNQ_EINVAL;
-    if (misaligned(xq, 4) || misaligned(wq, 4) || misaligned(y, 4) || misaligned(qpx, 4) || misaligned(qpw, 4) || misaligned(bias, 4) ||
-        misaligned(rw, 4) || misaligned(ws, 16))
+// the requantizing entries' own arguments (section 37): the output format, its rows of whole dwords, the table per tensor or per
+// row / image (`per`), the pointers
+static int rq_check(int fy, int64_t N, const void* y, const float* qpy, int64_t Cy, int64_t per) {
+    if (!lc_fmt_ok(fy) || N % (fy == CNNQ_CODES_U8 ? 4 : 8) || (Cy != 1 && Cy != per)) return CNNQ_EINVAL;
+    return !y || !qpy || misaligned(y, 4) || misaligned(qpy, 4) ? CNNQ_EINVAL : 0;
+}
+static RqOut rq_out(uint8_t* y, int fy, int64_t N, const float* qpy, int64_t Cy, int relu) {
+    const int64_t rowbytes = fy == CNNQ_CODES_U8 ? N : N / 2;
+    return RqOut{y, qpy, (int)Cy, fy, relu != 0, rowbytes % 16 == 0 && (uintptr_t)y % 16 == 0};
+}
+
+// the body of cnnq_linear_codes (q.y == NULL: fp32 into y) and cnnq_linear_codes_q (codes into q.y); the output is checked
+static int lc_run(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const RqOut& q, int64_t M, int64_t N, int64_t K,
+                  const float* qpx, int64_t Cx, const float* qpw, const float* bias, const int32_t* rw, int splits, void* ws, size_t ws_bytes,
+                  void* stream) {
+    if (!xq || !wq || !qpx || !qpw || !ws || (Cx != 1 && Cx != M)) return CNNQ_EINVAL;
+    if (misaligned(xq, 4) || misaligned(wq, 4) || misaligned(qpx, 4) || misaligned(qpw, 4) || misaligned(bias, 4) || misaligned(rw, 4) ||
+        misaligned(ws, 16))
         return CNNQ_EINVAL;
     const LcPlan p = lc_plan(M, N, K, splits);
     if (ws_bytes < LcWs::bytes(M, N, p.splits)) return CNNQ_EINVAL;
@@ -3148,20 +3160,62 @@ int cnnq_linear_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w
     a.e.K = (int)K;
     a.e.ox = fmt_x == CNNQ_CODES_U8 ? 128 : 0;
     a.e.ow = fmt_w == CNNQ_CODES_U8 ? 128 : 0;
+    a.q = q;
     const dim3 grid((unsigned)((int64_t)p.tilesM * p.tilesN * p.splits));
     with_int<0, 1, 2>(p.tile, [&](auto t) {
         with_bool(fmt_x == CNNQ_CODES_PACK4, fmt_w == CNNQ_CODES_PACK4, lc_v16(K, fmt_x, fmt_w, (uintptr_t)xq, (uintptr_t)wq), [&](auto px, auto pw, auto v) {
-            constexpr int T = decltype(t)::value;
-            constexpr int WM = T == 0 ? 1 : 2, WN = T == 0 ? 4 : 2, TM = T == 0 ? 1 : T == 1 ? 2 : 4, TN = T == 0 ? 2 : T == 1 ? 2 : 4;
-            constexpr int FX = decltype(px)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, FW = decltype(pw)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8;
-            hipLaunchKernelGGL((k_lc_gemm<WM, WN, TM, TN, FX, FW, decltype(v)::value>), grid, dim3(TPB), 0, hs(stream), a);
+            with_bool(q.y != nullptr, [&](auto oq) {
+                constexpr int T = decltype(t)::value;
+                constexpr int WM = T == 0 ? 1 : 2, WN = T == 0 ? 4 : 2, TM = T == 0 ? 1 : T == 1 ? 2 : 4, TN = T == 0 ? 2 : T == 1 ? 2 : 4;
+                constexpr int FX = decltype(px)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, FW = decltype(pw)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8;
+                hipLaunchKernelGGL((k_lc_gemm<WM, WN, TM, TN, FX, FW, decltype(v)::value, decltype(oq)::value>), grid, dim3(TPB), 0, hs(stream), a);
+            });
         });
     });
     if (const int rc = launch_status()) return rc;
     if (p.splits == 1) return 0;
     const long long MN = (long long)M * N;
-    hipLaunchKernelGGL(k_lc_epilogue, dim3((unsigned)((MN + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.part, p.splits, MN, a.e, y);
+    if (!q.y) {
+        hipLaunchKernelGGL(k_lc_epilogue, dim3((unsigned)((MN + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.part, p.splits, MN, a.e, y);
+    } else {        // a thread per dword of codes
+        const long long ndw = MN / (q.fy == CNNQ_CODES_U8 ? 4 : 8);
+        with_bool(q.fy == CNNQ_CODES_PACK4, [&](auto p4) {
+            hipLaunchKernelGGL((k_lc_epilogue_q<decltype(p4)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8>), dim3((unsigned)((ndw + TPB - 1) / TPB)), dim3(TPB), 0,
+                               hs(stream), w.part, p.splits, MN, a.e, q);
+        });
+    }
     return launch_status();
+}
+
+int cnnq_linear_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, int64_t M, int64_t N, int64_t K, const float* qpx,
+                      int64_t Cx, const float* qpw, const float* bias, const int32_t* rw, int splits, void* ws, size_t ws_bytes, void* stream) {
+    if (const int rc = lc_check(M, N, K, fmt_x, fmt_w, splits)) return rc;
+    if (!y || misaligned(y, 4)) return CNNQ_EINVAL;
+    return lc_run(xq, fmt_x, wq, fmt_w, y, RqOut{}, M, N, K, qpx, Cx, qpw, bias, rw, splits, ws, ws_bytes, stream);
+}
+
+// ---- ... writing codes (cnnq_requant_codes.hip.h): the same contraction, ReLU, the output table, u8 / pack4 ----
+size_t cnnq_linear_codes_q_workspace(int64_t M, int64_t N, int64_t K, int fmt_x, int fmt_w, int fmt_y, int splits) {
+    if (!lc_fmt_ok(fmt_y) || N % (fmt_y == CNNQ_CODES_U8 ? 4 : 8)) return 0;
+    return cnnq_linear_codes_workspace(M, N, K, fmt_x, fmt_w, splits);
+}
+
+// out: cnnq_linear_codes_route's four, then 1 - 16-byte stores / 0 - dword stores of the codes.  No shape is sent away: DESIGN.md
+// section 37 for what was measured
+int cnnq_linear_codes_q_route(int64_t M, int64_t N, int64_t K, int fmt_x, int fmt_w, int fmt_y, int splits, int align_bytes, int32_t out[5]) {
+    if (!out) return CNNQ_EINVAL;
+    if (const int rc = cnnq_linear_codes_route(M, N, K, fmt_x, fmt_w, splits, align_bytes, out)) return rc;
+    if (!lc_fmt_ok(fmt_y) || N % (fmt_y == CNNQ_CODES_U8 ? 4 : 8)) return CNNQ_EINVAL;
+    out[4] = rq_out(reinterpret_cast<uint8_t*>((uintptr_t)align_bytes), fmt_y, N, nullptr, 1, 0).wide;
+    return 0;
+}
+
+int cnnq_linear_codes_q(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, uint8_t* y, int fmt_y, int64_t M, int64_t N, int64_t K,
+                        const float* qpx, int64_t Cx, const float* qpw, const float* bias, const float* qpy, int64_t Cy, int relu,
+                        const int32_t* rw, int splits, void* ws, size_t ws_bytes, void* stream) {
+    if (const int rc = lc_check(M, N, K, fmt_x, fmt_w, splits)) return rc;
+    if (const int rc = rq_check(fmt_y, N, y, qpy, Cy, M)) return rc;
+    return lc_run(xq, fmt_x, wq, fmt_w, nullptr, rq_out(y, fmt_y, N, qpy, Cy, relu), M, N, K, qpx, Cx, qpw, bias, rw, splits, ws, ws_bytes, stream);
 }
 
 // ---- the integer convolution on the stored codes (cnnq_conv_codes.hip.h): y [N][OH][OW][Cout] from NHWC xq and OHWI wq ------------------
@@ -3229,13 +3283,12 @@ int cnnq_conv_codes_tapsums(const uint8_t* wq, int fmt_w, int64_t Cout, int64_t 
     return cc_tapsums_launch(wq, fmt_w, Cout, KH, KW, Cin, taps, stream);
 }
 
-int cnnq_conv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const int64_t g[11], const float* qpx, int64_t Cx,
-                    const float* qpw, const float* bias, const int32_t* taps, int splits, void* ws, size_t ws_bytes, void* stream) {
-    CcShape s;
-    if (const int rc = cc_check(g, fmt_x, fmt_w, splits, s)) return rc;
-    if (!xq || !wq || !y || !qpx || !qpw || !ws || (Cx != 1 && Cx != s.N)) return CNNQ_EINVAL;
-    if (misaligned(xq, 4) || misaligned(wq, 4) || misaligned(y, 4) || misaligned(qpx, 4) || misaligned(qpw, 4) || misaligned(bias, 4) ||
-        misaligned(taps, 4) || misaligned(ws, 16))
+// the body of cnnq_conv_codes (q.y == NULL: fp32 into y) and cnnq_conv_codes_q (codes into q.y); the output is checked
+static int cc_run(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const RqOut& q, const CcShape& s, const float* qpx,
+                  int64_t Cx, const float* qpw, const float* bias, const int32_t* taps, int splits, void* ws, size_t ws_bytes, void* stream) {
+    if (!xq || !wq || !qpx || !qpw || !ws || (Cx != 1 && Cx != s.N)) return CNNQ_EINVAL;
+    if (misaligned(xq, 4) || misaligned(wq, 4) || misaligned(qpx, 4) || misaligned(qpw, 4) || misaligned(bias, 4) || misaligned(taps, 4) ||
+        misaligned(ws, 16))
         return CNNQ_EINVAL;
     const LcPlan p = lc_plan(s.M, s.Cout, s.K, splits);
     if (ws_bytes < CcWs::bytes(s.pixels, s.M, taps ? 0 : s.ntab, s.Cout, p.splits)) return CNNQ_EINVAL;
@@ -3266,6 +3319,7 @@ int cnnq_conv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, 
     a.e.ntab = (int)((s.KH + 1) * (s.KW + 1));
     a.e.C = (int)s.C;
     a.e.OHW = a.g.OHW;
+    a.q = q;
     // the pixels' channel sums (the linear layer's row sums on [N H W][C]), the windows over them, the layer's table unless held
     if (const int rc = lc_rowsums_launch(xq, fmt_x, s.pixels, nullptr, fmt_w, 0, s.C, w.pix, nullptr, stream)) return rc;
     hipLaunchKernelGGL(k_cc_winsums, dim3((unsigned)((s.M + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.pix, a.g, a.M, w.rx, w.rect);
@@ -3275,17 +3329,59 @@ int cnnq_conv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, 
     const dim3 grid((unsigned)((int64_t)p.tilesM * p.tilesN * p.splits));
     with_int<0, 1, 2>(p.tile, [&](auto t) {
         with_bool(fmt_x == CNNQ_CODES_PACK4, fmt_w == CNNQ_CODES_PACK4, cc_v16(s, fmt_x, fmt_w, (uintptr_t)xq, (uintptr_t)wq), [&](auto px, auto pw, auto v) {
-            constexpr int T = decltype(t)::value;
-            constexpr int WM = T == 0 ? 1 : 2, WN = T == 0 ? 4 : 2, TM = T == 0 ? 1 : T == 1 ? 2 : 4, TN = T == 0 ? 2 : T == 1 ? 2 : 4;
-            constexpr int FX = decltype(px)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, FW = decltype(pw)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8;
-            hipLaunchKernelGGL((k_cc_gemm<WM, WN, TM, TN, FX, FW, decltype(v)::value>), grid, dim3(TPB), 0, hs(stream), a);
+            with_bool(q.y != nullptr, [&](auto oq) {
+                constexpr int T = decltype(t)::value;
+                constexpr int WM = T == 0 ? 1 : 2, WN = T == 0 ? 4 : 2, TM = T == 0 ? 1 : T == 1 ? 2 : 4, TN = T == 0 ? 2 : T == 1 ? 2 : 4;
+                constexpr int FX = decltype(px)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, FW = decltype(pw)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8;
+                hipLaunchKernelGGL((k_cc_gemm<WM, WN, TM, TN, FX, FW, decltype(v)::value, decltype(oq)::value>), grid, dim3(TPB), 0, hs(stream), a);
+            });
         });
     });
     if (const int rc = launch_status()) return rc;
     if (p.splits == 1) return 0;
     const long long MN = (long long)s.M * s.Cout;
-    hipLaunchKernelGGL(k_cc_epilogue, dim3((unsigned)((MN + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.part, p.splits, MN, a.e, y);
+    if (!q.y) {
+        hipLaunchKernelGGL(k_cc_epilogue, dim3((unsigned)((MN + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.part, p.splits, MN, a.e, y);
+    } else {        // a thread per dword of codes
+        const long long ndw = MN / (q.fy == CNNQ_CODES_U8 ? 4 : 8);
+        with_bool(q.fy == CNNQ_CODES_PACK4, [&](auto p4) {
+            hipLaunchKernelGGL((k_cc_epilogue_q<decltype(p4)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8>), dim3((unsigned)((ndw + TPB - 1) / TPB)), dim3(TPB), 0,
+                               hs(stream), w.part, p.splits, MN, a.e, q);
+        });
+    }
     return launch_status();
+}
+
+int cnnq_conv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const int64_t g[11], const float* qpx, int64_t Cx,
+                    const float* qpw, const float* bias, const int32_t* taps, int splits, void* ws, size_t ws_bytes, void* stream) {
+    CcShape s;
+    if (const int rc = cc_check(g, fmt_x, fmt_w, splits, s)) return rc;
+    if (!y || misaligned(y, 4)) return CNNQ_EINVAL;
+    return cc_run(xq, fmt_x, wq, fmt_w, y, RqOut{}, s, qpx, Cx, qpw, bias, taps, splits, ws, ws_bytes, stream);
+}
+
+// ---- ... writing NHWC codes (cnnq_requant_codes.hip.h) ---------------------------------------------------------
+size_t cnnq_conv_codes_q_workspace(const int64_t g[11], int fmt_x, int fmt_w, int fmt_y, int have_taps, int splits) {
+    if (!g || !lc_fmt_ok(fmt_y) || g[4] % (fmt_y == CNNQ_CODES_U8 ? 4 : 8)) return 0;
+    return cnnq_conv_codes_workspace(g, fmt_x, fmt_w, have_taps, splits);
+}
+
+// out: cnnq_conv_codes_route's six, then 1 - 16-byte stores / 0 - dword stores of the codes
+int cnnq_conv_codes_q_route(const int64_t g[11], int fmt_x, int fmt_w, int fmt_y, int splits, int align_bytes, int32_t out[7]) {
+    if (!out) return CNNQ_EINVAL;
+    if (const int rc = cnnq_conv_codes_route(g, fmt_x, fmt_w, splits, align_bytes, out)) return rc;
+    if (!lc_fmt_ok(fmt_y) || g[4] % (fmt_y == CNNQ_CODES_U8 ? 4 : 8)) return CNNQ_EINVAL;
+    out[6] = rq_out(reinterpret_cast<uint8_t*>((uintptr_t)align_bytes), fmt_y, g[4], nullptr, 1, 0).wide;
+    return 0;
+}
+
+int cnnq_conv_codes_q(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, uint8_t* y, int fmt_y, const int64_t g[11], const float* qpx,
+                      int64_t Cx, const float* qpw, const float* bias, const float* qpy, int64_t Cy, int relu, const int32_t* taps, int splits,
+                      void* ws, size_t ws_bytes, void* stream) {
+    CcShape s;
+    if (const int rc = cc_check(g, fmt_x, fmt_w, splits, s)) return rc;
+    if (const int rc = rq_check(fmt_y, s.Cout, y, qpy, Cy, s.N)) return rc;
+    return cc_run(xq, fmt_x, wq, fmt_w, nullptr, rq_out(y, fmt_y, s.Cout, qpy, Cy, relu), s, qpx, Cx, qpw, bias, taps, splits, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -19,6 +19,8 @@
 //   k_lc_gemm      the tiles of S' (below); with one split its tail is the epilogue.
 //   k_lc_epilogue  splits > 1: adds the splits' int32 partial tiles (integer addition: the same bits for every split count), then
 //                  the same lc_finish.
+// The Q instances of k_lc_gemm and k_lc_epilogue_q store codes instead of fp32 - ReLU and the output table's quantizer behind the same
+// lc_finish: cnnq_requant_codes.hip.h.
 //
 // k_lc_gemm.  A workgroup of four waves (WM x WN) owns a BM x BN macro tile of y and one split of the k range; a wave owns TM x TN
 // instruction tiles of 16 x 16 whose int32 accumulators (four per lane and tile) stay in registers over all its k steps.  A step is
@@ -44,6 +46,7 @@
 //     element of every split written (a split without steps writes zeros): no initialisation, no atomics.
 #pragma once
 #include "cnnq_common.hip.h"
+#include "cnnq_requant_codes.hip.h"
 
 namespace {
 
@@ -70,6 +73,7 @@ struct LcArgs {
     int* part;            // [splits][M][N], splits > 1
     int M, tilesM, tilesN, splits;
     LcEpi e;
+    RqOut q;              // Q instances: the codes' destination instead of y (cnnq_requant_codes.hip.h)
 };
 
 // S' (signed-domain sum of products) of element (m, n) -> y: exact integers, one fp64 combination, one rounding to fp32
@@ -177,7 +181,8 @@ __device__ __forceinline__ lc_u4 lc_signed(const LcRaw<FMT>& r) {
 __device__ __forceinline__ int lc_slot(int r, int kc) { return r * 4 + (kc ^ ((r >> 2) & 3)); }
 
 // ---- the tiles ------------------------------------------------------------------------------------------------------------------
-template <int WM, int WN, int TM, int TN, int FX, int FW, bool V16>
+// Q: with one split the tail stores codes (a.q) instead of fp32 (a.y): section 37
+template <int WM, int WN, int TM, int TN, int FX, int FW, bool V16, bool Q = false>
 __global__ __launch_bounds__(TPB) void k_lc_gemm(const LcArgs a) {
     static_assert(WM * WN == TPB / 64, "four waves");
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
@@ -255,6 +260,36 @@ __global__ __launch_bounds__(TPB) void k_lc_gemm(const LcArgs a) {
 
     // the lane's results: rows 4 (lane / 16) + r, column lane % 16 of every instruction tile
     int* part = a.splits > 1 ? a.part + (size_t)split * M * N : nullptr;
+    if constexpr (Q) {
+        if (!part) {                                                 // uniform: quantize, stage through the free operand buffers, store
+            unsigned* tile = reinterpret_cast<unsigned*>(&lds[0][0]);
+            static_assert(BM * RqTile<BN>::P * 4 <= (int)sizeof(lds), "the codes of the tile fit the operand buffers");
+            unsigned cd[TM][TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+#pragma unroll
+                for (int j = 0; j < TN; ++j) cd[i][j] = 0u;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int m = m0 + (wm * TM + i) * 16 + fc * 4 + r;
+                    if (m >= M) continue;
+                    const RqRow row = rq_row(a.q, m);
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const int n = n0 + (wn * TN + j) * 16 + fr;
+                        if (n < N) cd[i][j] |= rq_code(lc_finish(acc[i][j][r], m, n, a.e), a.q, row) << (8 * r);
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) rq_stage<BN>(tile, (wm * TM + i) * 16, (wn * TN + j) * 16, lane, cd[i][j]);
+            __syncthreads();
+            rq_store_tile<BM, BN>(tile, a.q, m0, n0, M, N);
+            return;
+        }
+    }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int n = n0 + (wn * TN + j) * 16 + fr;
@@ -279,6 +314,26 @@ __global__ __launch_bounds__(TPB) void k_lc_epilogue(const int* __restrict__ par
     long long s = 0;
     for (int i = 0; i < splits; ++i) s += part[(size_t)i * MN + idx];
     y[idx] = lc_finish(s, (int)(idx / e.N), (int)(idx % e.N), e);
+}
+
+// ... to codes: thread idx owns dword idx of y, 4 (u8) or 8 (pack4) consecutive n of one row
+template <int FY>
+__global__ __launch_bounds__(TPB) void k_lc_epilogue_q(const int* __restrict__ part, int splits, long long MN, const LcEpi e, const RqOut o) {
+    constexpr int CPD = FY == CNNQ_CODES_U8 ? 4 : 8;
+    const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (idx >= MN / CPD) return;
+    const long long at = idx * CPD;
+    const int m = (int)(at / e.N), n = (int)(at % e.N);
+    const RqRow row = rq_row(o, m);
+    unsigned w = 0u;
+#pragma unroll
+    for (int c = 0; c < CPD; c += 4) {
+        long long s[4];
+        rq_add_splits(part, splits, MN, at + c, s);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w |= rq_code(lc_finish(s[k], m, n + c + k, e), o, row) << ((c + k) * (32 / CPD));
+    }
+    reinterpret_cast<unsigned*>(o.y)[idx] = w;
 }
 
 // ---- the plan (host) ----------------------------------------------------------------------------------------------------------------

@@ -2879,6 +2879,49 @@ def linear_codes_rowsums(wq, w_format='u8'):
     return sums
 
 
+def _codes_out(what, out, shape, fy, N, device):
+    """The uint8 code tensor a *_codes_q call writes: `shape` with its last axis N ('u8') or N / 2 ('pack4')."""
+    if fy not in _CODE_FORMATS:
+        raise L.CnnqError("%s: y_format must be 'u8' or 'pack4', got %r" % (what, fy))
+    if N % (8 if fy == 'pack4' else 4):
+        raise L.CnnqError('%s: %d output columns are not whole dwords of %s codes' % (what, N, fy))
+    shape = tuple(shape) + (N // 2 if fy == 'pack4' else N,)
+    return torch.empty(shape, dtype=torch.uint8, device=device) if out is None else _lc_table(out, 'out', torch.uint8, (shape,), device)
+
+
+def _linear_codes(what, xq, wq, qpx, qpw, bias, x_format, w_format, rw, out, splits, q=None):
+    """linear_codes (q None) and linear_codes_q (q = (qpy, relu, y_format)): one front, one call each."""
+    lib = L.load()
+    xq, fx, M, K = _codes(xq, x_format, 'xq')
+    wq, fw, N, Kw = _codes(wq, w_format, 'wq')
+    if Kw != K or wq.device != xq.device:
+        raise L.CnnqError('%s: xq has K = %d on %s, wq has K = %d on %s' % (what, K, xq.device, Kw, wq.device))
+    qpx = _lc_table(qpx, 'qpx', torch.float32, ((L.NQP, 1), (L.NQP, M)), xq.device)
+    qpw = _lc_table(qpw, 'qpw', torch.float32, ((L.NQP, N),), xq.device)
+    if bias is not None:
+        bias = _lc_table(bias, 'bias', torch.float32, ((N,),), xq.device)
+    if rw is not None:
+        rw = _lc_table(rw, 'rw', torch.int32, ((N,),), xq.device)
+    if q is None:
+        y = torch.empty((M, N), dtype=torch.float32, device=xq.device) if out is None else _lc_table(out, 'out', torch.float32, ((M, N),), xq.device)
+    else:
+        qpy = _lc_table(q[0], 'qpy', torch.float32, ((L.NQP, 1), (L.NQP, M)), xq.device)
+        y = _codes_out(what, out, (M,), q[2], N, xq.device)
+    splits = int(splits)
+    nbytes = lib.cnnq_linear_codes_workspace(M, N, K, fx, fw, splits)
+    st = _raw_stream(xq.device.index)
+    ws = _scratch(xq, 'linear_codes', nbytes, st)
+    # a geometry the library refuses sizes no workspace (nbytes == 0): the call below names the error
+    if q is None:
+        L.check(lib.cnnq_linear_codes(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), M, N, K, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias), _ptr(rw),
+                                      splits, _ptr(ws), nbytes, st), 'cnnq_linear_codes')
+    else:
+        L.check(lib.cnnq_linear_codes_q(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), _CODE_FORMATS[q[2]], M, N, K, _ptr(qpx), qpx.shape[1], _ptr(qpw),
+                                        _ptr(bias), _ptr(qpy), qpy.shape[1], int(bool(q[1])), _ptr(rw), splits, _ptr(ws), nbytes, st),
+                'cnnq_linear_codes_q')
+    return y
+
+
 def linear_codes(xq, wq, qpx, qpw, bias=None, x_format='u8', w_format='u8', rw=None, out=None, splits=0):
     """The fully-connected layer on the stored codes (cnnq_linear_codes): activation codes xq [M, K] with the
     table qpx [NQP, 1] (per tensor) or [NQP, M] (per sample), weight codes wq [N, K] with qpw [NQP, N] (per output channel), each
@@ -2886,26 +2929,16 @@ def linear_codes(xq, wq, qpx, qpw, bias=None, x_format='u8', w_format='u8', rw=N
     sum_k ((xq - zx) sx) ((wq - zw) sw) + bias as float32 [M, N]: the integer dot products of the gfx950 int8 matrix instructions,
     combined in fp64 and rounded once.  rw: linear_codes_rowsums(wq, w_format), held by the caller (None: computed per call);
     splits: 0 - the plan's split of k, 1..64 forced (the same bits for every count).  On the stream of xq; no host synchronisation."""
-    lib = L.load()
-    xq, fx, M, K = _codes(xq, x_format, 'xq')
-    wq, fw, N, Kw = _codes(wq, w_format, 'wq')
-    if Kw != K or wq.device != xq.device:
-        raise L.CnnqError('linear_codes: xq has K = %d on %s, wq has K = %d on %s' % (K, xq.device, Kw, wq.device))
-    qpx = _lc_table(qpx, 'qpx', torch.float32, ((L.NQP, 1), (L.NQP, M)), xq.device)
-    qpw = _lc_table(qpw, 'qpw', torch.float32, ((L.NQP, N),), xq.device)
-    if bias is not None:
-        bias = _lc_table(bias, 'bias', torch.float32, ((N,),), xq.device)
-    if rw is not None:
-        rw = _lc_table(rw, 'rw', torch.int32, ((N,),), xq.device)
-    y = torch.empty((M, N), dtype=torch.float32, device=xq.device) if out is None else _lc_table(out, 'out', torch.float32, ((M, N),), xq.device)
-    splits = int(splits)
-    nbytes = lib.cnnq_linear_codes_workspace(M, N, K, fx, fw, splits)
-    st = _raw_stream(xq.device.index)
-    ws = _scratch(xq, 'linear_codes', nbytes, st)
-    # a geometry the library refuses sizes no workspace (nbytes == 0): the call below names the error
-    L.check(lib.cnnq_linear_codes(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), M, N, K, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias), _ptr(rw),
-                                  splits, _ptr(ws), nbytes, st), 'cnnq_linear_codes')
-    return y
+    return _linear_codes('linear_codes', xq, wq, qpx, qpw, bias, x_format, w_format, rw, out, splits)
+
+
+def linear_codes_q(xq, wq, qpx, qpw, qpy, bias=None, relu=False, x_format='u8', w_format='u8', y_format='u8', rw=None, out=None, splits=0):
+    """linear_codes writing CODES (cnnq_linear_codes_q): the same float32 value, then ReLU if `relu`, then the
+    stored format's quantizer with the output table qpy [NQP, 1] (per tensor) or [NQP, M] (per sample) - round(clamp(y / scale + zp,
+    0, qmax)), the bytes of linear_codes -> torch.relu_ -> quantize_packed_nhwc at a uniform 8 / 4 bits - in the same launch.
+    Returns uint8 [M, N] ('u8', N % 4 == 0) or [M, N / 2] ('pack4', N % 8 == 0, the even column in the low nibble): the xq of the
+    next linear_codes* call as it is.  out: such a tensor of the caller's.  Everything else as in linear_codes."""
+    return _linear_codes('linear_codes_q', xq, wq, qpx, qpw, bias, x_format, w_format, rw, out, splits, (qpy, relu, y_format))
 
 
 # ------------------------------------------------------------------------------------- the integer convolution on the codes
@@ -2938,20 +2971,13 @@ def conv_codes_tapsums(wq, w_format='u8'):
     return taps
 
 
-def conv_codes(xq, wq, qpx, qpw, bias=None, stride=1, padding=0, x_format='u8', w_format='u8', taps=None, out=None, splits=0):
-    """The 2-D convolution on the stored codes (DESIGN.md section 36, cnnq_conv_codes): NHWC activation codes xq [N, H, W, Cin] with
-    the table qpx [NQP, 1] (per tensor) or [NQP, N] (per image), OHWI weight codes wq [Cout, KH, KW, Cin] - the bytes of a
-    channels_last weight - with qpw [NQP, Cout], each operand 'u8' or 'pack4' (last axis Cin / 2, the even channel in the low nibble)
-    -> the zero-padded convolution of the decoded operands + bias as float32 [N, Cout, OH, OW] with channels_last strides: integer
-    dot products over each output pixel's valid taps on the gfx950 int8 matrix instructions, combined in fp64 and rounded once.
-    stride, padding: an int or (h, w); dilation and groups are 1.  taps: conv_codes_tapsums(wq, w_format), held by the caller
-    (None: computed per call); out: a float32 [N, Cout, OH, OW] channels_last tensor; splits as in linear_codes.  On the stream
-    of xq; no host synchronisation."""
+def _conv_codes(what, xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, taps, out, splits, q=None):
+    """conv_codes (q None) and conv_codes_q (q = (qpy, relu, y_format)): one front, one call each; the NHWC result."""
     lib = L.load()
     xq, fx, Cin = _codes_nhwc(xq, x_format, 'xq')
     wq, fw, Cw = _codes_nhwc(wq, w_format, 'wq')
     if Cw != Cin or wq.device != xq.device:
-        raise L.CnnqError('conv_codes: xq has Cin = %d on %s, wq has Cin = %d on %s' % (Cin, xq.device, Cw, wq.device))
+        raise L.CnnqError('%s: xq has Cin = %d on %s, wq has Cin = %d on %s' % (what, Cin, xq.device, Cw, wq.device))
     (N, H, W), (Cout, KH, KW) = xq.shape[:3], wq.shape[:3]
     g = (ctypes.c_int64 * 11)(N, H, W, Cin, Cout, KH, KW, *_pair(stride, 'stride'), *_pair(padding, 'padding'))
     splits = int(splits)
@@ -2964,7 +2990,10 @@ def conv_codes(xq, wq, qpx, qpw, bias=None, stride=1, padding=0, x_format='u8', 
         bias = _lc_table(bias, 'bias', torch.float32, ((Cout,),), xq.device)
     if taps is not None:
         taps = _lc_table(taps, 'taps', torch.int32, ((Cout, KH + 1, KW + 1),), xq.device)
-    if out is None:
+    if q is not None:
+        qpy = _lc_table(q[0], 'qpy', torch.float32, ((L.NQP, 1), (L.NQP, N)), xq.device)
+        y = _codes_out(what, out, (N, OH, OW), q[2], Cout, xq.device)
+    elif out is None:
         y = torch.empty((N, OH, OW, Cout), dtype=torch.float32, device=xq.device)
     else:       # the caller's [N, Cout, OH, OW] channels_last tensor: its storage is [N, OH, OW, Cout]
         y = _lc_table(out.permute(0, 2, 3, 1) if isinstance(out, torch.Tensor) and out.dim() == 4 else out, 'out (seen as NHWC)',
@@ -2972,6 +3001,33 @@ def conv_codes(xq, wq, qpx, qpw, bias=None, stride=1, padding=0, x_format='u8', 
     nbytes = lib.cnnq_conv_codes_workspace(g, fx, fw, int(taps is not None), splits)
     st = _raw_stream(xq.device.index)
     ws = _scratch(xq, 'conv_codes', nbytes, st)
-    L.check(lib.cnnq_conv_codes(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), g, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias), _ptr(taps), splits,
-                                _ptr(ws), nbytes, st), 'cnnq_conv_codes')
-    return y.permute(0, 3, 1, 2)
+    if q is None:
+        L.check(lib.cnnq_conv_codes(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), g, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias), _ptr(taps), splits,
+                                    _ptr(ws), nbytes, st), 'cnnq_conv_codes')
+    else:
+        L.check(lib.cnnq_conv_codes_q(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), _CODE_FORMATS[q[2]], g, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias),
+                                      _ptr(qpy), qpy.shape[1], int(bool(q[1])), _ptr(taps), splits, _ptr(ws), nbytes, st), 'cnnq_conv_codes_q')
+    return y
+
+
+def conv_codes(xq, wq, qpx, qpw, bias=None, stride=1, padding=0, x_format='u8', w_format='u8', taps=None, out=None, splits=0):
+    """The 2-D convolution on the stored codes (DESIGN.md section 36, cnnq_conv_codes): NHWC activation codes xq [N, H, W, Cin] with
+    the table qpx [NQP, 1] (per tensor) or [NQP, N] (per image), OHWI weight codes wq [Cout, KH, KW, Cin] - the bytes of a
+    channels_last weight - with qpw [NQP, Cout], each operand 'u8' or 'pack4' (last axis Cin / 2, the even channel in the low nibble)
+    -> the zero-padded convolution of the decoded operands + bias as float32 [N, Cout, OH, OW] with channels_last strides: integer
+    dot products over each output pixel's valid taps on the gfx950 int8 matrix instructions, combined in fp64 and rounded once.
+    stride, padding: an int or (h, w); dilation and groups are 1.  taps: conv_codes_tapsums(wq, w_format), held by the caller
+    (None: computed per call); out: a float32 [N, Cout, OH, OW] channels_last tensor; splits as in linear_codes.  On the stream
+    of xq; no host synchronisation."""
+    return _conv_codes('conv_codes', xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, taps, out, splits).permute(0, 3, 1, 2)
+
+
+def conv_codes_q(xq, wq, qpx, qpw, qpy, bias=None, relu=False, stride=1, padding=0, x_format='u8', w_format='u8', y_format='u8', taps=None,
+                 out=None, splits=0):
+    """conv_codes writing CODES (cnnq_conv_codes_q): the same float32 value, then ReLU if `relu`, then the stored
+    format's quantizer with the output table qpy [NQP, 1] (per tensor) or [NQP, N] (per image), in the same launch - the bytes of
+    conv_codes -> torch.relu_ -> quantize_packed_nhwc at a uniform 8 / 4 bits.  Returns NHWC codes, uint8 [N, OH, OW, Cout] ('u8',
+    Cout % 4 == 0) or [N, OH, OW, Cout / 2] ('pack4', Cout % 8 == 0, the even channel in the low nibble): the xq of the next
+    conv_codes* call as it is (and, seen as [N OH OW, Cout], of linear_codes*).  out: such a tensor of the caller's.  Everything else
+    as in conv_codes."""
+    return _conv_codes('conv_codes_q', xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, taps, out, splits, (qpy, relu, y_format))

@@ -1325,6 +1325,36 @@ int cnnq_conv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, 
                     int64_t Cx, const float* qpw, const float* bias, const int32_t* taps, int splits, void* ws, size_t ws_bytes,
                     void* stream);
 
+/* The integer layers WRITING CODES: cnnq_linear_codes / cnnq_conv_codes followed, inside the same launch, by
+ * an optional ReLU and the quantizer of the stored format, so that a layer's result is the next layer's operand with nothing in
+ * between.  Per element: y32 = what the fp32 entry stores, bit for bit; relu != 0: y32 > 0 ? y32 : 0; code = round-half-even(
+ * clamp(y32 / scale + zp, 0, qmax)) with the IEEE divide and a separately rounded sum (the code cnnq_pc_quantize_packed_nhwc stores;
+ * a NaN is stored as 0), limited to the format's largest code, 255 / 15.  (scale, zp, qmax) come from qpy [CNNQ_NQP][Cy]: Cy = 1 per
+ * tensor, Cy = M (linear) / N (convolution) per sample / image.  The bytes do not depend on the tile, the split count or a held
+ * rw / taps.
+ *
+ * Output.  fmt_y CNNQ_CODES_U8: uint8 y [M][N] / [N][OH][OW][Cout], N resp. Cout % 4 == 0; CNNQ_CODES_PACK4: [M][N / 2] /
+ * [N][OH][OW][Cout / 2], the even column in the low nibble, N resp. Cout % 8 == 0.  Rows back to back, y 4-byte aligned: the
+ * operand format of cnnq_linear_codes* / cnnq_conv_codes* and the uniform 8- / 4-bit stream of cnnq_pc_dequantize_packed_nhwc.  Rows
+ * of whole 16-byte pieces on a 16-byte aligned y take 16-byte stores.
+ *
+ * The _workspace entries return what the fp32 entries return (the workspace is the same; 0 also for a refused fmt_y / N); the
+ * _route entries fill the fp32 route's words and one more: 1 - 16-byte stores / 0 - dword stores.  Everything else - operands,
+ * tables, bias, rw / taps, splits, ws, the launches (the epilogue of splits > 1 writes the codes) - is as in the fp32 entries.
+ * CNNQ_EINVAL before anything touches the device for what the fp32 entries refuse so, fmt_y outside cnnq_code_format, N / Cout not
+ * a multiple of 4 (u8) / 8 (pack4), Cy not 1 or M / N, a NULL or misaligned qpy, a NULL y or one not 4-byte aligned; CNNQ_ERANGE as
+ * there.  Re-entrant, allocate nothing, no atomics, no host synchronisation, graph-capturable. */
+size_t cnnq_linear_codes_q_workspace(int64_t M, int64_t N, int64_t K, int fmt_x, int fmt_w, int fmt_y, int splits);
+int cnnq_linear_codes_q_route(int64_t M, int64_t N, int64_t K, int fmt_x, int fmt_w, int fmt_y, int splits, int align_bytes, int32_t out[5]);
+int cnnq_linear_codes_q(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, uint8_t* y, int fmt_y, int64_t M, int64_t N, int64_t K,
+                        const float* qpx, int64_t Cx, const float* qpw, const float* bias, const float* qpy, int64_t Cy, int relu,
+                        const int32_t* rw, int splits, void* ws, size_t ws_bytes, void* stream);
+size_t cnnq_conv_codes_q_workspace(const int64_t g[11], int fmt_x, int fmt_w, int fmt_y, int have_taps, int splits);
+int cnnq_conv_codes_q_route(const int64_t g[11], int fmt_x, int fmt_w, int fmt_y, int splits, int align_bytes, int32_t out[7]);
+int cnnq_conv_codes_q(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, uint8_t* y, int fmt_y, const int64_t g[11], const float* qpx,
+                      int64_t Cx, const float* qpw, const float* bias, const float* qpy, int64_t Cy, int relu, const int32_t* taps, int splits,
+                      void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

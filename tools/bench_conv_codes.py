@@ -10,7 +10,13 @@ and count a layer as faster only when its slower `int` median beats the faster `
 the two routes' results are compared on every layer (they differ by the fp32 convolution's rounding).  Prints one JSON line; exit
 status 1 if that comparison fails.
 
-    tools/bench_conv_codes.py [--batches 64,1] [--steps 20] [--warmup 5]"""
+--requant times the layer that hands CODES to the next one instead, two other legs:
+    q        ops.conv_codes_q with ReLU: codes in, codes out, the tap table held;
+    chain    the same bytes without it: ops.conv_codes, torch.relu_, ops.quantize_packed_nhwc at a uniform 8 / 4 bits, coloff held.
+The two legs' bytes are compared (they are equal) before anything is timed, and not_faster lists the layers whose `q` median is not
+below the `chain` median; the rule of two runs is the same.
+
+    tools/bench_conv_codes.py [--batches 64,1] [--steps 20] [--warmup 5] [--requant]"""
 import argparse
 import json
 import os
@@ -32,7 +38,6 @@ LAYERS = (
     ('c5_1x1_1024_512', 14, 1024, 512, 1, 1), ('c5_1x1_512_2048', 7, 512, 2048, 1, 1), ('c5_1x1_2048_512', 7, 2048, 512, 1, 1),
     ('c3_down_1x1s2', 56, 256, 512, 1, 2), ('c4_down_1x1s2', 28, 512, 1024, 1, 2), ('c5_down_1x1s2', 14, 1024, 2048, 1, 2),
 )
-LEGS = ('int', 'former')
 
 
 def make(fmt, N, H, Cin, Cout, k, stride, dev, gen):
@@ -63,6 +68,12 @@ def run_leg(ops, leg, L):
     if leg == 'int':
         return ops.conv_codes(L['xq'], L['wq'], L['qpx'], L['qpw'], bias=L['bias'], stride=L['stride'], padding=L['pad'], x_format=L['fmt'],
                               w_format=L['fmt'], taps=L['taps'], out=L['y'])
+    if leg in ('q', 'chain'):
+        kw = dict(bias=L['bias'], stride=L['stride'], padding=L['pad'], x_format=L['fmt'], w_format=L['fmt'], taps=L['taps'])
+        if leg == 'q':
+            return ops.conv_codes_q(L['xq'], L['wq'], L['qpx'], L['qpw'], L['qpy'], relu=True, y_format=L['fmt'], out=L['yq'], **kw)
+        y = torch.relu_(ops.conv_codes(L['xq'], L['wq'], L['qpx'], L['qpw'], out=L['y'], **kw))
+        return ops.quantize_packed_nhwc(y, L['qpc'], L['bits'], out=L['packed'], coloff=L['coloff'])[0]
     x, w = dequantize(ops, L)
     return torch.nn.functional.conv2d(x, w, L['bias'], stride=L['stride'], padding=L['pad'])
 
@@ -72,7 +83,9 @@ def main():
     p.add_argument('--batches', default='64,1')
     p.add_argument('--steps', type=int, default=20)
     p.add_argument('--warmup', type=int, default=5)
+    p.add_argument('--requant', action='store_true')
     a = p.parse_args()
+    LEGS = ('q', 'chain') if a.requant else ('int', 'former')
     if not torch.cuda.is_available():
         sys.exit('bench_conv_codes.py needs a GPU')
     from cnn_quantization_amd import ops
@@ -84,9 +97,19 @@ def main():
             for fmt in ('u8', 'pack4'):
                 L = make(fmt, N, H, Cin, Cout, k, stride, dev, gen)
                 L['taps'], L['y'] = ops.conv_codes_tapsums(L['wq'], fmt), None
-                ref = run_leg(ops, 'former', L)
-                L['y'] = torch.empty_like(ref, memory_format=torch.channels_last)
-                same = bool(torch.allclose(run_leg(ops, 'int', L), ref, rtol=1e-3, atol=1e-3 * float(ref.abs().max())))
+                if a.requant:       # the output table: zero at a non-integer code, the largest output at 1.25 times the top code
+                    y, top = run_leg(ops, 'int', L), float(L['qpx'][2, 0])
+                    L['y'], L['bits'] = y, 8 if fmt == 'u8' else 4
+                    L['qpy'] = torch.tensor([[float(y.max()) / top * 0.8], [0.37], [top]], device=dev)
+                    L['qpc'], L['coloff'] = L['qpy'].expand(3, Cout).contiguous(), ops.packed_layout_nhwc(L['bits'], Cout)
+                    L['yq'] = torch.empty((N, y.shape[2], y.shape[3], Cout // (1 if fmt == 'u8' else 2)), dtype=torch.uint8, device=dev)
+                    L['packed'] = torch.empty(L['yq'].numel(), dtype=torch.uint8, device=dev)
+                    ref = run_leg(ops, 'chain', L).clone()
+                    same = bool(torch.equal(run_leg(ops, 'q', L).flatten(), ref))
+                else:
+                    ref = run_leg(ops, 'former', L)
+                    L['y'] = torch.empty_like(ref, memory_format=torch.channels_last)
+                    same = bool(torch.allclose(run_leg(ops, 'int', L), ref, rtol=1e-3, atol=1e-3 * float(ref.abs().max())))
                 ok = ok and same
                 del ref
                 for _ in range(a.warmup):
@@ -104,14 +127,15 @@ def main():
                         t[leg].append(e0.elapsed_time(e1) * 1e3)
                 us = {leg: [round(statistics.median(t[leg]), 1), round(min(t[leg]), 1), round(max(t[leg]), 1)] for leg in LEGS}
                 M = L['y'].numel() // Cout
-                res['%s b%d %s' % (name, N, fmt)] = dict(
-                    us_median_min_max=us, int_Top_per_s=round(2.0 * M * Cout * k * k * Cin / us['int'][0] / 1e6, 2),
-                    int_over_former=round(us['int'][0] / us['former'][0], 4), results_agree=same)
+                new, old = LEGS
+                res['%s b%d %s' % (name, N, fmt)] = {
+                    'us_median_min_max': us, new + '_Top_per_s': round(2.0 * M * Cout * k * k * Cin / us[new][0] / 1e6, 2),
+                    new + '_over_' + old: round(us[new][0] / us[old][0], 4), 'results_agree': same}
                 del L
                 torch.cuda.empty_cache()
     print(json.dumps(dict(workload='convolution on stored codes: ResNet-50 3x3 and 1x1 layers', steps=a.steps, warmup=a.warmup,
                           device=torch.cuda.get_device_name(0), results=res,
-                          not_faster=[k for k, r in res.items() if r['us_median_min_max']['int'][0] >= r['us_median_min_max']['former'][0]])))
+                          not_faster=[k for k, r in res.items() if r['us_median_min_max'][LEGS[0]][0] >= r['us_median_min_max'][LEGS[1]][0]])))
     if not ok:
         sys.exit(1)
 

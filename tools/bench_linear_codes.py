@@ -11,7 +11,13 @@ Per leg the median, minimum and maximum time of --steps calls after --warmup (HI
 the `former` maximum is listed under not_faster.  Before anything is timed the two routes' results are compared on every shape
 (they differ by the fp32 GEMM's rounding).  Prints one JSON line; exit status 1 if that comparison fails.
 
-    tools/bench_linear_codes.py [--batches 512,1] [--steps 20] [--warmup 5]"""
+--requant times the layer that hands CODES to the next one instead, two other legs:
+    q        ops.linear_codes_q with ReLU: codes in, codes out, Rw held;
+    chain    the same bytes without it: ops.linear_codes, torch.relu_, and ops.quantize_u8 / quantize_pack4 of y seen as one channel
+             (a per-tensor table).
+The two legs' bytes are compared (they are equal) before anything is timed; not_faster by the same rule.
+
+    tools/bench_linear_codes.py [--batches 512,1] [--steps 20] [--warmup 5] [--requant]"""
 import argparse
 import json
 import os
@@ -24,7 +30,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 LAYERS = (('vgg16_fc1', 25088, 4096), ('vgg16_fc2', 4096, 4096), ('vgg16_fc3', 4096, 1000), ('resnet50_fc', 2048, 1000))
-LEGS = ('int', 'former', 'gemm')
 
 
 def make(fmt, M, N, K, dev, gen):
@@ -53,6 +58,12 @@ def dequantize(ops, L):
 def run_leg(ops, leg, L):
     if leg == 'int':
         return ops.linear_codes(L['xq'], L['wq'], L['qpx'], L['qpw'], bias=L['bias'], x_format=L['fmt'], w_format=L['fmt'], rw=L['rw'], out=L['y'])
+    if leg in ('q', 'chain'):
+        kw = dict(bias=L['bias'], x_format=L['fmt'], w_format=L['fmt'], rw=L['rw'])
+        if leg == 'q':
+            return ops.linear_codes_q(L['xq'], L['wq'], L['qpx'], L['qpw'], L['qpy'], relu=True, y_format=L['fmt'], out=L['yq'], **kw)
+        y = torch.relu_(ops.linear_codes(L['xq'], L['wq'], L['qpx'], L['qpw'], out=L['y'], **kw)).view(1, 1, -1, 1)
+        return ops.quantize_u8(y, L['qpy']) if L['fmt'] == 'u8' else ops.quantize_pack4(y, L['qpy'])
     x, w = dequantize(ops, L) if leg == 'former' else (L['xf'], L['wf'])
     return torch.nn.functional.linear(x, w, L['bias'])
 
@@ -62,7 +73,9 @@ def main():
     p.add_argument('--batches', default='512,1')
     p.add_argument('--steps', type=int, default=20)
     p.add_argument('--warmup', type=int, default=5)
+    p.add_argument('--requant', action='store_true')
     a = p.parse_args()
+    LEGS = ('q', 'chain') if a.requant else ('int', 'former', 'gemm')
     if not torch.cuda.is_available():
         sys.exit('bench_linear_codes.py needs a GPU')
     from cnn_quantization_amd import ops
@@ -75,9 +88,15 @@ def main():
                 L = make(fmt, M, N, K, dev, gen)
                 L['rw'] = ops.linear_codes_rowsums(L['wq'], fmt)
                 L['y'] = torch.empty((M, N), device=dev)
-                L['xf'], L['wf'] = dequantize(ops, L)
-                ref = run_leg(ops, 'gemm', L)
-                same = bool(torch.allclose(run_leg(ops, 'int', L), ref, rtol=1e-3, atol=1e-3 * float(ref.abs().max())))
+                if a.requant:       # the output table: zero at a non-integer code, the largest output at 1.25 times the top code
+                    top = float(L['qpx'][2, 0])
+                    L['qpy'] = torch.tensor([[float(run_leg(ops, 'int', L).max()) / top * 0.8], [0.37], [top]], device=dev)
+                    L['yq'] = torch.empty((M, N // (1 if fmt == 'u8' else 2)), dtype=torch.uint8, device=dev)
+                    same = bool(torch.equal(run_leg(ops, 'q', L).flatten(), run_leg(ops, 'chain', L).flatten()))
+                else:
+                    L['xf'], L['wf'] = dequantize(ops, L)
+                    ref = run_leg(ops, 'gemm', L)
+                    same = bool(torch.allclose(run_leg(ops, 'int', L), ref, rtol=1e-3, atol=1e-3 * float(ref.abs().max())))
                 ok = ok and same
                 for _ in range(a.warmup):
                     for leg in LEGS:
@@ -94,6 +113,9 @@ def main():
                         t[leg].append(e0.elapsed_time(e1) * 1e3)
                 us = {leg: [round(statistics.median(t[leg]), 1), round(min(t[leg]), 1), round(max(t[leg]), 1)] for leg in LEGS}
                 nbytes = L['xq'].numel() + L['wq'].numel() + 4 * M * N
+                if a.requant:
+                    res['%s b%d %s' % (name, M, fmt)] = dict(us_median_min_max=us, q_over_chain=round(us['q'][0] / us['chain'][0], 4), results_agree=same)
+                    continue
                 res['%s b%d %s' % (name, M, fmt)] = dict(
                     us_median_min_max=us, int_Top_per_s=round(2.0 * M * N * K / us['int'][0] / 1e6, 2), int_bytes=nbytes,
                     int_GB_per_s=round(nbytes / us['int'][0] / 1e3, 1), int_over_former=round(us['int'][0] / us['former'][0], 4),
@@ -102,7 +124,7 @@ def main():
                 torch.cuda.empty_cache()
     print(json.dumps(dict(workload='linear layer on stored codes: VGG-16 and ResNet-50 classifier layers', steps=a.steps, warmup=a.warmup,
                           device=torch.cuda.get_device_name(0), results=res,
-                          not_faster=[k for k, r in res.items() if r['us_median_min_max']['int'][1] >= r['us_median_min_max']['former'][2]])))
+                          not_faster=[k for k, r in res.items() if r['us_median_min_max'][LEGS[0]][1] >= r['us_median_min_max'][LEGS[1]][2]])))
     if not ok:
         sys.exit(1)
 
