@@ -18,7 +18,8 @@
 //   k_cc_winsums   one thread per output pixel: its valid rectangle, packed into a word, and Rx = the valid pixels' sums.
 //   k_cc_gemm      the tiles of S'; k_lc_gemm's schedule with a gathered A operand (below); with one split its tail finishes.
 //   k_cc_epilogue  splits > 1: adds the splits' int32 partial tiles, then the same cc_finish - the same bits for every split count.
-// The Q instances of k_cc_gemm and k_cc_epilogue_q store NHWC codes instead of fp32, as the linear layer's: cnnq_requant_codes.hip.h.
+// The Q instances of k_cc_gemm and k_cc_epilogue_q store NHWC codes instead of fp32, as the linear layer's: cnnq_requant_codes.hip.h;
+// the R instances add a residual of NHWC codes before ReLU and the quantizer (section 38).
 //
 // The A path.  The rows a thread fetches are the same for every step of a tile: they are decomposed into (image, oh, ow) and the
 // window origin ih0 = oh sh - ph, iw0 = ow sw - pw ONCE, before the k loop (rows beyond M get an origin no tap of which is inside
@@ -57,6 +58,7 @@ struct CcArgs {
     CcGeo g;
     CcEpi e;
     RqOut q;                // Q instances: the codes' destination instead of y (cnnq_requant_codes.hip.h)
+    RqRes r;                // R instances: the residual codes added before ReLU and the quantizer (section 38)
 };
 
 // the valid taps of the window whose origin is (ih0, iw0): kh0 <= kh1, kw0 <= kw1 (an empty rectangle where no tap is inside)
@@ -191,10 +193,12 @@ __device__ __forceinline__ void cc_fetch(const unsigned char* __restrict__ xq, c
 }
 
 // ---- the tiles ------------------------------------------------------------------------------------------------------------------
-// Q: with one split the tail stores codes (a.q) instead of fp32 (a.y): section 37
-template <int WM, int WN, int TM, int TN, int FX, int FW, bool V16, bool Q = false>
+// Q: with one split the tail stores codes (a.q) instead of fp32 (a.y): section 37.  R (with Q): it adds the residual codes a.r first:
+// section 38
+template <int WM, int WN, int TM, int TN, int FX, int FW, bool V16, bool Q = false, bool R = false>
 __global__ __launch_bounds__(TPB) void k_cc_gemm(const CcArgs a) {
     static_assert(WM * WN == TPB / 64, "four waves");
+    static_assert(Q || !R, "the residual is added on the way to codes");
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     constexpr int CA = BM * 4, CB = BN * 4;                          // chunks per step
     constexpr int NA = (CA + TPB - 1) / TPB, NB = (CB + TPB - 1) / TPB;
@@ -299,21 +303,38 @@ __global__ __launch_bounds__(TPB) void k_cc_gemm(const CcArgs a) {
         if (!part) {                                                 // uniform: quantize, stage through the free operand buffers, store
             unsigned* tile = reinterpret_cast<unsigned*>(&lds[0][0]);
             static_assert(BM * RqTile<BN>::P * 4 <= (int)sizeof(lds), "the codes of the tile fit the operand buffers");
+            if constexpr (R) {
+                // the residual's pieces: global -> the registers the operands have left -> LDS; ONE barrier later every lane reads
+                // back the dwords it will write below, so the codes overwrite the residual's image
+                rq_u4 res[RqPieces<BM, BN>::NPT];
+                rq_fetch_tile<BM, BN>(a.r, m0, n0, M, N, res);
+                rq_put_tile<BM, BN>(tile, a.r, res);
+                __syncthreads();
+            }
             unsigned cd[TM][TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
+                unsigned rd[TN];
 #pragma unroll
-                for (int j = 0; j < TN; ++j) cd[i][j] = 0u;
+                for (int j = 0; j < TN; ++j) {
+                    cd[i][j] = 0u;
+                    if constexpr (R) rd[j] = rq_unstage<BN>(tile, (wm * TM + i) * 16, (wn * TN + j) * 16, lane);
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int m = m0 + (wm * TM + i) * 16 + fc * 4 + r;
                     if (m >= M) continue;
                     const CcRow row = cc_row(m, a.e);
                     const RqRow qrow = rq_row(a.q, a.q.Cy == 1 ? 0 : m / a.e.OHW);
+                    RqResRow rrow;
+                    if constexpr (R) rrow = rq_res_row(a.r, a.r.Cr == 1 ? 0 : m / a.e.OHW);
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         const int n = n0 + (wn * TN + j) * 16 + fr;
-                        if (n < N) cd[i][j] |= rq_code(cc_finish(acc[i][j][r], row, n, a.e), a.q, qrow) << (8 * r);
+                        if (n >= N) continue;
+                        float y = cc_finish(acc[i][j][r], row, n, a.e);
+                        if constexpr (R) y = rq_add_res(y, (rd[j] >> (8 * r)) & 255u, rrow);
+                        cd[i][j] |= rq_code(y, a.q, qrow) << (8 * r);
                     }
                 }
             }
@@ -353,9 +374,10 @@ __global__ __launch_bounds__(TPB) void k_cc_epilogue(const int* __restrict__ par
     y[idx] = cc_finish(s, cc_row((int)(idx / e.e.N), e), (int)(idx % e.e.N), e);
 }
 
-// ... to codes: thread idx owns dword idx of y, 4 (u8) or 8 (pack4) consecutive channels of one output pixel
-template <int FY>
-__global__ __launch_bounds__(TPB) void k_cc_epilogue_q(const int* __restrict__ part, int splits, long long MN, const CcEpi e, const RqOut o) {
+// ... to codes: thread idx owns dword idx of y, 4 (u8) or 8 (pack4) consecutive channels of one output pixel.  FR >= 0: the residual
+// form (section 38) - the matching residual codes (rq_res_codes) and the residual row's table entry are read once per thread
+template <int FY, int FR = -1>
+__global__ __launch_bounds__(TPB) void k_cc_epilogue_q(const int* __restrict__ part, int splits, long long MN, const CcEpi e, const RqOut o, const RqRes s) {
     constexpr int CPD = FY == CNNQ_CODES_U8 ? 4 : 8;
     const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
     if (idx >= MN / CPD) return;
@@ -363,13 +385,23 @@ __global__ __launch_bounds__(TPB) void k_cc_epilogue_q(const int* __restrict__ p
     const int m = (int)(at / e.e.N), n = (int)(at % e.e.N);
     const CcRow row = cc_row(m, e);
     const RqRow qrow = rq_row(o, o.Cy == 1 ? 0 : m / e.OHW);
+    unsigned rc[2] = {0u, 0u};
+    RqResRow rrow{};
+    if constexpr (FR >= 0) {
+        rq_res_codes<FY, FR>(s, idx, rc[0], rc[1]);
+        rrow = rq_res_row(s, s.Cr == 1 ? 0 : m / e.OHW);
+    }
     unsigned w = 0u;
 #pragma unroll
     for (int c = 0; c < CPD; c += 4) {
-        long long s[4];
-        rq_add_splits(part, splits, MN, at + c, s);
+        long long sum[4];
+        rq_add_splits(part, splits, MN, at + c, sum);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) w |= rq_code(cc_finish(s[k], row, n + c + k, e), o, qrow) << ((c + k) * (32 / CPD));
+        for (int k = 0; k < 4; ++k) {
+            float y = cc_finish(sum[k], row, n + c + k, e);
+            if constexpr (FR >= 0) y = rq_add_res(y, (rc[c / 4] >> (8 * k)) & 255u, rrow);
+            w |= rq_code(y, o, qrow) << ((c + k) * (32 / CPD));
+        }
     }
     reinterpret_cast<unsigned*>(o.y)[idx] = w;
 }

@@ -3283,9 +3283,11 @@ int cnnq_conv_codes_tapsums(const uint8_t* wq, int fmt_w, int64_t Cout, int64_t 
     return cc_tapsums_launch(wq, fmt_w, Cout, KH, KW, Cin, taps, stream);
 }
 
-// the body of cnnq_conv_codes (q.y == NULL: fp32 into y) and cnnq_conv_codes_q (codes into q.y); the output is checked
-static int cc_run(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const RqOut& q, const CcShape& s, const float* qpx,
-                  int64_t Cx, const float* qpw, const float* bias, const int32_t* taps, int splits, void* ws, size_t ws_bytes, void* stream) {
+// the body of cnnq_conv_codes (q.y == NULL: fp32 into y), cnnq_conv_codes_q (codes into q.y) and cnnq_conv_codes_q_add (r.rq != NULL:
+// the residual codes added first); the output and the residual are checked
+static int cc_run(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const RqOut& q, const RqRes& r, const CcShape& s,
+                  const float* qpx, int64_t Cx, const float* qpw, const float* bias, const int32_t* taps, int splits, void* ws, size_t ws_bytes,
+                  void* stream) {
     if (!xq || !wq || !qpx || !qpw || !ws || (Cx != 1 && Cx != s.N)) return CNNQ_EINVAL;
     if (misaligned(xq, 4) || misaligned(wq, 4) || misaligned(qpx, 4) || misaligned(qpw, 4) || misaligned(bias, 4) || misaligned(taps, 4) ||
         misaligned(ws, 16))
@@ -3320,6 +3322,7 @@ static int cc_run(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, fl
     a.e.C = (int)s.C;
     a.e.OHW = a.g.OHW;
     a.q = q;
+    a.r = r;
     // the pixels' channel sums (the linear layer's row sums on [N H W][C]), the windows over them, the layer's table unless held
     if (const int rc = lc_rowsums_launch(xq, fmt_x, s.pixels, nullptr, fmt_w, 0, s.C, w.pix, nullptr, stream)) return rc;
     hipLaunchKernelGGL(k_cc_winsums, dim3((unsigned)((s.M + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.pix, a.g, a.M, w.rx, w.rect);
@@ -3329,11 +3332,11 @@ static int cc_run(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, fl
     const dim3 grid((unsigned)((int64_t)p.tilesM * p.tilesN * p.splits));
     with_int<0, 1, 2>(p.tile, [&](auto t) {
         with_bool(fmt_x == CNNQ_CODES_PACK4, fmt_w == CNNQ_CODES_PACK4, cc_v16(s, fmt_x, fmt_w, (uintptr_t)xq, (uintptr_t)wq), [&](auto px, auto pw, auto v) {
-            with_bool(q.y != nullptr, [&](auto oq) {
-                constexpr int T = decltype(t)::value;
+            with_int<0, 1, 2>(q.y ? (r.rq ? 2 : 1) : 0, [&](auto out) {      // fp32, codes, codes with the residual
+                constexpr int T = decltype(t)::value, OUT = decltype(out)::value;
                 constexpr int WM = T == 0 ? 1 : 2, WN = T == 0 ? 4 : 2, TM = T == 0 ? 1 : T == 1 ? 2 : 4, TN = T == 0 ? 2 : T == 1 ? 2 : 4;
                 constexpr int FX = decltype(px)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, FW = decltype(pw)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8;
-                hipLaunchKernelGGL((k_cc_gemm<WM, WN, TM, TN, FX, FW, decltype(v)::value, decltype(oq)::value>), grid, dim3(TPB), 0, hs(stream), a);
+                hipLaunchKernelGGL((k_cc_gemm<WM, WN, TM, TN, FX, FW, decltype(v)::value, OUT >= 1, OUT == 2>), grid, dim3(TPB), 0, hs(stream), a);
             });
         });
     });
@@ -3344,9 +3347,12 @@ static int cc_run(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, fl
         hipLaunchKernelGGL(k_cc_epilogue, dim3((unsigned)((MN + TPB - 1) / TPB)), dim3(TPB), 0, hs(stream), w.part, p.splits, MN, a.e, y);
     } else {        // a thread per dword of codes
         const long long ndw = MN / (q.fy == CNNQ_CODES_U8 ? 4 : 8);
+        const dim3 eg((unsigned)((ndw + TPB - 1) / TPB));
         with_bool(q.fy == CNNQ_CODES_PACK4, [&](auto p4) {
-            hipLaunchKernelGGL((k_cc_epilogue_q<decltype(p4)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8>), dim3((unsigned)((ndw + TPB - 1) / TPB)), dim3(TPB), 0,
-                               hs(stream), w.part, p.splits, MN, a.e, q);
+            with_int<-1, CNNQ_CODES_U8, CNNQ_CODES_PACK4>(r.rq ? r.fr : -1, [&](auto fr) {
+                hipLaunchKernelGGL((k_cc_epilogue_q<decltype(p4)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, decltype(fr)::value>), eg, dim3(TPB), 0,
+                                   hs(stream), w.part, p.splits, MN, a.e, q, r);
+            });
         });
     }
     return launch_status();
@@ -3357,7 +3363,7 @@ int cnnq_conv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, 
     CcShape s;
     if (const int rc = cc_check(g, fmt_x, fmt_w, splits, s)) return rc;
     if (!y || misaligned(y, 4)) return CNNQ_EINVAL;
-    return cc_run(xq, fmt_x, wq, fmt_w, y, RqOut{}, s, qpx, Cx, qpw, bias, taps, splits, ws, ws_bytes, stream);
+    return cc_run(xq, fmt_x, wq, fmt_w, y, RqOut{}, RqRes{}, s, qpx, Cx, qpw, bias, taps, splits, ws, ws_bytes, stream);
 }
 
 // ---- ... writing NHWC codes (cnnq_requant_codes.hip.h) ---------------------------------------------------------
@@ -3381,7 +3387,41 @@ int cnnq_conv_codes_q(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w
     CcShape s;
     if (const int rc = cc_check(g, fmt_x, fmt_w, splits, s)) return rc;
     if (const int rc = rq_check(fmt_y, s.Cout, y, qpy, Cy, s.N)) return rc;
-    return cc_run(xq, fmt_x, wq, fmt_w, nullptr, rq_out(y, fmt_y, s.Cout, qpy, Cy, relu), s, qpx, Cx, qpw, bias, taps, splits, ws, ws_bytes, stream);
+    return cc_run(xq, fmt_x, wq, fmt_w, nullptr, rq_out(y, fmt_y, s.Cout, qpy, Cy, relu), RqRes{}, s, qpx, Cx, qpw, bias, taps, splits, ws, ws_bytes,
+                  stream);
+}
+
+// ---- ... with a residual: codes of the output's shape, decoded and added before ReLU and the quantizer --------------
+// the residual's own arguments are checked as the output's (rq_check): format, rows of whole dwords, table, pointers
+static RqRes rq_res(const uint8_t* rq, int fr, int64_t N, const float* qpr, int64_t Cr) {
+    const int64_t rowbytes = fr == CNNQ_CODES_U8 ? N : N / 2;
+    return RqRes{rq, qpr, (int)Cr, fr, rowbytes % 16 == 0 && (uintptr_t)rq % 16 == 0};
+}
+
+size_t cnnq_conv_codes_q_add_workspace(const int64_t g[11], int fmt_x, int fmt_w, int fmt_y, int fmt_r, int have_taps, int splits) {
+    if (!g || !lc_fmt_ok(fmt_r) || g[4] % (fmt_r == CNNQ_CODES_U8 ? 4 : 8)) return 0;
+    return cnnq_conv_codes_q_workspace(g, fmt_x, fmt_w, fmt_y, have_taps, splits);
+}
+
+// out: cnnq_conv_codes_q_route's seven, then 1 - 16-byte loads / 0 - dword loads of the residual
+int cnnq_conv_codes_q_add_route(const int64_t g[11], int fmt_x, int fmt_w, int fmt_y, int fmt_r, int splits, int align_bytes, int32_t out[8]) {
+    if (!out) return CNNQ_EINVAL;
+    if (const int rc = cnnq_conv_codes_q_route(g, fmt_x, fmt_w, fmt_y, splits, align_bytes, out)) return rc;
+    if (!lc_fmt_ok(fmt_r) || g[4] % (fmt_r == CNNQ_CODES_U8 ? 4 : 8)) return CNNQ_EINVAL;
+    out[7] = rq_res(reinterpret_cast<const uint8_t*>((uintptr_t)align_bytes), fmt_r, g[4], nullptr, 1).wide;
+    return 0;
+}
+
+int cnnq_conv_codes_q_add(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, uint8_t* y, int fmt_y, const int64_t g[11], const float* qpx,
+                          int64_t Cx, const float* qpw, const float* bias, const float* qpy, int64_t Cy, int relu, const uint8_t* rq, int fmt_r,
+                          const float* qpr, int64_t Cr, const int32_t* taps, int splits, void* ws, size_t ws_bytes, void* stream) {
+    CcShape s;
+    if (const int rc = cc_check(g, fmt_x, fmt_w, splits, s)) return rc;
+    if (const int rc = rq_check(fmt_y, s.Cout, y, qpy, Cy, s.N)) return rc;
+    if (const int rc = rq_check(fmt_r, s.Cout, rq, qpr, Cr, s.N)) return rc;
+    if (rq == y && fmt_r != fmt_y) return CNNQ_EINVAL;       // in place only where a thread's dword of y is the dword it read
+    return cc_run(xq, fmt_x, wq, fmt_w, nullptr, rq_out(y, fmt_y, s.Cout, qpy, Cy, relu), rq_res(rq, fmt_r, s.Cout, qpr, Cr), s, qpx, Cx, qpw, bias,
+                  taps, splits, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -35,6 +35,13 @@
 //
 // Split k: the int32 partial tiles are as they were; k_lc_epilogue_q / k_cc_epilogue_q (beside the fp32 epilogues) give a thread
 // ONE dword of y - 4 u8 or 8 pack4 codes, consecutive n of one row: 16-byte loads of the partial tiles, the row's table entry once.
+//
+// The residual (the R instances of k_cc_gemm, k_cc_epilogue_q<FY, FR>): a second code operand of the output's
+// shape, u8 or pack4 independently of the output, s32 = y32 + (float(code) - zr) * sr in three separately rounded fp32 operations
+// before ReLU and the quantizer.  The store path run backwards: thread p loads piece p of the residual's tile (rq_fetch_pieces, one
+// 16-byte load where the residual's own `wide` holds), pack4 is expanded to one code per byte on the way IN (rq_unpack8), the pieces
+// go to the same LDS image (rq_put_pieces), and after one barrier a lane reads the dword it will later write (rq_unstage: rq_stage's
+// address and the same quad transpose, which is its own inverse).  The output codes overwrite the residual's image in place.
 #pragma once
 #include "cnnq_common.hip.h"
 #include "cnnq_qdq.hip.h"
@@ -75,11 +82,10 @@ struct RqTile {
     static constexpr int P = BN / 4 + 4;
 };
 
-// cd: the lane's codes of rows 4 (lane / 16) + r (byte r) of column lane % 16 of the instruction tile at (row0, col0) of the macro
-// tile -> transposed within the quad and written as the four bytes (row0 + 4 (lane / 16) + lane % 4, col0 + 4 (lane % 16 / 4) ..)
-template <int BN>
-__device__ __forceinline__ void rq_stage(unsigned* __restrict__ tile, int row0, int col0, int lane, unsigned cd) {
-    const int t = lane & 3, q = (lane >> 2) & 3, fc = lane >> 4;
+// the 4 x 4 byte transpose of a quad: lane 4q + t gives byte j of its dword to lane 4q + j and holds byte t of each of the four
+// afterwards, lane j's in byte j.  Its own inverse: "my column, rows 0..3" <-> "my row, columns 4q .. 4q + 3"
+__device__ __forceinline__ unsigned rq_quad_transpose(unsigned cd, int lane) {
+    const int t = lane & 3;
     // quad_perm broadcasts of the quad's lanes 0..3
     const unsigned d0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)cd, 0x00, 0xF, 0xF, false);
     const unsigned d1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)cd, 0x55, 0xF, 0xF, false);
@@ -88,7 +94,24 @@ __device__ __forceinline__ void rq_stage(unsigned* __restrict__ tile, int row0, 
     // v_perm_b32: selector bytes 0..3 take the second source's bytes, 4..7 the first's.  Byte t of each of the four
     const unsigned sel = 0x0C0C0400u + (unsigned)t * 0x0101u;
     const unsigned p01 = __builtin_amdgcn_perm(d1, d0, sel), p23 = __builtin_amdgcn_perm(d3, d2, sel);
-    tile[(row0 + fc * 4 + t) * RqTile<BN>::P + (col0 >> 2) + q] = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
+    return __builtin_amdgcn_perm(p23, p01, 0x05040100u);
+}
+// the lane's dword of the instruction tile at (row0, col0) of the macro tile: the four bytes (row0 + 4 (lane / 16) + lane % 4,
+// col0 + 4 (lane % 16 / 4) ..) of the LDS image - written by rq_stage, read by rq_unstage
+template <int BN>
+__device__ __forceinline__ int rq_lane_dword(int row0, int col0, int lane) {
+    return (row0 + (lane >> 4) * 4 + (lane & 3)) * RqTile<BN>::P + (col0 >> 2) + ((lane >> 2) & 3);
+}
+// cd: the lane's codes of rows 4 (lane / 16) + r (byte r) of column lane % 16 of the instruction tile -> transposed within the
+// quad and written as the lane's dword
+template <int BN>
+__device__ __forceinline__ void rq_stage(unsigned* __restrict__ tile, int row0, int col0, int lane, unsigned cd) {
+    tile[rq_lane_dword<BN>(row0, col0, lane)] = rq_quad_transpose(cd, lane);
+}
+// the other direction (section 38): the lane's dword of the image -> the codes of rows 4 (lane / 16) + r (byte r) of column lane % 16
+template <int BN>
+__device__ __forceinline__ unsigned rq_unstage(const unsigned* __restrict__ tile, int row0, int col0, int lane) {
+    return rq_quad_transpose(tile[rq_lane_dword<BN>(row0, col0, lane)], lane);
 }
 
 // eight codes of 0..15, one per byte of a, b -> the dword of pack4, the first code in the lowest nibble
@@ -127,6 +150,116 @@ template <int BM, int BN>
 __device__ __forceinline__ void rq_store_tile(const unsigned* __restrict__ tile, const RqOut& o, int m0, int n0, int M, int N) {
     if (o.fy == CNNQ_CODES_U8) rq_store_pieces<BM, BN, CNNQ_CODES_U8>(tile, o, m0, n0, M, N);
     else rq_store_pieces<BM, BN, CNNQ_CODES_PACK4>(tile, o, m0, n0, M, N);
+}
+
+// ---- the residual operand (section 38): codes of the output's shape, decoded and added before ReLU and the quantizer ----------------
+// rq == NULL: none
+struct RqRes {
+    const unsigned char* rq;   // [M][N] (u8) or [M][N / 2] (pack4), rows back to back, 4-byte aligned; may be the output itself (same format)
+    const float* qpr;          // [CNNQ_NQP][Cr]
+    int Cr, fr;                // fr: cnnq_code_format
+    int wide;                  // residual rows of whole 16-byte pieces on a 16-byte base
+};
+struct RqResRow {
+    float scale, zp;
+};
+__device__ __forceinline__ RqResRow rq_res_row(const RqRes& s, int idx) {
+    const int c = s.Cr == 1 ? 0 : idx;
+    return RqResRow{s.qpr[CNNQ_QP_SCALE * (size_t)s.Cr + c], s.qpr[CNNQ_QP_ZP * (size_t)s.Cr + c]};
+}
+// y32 + the decoded code: the subtraction, the product and the sum each rounded to fp32 (-ffp-contract=off; the product is an
+// operand of the sum, never fused into it)
+__device__ __forceinline__ float rq_add_res(float y, unsigned code, const RqResRow& q) {
+    const float r = ((float)code - q.zp) * q.scale;
+    return y + r;
+}
+
+// the dword of pack4 -> eight codes, one per byte, the first in the lowest byte of a: rq_pack8's inverse
+__device__ __forceinline__ void rq_unpack8(unsigned v, unsigned& a, unsigned& b) {
+    const unsigned lo = v & 0x0F0F0F0Fu, hi = (v >> 4) & 0x0F0F0F0Fu;
+    a = __builtin_amdgcn_perm(hi, lo, 0x05010400u);
+    b = __builtin_amdgcn_perm(hi, lo, 0x07030602u);
+}
+
+// pieces per thread of a BM x BN tile: the u8 count (pack4 has half as many)
+template <int BM, int BN>
+struct RqPieces {
+    static constexpr int NPT = (BM * BN / 16 + TPB - 1) / TPB;
+};
+
+// global -> registers: piece p of the tile - 16 residual bytes of one output row, rq_store_pieces' map with the residual's format -
+// to thread p % TPB; one 16-byte load where `wide`, else dword by dword.  Rows beyond M and pieces beyond N are not loaded
+template <int BM, int BN, int FR>
+__device__ __forceinline__ void rq_fetch_pieces(const RqRes& s, int m0, int n0, int M, int N, rq_u4 (&v)[RqPieces<BM, BN>::NPT]) {
+    constexpr int CPD = FR == CNNQ_CODES_U8 ? 4 : 8, CPP = 4 * CPD;
+    constexpr int PPR = BN / CPP, NP = BM * PPR;
+    const size_t rowdw = (size_t)(N / CPD);
+#pragma unroll
+    for (int i = 0; i < (NP + TPB - 1) / TPB; ++i) {
+        const int p = threadIdx.x + i * TPB;
+        const int r = p / PPR, pc = p % PPR, m = m0 + r, n = n0 + pc * CPP;
+        v[i] = rq_u4{0u, 0u, 0u, 0u};
+        if ((NP % TPB && p >= NP) || m >= M || n >= N) continue;
+        const unsigned* src = reinterpret_cast<const unsigned*>(s.rq) + (size_t)m * rowdw + n / CPD;
+        if (s.wide && n + CPP <= N) {
+            v[i] = *reinterpret_cast<const rq_u4*>(src);
+        } else {
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+                if (n + d * CPD < N) v[i][d] = src[d];
+        }
+    }
+}
+// registers -> the tile's LDS image, one code per byte in both formats (pack4 expanded on the way in)
+template <int BM, int BN, int FR>
+__device__ __forceinline__ void rq_put_pieces(unsigned* __restrict__ tile, const rq_u4 (&v)[RqPieces<BM, BN>::NPT]) {
+    constexpr int CPP = FR == CNNQ_CODES_U8 ? 16 : 32;
+    constexpr int PPR = BN / CPP, NP = BM * PPR;
+#pragma unroll
+    for (int i = 0; i < (NP + TPB - 1) / TPB; ++i) {
+        const int p = threadIdx.x + i * TPB;
+        if (NP % TPB && p >= NP) continue;
+        rq_u4* dst = reinterpret_cast<rq_u4*>(tile + (p / PPR) * RqTile<BN>::P) + (p % PPR) * (CPP / 16);
+        if constexpr (FR == CNNQ_CODES_U8) {
+            dst[0] = v[i];
+        } else {
+            unsigned c[8];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) rq_unpack8(v[i][d], c[2 * d], c[2 * d + 1]);
+            dst[0] = rq_u4{c[0], c[1], c[2], c[3]};
+            dst[1] = rq_u4{c[4], c[5], c[6], c[7]};
+        }
+    }
+}
+template <int BM, int BN>
+__device__ __forceinline__ void rq_fetch_tile(const RqRes& s, int m0, int n0, int M, int N, rq_u4 (&v)[RqPieces<BM, BN>::NPT]) {
+    if (s.fr == CNNQ_CODES_U8) rq_fetch_pieces<BM, BN, CNNQ_CODES_U8>(s, m0, n0, M, N, v);
+    else rq_fetch_pieces<BM, BN, CNNQ_CODES_PACK4>(s, m0, n0, M, N, v);
+}
+template <int BM, int BN>
+__device__ __forceinline__ void rq_put_tile(unsigned* __restrict__ tile, const RqRes& s, const rq_u4 (&v)[RqPieces<BM, BN>::NPT]) {
+    if (s.fr == CNNQ_CODES_U8) rq_put_pieces<BM, BN, CNNQ_CODES_U8>(tile, v);
+    else rq_put_pieces<BM, BN, CNNQ_CODES_PACK4>(tile, v);
+}
+
+// split k: the residual codes that match thread idx's dword of y - CPD codes from element `at` of row-major [M][N], one per byte of
+// a (and b: the second four of a pack4 output).  u8 -> u8 and pack4 -> pack4: the dword idx; u8 -> pack4: dwords 2 idx, 2 idx + 1;
+// pack4 -> u8: the thread's OWN half of dword idx / 2 as one 16-bit load - no byte is loaded by two threads
+template <int FY, int FR>
+__device__ __forceinline__ void rq_res_codes(const RqRes& s, long long idx, unsigned& a, unsigned& b) {
+    const unsigned* src = reinterpret_cast<const unsigned*>(s.rq);
+    b = 0u;
+    if constexpr (FY == FR) {
+        const unsigned v = src[idx];
+        if constexpr (FR == CNNQ_CODES_U8) a = v;
+        else rq_unpack8(v, a, b);
+    } else if constexpr (FR == CNNQ_CODES_U8) {
+        a = src[2 * idx];
+        b = src[2 * idx + 1];
+    } else {
+        unsigned bb;
+        rq_unpack8(reinterpret_cast<const unsigned short*>(s.rq)[idx], a, bb);
+    }
 }
 
 // split k: the sums of four consecutive elements' partial tiles (at % 4 == 0, MN % 4 == 0: 16-byte loads)

@@ -2971,8 +2971,9 @@ def conv_codes_tapsums(wq, w_format='u8'):
     return taps
 
 
-def _conv_codes(what, xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, taps, out, splits, q=None):
-    """conv_codes (q None) and conv_codes_q (q = (qpy, relu, y_format)): one front, one call each; the NHWC result."""
+def _conv_codes(what, xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, taps, out, splits, q=None, res=None):
+    """conv_codes (q None) and conv_codes_q (q = (qpy, relu, y_format); res = (residual, qpr, r_format) or None): one front, one call
+    each; the NHWC result."""
     lib = L.load()
     xq, fx, Cin = _codes_nhwc(xq, x_format, 'xq')
     wq, fw, Cw = _codes_nhwc(wq, w_format, 'wq')
@@ -2993,6 +2994,11 @@ def _conv_codes(what, xq, wq, qpx, qpw, bias, stride, padding, x_format, w_forma
     if q is not None:
         qpy = _lc_table(q[0], 'qpy', torch.float32, ((L.NQP, 1), (L.NQP, N)), xq.device)
         y = _codes_out(what, out, (N, OH, OW), q[2], Cout, xq.device)
+        if res is not None:     # codes of the output's shape in their own format; `out` may be the residual itself
+            qpr = _lc_table(res[1], 'qpr', torch.float32, ((L.NQP, 1), (L.NQP, N)), xq.device)
+            if res[2] not in _CODE_FORMATS:
+                raise L.CnnqError("%s: r_format must be 'u8' or 'pack4', got %r" % (what, res[2]))
+            rq = _lc_table(res[0], 'residual', torch.uint8, ((N, OH, OW, Cout // 2 if res[2] == 'pack4' else Cout),), xq.device)
     elif out is None:
         y = torch.empty((N, OH, OW, Cout), dtype=torch.float32, device=xq.device)
     else:       # the caller's [N, Cout, OH, OW] channels_last tensor: its storage is [N, OH, OW, Cout]
@@ -3004,9 +3010,13 @@ def _conv_codes(what, xq, wq, qpx, qpw, bias, stride, padding, x_format, w_forma
     if q is None:
         L.check(lib.cnnq_conv_codes(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), g, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias), _ptr(taps), splits,
                                     _ptr(ws), nbytes, st), 'cnnq_conv_codes')
-    else:
+    elif res is None:
         L.check(lib.cnnq_conv_codes_q(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), _CODE_FORMATS[q[2]], g, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias),
                                       _ptr(qpy), qpy.shape[1], int(bool(q[1])), _ptr(taps), splits, _ptr(ws), nbytes, st), 'cnnq_conv_codes_q')
+    else:
+        L.check(lib.cnnq_conv_codes_q_add(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), _CODE_FORMATS[q[2]], g, _ptr(qpx), qpx.shape[1], _ptr(qpw),
+                                          _ptr(bias), _ptr(qpy), qpy.shape[1], int(bool(q[1])), _ptr(rq), _CODE_FORMATS[res[2]], _ptr(qpr),
+                                          qpr.shape[1], _ptr(taps), splits, _ptr(ws), nbytes, st), 'cnnq_conv_codes_q_add')
     return y
 
 
@@ -3023,11 +3033,20 @@ def conv_codes(xq, wq, qpx, qpw, bias=None, stride=1, padding=0, x_format='u8', 
 
 
 def conv_codes_q(xq, wq, qpx, qpw, qpy, bias=None, relu=False, stride=1, padding=0, x_format='u8', w_format='u8', y_format='u8', taps=None,
-                 out=None, splits=0):
+                 out=None, splits=0, residual=None, qpr=None, r_format='u8'):
     """conv_codes writing CODES (cnnq_conv_codes_q): the same float32 value, then ReLU if `relu`, then the stored
     format's quantizer with the output table qpy [NQP, 1] (per tensor) or [NQP, N] (per image), in the same launch - the bytes of
     conv_codes -> torch.relu_ -> quantize_packed_nhwc at a uniform 8 / 4 bits.  Returns NHWC codes, uint8 [N, OH, OW, Cout] ('u8',
     Cout % 4 == 0) or [N, OH, OW, Cout / 2] ('pack4', Cout % 8 == 0, the even channel in the low nibble): the xq of the next
     conv_codes* call as it is (and, seen as [N OH OW, Cout], of linear_codes*).  out: such a tensor of the caller's.  Everything else
-    as in conv_codes."""
-    return _conv_codes('conv_codes_q', xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, taps, out, splits, (qpy, relu, y_format))
+    as in conv_codes.
+
+    residual (cnnq_conv_codes_q_add): NHWC codes of the output's shape in `r_format` - independent of y_format -
+    with the table qpr [NQP, 1] or [NQP, N]; (code - zr) * sr is added to the float32 value before ReLU and the quantizer, in the same
+    launch: the close of a residual block, the bytes of conv_codes -> + dequantize_packed_nhwc(residual) -> relu_ ->
+    quantize_packed_nhwc.  out may be the residual tensor itself when the formats agree (the block updated in place).  None: the call
+    without it, byte for byte."""
+    if (residual is None) != (qpr is None):
+        raise L.CnnqError('conv_codes_q: residual and qpr are given together')
+    return _conv_codes('conv_codes_q', xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, taps, out, splits, (qpy, relu, y_format),
+                       None if residual is None else (residual, qpr, r_format))

@@ -1355,6 +1355,33 @@ int cnnq_conv_codes_q(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w
                       int64_t Cx, const float* qpw, const float* bias, const float* qpy, int64_t Cy, int relu, const int32_t* taps, int splits,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* The code-writing convolution WITH A RESIDUAL: relu(conv(x) + shortcut), the close of a ResNet block, in the
+ * launches of cnnq_conv_codes_q.  rq: NHWC codes of the output's shape in fmt_r - uint8 [N][OH][OW][Cout] (u8, Cout % 4 == 0) or
+ * [N][OH][OW][Cout / 2] (pack4, the even channel in the low nibble, Cout % 8 == 0), rows back to back, 4-byte aligned: what
+ * cnnq_conv_codes_q and cnnq_pc_quantize_packed_nhwc at a uniform 8 / 4 bits write.  fmt_r is independent of fmt_y.  qpr
+ * [CNNQ_NQP][Cr], Cr = 1 (per tensor) or N (per image); its qmax row is not read.  Per element: y32 = what cnnq_conv_codes stores;
+ * r32 = (float(code) - zr) * sr, the subtraction and the product each rounded to fp32 (the decode of
+ * cnnq_pc_dequantize_packed_nhwc); s32 = y32 + r32, one more rounding, never fused; then ReLU and the code of cnnq_conv_codes_q
+ * from s32.  The bytes are those of cnnq_conv_codes, + the dequantized residual, relu, cnnq_pc_quantize_packed_nhwc one after the
+ * other, for every tile, split count and held taps.
+ *
+ * Aliasing.  rq == y with fmt_r == fmt_y is allowed: a block updated in place (every dword of the residual is read before its owner
+ * writes it, in the tile and in the epilogue of splits > 1).  rq == y with different formats is CNNQ_EINVAL; any other overlap of
+ * the two is the caller's error.
+ *
+ * cnnq_conv_codes_q_add_workspace: what cnnq_conv_codes_q_workspace returns (0 also for a refused fmt_r / Cout).
+ * cnnq_conv_codes_q_add_route: cnnq_conv_codes_q_route's seven words and one more: 1 - 16-byte loads of the residual (its rows whole
+ *   16-byte pieces on a 16-byte base) / 0 - dword loads.
+ * CNNQ_EINVAL before anything touches the device for what cnnq_conv_codes_q refuses so, fmt_r outside cnnq_code_format, Cout not a
+ * multiple of 4 (u8) / 8 (pack4) of the residual's format, Cr not 1 or N, a NULL or misaligned rq / qpr; CNNQ_ERANGE as there.
+ * Re-entrant, allocates nothing, no atomics, no host synchronisation, graph-capturable. */
+size_t cnnq_conv_codes_q_add_workspace(const int64_t g[11], int fmt_x, int fmt_w, int fmt_y, int fmt_r, int have_taps, int splits);
+int cnnq_conv_codes_q_add_route(const int64_t g[11], int fmt_x, int fmt_w, int fmt_y, int fmt_r, int splits, int align_bytes, int32_t out[8]);
+int cnnq_conv_codes_q_add(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, uint8_t* y, int fmt_y, const int64_t g[11],
+                          const float* qpx, int64_t Cx, const float* qpw, const float* bias, const float* qpy, int64_t Cy, int relu,
+                          const uint8_t* rq, int fmt_r, const float* qpr, int64_t Cr, const int32_t* taps, int splits, void* ws,
+                          size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,14 @@ status 1 if that comparison fails.
 The two legs' bytes are compared (they are equal) before anything is timed, and not_faster lists the layers whose `q` median is not
 below the `chain` median; the rule of two runs is the same.
 
-    tools/bench_conv_codes.py [--batches 64,1] [--steps 20] [--warmup 5] [--requant]"""
+--residual times the layer that closes a residual block on ResNet-50's four block-closing 1 x 1 layers, with
+ReLU, the tables and taps held, two legs again:
+    qadd     ops.conv_codes_q(..., residual=): codes and shortcut codes in, codes out, one call;
+    five     the same bytes without it: ops.conv_codes, ops.dequantize_packed_nhwc of the shortcut, add_, relu_,
+             ops.quantize_packed_nhwc, every buffer held.
+The bytes are compared before anything is timed; not_faster and the rule of two runs as above.
+
+    tools/bench_conv_codes.py [--batches 64,1] [--steps 20] [--warmup 5] [--requant | --residual]"""
 import argparse
 import json
 import os
@@ -38,6 +45,9 @@ LAYERS = (
     ('c5_1x1_1024_512', 14, 1024, 512, 1, 1), ('c5_1x1_512_2048', 7, 512, 2048, 1, 1), ('c5_1x1_2048_512', 7, 2048, 512, 1, 1),
     ('c3_down_1x1s2', 56, 256, 512, 1, 2), ('c4_down_1x1s2', 28, 512, 1024, 1, 2), ('c5_down_1x1s2', 14, 1024, 2048, 1, 2),
 )
+# ... and the 1 x 1 layers that close a block: relu(conv(x) + shortcut)
+CLOSING = (('c2_1x1_64_256', 56, 64, 256, 1, 1), ('c3_1x1_128_512', 28, 128, 512, 1, 1), ('c4_1x1_256_1024', 14, 256, 1024, 1, 1),
+           ('c5_1x1_512_2048', 7, 512, 2048, 1, 1))
 
 
 def make(fmt, N, H, Cin, Cout, k, stride, dev, gen):
@@ -68,11 +78,17 @@ def run_leg(ops, leg, L):
     if leg == 'int':
         return ops.conv_codes(L['xq'], L['wq'], L['qpx'], L['qpw'], bias=L['bias'], stride=L['stride'], padding=L['pad'], x_format=L['fmt'],
                               w_format=L['fmt'], taps=L['taps'], out=L['y'])
-    if leg in ('q', 'chain'):
+    if leg in ('q', 'chain', 'qadd', 'five'):
         kw = dict(bias=L['bias'], stride=L['stride'], padding=L['pad'], x_format=L['fmt'], w_format=L['fmt'], taps=L['taps'])
         if leg == 'q':
             return ops.conv_codes_q(L['xq'], L['wq'], L['qpx'], L['qpw'], L['qpy'], relu=True, y_format=L['fmt'], out=L['yq'], **kw)
-        y = torch.relu_(ops.conv_codes(L['xq'], L['wq'], L['qpx'], L['qpw'], out=L['y'], **kw))
+        if leg == 'qadd':
+            return ops.conv_codes_q(L['xq'], L['wq'], L['qpx'], L['qpw'], L['qpy'], relu=True, y_format=L['fmt'], out=L['yq'], residual=L['rq'],
+                                    qpr=L['qpr'], r_format=L['fmt'], **kw)
+        y = ops.conv_codes(L['xq'], L['wq'], L['qpx'], L['qpw'], out=L['y'], **kw)
+        if leg == 'five':
+            y.add_(ops.dequantize_packed_nhwc(L['rq'].view(-1), y.shape, torch.float32, L['qprc'], L['coloff'], out=L['r32']))
+        y = torch.relu_(y)
         return ops.quantize_packed_nhwc(y, L['qpc'], L['bits'], out=L['packed'], coloff=L['coloff'])[0]
     x, w = dequantize(ops, L)
     return torch.nn.functional.conv2d(x, w, L['bias'], stride=L['stride'], padding=L['pad'])
@@ -84,8 +100,9 @@ def main():
     p.add_argument('--steps', type=int, default=20)
     p.add_argument('--warmup', type=int, default=5)
     p.add_argument('--requant', action='store_true')
+    p.add_argument('--residual', action='store_true')
     a = p.parse_args()
-    LEGS = ('q', 'chain') if a.requant else ('int', 'former')
+    LEGS = ('qadd', 'five') if a.residual else ('q', 'chain') if a.requant else ('int', 'former')
     if not torch.cuda.is_available():
         sys.exit('bench_conv_codes.py needs a GPU')
     from cnn_quantization_amd import ops
@@ -93,19 +110,23 @@ def main():
     gen = torch.Generator().manual_seed(1234)
     res, ok = {}, True
     for N in (int(b) for b in a.batches.split(',')):
-        for name, H, Cin, Cout, k, stride in LAYERS:
+        for name, H, Cin, Cout, k, stride in (CLOSING if a.residual else LAYERS):
             for fmt in ('u8', 'pack4'):
                 L = make(fmt, N, H, Cin, Cout, k, stride, dev, gen)
                 L['taps'], L['y'] = ops.conv_codes_tapsums(L['wq'], fmt), None
-                if a.requant:       # the output table: zero at a non-integer code, the largest output at 1.25 times the top code
+                if a.requant or a.residual:       # the output table: zero at a non-integer code, the largest output at 1.25 times the top code
                     y, top = run_leg(ops, 'int', L), float(L['qpx'][2, 0])
                     L['y'], L['bits'] = y, 8 if fmt == 'u8' else 4
                     L['qpy'] = torch.tensor([[float(y.max()) / top * 0.8], [0.37], [top]], device=dev)
                     L['qpc'], L['coloff'] = L['qpy'].expand(3, Cout).contiguous(), ops.packed_layout_nhwc(L['bits'], Cout)
                     L['yq'] = torch.empty((N, y.shape[2], y.shape[3], Cout // (1 if fmt == 'u8' else 2)), dtype=torch.uint8, device=dev)
                     L['packed'] = torch.empty(L['yq'].numel(), dtype=torch.uint8, device=dev)
-                    ref = run_leg(ops, 'chain', L).clone()
-                    same = bool(torch.equal(run_leg(ops, 'q', L).flatten(), ref))
+                    if a.residual:  # shortcut codes over the whole range, zero at a non-integer code near its middle, the conv's spread
+                        L['rq'] = torch.randint(0, 256, L['yq'].shape, generator=gen, dtype=torch.uint8).to(dev)
+                        L['qpr'] = torch.tensor([[2 * float(y.std()) / top], [0.37 + top / 3], [top]], device=dev)
+                        L['qprc'], L['r32'] = L['qpr'].expand(3, Cout).contiguous(), torch.empty_like(y)
+                    ref = run_leg(ops, LEGS[1], L).clone()
+                    same = bool(torch.equal(run_leg(ops, LEGS[0], L).flatten(), ref))
                 else:
                     ref = run_leg(ops, 'former', L)
                     L['y'] = torch.empty_like(ref, memory_format=torch.channels_last)
