@@ -226,6 +226,10 @@ SIGNATURES = {
     'cnnq_conv_codes_q_add_route': (_I, [ctypes.POINTER(_L), _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
     'cnnq_conv_codes_q_add': (_I, [_P, _I, _P, _I, _P, _I, ctypes.POINTER(_L), _P, _L, _P, _P, _P, _L, _I, _P, _I, _P, _L, _P, _I, _P,
                                    ctypes.c_size_t, _P]),
+    'cnnq_max_pool_codes_route': (_I, [ctypes.POINTER(_L), _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_max_pool_codes': (_I, [_P, _I, _P, ctypes.POINTER(_L), _P]),
+    'cnnq_avg_pool_codes': (_I, [_P, _I, _P, ctypes.POINTER(_L), _P, _L, _P]),
+    'cnnq_avg_pool_codes_q': (_I, [_P, _I, _P, _I, ctypes.POINTER(_L), _P, _L, _P, _L, _P]),
 }
 
 _lib = None

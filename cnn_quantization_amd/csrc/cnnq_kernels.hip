@@ -72,6 +72,7 @@
 #include "cnnq_flat.hip.h"
 #include "cnnq_linear_codes.hip.h"
 #include "cnnq_conv_codes.hip.h"
+#include "cnnq_pool_codes.hip.h"
 
 namespace {
 
@@ -3422,6 +3423,115 @@ int cnnq_conv_codes_q_add(const uint8_t* xq, int fmt_x, const uint8_t* wq, int f
     if (rq == y && fmt_r != fmt_y) return CNNQ_EINVAL;       // in place only where a thread's dword of y is the dword it read
     return cc_run(xq, fmt_x, wq, fmt_w, nullptr, rq_out(y, fmt_y, s.Cout, qpy, Cy, relu), rq_res(rq, fmt_r, s.Cout, qpr, Cr), s, qpx, Cx, qpw, bias,
                   taps, splits, ws, ws_bytes, stream);
+}
+
+// ---- pooling on the stored codes (cnnq_pool_codes.hip.h) ---------------------------------------------------------
+// g = {N, H, W, C, KH, KW, sh, sw, ph, pw} checked: the output's size and the dwords of a pixel's channels
+struct MpShape {
+    int64_t N, H, W, C, KH, KW, sh, sw, ph, pw, OH, OW, Cdw;
+};
+static int pc_pixels_check(int64_t N, int64_t H, int64_t W) {
+    // N H W without overflow: every factor is below 2^31
+    return N * H >= ((int64_t)1 << 31) || N * H * W >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
+}
+static int mp_check(const int64_t* g, int fmt, MpShape& s, MpPlan& p, bool wide) {
+    if (!g || !lc_fmt_ok(fmt)) return CNNQ_EINVAL;
+    for (int i = 0; i < 10; ++i)
+        if (g[i] < (i < 8 ? 1 : 0)) return CNNQ_EINVAL;
+    for (int i = 0; i < 10; ++i)
+        if (g[i] >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    s.N = g[0], s.H = g[1], s.W = g[2], s.C = g[3], s.KH = g[4], s.KW = g[5], s.sh = g[6], s.sw = g[7], s.ph = g[8], s.pw = g[9];
+    if (2 * s.ph > s.KH || 2 * s.pw > s.KW) return CNNQ_EINVAL;                     // every window holds a real element
+    if (s.H + 2 * s.ph < s.KH || s.W + 2 * s.pw < s.KW) return CNNQ_EINVAL;         // no output pixel
+    if (s.C % (fmt == CNNQ_CODES_U8 ? 4 : 8)) return CNNQ_EINVAL;
+    s.OH = (s.H + 2 * s.ph - s.KH) / s.sh + 1;
+    s.OW = (s.W + 2 * s.pw - s.KW) / s.sw + 1;
+    s.Cdw = s.C / (fmt == CNNQ_CODES_U8 ? 4 : 8);
+    if (pc_pixels_check(s.N, s.H, s.W) || pc_pixels_check(s.N, s.OH, s.OW)) return CNNQ_ERANGE;
+    p = mp_plan(s.OH, s.OW, s.Cdw, s.KH, s.KW, s.sh, s.sw, wide && s.Cdw % 4 == 0);
+    // a window no tile of which fits the LDS, 2^31 workgroups
+    return !p.ok || s.N * p.tilesH * p.tilesW * p.slabs >= ((int64_t)1 << 31) ? CNNQ_ERANGE : 0;
+}
+
+// Which launch cnnq_max_pool_codes makes for this geometry (host only): out = {output rows of the tile, its columns, channel bytes
+// of the slab, 1 - 16-byte loads and stores / 0 - the dword path, OH, OW}
+int cnnq_max_pool_codes_route(const int64_t g[10], int fmt, int align_bytes, int32_t out[6]) {
+    if (!out || !pow2(align_bytes) || align_bytes < 4) return CNNQ_EINVAL;
+    MpShape s;
+    MpPlan p;
+    if (const int rc = mp_check(g, fmt, s, p, align_bytes % 16 == 0)) return rc;
+    out[0] = p.TOH;
+    out[1] = p.TOW;
+    out[2] = p.SD * 4;
+    out[3] = p.wide;
+    out[4] = (int32_t)s.OH;
+    out[5] = (int32_t)s.OW;
+    return 0;
+}
+
+int cnnq_max_pool_codes(const uint8_t* xq, int fmt, uint8_t* y, const int64_t g[10], void* stream) {
+    MpShape s;
+    MpPlan p;
+    if (const int rc = mp_check(g, fmt, s, p, al16(xq) && al16(y))) return rc;
+    if (!xq || !y || misaligned(xq, 4) || misaligned(y, 4)) return CNNQ_EINVAL;
+    const MpArgs a{reinterpret_cast<const unsigned*>(xq), reinterpret_cast<unsigned*>(y), (int)s.H, (int)s.W, (int)s.OH, (int)s.OW, (int)s.Cdw,
+                   (int)s.KH, (int)s.KW, (int)s.sh, (int)s.sw, (int)s.ph, (int)s.pw, p.TOH, p.TOW, p.SD, p.PWp, p.PHp,
+                   (int)p.tilesH, (int)p.tilesW, (int)p.slabs};
+    const dim3 grid((unsigned)(s.N * p.tilesH * p.tilesW * p.slabs));
+    with_bool(fmt == CNNQ_CODES_PACK4, p.wide != 0, [&](auto p4, auto w) {
+        hipLaunchKernelGGL((k_mp_codes<decltype(p4)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, decltype(w)::value ? 4 : 1>), grid, dim3(TPB), 0,
+                           hs(stream), a);
+    });
+    return launch_status();
+}
+
+// g = {N, H, W, C}.  CNNQ_ERANGE: H W of 2^23 and more (S stays in int32), an extent or N H W of 2^31 and more
+static int ap_check(const int64_t* g, int fmt_x, const void* xq, const float* qpx, int64_t Cx) {
+    if (!g || !lc_fmt_ok(fmt_x)) return CNNQ_EINVAL;
+    for (int i = 0; i < 4; ++i)
+        if (g[i] < 1) return CNNQ_EINVAL;
+    for (int i = 0; i < 4; ++i)
+        if (g[i] >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    if (g[3] % (fmt_x == CNNQ_CODES_U8 ? 4 : 8) || (Cx != 1 && Cx != g[0])) return CNNQ_EINVAL;
+    if (g[1] * g[2] >= ((int64_t)1 << 23) || pc_pixels_check(g[0], g[1], g[2])) return CNNQ_ERANGE;
+    return !xq || !qpx || misaligned(xq, 4) || misaligned(qpx, 4) ? CNNQ_EINVAL : 0;
+}
+// the body of cnnq_avg_pool_codes (q.y == NULL: fp32 into y) and cnnq_avg_pool_codes_q (codes into q.y); the output is checked
+static int ap_run(const uint8_t* xq, int fmt_x, float* y, const RqOut& q, const int64_t* g, const float* qpx, int64_t Cx, void* stream) {
+    const int64_t N = g[0], HW = g[1] * g[2], C = g[3], Cdw = C / (fmt_x == CNNQ_CODES_U8 ? 4 : 8);
+    const bool wide = Cdw % 4 == 0 && al16(xq);
+    const int64_t slabs = (Cdw + AP_SD - 1) / AP_SD;
+    if (N * slabs >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    ApArgs a;
+    a.xq = reinterpret_cast<const unsigned*>(xq);
+    a.y = y;
+    a.q = q;
+    a.qpx = qpx;
+    a.Cx = (int)Cx;
+    a.HW = (int)HW;
+    a.Cdw = (int)Cdw;
+    a.C = (int)C;
+    a.cols = (int)((Cdw < AP_SD ? Cdw : AP_SD) / (wide ? 4 : 1));
+    a.G = (int)(HW < TPB / a.cols ? HW : TPB / a.cols);
+    a.slabs = (int)slabs;
+    with_bool(fmt_x == CNNQ_CODES_PACK4, wide, q.y != nullptr, [&](auto p4, auto w, auto oq) {
+        hipLaunchKernelGGL((k_ap_codes<decltype(p4)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, decltype(w)::value ? 4 : 1, decltype(oq)::value>),
+                           dim3((unsigned)(N * slabs)), dim3(TPB), 0, hs(stream), a);
+    });
+    return launch_status();
+}
+
+int cnnq_avg_pool_codes(const uint8_t* xq, int fmt_x, float* y, const int64_t g[4], const float* qpx, int64_t Cx, void* stream) {
+    if (const int rc = ap_check(g, fmt_x, xq, qpx, Cx)) return rc;
+    if (!y || misaligned(y, 16)) return CNNQ_EINVAL;
+    return ap_run(xq, fmt_x, y, RqOut{}, g, qpx, Cx, stream);
+}
+
+int cnnq_avg_pool_codes_q(const uint8_t* xq, int fmt_x, uint8_t* y, int fmt_y, const int64_t g[4], const float* qpx, int64_t Cx, const float* qpy,
+                          int64_t Cy, void* stream) {
+    if (const int rc = ap_check(g, fmt_x, xq, qpx, Cx)) return rc;
+    if (const int rc = rq_check(fmt_y, g[3], y, qpy, Cy, g[0])) return rc;
+    return ap_run(xq, fmt_x, nullptr, rq_out(y, fmt_y, g[3], qpy, Cy, 0), g, qpx, Cx, stream);
 }
 
 }  // extern "C"

@@ -3050,3 +3050,55 @@ def conv_codes_q(xq, wq, qpx, qpw, qpy, bias=None, relu=False, stride=1, padding
         raise L.CnnqError('conv_codes_q: residual and qpr are given together')
     return _conv_codes('conv_codes_q', xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, taps, out, splits, (qpy, relu, y_format),
                        None if residual is None else (residual, qpr, r_format))
+
+
+# ------------------------------------------------------------------------------------- pooling on the codes
+def max_pool_codes(xq, kernel_size, stride=None, padding=0, x_format='u8', out=None):
+    """MaxPool2d on the stored codes (cnnq_max_pool_codes): NHWC codes xq [N, H, W, C] ('u8', C % 4 == 0) or
+    [N, H, W, C / 2] ('pack4', the even channel in the low nibble, C % 8 == 0) -> the maximum of every window's valid codes as codes
+    [N, OH, OW, C] (C / 2) in the same format.  No table is read: a decode (code - zp) * scale with scale > 0 does not decrease in the
+    code, so dequantizing the result with the INPUT's table gives max_pool2d of the dequantized input bit for bit.  kernel_size,
+    stride (None: the kernel), padding (at most half the kernel): an int or (h, w); dilation 1, no ceil mode.  out: such a tensor of
+    the caller's, not overlapping xq.  One launch on the stream of xq; no host synchronisation."""
+    lib = L.load()
+    xq, fx, C = _codes_nhwc(xq, x_format, 'xq')
+    kernel = _pair(kernel_size, 'kernel_size')
+    g = (ctypes.c_int64 * 10)(*xq.shape[:3], C, *kernel, *(kernel if stride is None else _pair(stride, 'stride')), *_pair(padding, 'padding'))
+    route = (ctypes.c_int32 * 6)()
+    L.check(lib.cnnq_max_pool_codes_route(g, fx, 4, route), 'cnnq_max_pool_codes_route')
+    y = _codes_out('max_pool_codes', out, (xq.shape[0], route[4], route[5]), x_format, C, xq.device)
+    L.check(lib.cnnq_max_pool_codes(_ptr(xq), fx, _ptr(y), g, _stream(xq)), 'cnnq_max_pool_codes')
+    return y
+
+
+def _avg_pool_codes(what, xq, qpx, x_format, out, q=None):
+    """avg_pool_codes (q None) and avg_pool_codes_q (q = (qpy, y_format)): one front, one call each."""
+    lib = L.load()
+    xq, fx, C = _codes_nhwc(xq, x_format, 'xq')
+    N = xq.shape[0]
+    g = (ctypes.c_int64 * 4)(*xq.shape[:3], C)
+    qpx = _lc_table(qpx, 'qpx', torch.float32, ((L.NQP, 1), (L.NQP, N)), xq.device)
+    if q is None:
+        y = torch.empty((N, C), dtype=torch.float32, device=xq.device) if out is None else _lc_table(out, 'out', torch.float32, ((N, C),), xq.device)
+        L.check(lib.cnnq_avg_pool_codes(_ptr(xq), fx, _ptr(y), g, _ptr(qpx), qpx.shape[1], _stream(xq)), 'cnnq_avg_pool_codes')
+    else:
+        qpy = _lc_table(q[0], 'qpy', torch.float32, ((L.NQP, 1), (L.NQP, N)), xq.device)
+        y = _codes_out(what, out, (N,), q[1], C, xq.device)
+        L.check(lib.cnnq_avg_pool_codes_q(_ptr(xq), fx, _ptr(y), _CODE_FORMATS[q[1]], g, _ptr(qpx), qpx.shape[1], _ptr(qpy), qpy.shape[1],
+                                          _stream(xq)), 'cnnq_avg_pool_codes_q')
+    return y
+
+
+def avg_pool_codes(xq, qpx, x_format='u8', out=None):
+    """AdaptiveAvgPool2d((1, 1)) on the stored codes (cnnq_avg_pool_codes): NHWC codes xq [N, H, W, C] ('u8') or
+    [N, H, W, C / 2] ('pack4') with the table qpx [NQP, 1] (per tensor) or [NQP, N] (per image) -> float32 [N, C], the mean of the
+    decoded codes: S = the exact integer sum of the channel's H W codes, (float)((S / (H W) - zx) * sx) with the three operations in
+    fp64 and ONE rounding to fp32.  out: such a tensor of the caller's.  One launch on the stream of xq; no host synchronisation."""
+    return _avg_pool_codes('avg_pool_codes', xq, qpx, x_format, out)
+
+
+def avg_pool_codes_q(xq, qpx, qpy, x_format='u8', y_format='u8', out=None):
+    """avg_pool_codes writing CODES (cnnq_avg_pool_codes_q): the same float32 value, then the stored format's quantizer with the output
+    table qpy [NQP, 1] or [NQP, N] (per image = per sample of the classifier), in the same launch.  Returns uint8 [N, C] ('u8', C % 4
+    == 0) or [N, C / 2] ('pack4', C % 8 == 0): the xq of linear_codes* as it is."""
+    return _avg_pool_codes('avg_pool_codes_q', xq, qpx, x_format, out, (qpy, y_format))

@@ -1382,6 +1382,39 @@ int cnnq_conv_codes_q_add(const uint8_t* xq, int fmt_x, const uint8_t* wq, int f
                           const uint8_t* rq, int fmt_r, const float* qpr, int64_t Cr, const int32_t* taps, int splits, void* ws,
                           size_t ws_bytes, void* stream);
 
+/* POOLING ON THE STORED CODES: the two layers between the integer convolutions and the classifier, on NHWC
+ * codes as cnnq_conv_codes reads and cnnq_conv_codes_q writes them - uint8 [N][H][W][C] (CNNQ_CODES_U8, C % 4 == 0) or
+ * [N][H][W][C / 2] (CNNQ_CODES_PACK4, the even channel in the low nibble, C % 8 == 0), pixels back to back, 4-byte aligned.  A
+ * pixel's channel bytes in whole 16-byte pieces on 16-byte aligned bases take 16-byte loads and stores, everything else dwords.
+ *
+ * cnnq_max_pool_codes: MaxPool2d on the codes.  g = {N, H, W, C, KH, KW, sh, sw, ph, pw}: kernel and stride >= 1, padding >= 0 and
+ *   at most half the kernel per axis (every window holds a real element), dilation 1, no ceil mode; OH = (H + 2 ph - KH) / sh + 1,
+ *   OW likewise.  y: codes [N][OH][OW][C] (C / 2) in the SAME format; it does not overlap xq.  Output code = the maximum of the
+ *   window's valid codes; no table is read: (code - zp) * scale with scale > 0 does not decrease in the code, so for every such table
+ *   the decoded output is max_pool2d of the decoded input bit for bit, and the output keeps the input's table.  One launch: a
+ *   workgroup loads the input patch of its tile of output pixels x slab of channels into LDS once and takes the maximum along the
+ *   row, then down the column, on packed 16-bit lanes.
+ * cnnq_max_pool_codes_route (host only, nothing enqueued): out = {output rows of a workgroup's tile, its columns, channel bytes of
+ *   its slab, 1 - 16-byte loads and stores / 0 - dwords, OH, OW}; align_bytes: a power of two (>= 4) that divides both pointers.
+ * cnnq_avg_pool_codes: AdaptiveAvgPool2d((1, 1)).  g = {N, H, W, C}; qpx[CNNQ_NQP][Cx], Cx = 1 (per tensor) or N (per image), its
+ *   qmax row is not read.  y fp32 [N][C], 16-byte aligned: S = the exact integer sum of the channel's H W codes,
+ *   y = (float)(((double)S / (H W) - (double)zx) * (double)sx) - fp64 operations in that order, each rounded on its own, then ONE
+ *   rounding to fp32.  One launch, no workspace.
+ * cnnq_avg_pool_codes_q: the same value, then the quantizer of cnnq_linear_codes_q / cnnq_conv_codes_q (no ReLU) with qpy
+ *   [CNNQ_NQP][Cy], Cy = 1 or N: y uint8 [N][C] (fmt_y u8, C % 4 == 0) or [N][C / 2] (pack4, C % 8 == 0), 4-byte aligned - the xq
+ *   of cnnq_linear_codes* as it is.  The bytes are those of cnnq_avg_pool_codes followed by the stored format's quantizer.
+ * All return CNNQ_EINVAL before anything touches the device for a format outside cnnq_code_format, a size, kernel or stride below 1,
+ * a negative padding or one above half the kernel, a kernel larger than the padded image (no output pixel), C not a multiple of 4
+ * (u8) / 8 (pack4) of every format involved, Cx / Cy not 1 or N, a NULL or misaligned pointer; CNNQ_ERANGE for an extent, N H W or
+ * N OH OW of 2^31 and more, H W >= 2^23 for the average (S must fit int32), and a pooling window so large that the patch of one
+ * output pixel of one channel dword exceeds the workgroup's 40 KB of LDS (about 10^4 taps).  Re-entrant, allocate nothing, no
+ * atomics, no host synchronisation, graph-capturable. */
+int cnnq_max_pool_codes_route(const int64_t g[10], int fmt, int align_bytes, int32_t out[6]);
+int cnnq_max_pool_codes(const uint8_t* xq, int fmt, uint8_t* y, const int64_t g[10], void* stream);
+int cnnq_avg_pool_codes(const uint8_t* xq, int fmt_x, float* y, const int64_t g[4], const float* qpx, int64_t Cx, void* stream);
+int cnnq_avg_pool_codes_q(const uint8_t* xq, int fmt_x, uint8_t* y, int fmt_y, const int64_t g[4], const float* qpx, int64_t Cx,
+                          const float* qpy, int64_t Cy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
