@@ -230,6 +230,9 @@ SIGNATURES = {
     'cnnq_max_pool_codes': (_I, [_P, _I, _P, ctypes.POINTER(_L), _P]),
     'cnnq_avg_pool_codes': (_I, [_P, _I, _P, ctypes.POINTER(_L), _P, _L, _P]),
     'cnnq_avg_pool_codes_q': (_I, [_P, _I, _P, _I, ctypes.POINTER(_L), _P, _L, _P, _L, _P]),
+    'cnnq_dwconv_codes_route': (_I, [ctypes.POINTER(_L), _I, _I, _I, ctypes.POINTER(ctypes.c_int32)]),
+    'cnnq_dwconv_codes': (_I, [_P, _I, _P, _I, _P, ctypes.POINTER(_L), _P, _L, _P, _P, _P]),
+    'cnnq_dwconv_codes_q': (_I, [_P, _I, _P, _I, _P, _I, ctypes.POINTER(_L), _P, _L, _P, _P, _P, _L, _I, _P]),
 }
 
 _lib = None

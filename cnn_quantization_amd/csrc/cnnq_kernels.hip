@@ -73,6 +73,7 @@
 #include "cnnq_linear_codes.hip.h"
 #include "cnnq_conv_codes.hip.h"
 #include "cnnq_pool_codes.hip.h"
+#include "cnnq_dwconv_codes.hip.h"
 
 namespace {
 
@@ -3532,6 +3533,98 @@ int cnnq_avg_pool_codes_q(const uint8_t* xq, int fmt_x, uint8_t* y, int fmt_y, c
     if (const int rc = ap_check(g, fmt_x, xq, qpx, Cx)) return rc;
     if (const int rc = rq_check(fmt_y, g[3], y, qpy, Cy, g[0])) return rc;
     return ap_run(xq, fmt_x, nullptr, rq_out(y, fmt_y, g[3], qpy, Cy, 0), g, qpx, Cx, stream);
+}
+
+// ---- the depthwise convolution on the stored codes (cnnq_dwconv_codes.hip.h) ----------------------------------------
+// g = {N, H, W, C, KH, KW, sh, sw, ph, pw} checked: the output's size, the LDS dwords of a pixel, the tile.  fmt_y: the output's
+// code format, or -1 for fp32.  CNNQ_ERANGE: more than 64 taps, an extent or N OH OW C of 2^31 and more, a window no tile of which
+// fits the LDS
+struct DwShape {
+    int64_t N, H, W, C, KH, KW, sh, sw, ph, pw, OH, OW, Cdw;
+    bool wide;
+};
+static int dw_check(const int64_t* g, int fmt_x, int fmt_w, int fmt_y, bool aligned16, DwShape& s, DwPlan& p) {
+    if (!g || !lc_fmt_ok(fmt_x) || !lc_fmt_ok(fmt_w) || (fmt_y != -1 && !lc_fmt_ok(fmt_y))) return CNNQ_EINVAL;
+    for (int i = 0; i < 10; ++i)
+        if (g[i] < (i < 8 ? 1 : 0)) return CNNQ_EINVAL;
+    for (int i = 0; i < 10; ++i)
+        if (g[i] >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    s.N = g[0], s.H = g[1], s.W = g[2], s.C = g[3], s.KH = g[4], s.KW = g[5], s.sh = g[6], s.sw = g[7], s.ph = g[8], s.pw = g[9];
+    if (s.H + 2 * s.ph < s.KH || s.W + 2 * s.pw < s.KW) return CNNQ_EINVAL;         // no output pixel
+    if (s.H + 2 * s.ph >= ((int64_t)1 << 31) || s.W + 2 * s.pw >= ((int64_t)1 << 31) || s.KH * s.KW > CC_MAX_TAPS) return CNNQ_ERANGE;
+    const bool p4 = fmt_x == CNNQ_CODES_PACK4 || fmt_w == CNNQ_CODES_PACK4 || fmt_y == CNNQ_CODES_PACK4;
+    if (s.C % (p4 ? 8 : 4)) return CNNQ_EINVAL;
+    s.OH = (s.H + 2 * s.ph - s.KH) / s.sh + 1;
+    s.OW = (s.W + 2 * s.pw - s.KW) / s.sw + 1;
+    s.Cdw = s.C / 4;
+    if (pc_pixels_check(s.N, s.H, s.W) || pc_pixels_check(s.N, s.OH, s.OW) || s.N * s.OH * s.OW * s.C >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    p = dw_plan(s.N, s.OH, s.OW, s.Cdw, s.KH, s.KW, s.sh, s.sw);
+    if (!p.ok || s.N * p.tilesH * p.tilesW * p.slabs >= ((int64_t)1 << 31)) return CNNQ_ERANGE;
+    // 16-byte loads: the pixel's and the slab's bytes of xq in whole 16-byte pieces on a 16-byte base
+    const int64_t xg = fmt_x == CNNQ_CODES_U8 ? 4 : 8;                              // LDS dwords of 16 bytes of xq
+    s.wide = aligned16 && s.Cdw % xg == 0 && p.SD % xg == 0;
+    return 0;
+}
+
+// Which launch cnnq_dwconv_codes* makes for this geometry (host only): out = {output rows of the tile, its columns, the slab's bytes
+// of xq, 1 - 16-byte loads / 0 - the dword path, OH, OW}
+int cnnq_dwconv_codes_route(const int64_t g[10], int fmt_x, int fmt_w, int align_bytes, int32_t out[6]) {
+    if (!out || !pow2(align_bytes) || align_bytes < 4) return CNNQ_EINVAL;
+    DwShape s;
+    DwPlan p;
+    if (const int rc = dw_check(g, fmt_x, fmt_w, -1, align_bytes % 16 == 0, s, p)) return rc;
+    out[0] = p.TOH;
+    out[1] = p.TOW;
+    out[2] = p.SD * (fmt_x == CNNQ_CODES_U8 ? 4 : 2);
+    out[3] = s.wide;
+    out[4] = (int32_t)s.OH;
+    out[5] = (int32_t)s.OW;
+    return 0;
+}
+
+// the body of cnnq_dwconv_codes (q.y == NULL: fp32 into y) and cnnq_dwconv_codes_q (codes into q.y); the output is checked
+static int dw_run(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const RqOut& q, const DwShape& s, const DwPlan& p,
+                  const float* qpx, int64_t Cx, const float* qpw, const float* bias, void* stream) {
+    if (!xq || !wq || !qpx || !qpw || (Cx != 1 && Cx != s.N)) return CNNQ_EINVAL;
+    if (misaligned(xq, 4) || misaligned(wq, 4) || misaligned(qpx, 4) || misaligned(qpw, 4) || misaligned(bias, 4)) return CNNQ_EINVAL;
+    DwArgs a;
+    a.xq = reinterpret_cast<const unsigned*>(xq);
+    a.wq = reinterpret_cast<const unsigned*>(wq);
+    a.y = y;
+    a.q = q;
+    a.e = LcEpi{qpx, qpw, bias, nullptr, nullptr, (int)Cx, (int)s.C, 0, 0, 0};
+    a.g = CcGeo{(int)s.H, (int)s.W, (int)s.C, (int)s.OW, (int)(s.OH * s.OW), (int)s.KH, (int)s.KW, (int)s.sh, (int)s.sw, (int)s.ph, (int)s.pw};
+    a.OH = (int)s.OH;
+    a.Cdw = (int)s.Cdw;
+    a.TOH = p.TOH, a.TOW = p.TOW, a.SD = p.SD, a.RP = p.RP;
+    a.tilesH = (int)p.tilesH, a.tilesW = (int)p.tilesW, a.slabs = (int)p.slabs, a.wide = s.wide;
+    const dim3 grid((unsigned)(s.N * p.tilesH * p.tilesW * p.slabs));
+    with_bool(fmt_x == CNNQ_CODES_PACK4, fmt_w == CNNQ_CODES_PACK4, [&](auto px, auto pw) {
+        with_int<0, 1, 2>(q.y ? (q.fy == CNNQ_CODES_PACK4 ? 2 : 1) : 0, [&](auto out) {      // fp32, u8 codes, pack4 codes
+            constexpr int FX = decltype(px)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8, FW = decltype(pw)::value ? CNNQ_CODES_PACK4 : CNNQ_CODES_U8;
+            hipLaunchKernelGGL((k_dw_codes<FX, FW, decltype(out)::value>), grid, dim3(TPB), 0, hs(stream), a);
+        });
+    });
+    return launch_status();
+}
+
+int cnnq_dwconv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const int64_t g[10], const float* qpx, int64_t Cx,
+                      const float* qpw, const float* bias, void* stream) {
+    DwShape s;
+    DwPlan p;
+    if (const int rc = dw_check(g, fmt_x, fmt_w, -1, al16(xq), s, p)) return rc;
+    if (!y || misaligned(y, 16)) return CNNQ_EINVAL;
+    return dw_run(xq, fmt_x, wq, fmt_w, y, RqOut{}, s, p, qpx, Cx, qpw, bias, stream);
+}
+
+int cnnq_dwconv_codes_q(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, uint8_t* y, int fmt_y, const int64_t g[10], const float* qpx,
+                        int64_t Cx, const float* qpw, const float* bias, const float* qpy, int64_t Cy, int relu, void* stream) {
+    DwShape s;
+    DwPlan p;
+    if (!lc_fmt_ok(fmt_y)) return CNNQ_EINVAL;
+    if (const int rc = dw_check(g, fmt_x, fmt_w, fmt_y, al16(xq), s, p)) return rc;
+    if (const int rc = rq_check(fmt_y, s.C, y, qpy, Cy, s.N)) return rc;
+    return dw_run(xq, fmt_x, wq, fmt_w, nullptr, rq_out(y, fmt_y, s.C, qpy, Cy, relu), s, p, qpx, Cx, qpw, bias, stream);
 }
 
 }  // extern "C"

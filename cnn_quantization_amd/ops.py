@@ -3102,3 +3102,60 @@ def avg_pool_codes_q(xq, qpx, qpy, x_format='u8', y_format='u8', out=None):
     table qpy [NQP, 1] or [NQP, N] (per image = per sample of the classifier), in the same launch.  Returns uint8 [N, C] ('u8', C % 4
     == 0) or [N, C / 2] ('pack4', C % 8 == 0): the xq of linear_codes* as it is."""
     return _avg_pool_codes('avg_pool_codes_q', xq, qpx, x_format, out, (qpy, y_format))
+
+
+# ------------------------------------------------------------------------------------- the depthwise convolution on the codes
+def _dwconv_codes(what, xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, out, q=None):
+    """dwconv_codes (q None) and dwconv_codes_q (q = (qpy, relu, y_format)): one front, one call each; the NHWC result."""
+    lib = L.load()
+    xq, fx, C = _codes_nhwc(xq, x_format, 'xq')
+    if not (isinstance(wq, torch.Tensor) and wq.dim() == 3):
+        raise L.CnnqError('%s: wq must be tap-major weight codes [KH, KW, C], got %r' % (what, getattr(wq, 'shape', wq)))
+    wq, fw, Cw = _codes_nhwc(wq.unsqueeze(0), w_format, 'wq')
+    if Cw != C or wq.device != xq.device:
+        raise L.CnnqError('%s: xq has C = %d on %s, wq has C = %d on %s' % (what, C, xq.device, Cw, wq.device))
+    N = xq.shape[0]
+    g = (ctypes.c_int64 * 10)(*xq.shape[:3], C, *wq.shape[1:3], *_pair(stride, 'stride'), *_pair(padding, 'padding'))
+    route = (ctypes.c_int32 * 6)()
+    L.check(lib.cnnq_dwconv_codes_route(g, fx, fw, 4, route), 'cnnq_dwconv_codes_route')
+    OH, OW = route[4], route[5]
+    qpx = _lc_table(qpx, 'qpx', torch.float32, ((L.NQP, 1), (L.NQP, N)), xq.device)
+    qpw = _lc_table(qpw, 'qpw', torch.float32, ((L.NQP, C),), xq.device)
+    if bias is not None:
+        bias = _lc_table(bias, 'bias', torch.float32, ((C,),), xq.device)
+    st = _stream(xq)
+    if q is not None:
+        qpy = _lc_table(q[0], 'qpy', torch.float32, ((L.NQP, 1), (L.NQP, N)), xq.device)
+        y = _codes_out(what, out, (N, OH, OW), q[2], C, xq.device)
+        L.check(lib.cnnq_dwconv_codes_q(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), _CODE_FORMATS[q[2]], g, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias),
+                                        _ptr(qpy), qpy.shape[1], int(bool(q[1])), st), 'cnnq_dwconv_codes_q')
+        return y
+    if out is None:
+        y = torch.empty((N, OH, OW, C), dtype=torch.float32, device=xq.device)
+    else:       # the caller's [N, C, OH, OW] channels_last tensor: its storage is [N, OH, OW, C]
+        y = _lc_table(out.permute(0, 2, 3, 1) if isinstance(out, torch.Tensor) and out.dim() == 4 else out, 'out (seen as NHWC)',
+                      torch.float32, ((N, OH, OW, C),), xq.device)
+    L.check(lib.cnnq_dwconv_codes(_ptr(xq), fx, _ptr(wq), fw, _ptr(y), g, _ptr(qpx), qpx.shape[1], _ptr(qpw), _ptr(bias), st), 'cnnq_dwconv_codes')
+    return y
+
+
+def dwconv_codes(xq, wq, qpx, qpw, bias=None, stride=1, padding=0, x_format='u8', w_format='u8', out=None):
+    """The depthwise 2-D convolution on the stored codes (cnnq_dwconv_codes): NHWC activation codes xq
+    [N, H, W, C] ('u8', C % 4 == 0) or [N, H, W, C / 2] ('pack4', the even channel in the low nibble, C % 8 == 0) with the table qpx
+    [NQP, 1] (per tensor) or [NQP, N] (per image), TAP-MAJOR weight codes wq [KH, KW, C] (C / 2 for 'pack4') - the torch weight
+    [C, 1, KH, KW] permuted once per layer - with qpw [NQP, C] -> the zero-padded conv2d(groups=C) of the decoded operands + bias as
+    float32 [N, C, OH, OW] with channels_last strides: per channel the exact integer sums over each output pixel's valid taps on
+    v_dot4_u32_u8, combined in fp64 as conv_codes combines them and rounded once.  stride, padding: an int or (h, w); dilation and
+    the channel multiplier are 1, KH KW <= 64.  out: a float32 [N, C, OH, OW] channels_last tensor.  One launch on the stream of
+    xq, no workspace; no host synchronisation."""
+    return _dwconv_codes('dwconv_codes', xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, out).permute(0, 3, 1, 2)
+
+
+def dwconv_codes_q(xq, wq, qpx, qpw, qpy, bias=None, relu=False, stride=1, padding=0, x_format='u8', w_format='u8', y_format='u8', out=None):
+    """dwconv_codes writing CODES (cnnq_dwconv_codes_q): the same float32 value, then ReLU if `relu`, then the stored format's quantizer
+    with the output table qpy [NQP, 1] (per tensor) or [NQP, N] (per image), in the same launch - the bytes of dwconv_codes ->
+    torch.relu_ -> quantize_packed_nhwc at a uniform 8 / 4 bits.  Returns NHWC codes, uint8 [N, OH, OW, C] ('u8') or [N, OH, OW, C / 2]
+    ('pack4', C % 8 == 0): the xq of the next conv_codes* call as it is - with conv_codes_q's 1 x 1 layers and its residual=, a
+    MobileNetV2 block that never leaves codes (ReLU6 is the clamp of an output table whose range ends at 6).  out: such a tensor of
+    the caller's.  Everything else as in dwconv_codes."""
+    return _dwconv_codes('dwconv_codes_q', xq, wq, qpx, qpw, bias, stride, padding, x_format, w_format, out, (qpy, relu, y_format))

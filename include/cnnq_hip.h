@@ -1415,6 +1415,37 @@ int cnnq_avg_pool_codes(const uint8_t* xq, int fmt_x, float* y, const int64_t g[
 int cnnq_avg_pool_codes_q(const uint8_t* xq, int fmt_x, uint8_t* y, int fmt_y, const int64_t g[4], const float* qpx, int64_t Cx,
                           const float* qpy, int64_t Cy, void* stream);
 
+/* THE DEPTHWISE CONVOLUTION ON THE STORED CODES: the 3 x 3 of a MobileNetV2 block between two
+ * cnnq_conv_codes_q calls, channel multiplier 1, on v_dot4_u32_u8 - one launch, no workspace, no atomics.
+ *
+ * Operands.  xq: NHWC codes as cnnq_conv_codes takes them, uint8 [N][H][W][C] (CNNQ_CODES_U8) or [N][H][W][C / 2]
+ * (CNNQ_CODES_PACK4, the even channel in the low nibble), 4-byte aligned; qpx[CNNQ_NQP][Cx], Cx = 1 (per tensor) or N (per image).
+ * wq: TAP-MAJOR weight codes uint8 [KH][KW][C] ([C / 2] for pack4) - the torch weight [C][1][KH][KW] permuted once per layer, so that
+ * a dword of weights lines up with a dword of activations; qpw[CNNQ_NQP][C]; bias [C] or NULL.  C % 4 == 0, C % 8 == 0 with any
+ * pack4 operand or output.  g = {N, H, W, C, KH, KW, sh, sw, ph, pw}: kernel and stride >= 1, zero padding >= 0 per axis, dilation
+ * 1, KH KW <= 64; OH = (H + 2 ph - KH) / sh + 1, OW likewise.
+ *
+ * cnnq_dwconv_codes: y fp32 [N][OH][OW][C], 16-byte aligned.  A padded tap is the real value 0.0; with the sums over an output
+ *   pixel's valid taps, per channel, S = sum xq wq, Rx = sum xq, RwV = sum wq, Kv = their count:
+ *     y[m][c] = (float)(sx sw[c] (S - zw[c] Rx - zx RwV + Kv zx zw[c]) + bias[c])
+ *   - exact integers, combined in fp64 exactly as cnnq_conv_codes combines them, one rounding to fp32.
+ * cnnq_dwconv_codes_q: the same value, ReLU if `relu`, then the quantizer of cnnq_conv_codes_q with qpy[CNNQ_NQP][Cy], Cy = 1 or N:
+ *   y NHWC codes [N][OH][OW][C] (fmt_y u8) or [C / 2] (pack4), 4-byte aligned - the xq of the next cnnq_conv_codes* call as it is.
+ *   The bytes are those of cnnq_dwconv_codes, ReLU and the stored format's quantizer one after the other.
+ * cnnq_dwconv_codes_route (host only, nothing enqueued): out = {output rows of a workgroup's tile, its columns, the bytes of xq in a
+ *   pixel's slab of channels, 1 - 16-byte loads / 0 - dwords, OH, OW}; align_bytes: a power of two (>= 4) that divides xq.
+ * All return CNNQ_EINVAL before anything touches the device for a format outside cnnq_code_format, a size, kernel or stride below 1,
+ * a negative padding, a kernel larger than the padded image (no output pixel), C not a multiple of 4 (8 with any pack4 format), Cx /
+ * Cy not 1 or N, a NULL or misaligned pointer; CNNQ_ERANGE for KH KW > 64, an extent, N H W or N OH OW C of 2^31 and more, and a
+ * window so large that the patch of one output pixel of one channel dword exceeds the workgroup's 32 KB patch.  Re-entrant, allocate
+ * nothing, no host synchronisation, graph-capturable. */
+int cnnq_dwconv_codes_route(const int64_t g[10], int fmt_x, int fmt_w, int align_bytes, int32_t out[6]);
+int cnnq_dwconv_codes(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, float* y, const int64_t g[10], const float* qpx,
+                      int64_t Cx, const float* qpw, const float* bias, void* stream);
+int cnnq_dwconv_codes_q(const uint8_t* xq, int fmt_x, const uint8_t* wq, int fmt_w, uint8_t* y, int fmt_y, const int64_t g[10],
+                        const float* qpx, int64_t Cx, const float* qpw, const float* bias, const float* qpy, int64_t Cy, int relu,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
